@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Critic-VAE train-step images/sec on synthetic 64x64x3 frames (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--preset config2|config4|config5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--preset config2|config4|config5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -39,6 +39,9 @@ the C-ABI (critic-vae_amd FusedTrainer), inputs resident in HBM.  Rank 0 prints 
   traffic      — HBM bytes per launch of that kernel from the committed rocprofv3 PMC passes of the same workload
                  (profiles/traffic_per_launch.json, stamped with the sha256 of the kernel sources; null if stale);
   cpu_baseline — the oracle's training step timed on the host cores (bounded sample).
+
+Every timed loop on the GPU runs --warmup untimed and then --steps timed iterations.  --dump-outputs DIR writes what the
+headline's last timed step computed to DIR/<name>.npy (dump_outputs), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -73,6 +76,7 @@ HBM_PROBE_NAMES = {0: "e1_fwd", 8: "d4_fwd", 17: "d4_bwd", 18: "e1_wgrad", 27: "
 HBM_PROBE_IDS = sorted(HBM_PROBE_NAMES)
 BN_CH_H = [(32, 64), (64, 32), (128, 16), (256, 8)]
 TRAFFIC_JSON = os.path.join(ROOT, "profiles", "traffic_per_launch.json")
+DUMP_BUDGET_BYTES = 60 * 2 ** 20                 # --dump-outputs: array data in all (64 MB with room for the .npy headers)
 
 PRESETS = {   # BASELINE.json configs (configs[0] is the CPU case: cpu_baseline.batch32)
     "config1": dict(precision="f32", batch=256, width=64, label="BASELINE.json configs[1]: fp32"),
@@ -248,11 +252,45 @@ class Ctx:
             torch.distributed.barrier()
 
 
-def time_workload(cx, spec, steps, warmup, probing, allreduce_dtype=None, overlaps=(None,), fwd_bwd_rate=False, side_stream_wgrad=False):
+def dump_outputs(path, tr, vae, budget_bytes=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the timed path handed its caller after its last step, one float32 `<name>.npy` per array in
+    `path` — the loss scalars (cvae.h: [0] total, [1] MS-SSIM, [2] KLD, [3..12] level means), mu, logvar, recon, and the
+    parameters after Adam, their gradients and the BatchNorm running statistics under the reference's names and layouts
+    (so that builds with different flat layouts compare name for name).  If the arrays exceed `budget_bytes` in all, the
+    largest are cut to a common element count, each to a fixed-seed sample of its flattened elements (sorted indices; the
+    same for every run and build with the same arguments)."""
+    import numpy as np
+    from critic_vae_amd import layout as L
+
+    layout = vae.handle.layout
+    arrays = {"loss_scalars": tr.scalars[:13], "mu": tr.mu, "logvar": tr.logvar, "recon": tr.recon}
+    arrays.update({f"param.{k}": v for k, v in L.native_to_ref(layout, vae.theta.detach().cpu()).items()})
+    arrays.update({f"grad.{k}": v for k, v in L.native_to_ref(layout, tr.grads.cpu()).items()})
+    arrays.update({f"bn.{k}": v for k, v in L.bn_state_to_ref(vae.bn_state.cpu(), 0).items() if k.endswith(("_mean", "_var"))})
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    cap, left = None, budget_bytes // 4                     # water-filling: the smallest arrays whole, the rest cut to `cap`
+    sizes = sorted(a.size for a in arrays.values())
+    for i, n in enumerate(sizes):
+        if n * (len(sizes) - i) > left:
+            cap = left // (len(sizes) - i)
+            break
+        left -= n
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if cap is not None and a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": path, "arrays": len(arrays), "sampled_to_elements": cap}
+
+
+def time_workload(cx, spec, steps, warmup, probing, allreduce_dtype=None, overlaps=(None,), fwd_bwd_rate=False, side_stream_wgrad=False,
+                  dump_dir=None):
     """Build the model for `spec` (precision, batch, width), run `warmup` untimed + `steps` timed training steps
     bracketed by barrier + synchronize on both sides, max over ranks.  Returns (result dict, trainer, inputs).
     overlaps: all-reduce modes to time at N > 1 (None = the trainer's default); the first one is the result, the
-    others are returned under result["allreduce_modes"]."""
+    others are returned under result["allreduce_modes"].  dump_dir: rank 0 writes the outputs of the last timed step
+    of the first mode there (dump_outputs), after its timed region."""
     from critic_vae_amd import dp
     from critic_vae_amd.nets import VariationalAutoencoder
     from critic_vae_amd.train import FusedTrainer
@@ -355,6 +393,8 @@ def time_workload(cx, spec, steps, warmup, probing, allreduce_dtype=None, overla
         return r
 
     res = timed(overlaps[0])
+    if dump_dir is not None and rank == 0:
+        res["dump_outputs"] = dump_outputs(dump_dir, tr, vae)
     if len(overlaps) > 1:
         res["allreduce_modes"] = {("overlap" if o else "single"): {k: v for k, v in timed(o).items() if k in
                                   ("value", "ms_per_step", "grad_allreduce", "allreduce_exposed_us", "final_loss")} for o in overlaps[1:]}
@@ -372,7 +412,7 @@ def time_workload(cx, spec, steps, warmup, probing, allreduce_dtype=None, overla
                               "allreduce_bytes": int(tr.grads.numel() * (2 if tr.reduce_dtype == "bf16" else 4))}
     if fwd_bwd_rate:
         # SURVEY 8d also asks for the C-ABI path proper (forward + loss + backward, no all-reduce / optimizer):
-        # same rotating inputs as the timed region, 3 warm-up passes, at least as many passes as timed steps
+        # same rotating inputs, warm-up passes and timed passes as the timed region
         theta = vae.theta.data
 
         def fwd_loss_bwd(i):
@@ -381,8 +421,8 @@ def time_workload(cx, spec, steps, warmup, probing, allreduce_dtype=None, overla
             H.loss(B, x0, tr.mu, tr.logvar, tr.recon, tr.ws, tr.scalars, tr.d_recon, tr.d_mu, tr.d_logvar)
             H.backward(B, x0, p0, e0, theta, tr.logvar, tr.recon, tr.d_recon, tr.d_mu, tr.d_logvar, tr.ws, tr.grads)
 
-        n_fb = max(steps, 20)
-        for i in range(3):
+        n_fb = steps
+        for i in range(warmup):
             fwd_loss_bwd(i)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -398,8 +438,8 @@ def time_workload(cx, spec, steps, warmup, probing, allreduce_dtype=None, overla
 def dropin_rate(cx, B=256, steps=40, warmup=8):
     """critic_vae_amd.train.train (the reference loop: autograd Functions + torch.optim.Adam)
     over a host uint8 dataset through FrameFeeder (pinned double buffer, H2D on a side stream) with the HIP
-    pre-processing and the HIP critic in the loop.  One epoch of warmup+steps batches; the first `warmup`
-    batches are not timed."""
+    pre-processing and the HIP critic in the loop.  One epoch of max(warmup, 1) + 1 + steps batches; the last
+    `steps` batches are timed."""
     import numpy as np
     from critic_vae_amd import synth
     from critic_vae_amd import train as T
@@ -410,8 +450,9 @@ def dropin_rate(cx, B=256, steps=40, warmup=8):
     vae = VariationalAutoencoder(max_batch=B, seed=0).to(dev)
     critic = Critic(handle=vae.handle).to(dev)
     critic.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_critic_params(0).items()})
+    every = max(warmup, 1)             # batches between two log calls
     rng = np.random.default_rng(7)
-    frames = rng.integers(0, 256, size=((warmup + steps) * B, 64, 64, 3), dtype=np.uint8)
+    frames = rng.integers(0, 256, size=((every + 1 + steps) * B, 64, 64, 3), dtype=np.uint8)
     marks = []
 
     class _Clock:                      # train() logs every log_n images: use the log hook as the warm-up / end marker
@@ -420,20 +461,20 @@ def dropin_rate(cx, B=256, steps=40, warmup=8):
             marks.append(time.perf_counter())
 
     np.random.seed(0)
-    T.train(vae, frames, critic, dev, epochs=1, batch_size=B, log_n=warmup * B, log=_Clock())
+    T.train(vae, frames, critic, dev, epochs=1, batch_size=B, log_n=every * B, log=_Clock())
     torch.cuda.synchronize()
     t_end = time.perf_counter()
-    # log fires at batch_i = 0 (before warm-up) and batch_i = warmup*B (start of the timed part; the sync there drains
-    # the warm-up batches), then every warmup*B images: the timed part is from marks[1] to the end of the epoch
+    # log fires at batch_i = 0 (before warm-up) and batch_i = every*B (start of the timed part; the sync there drains
+    # the warm-up batches), then every every*B images: the timed part is from marks[1] to the end of the epoch
     t_start = marks[1]
-    n_timed = (steps - 1) * B          # batch `warmup` itself was enqueued and drained before marks[1] was taken
+    n_timed = steps * B                # batch `every` itself was enqueued and drained before marks[1] was taken
     del vae, critic
     torch.cuda.empty_cache()
     return {"value": round(n_timed / (t_end - t_start), 1), "unit": "images/s",
             "what": f"critic_vae_amd.train.train (reference loop vae.py:33-66: autograd + torch.optim.Adam on the flat parameter), "
-                    f"batch {B}, fp32, {steps - 1} timed batches after {warmup + 1}; frames start as uint8 HWC on the HOST: pinned "
+                    f"batch {B}, fp32, {steps} timed batches after {every + 1}; frames start as uint8 HWC on the HOST: pinned "
                     f"double-buffered gather, H2D on a side stream, cvae_preprocess_u8 + cvae_critic_forward on the GPU "
-                    f"(PCIe-inclusive; log hook synchronises every {warmup} batches)"}
+                    f"(PCIe-inclusive; log hook synchronises every {every} batches)"}
 
 
 def main():
@@ -453,7 +494,13 @@ def main():
     ap.add_argument("--no-probe", action="store_true")
     ap.add_argument("--no-fwd-bwd-rate", action="store_true", help="skip the extra forward+loss+backward-only loop (profiling runs)")
     ap.add_argument("--no-extra-configs", action="store_true", help="headline workload only (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step computed (loss scalars, mu, logvar, "
+                         "recon, updated parameters, gradients, BatchNorm statistics) to DIR/<name>.npy as float32, at most 64 MB "
+                         "in all (larger outputs: a fixed-seed sample); inputs are the same for every run with the same arguments")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     explicit = args.preset or args.batch is not None or args.width is not None or args.precision is not None
     if args.preset:
         clash = [k for k in ("batch", "width", "precision") if getattr(args, k) is not None and getattr(args, k) != PRESETS[args.preset][k]]
@@ -482,7 +529,7 @@ def main():
     probing = world == 1 and not args.no_probe
 
     h = time_workload(cx, head, args.steps, args.warmup, probing, args.allreduce_dtype,
-                      fwd_bwd_rate=not args.no_fwd_bwd_rate)
+                      fwd_bwd_rate=not args.no_fwd_bwd_rate, dump_dir=args.dump_outputs)
     res = {
         "metric": f"VAE train-step images/sec on {head['width']}x{head['width']}x3 frames",
         "value": h["value"], "unit": "images/s",
@@ -494,7 +541,7 @@ def main():
                    "grad_allreduce": h.get("grad_allreduce", "none"),
                    "final_loss": h["final_loss"], "loss_finite": h["loss_finite"]},
     }
-    for k in ("whole_step_algorithmic_TFLOPs", "whole_step_algorithmic_GBps", "fwd_loss_bwd_only_images_per_s_per_gpu"):
+    for k in ("whole_step_algorithmic_TFLOPs", "whole_step_algorithmic_GBps", "fwd_loss_bwd_only_images_per_s_per_gpu", "dump_outputs"):
         if k in h:
             res["config"][k] = h[k]
     for k in ("roofline", "roofline_hbm"):
@@ -539,12 +586,12 @@ def main():
                 detail[f"fp32_emulated_{prec}"] = full
                 keep = ("images_per_s", "ms_per_step", "steps", "final_loss", "roofline_kernel", "roofline_frac", "roofline_avg_launch_us")
                 cfgd.update({k: v for k, v in flat_summary(prec, full).items() if k[len(prec) + 1:] in keep})       # nested form: detail file only
-            dr = dropin_rate(cx)
+            dr = dropin_rate(cx, steps=args.steps, warmup=args.warmup)
             detail["dropin"] = dr
             cfgd["dropin_images_per_s"] = dr["value"]
             # the step the reference runs by default (vae_parameters.py:10, batch_size = 128): fp32, one number, no rooflines
             b128 = time_workload(cx, dict(PRESETS["config1"], batch=128, key="b128", label="the reference's default batch (vae_parameters.py:10): fp32"),
-                                 max(20, min(args.steps, 50)), min(args.warmup, 10), False)
+                                 args.steps, args.warmup, False)
             detail["b128"] = b128
             cfgd["b128_images_per_s"] = b128["value"]
         else:

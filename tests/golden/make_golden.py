@@ -11,9 +11,14 @@ file.  Fixtures hold data only (inputs are regenerated from the seeds stored ins
 import os
 import sys
 
-import numpy as np
-import torch
+# CPU round-off the same on every x86 host (tests/conftest.py sets the same mode, tests/test_oracle.py the same thread count): MKL's
+# COMPATIBLE branch, read by MKL on its first call, and 8 threads
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
 
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+torch.set_num_threads(8)
 sys.dont_write_bytecode = True
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))

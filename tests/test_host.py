@@ -105,6 +105,41 @@ def test_two_handles_do_not_share_state():
     assert a.lib.cvae_param_name(a.h, 0) == b"enc0.w" and "decin.b" in a.layout
 
 
+def test_bench_dump_outputs_float32_within_budget_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: every array of the timed path (loss scalars, mu, logvar, recon, each parameter and gradient,
+    BatchNorm statistics) as float32 .npy, the total inside the budget (a fixed-seed sample when it would not fit), and the
+    same files for the same state.  A child process: importing bench.py sets an environment default."""
+    code = """
+import os, sys
+import numpy as np
+sys.path.insert(0, %r)
+import bench
+from critic_vae_amd import synth
+from critic_vae_amd.nets import VariationalAutoencoder
+from critic_vae_amd.train import FusedTrainer
+vae = VariationalAutoencoder(max_batch=8, seed=0)
+tr = FusedTrainer(vae)
+for t in (tr.scalars, tr.mu, tr.logvar, tr.recon, tr.grads):
+    t.normal_()
+for budget, sampled in ((bench.DUMP_BUDGET_BYTES, False), (400000, True)):
+    a, b = (os.path.join(%r, f"{budget}_{i}") for i in (0, 1))
+    info = bench.dump_outputs(a, tr, vae, budget_bytes=budget)
+    bench.dump_outputs(b, tr, vae, budget_bytes=budget)
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b)) and len(names) == info["arrays"] == 4 + 2 * len(synth.make_params(0)) + 8, names
+    assert (info["sampled_to_elements"] is not None) == sampled
+    arrs = [np.load(os.path.join(a, n)) for n in names]
+    assert all(x.dtype == np.float32 for x in arrs) and sum(x.nbytes for x in arrs) <= budget
+    assert all(np.array_equal(x, np.load(os.path.join(b, n))) for x, n in zip(arrs, names))
+    if not sampled:
+        assert np.array_equal(np.load(os.path.join(a, "recon.npy")), tr.recon.numpy())
+print("ok")
+""" % (ROOT, str(tmp_path))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CVAE_")}
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_data_parallel_two_ranks_gloo():
     """N-rank all-reduced gradient == mean over ranks of the single-rank (oracle) gradient on that
     rank's shard, through the same flat native buffer the GPU path reduces."""
