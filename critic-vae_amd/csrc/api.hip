@@ -58,21 +58,13 @@ int cvae_num_cus() {
 }
 
 thread_local bool g_conv_dry = false;
+bool conv_per_tile_only() { static const bool on = [] { const char* e = getenv("CVAE_CONV_PER_TILE"); return e && e[0] == '1'; }(); return on; }
 // include/cvae.h: which kernel family a conv pass of E2..E4 takes at a batch size (host logic only, no device access)
 extern "C" int32_t cvae_conv_route(int32_t precision, int32_t width, int32_t layer, int32_t dgrad, int64_t batch) {
     if ((width != 64 && width != 128) || layer < 1 || layer > 3 || precision < 0 || precision > 3 || batch < 1 || batch > 0x7fffffffLL) return CVAE_EINVAL;
     if (precision == 0) return conv_f32_route(layer, width, dgrad != 0, (int)batch);
     if (precision == 1) return conv_bf16_route(layer, width, dgrad != 0, (int)batch);
     return 0;                                                  // fp32 emulation (three operand splits): the per-tile kernels
-}
-
-struct SideRed { hipStream_t st; hipEvent_t ev; };
-static thread_local const SideRed* g_side_red = nullptr;
-hipStream_t cvae_reduce_stream(hipStream_t st) {
-    const SideRed* sr = g_side_red;
-    if (!sr) return st;
-    if (hipEventRecord(sr->ev, st) != hipSuccess || hipStreamWaitEvent(sr->st, sr->ev, 0) != hipSuccess) return st;
-    return sr->st;
 }
 
 struct ParamEntry { std::string name; int64_t offset, numel; };
@@ -96,14 +88,12 @@ struct cvae_handle_s {
     int enc_w[4], enc_b[4], enc_g[4], enc_be[4], fc_w, fc_b, dec_w[5], dec_b[5], di_w, di_b;
     // weight-gradient work runs on a lower-priority side stream, off the dgrad critical path
     hipStream_t side = nullptr;
-    hipEvent_t ev_ready[8] = {}, ev_side = nullptr, ev_red = nullptr, ev_red_done = nullptr;
+    hipEvent_t ev_ready[8] = {}, ev_side = nullptr;
     bool streams_ready = false;
     bool e1_two_pass = false;        // bf16 mode: E1 forward as statistics pass + fused BatchNorm/pool pass (CVAE_E1_TWO_PASS=0: conv, then bn_pool_act_fwd)
     const void* xp_ws = nullptr;     // the workspace (and batch) whose packed bf16 frame the last train-mode forward wrote: the backward stages E1's strips from
     int xp_B = 0;                    // it only then (an eval-mode forward, or another workspace, leaves it stale -> the fp32 frame is staged instead)
     bool fuse_e1 = true;             // block 0's BatchNorm backward applied inside E1's weight-gradient kernel (CVAE_FUSE_E1=0: separate apply pass, for A/B runs)
-    bool side_reduce = false;        // weight-gradient slab reductions on the side stream: measured -2.8 % (fp32, B=256) and
-                                     // -1.6 % (bf16, B=2048) against in-order launches, so OFF; CVAE_SIDE_REDUCE=1 enables it for A/B runs
     ProbeState probe;
 };
 
@@ -122,8 +112,6 @@ static int ensure_streams(cvae_handle_s* h) {
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, lo);
     for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->ev_ready[i], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_side, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_red, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_red_done, hipEventDisableTiming);
     if (e != hipSuccess) { cvae_set_error("side stream setup failed: %s", hipGetErrorString(e)); return (int)e; }
     h->streams_ready = true;
     return 0;
@@ -200,7 +188,6 @@ int cvae_create(const cvae_config* cfg, cvae_handle* out) {
     if (cfg->precision < 0 || cfg->precision > 3) { cvae_set_error("cvae_create: precision %d not supported (0 = fp32, 1 = bf16 MFMA, 2 = fp32 emulated by 3-way bf16 splits)", cfg->precision); return CVAE_EUNSUPPORTED; }
     cvae_handle_s* h = new cvae_handle_s();
     h->cfg = *cfg;
-    { const char* e = getenv("CVAE_SIDE_REDUCE"); h->side_reduce = e && e[0] == '1'; }
     { const char* e = getenv("CVAE_FUSE_E1"); h->fuse_e1 = !(e && e[0] == '0'); }
     { const char* e = getenv("CVAE_E1_TWO_PASS"); h->e1_two_pass = cfg->precision == 1 && !(e && e[0] == '0'); }
     h->param_total = 0;
@@ -229,8 +216,6 @@ void cvae_destroy(cvae_handle h) {
     if (h->streams_ready) {
         for (int i = 0; i < 8; ++i) (void)hipEventDestroy(h->ev_ready[i]);
         (void)hipEventDestroy(h->ev_side);
-        (void)hipEventDestroy(h->ev_red);
-        (void)hipEventDestroy(h->ev_red_done);
         (void)hipStreamDestroy(h->side);
     }
     delete h;
@@ -286,13 +271,10 @@ static bool use_bf16(cvae_handle h, int layer) {
 // precision 1: activations and activation gradients are bf16 IN HBM (every kernel that touches them is told so)
 static bool io_bf16(cvae_handle h) { return h->cfg.precision == 1; }
 static bool use_bf16_wgrad(cvae_handle h, int layer) { return h->cfg.precision == 1 && conv_bf16_supported(layer, h->cfg.width); }
-// fp32-emulation modes: weight gradients of E2..E4 / D0 on the bf16 MFMA with exact 3-way operand splits (conv_bf16.hip);
-// CVAE_SPLIT_WGRAD = bit mask of the layers (bit l-1 = layer l), for A/B runs against the fp32-MFMA kernels
+// fp32-emulation modes: weight gradients of E2..E4 / D0 on the bf16 MFMA with exact 3-way operand splits (conv_wgrad_split.hip)
 static bool use_split_wgrad(cvae_handle h, int layer) {
     if (h->cfg.precision < 2 || layer < 1 || layer > 4 || !conv_bf16_supported(layer, h->cfg.width)) return false;
-    if (!conv_wgrad_split_supported(h->cfg.precision == 3 ? 6 : 9)) return false;
-    static const int mask = [] { const char* e = getenv("CVAE_SPLIT_WGRAD"); return e ? atoi(e) : 15; }();
-    return ((mask >> (layer - 1)) & 1) != 0;
+    return conv_wgrad_split_supported(h->cfg.precision == 3 ? 6 : 9);
 }
 static int bf16_splits(cvae_handle h) { return h->cfg.precision >= 2 ? 3 : 1; }          // packed weight copies
 static int bf16_mode(cvae_handle h) { return h->cfg.precision == 2 ? 3 : (h->cfg.precision == 3 ? 6 : 1); }   // launcher code: 1 bf16, 3 x9, 6 x6
@@ -442,28 +424,8 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
     // cfg.overlap_wgrad != 0: weight-gradient work on a lower-priority side stream (bit-identical results; round 3: +1.5 % in
     // bf16 mode at B = 2048, -3 % in fp32 mode at B = 256); default: everything in order on the caller's stream.
     const bool overlap = h->cfg.overlap_wgrad != 0;
-    const bool side_red = !overlap && h->side_reduce;          // slab reductions only (the wgrad kernels stay on `st`)
-    if (overlap || side_red) RC(ensure_streams(h));
+    if (overlap) RC(ensure_streams(h));
     hipStream_t sd = overlap ? h->side : st;
-    const SideRed sred{h->side, h->ev_red};
-    bool red_pending = false;
-    // Arm: the launcher called inside the scope sends its reductions to the side stream; the shared slab scratch is
-    // only reused once the previous layer's reductions have read it (main waits for ev_red_done first).
-    struct RedArm {
-        cvae_handle_s* h; bool on; bool* pending; hipStream_t st;
-        RedArm(cvae_handle_s* h_, bool on_, bool* p, hipStream_t st_) : h(h_), on(on_), pending(p), st(st_) {
-            if (!on) return;
-            if (*pending) (void)hipStreamWaitEvent(st, h->ev_red_done, 0);
-            g_side_red = nullptr;
-        }
-        void arm(const SideRed* sr) { if (on) g_side_red = sr; }
-        ~RedArm() {
-            if (!on) return;
-            g_side_red = nullptr;
-            (void)hipEventRecord(h->ev_red_done, h->side);
-            *pending = true;
-        }
-    };
 #define HIPRC(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cvae_set_error("%s: %s", #call, hipGetErrorString(e_)); return (int)e_; } } while (0)
     // `ready k` = the gradient a weight-gradient kernel needs exists on the main stream; the side
     // stream picks it up from there, so dW/db never delay the dgrad chain.
@@ -474,10 +436,9 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
         return 0;
     };
     auto join = [&]() -> int {                          // side-stream work of this phase is complete on the caller's stream
-        if (!overlap && !side_red) return 0;
+        if (!overlap) return 0;
         HIPRC(hipEventRecord(h->ev_side, h->side));
         HIPRC(hipStreamWaitEvent(st, h->ev_side, 0));
-        red_pending = false;
         return 0;
     };
     if (phase_mask & 1) {
@@ -490,7 +451,7 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
         const float* in = i == 0 ? ws + w.h : ws + w.o[i - 1];
         RC(fork(3 - i));
         if (i == 0) {
-            { ProbeArm pa(h, 2, l); RedArm ra(h, side_red, &red_pending, st); ra.arm(&sred);
+            { ProbeArm pa(h, 2, l);
               if (use_bf16_wgrad(h, 4)) RC(launch_conv_wgrad_bf16(4, W, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd));
               else if (use_split_wgrad(h, 4)) RC(launch_conv_wgrad_split(4, W, bf16_mode(h) == 6 ? 6 : 9, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd));
               else RC(launch_conv_wgrad(l, W, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd)); }
@@ -498,7 +459,7 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
               if (use_bf16(h, 4)) RC(launch_conv_dgrad_bf16(4, W, bf16_mode(h), B, ws + w.d_o[0], ws + w.wpack, ws + w.d_h, ws + w.scratch, st));
               else RC(launch_conv_dgrad(l, W, B, ws + w.d_o[0], P_(h->dec_w[0]), nullptr, ws + w.d_h, ws + w.scratch, st)); }
         } else {
-            { ProbeArm pa(h, 2, l); RedArm ra(h, side_red, &red_pending, st); ra.arm(&sred);
+            { ProbeArm pa(h, 2, l);
               RC(launch_conv_up_wgrad(l, W, B, in, ws + w.d_o[i], G_(h->dec_w[i]), G_(h->dec_b[i]), scw, sd, use_bf16_wgrad(h, l))); }
             { ProbeArm pa(h, 1, l);
               if (use_bf16(h, l)) RC(launch_conv_up_dgrad_bf16(l, W, bf16_mode(h), B, ws + w.d_o[i], ws + w.wpack, ws + w.o[i - 1], ws + w.d_o[i - 1], st));
@@ -525,11 +486,11 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
         if (l == 0) {
             const float* fu[7] = {ws + w.y[0], ws + w.a[0], ws + w.d_a[0], ws + w.coef[0], bn_bwd_bcoef(0, W, B, sc),
                                   P_(h->enc_w[0]), P_(h->enc_b[0])};
-            { ProbeArm pa(h, 2, 0); RedArm ra(h, side_red, &red_pending, st); ra.arm(&sred);
+            { ProbeArm pa(h, 2, 0);
               RC(launch_e1_wgrad(W, B, x, fuse0 ? nullptr : ws + w.d_y[0], G_(h->enc_w[0]), G_(h->enc_b[0]), scw, sd, h->cfg.precision == 1, fuse0 ? fu : nullptr,
                                  (h->e1_two_pass && fuse0 && h->xp_ws == (const void*)ws && h->xp_B == B) ? ws + w.xp : nullptr)); }
         } else {
-            { ProbeArm pa(h, 2, l); RedArm ra(h, side_red, &red_pending, st); ra.arm(&sred);
+            { ProbeArm pa(h, 2, l);
               if (use_bf16_wgrad(h, l)) RC(launch_conv_wgrad_bf16(l, W, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd));
               else if (use_split_wgrad(h, l)) RC(launch_conv_wgrad_split(l, W, bf16_mode(h) == 6 ? 6 : 9, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd));
               else RC(launch_conv_wgrad(l, W, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd)); }

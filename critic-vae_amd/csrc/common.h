@@ -135,12 +135,6 @@ __device__ __forceinline__ bool wg_arrive_last(unsigned* counter, unsigned total
 void cvae_probe_begin(hipStream_t st);
 void cvae_probe_end(hipStream_t st);
 
-// Split-K slab reductions of the weight gradients are off the critical path (nothing reads dW before the phase
-// ends): when the orchestration arms a side stream (api.hip), a wgrad launcher calls cvae_reduce_stream(st) right
-// after its main kernel and enqueues its small reduce / expand kernels on the stream it returns (ordered behind
-// the main kernel by an event), so their ~5 us launch floors overlap the next input-gradient kernel.
-hipStream_t cvae_reduce_stream(hipStream_t st);
-
 // error plumbing (api.hip)
 void cvae_set_error(const char* fmt, ...);
 #define CVAE_CHECK_LAUNCH()                                                        \
@@ -185,6 +179,8 @@ int64_t conv_bf16_pack_floats(int ns);
 int launch_pack_w_bf16(const float* const w[4], float* packed, int ns, hipStream_t st);     // ns = 1 (bf16) or 3 (fp32 emulation)
 // cvae_conv_route (host logic only): while set, the persistent launchers return 0 behind their size guards WITHOUT touching the device
 extern thread_local bool g_conv_dry;
+// CVAE_CONV_PER_TILE=1 (tests): every conv pass of both precisions on the per-tile kernels, the route tensors of 2 GiB and more take
+bool conv_per_tile_only();
 // kernel family the conv launchers pick for E2..E4 (layer 1..3; 4 = D0 at 128 x 128) at batch B: 0 per-tile, 1 two-workgroup persistent, 2 big-tile persistent
 int conv_bf16_route(int layer, int width, bool dgrad, int B);
 int conv_f32_route(int layer, int width, bool dgrad, int B);

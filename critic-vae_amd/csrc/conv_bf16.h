@@ -24,12 +24,12 @@ template <int H, int OCT> struct Bf16Geom {
 };
 
 
-// conv_bf16_ps.hip: persistent forward / input-gradient kernel of E2..E4 in bf16 mode (returns -100 if the layer has no instantiation)
+// conv_bf16_ps.hip: persistent two-workgroup forward kernel of D0 at 128 x 128 in bf16 mode (returns -100 for any other pass, or a tensor too large
+// for its 32-bit offsets)
 int launch_conv_bf16_ps(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st);
-// conv_bf16_big.hip: persistent big-tile kernel (16 accumulator tiles per wave; `mask`: the layer bits of CVAE_BF16_BIG for this pass); -100 if the
-// layer has no instantiation, is masked out, or a tensor is too large for its 32-bit offsets
-int launch_conv_bf16_big(int layer, int width, bool dgrad, int mask, const ConvBf16Args& a, hipStream_t st);
-bool conv_bf16_big_has(int layer, int width, bool dgrad, int mask);
+// conv_bf16_big.hip: persistent big-tile kernel of E2..E4 (16 accumulator tiles per wave); -100 if the layer has no instantiation or a tensor is
+// too large for its 32-bit offsets
+int launch_conv_bf16_big(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st);
 int conv_bf16_big_tiles(int layer, int width, bool dgrad);      // 128-pixel tiles per item (= per BatchNorm partial of its forward passes)
 
 // Exact 3-way bf16 split of an fp32 value: x == hi + mid + lo (each difference is exact in fp32, RNE

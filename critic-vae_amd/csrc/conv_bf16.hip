@@ -21,7 +21,6 @@
 // Results differ from the fp32 path at the bf16 rounding level (~3e-3 relative per product);
 // tests/test_gpu_bf16.py states the tolerances.
 #include "common.h"
-#include <stdlib.h>
 #include "conv_epilogue.h"
 #include "conv_bf16.h"
 
@@ -34,24 +33,7 @@
 // MODE_UP_DGRAD: its input gradient: K = 4 phases x COUT channels gathered from dout by phase
 //   (space-to-depth view), taps flipped in the packed weights, ReLU mask of the producer in the epilogue.
 enum { MODE_STD = 0, MODE_UP_FWD = 1, MODE_UP_DGRAD = 2 };
-#ifndef BF16_MT
-#define BF16_MT 2          // 128-pixel tiles per workgroup of the plain bf16 kernels (1 = round-1 structure)
-#endif
-#ifndef BF16_BIG_DEFAULT
-// CVAE_BF16_BIG: layers on the persistent big-tile kernel (conv_bf16_big.hip) — bit 2 = E4 input gradient, bit 3 = E3 input gradient, bit 4 = E3 forward,
-// bit 5 = E4 forward, bit 6 = E2 forward and bit 7 = E2 input gradient at 64 x 64 (image-high items on an 8 x 1 wave tile; one BatchNorm partial per item of
-// four / eight tiles); 0 = the two-workgroup / per-tile kernels (A/B runs).  Defaults from the un-profiled step on one box, masks alternating
-// (profiles/r05_g_big_mask_sweep.txt, r05_k_big_image_layout.txt, r05_r_e2_on_big_kernel.txt): every bit at 64 x 64 (252: E2 forward 196 vs 209 us, E2 input gradient
-// 192 vs 209 us, step +0.8 % over mask 60) and at 128 x 128 (E2's 64-row images as 16-row strips with real halo rows: input gradient 379 vs 415 us, forward 424 vs 431, step +0.9 %).
-#define BF16_BIG_DEFAULT 252
-#endif
-#ifndef BF16_BIG_DEFAULT_W128
-#define BF16_BIG_DEFAULT_W128 252
-#endif
-#ifndef BF16_WDMA
-#define BF16_WDMA 0        // 1 (experiment, round 3): weight slabs travel HBM -> LDS by LDS-DMA (global_load_lds_dwordx4) into a double
-#endif                     // buffer, one barrier per K stage.  Correct (tests green) but SLOWER on the MI355X: E2 fwd 227 -> 237 us, E2 dgrad
-                           // 223 -> 261, E4 dgrad 206 -> 227, E3 fwd 206 -> 216 at B = 2048 (0: registers -> ds_write_b128, two barriers per stage)
+constexpr int BF16_MT = 2;         // 128-pixel tiles per workgroup of the plain bf16 kernels
 
 __device__ __forceinline__ bf16x8 to_bf16x8(f32x4 lo, f32x4 hi) {
     bf16x8 r;
@@ -70,27 +52,9 @@ template <int KCH, int NS, int MT> struct Bf16Chunk {
 // MT = 128-pixel tiles per workgroup (bf16 mode: 2): one weight slab staged into LDS — and one weight fragment read
 // from LDS — serves MT times as many MFMAs; the K chunk shrinks to 32 channels so that the LDS footprint (and with
 // it the number of resident workgroups) stays where it was.
-#ifdef EPI_TIMING
-extern "C" int cvae_epi_dbg_read(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(epi_dbg), sizeof(epi_dbg)); }
-#endif
-#ifdef CONV_TIMING     // experiment builds only: where a wave of ONE instantiation (-DCONV_TIMING_KCH/NCH/H) spends its stages
-__device__ long long conv_dbg[16 * 4 * 12];
-extern "C" int cvae_conv_dbg_read(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(conv_dbg), sizeof(conv_dbg)); }
-#define CT_ON (KCH == CONV_TIMING_KCH && NCH == CONV_TIMING_NCH && H == CONV_TIMING_H && NS == 1 && MODE == MODE_STD)
-#define CT_STAMP(v) do { if (CT_ON) v = clock64(); } while (0)
-#else
-#define CT_ON false
-#define CT_STAMP(v)
-#endif
 
-#ifndef BF16_WAVES_ATTR
-#define BF16_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(MT > 2 ? 1 : 2, MT > 2 ? 1 : 2)))      // MT = 4 (big-tile experiment): one wave per SIMD, 512 registers
-#endif
-#ifndef BF16_WAVES_PER_SIMD
-#define BF16_WAVES_PER_SIMD 1      // experiment: 3 = cap the kernel at 168 VGPRs so that three workgroups fit a CU where the LDS allows it
-#endif
 template <int KCH, int NCH, int H, int NT, int EPI, int KSPLIT, int KS = 5, int MODE = MODE_STD, int NS = 1, int DMAX = 4, int MT = 1>
-__global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv5x5_bf16_kernel(ConvBf16Args a) {
+__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv5x5_bf16_kernel(ConvBf16Args a) {
     using T = Tile<H>;
     static_assert(NS == 1 || NS == 3, "operand splits: 1 (bf16) or 3 (fp32 emulation, 9 MFMAs per product block)");
     static_assert(MT == 1 || NS == 1, "multi-tile workgroups are a bf16-mode feature");
@@ -100,21 +64,12 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
     constexpr int KB = KCB / 16, OCT = KCB / 8, NB = NT / 32;
     constexpr int PSP = Bf16Geom<H, OCT>::PSP;
     constexpr int A_UNITS = OCT * PSP, W_UNITS = KS * KB * 2 * NT;
-    // WDMA (bf16 mode): the weight slab of stage st+1 is copied HBM -> LDS by LDS-DMA while stage st computes — no staging
-    // registers, no ds_write_b128 (13 issue cycles each), and with two slab buffers ONE barrier per stage: the slab's unit
-    // order in LDS is the staging thread order (unit q <- thread q), which is exactly the DMA's "wave base + lane * 16".
-    constexpr bool WDMA = NS == 1 && BF16_WDMA != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16x8* lds_a = reinterpret_cast<bf16x8*>(smem_raw);      // [tile][split][octet][halo pixel]
-    bf16x8* lds_w = lds_a + MT * NS * A_UNITS;                 // [buffer (WDMA: 2)][split][tap][kb][half][n]
+    bf16x8* lds_w = lds_a + MT * NS * A_UNITS;                 // [split][tap][kb][half][n]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
     const int mt0 = xcd_tile(blockIdx.x, gridDim.x) * MT, n0 = blockIdx.y * NT;
-#ifdef CONV_STAGGER        // timing experiment: the workgroups of the second residency slot start CONV_STAGGER x 4 k cycles late
-    if (blockIdx.y == 0 && blockIdx.z == 0 && blockIdx.x >= 256 && blockIdx.x < 512) {
-        for (int i = 0; i < CONV_STAGGER; ++i) __builtin_amdgcn_s_sleep(64);
-    }
-#endif
     int img0v[MT], ty0v[MT], tx0v[MT];
 #pragma unroll
     for (int tl = 0; tl < MT; ++tl) {          // a tile index past the end maps to images >= B: loads give 0, stores are skipped
@@ -136,8 +91,7 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
 
     // weight slab of stage (cc, r): units [s][kb][half][n] <- wp[(r*5+s)][cc*KB + kb][half][n0 + n]
     constexpr int WPT = (W_UNITS + 255) / 256;
-    static_assert(!WDMA || W_UNITS % 64 == 0, "whole wave-instructions of 64 units");
-    bf16x8 wreg[WDMA ? 1 : NS * WPT];
+    bf16x8 wreg[NS * WPT];
     // per-thread part of every staging address is fixed for the whole launch: computed once, so a stage adds one
     // wave-uniform term per load instead of redoing the div/mod chains (they were ~3 VALU instructions per MFMA)
     int wbase[WPT];
@@ -157,16 +111,6 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
 #pragma unroll
                 for (int sp = 0; sp < NS; ++sp) wreg[sp * WPT + i] = wst[wbase[i] + sp * a.splitStride];
             }
-        }
-    };
-    auto dma_w = [&](int st, int buf) {          // WDMA: stage st's slab -> lds_w buffer `buf`
-        const int cc = st / KS, r = st % KS;
-        const bf16x8* wst = a.wp + (size_t)(r * KS * (KCH / 16) + cc * KB) * 2 * NCH;
-#pragma unroll
-        for (int i = 0; i < WPT; ++i) {
-            if (W_UNITS % 256 == 0 || i * 256 + wave * 64 < W_UNITS)          // wave-uniform
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wst + wbase[i]),
-                                                 (__attribute__((address_space(3))) void*)(lds_w + buf * W_UNITS + i * 256 + wave * 64), 16, 0, 0);
         }
     };
     auto store_w = [&]() {
@@ -272,7 +216,7 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
     constexpr bool HAS_BIAS = (MODE == MODE_STD && KSPLIT == 1 && (EPI == EPI_BIAS_BNSTAT || EPI == EPI_BIAS_RELU)) || MODE == MODE_UP_FWD;
     constexpr bool BNSTAT = MODE == MODE_STD && KSPLIT == 1 && EPI == EPI_BIAS_BNSTAT;
     // bf16 mode (NS == 1): channel-major accumulators.  Behind the staging buffers: [NT bias][MT][2][4 waves][NT] BatchNorm rows
-    float* lds_x = reinterpret_cast<float*>(smem_raw) + (size_t)(MT * NS * A_UNITS + (WDMA ? 2 : 1) * NS * W_UNITS) * 4;
+    float* lds_x = reinterpret_cast<float*>(smem_raw) + (size_t)(MT * NS * A_UNITS + NS * W_UNITS) * 4;
     [[maybe_unused]] float biasv[NB] = {};
     [[maybe_unused]] float bias_stash = 0.f;    // requested first, written to LDS with the first weight slab (no wait of its own)
     if constexpr (HAS_BIAS && NS == 1) {
@@ -299,69 +243,22 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
                 for (int k = 0; k < 2; ++k) mkv[(tl * NB + nb) * 2 + k] = Act<__bf16>::ld8(a.aux, ib < a.B ? base + nb * 32 + 16 * k : 0);
         }
     }
-    if constexpr (WDMA) dma_w(st0, 0); else load_w(st0);
+    load_w(st0);
     load_input(st0 / KS);
-    [[maybe_unused]] long long ct0 = 0, ct1 = 0, ct2 = 0, ct3 = 0, ct4 = 0, cd[6] = {0, 0, 0, 0, 0, 0}, ctb = 0, cta = 0, ctw = 0;      // CONV_TIMING builds
-    CT_STAMP(ctb);
-    [[maybe_unused]] const long long crt0 = CT_ON ? (long long)wall_clock64() : 0;
     for (int st = st0; st < st1; ++st) {
         const int r = st % KS;
-        int wbuf = 0;
-        CT_STAMP(ct0);
-        if constexpr (WDMA) {
-            wbuf = (st - st0) & 1;
-            if (r == 0) {
-                __syncthreads();                   // chunk boundary: everyone finished reading the previous chunk's input tiles
-                store_input();
-            }
-            CT_STAMP(ct1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's part of slab st has landed (and the next chunk's inputs)
-            CT_STAMP(cta); CT_STAMP(ctw);
-            __syncthreads();                       // slab st (and the input tiles) visible to all; everyone is done with slab st-1
-            CT_STAMP(ct2);
-            if (r == 0 && st + KS < st1) load_input(st / KS + 1);
-            if (st + 1 < st1) dma_w(st + 1, wbuf ^ 1);            // lands in the buffer stage st-1 read, while this stage computes
-            CT_STAMP(ct3);
-        } else {
         __syncthreads();                       // everyone finished reading the previous stage
-        CT_STAMP(ct1);
         if (r == 0) store_input();
-        CT_STAMP(cta);
         store_w();
         if constexpr (HAS_BIAS && NS == 1) { if (st == st0 && tid < NT) lds_x[tid] = bias_stash; }
-        CT_STAMP(ctw);
         // issue order: vmcnt retires in order, so the (older) halo loads must not sit between a weight
         // load and the store_w that waits for it (see conv_mfma.hip)
         if (r == 0 && st + KS < st1) load_input(st / KS + 1);
         if (st + 1 < st1) load_w(st + 1);      // in flight while this stage computes
-        CT_STAMP(ct2);
         __syncthreads();
-        CT_STAMP(ct3);
-        }
         const bf16x8* ap = lds_a + lh * PSP + aPix + (r + OFF) * T::HTW + OFF;
-        const bf16x8* bp = lds_w + wbuf * W_UNITS + lh * NT + li;
-#ifndef BF16_LOOP
-#define BF16_LOOP 0       // timing experiments (results WRONG unless 0): bit 0 = compiler-scheduled loop (iglp_opt) instead of the pinned pipeline, bit 1 = operands not swapped
-#endif
-        if constexpr (NS == 1 && (BF16_LOOP & 1)) {
-            __builtin_amdgcn_iglp_opt(0);
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb) {
-                    bf16x8 bv[NB];
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) bv[nb] = bp[((s * KB + kb) * 2) * NT + nb * 32];
-#pragma unroll
-                    for (int tl = 0; tl < MT; ++tl) {
-                        const bf16x8 av = ap[tl * A_UNITS + (kb * 2) * PSP + s];
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb)
-                            acc[tl][nb] = (BF16_LOOP & 2) ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv[nb], acc[tl][nb], 0, 0, 0)
-                                                          : __builtin_amdgcn_mfma_f32_32x32x16_bf16(bv[nb], av, acc[tl][nb], 0, 0, 0);
-                    }
-                }
-        } else if constexpr (NS == 1) {
+        const bf16x8* bp = lds_w + lh * NT + li;
+        if constexpr (NS == 1) {
             // Software pipeline, written out: the fragments of step i + PF are requested before the MFMAs of step i (a step = one tap x one
             // 16-channel block: NB weight + MT pixel fragments, MT x NB MFMAs), three register sets in rotation, and the order is PINNED with
             // sched_group_barrier — left to itself (iglp_opt) the scheduler of hipcc 7.2 serialised `ds_read -> s_waitcnt lgkmcnt(0) -> MFMA`
@@ -385,8 +282,7 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
                 for (int tl = 0; tl < MT; ++tl)
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb)      // weights as the A operand: D[channel][pixel], see conv_epilogue.h (channel-major)
-                        acc[tl][nb] = (BF16_LOOP & 2) ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[i % NSET][tl], wf[i % NSET][nb], acc[tl][nb], 0, 0, 0)
-                                                      : __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i % NSET][nb], xf[i % NSET][tl], acc[tl][nb], 0, 0, 0);
+                        acc[tl][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i % NSET][nb], xf[i % NSET][tl], acc[tl][nb], 0, 0, 0);
                 // one fragment read behind each MFMA while there are reads left in this step, then the remaining MFMAs back to back
                 constexpr int NM = MT * NB, NR = NB + MT;
 #pragma unroll
@@ -423,20 +319,10 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
                     }
                 }
             }
-#ifdef CONV_TIMING
-        if (CT_ON) {
-            __builtin_amdgcn_sched_barrier(0);
-            long long te = clock64();
-            cd[0] += ct1 - ct0; cd[1] += ct2 - ct1; cd[2] += ct3 - ct2; cd[3] += te - ct3; cd[4] += cta - ct1; cd[5] += ctw - cta;
-        }
-#endif
     }
     vm_drained();
     float* smem = reinterpret_cast<float*>(smem_raw);
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG;
-#ifdef CONV_TIMING
-    if (CT_ON) { CT_STAMP(ct4); cd[0] += 0; }
-#endif
     if constexpr (NS == 1) {
         // ---- channel-major epilogue (conv_epilogue.h): every wave on its own, straight from the accumulators ----
         [[maybe_unused]] f32x4 bq[NB][4];                 // bias of the lane's 16 channels per block: quads 8g + 4lh .. +3
@@ -487,10 +373,9 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
                             for (int e = 0; e < 8; ++e) u[k][e] = (float)mk[e] > 0.f ? u[k][e] : (__bf16)0.f;
                         }
                     }
-                    if (valid && !(EPI_EXPERIMENT & 1)) { Act<__bf16>::st8(a.out, base, u[0]); Act<__bf16>::st8(a.out, base + 16, u[1]); }
-                    if ((EPI_EXPERIMENT & 1) && u[0][0] == (__bf16)123.f && u[1][7] == (__bf16)77.f) Act<__bf16>::st8(a.out, base, u[0]);     // timing builds: keeps the values alive
+                    if (valid) { Act<__bf16>::st8(a.out, base, u[0]); Act<__bf16>::st8(a.out, base + 16, u[1]); }
                 }
-                if constexpr (BNSTAT && !(EPI_EXPERIMENT & 2)) {          // per-wave column sums of y and y*y over its 32 pixels (pixels past the batch count as 0)
+                if constexpr (BNSTAT) {          // per-wave column sums of y and y*y over its 32 pixels (pixels past the batch count as 0)
                     float sv[16], qv[16];
 #pragma unroll
                     for (int v = 0; v < 16; ++v) { sv[v] = valid ? c[v] : 0.f; qv[v] = sv[v] * sv[v]; }
@@ -502,7 +387,7 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
                 }
             }
         }
-        if constexpr (BNSTAT && !(EPI_EXPERIMENT & 2)) {
+        if constexpr (BNSTAT) {
             // the four waves' rows meet once: per tile and channel (sum, M2 about the tile mean) as bn_fwd_finalize merges them
             // (nn.BatchNorm2d train-mode statistics, vae_nets.py:70,75,80,85); M2 = Q - S*S/n in double
             __syncthreads();
@@ -589,19 +474,11 @@ __global__ __launch_bounds__(256, BF16_WAVES_PER_SIMD) BF16_WAVES_ATTR void conv
         epilogue_store<H, NT, NCH, EPI_PLAIN, float, NS == 1>(acc[tl], a.out + (size_t)blockIdx.z * a.sliceFloats, nullptr, smem, a.B,
                                                               mt, n0, img0, ty0, tx0, numTiles);
     } else {
-        if constexpr (NS == 1) epilogue_store<H, NT, NCH, EPI, __bf16, true>(acc[tl], a.out, a.bnpart, smem, a.B, mt, n0, img0, ty0, tx0, numTiles, CT_ON ? tl * 12 : 32);
+        if constexpr (NS == 1) epilogue_store<H, NT, NCH, EPI, __bf16, true>(acc[tl], a.out, a.bnpart, smem, a.B, mt, n0, img0, ty0, tx0, numTiles);
         else epilogue_store<H, NT, NCH, EPI>(acc[tl], a.out, a.bnpart, smem, a.B, mt, n0, img0, ty0, tx0, numTiles);
     }
     }
     }
-#ifdef CONV_TIMING
-    if (CT_ON && (blockIdx.x & 63) == 0 && blockIdx.x < 1024 && blockIdx.y == 0 && lane == 0) {
-        long long tend = clock64();
-        long long* o = conv_dbg + ((blockIdx.x >> 6) * 4 + wave) * 12;
-        o[0] = cd[0]; o[1] = cd[1]; o[2] = cd[2]; o[3] = cd[3]; o[4] = ct4 - ctb; o[5] = tend - ct4; o[6] = st1 - st0; o[7] = tend - ctb; o[8] = cd[4]; o[9] = cd[5];
-        o[10] = (long long)wall_clock64() - crt0;        // 100 MHz ticks over the same span: in-kernel clock = o[7] / o[10] * 100 MHz
-    }
-#endif
 }
 
 // ---- weight packing into bf16 units: unit ((tap*(K/16) + kb)*2 + half)*N + n holds k = kb*16 + half*8 .. +7.
@@ -691,8 +568,7 @@ template <int KCH, int NCH, int H, int NT, int EPI, int KSPLIT = 1, int KS = 5, 
 static int run_bf16_ns(const ConvBf16Args& a, hipStream_t st) {
     using T = Tile<H>;
     constexpr int KCB = Bf16Chunk<KCH, NS, MT>::KCB;
-    constexpr int WBUF = (NS == 1 && BF16_WDMA != 0) ? 2 : 1;          // LDS-DMA weight slabs are double-buffered
-    constexpr int STAGE = (MT * NS * (KCB / 8) * Bf16Geom<H, KCB / 8>::PSP + WBUF * NS * KS * (KCB / 16) * 2 * NT) * 16;
+    constexpr int STAGE = (MT * NS * (KCB / 8) * Bf16Geom<H, KCB / 8>::PSP + NS * KS * (KCB / 16) * 2 * NT) * 16;
     constexpr int EPI_BYTES = (8 * NT > 4 * 32 * 36 ? 8 * NT : 4 * 32 * 36) * 4;
     // bf16 mode: no transpose patch; bias row + BatchNorm rows of the channel-major epilogue sit behind the staging buffers
     constexpr int SMEM = NS == 1 ? STAGE + (NT + MT * 8 * NT) * 4 : (STAGE > EPI_BYTES ? STAGE : EPI_BYTES);
@@ -846,31 +722,20 @@ static int run4x4_bf16(const ConvBf16Args& a, hipStream_t st) {
 
 bool conv_bf16_supported(int layer, int width) { return (width == 64 || width == 128) && layer >= 1 && layer <= 7; }
 
-// bf16 mode: E2..E4 forward / input gradient run on the persistent kernel of conv_bf16_ps.hip (CVAE_CONV_PS=0: the per-tile kernel, for A/B runs)
-// CVAE_CONV_PS = bit mask of the layers that run on it: bit (layer - 1) forward, bit (3 + layer - 1) input gradient (0 = none: A/B runs)
-#ifndef CONV_PS_DEFAULT
-#define CONV_PS_DEFAULT 7        // forward E2..E4 on the persistent kernel; the input gradients measured level or slower on it
-#endif
-static bool use_ps_kernel(int layer, bool dgrad) {
-    static const int mask = [] { const char* e = getenv("CVAE_CONV_PS"); return e ? atoi(e) : CONV_PS_DEFAULT; }();
-    const int bit = (dgrad ? 3 : 0) + (layer >= 4 ? 2 : layer - 1);       // layer 4 (128-wide frames only) shares E4's bit
-    return ((mask >> bit) & 1) != 0;
-}
-
-static int bf16_big_mask(int width) {
-    static const int big = [] { const char* e = getenv("CVAE_BF16_BIG"); return e ? atoi(e) : -1; }();
-    return big >= 0 ? big : (width == 128 ? BF16_BIG_DEFAULT_W128 : BF16_BIG_DEFAULT);
-}
-// E2..E4 forward / input gradient in bf16 mode: the persistent kernel families in the order the launchers try them.  *family = 2 (the big-tile
-// kernel of conv_bf16_big.hip took the layer), 1 (the two-workgroup kernel of conv_bf16_ps.hip did) or 0 (neither serves this layer at this size — no
-// instantiation, masked out, or a tensor of 2 GiB and more: the caller runs the per-tile kernel).  Returns the launch's error code.
+// bf16 mode: the persistent kernel a forward / input-gradient pass runs on.  *family = 2: E2..E4 (layers 1..3), both passes, at both frame sizes on the
+// big-tile kernel of conv_bf16_big.hip (E2 forward 196 vs 209 us, E2 input gradient 192 vs 209 us at 64 x 64; at 128 x 128 E2's input gradient 379 vs
+// 415 us, forward 424 vs 431: profiles/r05_g_big_mask_sweep.txt, r05_k_big_image_layout.txt, r05_r_e2_on_big_kernel.txt); 1: D0's forward at 128 x 128
+// on the two-workgroup kernel of conv_bf16_ps.hip; 0: the caller runs the per-tile kernel — every other pass, a tensor of 2 GiB and more (the persistent
+// launchers return -100), or CVAE_CONV_PER_TILE=1.  Returns the launch's error code.
 static int try_persistent_bf16(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st, int* family) {
     *family = 0;
-    const int big = bf16_big_mask(width);
-    const int m = dgrad ? ((big >> 2) & 3) | ((big >> 5) & 4) : (big >> 4) & 7;      // bits 2 / 3 / 7: E4 / E3 / E2 input gradient; bits 4 / 5 / 6: E3 / E4 / E2 forward
-    if (m) { const int rc = launch_conv_bf16_big(layer, width, dgrad, m, a, st); if (rc != -100) { *family = 2; return rc; } }
-    if (use_ps_kernel(layer, dgrad)) { const int rc = launch_conv_bf16_ps(layer, width, dgrad, a, st); if (rc != -100) { *family = 1; return rc; } }
-    return 0;
+    if (conv_per_tile_only()) return 0;
+    int rc = -100, fam = 0;
+    if (layer >= 1 && layer <= 3) { rc = launch_conv_bf16_big(layer, width, dgrad, a, st); fam = 2; }
+    else if (layer == 4 && width == 128 && !dgrad) { rc = launch_conv_bf16_ps(layer, width, dgrad, a, st); fam = 1; }
+    if (rc == -100) return 0;
+    *family = fam;
+    return rc;
 }
 int conv_bf16_route(int layer, int width, bool dgrad, int B) {
     ConvBf16Args a{};
@@ -1015,9 +880,6 @@ int launch_conv_up_dgrad_bf16(int layer, int width, int ns, int B, const float* 
 
 // WT_NW waves per workgroup (4: two workgroups per CU, 8 accumulator tiles per wave; 8: one workgroup per CU whose
 // 8 waves share every staged tile, 5 accumulator tiles per wave — better for the 32-channel layer E2)
-#ifndef WGRAD_PIPE
-#define WGRAD_PIPE 2       // input fragments requested this many MFMA slots ahead (0: round-4 form — request, wait, MFMA)
-#endif
 template <int H, int WT_NW, int W, int COB>
 __device__ __forceinline__ void wgrad_tr_body(f32x16 (&acc)[COB][24 / WT_NW + 2], const __bf16* lds_in, const __bf16* lds_d, int ibase, int dbase,
                                               bf16x8 ones) {
@@ -1025,7 +887,7 @@ __device__ __forceinline__ void wgrad_tr_body(f32x16 (&acc)[COB][24 / WT_NW + 2]
     constexpr int JT = 24 / WT_NW;
     static_assert(T::KG % WT_NW == 0, "pixel groups per tile must split evenly over the waves");
     // A slot = one input fragment (two transposed reads) and its COB MFMAs: the JT taps of this wave for every pixel group.
-    // Round 5: the fragment of slot n + WGRAD_PIPE is requested before the MFMAs of slot n and the dy fragments of the
+    // Round 5: the fragment of slot n + PD (= 2) is requested before the MFMAs of slot n and the dy fragments of the
     // next pixel group half a group ahead, pinned (one MFMA, then its share of reads).  Round 4 left the order to the compiler, which emitted
     // request -> s_waitcnt lgkmcnt(0) -> MFMA for every slot: a wave's MFMA sat behind the full latency of its own transposed reads and the
     // matrix pipe was busy 47-58 % with two waves per SIMD (profiles/r04_m_pmc_summary_bf16.csv).
@@ -1038,7 +900,7 @@ __device__ __forceinline__ void wgrad_tr_body(f32x16 (&acc)[COB][24 / WT_NW + 2]
         const __bf16* dp = lds_d + cb * T::NPX * 32 + dbase + T::pixbase(kg) * 32;
         return tr_frag(dp, dp + T::DT * 32);
     };
-    constexpr int NSLOT = T::KG * JT, PD = WGRAD_PIPE, RING = PD + 1;        // the regular slots: n = kg * JT + j (tap 24 rides outside the pipeline)
+    constexpr int NSLOT = T::KG * JT, PD = 2, RING = PD + 1;                 // the regular slots: n = kg * JT + j (tap 24 rides outside the pipeline)
     bf16x8 av[RING], bv[2][COB];
 #pragma unroll
     for (int cb = 0; cb < COB; ++cb) bv[0][cb] = dy_frag(0, cb);
@@ -1057,11 +919,9 @@ __device__ __forceinline__ void wgrad_tr_body(f32x16 (&acc)[COB][24 / WT_NW + 2]
 #pragma unroll
             for (int cb = 0; cb < COB; ++cb)
                 acc[cb][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[n % RING], bv[kg & 1][cb], acc[cb][j], 0, 0, 0);
-            if constexpr (PD > 0) {
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                if (j == JT / 2 && kg + 1 < T::KG) __builtin_amdgcn_sched_group_barrier(0x100, 2 * COB, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, COB, 0);
-            }
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            if (j == JT / 2 && kg + 1 < T::KG) __builtin_amdgcn_sched_group_barrier(0x100, 2 * COB, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, COB, 0);
         }
         if ((kg % WT_NW) == W) {                                // tap 24: every WT_NW-th pixel group of this wave (1 / 25 of the MFMAs, unpipelined)
             const bf16x8 a24 = in_frag(kg, 24);
@@ -1237,7 +1097,6 @@ static int run_wgrad_bf16(int B, const float* in, const float* dout, float* dw, 
     cvae_probe_end(st);
     CVAE_CHECK_LAUNCH();
     float* mid = ws + (size_t)S * row;
-    st = cvae_reduce_stream(st);
     if (dbias == dw + n) return launch_reduce_slabs(ws, dw, row, S, row, st, mid);
     int rc = launch_reduce_slabs(ws, dw, n, S, row, st, mid);
     if (rc || !dbias) return rc;
@@ -1283,10 +1142,7 @@ int launch_conv_wgrad_bf16(int layer, int width, int B, const float* in, const f
 // 8x8 blocks in registers while staging and had no tile in flight (83 / 45 / 45 us at B = 2048).
 // The slab row [36][CIN][COUT] | bias[COUT] is what conv_up.hip's reduce + expand_dw_kernel consume.
 // ---------------------------------------------------------------------------------------------
-#ifndef UPW_NP
-#define UPW_NP 64
-#endif
-template <int HS> using UpWgTile = WtTile<HS, 1, UPW_NP>;        // low-res pixels per tile, halo 1
+template <int HS> using UpWgTile = WtTile<HS, 1, 64>;        // low-res pixels per tile, halo 1
 
 template <int CIN, int COUT, int HS>
 __global__ __launch_bounds__(256, 2) void conv_up_wgrad_bf16_kernel(WgradBf16Args a) {

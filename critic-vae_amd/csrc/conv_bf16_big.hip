@@ -18,9 +18,7 @@
 //     slab 0 AND its slab 1 are requested before the current item's epilogue (vmcnt retires loads and stores in issue order: a load
 //     consumed behind the epilogue's stores would wait for their write acknowledgements), so an item starts without a cold prologue
 //     and the epilogue's stores drain under the next item's MFMAs.
-// IMGL (round 5): an item's tiles are whole images in LDS — borders zeroed once, only the interiors staged (see the kernel).  S16 (round 5, opt-in through
-// CVAE_BIG_S16=1): the same kernel on v_mfma_f32_16x16x32_bf16, on which the power-limited chip holds a 15 % higher clock (profiles/r05_l_mfma_shape_probe.txt,
-// r05_m_big_s16.txt: level with the 32x32x16 form so far; see stage16).
+// IMGL (round 5): an item's tiles are whole images in LDS — borders zeroed once, only the interiors staged (see the kernel).
 // Epilogues, both from channel-major accumulators (v_cvt_pk + two 16-byte buffer stores per tile, no transpose, invalid lanes as
 // out-of-range offsets): plain (input gradient), or bias (= the accumulators' initial value) + ONE BatchNorm partial per item — its MT
 // tiles summed in the lane before the cross-lane column sums (launch_bn_fwd_finalize(.., tilesPerPartial = MT)).
@@ -30,48 +28,9 @@
 #include "conv_epilogue.h"
 #include "conv_bf16.h"
 
-// -DBIG_TIMING (timing builds): cycles of ONE instantiation (-DBIG_T_KCH/NCH/H), wave 0 lane 0 of the sampled workgroups (blockIdx.x a
-// multiple of 16 below 256): [items, prologue, stages (MFMA stream with everything interleaved), chunk-closing barriers + first fragments,
-// epilogue, whole kernel, s_memrealtime ticks of the whole kernel, stages per item, entry tick, exit tick]
-#ifdef BIG_TIMING
-__device__ long long big_dbg[16 * 12];
-extern "C" int cvae_big_dbg_read(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(big_dbg), sizeof(big_dbg)); }
-#define BT_ON (KCH == BIG_T_KCH && NCH == BIG_T_NCH && H == BIG_T_H)
-#define BT(v) do { if (BT_ON) { __builtin_amdgcn_sched_barrier(0); v = clock64(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define BT_ON false
-#define BT(v)
-#endif
-// -DBIG_STEPTIME (with -DBIG_TIMING): s_memtime at the top of every step of ONE chunk pair (the second trip of the first item) of workgroup 0, wave 0
-#ifdef BIG_STEPTIME
-__device__ long long big_steps[128];
-extern "C" int cvae_big_steps_read(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(big_steps), sizeof(big_steps)); }
-#endif
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-// Timing experiments (WRONG results, never shipped; profiles/experiments/variant.sh -DBIG_EXP=n): what the stage loop pays for each of its
-// parts.  bit 0: no barrier in front of a stage's last step;  bit 1: no slab writes;  bit 2: no slab requests;  bit 3: no tile requests / writes;
-// bit 4: no BatchNorm sums in the epilogue;  bit 5: no column sums / partial rows;  bit 6: no output stores;  bit 7: workgroups start staggered
-#ifndef BIG_EXP
-#define BIG_EXP 0
-#endif
-#ifndef BIG_ST_AUX
-#define BIG_ST_AUX (BN ? 0 : 2)      // cache policy of the output stores: nt (2) for the input gradients — the written lines do not push the input lines the next chunks re-read out of
-                                      // L2 (counter fetch of E3's input gradient 260 -> 234 MB, E2's 318 -> 299; kernels -1 %; profiles/r05_r_e2_on_big_kernel.txt); forward outputs stay cached
-#endif
-#ifndef BIG_ALLC4
-#define BIG_ALLC4 false    // experiment builds: the same for E4's input gradient (4 lines per pixel, groups of four chunks)
-#endif
-#ifndef BIG_ALLC3
-#define BIG_ALLC3 false    // ... and E3's (2 lines per pixel)
-#endif
-#ifndef BIG_ALLC
-#define BIG_ALLC true      // false (A/B builds): E2's input gradient requests its tiles chunk by chunk like the others
-#endif
-#ifndef BIG_IMGL
-#define BIG_IMGL true      // false (A/B builds): the per-tile halo layout for the instantiations that existed before the image layout
-#endif
 
 // raw buffer descriptor over a whole tensor (gfx9 word 3: DATA_FORMAT_32): a lane whose byte offset is >= bytes is dropped by the
 // bounds check, so "store if valid" needs no branch (tensors of 2 GiB and more do not take this kernel: run_big returns -100)
@@ -80,35 +39,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t big_rsrc(const void* p, unsign
 }
 static constexpr unsigned BIG_OOB = 0x80000000u;
 
-// S16: which of the wave's 32 pixels (row-major inside the 128-pixel tile) sits behind column c of pixel block jh of a 16x16x32 fragment.  A
-// ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32): with k-block q = lane / 16 reading octet plane q & 1
-// (plane stride == 8 units mod 16) a group is conflict-free when lanes {0-3, 12-15} hold pixels at unit residues S u (S + 8) and lanes {4-11} the rest:
-// lanes 8-11 and 12-15 trade places.  8-pixel rows: a block is rows {0, 2} or {1, 3} of the wave's four (unit offsets 0..7 and 24..31 = residues 0..15).
-template <int H>
-__device__ __forceinline__ int s16_pix(int jh, int c) {
-    const int j = c < 8 ? c : (c < 12 ? c + 4 : c - 4);
-    if constexpr (Tile<H>::TW == 8) return ((j >> 3) * 2 + jh) * 8 + (j & 7);
-    else return 16 * jh + j;
-}
-// Sum x[k] (k = 0..15) over the 16 lanes of each DPP row, 45 instructions: lane L returns the total of element L & 15.  Fixed pairing, fixed order.
-__device__ __forceinline__ float row_colsum16(const float (&x)[16]) {
-    const int lane = threadIdx.x & 63;
-    const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0, b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
-    float r8[8], r4[4], r2[2];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r8[j] = (b3 ? x[j + 8] : x[j]) + dpp_mov<0x128>(b3 ? x[j] : x[j + 8]);            // partner i ^ 8 (row_ror:8)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r4[j] = (b2 ? r8[j + 4] : r8[j]) + dpp_mov<0x141>(b2 ? r8[j] : r8[j + 4]);        // partner 7 - i of the 8 (row_half_mirror: bit 2 flipped)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) r2[j] = (b1 ? r4[j + 2] : r4[j]) + dpp_mov<0x4E>(b1 ? r4[j] : r4[j + 2]);         // partner i ^ 2
-    return (b0 ? r2[1] : r2[0]) + dpp_mov<0xB1>(b0 ? r2[0] : r2[1]);                                                // partner i ^ 1
-}
-
-template <int KCH, int NCH, int H, int NT, int MT, int KB, int EPI, bool TDB, bool IMGL, bool S16 = false, bool ALLC = false>
+template <int KCH, int NCH, int H, int NT, int MT, int KB, int EPI, bool TDB, bool IMGL, bool ALLC = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv5x5_bf16_big_kernel(ConvBf16Args a, int numGroups) {
     using T = Tile<H>;
     static_assert(EPI == EPI_PLAIN || EPI == EPI_BIAS_BNSTAT, "epilogues: plain (input gradient) or bias + BatchNorm partials (forward)");
     constexpr bool BN = EPI == EPI_BIAS_BNSTAT;
+    // cache policy of the output stores: nt (2) for the input gradients — the written lines do not push the input lines the next chunks re-read out of
+    // L2 (counter fetch of E3's input gradient 260 -> 234 MB, E2's 318 -> 299; kernels -1 %; profiles/r05_r_e2_on_big_kernel.txt); forward outputs stay cached
+    constexpr int ST_AUX = BN ? 0 : 2;
     constexpr int NB = NT / 32, KS = 5, KCB = 16 * KB, OCT = KCB / 8, NY = NCH / NT;
     constexpr int PSP = Bf16Geom<H, OCT>::PSP, A_UNITS = OCT * PSP, W_UNITS = KS * KB * 2 * NT;
     constexpr int NCHUNK = KCH / KCB, NST = NCHUNK * KS, NSTEP = KS * KB;
@@ -123,7 +61,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr bool STRIP = IMGL && T::TW != H;
     constexpr int SR = STRIP ? MT * 128 / H : 0;
     static_assert(!IMGL || STRIP || (NIMG >= 1 && NIMG * H * H == MT * 128 && T::TW == H && T::HTW == HW), "image layout: the item's tiles are whole images");
-    static_assert(!STRIP || (H % SR == 0 && MT % T::TILES_X == 0 && T::TH * (MT / T::TILES_X) == SR && T::IMGS == 1 && !S16 && !ALLC && 256 / OCT == 2 * H), "strip layout");
+    static_assert(!STRIP || (H % SR == 0 && MT % T::TILES_X == 0 && T::TH * (MT / T::TILES_X) == SR && T::IMGS == 1 && !ALLC && 256 / OCT == 2 * H), "strip layout");
     constexpr int PLPX = STRIP ? (SR + 4) * HW : NIMG * HW * HW;          // halo pixels of one octet plane
     constexpr int PSPI = ((PLPX + 15 - Bf16Geom<H, OCT>::PAD) / 16) * 16 + Bf16Geom<H, OCT>::PAD;      // plane stride, == 16 / OCT (mod 16) like PSP
     constexpr int PSX = IMGL ? PSPI : PSP;                     // octet-plane stride of the layout in use
@@ -132,7 +70,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     bf16x8* lds_a = reinterpret_cast<bf16x8*>(smem_raw);       // [tile][octet][halo pixel]; IMGL: [octet][image][halo pixel]
     constexpr int TBUFS = TDB ? 2 : 1;                         // TDB: the input tiles are double-buffered too (tile buffer = chunk parity)
     bf16x8* lds_w = lds_a + TBUFS * TILE_UNITS;                // [buffer][tap][kb][half][n]
-    constexpr int NSLAB = S16 ? 3 : 2;                         // slab buffers (S16: a ring of three, see stage16)
+    constexpr int NSLAB = 2;                                   // slab buffers
     // behind the slabs: 256 dump units (4 KB) for the staging stores of units that do not exist, then (forward) the [S | Q][wave][NT] rows of the
     // BatchNorm partials (they live from an item's epilogue until the next item's first stage barrier: not in the dump area) and [NCH] bias
     [[maybe_unused]] float* red = reinterpret_cast<float*>(lds_w + NSLAB * W_UNITS + 256);
@@ -140,10 +78,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     bf16x8* const lds_patch = lds_w + NSLAB * W_UNITS + 256 + (BN ? (2 * 4 * NT + NCH) / 4 : 0);              // [wave][32 rows][8 + 1] units: the epilogue's transposing patch
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-    [[maybe_unused]] long long b0 = 0, b1 = 0, b2 = 0, tpro = 0, tstage = 0, tclose = 0, tepi = 0, nit = 0;
-    [[maybe_unused]] const long long brt0 = BT_ON ? (long long)wall_clock64() : 0;
-    BT(b0);
-    [[maybe_unused]] const long long bt_entry = b0;
 
     // item -> (tile group, channel block): XCD x (= item & 7 while gridDim.x % 8 == 0) owns the contiguous range of groups
     // [x PP, (x+1) PP) — neighbouring tiles share halo rows in ONE L2 — and walks it group by group, the NY channel blocks of a group
@@ -310,7 +244,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // chunks of the NEXT item are therefore requested together, in the item's last chunk: chunk 0 goes to LDS as before, chunks 1.. wait in registers (hreg: the 8 x 1
     // wave tile leaves 290 of them unused) and are written into the tile buffer that has just become free, one chunk later each.
     // More than four chunks (KCH > 64: several lines per pixel): the same in GROUPS of four chunks = one line — the group's last chunk requests the next group.
-    static_assert(!ALLC || (TDB && IMGL && !S16 && NCHUNK % 4 == 0 && NU <= 8), "ALLC: image layout, double-buffered tiles, chunks in groups of four");
+    static_assert(!ALLC || (TDB && IMGL && NCHUNK % 4 == 0 && NU <= 8), "ALLC: image layout, double-buffered tiles, chunks in groups of four");
     [[maybe_unused]] bf16x8 hreg[ALLC ? 3 * NU : 1];
     [[maybe_unused]] auto load_unit_to = [&](bf16x8& dst, int uu, unsigned soff) {
         const int cimg = (uu * UPX) / (H * H);
@@ -351,11 +285,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     //   R == KS - 1:       they are written in the last step behind the barrier (chunk / item boundary; the tiles are single-buffered).
     constexpr int WN = KB == 2 ? 5 : 2, WU = (WPT + WN - 1) / WN;
     static_assert(WN < NSTEP - 1, "the slab request sits in front of the stage's barrier");
-#ifdef BIG_STEPTIME
-    bool steptime_on = false, steptime_first = false;
-    int steptime_idx = 0;
-    const __amdgpu_buffer_rsrc_t rs_steps = big_rsrc(big_steps, (unsigned)sizeof(big_steps));
-#endif
     static_assert(!TDB || (KB == 1 && NU <= 12), "the unit schedule of the double-buffered tiles: 6 slots of two units");
     auto stage = [&](auto p0c, auto rc, auto tbc, int gst, unsigned wsoff, const unsigned (&tsoff)[MT], [[maybe_unused]] int ci = 0) {
         constexpr int P0 = decltype(p0c)::value, R = decltype(rc)::value, TB = decltype(tbc)::value;       // TB: tile buffer of this chunk (TDB)
@@ -365,30 +294,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int i = 0; i < NSTEP; ++i) {
             constexpr int NR = NB + MT;
             const int set = (P0 + i) & 1;
-#ifdef BIG_STEPTIME
-            if (BT_ON) {                                       // branch-free: every lane but one carries an out-of-range offset
-                __builtin_amdgcn_sched_barrier(0);
-                const long long t = clock64();
-                const unsigned so = (steptime_on && tid == 0) ? (unsigned)(steptime_idx * 8) : BIG_OOB;
-                __builtin_amdgcn_raw_buffer_store_b32((unsigned)t, rs_steps, so, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32((unsigned)(t >> 32), rs_steps, so == BIG_OOB ? BIG_OOB : so + 4u, 0, 0);
-                ++steptime_idx;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
             if (i == NSTEP - 1) {
-                if (!(BIG_EXP & 1)) __syncthreads();           // slab gst + 1 visible; every wave holds its last fragments of slab gst (and of the tiles)
+                __syncthreads();           // slab gst + 1 visible; every wave holds its last fragments of slab gst (and of the tiles)
                 if constexpr (TDB) ldf(set ^ 1, 0, RN, buf ^ 1, R == KS - 1 ? TB ^ 1 : TB);      // the next chunk's tiles were written in stages 2..4
-                else if constexpr (R == KS - 1) { if (!(BIG_EXP & 8)) store_input(); }
+                else if constexpr (R == KS - 1) store_input();
                 else ldf(set ^ 1, 0, RN, buf ^ 1);
             } else ldf(set ^ 1, i + 1, R, buf, TB);
-            if (i < WN && !(BIG_EXP & 2)) store_w(WU * i, WU * (i + 1), buf ^ 1);
-            if (i == WN && !(BIG_EXP & 4)) load_w(wsoff);
+            if (i < WN) store_w(WU * i, WU * (i + 1), buf ^ 1);
+            if (i == WN) load_w(wsoff);
             if constexpr (ALLC) {
                 // ci = this chunk's index in its group of four (a constant: the group loop is unrolled).  Last chunk of a group: the next group's 4 x NU units (the
                 // next item's first group behind the item's last chunk) are requested four per step in rows 0..3 (its first chunk first: that one is written below, in
                 // this chunk); other chunks: no request, chunk ci + 1 of the group leaves hreg for the free tile buffer.
-                if (ci == 3 && R <= 3 && (i == 3 || i == 4) && !(BIG_EXP & 8)) {
+                if (ci == 3 && R <= 3 && (i == 3 || i == 4)) {
                     const int sl = R * 2 + (i - 3);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -396,7 +314,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         if (u < 4 * NU) { if (k == 0) load_unit_to(breg[uu], uu, tsoff[0]); else load_unit_to(hreg[(k - 1) * NU + uu], uu, tsoff[0] + (unsigned)(k * KCB * 2)); }
                     }
                 }
-                if ((((R == 2 || R == 3) && (i == 3 || i == 4)) || (R == 4 && (i == 2 || i == 3))) && !(BIG_EXP & 8)) {
+                if ((((R == 2 || R == 3) && (i == 3 || i == 4)) || (R == 4 && (i == 2 || i == 3)))) {
                     const int sl = R == 4 ? 4 + (i - 2) : (R - 2) * 2 + (i - 3);
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
@@ -407,11 +325,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             } else if constexpr (TDB) {
                 // the tile stream, two units per step (the 12 requests of a chunk in ONE step held the wave at the texture unit for 800 cycles, and
                 // their 12 LDS writes + a second barrier closed every chunk: 1.7 k of a 16.4 k-cycle chunk, profiles/r05_f_big_steptime.txt)
-                if (R <= 2 && (i == 3 || i == 4) && !(BIG_EXP & 8)) { const int sl = R * 2 + (i - 3); load_unit(2 * sl, tsoff); load_unit(2 * sl + 1, tsoff); }
-                if ((R == 2 || R == 3) && (i == 3 || i == 4) && !(BIG_EXP & 8)) { const int sl = (R - 2) * 2 + (i - 3); store_unit(2 * sl, TB ^ 1); store_unit(2 * sl + 1, TB ^ 1); }
-                if (R == 4 && (i == 2 || i == 3) && !(BIG_EXP & 8)) { const int sl = 4 + (i - 2); store_unit(2 * sl, TB ^ 1); store_unit(2 * sl + 1, TB ^ 1); }
+                if (R <= 2 && (i == 3 || i == 4)) { const int sl = R * 2 + (i - 3); load_unit(2 * sl, tsoff); load_unit(2 * sl + 1, tsoff); }
+                if ((R == 2 || R == 3) && (i == 3 || i == 4)) { const int sl = (R - 2) * 2 + (i - 3); store_unit(2 * sl, TB ^ 1); store_unit(2 * sl + 1, TB ^ 1); }
+                if (R == 4 && (i == 2 || i == 3)) { const int sl = 4 + (i - 2); store_unit(2 * sl, TB ^ 1); store_unit(2 * sl + 1, TB ^ 1); }
             } else {
-                if (i == WN + 1 && R == KS - 3 && !(BIG_EXP & 8)) load_input(tsoff);
+                if (i == WN + 1 && R == KS - 3) load_input(tsoff);
             }
 #pragma unroll
             for (int tl = 0; tl < MT; ++tl)
@@ -429,129 +347,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
     };
 
-    // ---- S16 (round 5): the same tiles, slabs and staging on v_mfma_f32_16x16x32_bf16 — the chip holds a higher clock on that shape under its power
-    // limit (profiles/r05_l_mfma_shape_probe.txt: +14 % sustained).  k = 32 of one MFMA = TWO TAPS x the chunk's 16 channels: lane (c, q) of a
-    // fragment reads the unit of tap A (q < 2) or tap B (q >= 2), octet q & 1 — the LDS images stay as they are, only the lane -> address map changes.
-    // The wave tile is 2 MT pixel blocks (16 pixels: rows 16 jh .. + 15 of the wave's 32 in tile tl) x 2 NB channel blocks of 16; acc16[j][i], lane
-    // (c, q) = pixel c of block j, channels 16 i + 4 q .. + 3.  25 taps of a (chunk, 5 kernel rows) = 12.5 steps: a chunk PAIR is 25 steps — stage
-    // g = 5 h + r (h = chunk of the pair, r = kernel row) runs the steps whose first tap lies in its slab: three (taps 0|1, 2|3, 4|next slab's 0) when g
-    // is even, two (1|2, 3|4) when odd; the crossing step reads slab g + 1 and (r = 4) the next chunk's tiles, both visible behind the barrier that
-    // stands in front of every stage's last step anyway.
-    constexpr int NJ = S16 ? 2 * MT : 1, NI = S16 ? 2 * NB : 1;
-    [[maybe_unused]] f32x4 acc16[NJ][NI];
-    [[maybe_unused]] bf16x8 wf16[2][NI], xf16[2][NJ];          // two fragment sets, alternating per step
-    [[maybe_unused]] const int c16 = lane & 15, q4 = lane >> 4;
-    [[maybe_unused]] const bool hiq = q4 >= 2;
-    [[maybe_unused]] int xb16[2], wb16 = 0;
-    if constexpr (S16) {
-        static_assert(!S16 || (TDB && IMGL && KB == 1 && NCHUNK % 2 == 0 && NT % 64 == 0), "S16: image layout, double-buffered tiles, 16-channel chunks");
-#pragma unroll
-        for (int jh = 0; jh < 2; ++jh) {
-            const int mj = wave * 32 + s16_pix<H>(jh, c16), pi = mj / (T::TH * T::TW), pr = mj % (T::TH * T::TW);
-            xb16[jh] = (q4 & 1) * PSX + pi * T::HPI + (pr / T::TW) * T::HTW + (pr % T::TW);
-        }
-        wb16 = (q4 & 1) * NT + c16;
-    }
-    // Fragment reads = ONE lane pointer per KIND of tap pair + a compile-time offset (the ds_read's immediate): the lanes of tap B (q >= 2) sit a
-    // constant distance D behind tap A's — kind 0: the next column of the same kernel row (D = 1 unit; weights: 2 NT), kind 1: tap 4 of a row | tap 0 of
-    // the next row (D = HTW - 4), kind 2: tap (4, 4) of a chunk | tap (0, 0) of the next chunk in the other tile buffer (D = TILE_UNITS - 4 HTW - 4).
-    // (Per-step lane pointers with both taps' offsets folded in are 50 loop invariants: hoisted, spilled, and every reload inside the loop is followed
-    // by s_waitcnt vmcnt(0) — behind the slab and tile requests in flight: 5.1 k instead of 2.8 k cycles per stage.)
-    [[maybe_unused]] int xbk[3][2], wbh = 0;
-    if constexpr (S16) {
-#pragma unroll
-        for (int jh = 0; jh < 2; ++jh) {
-            xbk[0][jh] = xb16[jh] + (hiq ? 1 : 0);
-            xbk[1][jh] = xb16[jh] + (hiq ? T::HTW - 4 : 0);
-            xbk[2][jh] = xb16[jh] + (hiq ? TILE_UNITS - 4 * T::HTW - 4 : 0);
-        }
-        wbh = wb16 + (hiq ? 2 * NT : 0);
-    }
-    // weights of a tap pair (sA, sA + 1) inside ring slot `slot`
-    auto ldw16 = [&](int set, int sA, int slot) {
-        const bf16x8* wp = lds_w + wbh + slot * W_UNITS;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) wf16[set][i] = wp[sA * 2 * NT + 16 * i];
-    };
-    // weights of the crossing pair: tap 4 of ring slot b0 | tap 0 of ring slot b1
-    auto ldw16x = [&](int set, int b0, int b1) {
-        const bf16x8* wp = lds_w + wb16 + (hiq ? b1 * W_UNITS : b0 * W_UNITS + 8 * NT);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) wf16[set][i] = wp[16 * i];
-    };
-    // pixel fragments: kind of the pair, cA = tap A's compile-time unit offset (tile buffer, kernel row, column)
-    auto ldx16 = [&](int set, int kind, int cA) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int tl = j >> 1, toff = (tl * 128 / (H * H)) * (HW * HW) + ((tl * 128 % (H * H)) / H) * HW;
-            xf16[set][j] = (lds_a + xbk[kind][j & 1])[cA + toff];
-        }
-    };
-    // One stage on the 16x16x32 shape.  HC = chunk of the pair (= tile buffer), R = kernel row, P0 = fragment set of its first step; sb = ring slot of
-    // the stage's slab (THREE slab buffers: g in sb, g + 1 in sb + 1, and slab g + 2 — travelling in wreg — is written into sb + 2 during this stage).
-    //   step 0: fragments of step 1 (own slab) are read, nothing else;
-    //   step 1: BARRIER in front of it — the crossing step's fragments (THREE: tap 4 | tap 0 of slab g + 1, at R = 4 of the next chunk's tiles) or the next
-    //           stage's first fragments (two-step stage) lie behind it; then slab g + 2 goes from wreg into ring slot sb + 2 (its previous tenant g - 1 was
-    //           last read right behind the PREVIOUS stage's barrier: every wave is past that) and slab g + 3 (at wsoff) is requested;
-    //   step 2 (THREE): the next stage's first fragments.
-    //   Tile units of the next chunk: requested two per step at (R, step) = (0,1) (1,0) (1,1) (2,0), written two stages later at (2,1) (3,0) (3,1) (4,0) —
-    //   all in front of stage 4's barrier, behind which the crossing step reads them.
-    auto stage16 = [&](auto hc, auto rc, auto p0c, int sb, unsigned wsoff, const unsigned (&tsoff)[MT]) {
-        constexpr int HC = decltype(hc)::value, R = decltype(rc)::value, P0 = decltype(p0c)::value, TB = HC;
-        constexpr bool THREE = ((HC * KS + R) & 1) == 0;
-        constexpr int NSTP = THREE ? 3 : 2;
-        constexpr int RN = R == KS - 1 ? 0 : R + 1, TBN = R == KS - 1 ? TB ^ 1 : TB;
-        const int b0 = sb, b1 = sb == 2 ? 0 : sb + 1, b2 = b1 == 2 ? 0 : b1 + 1;
-#pragma unroll
-        for (int i = 0; i < NSTP; ++i) {
-            const int set = (P0 + i) & 1;
-#ifdef BIG_STEPTIME
-            if (BT_ON) {
-                __builtin_amdgcn_sched_barrier(0);
-                const long long t = clock64();
-                const unsigned so = (steptime_on && tid == 0) ? (unsigned)(steptime_idx * 8) : BIG_OOB;
-                __builtin_amdgcn_raw_buffer_store_b32((unsigned)t, rs_steps, so, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32((unsigned)(t >> 32), rs_steps, so == BIG_OOB ? BIG_OOB : so + 4u, 0, 0);
-                ++steptime_idx;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
-            // the NEXT step's taps: step 0 -> own slab (THREE: 2|3, else 3|4); step 1 -> behind the barrier: THREE: 4 | next slab's 0, else the next stage's
-            // first step (0|1 of slab g + 1); step 2 (THREE) -> the next stage's first step (1|2 of slab g + 1)
-            if (i == 0) { ldw16(set ^ 1, THREE ? 2 : 3, b0); ldx16(set ^ 1, 0, TB * TILE_UNITS + R * T::HTW + (THREE ? 2 : 3)); }
-            if (i == 1) {
-                if (!(BIG_EXP & 1)) __syncthreads();
-                if constexpr (THREE) { ldw16x(set ^ 1, b0, b1); ldx16(set ^ 1, R == KS - 1 ? 2 : 1, TB * TILE_UNITS + R * T::HTW + 4); }
-                else { ldw16(set ^ 1, 0, b1); ldx16(set ^ 1, 0, TBN * TILE_UNITS + RN * T::HTW); }
-                if (!(BIG_EXP & 2)) store_w(0, WPT, b2);
-                if (!(BIG_EXP & 4)) load_w(wsoff);
-            }
-            if (i == 2) { ldw16(set ^ 1, 1, b1); ldx16(set ^ 1, 0, TBN * TILE_UNITS + RN * T::HTW + 1); }
-            if (!(BIG_EXP & 8)) {
-                constexpr int RQ = R == 0 ? 0 : (R == 1 ? 1 : 3);             // first request slot of row R (rows 0..2), first write slot of row R + 2
-                if ((R == 0 && i == 1) || (R == 1 && i <= 1) || (R == 2 && i == 0)) { const int sl = RQ + (R == 1 ? i : 0); load_unit(2 * sl, tsoff); load_unit(2 * sl + 1, tsoff); }
-                if ((R == 2 && i == 1) || (R == 3 && i <= 1) || (R == 4 && i == 0)) {
-                    const int sl = (R == 2 ? 0 : (R == 3 ? 1 : 3)) + (R == 3 ? i : 0);
-                    store_unit(2 * sl, TB ^ 1); store_unit(2 * sl + 1, TB ^ 1);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-                for (int ii = 0; ii < NI; ++ii)                // weights as the A operand: D[channel][pixel]
-                    acc16[j][ii] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf16[set][ii], xf16[set][j], acc16[j][ii], 0, 0, 0);
-            }
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {                     // pinned: a fragment read per four MFMAs (LDS at half its rate), the step's writes / requests between
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x220, 2, 0);      // (one per gap stretches wreg's live range: 92 spills)
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
     // Forward: the finished item's per-wave rows [S | Q][wave][NT] -> ONE (sum, M2) partial per channel.  Deferred: a barrier of its own in the
     // epilogue waited for the slowest wave's store issue (8.5 k of the 16 k-cycle epilogue, profiles/r05_d_big_epilogue_ablation.txt); the rows are
     // combined behind the first stage barrier of the NEXT item instead (or behind one barrier at the very end), no branch: without a finished item
@@ -559,7 +354,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     [[maybe_unused]] int pd_grp = 0, pd_n0 = 0, pd_cnt = 0;
     [[maybe_unused]] bool have_pd = false;
     auto bn_combine = [&]() {
-        if constexpr (BN && !(BIG_EXP & 32)) {
+        if constexpr (BN) {
             const int c = tid < NT ? tid : 0;
             float S = 0.f, Q = 0.f;
 #pragma unroll
@@ -574,7 +369,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                                   ok ? o + (unsigned)(numGroups * NCH) * 4u : BIG_OOB, 0, 0);
         }
     };
-    if (BIG_EXP & 128) { for (int k = 0; k < ((int)(blockIdx.x >> 3) & 7); ++k) __builtin_amdgcn_s_sleep(30); }      // 8 phases, ~1.9 k cycles apart
     // ---- prologue: the first item's tiles and slab 0 into LDS, its slab 1 on the way ----
     if constexpr (BN) { for (int c = tid; c < NCH; c += 256) lds_bias[c] = a.bias[c]; }
     if constexpr (IMGL) {                                      // the zero padding around every image, once: staging never writes there
@@ -599,39 +393,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     store_input();
     store_w(0, WPT, 0);
     load_w(slab_soff(cur.n0, 1));
-    if constexpr (S16) {                                       // ring slots 0 and 1 filled, slab 2 on the way (stage 0 writes it into slot 2)
-        store_w(0, WPT, 1);
-        load_w(slab_soff(cur.n0, 2));
-        __syncthreads();
-        ldw16(0, 0, 0);
-        ldx16(0, 0, 0);
-    } else {
     __syncthreads();
     ldf(0, 0, 0, 0);
-    }
-    BT(b1);
-#ifdef BIG_TIMING
-    if (BT_ON) tpro = b1 - bt_entry;
-#endif
 
     int gst = 0;
-    [[maybe_unused]] int sb16 = 0;                             // S16: ring slot of the current stage's slab
-#ifdef BIG_STEPTIME
-    steptime_first = true;
-#endif
     for (;;) {
         int itn = it + G, grpn, n0n;
         decode(itn, grpn, n0n);
         const bool have_next = itn < numItems && grpn < numGroups;
-        if constexpr (S16) {
-#pragma unroll
-            for (int ii = 0; ii < NI; ++ii) {
-                f32x4 bq4 = f32x4{0.f, 0.f, 0.f, 0.f};
-                if constexpr (BN) bq4 = *reinterpret_cast<const f32x4*>(lds_bias + cur.n0 + 16 * ii + 4 * q4);
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc16[j][ii] = bq4;
-            }
-        } else
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             f32x4 bq[4];
@@ -645,7 +414,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[tl][nb][v] = bq[v >> 2][v & 3];
         }
-        BT(b1);
         // Two chunks per trip (the fragment sets alternate per step, a chunk has KS x NSTEP steps), kernel rows unrolled.  Slab st + 1 is
         // travelling in wreg when stage st starts (requested by stage st - 1, by the previous item's last stage, or by the prologue).
         static_assert(NCHUNK % 2 == 0, "chunks are walked in pairs");
@@ -654,10 +422,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int g2 = 0; g2 < GP; ++g2) {
             const int cp = cq + 2 * g2;
-#ifdef BIG_STEPTIME
-            steptime_on = BT_ON && blockIdx.x == 0 && steptime_first && cp == (NCHUNK >= 4 ? 2 : 0);
-            steptime_idx = 0;
-#endif
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int cc = cp + h;
@@ -671,33 +435,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                     for (int tl = 0; tl < MT; ++tl) ts[tl] = (unsigned)nx.ibase[tl];
                 }
-                [[maybe_unused]] long long b3 = 0, b4 = 0;
-                BT(b2);
 #pragma unroll
                 for (int r = 0; r < KS; ++r) {
-                    const int s2 = cc * KS + r + (S16 ? 3 : 2);    // the slab requested in this stage: two (S16: three) stages ahead, across the item boundary
+                    const int s2 = cc * KS + r + 2;                // the slab requested in this stage: two stages ahead, across the item boundary
                     const bool own = s2 < NST;
                     const unsigned wsoff = slab_soff(own || !have_next ? cur.n0 : n0n, own ? s2 : (have_next ? s2 - NST : 0));
                     constexpr int P0v[2][5] = {{0, NSTEP & 1, 0, NSTEP & 1, 0}, {NSTEP & 1, 0, NSTEP & 1, 0, NSTEP & 1}};
-                    if constexpr (S16) {
-                        // fragment set of a stage's first step = parity of the steps before it in the pair (3, 2, 3, 2 ... steps per stage)
-                        constexpr int P16[2][5] = {{0, 1, 1, 0, 0}, {1, 1, 0, 0, 1}};
-                        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-                        if (h == 0) {
-                            if (r == 0) stage16(I0{}, std::integral_constant<int, 0>{}, std::integral_constant<int, P16[0][0]>{}, sb16, wsoff, ts);
-                            if (r == 1) stage16(I0{}, std::integral_constant<int, 1>{}, std::integral_constant<int, P16[0][1]>{}, sb16, wsoff, ts);
-                            if (r == 2) stage16(I0{}, std::integral_constant<int, 2>{}, std::integral_constant<int, P16[0][2]>{}, sb16, wsoff, ts);
-                            if (r == 3) stage16(I0{}, std::integral_constant<int, 3>{}, std::integral_constant<int, P16[0][3]>{}, sb16, wsoff, ts);
-                            if (r == 4) stage16(I0{}, std::integral_constant<int, 4>{}, std::integral_constant<int, P16[0][4]>{}, sb16, wsoff, ts);
-                        } else {
-                            if (r == 0) stage16(I1{}, std::integral_constant<int, 0>{}, std::integral_constant<int, P16[1][0]>{}, sb16, wsoff, ts);
-                            if (r == 1) stage16(I1{}, std::integral_constant<int, 1>{}, std::integral_constant<int, P16[1][1]>{}, sb16, wsoff, ts);
-                            if (r == 2) stage16(I1{}, std::integral_constant<int, 2>{}, std::integral_constant<int, P16[1][2]>{}, sb16, wsoff, ts);
-                            if (r == 3) stage16(I1{}, std::integral_constant<int, 3>{}, std::integral_constant<int, P16[1][3]>{}, sb16, wsoff, ts);
-                            if (r == 4) stage16(I1{}, std::integral_constant<int, 4>{}, std::integral_constant<int, P16[1][4]>{}, sb16, wsoff, ts);
-                        }
-                        sb16 = sb16 == 2 ? 0 : sb16 + 1;
-                    } else
                     if (h == 0) {
                         if (r == 0) stage(std::integral_constant<int, P0v[0][0]>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, gst, wsoff, ts, 2 * g2 + h);
                         if (r == 1) stage(std::integral_constant<int, P0v[0][1]>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, gst, wsoff, ts, 2 * g2 + h);
@@ -714,25 +457,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     ++gst;
                     if (BN && h == 0 && r == 0 && cp == 0) bn_combine();      // behind stage 0's barrier: the previous item's rows are complete
                 }
-                BT(b3);
                 if constexpr (!TDB) {
                     __syncthreads();                           // chunk / item boundary: the new tiles are visible behind this barrier
                     if (!lastc) ldf(h == 0 ? (NSTEP & 1) : 0, 0, 0, gst & 1);
                 }
-                BT(b4);
-#ifdef BIG_TIMING
-                if (BT_ON) { tstage += b3 - b2; tclose += b4 - b3; }
-#endif
-            }
-            if constexpr (S16) {                               // a chunk pair is 25 steps: its last step left the next first fragments in set 1 — every pair starts from set 0
-#pragma unroll
-                for (int ii = 0; ii < NI; ++ii) wf16[0][ii] = wf16[1][ii];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) xf16[0][j] = xf16[1][j];
             }
         }
         }
-        BT(b1);
 
         // ---- epilogue: lane = pixel m of each tile, element v of block nb = channel 32 nb + (v & 3) + 8 (v >> 2) + 4 lh (channel-major accumulators);
         // u[k] = channels 16 k + 8 lh .. + 7 of a 32-channel block.  Forward: ONE BatchNorm partial per item and channel — (sum, M2 about the
@@ -749,88 +480,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // layout a lane stores 16 bytes of ITS pixel: 64 lines per instruction, and the 16-tile epilogue was bound by exactly that (9.5 k cycles for
         // 128 KB per CU, profiles/r05_b_big_timing_persistent.txt).  A wave's LDS operations execute in order: no wait between the patch's writes
         // and reads.  Forward: the BatchNorm sums of the pair's 2 x 16 channels per lane are taken from the same register copies.
-        if constexpr (S16) {
-            // 16x16 accumulator tiles: lane (c, q) holds channels 16 i + 4 q .. + 3 of pixel c of block j.  64 channels (four channel blocks = one 128-byte
-            // line per pixel) at a time, block by block, through the wave's patch [16 pixel rows][8 + 1 units]: the lane writes its 8 bytes of every
-            // channel block into row c (conflict-free ds_write_b64), reads back unit lane % 8 of rows lane / 8 and lane / 8 + 8, and 8 consecutive lanes
-            // store one pixel's whole line.  Forward: per-lane sums of the 16 (channel block, e) values over the wave's blocks, then row_colsum16 over
-            // the 16 pixel lanes of each DPP row: lane (c, q) ends with channel 64 hp + 16 (c >> 2) + 4 q + (c & 3) — 64 lanes, 64 channels.
-            constexpr int NPASS = NT / 64;
-            // the epilogue's lane tables are rebuilt here from an opaque copy of the lane id: as loop invariants they would be hoisted over the stage loop,
-            // where the register file has no room for them (spilled, and every reload inside the loop waits for vmcnt(0))
-            int lz = lane;
-            asm volatile("" : "+v"(lz));
-            const int cz = lz & 15, qz = lz >> 4;
-            char* const pw = reinterpret_cast<char*>(lds_patch + wave * (16 * 9)) + cz * 144 + 8 * qz;
-            const bf16x8* const pr = lds_patch + wave * (16 * 9) + (lz >> 3) * 9 + (lz & 7);
-            const unsigned pcol16 = (unsigned)(lz & 7) * 16u;
-            unsigned orow16[2][2];                             // byte offset (from the tile's first pixel) of the pixel rows lane / 8 and lane / 8 + 8 of block jh
-#pragma unroll
-            for (int jh = 0; jh < 2; ++jh)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int mr = wave * 32 + s16_pix<H>(jh, (lz >> 3) + 8 * k), ir = mr / (T::TH * T::TW), rr = mr % (T::TH * T::TW);
-                    orow16[jh][k] = (unsigned)(((ir * H + rr / T::TW) * H + rr % T::TW) * NCH * 2);
-                }
-            if constexpr (BN) {
-                if (!allv) {
-#pragma unroll
-                    for (int tl = 0; tl < MT; ++tl)
-                        if (!validv[tl]) {
-#pragma unroll
-                            for (int jh = 0; jh < 2; ++jh)
-#pragma unroll
-                                for (int ii = 0; ii < NI; ++ii) acc16[2 * tl + jh][ii] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        }
-                }
-            }
-#pragma unroll
-            for (int hp = 0; hp < NPASS; ++hp) {
-                [[maybe_unused]] float sv[16], qv[16];
-                if constexpr (BN) {
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) { sv[k] = 0.f; qv[k] = 0.f; }
-                }
-                bf16x8 rows[2];
-                unsigned rbase = BIG_OOB;
-                auto flush16 = [&](int jhp) {
-#pragma unroll
-                    for (int k = 0; k < 2; ++k)
-                        if (!(BIG_EXP & 64)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, rows[k]), rs_out, rbase == BIG_OOB ? BIG_OOB : rbase + orow16[jhp][k], 0, 0);
-                };
-#pragma unroll
-                for (int tl = 0; tl < MT; ++tl)
-#pragma unroll
-                    for (int jh = 0; jh < 2; ++jh) {
-                        const int j = 2 * tl + jh;
-#pragma unroll
-                        for (int il = 0; il < 4; ++il) {
-                            const int ii = hp * 4 + il;
-                            asm volatile("" : "+a"(acc16[j][ii]));      // one tile at a time out of the AGPRs (see the 32x32 epilogue)
-                            const f32x4 cv = acc16[j][ii];
-                            u32x2v pk;
-                            pk[0] = pack_bf16x2(cv[0], cv[1]); pk[1] = pack_bf16x2(cv[2], cv[3]);
-                            *reinterpret_cast<u32x2v*>(pw + 32 * il) = pk;
-                            if constexpr (BN && !(BIG_EXP & 16)) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) { sv[il * 4 + e] += cv[e]; qv[il * 4 + e] = __builtin_fmaf(cv[e], cv[e], qv[il * 4 + e]); }
-                            }
-                        }
-                        asm volatile("" ::: "memory");
-                        if (j > 0) flush16(jh ^ 1);
-#pragma unroll
-                        for (int k = 0; k < 2; ++k) rows[k] = pr[k * 8 * 9];
-                        rbase = validv[tl] ? ((unsigned)(cur.ibase[tl] / (KCH * 2)) * NCH + cur.n0 + hp * 64) * 2u + pcol16 : BIG_OOB;
-                        asm volatile("" ::: "memory");
-                    }
-                if constexpr (BN && !(BIG_EXP & 32)) {
-                    const float S = row_colsum16(sv), Q = row_colsum16(qv);
-                    const int ch = hp * 64 + 16 * (cz >> 2) + 4 * qz + (cz & 3);
-                    red[(0 * 4 + wave) * NT + ch] = S; red[(1 * 4 + wave) * NT + ch] = Q;
-                }
-                flush16(1);
-            }
-        } else {
         if constexpr (BN) {
             // ragged end only (wave-uniform, rare): the accumulators of tiles that do not exist hold the bias — zeroed, so that the sums below need no mask
             if (!allv) {
@@ -858,7 +507,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             auto flush_rows = [&]() {
 #pragma unroll
                 for (int k = 0; k < PIT; ++k)
-                    if (!(BIG_EXP & 64)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, rows[k]), rs_out, rbase == BIG_OOB ? BIG_OOB : rbase + orow[k], 0, BIG_ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, rows[k]), rs_out, rbase == BIG_OOB ? BIG_OOB : rbase + orow[k], 0, ST_AUX);
             };
 #pragma unroll
             for (int tl = 0; tl < MT; ++tl) {
@@ -873,7 +522,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     cm_pack_units(c, u);
                     patch_w[4 * j] = u[0];
                     patch_w[4 * j + 2] = u[1];
-                    if constexpr (BN && !(BIG_EXP & 16)) {
+                    if constexpr (BN) {
 #pragma unroll
                         for (int v = 0; v < 8; ++v) {
                             const f32x2 x = f32x2{c[2 * v], c[2 * v + 1]};
@@ -889,7 +538,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 rbase = validv[tl] ? ((unsigned)(cur.ibase[tl] / (KCH * 2)) * NCH + cur.n0 + hp * HB * 32) * 2u + pcol : BIG_OOB;
                 asm volatile("" ::: "memory");
             }
-            if constexpr (BN && !(BIG_EXP & 32)) {
+            if constexpr (BN) {
 #pragma unroll
                 for (int j = 0; j < HB; ++j) {
                     const int nb = hp * HB + j;
@@ -903,20 +552,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             flush_rows();                                      // the pair's last tile (behind the column sums: its patch reads have long landed)
         }
-        }
         if constexpr (BN) {                                    // the four waves' rows meet behind the NEXT barrier the workgroup passes anyway (bn_combine)
             pd_cnt = 0;
 #pragma unroll
             for (int tl = 0; tl < MT; ++tl) { int ni = a.B - cur.img0[tl]; ni = ni < 0 ? 0 : (ni > T::IMGS ? T::IMGS : ni); pd_cnt += ni * T::TH * T::TW; }
             pd_grp = cur.grp; pd_n0 = cur.n0; have_pd = true;
         }
-        BT(b2);
-#ifdef BIG_TIMING
-        if (BT_ON) { tepi += b2 - b1; ++nit; }
-#endif
-#ifdef BIG_STEPTIME
-        steptime_first = false;
-#endif
         if (!have_next) break;
         cur = setup(grpn, n0n); it = itn;
         set_voff(cur);                                         // recomputed (not kept) across the epilogue: ~100 VALU per item for 12-16 registers
@@ -924,18 +565,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                                                // TDB: the last stage's last step has requested them already (tile buffer 0, kernel row 0)
     }
     if constexpr (BN) { __syncthreads(); bn_combine(); }       // the last item's rows
-#ifdef BIG_TIMING
-    if (BT_ON && (blockIdx.x & 15) == 0 && blockIdx.x < 256 && tid == 0) {
-        __builtin_amdgcn_sched_barrier(0);
-        const long long e = clock64();
-        long long* o = big_dbg + (blockIdx.x >> 4) * 12;
-        o[0] = nit; o[1] = tpro; o[2] = tstage; o[3] = tclose; o[4] = tepi; o[5] = e - bt_entry;
-        o[6] = (long long)wall_clock64() - brt0; o[7] = NST; o[8] = brt0; o[9] = (long long)wall_clock64();
-    }
-#endif
 }
 
-template <int KCH, int NCH, int H, int NT, int MT, int KB, int EPI, bool IMGL = false, bool S16 = false, bool ALLC = false>
+template <int KCH, int NCH, int H, int NT, int MT, int KB, int EPI, bool IMGL = false, bool ALLC = false>
 static int run_big(const ConvBf16Args& a, hipStream_t st) {
     // (8 x 1 wave tile, E2's input gradient: 8 accumulator tiles = 256 registers would let TWO workgroups share a CU with single-buffered tiles — measured:
     //  194.0 us against 192.1 for one workgroup with double-buffered tiles, step level; profiles/r05_r_e2_on_big_kernel.txt)
@@ -946,12 +578,12 @@ static int run_big(const ConvBf16Args& a, hipStream_t st) {
     constexpr int NIMG = MT * 128 / (H * H), PAD = Bf16Geom<H, OCT>::PAD;
     constexpr int PLPX = (IMGL && T::TW != H) ? (MT * 128 / H + 4) * (H + 4) : NIMG * (H + 4) * (H + 4);      // strip layout: SR + 4 rows of H + 4
     constexpr int TILE_UNITS = IMGL ? OCT * (((PLPX + 15 - PAD) / 16) * 16 + PAD) : MT * OCT * Bf16Geom<H, OCT>::PSP;
-    constexpr int SMEM = ((TDB ? 2 : 1) * TILE_UNITS + (S16 ? 3 : 2) * 5 * KB * 2 * NT + 256 + (S16 ? 4 * 16 * 9 : 4 * 32 * 9)) * 16 + (EPI == EPI_BIAS_BNSTAT ? (2 * 4 * NT + NCH) * 4 : 0);
+    constexpr int SMEM = ((TDB ? 2 : 1) * TILE_UNITS + 2 * 5 * KB * 2 * NT + 256 + 4 * 32 * 9) * 16 + (EPI == EPI_BIAS_BNSTAT ? (2 * 4 * NT + NCH) * 4 : 0);
     static_assert(SMEM <= 160 * 1024, "LDS");
     // 32-bit byte offsets and buffer descriptors inside: larger tensors take the per-tile kernels (size_t addressing)
     if ((size_t)a.B * H * H * KCH * 2 >= (1ull << 31) || (size_t)a.B * H * H * NCH * 2 >= (1ull << 31)) return -100;
     if (g_conv_dry) return 0;
-    auto kern = conv5x5_bf16_big_kernel<KCH, NCH, H, NT, MT, KB, EPI, TDB, IMGL, S16, ALLC>;
+    auto kern = conv5x5_bf16_big_kernel<KCH, NCH, H, NT, MT, KB, EPI, TDB, IMGL, ALLC>;
     static DeviceOnce once;
     { int rc = cvae_grant_lds(once, reinterpret_cast<const void*>(kern), SMEM); if (rc) return rc; }
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG, numGroups = cdiv(numTiles, MT);
@@ -970,37 +602,27 @@ static int run_big(const ConvBf16Args& a, hipStream_t st) {
     return 0;
 }
 
-// Which layers this file serves, by mask bit: input gradients — bit 0 = E4 (256 -> 128, 4 x 4 wave tile), bit 1 = E3 (128 -> 64, 8 x 2), bit 2 = E2 at 64 x 64 (64 -> 32:
-// an image-high item on an 8 x 1 wave tile, 9 fragment reads per 8 MFMAs where the per-tile kernel reads 12: 192 vs 209 us); forward (bias + ONE BatchNorm partial per
-// item of conv_bf16_big_tiles(..) tiles — the kernel that ran tells launch_bn_fwd_finalize) — bit 0 = E3 (64 -> 128), bit 1 = E4 (128 -> 256), both 4 x 4, bit 2 = E2 at
-// 64 x 64 (32 -> 64 as two 32-channel halves of an image-high item, 8 x 1: 196 vs 209 us on the two-workgroup persistent kernel; as ONE 8 x 2 item it lost, 244 us:
-// its 16-tile BatchNorm epilogue was half of a 10-stage item, profiles/r05_k_big_image_layout.txt).
-// CVAE_BIG_S16 (experiment): the instantiations built on v_mfma_f32_16x16x32_bf16 (S16)
-static bool big_s16() { static const bool on = [] { const char* e = getenv("CVAE_BIG_S16"); return e && atoi(e) != 0; }(); return on; }
-bool conv_bf16_big_has(int layer, int width, bool dgrad, int mask) {
-    if (width != 64 && width != 128) return false;
-    if (dgrad) return (layer == 3 && (mask & 1)) || (layer == 2 && (mask & 2)) || (layer == 1 && (mask & 4));
-    return (layer == 2 && (mask & 1)) || (layer == 3 && (mask & 2)) || (layer == 1 && (mask & 4));
-}
+// The layers this file serves, at both frame sizes.  Input gradients: E4 (256 -> 128, 4 x 4 wave tile), E3 (128 -> 64, 8 x 2), E2 (64 -> 32: an image-high item
+// on an 8 x 1 wave tile, 9 fragment reads per 8 MFMAs where the per-tile kernel reads 12: 192 vs 209 us at 64 x 64).  Forward (bias + ONE BatchNorm partial per
+// item of conv_bf16_big_tiles(..) tiles — the kernel that ran tells launch_bn_fwd_finalize): E3 (64 -> 128), E4 (128 -> 256), both 4 x 4, E2 (32 -> 64 as two
+// 32-channel halves of an image-high item, 8 x 1: 196 vs 209 us on the two-workgroup persistent kernel at 64 x 64; as ONE 8 x 2 item it lost, 244 us: its 16-tile
+// BatchNorm epilogue was half of a 10-stage item, profiles/r05_k_big_image_layout.txt).
 int conv_bf16_big_tiles(int layer, int width, bool dgrad) { (void)width; return ((dgrad && layer == 2) || (!dgrad && layer == 1)) ? 8 : 4; }
 // returns -100 when the layer has no instantiation (or the tensors are too large for its 32-bit offsets)
-int launch_conv_bf16_big(int layer, int width, bool dgrad, int mask, const ConvBf16Args& a, hipStream_t st) {
-    if (!conv_bf16_big_has(layer, width, dgrad, mask)) return -100;
+int launch_conv_bf16_big(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st) {
     if (dgrad) {
-        if (width == 64 && layer == 3 && big_s16()) return run_big<256, 128, 8, 128, 4, 1, EPI_PLAIN, true, true>(a, st);
-        if (width == 64 && layer == 3) return run_big<256, 128, 8, 128, 4, 1, EPI_PLAIN, BIG_IMGL, false, BIG_ALLC4>(a, st);
-        if (width == 64 && layer == 2) return run_big<128, 64, 16, 64, 8, 1, EPI_PLAIN, BIG_IMGL, false, BIG_ALLC3>(a, st);
-        if (width == 64 && layer == 1) return run_big<64, 32, 32, 32, 8, 1, EPI_PLAIN, true, false, BIG_ALLC>(a, st);      // E2: image-high item, 8 x 1 wave tile, whole lines fetched once
-        if (width == 128 && layer == 3) return run_big<256, 128, 16, 128, 4, 1, EPI_PLAIN, BIG_IMGL>(a, st);
-        if (width == 128 && layer == 2) return run_big<128, 64, 32, 64, 8, 1, EPI_PLAIN, BIG_IMGL>(a, st);
+        if (width == 64 && layer == 3) return run_big<256, 128, 8, 128, 4, 1, EPI_PLAIN, true>(a, st);
+        if (width == 64 && layer == 2) return run_big<128, 64, 16, 64, 8, 1, EPI_PLAIN, true>(a, st);
+        if (width == 64 && layer == 1) return run_big<64, 32, 32, 32, 8, 1, EPI_PLAIN, true, true>(a, st);      // E2: image-high item, 8 x 1 wave tile, whole lines fetched once
+        if (width == 128 && layer == 3) return run_big<256, 128, 16, 128, 4, 1, EPI_PLAIN, true>(a, st);
+        if (width == 128 && layer == 2) return run_big<128, 64, 32, 64, 8, 1, EPI_PLAIN, true>(a, st);
         if (width == 128 && layer == 1) return run_big<64, 32, 64, 32, 8, 1, EPI_PLAIN, true>(a, st);       // 16-row strips of the 64-row image, 8 x 1
     } else {
         if (width == 64 && layer == 1) return run_big<32, 64, 32, 32, 8, 1, EPI_BIAS_BNSTAT, true>(a, st);      // 8 x 1 (two channel halves per image); 8 x 2: 244 us
-        if (width == 64 && layer == 2) return run_big<64, 128, 16, 128, 4, 1, EPI_BIAS_BNSTAT, BIG_IMGL>(a, st);
-        if (width == 64 && layer == 3 && big_s16()) return run_big<128, 256, 8, 128, 4, 1, EPI_BIAS_BNSTAT, true, true>(a, st);
-        if (width == 64 && layer == 3) return run_big<128, 256, 8, 128, 4, 1, EPI_BIAS_BNSTAT, BIG_IMGL>(a, st);
+        if (width == 64 && layer == 2) return run_big<64, 128, 16, 128, 4, 1, EPI_BIAS_BNSTAT, true>(a, st);
+        if (width == 64 && layer == 3) return run_big<128, 256, 8, 128, 4, 1, EPI_BIAS_BNSTAT, true>(a, st);
         if (width == 128 && layer == 2) return run_big<64, 128, 32, 128, 4, 1, EPI_BIAS_BNSTAT>(a, st);       // half an image per item: per-tile layout
-        if (width == 128 && layer == 3) return run_big<128, 256, 16, 128, 4, 1, EPI_BIAS_BNSTAT, BIG_IMGL>(a, st);
+        if (width == 128 && layer == 3) return run_big<128, 256, 16, 128, 4, 1, EPI_BIAS_BNSTAT, true>(a, st);
         if (width == 128 && layer == 1) return run_big<32, 64, 64, 32, 8, 1, EPI_BIAS_BNSTAT, true>(a, st);
     }
     return -100;

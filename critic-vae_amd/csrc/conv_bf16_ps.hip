@@ -1,7 +1,8 @@
 // conv_bf16_ps.hip — persistent bf16-MFMA 5x5 conv forward / input-gradient kernel (precision mode 1, round 4).
 //
-// Same call sites as conv5x5_bf16_kernel<.., MODE_STD, NS = 1> (nn.Conv2d E2..E4, vae_nets.py:74,79,84, and their input
-// gradients in loss.backward(), vae.py:57), same tiling (two 128-pixel tiles x NT channels per workgroup-step, 32-channel K
+// Written for the call sites of conv5x5_bf16_kernel<.., MODE_STD, NS = 1> (nn.Conv2d E2..E4 and D0, vae_nets.py:74,79,84,117, and their input
+// gradients in loss.backward(), vae.py:57); since round 5 the big-tile kernel (conv_bf16_big.hip) serves E2..E4, and the one instantiation
+// left is D0's forward at 128 x 128 frames (D0 at 64 x 64 has 4 x 4 images: conv4x4_row_bf16_kernel).  Same tiling (two 128-pixel tiles x NT channels per workgroup-step, 32-channel K
 // chunks, one kernel row per stage), same packed weights, same LDS images.  What changes is everything AROUND the MFMA loop —
 // stage timing of the round-3 kernel (profiles/r04_stage_timing.txt): of a 25 k-cycle E2-forward workgroup 7.5 k are MFMAs,
 // 3 k wait for its (cold) input tiles, 8-10 k are the epilogue at ~15 cycles per VALU instruction beside the co-resident
@@ -25,17 +26,6 @@
 #include "conv_epilogue.h"
 #include "conv_bf16.h"
 
-// -DPS_TIMING (timing builds): cycles per phase of ONE instantiation (-DPS_T_KCH/NCH/H), summed over the items of the sampled
-// workgroups (blockIdx.x a multiple of 32), wave 0 lane 0: [items, barrier 1, staging, drain, barrier 2, MFMA, epilogue, whole loop]
-#ifdef PS_TIMING
-__device__ long long ps_dbg[16 * 12];
-extern "C" int cvae_ps_dbg_read(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ps_dbg), sizeof(ps_dbg)); }
-#define PT_ON (KCH == PS_T_KCH && NCH == PS_T_NCH && H == PS_T_H)
-#define PT(v) do { if (PT_ON) { __builtin_amdgcn_sched_barrier(0); v = clock64(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define PT_ON false
-#define PT(v)
-#endif
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
 
@@ -63,7 +53,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float* red = lds_bias + NCH;                               // [tile][S | Q][wave][NT]
     __bf16* patch = reinterpret_cast<__bf16*>(red + MT * 2 * 4 * NT);      // [wave][NT channel rows][PRS]
 
-    [[maybe_unused]] const long long rt_entry = PT_ON ? (long long)wall_clock64() : 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
     const int G = gridDim.x;
     // item -> (tile pair, channel block).  Workgroups are dealt to the 8 XCDs round-robin (item & 7 = the XCD while G % 8 == 0): XCD x
@@ -256,18 +245,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     load_input(cur, 0);
     __syncthreads();                                           // bias row visible
 
-    [[maybe_unused]] long long c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, tb1 = 0, tst = 0, tdr = 0, tb2 = 0, tmf = 0, tep = 0, nit = 0, tall = 0;
-    PT(tall);
-    [[maybe_unused]] const long long rt0 = PT_ON ? (long long)wall_clock64() : 0;
-#ifndef PS_PRIO
-#define PS_PRIO 1
-#endif
     int itemNo = 0;
     for (;;) {
         // The two workgroups of a CU share each SIMD's issue ports, arbitrated by priority, then AGE: left alone, the workgroup that
-        // was dispatched second loses every tie and finishes its 16 items 50 us after the first (173 vs 225 us, ps_timing.py), running
+        // was dispatched second loses every tie and finishes its 16 items 50 us after the first (173 vs 225 us), running
         // the tail alone.  Alternating the priority per item (the halves in opposite phase) shares the ports evenly.
-        if (PS_PRIO) { if (((itemNo++ ^ (blockIdx.x >= (unsigned)(G / 2))) & 1) != 0) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+        if (((itemNo++ ^ (blockIdx.x >= (unsigned)(G / 2))) & 1) != 0) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
         int itn = it + G, pairn, n0n;
         decode(itn, pairn, n0n);
         const bool have_next = itn < numItems && pairn < numPairs;
@@ -283,53 +266,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // chunk 0: five stages, each with its share of the previous item's drain
 #pragma unroll
         for (int r = 0; r < KS; ++r) {
-            PT(c0);
             __syncthreads();                                   // everyone finished reading the previous stage (and its drain reads)
-            PT(c1);
             if (r == 0) store_input();
             store_w();
             // the loads of the coming stage / chunk are issued BEFORE this slot's stores: waiting for them later does not wait for the stores
             if (r == 0) { if (NCHUNK > 1) load_input(cur, 1); else load_input(nxt, 0); }
             if (r < KS - 1) load_w(cur, 0, r + 1); else if (NCHUNK > 1) load_w(cur, 1, 0); else load_w(nxt, 0, 0);
             __builtin_amdgcn_sched_barrier(0);                 // pinned: the scheduler otherwise sinks the loads below the drain's stores
-            PT(c2);
             if (r == 0) { bn_combine(pd, have_pd); drain_units(pd, have_pd, 0, 0); }
             if (r == 1) drain_units(pd, have_pd, 0, 2);
             if (r == 2) park_tile1();
             if (r == 3) drain_units(pd, have_pd, 1, 0);
             if (r == 4) drain_units(pd, have_pd, 1, 2);
-            PT(c3);
             __syncthreads();
-            PT(c4);
             mfma_phase(r);
-            PT(c5);
-#ifdef PS_TIMING
-            if (PT_ON) { tb1 += c1 - c0; tst += c2 - c1; tdr += c3 - c2; tb2 += c4 - c3; tmf += c5 - c4; }
-#endif
         }
         for (int cc = 1; cc < NCHUNK; ++cc) {
             const bool lastc = cc == NCHUNK - 1;
 #pragma unroll
             for (int r = 0; r < KS; ++r) {
-                PT(c0);
                 __syncthreads();
-                PT(c1);
                 if (r == 0) store_input();
                 store_w();
                 if (r == 0) { if (lastc) load_input(nxt, 0); else load_input(cur, cc + 1); }
                 if (r < KS - 1) load_w(cur, cc, r + 1); else if (lastc) load_w(nxt, 0, 0); else load_w(cur, cc + 1, 0);
-                PT(c2);
                 __syncthreads();
-                PT(c4);
                 mfma_phase(r);
-                PT(c5);
-#ifdef PS_TIMING
-                if (PT_ON) { tb1 += c1 - c0; tst += c2 - c1; tb2 += c4 - c2; tmf += c5 - c4; }
-#endif
             }
         }
         // ---- epilogue: what must happen before the accumulators are reused ----
-        PT(c0);
 #pragma unroll
         for (int tl = 0; tl < MT; ++tl)
 #pragma unroll
@@ -359,23 +324,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     else { p1[nb][2 * g] = w0; p1[nb][2 * g + 1] = w1; }
                 }
             }
-        PT(c1);
-#ifdef PS_TIMING
-        if (PT_ON) { tep += c1 - c0; ++nit; }
-#endif
         pd = cur; have_pd = true;
         if (!have_next) break;
         cur = nxt; it = itn;
     }
-#ifdef PS_TIMING
-    if (PT_ON && (blockIdx.x & 31) == 0 && blockIdx.x < 512 && tid == 0) {
-        long long* o = ps_dbg + (blockIdx.x >> 5) * 12;
-        o[10] = rt_entry;
-        o[0] = nit; o[1] = tb1; o[2] = tst; o[3] = tdr; o[4] = tb2; o[5] = tmf; o[6] = tep; o[7] = clock64() - tall;
-        o[9] = rt0;                                       // absolute start (100 MHz ticks): do the workgroups 256..511 start with 0..255?
-        o[8] = (long long)wall_clock64() - rt0;          // s_memrealtime ticks (100 MHz) over the same span: in-kernel clock = o[7] / o[8] * 100 MHz
-    }
-#endif
     // ---- tail: the last item's tiles ----
     __syncthreads();
     bn_combine(pd, true);
@@ -384,9 +336,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     park_tile1();
     __syncthreads();
     drain_units(pd, true, 1, 0); drain_units(pd, true, 1, 2);
-#ifdef PS_TIMING
-    if (PT_ON && (blockIdx.x & 31) == 0 && blockIdx.x < 512 && tid == 0) ps_dbg[(blockIdx.x >> 5) * 12 + 11] = (long long)wall_clock64();
-#endif
 }
 
 template <int KCH, int NCH, int H, int NT, int EPI>
@@ -416,36 +365,6 @@ static int run_ps(const ConvBf16Args& a, hipStream_t st) {
 }
 
 int launch_conv_bf16_ps(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st) {
-    if (!dgrad) {
-        if (width == 64) {
-            switch (layer) {
-                case 1: return run_ps<32, 64, 32, 64, EPI_BIAS_BNSTAT>(a, st);
-                case 2: return run_ps<64, 128, 16, 64, EPI_BIAS_BNSTAT>(a, st);
-                case 3: return run_ps<128, 256, 8, 64, EPI_BIAS_BNSTAT>(a, st);
-            }
-        } else if (width == 128) {
-            switch (layer) {
-                case 1: return run_ps<32, 64, 64, 64, EPI_BIAS_BNSTAT>(a, st);
-                case 2: return run_ps<64, 128, 32, 64, EPI_BIAS_BNSTAT>(a, st);
-                case 3: return run_ps<128, 256, 16, 64, EPI_BIAS_BNSTAT>(a, st);
-                case 4: return run_ps<256, 128, 8, 64, EPI_BIAS_RELU>(a, st);
-            }
-        }
-    } else {
-        if (width == 64) {
-            switch (layer) {
-                case 1: return run_ps<64, 32, 32, 32, EPI_PLAIN>(a, st);
-                case 2: return run_ps<128, 64, 16, 64, EPI_PLAIN>(a, st);
-                case 3: return run_ps<256, 128, 8, 64, EPI_PLAIN>(a, st);
-            }
-        } else if (width == 128) {
-            switch (layer) {
-                case 1: return run_ps<64, 32, 64, 32, EPI_PLAIN>(a, st);
-                case 2: return run_ps<128, 64, 32, 64, EPI_PLAIN>(a, st);
-                case 3: return run_ps<256, 128, 16, 64, EPI_PLAIN>(a, st);
-                case 4: return run_ps<128, 256, 8, 64, EPI_PLAIN>(a, st);
-            }
-        }
-    }
+    if (layer == 4 && width == 128 && !dgrad) return run_ps<256, 128, 8, 64, EPI_BIAS_RELU>(a, st);
     return -100;
 }

@@ -4,28 +4,6 @@
 
 enum { EPI_BIAS_BNSTAT = 0, EPI_BIAS_RELU = 1, EPI_PLAIN = 2, EPI_POOLSUM_MASK = 3 };
 
-// Timing experiments (WRONG results, never shipped; profiles/experiments/variant.sh -DEPI_EXPERIMENT=n): which part of the
-// epilogue a kernel's time sits in.  bit 0: no global stores of the tile;  bit 1: no BatchNorm partials;  bit 2: no LDS transpose
-// (stores whatever the patch holds).
-#ifndef EPI_EXPERIMENT
-#define EPI_EXPERIMENT 0
-#endif
-// -DEPI_TIMING (timing builds): s_memtime stamps inside epilogue_store of the sampled workgroups (blockIdx.x a multiple of 64
-// below 1024, blockIdx.y == 0; lane 0 of every wave), read back through cvae_epi_dbg_read: [16 workgroups][4 waves][32 stamps]
-#ifdef EPI_TIMING
-__device__ long long epi_dbg[16 * 4 * 32];
-__device__ __forceinline__ void epi_stamp(int& k) {
-    if ((blockIdx.x & 63) == 0 && blockIdx.x < 1024 && blockIdx.y == 0 && (threadIdx.x & 63) == 0 && k < 32) {
-        __builtin_amdgcn_sched_barrier(0);
-        epi_dbg[((blockIdx.x >> 6) * 4 + (threadIdx.x >> 6)) * 32 + k] = clock64();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    ++k;
-}
-#define EPI_STAMP(k) epi_stamp(k)
-#else
-#define EPI_STAMP(k)
-#endif
 
 // Row r (0..31) of a wave's 32-pixel MFMA sub-tile -> pixel of that sub-tile (row-major tile order).  Identity for
 // the fp32 kernels.  The bf16 kernels read their A fragments as 16-byte units `[octet][halo pixel]` with
@@ -79,7 +57,7 @@ __device__ __forceinline__ void apply_bias(f32x16 (&acc)[NT / 32], const float (
 template <int H, int NT, int NCH, int EPI, typename AT = float, bool PERM = false>      // AT: storage type of `out`; PERM: lane_pix
 __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[NT / 32], float* out,
                                                float* bnpart, float* smem, int B, int mt, int n0,
-                                               int img0, int ty0, int tx0, int numTiles = -1, [[maybe_unused]] int ek = 0) {
+                                               int img0, int ty0, int tx0, int numTiles = -1) {
     using T = Tile<H>;
     constexpr int NB = NT / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -87,18 +65,12 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[NT / 32], float* ou
     // Stores are issue-bound (one instruction per accumulator register moves only 4 B per lane), so each
     // wave transposes its 32x32 tile through a private LDS patch and writes 16 B per lane: 4 store
     // instructions per tile instead of 16 (cdna guide T21: the store tail is bound by instruction count).
-    EPI_STAMP(ek);
     __syncthreads();                                   // every wave is done with the staging buffers
-    EPI_STAMP(ek);
     float* patch = smem + wave * (32 * 36);            // [32 pixels][36] floats, rows 16-byte aligned
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        if (!(EPI_EXPERIMENT & 4)) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) patch[((v & 3) + 8 * (v >> 2) + 4 * lh) * 36 + li] = acc[nb][v];
-        }
-        EPI_STAMP(ek);
-        if (EPI_EXPERIMENT & 1) continue;
         if constexpr (Act<AT>::BF16) {        // 8 channels = one 16-byte unit per lane: 2 store instructions per tile
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
@@ -125,11 +97,9 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[NT / 32], float* ou
                 *reinterpret_cast<float4*>(out + ((size_t)(ib * H + gy) * H + gx) * NCH + n0 + nb * 32 + c4 * 4) = val;
         }
         }
-        EPI_STAMP(ek);
     }
-    if (EPI == EPI_BIAS_BNSTAT && !(EPI_EXPERIMENT & 2)) {
+    if (EPI == EPI_BIAS_BNSTAT) {
         __syncthreads();
-        EPI_STAMP(ek);
         float* red = smem;                       // [2][4][NT]
         int nvalid_img = B - img0;
         if (nvalid_img > T::IMGS) nvalid_img = T::IMGS;
@@ -145,9 +115,7 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[NT / 32], float* ou
             t += __shfl_xor(t, 32, 64);
             if (lh == 0) red[wave * NT + nb * 32 + li] = t;
         }
-        EPI_STAMP(ek);
         __syncthreads();
-        EPI_STAMP(ek);
         float mean[NB];
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
@@ -166,9 +134,7 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[NT / 32], float* ou
             t += __shfl_xor(t, 32, 64);
             if (lh == 0) red[4 * NT + wave * NT + nb * 32 + li] = t;
         }
-        EPI_STAMP(ek);
         __syncthreads();
-        EPI_STAMP(ek);
         const size_t nt = numTiles < 0 ? gridDim.x : numTiles;     // multi-tile workgroups pass the true tile count
         if (tid < NT && (size_t)mt < nt) {
             const int c = tid;
@@ -177,7 +143,6 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[NT / 32], float* ou
             bnpart[(size_t)mt * NCH + n0 + c] = sum;
             bnpart[(nt + mt) * NCH + n0 + c] = m2;
         }
-        EPI_STAMP(ek);
     }
 }
 

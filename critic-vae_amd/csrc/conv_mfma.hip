@@ -16,7 +16,6 @@
 // src=(y>>1,x>>1) into the halo gather; its backward (2x2 sum) and the ReLU mask are the
 // POOLSUM epilogue of dgrad.
 #include "common.h"
-#include <stdlib.h>
 #include "conv_epilogue.h"
 
 
@@ -35,15 +34,6 @@ struct ConvArgs {
 // chunks to keep ~80 MFMAs per wave between barrier pairs; KCP = padded row of the transposed (dgrad) slab
 template <int NT> struct KChunk { static constexpr int KC = NT == 32 ? 32 : 16, KCP = KC + 1; };
 
-#ifdef CONVF_TIMING     // experiment builds only (see conv_bf16.hip CONV_TIMING): stage timing of one fp32 instantiation
-__device__ long long convf_dbg[16 * 4 * 10];
-extern "C" int cvae_convf_dbg_read(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(convf_dbg), sizeof(convf_dbg)); }
-#define CF_ON (KCH == CONVF_TIMING_KCH && NCH == CONVF_TIMING_NCH && H == CONVF_TIMING_H && !UP)
-#define CF_STAMP(v) do { if (CF_ON) v = clock64(); } while (0)
-#else
-#define CF_ON false
-#define CF_STAMP(v)
-#endif
 
 template <int KCH, int NCH, int H, bool UP, bool DGRAD, int NT, int EPI, int KSPLIT>
 __global__ __launch_bounds__(256) void conv5x5_mfma_kernel(ConvArgs a) {
@@ -156,24 +146,16 @@ __global__ __launch_bounds__(256) void conv5x5_mfma_kernel(ConvArgs a) {
     if constexpr (KSPLIT == 1 && (EPI == EPI_BIAS_BNSTAT || EPI == EPI_BIAS_RELU)) load_bias<NT, EPI>(biasv, a.bias, n0);
     load_w(st0);
     load_input(st0 / 5);
-    [[maybe_unused]] long long ct0 = 0, ct1 = 0, ct2 = 0, ct3 = 0, ct4 = 0, cd[6] = {0, 0, 0, 0, 0, 0}, ctb = 0, cta = 0, ctw = 0;      // CONVF_TIMING builds
-    CF_STAMP(ctb);
     for (int st = st0; st < st1; ++st) {
         const int r = st % 5;
-        CF_STAMP(ct0);
         __syncthreads();                       // everyone finished reading the previous stage
-        CF_STAMP(ct1);
         if (r == 0) store_input();
-        CF_STAMP(cta);
         store_w();
-        CF_STAMP(ctw);
         // issue order matters: vmcnt retires in order, so the (older) halo loads must not sit
         // between a weight load and the store_w that waits for it
         if (r == 0 && st + 5 < st1) load_input(st / 5 + 1);     // lands during this stage's MFMAs
         if (st + 1 < st1) load_w(st + 1);      // in flight while this stage computes
-        CF_STAMP(ct2);
         __syncthreads();
-        CF_STAMP(ct3);
         const float* ap = lds_in + aBase + r * T::HTW;
         __builtin_amdgcn_iglp_opt(0);
 #pragma unroll
@@ -189,15 +171,7 @@ __global__ __launch_bounds__(256) void conv5x5_mfma_kernel(ConvArgs a) {
                 }
             }
         }
-#ifdef CONVF_TIMING
-        if (CF_ON) {
-            __builtin_amdgcn_sched_barrier(0);
-            long long te = clock64();
-            cd[0] += ct1 - ct0; cd[1] += ct2 - ct1; cd[2] += ct3 - ct2; cd[3] += te - ct3; cd[4] += cta - ct1; cd[5] += ctw - cta;
-        }
-#endif
     }
-    CF_STAMP(ct4);
     vm_drained();
 
     // ------------------------------- epilogue -------------------------------
@@ -232,13 +206,6 @@ __global__ __launch_bounds__(256) void conv5x5_mfma_kernel(ConvArgs a) {
             a.out[o] = a.aux[o] > 0.f ? sum : 0.f;
         }
     }
-#ifdef CONVF_TIMING
-    if (CF_ON && (blockIdx.x & 63) == 0 && blockIdx.x < 1024 && blockIdx.y == 0 && lane == 0) {
-        long long tend = clock64();
-        long long* o = convf_dbg + ((blockIdx.x >> 6) * 4 + wave) * 10;
-        o[0] = cd[0]; o[1] = cd[1]; o[2] = cd[2]; o[3] = cd[3]; o[4] = ct4 - ctb; o[5] = tend - ct4; o[6] = st1 - st0; o[7] = tend - ctb; o[8] = cd[4]; o[9] = cd[5];
-    }
-#endif
 }
 
 template <int KCH, int NCH, int H, bool UP, bool DGRAD, int NT, int EPI, int KSPLIT = 1>
@@ -434,34 +401,26 @@ int launch_splitk_bias_relu(const float* slab, const float* bias, float* out, in
     return 0;
 }
 
-#ifndef D0_KS
-#define D0_KS 8
-#endif
-#ifndef D0_DKS
-#define D0_DKS 4
-#endif
-static constexpr int D0_KSPLIT = D0_KS;
+static constexpr int D0_KSPLIT = 8;
 int64_t conv_fwd_ws_floats(int layer, int width, int B) {
     if (layer != 4 || width != 64) return 0;
     const int64_t h = kLayers[4].h * (width / 64);
     return (int64_t)D0_KSPLIT * B * h * h * kLayers[4].cout;
 }
 
-// conv_mfma_ps.hip: persistent form of E2..E4 forward / input gradient.  CVAE_CONVF_PS = bit mask of the layers that run on it
-// (bit layer-1 forward, bit 3+layer-1 input gradient; 0 = none, for A/B runs).
+// conv_mfma_ps.hip: persistent form of E2..E4 forward / input gradient (-100: no instantiation, or a tensor of 2 GiB and more).
 int launch_conv_mfma_ps(int layer, int width, bool dgrad, int B, const float* in, const float* w, const float* bias, float* out, float* bnpart, hipStream_t st);
-#ifndef CONVF_PS_DEFAULT
-#define CONVF_PS_DEFAULT 55      // the 64-channel-tile layers: E2, E3 forward, E3 input gradient (-2.5 % each), and — round 5, once the kernel's operands travelled
-                                 // as buffer loads — E4 forward / input gradient on 64-channel tiles (step 87.90 -> 88.32 k img/s, masks alternating on one box,
-                                 // profiles/r05_h_ps_buffer_loads.txt); the 32-channel-tile instantiations (E2 input gradient) spill and lose
-#endif
-static bool use_f32_ps(int layer, bool dgrad) {
-    static const int mask = [] { const char* e = getenv("CVAE_CONVF_PS"); return e ? atoi(e) : CONVF_PS_DEFAULT; }();
-    return ((mask >> ((dgrad ? 3 : 0) + (layer >= 4 ? 2 : layer - 1))) & 1) != 0;
+// The passes that run on it: the 64-channel-tile layers — E2, E3 forward, E3 input gradient (-2.5 % each), and (round 5, once the kernel's operands travelled
+// as buffer loads) E4 forward / input gradient at 64 x 64 on 64-channel tiles (step 87.90 -> 88.32 k img/s, profiles/r05_h_ps_buffer_loads.txt).  The
+// 32-channel-tile form of E2's input gradient spills and loses.  CVAE_CONV_PER_TILE=1: none.
+static bool use_f32_ps(int layer, int width, bool dgrad) {
+    if (conv_per_tile_only()) return false;
+    if (layer == 3) return width == 64;
+    return layer == 2 || (layer == 1 && !dgrad);
 }
 
 int conv_f32_route(int layer, int width, bool dgrad, int B) {
-    if (!use_f32_ps(layer, dgrad)) return 0;
+    if (!use_f32_ps(layer, width, dgrad)) return 0;
     g_conv_dry = true;
     const int rc = launch_conv_mfma_ps(layer, width, dgrad, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     g_conv_dry = false;
@@ -470,7 +429,7 @@ int conv_f32_route(int layer, int width, bool dgrad, int B) {
 
 int launch_conv_fwd(int layer, int width, int B, const float* in, const float* w, const float* bias,
                     float* out, float* bnpart, float* ws, hipStream_t st) {
-    if (use_f32_ps(layer, false)) { const int rc = launch_conv_mfma_ps(layer, width, false, B, in, w, bias, out, bnpart, st); if (rc != -100) return rc; }
+    if (use_f32_ps(layer, width, false)) { const int rc = launch_conv_mfma_ps(layer, width, false, B, in, w, bias, out, bnpart, st); if (rc != -100) return rc; }
     ConvArgs a{in, w, bias, nullptr, out, bnpart, B, 0};
     if (width == 64) {
         switch (layer) {
@@ -503,7 +462,7 @@ int launch_conv_fwd(int layer, int width, int B, const float* in, const float* w
 
 // D0 dgrad at 4x4 images is 256 workgroups only: split-K x2 over the co chunks when the caller
 // provides scratch (the training step does; the single-op entry point runs the unsplit kernel)
-static constexpr int D0_DGRAD_KSPLIT = D0_DKS;
+static constexpr int D0_DGRAD_KSPLIT = 4;
 int64_t conv_dgrad_ws_floats(int layer, int width, int B) {
     if (layer != 4 || width != 64) return 0;
     return (int64_t)D0_DGRAD_KSPLIT * B * 16 * kLayers[4].cin;
@@ -512,7 +471,7 @@ int64_t conv_dgrad_ws_floats(int layer, int width, int B) {
 int launch_conv_dgrad(int layer, int width, int B, const float* dout, const float* w,
                       const float* mask_src, float* din, float* ws, hipStream_t st) {
     // KCH = layer Cout (channels of dout), NCH = layer Cin (channels of din)
-    if (!mask_src && use_f32_ps(layer, true)) { const int rc = launch_conv_mfma_ps(layer, width, true, B, dout, w, nullptr, din, nullptr, st); if (rc != -100) return rc; }
+    if (!mask_src && use_f32_ps(layer, width, true)) { const int rc = launch_conv_mfma_ps(layer, width, true, B, dout, w, nullptr, din, nullptr, st); if (rc != -100) return rc; }
     ConvArgs a{dout, w, nullptr, mask_src, din, nullptr, B, 0};
     if (width == 64 && layer == 4 && ws != nullptr) {
         const int64_t slice = (int64_t)B * 16 * 256;

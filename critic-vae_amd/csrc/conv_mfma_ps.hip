@@ -15,7 +15,7 @@
 //     issue order; buffer stores with an out-of-range offset for invalid lanes keep every wait counted).
 // Measured (MI355X, B = 256, rocprofv3): the 64-channel-tile layers gain 2-3 % (E2 forward 222.5 -> 216.7 us, E3 forward 215.2 ->
 // 209.4, E3 input gradient 212.4 -> 208.0); the 32-channel-tile instantiations (KC = 32: 36 staging registers more) spill under
-// the 256-register budget and lose (E2 input gradient 222 -> 262 us) — they stay on the per-tile kernel (conv_mfma.hip, CONVF_PS_DEFAULT).
+// the 256-register budget and lose (E2 input gradient 222 -> 262 us) — they stay on the per-tile kernel (conv_mfma.hip, use_f32_ps).
 // BatchNorm partials: per tile and channel (sum, M2 about the tile mean), M2 = Q - S*S/n in double from the per-wave fp32 sums of
 // the biased accumulators; the sums themselves are exact-order-fixed (bitwise reproducible), the values summed are the same fp32
 // accumulators as in the per-tile kernel.
@@ -300,10 +300,8 @@ static int run_mfma_ps(const ConvPsArgs& a, hipStream_t st) {
     return 0;
 }
 
-// returns -100 when the layer has no persistent instantiation (the caller falls back to the per-tile kernel).  Built by default: the
-// 64-channel-tile layers the default mask selects (E2 / E3 / E4 forward, E3 / E4 input gradient at 64 x 64; E2 / E3 forward and E3 input gradient
-// at 128 x 128).  -DCONVF_PS_ALL adds the others — the 32-channel-tile ones spill and lose (header comment), the rest were never the default —
-// at 8 minutes of compile time.
+// returns -100 when the layer has no persistent instantiation (the caller falls back to the per-tile kernel): E2 / E3 / E4 forward,
+// E3 / E4 input gradient at 64 x 64; E2 / E3 forward and E3 input gradient at 128 x 128.
 int launch_conv_mfma_ps(int layer, int width, bool dgrad, int B, const float* in, const float* w, const float* bias, float* out, float* bnpart, hipStream_t st) {
     const ConvPsArgs a{in, w, bias, out, bnpart, B};
     if (!dgrad) {
@@ -311,41 +309,23 @@ int launch_conv_mfma_ps(int layer, int width, bool dgrad, int B, const float* in
             switch (layer) {
                 case 1: return run_mfma_ps<32, 64, 32, false, 64, EPI_BIAS_BNSTAT>(a, st);
                 case 2: return run_mfma_ps<64, 128, 16, false, 64, EPI_BIAS_BNSTAT>(a, st);
-#ifdef CONVF_PS_ALL
-                case 3: return run_mfma_ps<128, 256, 8, false, 32, EPI_BIAS_BNSTAT>(a, st);
-#else
                 case 3: return run_mfma_ps<128, 256, 8, false, 64, EPI_BIAS_BNSTAT>(a, st);      // round 5: E4 on 64-channel tiles (no spills): 215 -> 207 us
-#endif
             }
         } else if (width == 128) {
             switch (layer) {
                 case 1: return run_mfma_ps<32, 64, 64, false, 64, EPI_BIAS_BNSTAT>(a, st);
                 case 2: return run_mfma_ps<64, 128, 32, false, 64, EPI_BIAS_BNSTAT>(a, st);
-#ifdef CONVF_PS_ALL
-                case 3: return run_mfma_ps<128, 256, 16, false, 64, EPI_BIAS_BNSTAT>(a, st);
-                case 4: return run_mfma_ps<256, 128, 8, false, 64, EPI_BIAS_RELU>(a, st);
-#endif
             }
         }
     } else {
         if (width == 64) {
             switch (layer) {
                 case 2: return run_mfma_ps<128, 64, 16, true, 64, EPI_PLAIN>(a, st);
-#ifdef CONVF_PS_ALL
-                case 1: return run_mfma_ps<64, 32, 32, true, 32, EPI_PLAIN>(a, st);
-                case 3: return run_mfma_ps<256, 128, 8, true, 32, EPI_PLAIN>(a, st);
-#else
                 case 3: return run_mfma_ps<256, 128, 8, true, 64, EPI_PLAIN>(a, st);              // 212 -> 211 us
-#endif
             }
         } else if (width == 128) {
             switch (layer) {
                 case 2: return run_mfma_ps<128, 64, 32, true, 64, EPI_PLAIN>(a, st);
-#ifdef CONVF_PS_ALL
-                case 1: return run_mfma_ps<64, 32, 64, true, 32, EPI_PLAIN>(a, st);
-                case 3: return run_mfma_ps<256, 128, 16, true, 64, EPI_PLAIN>(a, st);
-                case 4: return run_mfma_ps<128, 256, 8, true, 64, EPI_PLAIN>(a, st);
-#endif
             }
         }
     }

@@ -13,9 +13,7 @@
 //                K=src pixels) — one fused kernel builds each G tile once in LDS for both.
 #include "common.h"
 #include "conv_epilogue.h"
-#ifndef THIN_F32_OCC
-#define THIN_F32_OCC 2      // waves per SIMD promised to the compiler for the fp32 E1 / D4 kernels (e1_fwd 160 -> 110 VGPRs; -1..2 us each)
-#endif
+constexpr int THIN_F32_OCC = 2;     // waves per SIMD promised to the compiler for the fp32 E1 / D4 kernels (e1_fwd 160 -> 110 VGPRs; -1..2 us each)
 
 // LDS offset of GEMM-k = tap*3 + ci inside the 3-plane x halo (k = 75 is the zero pad row)
 template <int PS, int HTW>
@@ -566,9 +564,7 @@ static constexpr int E1W_ROW = 128 * 32;
 //   3. dy never leaves the registers: the weight-gradient MFMA contracts over pixels in any order, so accumulator elements
 //      8ks .. 8ks+7 of every lane ARE its B fragment of k-step ks (quadrant row ks), and the transposed reads of the A operand
 //      fetch the pixels in that order (an earlier form stored dy to LDS channel-major and read it back behind a third barrier).
-#ifndef E1W_OCC
-#define E1W_OCC 3          // workgroups per CU of the bf16 E1 weight-gradient kernel (VGPR budget 512 / (E1W_OCC) per lane; splits = E1W_OCC * CUs)
-#endif
+constexpr int E1W_OCC = 3;          // workgroups per CU of the bf16 E1 weight-gradient kernel (VGPR budget 512 / (E1W_OCC) per lane; splits = E1W_OCC * CUs)
 template <int H, bool FUSE, bool XP>          // XP: the strip comes from the packed bf16 frame the forward's statistics pass left in the workspace (a.xp)
 __global__ __launch_bounds__(256, E1W_OCC) void e1_wgrad_bf16_kernel(ThinWgradArgs a, E1Fuse fu) {
     using T = Tile<H>;
@@ -807,7 +803,7 @@ __global__ __launch_bounds__(256) void d4_perm_kernel(const float* __restrict__ 
 }
 
 // Split counts of the E1 weight-gradient / D4 backward kernels.  THIN_SPLIT_CAP is the ONE bound shared by the workspace
-// sizing (e1_wgrad_ws_floats / d4_bwd_ws_floats) and the launches: whatever occupancy switch (-DE1W_OCC, -DD4B_OCC) or
+// sizing (e1_wgrad_ws_floats / d4_bwd_ws_floats) and the launches: whatever occupancy (E1W_OCC, D4B_OCC) or
 // device CU count asks for, a launch never writes more slab rows than the workspace was sized for.
 static constexpr int THIN_SPLIT_CAP = 1024;
 static int thin_splits(int numTiles, int* tps, int want = 512) {
@@ -870,7 +866,6 @@ int launch_e1_wgrad(int width, int B, const float* x, const float* dy, float* dw
         else hipLaunchKernelGGL((e1_wgrad_bf16_kernel<128, false, false>), dim3(S), dim3(256), 0, st, a, fu);
         cvae_probe_end(st);
         CVAE_CHECK_LAUNCH();
-        st = cvae_reduce_stream(st);
         float* red = ws + (size_t)S * E1W_ROW;
         { int rc = launch_col_reduce(ws, S, E1W_ROW, E1W_ROW, red, red + E1W_ROW + 32, st); if (rc) return rc; }
         hipLaunchKernelGGL(e1_perm_kernel, dim3(10), dim3(256), 0, st, red, dw, dbias);
@@ -883,7 +878,6 @@ int launch_e1_wgrad(int width, int B, const float* x, const float* dy, float* dw
     else hipLaunchKernelGGL((e1_wgrad_kernel<128, false>), dim3(S), dim3(256), 0, st, a, fu);
     cvae_probe_end(st);
     CVAE_CHECK_LAUNCH();
-    st = cvae_reduce_stream(st);
     // slab row = [75 x 32 weights | 32 zeros (K pad) | 32 bias partials]: in the flat buffer enc0.b sits at
     // enc0.w + 2432 (2400 weights padded to 64 floats), so ONE column reduction fills both
     if (dbias == dw + 2432)
@@ -1296,15 +1290,8 @@ __global__ __launch_bounds__(256, THIN_F32_OCC) void d4_bwd_kernel(ThinWgradArgs
 //   weight gradient: dV[k][ci] over K = source pixels; wave w takes k-blocks {w>>1, (w>>1)+2, (w>>1)+4} over the tile half w&1
 //                    (3 accumulators per wave instead of 6); halves are added through LDS at the end.
 // Slab row of a workgroup: [192 k][32 ci], k = i*32 + j*4 + co; row 3 (a zero row: co = 3) carries the bias-gradient partials.
-#ifndef D4B_OCC
-#define D4B_OCC 2          // workgroups per CU of the bf16 D4 backward (splits = D4B_OCC * CUs)
-#endif
-#ifndef D4B_VWLDS
-#define D4B_VWLDS 0
-#endif
-#ifndef D4B_ACC2
-#define D4B_ACC2 1          // input gradient as two chains of 6 MFMAs (119 -> 116 us); D4B_VWLDS=1 (weights re-read from LDS, 3 workgroups per CU): 134-142 us
-#endif
+constexpr int D4B_OCC = 2;          // workgroups per CU of the bf16 D4 backward (splits = D4B_OCC * CUs); the input gradient's weight fragments stay in
+                                    // registers (re-read from LDS at 3 workgroups per CU: 134-142 us), its MFMAs as two chains of 6 (119 -> 116 us)
 static constexpr int D4P_ROW = 192 * 32;
 static constexpr int D4P_IW = 40;                 // image row stride in pixels (36 staged + 4 zero columns for the 8-wide runs)
 static constexpr int D4_BWD_BF16_SMEM_BYTES = 2 * 3 * 16 * 64 * 4;      // dynamic LDS of d4_bwd_bf16_kernel (see D4_BWD_BF16_SMEM)
@@ -1315,12 +1302,9 @@ __global__ __launch_bounds__(256, D4B_OCC) void d4_bwd_bf16_kernel(ThinWgradArgs
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __bf16* img = reinterpret_cast<__bf16*>(smem_raw);                          // [20 rows][40 columns][4]
     __bf16* lds_o = img + IMG;                                                  // o3 tile [128][32]
-#if D4B_VWLDS
-    __shared__ __attribute__((aligned(16))) __bf16 lds_v[12 * 64 * 8];          // the input gradient's weight fragments [k-step][lane]
-#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
     // collapsed weights as A fragments of the input gradient: row ci = li, k-step m covers k = 16m + 8lh + jj
-    bf16x8 vw[D4B_VWLDS ? 1 : 12];
+    bf16x8 vw[12];
     {
         static_assert(12 * 32 * 2 * 8 * 2 + 2400 * 4 <= D4_BWD_BF16_SMEM_BYTES, "weight fragments + raw weights fit in the dynamic LDS");
         // the 2400 weights travel to LDS first (coalesced, all loads in flight at once; behind the fragment table): summing
@@ -1337,12 +1321,8 @@ __global__ __launch_bounds__(256, D4B_OCC) void d4_bwd_bf16_kernel(ThinWgradArgs
             img[(((k >> 4) * 32 + ci) * 2 + ((k >> 3) & 1)) * 8 + (k & 7)] = (__bf16)acc;
         }
         __syncthreads();
-#if D4B_VWLDS
-        for (int q = tid; q < 12 * 64; q += 256) reinterpret_cast<bf16x8*>(lds_v)[q] = reinterpret_cast<const bf16x8*>(img)[q];
-#else
 #pragma unroll
         for (int m = 0; m < 12; ++m) vw[m] = *reinterpret_cast<const bf16x8*>(img + ((m * 32 + li) * 2 + lh) * 8);
-#endif
         __syncthreads();
     }
     for (int q = tid; q < 20 * 2; q += 256)       // columns 36..39 of every image row stay zero (16 elements = two 16-byte units per row)
@@ -1424,18 +1404,12 @@ __global__ __launch_bounds__(256, D4B_OCC) void d4_bwd_bf16_kernel(ThinWgradArgs
 #pragma unroll
         for (int m = 0; m < 12; ++m) {
             const bf16x8 bv = *reinterpret_cast<const bf16x8*>(dsrc + ((m >> 1) * D4P_IW + 4 * (m & 1)) * 4);
-#if D4B_VWLDS
-            const bf16x8 av = *reinterpret_cast<const bf16x8*>(lds_v + ((m * 32 + li) * 2 + lh) * 8);
-#else
             const bf16x8 av = vw[m];
-#endif
-            if (D4B_ACC2 && (m & 1)) accd2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, accd2, 0, 0, 0);      // two chains of 6
+            if (m & 1) accd2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, accd2, 0, 0, 0);      // two chains of 6
             else accd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, accd, 0, 0, 0);
         }
-        if (D4B_ACC2) {
 #pragma unroll
-            for (int v = 0; v < 16; ++v) accd[v] += accd2[v];
-        }
+        for (int v = 0; v < 16; ++v) accd[v] += accd2[v];
         {
             const int sp = dy * 16 + dx;                     // accumulator column = this lane's source pixel; rows = channels
             const size_t o = ((size_t)(ib * HS + sy0 + dy) * HS + sx0 + dx) * 32;

@@ -14,9 +14,6 @@
 // w, w+4, .., w+20 and every 4th pixel group of tap 24 and of the bias row (8 accumulator tiles).  One staged fragment triple serves
 // 6 / 9 MFMAs: 0.6 / 0.4 KB of LDS reads per MFMA where the plain bf16 kernel needs 2 KB — this kernel is MFMA-bound.
 // ---------------------------------------------------------------------------------------------
-#ifndef SPLIT_PIPE
-#define SPLIT_PIPE 0      // 1 (experiment): the next tap's fragment triple is requested before this tap's MFMAs — 12 more live registers, 20-76 B of
-#endif                    // spills at the 256-register budget, 131 / 127.5 / 127 -> 140 / 130 / 131 us (E2 / E3 / E4, six products, B = 256)
 template <int H> using SplitTile = WtTile<H, 2, (H == 4 ? 64 : 128)>;
 
 // W = wave index as a RUNTIME (wave-uniform) value: the six tap offsets of the wave sit in registers, everything else of an LDS
@@ -53,24 +50,16 @@ __device__ __forceinline__ void wgrad_split_body(f32x16 (&acc)[8], const __bf16*
             bv[sp] = tr_frag(dp, dp + T::DT * 32);
         }
         load_a(av[0], tapp[0] + T::halobase(kg) * 32);
-        // the compiler's own order is read -> wait -> 6 / 9 MFMAs per tap; the co-resident workgroup's wave covers the LDS latency
+        // the compiler's own order is read -> wait -> 6 / 9 MFMAs per tap; the co-resident workgroup's wave covers the LDS latency (requesting
+        // the next tap's fragment triple before this tap's MFMAs costs 12 live registers, 20-76 B of spills at the 256-register budget:
+        // 131 / 127.5 / 127 -> 140 / 130 / 131 us for E2 / E3 / E4, six products, B = 256)
 #pragma unroll
         for (int j = 0; j < JT; ++j) {
-#if SPLIT_PIPE
-            if (j + 1 < JT) load_a(av[(j + 1) & 1], tapp[j + 1] + T::halobase(kg) * 32);
-            else if ((kg % 4) == W) load_a(av[(j + 1) & 1], tap24 + T::halobase(kg) * 32);
-            __builtin_amdgcn_sched_barrier(0);
-            mfmas(acc[j], av[j & 1], bv);
-            __builtin_amdgcn_sched_barrier(0);
-#else
             if (j > 0) load_a(av[j & 1], tapp[j] + T::halobase(kg) * 32);
             mfmas(acc[j], av[j & 1], bv);
-#endif
         }
         if ((kg % 4) == W) {
-#if !SPLIT_PIPE
             load_a(av[JT & 1], tap24 + T::halobase(kg) * 32);
-#endif
             mfmas(acc[JT], av[JT & 1], bv);
         }
         if ((kg % 4) == ((W + 1) & 3)) {
@@ -223,7 +212,6 @@ static int run_wgrad_split(int products, int B, const float* in, const float* do
     cvae_probe_end(st);
     CVAE_CHECK_LAUNCH();
     float* mid = ws + (size_t)S * row;
-    st = cvae_reduce_stream(st);
     if (dbias == dw + n) return launch_reduce_slabs(ws, dw, row, S, row, st, mid);
     int rc = launch_reduce_slabs(ws, dw, n, S, row, st, mid);
     if (rc || !dbias) return rc;

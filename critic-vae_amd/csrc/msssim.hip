@@ -38,18 +38,9 @@ static MsWin make_window() {
 }
 
 static constexpr int MS_NF = 32;            // finalize workgroups
-#ifndef CVAE_MS_NT
-#define CVAE_MS_NT 768
-#endif
-#ifndef CVAE_MS_RS
-#define CVAE_MS_RS 16        // tile rows of the 64- and 128-wide levels (32: one workgroup per CU, 117 KB of LDS)
-#endif
-#ifndef CVAE_MS_VR
-#define CVAE_MS_VR 2
-#endif
-static constexpr int MS_NT = CVAE_MS_NT;     // threads of a tile workgroup: two workgroups per CU (80 KB of LDS each) = 6 waves per SIMD at <= 80 VGPRs;
-                                             // 768 runs the first horizontal pass (684 items at S = 64) in one round: 371 us against 392 (512) / 366 (1024) at B = 2048
-static constexpr int MS_VR = CVAE_MS_VR;     // output rows per item of the vertical passes (VR + 10 staged rows are read per item)
+static constexpr int MS_NT = 768;           // threads of a tile workgroup: two workgroups per CU (80 KB of LDS each) = 6 waves per SIMD at <= 80 VGPRs;
+                                            // 768 runs the first horizontal pass (684 items at S = 64) in one round: 371 us against 392 (512) / 366 (1024) at B = 2048
+static constexpr int MS_VR = 2;             // output rows per item of the vertical passes (VR + 10 staged rows are read per item)
 
 // ------------------------------------------------------------------------------------------------
 // large levels (S = 128, 64, 32): one workgroup per (plane, RS x CS tile)
@@ -70,7 +61,7 @@ __device__ __forceinline__ f32x2 splat2(float v) { return f32x2{v, v}; }
 template <int S>
 struct MsT {
     static constexpr int CS = S < 64 ? S : 64;             // tile columns
-    static constexpr int RS = S == 32 ? 32 : CVAE_MS_RS;   // tile rows
+    static constexpr int RS = S == 32 ? 32 : 16;           // tile rows (the 64- and 128-wide levels at 32: one workgroup per CU, 117 KB of LDS)
     static constexpr int TX = S / CS, TY = S / RS, TILES = TX * TY;
     static constexpr int ER = RS + 20;                      // input rows staged (tile + 2 window radii)
     static constexpr int MR = RS + 10, MC = CS + 10;        // map region (tile + 1 window radius)
@@ -440,15 +431,6 @@ struct MsP {
     static_assert(SMEM <= 160 * 1024 - 256, "LDS");
 };
 
-#ifdef MS_TIMING      // experiment builds only (profiles/experiments/variant.sh ... -DMS_TIMING): phase timestamps of a few waves
-__device__ long long ms_dbg[4 * 2 * 16];
-extern "C" int cvae_ms_dbg_read(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ms_dbg), sizeof(long long) * 4 * 2 * 16); }
-#define MS_T(k) do { if (S == 64 && (threadIdx.x == 0 || threadIdx.x == NT - 64) && (blockIdx.x & 63) == 0 && blockIdx.x < 256) \
-        ms_dbg[((blockIdx.x >> 6) * 2 + (threadIdx.x != 0)) * 16 + (k)] = clock64(); } while (0)
-#else
-#define MS_T(k)
-#endif
-
 template <int S, bool LAST>
 __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
     using T = MsP<S>;
@@ -503,7 +485,6 @@ __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
     const int pl = grp * PPW + sub;
     const bool valid = pl < a.P;                          // planes past the end: same work on the last plane, no stores
     const int plane = valid ? pl : a.P - 1;
-    MS_T(0);
     // ---- stage the plane, (x, y) interleaved per pixel (the zero columns either side are already there) ----
     {
         const int r = tid / H, c = (tid % H) * 2;
@@ -519,9 +500,7 @@ __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
             }
         }
     }
-    MS_T(1);
     __syncthreads();
-    MS_T(2);
     // ---- 2x2 average for the next level (avg_pool2d, vae_nets.py:232-233): one output per thread ----
     if (a.nx) {
         const int pr = tid / H, pc = tid % H;
@@ -563,9 +542,7 @@ __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
         *reinterpret_cast<f32x4*>(tB + d + 4) = f32x4{hB[2].x, hB[2].y, hB[3].x, hB[3].y};
         *reinterpret_cast<f32x4*>(tC + (hr + 5) * S + hc) = f32x4{hC[0], hC[1], hC[2], hC[3]};
     }
-    MS_T(3);
     __syncthreads();
-    MS_T(4);
     // ---- vertical pass (2 rows x 2 columns per thread) + SSIM / CS maps + derivative maps into the input buffer ----
     const int vr = (tid / H) * 2, vc = (tid % H) * 2;
     float* dA = lin; float* dC = lin + 2 * S * T::DAS;
@@ -616,9 +593,7 @@ __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
         a.part[(size_t)plane * 2] = s_ssim;
         a.part[(size_t)plane * 2 + 1] = s_cs;
     }
-    MS_T(5);
     __syncthreads();
-    MS_T(6);
     if constexpr (WPP > 1) {
         if (tid == 0 && valid) {
             float t0 = 0.f, t1 = 0.f;
@@ -661,9 +636,7 @@ __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
         *reinterpret_cast<f32x4*>(tA + d + 4) = f32x4{gAo[2].x, gAo[2].y, gAo[3].x, gAo[3].y};
         *reinterpret_cast<f32x4*>(tC + (hr + 5) * S + hc) = gCo;
     }
-    MS_T(7);
     __syncthreads();
-    MS_T(8);
     // ---- ... vertical (2 rows x 2 columns per thread), then F = f0 + 2 x f1 + y f2 ----
     {
         constexpr int VR = 2;
@@ -700,7 +673,6 @@ __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
                                 f01[o][1].x + 2.0f * xv[o].y * f01[o][1].y + yv[o].y * f2[o].y);
         }
     }
-    MS_T(9);
   }
 }
 

@@ -1,5 +1,5 @@
 """Child process of test_gpu_bf16.py::test_big_tile_bn_partials_match_the_per_tile_kernels: one bf16 forward (train mode) at the given frame
-size / batch with whatever conv kernels the environment selects (CVAE_BF16_BIG), running statistics and outputs saved to an .npz."""
+size / batch with whatever conv kernels the environment selects (CVAE_CONV_PER_TILE), running statistics and outputs saved to an .npz."""
 import sys
 
 import numpy as np

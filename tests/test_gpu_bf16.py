@@ -346,22 +346,19 @@ def test_bf16x6_step_at_128x128_frames_meets_the_fp32_parity_bar():
     assert abs(float(losses["total_loss"].item()) - float(o["total_loss"].detach())) < 1e-4
 
 
-@pytest.mark.parametrize("s16", ["0", "1"])
-def test_big_tile_conv_kernels_every_instantiation_exact_on_their_stored_operands(s16):
+def test_big_tile_conv_kernels_every_instantiation_exact_on_their_stored_operands():
     """conv_bf16_big.hip (rounds 4-5: PERSISTENT workgroups on a 16-accumulator-tile wave tile, everything inside the MFMA stream) runs
-    E3 / E4 forward and input gradient (and, behind its mask bit, E2 forward on an image-high item) by default.  At test batch sizes every item would get its own workgroup, so the item loop — next
+    E2 / E3 / E4 forward and input gradient (E2 on image-high items / 16-row strips).  At test batch sizes every item would get its own workgroup, so the item loop — next
     item's tiles and slabs requested across the epilogue, fragment sets and slab buffers carried over — would never run: a child process
     caps the grid at 8 workgroups (CVAE_BIG_MAXWG, read once per process) and runs the stored-operand test of this file — every conv
     output recomputed on the CPU from the bf16 operands the kernels consumed; B = 8, the ragged B = 5, and B = 37 (74 / 19 tiles: several
-    items per workgroup, uneven ends, partial groups, the forward kernels' four-tile BatchNorm partials).  s16 = "1": the same with CVAE_BIG_S16=1 — E4's
-    two passes on the v_mfma_f32_16x16x32_bf16 form of the kernel (two taps per MFMA, three-slot slab ring, 16x16 accumulator tiles; an opt-in experiment,
-    profiles/r05_m_big_s16.txt) — plus the BatchNorm-partial geometry test below through that form."""
+    items per workgroup, uneven ends, partial groups, the forward kernels' four-tile BatchNorm partials)."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, CVAE_BF16_BIG="252", CVAE_BIG_MAXWG="8", CVAE_BIG_S16=s16)
-    sel = "kernels_exact_on_their_stored_operands or two_pass_e1" + (" or (bn_partials_match and 64-5)" if s16 == "1" else "")
+    env = dict(os.environ, CVAE_BIG_MAXWG="8")
+    sel = "kernels_exact_on_their_stored_operands or two_pass_e1"
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_bf16.py"), "-m", "gpu", "-q", "-x",
                         "-k", sel], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
@@ -373,21 +370,21 @@ def test_big_tile_bn_partials_match_the_per_tile_kernels(W, B, tmp_path):
     """The persistent big-tile forward kernels emit ONE BatchNorm partial per item of four 128-pixel tiles, and launch_bn_fwd_finalize derives the
     pixel count of every partial from the tile geometry: a quarter of an image (tiles per image >= 4: E3 at 128 x 128), two whole images (two tiles
     per image: E4 at 128 x 128, E3 at 64 x 64), four half-filled... (8 x 8 images: E4 at 64 x 64), with ragged ends at odd batch sizes.  Two child
-    processes (the switch is read once per process) run the same bf16 forward with the big-tile kernels (CVAE_BF16_BIG=252: all six) and with
-    the per-tile / two-workgroup kernels (0): the running statistics — sums over ALL pixels, merged from differently grouped partials — must agree
+    processes (the switch is read once per process) run the same bf16 forward with the big-tile kernels (the default: all six) and with
+    the per-tile kernels (CVAE_CONV_PER_TILE=1): the running statistics — sums over ALL pixels, merged from differently grouped partials — must agree
     to fp32 summation noise, the outputs to bf16 noise.  A wrong count or a wrong partial row would be off by whole percents."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
-    for mask in ("252", "0"):
-        out = str(tmp_path / f"bn_{mask}.npz")
+    for per_tile in ("0", "1"):
+        out = str(tmp_path / f"bn_{per_tile}.npz")
         r = subprocess.run([sys.executable, os.path.join(root, "tests", "bn_geom_worker.py"), str(W), str(B), out],
-                           env=dict(os.environ, CVAE_BF16_BIG=mask), capture_output=True, text=True, timeout=300, cwd=root)
+                           env=dict(os.environ, CVAE_CONV_PER_TILE=per_tile), capture_output=True, text=True, timeout=300, cwd=root)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        res[mask] = np.load(out)
-    a, b = res["252"], res["0"]
+        res[per_tile] = np.load(out)
+    a, b = res["0"], res["1"]
     for bi in (1, 5, 9, 13):
         for k in (f"rm{bi}", f"rv{bi}"):
             scale = max(float(np.abs(b[k]).max()), 1e-6)

@@ -1,5 +1,6 @@
 """CPU: host-side logic that needs no GPU — the C-ABI library loads and exports every symbol
 include/cvae.h declares, layout conversions are exact inverses, the DP path (gloo, 2 ranks)."""
+import json
 import os
 import re
 import subprocess
@@ -59,38 +60,65 @@ def test_bad_arguments_return_errors_not_crashes():
     assert h.workspace_bytes(4) > 0 and h.workspace_bytes(4) % 4 == 0
 
 
+# cvae_conv_route of every (precision, width) at B = 8, 256, 2048, edge - 1, edge (edge: the first batch whose larger tensor of the layer has 2^31
+# bytes), one string per (layer, dgrad) = (1, 0) (1, 1) (2, 0) (2, 1) (3, 0) (3, 1): 0 per-tile, 1 two-workgroup persistent, 2 big-tile persistent
+CONV_ROUTES = {
+    (0, 64): ["11110", "00000", "11110", "11110", "11110", "11110"],
+    (0, 128): ["11010", "00000", "11110", "11110", "00000", "00000"],
+    (1, 64): ["22220"] * 6,
+    (1, 128): ["22220"] * 6,
+    (2, 64): ["00000"] * 6,
+    (2, 128): ["00000"] * 6,
+    (3, 64): ["00000"] * 6,
+    (3, 128): ["00000"] * 6,
+}
+
+
 def test_persistent_conv_kernels_refuse_tensors_of_two_gib():
     """The persistent conv kernels (conv_bf16_big.hip, conv_bf16_ps.hip, conv_mfma_ps.hip) address their tensors with 32-bit byte offsets
     and buffer descriptors; their launchers must hand an activation of 2 GiB or more to the per-tile kernels (64-bit addressing).
     cvae_conv_route walks the launchers' own decision path up to the launch (no device access): the family changes exactly where
-    the larger of a layer's two tensors crosses 2^31 bytes.  A child process, so that no CVAE_* switch of the caller changes the masks."""
+    the larger of a layer's two tensors crosses 2^31 bytes.  The whole route table is pinned (CONV_ROUTES), and CVAE_CONV_PER_TILE=1 sends
+    every pass to the per-tile kernels.  Child processes, so that no CVAE_* switch of the caller changes the routes."""
     code = """
-import sys
+import json, os, sys
 sys.path.insert(0, %r)
 from critic_vae_amd import lib as cvlib
 lib = cvlib.load()
 r = lib.cvae_conv_route
 ch = {1: (32, 64), 2: (64, 128), 3: (128, 256)}
-for prec, elt in ((0, 4), (1, 2)):
+tab = {}
+for prec in range(4):
+    elt = 2 if prec == 1 else 4
     for width in (64, 128):
+        row = []
         for layer in (1, 2, 3):
             H = (width // 2) >> (layer - 1)
             edge = (1 << 31) // (H * H * max(ch[layer]) * elt)          # first batch whose larger tensor has 2^31 bytes
             for dgrad in (0, 1):
+                row.append("".join(str(r(prec, width, layer, dgrad, b)) for b in (8, 256, 2048, edge - 1, edge)))
                 small, below, at = r(prec, width, layer, dgrad, 8), r(prec, width, layer, dgrad, edge - 1), r(prec, width, layer, dgrad, edge)
                 assert small == below, (prec, width, layer, dgrad, small, below)
                 assert at == 0 and r(prec, width, layer, dgrad, 4 * edge) == 0, (prec, width, layer, dgrad, at)
-                print(prec, width, layer, dgrad, edge, small)
-# the default configuration does use them below the edge: fp32 E2..E4 forward on the two-workgroup kernel, bf16 E2..E4 (64 x 64) on the big-tile kernel
-assert [r(0, 64, l, 0, 256) for l in (1, 2, 3)] == [1, 1, 1] and r(0, 64, 1, 1, 256) == 0
-assert [r(1, 64, l, d, 2048) for l in (1, 2, 3) for d in (0, 1)] == [2] * 6 and r(1, 128, 1, 0, 1024) == 2 and r(1, 128, 1, 1, 1024) == 2
-assert r(1, 64, 1, 0, 16383) == 2 and r(1, 64, 1, 0, 16384) == 0 and r(0, 64, 1, 0, 8191) == 1 and r(0, 64, 1, 0, 8192) == 0
+        tab["%%d,%%d" %% (prec, width)] = row
+if os.environ.get("CVAE_CONV_PER_TILE") != "1":
+    # the default configuration does use them below the edge: fp32 E2..E4 forward on the two-workgroup kernel, bf16 E2..E4 (64 x 64) on the big-tile kernel
+    assert [r(0, 64, l, 0, 256) for l in (1, 2, 3)] == [1, 1, 1] and r(0, 64, 1, 1, 256) == 0
+    assert [r(1, 64, l, d, 2048) for l in (1, 2, 3) for d in (0, 1)] == [2] * 6 and r(1, 128, 1, 0, 1024) == 2 and r(1, 128, 1, 1, 1024) == 2
+    assert r(1, 64, 1, 0, 16383) == 2 and r(1, 64, 1, 0, 16384) == 0 and r(0, 64, 1, 0, 8191) == 1 and r(0, 64, 1, 0, 8192) == 0
 assert r(2, 64, 1, 0, 256) == 0 and r(1, 32, 1, 0, 8) < 0 and r(1, 64, 4, 0, 8) < 0 and r(1, 64, 1, 0, 0) < 0 and r(1, 64, 1, 0, 1 << 32) < 0
+print(json.dumps(tab))
 print("ok")
 """ % ROOT
-    env = {k: v for k, v in os.environ.items() if not k.startswith("CVAE_")}
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-2000:]
+    want = {f"{p},{w}": row for (p, w), row in CONV_ROUTES.items()}
+    for per_tile in ("0", "1"):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("CVAE_")}
+        if per_tile == "1":
+            env["CVAE_CONV_PER_TILE"] = "1"
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-2000:]
+        got = json.loads(r.stdout.strip().splitlines()[-2])
+        assert got == (want if per_tile == "0" else {k: ["00000"] * 6 for k in want}), (per_tile, got)
 
 
 def test_two_handles_do_not_share_state():
