@@ -59,6 +59,9 @@ int cvae_num_cus() {
 
 thread_local bool g_conv_dry = false;
 bool conv_per_tile_only() { static const bool on = [] { const char* e = getenv("CVAE_CONV_PER_TILE"); return e && e[0] == '1'; }(); return on; }
+// CVAE_PERSIST_MAXWG (tests): caps the grid of the persistent conv launchers (run_mfma_ps, run_ps, run_big), so that test batches walk several
+// items per workgroup; 0 (unset) = no cap
+int conv_persist_maxwg() { static const int v = [] { const char* e = getenv("CVAE_PERSIST_MAXWG"); const int n = e ? atoi(e) : 0; return n > 0 ? n : 0; }(); return v; }
 // include/cvae.h: which kernel family a conv pass of E2..E4 takes at a batch size (host logic only, no device access)
 extern "C" int32_t cvae_conv_route(int32_t precision, int32_t width, int32_t layer, int32_t dgrad, int64_t batch) {
     if ((width != 64 && width != 128) || layer < 1 || layer > 3 || precision < 0 || precision > 3 || batch < 1 || batch > 0x7fffffffLL) return CVAE_EINVAL;
@@ -606,7 +609,7 @@ int cvae_op_conv_dgrad(cvae_handle h, int32_t layer, int32_t B, const float* dou
         RC(launch_collapse_w(layer, wt, wc, (hipStream_t)stream));
         return launch_conv_up_dgrad(layer, h->cfg.width, B, dout, wc, mask_src, din, wc + conv_up_wc_floats(layer), (hipStream_t)stream);
     }
-    return launch_conv_dgrad(layer, h->cfg.width, B, dout, wt, mask_src, din, nullptr, (hipStream_t)stream);
+    return launch_conv_dgrad(layer, h->cfg.width, B, dout, wt, mask_src, din, (float*)scratch, (hipStream_t)stream);
 }
 
 int64_t cvae_op_scratch_floats(cvae_handle h, int32_t B) {

@@ -181,6 +181,8 @@ int launch_pack_w_bf16(const float* const w[4], float* packed, int ns, hipStream
 extern thread_local bool g_conv_dry;
 // CVAE_CONV_PER_TILE=1 (tests): every conv pass of both precisions on the per-tile kernels, the route tensors of 2 GiB and more take
 bool conv_per_tile_only();
+// CVAE_PERSIST_MAXWG (tests): grid cap of the persistent conv launchers, applied before their multiple-of-8 rounding; 0 = none
+int conv_persist_maxwg();
 // kernel family the conv launchers pick for E2..E4 (layer 1..3; 4 = D0 at 128 x 128) at batch B: 0 per-tile, 1 two-workgroup persistent, 2 big-tile persistent
 int conv_bf16_route(int layer, int width, bool dgrad, int B);
 int conv_f32_route(int layer, int width, bool dgrad, int B);

@@ -588,10 +588,8 @@ static int run_big(const ConvBf16Args& a, hipStream_t st) {
     { int rc = cvae_grant_lds(once, reinterpret_cast<const void*>(kern), SMEM); if (rc) return rc; }
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG, numGroups = cdiv(numTiles, MT);
     const int numItems = 8 * cdiv(numGroups, 8) * NY;
-    // CVAE_BIG_MAXWG (tests): cap the persistent grid so that small batches walk several items per workgroup
-    static const int maxwg = [] { const char* e = getenv("CVAE_BIG_MAXWG"); return e ? atoi(e) : 0; }();
     int G = cvae_num_cus();
-    if (maxwg > 0 && G > maxwg) G = maxwg;
+    if (conv_persist_maxwg() > 0 && G > conv_persist_maxwg()) G = conv_persist_maxwg();     // tests: several items per workgroup
     G -= G % 8;
     if (G < 8) G = 8;
     if (G > numItems) G = numItems;

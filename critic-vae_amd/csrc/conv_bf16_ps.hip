@@ -354,6 +354,7 @@ static int run_ps(const ConvBf16Args& a, hipStream_t st) {
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG, numPairs = cdiv(numTiles, 2);
     const int numItems = 8 * cdiv(numPairs, 8) * NY;
     int G = 2 * cvae_num_cus();
+    if (conv_persist_maxwg() > 0 && G > conv_persist_maxwg()) G = conv_persist_maxwg();     // tests: several items per workgroup
     G -= G % 8;
     if (G < 8) G = 8;
     if (G > numItems) G = numItems;

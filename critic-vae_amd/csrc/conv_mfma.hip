@@ -460,8 +460,8 @@ int launch_conv_fwd(int layer, int width, int B, const float* in, const float* w
     return -2;
 }
 
-// D0 dgrad at 4x4 images is 256 workgroups only: split-K x2 over the co chunks when the caller
-// provides scratch (the training step does; the single-op entry point runs the unsplit kernel)
+// D0 dgrad at 4x4 images is 256 workgroups only: split-K over the co chunks when the caller
+// provides scratch (the training step and the single-op entry point do)
 static constexpr int D0_DGRAD_KSPLIT = 4;
 int64_t conv_dgrad_ws_floats(int layer, int width, int B) {
     if (layer != 4 || width != 64) return 0;

@@ -290,6 +290,7 @@ static int run_mfma_ps(const ConvPsArgs& a, hipStream_t st) {
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG;
     const int numItems = cdiv(numTiles, 8) * 8 * NY;
     int G = 2 * cvae_num_cus();
+    if (conv_persist_maxwg() > 0 && G > conv_persist_maxwg()) G = conv_persist_maxwg();     // tests: several items per workgroup
     G -= G % 8;
     if (G < 8) G = 8;
     if (G > numItems) G = numItems;

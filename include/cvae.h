@@ -220,7 +220,8 @@ int64_t cvae_op_msssim_ws_floats(cvae_handle h, int32_t batch);
 int cvae_op_conv_fwd(cvae_handle h, int32_t layer, int32_t batch, const float* in, const float* w,
                      const float* bias, float* out, float* bn_partials, void* scratch, void* stream);
 /* input gradient, layers 1..7; decoder layers 5..7 also fold Upsample backward (2x2 sum) and the
- * ReLU mask of the producing layer's output `mask_src` */
+ * ReLU mask of the producing layer's output `mask_src`; layer 4 (D0) at 64x64 runs the training
+ * step's split-K kernel, its partial slabs in `scratch` */
 int cvae_op_conv_dgrad(cvae_handle h, int32_t layer, int32_t batch, const float* dout,
                        const float* w, const float* mask_src, float* din, void* scratch, void* stream);
 /* weight (+ optional bias) gradient, layers 0..7 */

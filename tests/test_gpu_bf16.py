@@ -350,14 +350,16 @@ def test_big_tile_conv_kernels_every_instantiation_exact_on_their_stored_operand
     """conv_bf16_big.hip (rounds 4-5: PERSISTENT workgroups on a 16-accumulator-tile wave tile, everything inside the MFMA stream) runs
     E2 / E3 / E4 forward and input gradient (E2 on image-high items / 16-row strips).  At test batch sizes every item would get its own workgroup, so the item loop — next
     item's tiles and slabs requested across the epilogue, fragment sets and slab buffers carried over — would never run: a child process
-    caps the grid at 8 workgroups (CVAE_BIG_MAXWG, read once per process) and runs the stored-operand test of this file — every conv
+    caps the grid at 8 workgroups (CVAE_PERSIST_MAXWG, read once per process) and runs the stored-operand test of this file — every conv
     output recomputed on the CPU from the bf16 operands the kernels consumed; B = 8, the ragged B = 5, and B = 37 (74 / 19 tiles: several
-    items per workgroup, uneven ends, partial groups, the forward kernels' four-tile BatchNorm partials)."""
+    items per workgroup, uneven ends, partial groups, the forward kernels' four-tile BatchNorm partials).  The cap holds for every persistent
+    conv launcher: at (128, 37) D0's forward on conv_bf16_ps.hip walks 10 tile pairs x 2 channel blocks on 8 workgroups, so the workgroups
+    move on to the next pair as well as to the next channel block."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, CVAE_BIG_MAXWG="8")
+    env = dict(os.environ, CVAE_PERSIST_MAXWG="8")
     sel = "kernels_exact_on_their_stored_operands or two_pass_e1"
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_bf16.py"), "-m", "gpu", "-q", "-x",
                         "-k", sel], env=env, capture_output=True, text=True, timeout=900, cwd=root)
@@ -512,7 +514,7 @@ def test_bf16_step_never_stores_y0_unless_a_block0_gamma_is_tiny(B, vec_bound, t
             assert gk[0] == 0 and rk[0] == 0          # gamma = 0, beta = 0: the channel's output is 0 everywhere and ReLU'(0) = 0 blocks its gradient
 
 
-@pytest.mark.parametrize("W,B", [(64, 8), (64, 5), (64, 37), (128, 5)])      # 5, 37: ragged tile counts (the persistent D4 / MS-SSIM / E1 / conv loops end unevenly);
+@pytest.mark.parametrize("W,B", [(64, 8), (64, 5), (64, 37), (128, 5), (128, 37)])  # 5, 37: ragged tile counts (the persistent D4 / MS-SSIM / E1 / conv loops end unevenly);
 def test_bf16_kernels_exact_on_their_stored_operands(W, B):                       # 128 x 128: the other set of instantiations (every spatial size doubles)
     """Layout / indexing check of every bf16-mode contraction, independent of the bf16 rounding noise: after one
     bf16 step the workspace holds the bf16 activations and activation gradients the kernels actually consumed.

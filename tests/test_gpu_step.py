@@ -228,6 +228,26 @@ def test_step_b256_fp32_against_oracle(precision):
     assert rep["rel_forced"] <= 1e-4
 
 
+@pytest.mark.parametrize("width,B", [(64, 601), (128, 67)])
+def test_step_fp32_against_oracle_past_one_item_per_workgroup(width, B):
+    """The persistent fp32 conv kernels (conv_mfma_ps.hip, two workgroups per CU) set up and load the next item while they finish one; at
+    B <= 256 (64 x 64) and B = 2 (128 x 128) most of their passes have no more items than workgroups.  Here every one of them walks
+    several: B = 601 at 64 x 64 (E2 forward up to 10 items per workgroup, E4 input gradient 2, ragged 2-image tiles), B = 67 at 128 x 128
+    (E2 forward 5, E3 input gradient 2).  Same bar as test_step_b256_fp32_against_oracle."""
+    x, pred, eps = _inputs(1234, 0, B, width=width)
+    vae = _model(B, width=width)
+    (_, mu, logvar, recon), losses = _step(vae, x, pred, eps)
+    rep, o = check_step_against_oracle(vae, x, pred, eps, B, verbose=True)
+    assert rep is not None, "seed must give a finite loss"
+    assert (mu.detach().cpu() - o["mu"]).abs().max() < TOL and (logvar.detach().cpu() - o["logvar"]).abs().max() < TOL
+    assert (recon.detach().cpu() - o["recon"]).abs().max() < TOL
+    s = vae.last_scalars.cpu()
+    assert abs(float(s[0]) - float(o["total_loss"])) < TOL and abs(float(s[1]) - float(o["recon_loss"])) < TOL
+    assert abs(float(s[2]) - float(o["KLD"])) < TOL
+    assert (s[3:8] - o["ssim_levels"]).abs().max() < TOL and (s[8:13] - o["cs_levels"]).abs().max() < TOL
+    assert rep["rel_forced"] <= 1e-4
+
+
 def test_bitwise_reproducible_and_full_size():
     """BASELINE config 2 size (B=256): finite, and two runs are bit-identical (fixed-order reductions)."""
     B = 256
