@@ -57,17 +57,19 @@ int cvae_num_cus() {
     return n;
 }
 
-thread_local bool g_conv_dry = false;
-bool conv_per_tile_only() { static const bool on = [] { const char* e = getenv("CVAE_CONV_PER_TILE"); return e && e[0] == '1'; }(); return on; }
-// CVAE_PERSIST_MAXWG (tests): caps the grid of the persistent conv launchers (run_mfma_ps, run_ps, run_big), so that test batches walk several
-// items per workgroup; 0 (unset) = no cap
-int conv_persist_maxwg() { static const int v = [] { const char* e = getenv("CVAE_PERSIST_MAXWG"); const int n = e ? atoi(e) : 0; return n > 0 ? n : 0; }(); return v; }
+int persistent_grid(int wgs_per_cu, int num_items) {
+    // CVAE_PERSIST_MAXWG (tests): caps the grid, so that test batches walk several items per workgroup; 0 (unset) = no cap
+    static const int maxwg = [] { const char* e = getenv("CVAE_PERSIST_MAXWG"); const int n = e ? atoi(e) : 0; return n > 0 ? n : 0; }();
+    int G = wgs_per_cu * cvae_num_cus();
+    if (maxwg > 0 && G > maxwg) G = maxwg;
+    G -= G % 8;
+    if (G < 8) G = 8;
+    return G < num_items ? G : num_items;
+}
 // include/cvae.h: which kernel family a conv pass of E2..E4 takes at a batch size (host logic only, no device access)
 extern "C" int32_t cvae_conv_route(int32_t precision, int32_t width, int32_t layer, int32_t dgrad, int64_t batch) {
     if ((width != 64 && width != 128) || layer < 1 || layer > 3 || precision < 0 || precision > 3 || batch < 1 || batch > 0x7fffffffLL) return CVAE_EINVAL;
-    if (precision == 0) return conv_f32_route(layer, width, dgrad != 0, (int)batch);
-    if (precision == 1) return conv_bf16_route(layer, width, dgrad != 0, (int)batch);
-    return 0;                                                  // fp32 emulation (three operand splits): the per-tile kernels
+    return conv_route(precision, layer, width, dgrad != 0, batch).family;
 }
 
 struct ParamEntry { std::string name; int64_t offset, numel; };
@@ -281,6 +283,13 @@ static bool use_split_wgrad(cvae_handle h, int layer) {
 }
 static int bf16_splits(cvae_handle h) { return h->cfg.precision >= 2 ? 3 : 1; }          // packed weight copies
 static int bf16_mode(cvae_handle h) { return h->cfg.precision == 2 ? 3 : (h->cfg.precision == 3 ? 6 : 1); }   // launcher code: 1 bf16, 3 x9, 6 x6
+// weight gradient of conv layer 1..4 (E2..E4, D0): bf16 MFMA, exact 3-way operand splits (fp32-emulation modes) or fp32 MFMA
+static int conv_wgrad(cvae_handle h, int layer, int B, const float* in, const float* dout, float* dw, float* dbias, float* ws, hipStream_t st) {
+    const int W = h->cfg.width;
+    if (use_bf16_wgrad(h, layer)) return launch_conv_wgrad_bf16(layer, W, B, in, dout, dw, dbias, ws, st);
+    if (use_split_wgrad(h, layer)) return launch_conv_wgrad_split(layer, W, bf16_mode(h) == 6 ? 6 : 9, B, in, dout, dw, dbias, ws, st);
+    return launch_conv_wgrad(layer, W, B, in, dout, dw, dbias, ws, st);
+}
 static int pack_bf16_weights(cvae_handle h, const float* params, float* ws, const WsLayout& w, hipStream_t st) {
     if (!use_bf16(h, 1)) return 0;
     const float* wl[4] = {P_(h->enc_w[1]), P_(h->enc_w[2]), P_(h->enc_w[3]), P_(h->dec_w[0])};
@@ -454,10 +463,7 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
         const float* in = i == 0 ? ws + w.h : ws + w.o[i - 1];
         RC(fork(3 - i));
         if (i == 0) {
-            { ProbeArm pa(h, 2, l);
-              if (use_bf16_wgrad(h, 4)) RC(launch_conv_wgrad_bf16(4, W, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd));
-              else if (use_split_wgrad(h, 4)) RC(launch_conv_wgrad_split(4, W, bf16_mode(h) == 6 ? 6 : 9, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd));
-              else RC(launch_conv_wgrad(l, W, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd)); }
+            { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, 4, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd)); }
             { ProbeArm pa(h, 1, l);
               if (use_bf16(h, 4)) RC(launch_conv_dgrad_bf16(4, W, bf16_mode(h), B, ws + w.d_o[0], ws + w.wpack, ws + w.d_h, ws + w.scratch, st));
               else RC(launch_conv_dgrad(l, W, B, ws + w.d_o[0], P_(h->dec_w[0]), nullptr, ws + w.d_h, ws + w.scratch, st)); }
@@ -493,10 +499,7 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
               RC(launch_e1_wgrad(W, B, x, fuse0 ? nullptr : ws + w.d_y[0], G_(h->enc_w[0]), G_(h->enc_b[0]), scw, sd, h->cfg.precision == 1, fuse0 ? fu : nullptr,
                                  (h->e1_two_pass && fuse0 && h->xp_ws == (const void*)ws && h->xp_B == B) ? ws + w.xp : nullptr)); }
         } else {
-            { ProbeArm pa(h, 2, l);
-              if (use_bf16_wgrad(h, l)) RC(launch_conv_wgrad_bf16(l, W, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd));
-              else if (use_split_wgrad(h, l)) RC(launch_conv_wgrad_split(l, W, bf16_mode(h) == 6 ? 6 : 9, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd));
-              else RC(launch_conv_wgrad(l, W, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd)); }
+            { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, l, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd)); }
             { ProbeArm pa(h, 1, l);
               if (use_bf16(h, l)) RC(launch_conv_dgrad_bf16(l, W, bf16_mode(h), B, ws + w.d_y[l], ws + w.wpack, ws + w.d_a[l - 1], ws + w.scratch, st));
               else RC(launch_conv_dgrad(l, W, B, ws + w.d_y[l], P_(h->enc_w[l]), nullptr, ws + w.d_a[l - 1], nullptr, st)); }

@@ -164,6 +164,19 @@ inline int cvae_grant_lds(DeviceOnce& once, const void* kernel, int bytes) {
 
 // Compute units of the current device (256 on the MI355X), queried once per device: sizes the persistent grids.
 int cvae_num_cus();
+// Grid of a persistent conv kernel (api.hip): wgs_per_cu workgroups per compute unit, capped by CVAE_PERSIST_MAXWG (tests: several items
+// per workgroup), rounded down to a multiple of 8 (xcd_tile), at least 8 and at most num_items.
+int persistent_grid(int wgs_per_cu, int num_items);
+
+// Kernel family of a conv forward / input-gradient pass of layers 1..4 (E2..E4, D0); the codes are those of cvae_conv_route.
+// CONV_PS: conv_mfma_ps.hip in fp32 mode, conv_bf16_ps.hip in bf16 mode; CONV_BIG: conv_bf16_big.hip.
+enum ConvFamily { CONV_PER_TILE = 0, CONV_PS = 1, CONV_BIG = 2 };
+struct ConvRoute {
+    ConvFamily family;
+    int tilesPerPartial;      // forward passes: 128-pixel tiles per BatchNorm partial row of bnpart
+};
+// conv_mfma.hip: the one table the conv launchers read (host logic only, never touches the device); precision as in cvae_config
+ConvRoute conv_route(int precision, int layer, int width, bool dgrad, int64_t B);
 
 // ---- launchers implemented across the .hip files (all asynchronous on `st`) ----
 // conv_mfma.hip
@@ -177,15 +190,6 @@ int64_t conv_dgrad_ws_floats(int layer, int width, int B);
 bool conv_bf16_supported(int layer, int width);
 int64_t conv_bf16_pack_floats(int ns);
 int launch_pack_w_bf16(const float* const w[4], float* packed, int ns, hipStream_t st);     // ns = 1 (bf16) or 3 (fp32 emulation)
-// cvae_conv_route (host logic only): while set, the persistent launchers return 0 behind their size guards WITHOUT touching the device
-extern thread_local bool g_conv_dry;
-// CVAE_CONV_PER_TILE=1 (tests): every conv pass of both precisions on the per-tile kernels, the route tensors of 2 GiB and more take
-bool conv_per_tile_only();
-// CVAE_PERSIST_MAXWG (tests): grid cap of the persistent conv launchers, applied before their multiple-of-8 rounding; 0 = none
-int conv_persist_maxwg();
-// kernel family the conv launchers pick for E2..E4 (layer 1..3; 4 = D0 at 128 x 128) at batch B: 0 per-tile, 1 two-workgroup persistent, 2 big-tile persistent
-int conv_bf16_route(int layer, int width, bool dgrad, int B);
-int conv_f32_route(int layer, int width, bool dgrad, int B);
 int launch_conv_fwd_bf16(int layer, int width, int ns, int B, const float* in, const float* packed, const float* bias, float* out,
                          float* bnpart, float* ws, hipStream_t st, int* tilesPerPartial = nullptr);    // out: 128-pixel tiles per BatchNorm partial row
 int launch_conv_dgrad_bf16(int layer, int width, int ns, int B, const float* dout, const float* packed, float* din, float* ws, hipStream_t st);

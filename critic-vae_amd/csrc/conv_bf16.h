@@ -24,13 +24,10 @@ template <int H, int OCT> struct Bf16Geom {
 };
 
 
-// conv_bf16_ps.hip: persistent two-workgroup forward kernel of D0 at 128 x 128 in bf16 mode (returns -100 for any other pass, or a tensor too large
-// for its 32-bit offsets)
+// the persistent kernels of the passes conv_route sends to them in bf16 mode: conv_bf16_ps.hip (two-workgroup, CONV_PS: D0's forward at
+// 128 x 128) and conv_bf16_big.hip (big-tile, CONV_BIG: E2..E4, 16 accumulator tiles per wave)
 int launch_conv_bf16_ps(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st);
-// conv_bf16_big.hip: persistent big-tile kernel of E2..E4 (16 accumulator tiles per wave); -100 if the layer has no instantiation or a tensor is
-// too large for its 32-bit offsets
 int launch_conv_bf16_big(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st);
-int conv_bf16_big_tiles(int layer, int width, bool dgrad);      // 128-pixel tiles per item (= per BatchNorm partial of its forward passes)
 
 // Exact 3-way bf16 split of an fp32 value: x == hi + mid + lo (each difference is exact in fp32, RNE
 // leaves at most 8 significant bits per step), used by the fp32-emulation mode (NS == 3): the nine

@@ -722,43 +722,18 @@ static int run4x4_bf16(const ConvBf16Args& a, hipStream_t st) {
 
 bool conv_bf16_supported(int layer, int width) { return (width == 64 || width == 128) && layer >= 1 && layer <= 7; }
 
-// bf16 mode: the persistent kernel a forward / input-gradient pass runs on.  *family = 2: E2..E4 (layers 1..3), both passes, at both frame sizes on the
-// big-tile kernel of conv_bf16_big.hip (E2 forward 196 vs 209 us, E2 input gradient 192 vs 209 us at 64 x 64; at 128 x 128 E2's input gradient 379 vs
-// 415 us, forward 424 vs 431: profiles/r05_g_big_mask_sweep.txt, r05_k_big_image_layout.txt, r05_r_e2_on_big_kernel.txt); 1: D0's forward at 128 x 128
-// on the two-workgroup kernel of conv_bf16_ps.hip; 0: the caller runs the per-tile kernel — every other pass, a tensor of 2 GiB and more (the persistent
-// launchers return -100), or CVAE_CONV_PER_TILE=1.  Returns the launch's error code.
-static int try_persistent_bf16(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st, int* family) {
-    *family = 0;
-    if (conv_per_tile_only()) return 0;
-    int rc = -100, fam = 0;
-    if (layer >= 1 && layer <= 3) { rc = launch_conv_bf16_big(layer, width, dgrad, a, st); fam = 2; }
-    else if (layer == 4 && width == 128 && !dgrad) { rc = launch_conv_bf16_ps(layer, width, dgrad, a, st); fam = 1; }
-    if (rc == -100) return 0;
-    *family = fam;
-    return rc;
-}
-int conv_bf16_route(int layer, int width, bool dgrad, int B) {
-    ConvBf16Args a{};
-    a.B = B;
-    int family = 0;
-    g_conv_dry = true;
-    (void)try_persistent_bf16(layer, width, dgrad, a, nullptr, &family);
-    g_conv_dry = false;
-    return family;
-}
-// `tilesPerPartial` (out, may be null): how many 128-pixel tiles one BatchNorm partial row of `bnpart` covers — 1 for the per-tile and the
-// two-workgroup persistent kernels, 4 for the items of conv_bf16_big.hip.  The caller hands it to launch_bn_fwd_finalize: the kernel that
-// actually ran decides, not a second reading of the switches.
+// launcher code ns (1 bf16, 3 / 6 the fp32-emulation modes with nine / six partial products) -> cvae_config precision
+static int ns_precision(int ns) { return ns == 1 ? 1 : (ns == 3 ? 2 : 3); }
+
+// `tilesPerPartial` (out, may be null): how many 128-pixel tiles one BatchNorm partial row of `bnpart` covers (conv_route) — 1 for the per-tile
+// and the two-workgroup persistent kernels, MT for the items of conv_bf16_big.hip.  The caller hands it to launch_bn_fwd_finalize.
 int launch_conv_fwd_bf16(int layer, int width, int ns, int B, const float* in, const float* packed, const float* bias, float* out,
                          float* bnpart, float* ws, hipStream_t st, int* tilesPerPartial) {
     ConvBf16Args a{in, pack_ptr(const_cast<float*>(packed), layer, 0, ns >= 3 ? 3 : 1), bias, out, bnpart, B, 0, nullptr, ns >= 3 ? pack_units(layer) : 0, ns == 6 ? 6 : 9};
-    if (tilesPerPartial) *tilesPerPartial = 1;
-    if (ns == 1) {       // the persistent kernels; the big-tile one emits one BatchNorm partial per item
-        int family;
-        const int rc = try_persistent_bf16(layer, width, false, a, st, &family);
-        if (family == 2 && tilesPerPartial) *tilesPerPartial = conv_bf16_big_tiles(layer, width, false);
-        if (family) return rc;
-    }
+    const ConvRoute r = conv_route(ns_precision(ns), layer, width, false, B);
+    if (tilesPerPartial) *tilesPerPartial = r.tilesPerPartial;
+    if (r.family == CONV_BIG) return launch_conv_bf16_big(layer, width, false, a, st);
+    if (r.family == CONV_PS) return launch_conv_bf16_ps(layer, width, false, a, st);
     if (width == 64) {
         switch (layer) {
             case 1: return run_bf16<32, 64, 32, 64, EPI_BIAS_BNSTAT>(a, st);
@@ -789,11 +764,9 @@ int launch_conv_fwd_bf16(int layer, int width, int ns, int B, const float* in, c
 
 int launch_conv_dgrad_bf16(int layer, int width, int ns, int B, const float* dout, const float* packed, float* din, float* ws, hipStream_t st) {
     ConvBf16Args a{dout, pack_ptr(const_cast<float*>(packed), layer, 1, ns >= 3 ? 3 : 1), nullptr, din, nullptr, B, 0, nullptr, ns >= 3 ? pack_units(layer) : 0, ns == 6 ? 6 : 9};
-    if (ns == 1) {
-        int family;
-        const int rc = try_persistent_bf16(layer, width, true, a, st, &family);
-        if (family) return rc;
-    }
+    const ConvFamily family = conv_route(ns_precision(ns), layer, width, true, B).family;
+    if (family == CONV_BIG) return launch_conv_bf16_big(layer, width, true, a, st);
+    if (family == CONV_PS) return launch_conv_bf16_ps(layer, width, true, a, st);
     if (width == 64) {
         switch (layer) {
             case 1: return run_bf16<64, 32, 32, 32, EPI_PLAIN>(a, st);

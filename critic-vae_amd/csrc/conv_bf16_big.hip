@@ -33,7 +33,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
 
 // raw buffer descriptor over a whole tensor (gfx9 word 3: DATA_FORMAT_32): a lane whose byte offset is >= bytes is dropped by the
-// bounds check, so "store if valid" needs no branch (tensors of 2 GiB and more do not take this kernel: run_big returns -100)
+// bounds check, so "store if valid" needs no branch (conv_route keeps tensors of 2 GiB and more off this kernel)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t big_rsrc(const void* p, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
 }
@@ -580,19 +580,12 @@ static int run_big(const ConvBf16Args& a, hipStream_t st) {
     constexpr int TILE_UNITS = IMGL ? OCT * (((PLPX + 15 - PAD) / 16) * 16 + PAD) : MT * OCT * Bf16Geom<H, OCT>::PSP;
     constexpr int SMEM = ((TDB ? 2 : 1) * TILE_UNITS + 2 * 5 * KB * 2 * NT + 256 + 4 * 32 * 9) * 16 + (EPI == EPI_BIAS_BNSTAT ? (2 * 4 * NT + NCH) * 4 : 0);
     static_assert(SMEM <= 160 * 1024, "LDS");
-    // 32-bit byte offsets and buffer descriptors inside: larger tensors take the per-tile kernels (size_t addressing)
-    if ((size_t)a.B * H * H * KCH * 2 >= (1ull << 31) || (size_t)a.B * H * H * NCH * 2 >= (1ull << 31)) return -100;
-    if (g_conv_dry) return 0;
+    // 32-bit byte offsets and buffer descriptors inside: conv_route keeps tensors of 2 GiB and more on the per-tile kernels (size_t addressing)
     auto kern = conv5x5_bf16_big_kernel<KCH, NCH, H, NT, MT, KB, EPI, TDB, IMGL, ALLC>;
     static DeviceOnce once;
     { int rc = cvae_grant_lds(once, reinterpret_cast<const void*>(kern), SMEM); if (rc) return rc; }
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG, numGroups = cdiv(numTiles, MT);
-    const int numItems = 8 * cdiv(numGroups, 8) * NY;
-    int G = cvae_num_cus();
-    if (conv_persist_maxwg() > 0 && G > conv_persist_maxwg()) G = conv_persist_maxwg();     // tests: several items per workgroup
-    G -= G % 8;
-    if (G < 8) G = 8;
-    if (G > numItems) G = numItems;
+    const int G = persistent_grid(1, 8 * cdiv(numGroups, 8) * NY);
     cvae_probe_begin(st);
     hipLaunchKernelGGL(kern, dim3(G), dim3(256), SMEM, st, a, numGroups);
     cvae_probe_end(st);
@@ -602,11 +595,9 @@ static int run_big(const ConvBf16Args& a, hipStream_t st) {
 
 // The layers this file serves, at both frame sizes.  Input gradients: E4 (256 -> 128, 4 x 4 wave tile), E3 (128 -> 64, 8 x 2), E2 (64 -> 32: an image-high item
 // on an 8 x 1 wave tile, 9 fragment reads per 8 MFMAs where the per-tile kernel reads 12: 192 vs 209 us at 64 x 64).  Forward (bias + ONE BatchNorm partial per
-// item of conv_bf16_big_tiles(..) tiles — the kernel that ran tells launch_bn_fwd_finalize): E3 (64 -> 128), E4 (128 -> 256), both 4 x 4, E2 (32 -> 64 as two
+// item of MT tiles — conv_route's tilesPerPartial, handed to launch_bn_fwd_finalize): E3 (64 -> 128), E4 (128 -> 256), both 4 x 4, E2 (32 -> 64 as two
 // 32-channel halves of an image-high item, 8 x 1: 196 vs 209 us on the two-workgroup persistent kernel at 64 x 64; as ONE 8 x 2 item it lost, 244 us: its 16-tile
 // BatchNorm epilogue was half of a 10-stage item, profiles/r05_k_big_image_layout.txt).
-int conv_bf16_big_tiles(int layer, int width, bool dgrad) { (void)width; return ((dgrad && layer == 2) || (!dgrad && layer == 1)) ? 8 : 4; }
-// returns -100 when the layer has no instantiation (or the tensors are too large for its 32-bit offsets)
 int launch_conv_bf16_big(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st) {
     if (dgrad) {
         if (width == 64 && layer == 3) return run_big<256, 128, 8, 128, 4, 1, EPI_PLAIN, true>(a, st);
@@ -623,5 +614,6 @@ int launch_conv_bf16_big(int layer, int width, bool dgrad, const ConvBf16Args& a
         if (width == 128 && layer == 3) return run_big<128, 256, 16, 128, 4, 1, EPI_BIAS_BNSTAT, true>(a, st);
         if (width == 128 && layer == 1) return run_big<32, 64, 64, 32, 8, 1, EPI_BIAS_BNSTAT, true>(a, st);
     }
-    return -100;
+    cvae_set_error("conv_bf16_big: no instantiation for layer %d %s at width %d", layer, dgrad ? "dgrad" : "fwd", width);
+    return -2;
 }

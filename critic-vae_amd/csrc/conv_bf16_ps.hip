@@ -344,20 +344,13 @@ static int run_ps(const ConvBf16Args& a, hipStream_t st) {
     constexpr int NY = NCH / NT;
     constexpr int SMEM = (2 * 4 * Bf16Geom<H, 4>::PSP + 5 * 2 * 2 * NT) * 16 + (NCH + 2 * 2 * 4 * NT) * 4 + 4 * NT * 36 * 2;
     static_assert(SMEM <= 80 * 1024, "two workgroups per CU");
-    // 32-bit byte offsets, a 32-bit num_records and 0x80000000 as the "skip this lane" offset inside: tensors of 2 GiB and more take the
-    // per-tile kernel (size_t addressing) — the caller falls back on -100
-    if ((size_t)a.B * H * H * KCH * 2 >= (1ull << 31) || (size_t)a.B * H * H * NCH * 2 >= (1ull << 31)) return -100;
-    if (g_conv_dry) return 0;
+    // 32-bit byte offsets, a 32-bit num_records and 0x80000000 as the "skip this lane" offset inside: conv_route keeps tensors of 2 GiB
+    // and more on the per-tile kernel (size_t addressing)
     auto kern = conv5x5_bf16_ps_kernel<KCH, NCH, H, NT, EPI>;
     static DeviceOnce once;
     { int rc = cvae_grant_lds(once, reinterpret_cast<const void*>(kern), SMEM); if (rc) return rc; }
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG, numPairs = cdiv(numTiles, 2);
-    const int numItems = 8 * cdiv(numPairs, 8) * NY;
-    int G = 2 * cvae_num_cus();
-    if (conv_persist_maxwg() > 0 && G > conv_persist_maxwg()) G = conv_persist_maxwg();     // tests: several items per workgroup
-    G -= G % 8;
-    if (G < 8) G = 8;
-    if (G > numItems) G = numItems;
+    const int G = persistent_grid(2, 8 * cdiv(numPairs, 8) * NY);
     cvae_probe_begin(st);
     hipLaunchKernelGGL(kern, dim3(G), dim3(256), SMEM, st, a, numPairs, numTiles);
     cvae_probe_end(st);
@@ -367,5 +360,6 @@ static int run_ps(const ConvBf16Args& a, hipStream_t st) {
 
 int launch_conv_bf16_ps(int layer, int width, bool dgrad, const ConvBf16Args& a, hipStream_t st) {
     if (layer == 4 && width == 128 && !dgrad) return run_ps<256, 128, 8, 64, EPI_BIAS_RELU>(a, st);
-    return -100;
+    cvae_set_error("conv_bf16_ps: no instantiation for layer %d %s at width %d", layer, dgrad ? "dgrad" : "fwd", width);
+    return -2;
 }

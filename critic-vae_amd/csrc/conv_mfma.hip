@@ -12,11 +12,47 @@
 // rows [32w,32w+32) of the tile and NB=NT/32 accumulator tiles.  K loop = 16-channel chunks x
 // 5 kernel rows: the input halo of a chunk is staged once in LDS as channel planes and reused
 // by all 25 taps; the weight slab of one kernel row is register-prefetched one stage ahead.
-// The decoder's nearest-2x Upsample (vae_nets.py:119,...) is never materialised: UP folds
-// src=(y>>1,x>>1) into the halo gather; its backward (2x2 sum) and the ReLU mask are the
-// POOLSUM epilogue of dgrad.
 #include "common.h"
 #include "conv_epilogue.h"
+
+
+// ---- which kernel serves a conv forward / input-gradient pass ----
+// The passes without a row run on the per-tile kernels of this file and conv_bf16.hip, as does every pass of the fp32-emulation modes
+// (precision 2, 3).
+struct ConvRouteRow { int precision, layer, width; bool dgrad; ConvFamily family; int tilesPerPartial; };
+static constexpr ConvRouteRow kConvRoutes[] = {
+    // fp32, conv_mfma_ps.hip: the 64-channel-tile layers — E2, E3 forward, E3 input gradient (-2.5 % each), and (round 5, once the kernel's
+    // operands travelled as buffer loads) E4 forward / input gradient at 64 x 64 on 64-channel tiles (step 87.90 -> 88.32 k img/s,
+    // profiles/r05_h_ps_buffer_loads.txt).  The 32-channel-tile form of E2's input gradient spills and loses.
+    {0, 1, 64, false, CONV_PS, 1}, {0, 2, 64, false, CONV_PS, 1}, {0, 3, 64, false, CONV_PS, 1},
+    {0, 2, 64, true, CONV_PS, 1}, {0, 3, 64, true, CONV_PS, 1},
+    {0, 1, 128, false, CONV_PS, 1}, {0, 2, 128, false, CONV_PS, 1}, {0, 2, 128, true, CONV_PS, 1},
+    // bf16, conv_bf16_big.hip: E2..E4, both passes, at both frame sizes (E2 forward 196 vs 209 us, E2 input gradient 192 vs 209 us at 64 x 64;
+    // at 128 x 128 E2's input gradient 379 vs 415 us, forward 424 vs 431: profiles/r05_g_big_mask_sweep.txt, r05_k_big_image_layout.txt,
+    // r05_r_e2_on_big_kernel.txt).  A forward item — one BatchNorm partial — is MT tiles of its run_big instantiation.
+    {1, 1, 64, false, CONV_BIG, 8}, {1, 2, 64, false, CONV_BIG, 4}, {1, 3, 64, false, CONV_BIG, 4},
+    {1, 1, 64, true, CONV_BIG, 1}, {1, 2, 64, true, CONV_BIG, 1}, {1, 3, 64, true, CONV_BIG, 1},
+    {1, 1, 128, false, CONV_BIG, 8}, {1, 2, 128, false, CONV_BIG, 4}, {1, 3, 128, false, CONV_BIG, 4},
+    {1, 1, 128, true, CONV_BIG, 1}, {1, 2, 128, true, CONV_BIG, 1}, {1, 3, 128, true, CONV_BIG, 1},
+    // bf16, conv_bf16_ps.hip: D0's forward at 128 x 128
+    {1, 4, 128, false, CONV_PS, 1},
+};
+
+ConvRoute conv_route(int precision, int layer, int width, bool dgrad, int64_t B) {
+    // CVAE_CONV_PER_TILE=1 (tests): every pass on the per-tile kernels
+    static const bool per_tile_only = [] { const char* e = getenv("CVAE_CONV_PER_TILE"); return e && e[0] == '1'; }();
+    const ConvRoute per_tile{CONV_PER_TILE, 1};
+    if (per_tile_only) return per_tile;
+    for (const ConvRouteRow& r : kConvRoutes) {
+        if (r.precision != precision || r.layer != layer || r.width != width || r.dgrad != dgrad) continue;
+        // the persistent kernels address both tensors with 32-bit byte offsets (and mark skipped lanes with the offset 0x80000000):
+        // when the larger one reaches 2 GiB the pass takes the per-tile kernel (size_t addressing)
+        const int64_t h = kLayers[layer].h * width / 64, c = kLayers[layer].cin > kLayers[layer].cout ? kLayers[layer].cin : kLayers[layer].cout;
+        if (B * h * h * c * (precision == 1 ? 2 : 4) >= (1ll << 31)) return per_tile;
+        return {r.family, r.tilesPerPartial};
+    }
+    return per_tile;
+}
 
 
 struct ConvArgs {
@@ -35,7 +71,7 @@ struct ConvArgs {
 template <int NT> struct KChunk { static constexpr int KC = NT == 32 ? 32 : 16, KCP = KC + 1; };
 
 
-template <int KCH, int NCH, int H, bool UP, bool DGRAD, int NT, int EPI, int KSPLIT>
+template <int KCH, int NCH, int H, bool DGRAD, int NT, int EPI, int KSPLIT>
 __global__ __launch_bounds__(256) void conv5x5_mfma_kernel(ConvArgs a) {
     using T = Tile<H>;
     constexpr int NB = NT / 32;
@@ -54,7 +90,6 @@ __global__ __launch_bounds__(256) void conv5x5_mfma_kernel(ConvArgs a) {
     const int tileInImg = mt % T::TILES_PER_IMG;
     const int img0 = (mt / T::TILES_PER_IMG) * T::IMGS;
     const int ty0 = (tileInImg / T::TILES_X) * T::TH, tx0 = (tileInImg % T::TILES_X) * T::TW;
-    constexpr int HS = UP ? H / 2 : H;   // stored spatial size of the input tensor
 
     // A operand: lane (li, lh) reads pixel m = 32*wave + li, channel 2j+lh of the chunk
     const int m = wave * 32 + li;
@@ -120,10 +155,8 @@ __global__ __launch_bounds__(256) void conv5x5_mfma_kernel(ConvArgs a) {
             const int hy = rem / T::HTW, hx = rem - hy * T::HTW;
             const int gy = ty0 + hy - 2, gx = tx0 + hx - 2, ib = img0 + img;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if ((NQ % 256 == 0 || q < NQ) && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)H && ib < a.B) {
-                const int sy = UP ? (gy >> 1) : gy, sx = UP ? (gx >> 1) : gx;
-                v = *reinterpret_cast<const f32x4*>(a.in + ((size_t)(ib * HS + sy) * HS + sx) * KCH + cc * KC + c4 * 4);
-            }
+            if ((NQ % 256 == 0 || q < NQ) && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)H && ib < a.B)
+                v = *reinterpret_cast<const f32x4*>(a.in + ((size_t)(ib * H + gy) * H + gx) * KCH + cc * KC + c4 * 4);
             ireg[i] = v;
         }
     };
@@ -208,13 +241,13 @@ __global__ __launch_bounds__(256) void conv5x5_mfma_kernel(ConvArgs a) {
     }
 }
 
-template <int KCH, int NCH, int H, bool UP, bool DGRAD, int NT, int EPI, int KSPLIT = 1>
+template <int KCH, int NCH, int H, bool DGRAD, int NT, int EPI, int KSPLIT = 1>
 static int run(const ConvArgs& a, hipStream_t st) {
     using T = Tile<H>;
     static_assert(KCH % KChunk<NT>::KC == 0 && NCH % NT == 0, "channel tiling");
     dim3 grid(cdiv(a.B, T::IMGS) * T::TILES_PER_IMG, NCH / NT, KSPLIT);
     cvae_probe_begin(st);
-    hipLaunchKernelGGL((conv5x5_mfma_kernel<KCH, NCH, H, UP, DGRAD, NT, EPI, KSPLIT>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((conv5x5_mfma_kernel<KCH, NCH, H, DGRAD, NT, EPI, KSPLIT>), grid, dim3(256), 0, st, a);
     cvae_probe_end(st);
     CVAE_CHECK_LAUNCH();
     return 0;
@@ -408,34 +441,18 @@ int64_t conv_fwd_ws_floats(int layer, int width, int B) {
     return (int64_t)D0_KSPLIT * B * h * h * kLayers[4].cout;
 }
 
-// conv_mfma_ps.hip: persistent form of E2..E4 forward / input gradient (-100: no instantiation, or a tensor of 2 GiB and more).
+// conv_mfma_ps.hip: persistent form of the passes routed to CONV_PS in fp32 mode
 int launch_conv_mfma_ps(int layer, int width, bool dgrad, int B, const float* in, const float* w, const float* bias, float* out, float* bnpart, hipStream_t st);
-// The passes that run on it: the 64-channel-tile layers — E2, E3 forward, E3 input gradient (-2.5 % each), and (round 5, once the kernel's operands travelled
-// as buffer loads) E4 forward / input gradient at 64 x 64 on 64-channel tiles (step 87.90 -> 88.32 k img/s, profiles/r05_h_ps_buffer_loads.txt).  The
-// 32-channel-tile form of E2's input gradient spills and loses.  CVAE_CONV_PER_TILE=1: none.
-static bool use_f32_ps(int layer, int width, bool dgrad) {
-    if (conv_per_tile_only()) return false;
-    if (layer == 3) return width == 64;
-    return layer == 2 || (layer == 1 && !dgrad);
-}
-
-int conv_f32_route(int layer, int width, bool dgrad, int B) {
-    if (!use_f32_ps(layer, width, dgrad)) return 0;
-    g_conv_dry = true;
-    const int rc = launch_conv_mfma_ps(layer, width, dgrad, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    g_conv_dry = false;
-    return rc == 0 ? 1 : 0;
-}
 
 int launch_conv_fwd(int layer, int width, int B, const float* in, const float* w, const float* bias,
                     float* out, float* bnpart, float* ws, hipStream_t st) {
-    if (use_f32_ps(layer, width, false)) { const int rc = launch_conv_mfma_ps(layer, width, false, B, in, w, bias, out, bnpart, st); if (rc != -100) return rc; }
+    if (conv_route(0, layer, width, false, B).family == CONV_PS) return launch_conv_mfma_ps(layer, width, false, B, in, w, bias, out, bnpart, st);
     ConvArgs a{in, w, bias, nullptr, out, bnpart, B, 0};
     if (width == 64) {
         switch (layer) {
-            case 1: return run<32, 64, 32, false, false, 64, EPI_BIAS_BNSTAT>(a, st);
-            case 2: return run<64, 128, 16, false, false, 64, EPI_BIAS_BNSTAT>(a, st);
-            case 3: return run<128, 256, 8, false, false, 32, EPI_BIAS_BNSTAT>(a, st);
+            case 1: return run<32, 64, 32, false, 64, EPI_BIAS_BNSTAT>(a, st);
+            case 2: return run<64, 128, 16, false, 64, EPI_BIAS_BNSTAT>(a, st);
+            case 3: return run<128, 256, 8, false, 32, EPI_BIAS_BNSTAT>(a, st);
             case 4: {     // D0: 4x4 images, K = 6400 -> split-K over channel chunks to fill the chip
                 const int64_t slice = (int64_t)B * 4 * 4 * 128;
                 a.out = ws; a.sliceFloats = slice;
@@ -450,10 +467,10 @@ int launch_conv_fwd(int layer, int width, int B, const float* in, const float* w
     }
     if (width == 128) {
         switch (layer) {
-            case 1: return run<32, 64, 64, false, false, 64, EPI_BIAS_BNSTAT>(a, st);
-            case 2: return run<64, 128, 32, false, false, 64, EPI_BIAS_BNSTAT>(a, st);
-            case 3: return run<128, 256, 16, false, false, 64, EPI_BIAS_BNSTAT>(a, st);
-            case 4: return run<256, 128, 8, false, false, 64, EPI_BIAS_RELU>(a, st);
+            case 1: return run<32, 64, 64, false, 64, EPI_BIAS_BNSTAT>(a, st);
+            case 2: return run<64, 128, 32, false, 64, EPI_BIAS_BNSTAT>(a, st);
+            case 3: return run<128, 256, 16, false, 64, EPI_BIAS_BNSTAT>(a, st);
+            case 4: return run<256, 128, 8, false, 64, EPI_BIAS_RELU>(a, st);
         }
     }
     cvae_set_error("conv_fwd: unsupported layer %d at width %d", layer, width);
@@ -471,7 +488,7 @@ int64_t conv_dgrad_ws_floats(int layer, int width, int B) {
 int launch_conv_dgrad(int layer, int width, int B, const float* dout, const float* w,
                       const float* mask_src, float* din, float* ws, hipStream_t st) {
     // KCH = layer Cout (channels of dout), NCH = layer Cin (channels of din)
-    if (!mask_src && use_f32_ps(layer, width, true)) { const int rc = launch_conv_mfma_ps(layer, width, true, B, dout, w, nullptr, din, nullptr, st); if (rc != -100) return rc; }
+    if (!mask_src && conv_route(0, layer, width, true, B).family == CONV_PS) return launch_conv_mfma_ps(layer, width, true, B, dout, w, nullptr, din, nullptr, st);
     ConvArgs a{dout, w, nullptr, mask_src, din, nullptr, B, 0};
     if (width == 64 && layer == 4 && ws != nullptr) {
         const int64_t slice = (int64_t)B * 16 * 256;
@@ -482,18 +499,18 @@ int launch_conv_dgrad(int layer, int width, int B, const float* dout, const floa
     }
     if (width == 64) {
         switch (layer) {
-            case 1: return run<64, 32, 32, false, true, 32, EPI_PLAIN>(a, st);
-            case 2: return run<128, 64, 16, false, true, 64, EPI_PLAIN>(a, st);
-            case 3: return run<256, 128, 8, false, true, 32, EPI_PLAIN>(a, st);
-            case 4: return run<128, 256, 4, false, true, 32, EPI_PLAIN>(a, st);
+            case 1: return run<64, 32, 32, true, 32, EPI_PLAIN>(a, st);
+            case 2: return run<128, 64, 16, true, 64, EPI_PLAIN>(a, st);
+            case 3: return run<256, 128, 8, true, 32, EPI_PLAIN>(a, st);
+            case 4: return run<128, 256, 4, true, 32, EPI_PLAIN>(a, st);
         }
     }
     if (width == 128) {
         switch (layer) {
-            case 1: return run<64, 32, 64, false, true, 32, EPI_PLAIN>(a, st);
-            case 2: return run<128, 64, 32, false, true, 64, EPI_PLAIN>(a, st);
-            case 3: return run<256, 128, 16, false, true, 64, EPI_PLAIN>(a, st);
-            case 4: return run<128, 256, 8, false, true, 64, EPI_PLAIN>(a, st);
+            case 1: return run<64, 32, 64, true, 32, EPI_PLAIN>(a, st);
+            case 2: return run<128, 64, 32, true, 64, EPI_PLAIN>(a, st);
+            case 3: return run<256, 128, 16, true, 64, EPI_PLAIN>(a, st);
+            case 4: return run<128, 256, 8, true, 64, EPI_PLAIN>(a, st);
         }
     }
     cvae_set_error("conv_dgrad: unsupported layer %d at width %d", layer, width);

@@ -15,7 +15,7 @@
 //     issue order; buffer stores with an out-of-range offset for invalid lanes keep every wait counted).
 // Measured (MI355X, B = 256, rocprofv3): the 64-channel-tile layers gain 2-3 % (E2 forward 222.5 -> 216.7 us, E3 forward 215.2 ->
 // 209.4, E3 input gradient 212.4 -> 208.0); the 32-channel-tile instantiations (KC = 32: 36 staging registers more) spill under
-// the 256-register budget and lose (E2 input gradient 222 -> 262 us) — they stay on the per-tile kernel (conv_mfma.hip, use_f32_ps).
+// the 256-register budget and lose (E2 input gradient 222 -> 262 us) — they stay on the per-tile kernel (conv_mfma.hip, conv_route).
 // BatchNorm partials: per tile and channel (sum, M2 about the tile mean), M2 = Q - S*S/n in double from the per-wave fp32 sums of
 // the biased accumulators; the sums themselves are exact-order-fixed (bitwise reproducible), the values summed are the same fp32
 // accumulators as in the per-tile kernel.
@@ -283,17 +283,9 @@ template <int KCH, int NCH, int H, bool DGRAD, int NT, int EPI>
 static int run_mfma_ps(const ConvPsArgs& a, hipStream_t st) {
     using T = Tile<H>;
     constexpr int NY = NCH / NT;
-    // the kernel addresses both tensors with 32-bit byte offsets and marks skipped lanes with the offset 0x80000000: tensors of 2 GiB and
-    // more take the per-tile kernel (size_t addressing) — the caller falls back on -100
-    if ((size_t)a.B * H * H * KCH * 4 >= (1ull << 31) || (size_t)a.B * H * H * NCH * 4 >= (1ull << 31)) return -100;
-    if (g_conv_dry) return 0;
+    // the kernel addresses both tensors with 32-bit byte offsets: conv_route keeps tensors of 2 GiB and more on the per-tile kernel
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG;
-    const int numItems = cdiv(numTiles, 8) * 8 * NY;
-    int G = 2 * cvae_num_cus();
-    if (conv_persist_maxwg() > 0 && G > conv_persist_maxwg()) G = conv_persist_maxwg();     // tests: several items per workgroup
-    G -= G % 8;
-    if (G < 8) G = 8;
-    if (G > numItems) G = numItems;
+    const int G = persistent_grid(2, cdiv(numTiles, 8) * 8 * NY);
     cvae_probe_begin(st);
     hipLaunchKernelGGL((conv5x5_mfma_ps_kernel<KCH, NCH, H, DGRAD, NT, EPI>), dim3(G), dim3(256), 0, st, a, numTiles);
     cvae_probe_end(st);
@@ -301,8 +293,8 @@ static int run_mfma_ps(const ConvPsArgs& a, hipStream_t st) {
     return 0;
 }
 
-// returns -100 when the layer has no persistent instantiation (the caller falls back to the per-tile kernel): E2 / E3 / E4 forward,
-// E3 / E4 input gradient at 64 x 64; E2 / E3 forward and E3 input gradient at 128 x 128.
+// the passes conv_route sends to CONV_PS in fp32 mode: E2 / E3 / E4 forward, E3 / E4 input gradient at 64 x 64; E2 / E3 forward and E3
+// input gradient at 128 x 128.
 int launch_conv_mfma_ps(int layer, int width, bool dgrad, int B, const float* in, const float* w, const float* bias, float* out, float* bnpart, hipStream_t st) {
     const ConvPsArgs a{in, w, bias, out, bnpart, B};
     if (!dgrad) {
@@ -330,5 +322,6 @@ int launch_conv_mfma_ps(int layer, int width, bool dgrad, int B, const float* in
             }
         }
     }
-    return -100;
+    cvae_set_error("conv_mfma_ps: no instantiation for layer %d %s at width %d", layer, dgrad ? "dgrad" : "fwd", width);
+    return -2;
 }

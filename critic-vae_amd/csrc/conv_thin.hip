@@ -1157,7 +1157,7 @@ __global__ __launch_bounds__(256) void d4_actbwd_kernel(const float* __restrict_
 }
 
 // tile mt of the D4 backward into registers: dOut halo planes [3][20][36] (zero padded) and the o3 tile
-template <int H, typename AT>
+template <int H>
 __device__ __forceinline__ void d4_bwd_fetch(const ThinWgradArgs& a, int mt, float (&rg)[(3 * 720 + 255) / 256], f32x4 (&ro)[4], unsigned& okm) {
     constexpr int HS = H / 2, TPI = (HS / 8) * (HS / 16), G0 = 3 * 720;
     const int tid = threadIdx.x;
@@ -1174,11 +1174,11 @@ __device__ __forceinline__ void d4_bwd_fetch(const ThinWgradArgs& a, int mt, flo
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int q = tid + i * 256, c4 = q & 7, sp = q >> 3;
-        ro[i] = Act<AT>::ld4(a.a1, ((size_t)(ib * HS + sy0 + sp / 16) * HS + sx0 + sp % 16) * 32 + c4 * 4);
+        ro[i] = *reinterpret_cast<const f32x4*>(a.a1 + ((size_t)(ib * HS + sy0 + sp / 16) * HS + sx0 + sp % 16) * 32 + c4 * 4);
     }
 }
 
-template <int H, typename AT>   // H = output size (64); src tiles of 8 rows x 16 cols at HS = H/2; o3 / d_o3 stored as AT
+template <int H>   // H = output size (64); src tiles of 8 rows x 16 cols at HS = H/2; o3 / d_o3 fp32 (bf16 mode: d4_bwd_bf16_kernel)
 __global__ __launch_bounds__(256, THIN_F32_OCC) void d4_bwd_kernel(ThinWgradArgs a) {
     constexpr int HS = H / 2, TPI = (HS / 8) * (HS / 16);
     constexpr int G0 = 3 * 720, O = 128 * 32, G = 128 * 77 + 32, WR = 76 * 32;
@@ -1207,7 +1207,7 @@ __global__ __launch_bounds__(256, THIN_F32_OCC) void d4_bwd_kernel(ThinWgradArgs
     float rg[GQ];
     unsigned okm = 0u;
     f32x4 ro[4];
-    if (t0 < t1) d4_bwd_fetch<H, AT>(a, t0, rg, ro, okm);
+    if (t0 < t1) d4_bwd_fetch<H>(a, t0, rg, ro, okm);
     const int gsp = tid & 127, ghalf = tid >> 7, gsy = gsp >> 4, gsx = gsp & 15;
     for (int mt = t0; mt < t1; ++mt) {
         const int ib = mt / TPI, t = mt % TPI;
@@ -1224,7 +1224,7 @@ __global__ __launch_bounds__(256, THIN_F32_OCC) void d4_bwd_kernel(ThinWgradArgs
             *reinterpret_cast<f32x4*>(lds_o + (q >> 3) * 32 + (q & 7) * 4) = ro[i];
         }
         __syncthreads();
-        if (mt + 1 < t1) d4_bwd_fetch<H, AT>(a, mt + 1, rg, ro, okm);
+        if (mt + 1 < t1) d4_bwd_fetch<H>(a, mt + 1, rg, ro, okm);
         __builtin_amdgcn_sched_barrier(0);            // keep the loads HERE (the scheduler sank them below the MFMAs: nothing was prefetched)
         // G[src][(r*5+s)*3+co] = sum of dOut over the 2x2 block of src shifted by the tap: thread =
         // (src pixel, half of the 15 (co, r) pairs); the five s taps of a pair share six column sums
@@ -1259,7 +1259,7 @@ __global__ __launch_bounds__(256, THIN_F32_OCC) void d4_bwd_kernel(ThinWgradArgs
         for (int v = 0; v < 16; ++v) {
             const int sp = wave * 32 + (v & 3) + 8 * (v >> 2) + 4 * lh;
             const float x = lds_o[sp * 32 + li] > 0.f ? accd[v] : 0.f;
-            Act<AT>::st(a.din, ((size_t)(ib * HS + sy0 + sp / 16) * HS + sx0 + sp % 16) * 32 + li, x);
+            a.din[((size_t)(ib * HS + sy0 + sp / 16) * HS + sx0 + sp % 16) * 32 + li] = x;
         }
         // wgrad: dW[k][ci] += sum_src G[src][k] * o3[src][ci]
 #pragma unroll
@@ -1512,8 +1512,8 @@ int launch_d4_bwd(int width, int B, const float* o3, const float* d_recon, const
     }
     ThinWgradArgs a{bf16io ? d_recon : dout, bf16io ? recon : nullptr, o3, w, d_o3, ws, B, tiles, tps};
     static DeviceOnce once[4];
-    void (*kern)(ThinWgradArgs) = width == 64 ? (bf16io ? d4_bwd_bf16_kernel<64> : d4_bwd_kernel<64, float>)
-                                              : (bf16io ? d4_bwd_bf16_kernel<128> : d4_bwd_kernel<128, float>);
+    void (*kern)(ThinWgradArgs) = width == 64 ? (bf16io ? d4_bwd_bf16_kernel<64> : d4_bwd_kernel<64>)
+                                              : (bf16io ? d4_bwd_bf16_kernel<128> : d4_bwd_kernel<128>);
     const int smem_bytes = bf16io ? D4_BWD_BF16_SMEM : D4_BWD_SMEM;
     { int rc = cvae_grant_lds(once[(width == 128) * 2 + bf16io], reinterpret_cast<const void*>(kern), smem_bytes); if (rc) return rc; }
     cvae_probe_begin(st);

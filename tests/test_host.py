@@ -77,7 +77,7 @@ CONV_ROUTES = {
 def test_persistent_conv_kernels_refuse_tensors_of_two_gib():
     """The persistent conv kernels (conv_bf16_big.hip, conv_bf16_ps.hip, conv_mfma_ps.hip) address their tensors with 32-bit byte offsets
     and buffer descriptors; their launchers must hand an activation of 2 GiB or more to the per-tile kernels (64-bit addressing).
-    cvae_conv_route walks the launchers' own decision path up to the launch (no device access): the family changes exactly where
+    cvae_conv_route reads the route table the launchers read (conv_route, no device access): the family changes exactly where
     the larger of a layer's two tensors crosses 2^31 bytes.  The whole route table is pinned (CONV_ROUTES), and CVAE_CONV_PER_TILE=1 sends
     every pass to the per-tile kernels.  Child processes, so that no CVAE_* switch of the caller changes the routes."""
     code = """
