@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -555,6 +556,54 @@ int cvae_preprocess_u8(cvae_handle h, int32_t B, const uint8_t* frames_hwc, floa
 int cvae_diff_grey(cvae_handle h, int32_t B, const float* recon_one, const float* recon_zero, float* diff, void* stream) {
     if (!h || B < 1) { cvae_set_error("cvae_diff_grey: bad handle/batch"); return CVAE_EINVAL; }
     return launch_diff_grey(h->cfg.width, B, recon_one, recon_zero, diff, (hipStream_t)stream);
+}
+
+// ---- segmentation evaluation (eval_textured_frames, vae_utility.py:162-212; kernels in segment.hip) ----
+// batch is not capped by max_batch; the per-pixel launches need batch * W * W < 2^31 work-items
+static bool seg_batch_ok(cvae_handle h, int32_t B, const char* who) {
+    if (!h) { cvae_set_error("%s: null handle", who); return false; }
+    const int W = h->cfg.width;
+    if (W != 64 && W != 128) { cvae_set_error("%s: width %d not supported (64 or 128)", who, W); return false; }
+    if (B < 1 || (int64_t)B * W * W > 0x7fffffffLL) { cvae_set_error("%s: batch %d outside [1, 2^31 / (%d * %d))", who, B, W, W); return false; }
+    return true;
+}
+
+int64_t cvae_crf_scratch_bytes(cvae_handle h, int32_t B) {
+    if (!seg_batch_ok(h, B, "cvae_crf_scratch_bytes")) return CVAE_EINVAL;
+    return crf_scratch_bytes(h->cfg.width, B);
+}
+
+int cvae_dense_crf(cvae_handle h, int32_t B, const uint8_t* frames_hwc, const float* prob1, const cvae_crf_params* p,
+                   uint8_t* labels, float* q1, void* scratch, void* stream) {
+    if (!seg_batch_ok(h, B, "cvae_dense_crf")) return CVAE_EINVAL;
+    if (!frames_hwc || !prob1 || !p || !labels || !scratch) { cvae_set_error("cvae_dense_crf: null frames, prob1, params, labels or scratch"); return CVAE_EINVAL; }
+    const float fin[6] = {p->w1, p->alpha, p->beta, p->w2, p->gamma, p->p_floor};
+    for (float v : fin)
+        if (!std::isfinite(v)) { cvae_set_error("cvae_dense_crf: non-finite parameter"); return CVAE_EINVAL; }
+    if (p->w1 < 0.f || p->w2 < 0.f) { cvae_set_error("cvae_dense_crf: weights w1 %g, w2 %g must be >= 0", p->w1, p->w2); return CVAE_EINVAL; }
+    if (!(p->alpha > 0.f && p->beta > 0.f && p->gamma > 0.f)) { cvae_set_error("cvae_dense_crf: alpha %g, beta %g, gamma %g must be > 0", p->alpha, p->beta, p->gamma); return CVAE_EINVAL; }
+    if (!(p->p_floor > 0.f && p->p_floor <= 1.f)) { cvae_set_error("cvae_dense_crf: p_floor %g outside (0, 1]", p->p_floor); return CVAE_EINVAL; }
+    if (p->iterations < 0 || p->iterations > 10000) { cvae_set_error("cvae_dense_crf: iterations %d outside [0, 10000]", p->iterations); return CVAE_EINVAL; }
+    if (((uintptr_t)scratch & 255) != 0) { cvae_set_error("cvae_dense_crf: scratch not 256-byte aligned"); return CVAE_EINVAL; }
+    return launch_dense_crf(h->cfg.width, B, frames_hwc, prob1, *p, labels, q1, scratch, (hipStream_t)stream);
+}
+
+int cvae_diff_normalize(cvae_handle h, int32_t B, const float* diff, double mean_max, double diff_factor, int32_t thr,
+                        const uint8_t* gt, uint8_t* diff_u8, uint8_t* mask, int64_t* counts, int64_t* hist, void* stream) {
+    if (!seg_batch_ok(h, B, "cvae_diff_normalize")) return CVAE_EINVAL;
+    if (!diff || !diff_u8) { cvae_set_error("cvae_diff_normalize: null diff or diff_u8"); return CVAE_EINVAL; }
+    if (!std::isfinite(mean_max) || !std::isfinite(diff_factor) || mean_max < 0.0 || diff_factor < 0.0) {
+        cvae_set_error("cvae_diff_normalize: mean_max %g, diff_factor %g must be finite and >= 0", mean_max, diff_factor); return CVAE_EINVAL;
+    }
+    if (thr < 0 || thr > 255) { cvae_set_error("cvae_diff_normalize: thr %d outside [0, 255]", thr); return CVAE_EINVAL; }
+    if ((counts || hist) && !gt) { cvae_set_error("cvae_diff_normalize: frame counts and histogram need the ground truth"); return CVAE_EINVAL; }
+    return launch_diff_normalize(h->cfg.width, B, diff, mean_max, diff_factor, thr, gt, diff_u8, mask, counts, hist, (hipStream_t)stream);
+}
+
+int cvae_mask_counts(cvae_handle h, int32_t B, const uint8_t* mask, const uint8_t* gt, int64_t* counts, void* stream) {
+    if (!seg_batch_ok(h, B, "cvae_mask_counts")) return CVAE_EINVAL;
+    if (!mask || !gt || !counts) { cvae_set_error("cvae_mask_counts: null mask, gt or frame_counts"); return CVAE_EINVAL; }
+    return launch_mask_counts(h->cfg.width, B, mask, gt, counts, (hipStream_t)stream);
 }
 
 // ---- probe API: bracket chosen conv kernels of the real step with HIP events (bench.py roofline) ----

@@ -283,6 +283,13 @@ int critic_param_count();
 int launch_critic_fwd(int width, int B, const float* x, const float* critic_params, float* pred, hipStream_t st);
 int launch_preprocess_u8(int width, int B, const uint8_t* u8, float* x, hipStream_t st);
 int launch_diff_grey(int width, int B, const float* a, const float* b, float* diff, hipStream_t st);
+// segment.hip
+int64_t crf_scratch_bytes(int width, int B);
+int launch_dense_crf(int width, int B, const uint8_t* frames, const float* prob1, const struct cvae_crf_params& p,
+                     uint8_t* labels, float* q1, void* scratch, hipStream_t st);
+int launch_diff_normalize(int width, int B, const float* diff, double mean_max, double factor, int thr, const uint8_t* gt,
+                          uint8_t* u8, uint8_t* mask, int64_t* counts, int64_t* hist, hipStream_t st);
+int launch_mask_counts(int width, int B, const uint8_t* mask, const uint8_t* gt, int64_t* counts, hipStream_t st);
 // adam.hip
 int launch_grads_bf16(const float* src_f32, void* bf16_buf, float* dst_f32, int64_t n, hipStream_t st);   // src set: pack; else unpack
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1,

@@ -23,6 +23,12 @@ class _Config(C.Structure):
                 ("overlap_wgrad", C.c_int32), ("precision", C.c_int32)]
 
 
+class CrfParams(C.Structure):
+    """cvae_crf_params (include/cvae.h): the (w1, alpha, beta, w2, gamma, it) of crf(), vae_utility.py:22-54, plus the unary floor."""
+    _fields_ = [("w1", C.c_float), ("alpha", C.c_float), ("beta", C.c_float), ("w2", C.c_float),
+                ("gamma", C.c_float), ("p_floor", C.c_float), ("iterations", C.c_int32)]
+
+
 def build(verbose=False):
     """Compile the HIP sources for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     r = subprocess.run(["make", "-j8", "-C", os.path.join(_HERE, "csrc")],
@@ -63,6 +69,10 @@ _SIGS = {
     "cvae_critic_forward": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_preprocess_u8": (C.c_int, [_p, _i32, _p, _p, _p]),
     "cvae_diff_grey": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
+    "cvae_diff_normalize": (C.c_int, [_p, _i32, _p, C.c_double, C.c_double, _i32] + [_p] * 6),
+    "cvae_mask_counts": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
+    "cvae_crf_scratch_bytes": (_i64, [_p, _i32]),
+    "cvae_dense_crf": (C.c_int, [_p, _i32, _p, _p, C.POINTER(CrfParams), _p, _p, _p, _p]),
     "cvae_probe_config": (C.c_int, [_p, C.c_uint32]),
     "cvae_probe_read": (C.c_int, [_p, _i32, C.POINTER(C.c_float), _i32]),
     "cvae_op_scratch_floats": (_i64, [_p, _i32]),
@@ -225,6 +235,43 @@ class Handle:
 
     def diff_grey(self, B, recon_one, recon_zero, diff):
         self._check(self.lib.cvae_diff_grey(self.h, B, _ptr(recon_one), _ptr(recon_zero), _ptr(diff), _stream()))
+
+    # ---- segmentation evaluation (eval_textured_frames, vae_utility.py:162-212) ----
+    @staticmethod
+    def _u8(t, what):
+        if t is None:
+            return None
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous(), f"{what}: need a contiguous uint8 device tensor"
+        return t.data_ptr()
+
+    @staticmethod
+    def _i64(t, what):
+        if t is None:
+            return None
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous(), f"{what}: need a contiguous int64 device tensor"
+        return t.data_ptr()
+
+    def diff_normalize(self, B, diff, mean_max, diff_factor, thr, gt, diff_u8, mask=None, counts=None, hist=None):
+        """uint8 masks of the set-wide normalisation; counts (B,3) (tp, fn, fp); hist (2,256) is ADDED to."""
+        self._check(self.lib.cvae_diff_normalize(self.h, B, _ptr(diff), float(mean_max), float(diff_factor), int(thr),
+                                                 self._u8(gt, "gt"), self._u8(diff_u8, "diff_u8"), self._u8(mask, "mask"),
+                                                 self._i64(counts, "counts"), self._i64(hist, "hist"), _stream()))
+
+    def mask_counts(self, B, mask, gt, counts):
+        self._check(self.lib.cvae_mask_counts(self.h, B, self._u8(mask, "mask"), self._u8(gt, "gt"),
+                                              self._i64(counts, "counts"), _stream()))
+
+    def crf_scratch_bytes(self, B):
+        n = self.lib.cvae_crf_scratch_bytes(self.h, B)
+        if n < 0:
+            raise CvaeError(f"cvae_crf_scratch_bytes: {self.lib.cvae_last_error().decode()}")
+        return n
+
+    def dense_crf(self, B, frames_u8, prob1, params, labels, q1, scratch):
+        """params: CrfParams; scratch: a device tensor of at least crf_scratch_bytes(B) bytes."""
+        assert scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= self.crf_scratch_bytes(B)
+        self._check(self.lib.cvae_dense_crf(self.h, B, self._u8(frames_u8, "frames"), _ptr(prob1), C.byref(params),
+                                            self._u8(labels, "labels"), _ptr(q1), scratch.data_ptr(), _stream()))
 
     # ---- in-step kernel probe (bench.py roofline) ----
     def probe_config(self, ids):

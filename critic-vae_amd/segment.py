@@ -1,0 +1,315 @@
+"""Critic-guided segmentation: the evaluation of `python vae.py -video [-thresh]` (eval_textured_frames,
+vae_utility.py:162-212) on the MI355X.
+
+Per frame the critic value and the difference mask (VariationalAutoencoder.diff_images); over the whole set the
+normalisation by the mean of the per-frame maxima, the uint8 mask and its threshold (cvae_diff_normalize), the
+IoU against the ground truth, a dense CRF that refines every thresholded mask (cvae_dense_crf) and a second IoU,
+and the per-critic-value-bin statistics of save_bin_info.  PIL frame composition and the GIF are not reproduced.
+
+The CRF is an EXACT mean-field solution of the model SimpleCRF's denseCRF.densecrf names (include/cvae.h): every
+pairwise sum runs over all pixel pairs, where the densecrf library approximates the bilateral filter with a
+permutohedral lattice.  Its unary clamps probabilities at `p_floor` (default 1e-5, the `clip` default of the common
+unary_from_softmax helper); whether SimpleCRF clamps a 0/1 mask the same way has not been checked against SimpleCRF.
+
+    python -m critic_vae_amd.segment -video [-thresh] --frames X.npy --gt Y.npy --networks DIR [--critic CKPT]
+"""
+import argparse
+import os
+import statistics
+import sys
+from collections import defaultdict
+
+import numpy as np
+import torch
+
+from .lib import CrfParams, Handle
+
+CRF_REF = (22, 12, 3.1, 8, 1.8, 10)     # (w1, alpha, beta, w2, gamma, it) of crf(), vae_utility.py:25-30
+THRESHOLD = 50                          # vae_utility.py:17
+P_FLOOR = 1e-5                          # unary clamp (unary_from_softmax's clip default; unverified against SimpleCRF)
+SWEEP = tuple(range(0, 130, 10))        # the -thresh loop, vae.py:121
+BIN_FRAMES_DENOM = 1200                 # save_bin_info_file divides frame counts by a fixed 1200 (vae_utility.py:123)
+ENCODER_FILE, DECODER_FILE = "vae_encoder.pt", "vae_decoder.pt"            # vae_parameters.py:29-30
+CRITIC_FILE = "critic-rewidx=1-cepochs=15-datamode=trunk-datasize=99999-shift=12-chfak=1-dropout=0.3.pt"   # vae_parameters.py:46
+
+_handles = {}
+
+
+def _handle(width):
+    """A library handle for the entries that need only the frame width (none of them is capped by max_batch)."""
+    dev = torch.cuda.current_device()
+    h = _handles.get((width, dev))
+    if h is None:
+        h = _handles[(width, dev)] = Handle(width, 1)
+    return h
+
+
+def _cuda(a, dtype):
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to("cuda", dtype).contiguous()
+
+
+def _np(t):
+    return t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+# ---- IoU (get_iou, vae_utility.py:56-68) ----
+def iou_from_counts(tp, fn, fp):
+    """tp / (tp + fn + fp), 1 when the union is empty, rounded to 3 places on the host."""
+    tp, fn, fp = int(tp), int(fn), int(fp)
+    if tp + fn + fp == 0:
+        return 1
+    return round(tp / (tp + fn + fp), 3)
+
+
+def iou(G, T):
+    """get_iou(G, T) on boolean arrays of any (equal) shape."""
+    G, T = _np(G).astype(bool), _np(T).astype(bool)
+    return iou_from_counts(np.sum(G & T), np.sum(G & ~T), np.sum(~G & T))
+
+
+def iou_from_hist(hist, t):
+    """Set-wide IoU of the mask diff_u8 > t from the (2,256) histograms of cvae_diff_normalize (row 0: gt set,
+    row 1: gt clear): a threshold sweep never re-reads the masks."""
+    hist = _np(hist).astype(np.int64)
+    return iou_from_counts(hist[0, t + 1:].sum(), hist[0, :t + 1].sum(), hist[1, t + 1:].sum())
+
+
+# ---- normalisation + threshold (get_diff_factor / prepare_diff / get_diff_and_thr_masks) ----
+def diff_factor(max_values):
+    """get_diff_factor (vae_utility.py:106-110): (1 / mean_max or 0, mean_max), mean_max = statistics.mean."""
+    mean_max = statistics.mean(float(m) for m in _np(max_values).reshape(-1))
+    return (1.0 / mean_max if mean_max != 0 else 0), mean_max
+
+
+def _normalize(diff, max_values, t=THRESHOLD, gt=None, mask=False, counts=False, hist=None):
+    diff = _cuda(diff, torch.float32)
+    B, W = diff.shape[0], diff.shape[-1]
+    factor, mean_max = diff_factor(max_values)
+    u8 = torch.empty(B, W, W, dtype=torch.uint8, device=diff.device)
+    m = torch.empty_like(u8) if mask else None
+    c = torch.empty(B, 3, dtype=torch.int64, device=diff.device) if counts else None
+    _handle(W).diff_normalize(B, diff, mean_max, factor, t, gt, u8, m, c, hist)
+    return u8, m, c, mean_max
+
+
+def normalize_diffs(diff, max_values):
+    """(B,W,W) float difference masks + per-frame maxima -> (diff_u8 (B,W,W) uint8 on the device, mean_max):
+    trunc((min(d, mean_max) * diff_factor) * 255) in float64, as prepare_diff + astype(np.uint8)."""
+    u8, _, _, mean_max = _normalize(diff, max_values)
+    return u8, mean_max
+
+
+def threshold_masks(diff, max_values, t=THRESHOLD):
+    """get_diff_and_thr_masks (vae_utility.py:148-160): (diff_u8, diff_u8 > t), both (B,W,W) on the device."""
+    u8, m, _, _ = _normalize(diff, max_values, t, mask=True)
+    return u8, m.bool()
+
+
+# ---- dense CRF (crf, vae_utility.py:22-54) ----
+def crf_params(params=CRF_REF, p_floor=P_FLOOR):
+    w1, alpha, beta, w2, gamma, it = params
+    return CrfParams(float(w1), float(alpha), float(beta), float(w2), float(gamma), float(p_floor), int(it))
+
+
+def dense_crf(frames_u8, prob_or_mask, params=CRF_REF, p_floor=P_FLOOR, return_q1=False):
+    """frames_u8 (B,W,W,3) uint8 RGB, prob_or_mask (B,W,W): a 0/1 mask or the probability of label 1 (the
+    reference passes prob = stack(1 - m, m)) -> labels (B,W,W) bool on the device [, Q(1) (B,W,W) fp32].
+    One call for any B; params = (w1, alpha, beta, w2, gamma, it)."""
+    frames = _cuda(frames_u8, torch.uint8)
+    prob1 = _cuda(prob_or_mask, torch.float32)
+    B, W = frames.shape[0], frames.shape[1]
+    assert frames.shape == (B, W, W, 3) and prob1.shape == (B, W, W), (tuple(frames.shape), tuple(prob1.shape))
+    h = _handle(W)
+    p = crf_params(params, p_floor)
+    labels = torch.empty(B, W, W, dtype=torch.uint8, device=frames.device)
+    q1 = torch.empty(B, W, W, device=frames.device) if return_q1 else None
+    scratch = torch.empty(h.crf_scratch_bytes(B), dtype=torch.uint8, device=frames.device)
+    h.dense_crf(B, frames, prob1, p, labels, q1, scratch)
+    return (labels.bool(), q1) if return_q1 else labels.bool()
+
+
+def mask_counts(mask, gt):
+    """per-frame (tp, fn, fp) of get_iou(gt, mask), (B,3) int64 on the device"""
+    mask, gt = _cuda(mask, torch.uint8), _cuda(gt, torch.uint8)
+    c = torch.empty(mask.shape[0], 3, dtype=torch.int64, device=mask.device)
+    _handle(mask.shape[-1]).mask_counts(mask.shape[0], mask, gt, c)
+    return c
+
+
+# ---- per-critic-value bins (save_bin_info / save_bin_info_file, vae_utility.py:112-146) ----
+def bin_info(preds, gt, thr_masks):
+    """{"ious", "frames", "gts"}: dicts keyed by round(pred, 1) in first-seen order, as save_bin_info builds them."""
+    preds = _np(preds).reshape(-1)
+    gt, thr_masks = _np(gt).astype(bool), _np(thr_masks).astype(bool)
+    ious, frames, gts = defaultdict(list), defaultdict(int), defaultdict(int)
+    for i, pred in enumerate(preds):
+        b = round(float(pred), 1)
+        ious[b].append(iou(thr_masks[i], gt[i]))
+        frames[b] += 1
+        gts[b] += gt[i].sum()
+    return {"ious": dict(ious), "frames": dict(frames), "gts": dict(gts)}
+
+
+def bin_info_text(bins):
+    """The text of save_bin_info_file.  Where the reference's statistics.stdev raises (a bin of one frame), the
+    std is written as nan; a set without ground-truth pixels gives nan percentages, as numpy's division does."""
+    ious, frames, gts = bins["ious"], bins["frames"], bins["gts"]
+    total_gt = np.sum(list(gts.values()))
+    out = ["ground truth pixels sorted by bin:\n"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for b, count in gts.items():
+            out.append(f"bin: {b}, pixels = {count} = {round(np.int64(count) / total_gt, 2) * 100}%\n")
+    out.append("\nframes separated by bin:\n")
+    for b, count in frames.items():
+        out.append(f"bin: {b}, frames = {count} = {round(count / BIN_FRAMES_DENOM, 2) * 100}%\n")
+    out.append("\niou-mean and std:\n")
+    for b, vals in ious.items():
+        mean = round(statistics.mean(vals), 2)
+        std = round(statistics.stdev(vals), 2) if len(vals) > 1 else float("nan")
+        out.append(f"bin: {b}, iou_mean={mean}, iou_std={std}\n")
+    return "".join(out)
+
+
+def write_bin_info(path, bins):
+    """save_bin_info_file's file (the reference writes bin_info_vae1.txt in the working directory)."""
+    with open(path, "w") as f:
+        f.write(bin_info_text(bins))
+
+
+# ---- the pipeline ----
+def _infer(frames_u8, vae, critic, preds, chunk):
+    """critic values + difference masks of every frame, in chunks of at most vae.max_batch:
+    (preds (B,) fp32, diff (B,W,W) fp32 on the device, per-frame maxima (B,) fp32)."""
+    if (critic is None) == (preds is None):
+        raise ValueError("pass exactly one of critic and preds")
+    vae.eval()                                   # load_vae_network (vae_utility.py:345-361)
+    vae.encoder.eval()
+    vae.decoder.eval()
+    frames = _cuda(frames_u8, torch.uint8)
+    B, W = frames.shape[0], frames.shape[1]
+    if W != vae.width:
+        raise ValueError(f"frames are {W}x{W}, the VAE is {vae.width}x{vae.width}")
+    chunk = min(int(chunk or vae.max_batch), vae.max_batch)
+    if preds is not None:
+        preds = _cuda(preds, torch.float32).reshape(-1)
+        if preds.shape[0] != B:
+            raise ValueError(f"{preds.shape[0]} preds for {B} frames")
+    out_p = torch.empty(B, device=frames.device)
+    diff = torch.empty(B, W, W, device=frames.device)
+    maxv = torch.empty(B, device=frames.device)
+    x = torch.empty(chunk, 3, W, W, device=frames.device)
+    for s in range(0, B, chunk):
+        e = min(B, s + chunk)
+        xs = x[:e - s]
+        vae.handle.preprocess_u8(e - s, frames[s:e], xs)
+        if critic is not None:
+            cb = critic.handle.max_batch
+            for c0 in range(0, e - s, cb):
+                out_p[s + c0:s + min(e - s, c0 + cb)] = critic.evaluate(xs[c0:c0 + cb]).reshape(-1)
+        else:
+            out_p[s:e] = preds[s:e]
+        _, _, d, m = vae.diff_images(xs, out_p[s:e])
+        diff[s:e] = d
+        maxv[s:e] = m
+    return out_p, diff, maxv
+
+
+def _crf_counts(frames, thr_mask, gt, crf_params_, p_floor):
+    crf = dense_crf(frames, thr_mask, crf_params_, p_floor)
+    c = mask_counts(crf, gt).sum(0).tolist()
+    return crf, iou_from_counts(*c)
+
+
+def eval_frames(frames_u8, vae, gt, critic=None, preds=None, t=THRESHOLD, crf_params=CRF_REF, chunk=None,
+                p_floor=P_FLOOR):
+    """eval_textured_frames (vae_utility.py:162-212) without the PIL frames.  frames_u8 (B,W,W,3) uint8, gt (B,W,W)
+    bool; either a critic (64x64 only, as the reference's) or explicit preds (B,).  The VAE runs in eval mode in
+    chunks of at most vae.max_batch; normalisation, threshold, CRF and IoU run over the whole set at once.
+    Returns a dict: preds, diff (fp32), max_values, diff_u8, thr_masks, crf_masks (host arrays), thr_iou, crf_iou,
+    bins, mean_max, hist (the (2,256) histograms of diff_u8)."""
+    p, diff, maxv = _infer(frames_u8, vae, critic, preds, chunk)
+    frames = _cuda(frames_u8, torch.uint8)
+    gt_d = _cuda(_np(gt).astype(np.uint8), torch.uint8)
+    hist = torch.zeros(2, 256, dtype=torch.int64, device=frames.device)
+    u8, m, c, mean_max = _normalize(diff, maxv.cpu(), t, gt=gt_d, mask=True, counts=True, hist=hist)
+    thr_iou = iou_from_counts(*c.sum(0).tolist())
+    crf, crf_iou = _crf_counts(frames, m, gt_d, crf_params, p_floor)
+    thr_np = _np(m).astype(bool)
+    preds_np = _np(p)
+    return {"preds": preds_np, "diff": _np(diff), "max_values": _np(maxv), "diff_u8": _np(u8), "thr_masks": thr_np, "crf_masks": _np(crf), "thr_iou": thr_iou,
+            "crf_iou": crf_iou, "bins": bin_info(preds_np, gt, thr_np), "mean_max": mean_max, "hist": _np(hist)}
+
+
+def threshold_sweep(frames_u8, vae, gt, critic=None, preds=None, thresholds=SWEEP, crf_params=CRF_REF, chunk=None,
+                    p_floor=P_FLOOR):
+    """The -thresh loop (vae.py:119-124): the VAE and critic run once, the masks are normalised once (thr_iou at every
+    threshold from its histograms), the CRF once per threshold.  Returns [(t, thr_iou, crf_iou), ...]."""
+    p, diff, maxv = _infer(frames_u8, vae, critic, preds, chunk)
+    frames = _cuda(frames_u8, torch.uint8)
+    gt_d = _cuda(_np(gt).astype(np.uint8), torch.uint8)
+    hist = torch.zeros(2, 256, dtype=torch.int64, device=frames.device)
+    maxv = maxv.cpu()
+    _normalize(diff, maxv, 0, gt=gt_d, hist=hist)
+    hist = _np(hist)
+    out = []
+    for t in thresholds:
+        _, m, _, _ = _normalize(diff, maxv, t, mask=True)
+        _, crf_iou = _crf_counts(frames, m, gt_d, crf_params, p_floor)
+        out.append((t, iou_from_hist(hist, t), crf_iou))
+    return out
+
+
+def load_episode(x_npy, y_npy):
+    """load_textured_minerl (vae_utility.py:70-82): frames X[100:5000:2] (N,64,64,3) uint8 and the ground truth
+    np.all(Y, -1)[100:5000:2] (N,64,64) bool.  Paths or arrays.  (The reference's final squeeze() would also drop
+    the frame axis of a one-frame slice; here the frame axis always stays.)"""
+    X = np.load(x_npy) if isinstance(x_npy, (str, os.PathLike)) else np.asarray(x_npy)
+    Y = np.load(y_npy) if isinstance(y_npy, (str, os.PathLike)) else np.asarray(y_npy)
+    return X[100:5000:2], np.all(Y, axis=-1)[100:5000:2]
+
+
+# ---- CLI (vae.py -video [-thresh], vae.py:108-127) ----
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m critic_vae_amd.segment",
+                                 description="critic-guided segmentation masks of an episode: thr_iou and crf_iou")
+    ap.add_argument("-video", action="store_true", help="evaluate the episode (the only mode)")
+    ap.add_argument("-thresh", action="store_true", help="sweep thresholds 0, 10, ..., 120")
+    ap.add_argument("--frames", default="minerl-episode/X.npy", help="episode frames (N,64,64,3) uint8")
+    ap.add_argument("--gt", default="minerl-episode/Y.npy", help="episode ground truth (N,64,64,C)")
+    ap.add_argument("--networks", default="saved-networks", help=f"directory with {ENCODER_FILE} and {DECODER_FILE}")
+    ap.add_argument("--critic", default=None, help=f"critic checkpoint (default: NETWORKS/{CRITIC_FILE})")
+    ap.add_argument("--chunk", type=int, default=256, help="frames per VAE launch")
+    args = ap.parse_args(argv)
+    if not args.video:
+        ap.error("-video is required (-dataset, -second, -evalsecond and -inject are not part of this tool)")
+    if args.chunk < 1:
+        ap.error("--chunk must be >= 1")
+    if args.critic is None:
+        args.critic = os.path.join(args.networks, CRITIC_FILE)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from .critic import Critic
+    from .nets import VariationalAutoencoder
+    frames, gt = load_episode(args.frames, args.gt)
+    vae = VariationalAutoencoder(max_batch=args.chunk).to("cuda")
+    vae.encoder.load_state_dict(torch.load(os.path.join(args.networks, ENCODER_FILE), map_location="cpu"))
+    vae.decoder.load_state_dict(torch.load(os.path.join(args.networks, DECODER_FILE), map_location="cpu"))
+    critic = Critic(64, handle=Handle(64, args.chunk)).to("cuda")
+    critic.load_state_dict(torch.load(args.critic, map_location="cpu"))
+    if args.thresh:
+        print("testing thresholds (thr):")
+        for t, thr_iou, crf_iou in threshold_sweep(frames, vae, gt, critic=critic, chunk=args.chunk):
+            print(f"thr={t}, thr_iou={thr_iou}, crf_iou={crf_iou}")
+    else:
+        r = eval_frames(frames, vae, gt, critic=critic, chunk=args.chunk)
+        print(f"thr_iou={r['thr_iou']}")
+        print(f"crf_iou={r['crf_iou']}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -179,6 +179,50 @@ int cvae_preprocess_u8(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, 
 int cvae_diff_grey(cvae_handle h, int32_t batch, const float* recon_one, const float* recon_zero,
                    float* diff, void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Segmentation evaluation (eval_textured_frames, vae_utility.py:162-212), after the difference
+ * mask of cvae_diff_grey.  W is the handle's width; `batch` is NOT capped by max_batch (a whole
+ * episode may go in one call): any batch >= 1 with batch * W * W < 2^31.  uint8 masks are
+ * (B,W,W), nonzero = set.  Host-side argument checks come before any device access.
+ * ---------------------------------------------------------------------------------------- */
+
+/* Mask normalisation (get_diff_factor / prepare_diff / get_diff_and_thr_masks, vae_utility.py:106-110,
+ * 148-160, 279-284), in float64 and that operation order: diff_u8 = trunc((min(d, mean_max) * diff_factor) * 255)
+ * with mean_max = statistics.mean of the per-frame maxima and diff_factor = 1.0 / mean_max (0 if mean_max == 0),
+ * both from the host.  mask_or_null: diff_u8 > thr (thr in [0, 255]).  With gt_or_null set: frame_counts_or_null
+ * (B,3) int64 = per-frame (tp, fn, fp) of get_iou(gt, mask) (vae_utility.py:56-68), and hist_or_null (2,256) int64
+ * gains the histogram of diff_u8 over pixels where gt is set (row 0) and where it is clear (row 1): ADDED to what
+ * the buffer holds (integer atomics, order-free), so that one pass gives the set-wide IoU at every threshold.
+ * Counts or histogram without gt: CVAE_EINVAL. */
+int cvae_diff_normalize(cvae_handle h, int32_t batch, const float* diff, double mean_max, double diff_factor,
+                        int32_t thr, const uint8_t* gt_or_null, uint8_t* diff_u8, uint8_t* mask_or_null,
+                        int64_t* frame_counts_or_null, int64_t* hist_or_null, void* stream);
+
+/* per-frame (tp, fn, fp) of get_iou(gt, mask) for any uint8 mask -> frame_counts (B,3) int64 */
+int cvae_mask_counts(cvae_handle h, int32_t batch, const uint8_t* mask, const uint8_t* gt,
+                     int64_t* frame_counts, void* stream);
+
+/* Dense CRF of crf() (vae_utility.py:22-54; SimpleCRF denseCRF.densecrf with (w1, alpha, beta, w2, gamma, it)),
+ * two labels, prob = (1 - prob1, prob1).  EXACT mean field: every pairwise sum runs over all (W*W)^2 pixel pairs
+ * (the densecrf library approximates the bilateral filter with a permutohedral lattice instead).  Features
+ * (x/gamma, y/gamma) and (x/alpha, y/alpha, r/beta, g/beta, b/beta) on the raw uint8 RGB frame, kernels
+ * exp(-|f_i - f_j|^2 / 2) including j = i, symmetric normalisation n_i = (sum_j k(i,j))^-1/2, Potts weights w2
+ * (Gaussian) and w1 (bilateral), unary u(l) = -log(max(prob(l), p_floor)), Q0 = softmax(-u), `iterations`
+ * updates Q <- softmax(-u + sum_k w_k n_i sum_j k(i,j) n_j Q_j).  labels (B,W,W) uint8 = Q(1) > Q(0) (0 on a
+ * tie); q1_or_null (B,W,W) fp32 = Q(1).  frames_hwc (B,W,W,3) uint8, prob1 (B,W,W) fp32.  Deterministic: a
+ * frame's result is bitwise independent of the batch it is in and its position there.
+ * Ranges: w1, w2 >= 0; alpha, beta, gamma > 0; 0 < p_floor <= 1; 0 <= iterations <= 10000; all finite.
+ * `scratch`: cvae_crf_scratch_bytes(h, batch) bytes of device memory, 256-byte aligned (host-only query; -1 for
+ * a bad handle or batch). */
+typedef struct cvae_crf_params {
+    float w1, alpha, beta, w2, gamma, p_floor;
+    int32_t iterations;
+} cvae_crf_params;
+int64_t cvae_crf_scratch_bytes(cvae_handle h, int32_t batch);
+int cvae_dense_crf(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, const float* prob1,
+                   const cvae_crf_params* params, uint8_t* labels, float* q1_or_null, void* scratch,
+                   void* stream);
+
 /* float offset of a named saved tensor in the workspace ("y0".."y3", "a0".."a3", "o0".."o3",
  * "zcat", "h", "d_*" ...) for tests; -1 if unknown OR not allocated in this configuration: "d_y0" does not exist
  * (block 0's BatchNorm backward runs inside the E1 weight-gradient kernel; CVAE_FUSE_E1=0 restores it), and in
