@@ -69,7 +69,8 @@ int persistent_grid(int wgs_per_cu, int num_items) {
 }
 // include/cvae.h: which kernel family a conv pass of E2..E4 takes at a batch size (host logic only, no device access)
 extern "C" int32_t cvae_conv_route(int32_t precision, int32_t width, int32_t layer, int32_t dgrad, int64_t batch) {
-    if ((width != 64 && width != 128) || layer < 1 || layer > 3 || precision < 0 || precision > 3 || batch < 1 || batch > 0x7fffffffLL) return CVAE_EINVAL;
+    if ((width != 64 && width != 128) || layer < 0 || layer > 3 || precision < 0 || precision > 3 || batch < 1 || batch > 0x7fffffffLL) return CVAE_EINVAL;
+    if (layer == 0 && (precision != 1 || dgrad != 0)) return CVAE_EINVAL;        // layer 0: the packed-frame row of bf16 mode only
     return conv_route(precision, layer, width, dgrad != 0, batch).family;
 }
 
@@ -318,15 +319,17 @@ int cvae_forward(cvae_handle h, int32_t B, const float* x, const float* pred, co
         if (l == 0 && h->e1_two_pass) {
             // bf16 mode, block 0: conv (statistics only) -> merged statistics -> conv again with BatchNorm/pool/ReLU in its
             // epilogue (writes y0 for the backward and a0); bn_pool_act_fwd's read of y0 is replaced by a second read of x
-            if (train) RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), nullptr, ws + w.bnpart[0], st, true, 1, nullptr, nullptr, true, ws + w.xp));     // also writes the packed bf16 frame
-            h->xp_ws = train ? wsv : nullptr; h->xp_B = B;
+            // the packed bf16 frame (slot xp) while it stays below 2 GiB (conv_route); past that every E1 pass stages the fp32 frame
+            float* xp = train && conv_route(1, 0, W, false, B).family == E1_PACKED_FRAME ? ws + w.xp : nullptr;
+            if (train) RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), nullptr, ws + w.bnpart[0], st, true, 1, nullptr, nullptr, true, xp));     // also writes xp
+            h->xp_ws = xp ? wsv : nullptr; h->xp_B = B;
             RC(launch_bn_fwd_finalize(0, W, B, ws + w.bnpart[0], P_(h->enc_g[0]), P_(h->enc_be[0]), bn_state + kBnOff[0],
                                       bn_state + 480 + kBnOff[0], ws + w.coef[0], ws + w.scratch, train, st));
             { ProbeArm pa(h, 0, 0);
               // y0 is written only for the CVAE_FUSE_E1=0 path (or, decided on the device, when a channel's gamma is tiny):
               // the fused weight-gradient kernel recomputes it
               RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], nullptr, st, true, 2, ws + w.coef[0], ws + w.a[0],
-                               !h->fuse_e1, train ? ws + w.xp : nullptr)); }          // eval mode: no statistics pass, no packed frame
+                               !h->fuse_e1, xp)); }          // eval mode (no statistics pass) or no packed frame: E1_POOL_X
             continue;
         }
         if (l == 0) { ProbeArm pa(h, 0, 0); RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], ws + w.bnpart[0], st, h->cfg.precision == 1)); }
@@ -498,7 +501,8 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
                                   P_(h->enc_w[0]), P_(h->enc_b[0])};
             { ProbeArm pa(h, 2, 0);
               RC(launch_e1_wgrad(W, B, x, fuse0 ? nullptr : ws + w.d_y[0], G_(h->enc_w[0]), G_(h->enc_b[0]), scw, sd, h->cfg.precision == 1, fuse0 ? fu : nullptr,
-                                 (h->e1_two_pass && fuse0 && h->xp_ws == (const void*)ws && h->xp_B == B) ? ws + w.xp : nullptr)); }
+                                 (h->e1_two_pass && fuse0 && h->xp_ws == (const void*)ws && h->xp_B == B &&
+                                  conv_route(1, 0, W, false, B).family == E1_PACKED_FRAME) ? ws + w.xp : nullptr)); }
         } else {
             { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, l, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd)); }
             { ProbeArm pa(h, 1, l);

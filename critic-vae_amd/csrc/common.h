@@ -170,7 +170,9 @@ int persistent_grid(int wgs_per_cu, int num_items);
 
 // Kernel family of a conv forward / input-gradient pass of layers 1..4 (E2..E4, D0); the codes are those of cvae_conv_route.
 // CONV_PS: conv_mfma_ps.hip in fp32 mode, conv_bf16_ps.hip in bf16 mode; CONV_BIG: conv_bf16_big.hip.
-enum ConvFamily { CONV_PER_TILE = 0, CONV_PS = 1, CONV_BIG = 2 };
+// Layer 0 (E1) forward in bf16 mode: E1_PACKED_FRAME = E1's passes stage their strips from the packed bf16 frame (workspace slot xp),
+// CONV_PER_TILE (0) = from the fp32 frame x.
+enum ConvFamily { CONV_PER_TILE = 0, CONV_PS = 1, CONV_BIG = 2, E1_PACKED_FRAME = 1 };
 struct ConvRoute {
     ConvFamily family;
     int tilesPerPartial;      // forward passes: 128-pixel tiles per BatchNorm partial row of bnpart

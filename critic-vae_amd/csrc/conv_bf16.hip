@@ -130,7 +130,8 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     bf16x8 breg[NS == 1 ? MT * IPT : 1];
     unsigned okmask = 0u;                       // NS == 1: which staged units of breg are real (the others are zero padding)
     static_assert(NS != 1 || MT * IPT <= 32, "one validity bit per staged unit");
-    // element index of each staged unit's first channel at chunk 0 (-1: zero padding / past the batch / no unit)
+    // pixel index (image * H * H + row * H + column) of each staged unit (-1: zero padding / past the batch / no unit); the element index
+    // is formed in size_t where the unit is loaded: an int element index wraps from 2^31 elements on (bf16 input tensors of 4 GiB)
     int ebase[MODE == MODE_UP_DGRAD ? 1 : MT * IPT];
     if constexpr (MODE != MODE_UP_DGRAD) {
 #pragma unroll
@@ -138,11 +139,11 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
             for (int i = 0; i < IPT; ++i) {
                 const int q = tid + i * 256;
-                const int oct = q % OCT, hp = q / OCT;
+                const int hp = q / OCT;
                 const int img = hp / T::HPI, rem = hp - img * T::HPI;
                 const int gy = ty0v[tl] + rem / T::HTW - 2, gx = tx0v[tl] + rem % T::HTW - 2, ib = img0v[tl] + img;
                 const bool ok = (NQ % 256 == 0 || q < NQ) && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)H && ib < a.B;
-                ebase[tl * IPT + i] = ok ? ((ib * H + gy) * H + gx) * KCH + oct * 8 : -1;
+                ebase[tl * IPT + i] = ok ? (ib * H + gy) * H + gx : -1;
             }
     }
     auto load_input = [&](int cc) {
@@ -163,8 +164,9 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                     e = ((size_t)(ib * 2 * H + 2 * gy + (p >> 1)) * (2 * H) + 2 * gx + (p & 1)) * COUT_UP + co;
                 }
             } else {
+                const int oct = (tid + i * 256) % OCT;
                 ok = ebase[tl * IPT + i] >= 0;
-                e = ok ? (size_t)(ebase[tl * IPT + i] + cc * KCB) : 0;
+                e = ok ? (size_t)ebase[tl * IPT + i] * KCH + oct * 8 + cc * KCB : 0;
             }
             if constexpr (NS == 1) {
                 // e = 0 when !ok: the load itself is unconditional (no branch per unit).  The zero-select happens in store_input,

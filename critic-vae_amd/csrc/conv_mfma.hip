@@ -36,15 +36,26 @@ static constexpr ConvRouteRow kConvRoutes[] = {
     {1, 1, 128, true, CONV_BIG, 1}, {1, 2, 128, true, CONV_BIG, 1}, {1, 3, 128, true, CONV_BIG, 1},
     // bf16, conv_bf16_ps.hip: D0's forward at 128 x 128
     {1, 4, 128, false, CONV_PS, 1},
+    // bf16, conv_thin.hip: E1 stages its strips from the packed bf16 frame xp (the statistics pass writes it, the pool pass and the
+    // weight gradient read it)
+    {1, 0, 64, false, E1_PACKED_FRAME, 1}, {1, 0, 128, false, E1_PACKED_FRAME, 1},
 };
 
 ConvRoute conv_route(int precision, int layer, int width, bool dgrad, int64_t B) {
     // CVAE_CONV_PER_TILE=1 (tests): every pass on the per-tile kernels
     static const bool per_tile_only = [] { const char* e = getenv("CVAE_CONV_PER_TILE"); return e && e[0] == '1'; }();
     const ConvRoute per_tile{CONV_PER_TILE, 1};
-    if (per_tile_only) return per_tile;
     for (const ConvRouteRow& r : kConvRoutes) {
         if (r.precision != precision || r.layer != layer || r.width != width || r.dgrad != dgrad) continue;
+        if (layer == 0) {
+            // e1_fwd_bf16_kernel / e1_wgrad_bf16_kernel address xp (8 bytes per pixel) through a descriptor of B * W * W * 8 + XP_BIAS
+            // bytes (XP_BIAS = (2W + 2) * 8: the descriptor starts that far in front of xp), with 32-bit int byte offsets and 0x80000000
+            // as the "dropped" offset: from 2^31 bytes on, E1 stages the fp32 frame instead.  Not a conv kernel: CVAE_CONV_PER_TILE
+            // leaves it alone.
+            if (B * width * width * 8 + (2 * width + 2) * 8 >= (1ll << 31)) return per_tile;
+            return {r.family, r.tilesPerPartial};
+        }
+        if (per_tile_only) return per_tile;
         // the persistent kernels address both tensors with 32-bit byte offsets (and mark skipped lanes with the offset 0x80000000):
         // when the larger one reaches 2 GiB the pass takes the per-tile kernel (size_t addressing)
         const int64_t h = kLayers[layer].h * width / 64, c = kLayers[layer].cin > kLayers[layer].cout ? kLayers[layer].cin : kLayers[layer].cout;

@@ -827,18 +827,21 @@ int launch_e1_fwd(int width, int B, const float* x, const float* w, const float*
     const int keepY = keep_y ? 1 : 0;
     if (pass != 0 && !bf16) { cvae_set_error("e1_fwd: passes 1/2 exist in bf16 mode only"); return -2; }
     if (pass < 0 || pass > 2) { cvae_set_error("e1_fwd: pass %d", pass); return -2; }
-    if (pass == 2 && !xp) pass = 3;                       // no packed frame (eval mode: no statistics pass ran): the pool pass stages from the fp32 frame
+    if (pass == 2 && !xp) pass = 3;                       // no packed frame (eval mode, or a frame of 2 GiB and more): the pool pass stages from the fp32 frame
+    // the kernel's B sizes nothing but the packed frame's descriptor (B * H * H * 8 + XP_BIAS bytes, an int): without a frame the statistics
+    // pass gets an empty one, so that its 0x80000000 "not mine" store offsets stay out of range at every batch
+    const int xpB = xp ? B : 0;
     const int ns64 = B * 8, ns128 = B * 32, cap = cvae_num_cus() * 3;      // persistent: 3 workgroups per CU (<= 168 VGPRs), one strip each per turn
     const dim3 g64(ns64 < cap ? ns64 : cap), g128(ns128 < cap ? ns128 : cap);
     cvae_probe_begin(st);
-    if (width == 64 && bf16 && pass == 1) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_STATS>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, B, coef, a1, ns64, keepY, xp);
-    else if (width == 64 && bf16 && pass == 2) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_POOL>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, B, coef, a1, ns64, keepY, xp);
-    else if (width == 128 && bf16 && pass == 1) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_STATS>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, B, coef, a1, ns128, keepY, xp);
-    else if (width == 128 && bf16 && pass == 2) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_POOL>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, B, coef, a1, ns128, keepY, xp);
-    else if (width == 64 && bf16 && pass == 3) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_POOL_X>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, B, coef, a1, ns64, keepY, xp);
-    else if (width == 128 && bf16 && pass == 3) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_POOL_X>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, B, coef, a1, ns128, keepY, xp);
-    else if (width == 64 && bf16) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_Y>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, B, coef, a1, ns64, keepY, xp);
-    else if (width == 128 && bf16) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_Y>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, B, coef, a1, ns128, keepY, xp);
+    if (width == 64 && bf16 && pass == 1) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_STATS>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, keepY, xp);
+    else if (width == 64 && bf16 && pass == 2) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_POOL>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, keepY, xp);
+    else if (width == 128 && bf16 && pass == 1) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_STATS>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, keepY, xp);
+    else if (width == 128 && bf16 && pass == 2) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_POOL>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, keepY, xp);
+    else if (width == 64 && bf16 && pass == 3) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_POOL_X>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, keepY, xp);
+    else if (width == 128 && bf16 && pass == 3) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_POOL_X>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, keepY, xp);
+    else if (width == 64 && bf16) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_Y>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, keepY, xp);
+    else if (width == 128 && bf16) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_Y>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, keepY, xp);
     else if (width == 64) hipLaunchKernelGGL(e1_fwd_kernel<64>, dim3(B * 8), dim3(256), 0, st, x, w, bias, y, bnpart, B);
     else if (width == 128) hipLaunchKernelGGL(e1_fwd_kernel<128>, dim3(B * 32), dim3(256), 0, st, x, w, bias, y, bnpart, B);
     else { cvae_set_error("e1_fwd: width %d unsupported", width); return -2; }

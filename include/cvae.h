@@ -113,7 +113,7 @@ int cvae_loss(cvae_handle h, int32_t batch, const float* x, const float* mu, con
  * decisions from those values — and every mode reads the saved activations of that forward from `ws`.  (Round 5: in
  * precision mode 1 a train-mode forward also leaves the frame in `ws` as packed bf16 pixels — 8 bytes per pixel, slot "xp" —
  * and the backward stages E1's strips from that copy when `ws` and `batch` are the ones of the handle's last train-mode
- * forward; after an eval-mode forward, or on another workspace, it converts the fp32 `x` itself, as rounds 3-4 did.)
+ * forward and the copy stays below 2 GiB (cvae_conv_route(1, width, 0, 0, batch) == 1); after an eval-mode forward, or on another workspace, it converts the fp32 `x` itself, as rounds 3-4 did.)
  */
 int cvae_backward(cvae_handle h, int32_t batch, const float* x, const float* pred, const float* eps,
                   const float* params, const float* logvar, const float* recon, const float* d_recon,
@@ -234,7 +234,9 @@ int64_t cvae_ws_offset(cvae_handle h, int32_t batch, const char* name);
  * vae_nets.py:74,79,84) takes at `batch` images: 0 = per-tile kernel (64-bit addressing, any size), 1 = two-workgroup persistent kernel,
  * 2 = big-tile persistent kernel.  The persistent kernels address their tensors with 32-bit byte offsets, so activations of 2 GiB and
  * more (E2's output: batch >= 8192 in fp32, >= 16384 in bf16 mode at 64 x 64) take the per-tile kernel, without the caller doing
- * anything.  Host logic only (the route table the launchers read; no device access, works without a GPU);
+ * anything.  Layer 0 (E1), dgrad = 0, precision 1 only: 1 = E1's passes stage the packed bf16 frame (workspace slot "xp", addressed
+ * the same way), 0 = the fp32 frame x — from batch * width^2 * 8 + (2 * width + 2) * 8 >= 2^31 (batch >= 65536 at 64 x 64, >= 16384 at
+ * 128 x 128).  Host logic only (the route table the launchers read; no device access, works without a GPU);
  * CVAE_EINVAL for arguments outside these ranges.  precision as in cvae_config. */
 int32_t cvae_conv_route(int32_t precision, int32_t width, int32_t layer, int32_t dgrad, int64_t batch);
 

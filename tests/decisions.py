@@ -34,35 +34,49 @@ def tie_tol(vae):
     return TIE_TOL_BY_MODE.get(getattr(vae.handle, "precision", "f32"), TIE_TOL)
 
 
-def value_deviation(vae, B, taps):
+def _images(vae, B, images):
+    """(workspace, first image, image count) of the image range [i0, i1) of a B-image step (default: all of it)."""
+    i0, i1 = images if images is not None else (0, B)
+    assert 0 <= i0 < i1 <= B, images
+    return vae._workspace(B), i0, i1 - i0
+
+
+def _stored(vae, ws, B, name, c, s, i0, nimg):
+    """Images [i0, i0 + nimg) of the stored NHWC tensor `name` (c channels, s x s), as a device view (nothing is copied)."""
+    per = s * s * c
+    return vae.handle.ws_view(ws, B, name, (i0 + nimg) * per)[i0 * per:].view(nimg, s, s, c)
+
+
+def value_deviation(vae, B, taps, images=None):
     """E_l = max |n_hip - n_orc| of the normalised pre-pool values of encoder block l (what the pool / ReLU decisions are taken on), and of the
-    decoder's pre-activations recomputed from... the stored o_i (post-ReLU: compared where both sides are positive)."""
-    ws, h, k = vae._workspace(B), vae.handle, vae.width // 64
+    decoder's pre-activations recomputed from... the stored o_i (post-ReLU: compared where both sides are positive).
+    images = (i0, i1): the oracle ran on images [i0, i1) of the B-image step; only their slices are read."""
+    (ws, i0, nimg), h, k = _images(vae, B, images), vae.handle, vae.width // 64
     out = {}
     for l, (c, s) in enumerate(ENC):
         s *= k
-        y = h.ws_view(ws, B, f"y{l}", B * s * s * c).view(B, s, s, c).permute(0, 3, 1, 2).double()
+        y = _stored(vae, ws, B, f"y{l}", c, s, i0, nimg).permute(0, 3, 1, 2).double()
         coef = h.ws_view(ws, B, f"coef{l}", c * 4).view(c, 4).double()
         n = (y * coef[:, 0].view(1, c, 1, 1) + coef[:, 1].view(1, c, 1, 1)).float().cpu()
         out[f"enc{l}"] = float((n - taps[f"enc_n{l}"].detach()).abs().max())
     for i, (c, s) in enumerate(DEC):
-        o = h.ws_view(ws, B, f"o{i}", B * s * k * s * k * c).view(B, s * k, s * k, c).permute(0, 3, 1, 2).cpu()
+        o = _stored(vae, ws, B, f"o{i}", c, s * k, i0, nimg).permute(0, 3, 1, 2).cpu()
         pre = taps[f"dec_pre{i}"].detach()
         both = (o > 0) & (pre > 0)
         out[f"dec{i}"] = float((o - pre)[both].abs().max()) if bool(both.any()) else 0.0
     return out
 
 
-def hip_decisions(vae, B):
+def hip_decisions(vae, B, images=None):
     """Max-pool / ReLU decisions the HIP step actually took, read from what its kernels WROTE: the pooled output a_l
     is matched against the four candidates of its window (the first candidate whose value the kernel stored is the
     window's first maximum), so a kernel whose normalisation expression differed from the candidates recomputed here
     would leave windows without any matching candidate — asserted below — instead of silently imposing decisions the
-    kernel never made."""
-    ws, h, k = vae._workspace(B), vae.handle, vae.width // 64
+    kernel never made.  images = (i0, i1): the decisions of images [i0, i1) only, read from their slices."""
+    (ws, i0, nimg), h, k = _images(vae, B, images), vae.handle, vae.width // 64
 
     def view(name, c, s):
-        return h.ws_view(ws, B, name, B * s * s * c).view(B, s, s, c).permute(0, 3, 1, 2)
+        return _stored(vae, ws, B, name, c, s, i0, nimg).permute(0, 3, 1, 2)
 
     dec = {}
     for l, (c, s) in enumerate(ENC):
@@ -137,10 +151,12 @@ def is_pre_bn_bias(name):
     return name.startswith("encoder.model.") and name.endswith(".bias") and int(name.split(".")[2]) % 4 == 0
 
 
-def check_step_against_oracle(vae, x, pred, eps, B, wseed=0, tol=1e-4, rel=1e-4, max_flips=64, verbose=False):
+def check_step_against_oracle(vae, x, pred, eps, B, wseed=0, tol=1e-4, rel=1e-4, max_flips=64, verbose=False, images=None):
     """After vae's forward+loss+backward on (x, pred, eps): outputs / loss / every gradient element at `tol`
     absolute vs the plain oracle; flipped decisions counted and shown to be ties; every gradient element at
-    `rel` x the tensor's max vs the oracle with the HIP decisions imposed.  Returns a small report."""
+    `rel` x the tensor's max vs the oracle with the HIP decisions imposed.  Returns a small report.
+    images = (i0, i1): the step ran on B images of which (x, pred, eps) are [i0, i1) and whose loss and gradients equal those of
+    these images alone (a batch of replicas of them); the decisions are read from their slices of the workspace."""
     W = vae.width
     params = synth.make_params(wseed, W)
     p = orc.to_torch(params, requires_grad=True)
@@ -156,12 +172,12 @@ def check_step_against_oracle(vae, x, pred, eps, B, wseed=0, tol=1e-4, rel=1e-4,
         assert e <= tol, f"{k}: abs err {e:.3e}"
         if not is_pre_bn_bias(k):
             rep["rel_plain"] = max(rep["rel_plain"], e / max(float(v.grad.abs().max()), 1e-30))
-    d_hip, d_orc = hip_decisions(vae, B), oracle_decisions(taps)
+    d_hip, d_orc = hip_decisions(vae, B, images), oracle_decisions(taps)
     rep["flips"] = flips(d_hip, d_orc, taps)
     n_units = sum(v.numel() for v in d_hip.values())
     n_flips = sum(f[1] for f in rep["flips"])
     assert n_flips <= max_flips, f"{n_flips} decision flips among {n_units} units: {rep['flips']}"
-    rep["dev"] = value_deviation(vae, B, taps)
+    rep["dev"] = value_deviation(vae, B, taps, images)
     for k, nf, gap in rep["flips"]:
         if not k.startswith("relu_dec"):               # encoder decisions: E is exact there (decoder: measured on the units both sides keep, a proxy)
             e = rep["dev"]["enc" + k[-1]]

@@ -72,6 +72,10 @@ CONV_ROUTES = {
     (3, 64): ["00000"] * 6,
     (3, 128): ["00000"] * 6,
 }
+# the packed-frame row (layer 0, bf16 mode) at B = 8, 256, 1024, 2048, edge - 1, edge (edge: the first batch whose packed frame plus its
+# descriptor bias, B * W * W * 8 + (2W + 2) * 8 bytes, reaches 2^31): 1 = E1 stages the packed bf16 frame, 0 = the fp32 frame
+XP_EDGE = {64: 65536, 128: 16384}
+XP_ROUTES = {64: "111110", 128: "111110"}
 
 
 def test_persistent_conv_kernels_refuse_tensors_of_two_gib():
@@ -79,7 +83,8 @@ def test_persistent_conv_kernels_refuse_tensors_of_two_gib():
     and buffer descriptors; their launchers must hand an activation of 2 GiB or more to the per-tile kernels (64-bit addressing).
     cvae_conv_route reads the route table the launchers read (conv_route, no device access): the family changes exactly where
     the larger of a layer's two tensors crosses 2^31 bytes.  The whole route table is pinned (CONV_ROUTES), and CVAE_CONV_PER_TILE=1 sends
-    every pass to the per-tile kernels.  Child processes, so that no CVAE_* switch of the caller changes the routes."""
+    every pass to the per-tile kernels.  The packed bf16 frame of E1 (XP_ROUTES, layer 0 of bf16 mode; negative in every other mode) is
+    addressed the same way and is left for the fp32 frame from the batch on whose descriptor reaches 2^31 bytes.  Child processes, so that no CVAE_* switch of the caller changes the routes."""
     code = """
 import json, os, sys
 sys.path.insert(0, %r)
@@ -101,6 +106,12 @@ for prec in range(4):
                 assert small == below, (prec, width, layer, dgrad, small, below)
                 assert at == 0 and r(prec, width, layer, dgrad, 4 * edge) == 0, (prec, width, layer, dgrad, at)
         tab["%%d,%%d" %% (prec, width)] = row
+        for b in (8, 2048, (1 << 31) - 1):
+            assert prec == 1 or (r(prec, width, 0, 0, b) < 0 and r(prec, width, 0, 1, b) < 0), (prec, width, b)
+for width in (64, 128):
+    edge = -(-((1 << 31) - (2 * width + 2) * 8) // (width * width * 8))
+    tab["xp,%%d" %% width] = [edge, "".join(str(r(1, width, 0, 0, b)) for b in (8, 256, 1024, 2048, edge - 1, edge))]
+    assert r(1, width, 0, 1, 8) < 0 and r(1, width, 0, 0, 4 * edge) == 0
 if os.environ.get("CVAE_CONV_PER_TILE") != "1":
     # the default configuration does use them below the edge: fp32 E2..E4 forward on the two-workgroup kernel, bf16 E2..E4 (64 x 64) on the big-tile kernel
     assert [r(0, 64, l, 0, 256) for l in (1, 2, 3)] == [1, 1, 1] and r(0, 64, 1, 1, 256) == 0
@@ -111,6 +122,7 @@ print(json.dumps(tab))
 print("ok")
 """ % ROOT
     want = {f"{p},{w}": row for (p, w), row in CONV_ROUTES.items()}
+    xp = {f"xp,{w}": [XP_EDGE[w], XP_ROUTES[w]] for w in XP_EDGE}          # not a conv pass: CVAE_CONV_PER_TILE leaves it alone
     for per_tile in ("0", "1"):
         env = {k: v for k, v in os.environ.items() if not k.startswith("CVAE_")}
         if per_tile == "1":
@@ -118,7 +130,7 @@ print("ok")
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-2000:]
         got = json.loads(r.stdout.strip().splitlines()[-2])
-        assert got == (want if per_tile == "0" else {k: ["00000"] * 6 for k in want}), (per_tile, got)
+        assert got == dict(want if per_tile == "0" else {k: ["00000"] * 6 for k in want}, **xp), (per_tile, got)
 
 
 def test_two_handles_do_not_share_state():
