@@ -8,7 +8,6 @@
 #include "common.h"
 
 static constexpr int FC_KS = 32;         // K splits of the fc_mu|fc_var GEMM
-static constexpr int FC_IMGS = 16;       // images per workgroup
 
 // slab[ks][m][64] = sum_{k in K-slice ks} A[m][k] * Bm(k, n)   on v_mfma_f32_32x32x2_f32.
 // A is [M][K] row-major.  B_KMAJOR == false: Bm(k,n) = Bp[k*64 + n] (fc_mu|fc_var weights, N = 64);
@@ -85,35 +84,6 @@ __global__ __launch_bounds__(256) void decin_dz_finish_kernel(const float* __res
     dzcat[idx] = acc;
 }
 
-// part[ks][b][64] = sum_{k in split ks} flat[b][k] * Wfc[k][n]
-__global__ __launch_bounds__(256) void fc_fwd_partial_kernel(const float* __restrict__ flat, const float* __restrict__ wfc,
-                                                             float* __restrict__ part, int B, int K) {
-    extern __shared__ __attribute__((aligned(16))) float lds_f[];   // [FC_IMGS][kchunk]
-    const int kchunk = K / FC_KS;
-    const int b0 = blockIdx.x * FC_IMGS, ks = blockIdx.y, k0 = ks * kchunk;
-    const int n = threadIdx.x & 63, bq = threadIdx.x >> 6;
-    for (int q = threadIdx.x; q < FC_IMGS * kchunk / 4; q += 256) {
-        const int i = q / (kchunk / 4), k4 = q % (kchunk / 4);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (b0 + i < B) v = *reinterpret_cast<const float4*>(flat + (size_t)(b0 + i) * K + k0 + k4 * 4);
-        *reinterpret_cast<float4*>(lds_f + i * kchunk + k4 * 4) = v;
-    }
-    __syncthreads();
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    const float* f = lds_f + (bq * 4) * kchunk;
-#pragma unroll 8
-    for (int k = 0; k < kchunk; ++k) {
-        const float wv = wfc[(size_t)(k0 + k) * 64 + n];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = fmaf(f[i * kchunk + k], wv, acc[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int b = b0 + bq * 4 + i;
-        if (b < B) part[((size_t)ks * B + b) * 64 + n] = acc[i];
-    }
-}
-
 // mu, logvar = bias + sum of partials; z = mu + eps*exp(0.5*logvar); zcat = [z | pred]
 __global__ __launch_bounds__(256) void fc_finish_kernel(const float* __restrict__ part, const float* __restrict__ bfc,
                                                         const float* __restrict__ eps, const float* __restrict__ pred,
@@ -163,63 +133,6 @@ __global__ __launch_bounds__(256) void decin_fwd_kernel(const float* __restrict_
         if (b0 + m < B) Act<AT>::st4(h, (size_t)(b0 + m) * K + j, acc[m]);
 }
 
-// dzcat[b][i] = sum_j dh[b][j] * Wd[i][j].  One wave = 2 images x all 33 rows of Wd: lanes split K,
-// 66 per-lane partial sums, one shuffle reduction per output at the end (no LDS, no barriers).
-__global__ __launch_bounds__(256) void decin_bwd_dz_kernel(const float* __restrict__ dh, const float* __restrict__ wd,
-                                                           float* __restrict__ dzcat, int B, int K) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b0 = (blockIdx.x * 4 + wave) * 2;
-    if (b0 >= B) return;
-    const bool two = b0 + 1 < B;
-    float acc0[33], acc1[33];
-#pragma unroll
-    for (int i = 0; i < 33; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
-    for (int j = lane * 4; j < K; j += 256) {
-        const float4 g0 = *reinterpret_cast<const float4*>(dh + (size_t)b0 * K + j);
-        const float4 g1 = two ? *reinterpret_cast<const float4*>(dh + (size_t)(b0 + 1) * K + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int i = 0; i < 33; ++i) {
-            const float4 w = *reinterpret_cast<const float4*>(wd + (size_t)i * K + j);
-            acc0[i] += (g0.x * w.x + g0.y * w.y) + (g0.z * w.z + g0.w * w.w);
-            acc1[i] += (g1.x * w.x + g1.y * w.y) + (g1.z * w.z + g1.w * w.w);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 33; ++i) {
-        const float s0 = wave_sum(acc0[i]), s1 = wave_sum(acc1[i]);
-        if (lane == 0) { dzcat[b0 * 33 + i] = s0; if (two) dzcat[(b0 + 1) * 33 + i] = s1; }
-    }
-}
-
-// slab[bs][i][j] (i<33: dWd, i==33: dbd) = sum over the batch slice bs
-template <typename AT>
-__global__ __launch_bounds__(256) void decin_bwd_dw_kernel(const float* __restrict__ zcat, const float* __restrict__ dh,
-                                                           float* __restrict__ slab, int B, int K, int bPerSplit) {
-    constexpr int ZB = 16;                          // batch rows staged per barrier pair
-    __shared__ float z[ZB * 33];
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    const int b0 = blockIdx.y * bPerSplit;
-    int b1 = b0 + bPerSplit; if (b1 > B) b1 = B;
-    float acc[34];
-#pragma unroll
-    for (int i = 0; i < 34; ++i) acc[i] = 0.f;
-    for (int bb = b0; bb < b1; bb += ZB) {
-        const int nb = b1 - bb < ZB ? b1 - bb : ZB;
-        __syncthreads();
-        for (int q = threadIdx.x; q < nb * 33; q += 256) z[q] = zcat[bb * 33 + q];
-        __syncthreads();
-        for (int r = 0; r < nb; ++r) {
-            const float g = Act<AT>::ld(dh, (size_t)(bb + r) * K + j);
-#pragma unroll
-            for (int i = 0; i < 33; ++i) acc[i] = fmaf(z[r * 33 + i], g, acc[i]);
-            acc[33] += g;
-        }
-    }
-    float* o = slab + (size_t)blockIdx.y * 34 * K;
-#pragma unroll
-    for (int i = 0; i < 34; ++i) o[(size_t)i * K + j] = acc[i];
-}
-
 // dml[b][0..31] = dz + dmu_loss ; dml[b][32..63] = dz*eps*0.5*exp(0.5*logvar) + dlv_loss
 __global__ __launch_bounds__(256) void fc_bwd_prep_kernel(const float* __restrict__ dzcat, const float* __restrict__ eps,
                                                           const float* __restrict__ logvar, const float* __restrict__ dmu_loss,
@@ -264,23 +177,6 @@ __global__ __launch_bounds__(256) void fc_bwd_dflat_kernel(const float* __restri
         }
         Act<AT>::st(dflat, (size_t)(b0 + i) * K + k, acc);
     }
-}
-
-// dWfc[k][n] = sum_b flat[b][k] * dml[b][n]    (16 k-rows per workgroup: each wave 4 rows x 64 columns, all of
-// the batch; the four flat values of a row group are one 16-byte wave-uniform load per image)
-template <typename AT>
-__global__ __launch_bounds__(256) void fc_bwd_dw_kernel(const float* __restrict__ flat, const float* __restrict__ dml,
-                                                        float* __restrict__ dwfc, int B, int K) {
-    const int n = threadIdx.x & 63, k = blockIdx.x * 16 + (threadIdx.x >> 6) * 4;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll 8
-    for (int b = 0; b < B; ++b) {
-        const f32x4 f = Act<AT>::ld4(flat, (size_t)b * K + k);
-        const float d = dml[(size_t)b * 64 + n];
-        a0 = fmaf(f.x, d, a0); a1 = fmaf(f.y, d, a1); a2 = fmaf(f.z, d, a2); a3 = fmaf(f.w, d, a3);
-    }
-    dwfc[(size_t)k * 64 + n] = a0; dwfc[(size_t)(k + 1) * 64 + n] = a1;
-    dwfc[(size_t)(k + 2) * 64 + n] = a2; dwfc[(size_t)(k + 3) * 64 + n] = a3;
 }
 
 // precision mode 1: the two batch-contracted weight gradients  C[m][n] = sum_b A[b][m] * Bm[b][n]  on the bf16 MFMA
@@ -438,7 +334,7 @@ __global__ __launch_bounds__(256) void bgemm_tr_kernel(BGemmArgs a) {
 
 // fp32 mode: the same batch-contracted weight gradients on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32: one A and one B
 // value per lane and k-step, read as conflict-free LDS rows — no transposition needed).  Replaces the serial VALU loops
-// over the batch (fc_bwd_dw_kernel) and the batch-split slabs + two slab reductions (decin_bwd_dw_kernel).
+// over the batch and the batch-split slabs + two slab reductions they replaced.
 // A_PAD: A is [b][a_cols] fp32 with an implicit ones column at a_cols (decoder_input); else A is [b][lda] and the
 // workgroup takes columns m0..m0+MC.
 template <int MBLK, int NBLK, bool A_PAD>
@@ -579,18 +475,10 @@ int launch_decin_bwd(int width, int B, const float* zcat, const float* dh, const
         CVAE_CHECK_LAUNCH();
         return 0;
     }
-    {                    // fp32: [zcat | 1]^T . dh on the fp32 MFMA, whole batch per workgroup
-        BGemmArgs g{zcat, dh, 33, K, 33, dwd, K, 33, dbd, B};
-        hipLaunchKernelGGL((bgemm_f32_kernel<2, 1, true>), dim3(K / 32), dim3(256), 0, st, g);
-        CVAE_CHECK_LAUNCH();
-        return 0;
-    }
-    const int S = decin_splits(B), bps = cdiv(B, S);
-    hipLaunchKernelGGL(decin_bwd_dw_kernel<float>, dim3(K / 256, S), dim3(256), 0, st, zcat, dh, ws, B, K, bps);
+    BGemmArgs g{zcat, dh, 33, K, 33, dwd, K, 33, dbd, B};           // fp32: [zcat | 1]^T . dh on the fp32 MFMA, whole batch per workgroup
+    hipLaunchKernelGGL((bgemm_f32_kernel<2, 1, true>), dim3(K / 32), dim3(256), 0, st, g);
     CVAE_CHECK_LAUNCH();
-    int rc = launch_reduce_slabs(ws, dwd, (int64_t)33 * K, S, (int64_t)34 * K, st);
-    if (rc) return rc;
-    return launch_reduce_slabs(ws + (size_t)33 * K, dbd, K, S, (int64_t)34 * K, st);
+    return 0;
 }
 
 int launch_fc_bwd(int width, int B, const float* flat, const float* wfc, const float* dzcat, const float* eps,

@@ -514,28 +514,143 @@ def test_bf16_step_never_stores_y0_unless_a_block0_gamma_is_tiny(B, vec_bound, t
             assert gk[0] == 0 and rk[0] == 0          # gamma = 0, beta = 0: the channel's output is 0 everywhere and ReLU'(0) = 0 blocks its gradient
 
 
-@pytest.mark.parametrize("W,B", [(64, 8), (64, 5), (64, 37), (128, 5), (128, 37)])  # 5, 37: ragged tile counts (the persistent D4 / MS-SSIM / E1 / conv loops end unevenly);
-def test_bf16_kernels_exact_on_their_stored_operands(W, B):                       # 128 x 128: the other set of instantiations (every spatial size doubles)
-    """Layout / indexing check of every bf16-mode contraction, independent of the bf16 rounding noise: after one
-    bf16 step the workspace holds the bf16 activations and activation gradients the kernels actually consumed.
-    Recomputing each layer's result on the CPU in fp32 from THOSE operands (weights rounded to bf16 as the packed
-    copies are) must reproduce the kernel outputs up to fp32 summation order (weight / bias gradients: 2e-3 of the
-    tensor max) or up to the bf16 rounding of the stored result (activations: 2^-8 of the tensor max).  Catches
-    what the statistical bounds above cannot: a wrong tap, channel or pixel permutation in the transposed-LDS-read
-    weight-gradient kernels, the phase-collapsed up-convs or the E1 / fc permuting finishes."""
+def _bf16_step(W, B):
+    """One bf16-mode forward + loss + backward of B images; returns (vae, trainer, x, pred, eps, running statistics before it)."""
     from critic_vae_amd.nets import VariationalAutoencoder
     from critic_vae_amd.train import FusedTrainer
-    from ws_tools import check_bf16_stored_operands
     dev = torch.device("cuda:0")
     vae = VariationalAutoencoder(width=W, max_batch=B, seed=0, precision="bf16").to(dev)
     tr = FusedTrainer(vae)
     x, pred, eps = (torch.from_numpy(v).to(dev) for v in synth.make_batch(1234, 0, B, W))
     h, theta = vae.handle, vae.theta.data
+    bn0 = vae.bn_state.clone()
     h.forward(B, x, pred, eps, theta, vae.bn_state, tr.mu, tr.logvar, tr.recon, tr.ws, train=True)
     h.loss(B, x, tr.mu, tr.logvar, tr.recon, tr.ws, tr.scalars, tr.d_recon, tr.d_mu, tr.d_logvar)
     h.backward(B, x, pred, eps, theta, tr.logvar, tr.recon, tr.d_recon, tr.d_mu, tr.d_logvar, tr.ws, tr.grads)
     torch.cuda.synchronize()
-    check_bf16_stored_operands(h, tr.ws, B, x, theta, tr.grads, tr.recon, tr.d_recon)
+    return vae, tr, x, pred, eps, bn0
+
+
+# 5, 37: ragged tile counts (the persistent D4 / MS-SSIM / E1 / conv loops end unevenly); 128 x 128: the other set of instantiations (every
+# spatial size doubles); 133: every fc kernel runs past its first block and ends partway through its last one (latent_gemm 128 + 5 images,
+# fc_bwd_dflat 4 x 32 + 5, decin_fwd 8 x 16 + 5)
+@pytest.mark.parametrize("W,B", [(64, 8), (64, 5), (64, 37), (128, 5), (128, 37), (64, 133), (128, 133)])
+def test_bf16_kernels_exact_on_their_stored_operands(W, B):
+    """Layout / indexing check of every link of the bf16-mode step, independent of the bf16 rounding noise: after one bf16 step the
+    workspace holds the bf16 activations and activation gradients the kernels actually consumed.  Recomputing each link on the CPU from
+    THOSE operands (ws_tools.check_bf16_stored_operands: the convs, BatchNorm statistics and running statistics, BatchNorm / pool / act
+    forward and backward with dgamma / dbeta, fc_mu | fc_var, reparameterize, decoder_input forward and input gradient, the fc backward,
+    the loss) must reproduce the kernel outputs up to fp32 summation order or up to one bf16 rounding of the stored result.  Catches
+    what the statistical bounds above cannot: a wrong tap, channel or pixel permutation, a skipped tail image, a wrong flatten order or
+    pixel count, a tie routed to the wrong pool position."""
+    import time
+    from ws_tools import check_bf16_stored_operands
+    vae, tr, x, pred, eps, bn0 = _bf16_step(W, B)
+    ties, t0 = {}, time.perf_counter()
+    worst = check_bf16_stored_operands(vae.handle, tr, B, x, pred, eps, vae.theta.data, bn0, vae.bn_state, ties=ties)
+    print(f"W={W} B={B}: check {time.perf_counter() - t0:.1f} s; near-tie windows {ties}; err / allowed: "
+          + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+
+
+def test_stored_operand_check_names_each_corrupted_link():
+    """The links of check_bf16_stored_operands bite: after one bf16 step at (64, 133), a COPY of one link's stored result is corrupted in
+    the ragged tail (the last image, past the fc kernels' first blocks), and the check must fail naming that link.  Only copies change;
+    every kernel ran once, on the real data."""
+    import types
+    from ws_tools import check_bf16_stored_operands
+    W, B = 64, 133
+    vae, tr, x, pred, eps, bn0 = _bf16_step(W, B)
+    h, theta = vae.handle, vae.theta.data
+    names = ("ws", "grads", "mu", "logvar", "recon", "d_recon", "d_mu", "d_logvar", "scalars")
+    clean = {k: getattr(tr, k).clone() for k in names}
+    clean_bn = vae.bn_state.clone()
+    work = types.SimpleNamespace(**{k: v.clone() for k, v in clean.items()})
+    bn1 = clean_bn.clone()
+    K, last = 4096, B - 1
+
+    def off(name):
+        o = h.lib.cvae_ws_offset(h.h, B, name.encode())
+        assert o >= 0, name
+        return o
+
+    def bf16_last(name, per):       # the last image's elements of a stored bf16 tensor (a view into the copy)
+        return work.ws.view(torch.bfloat16)[2 * off(name) + last * per:2 * off(name) + B * per]
+
+    def windows(name, s, c):        # the last image of a stored bf16 NHWC tensor as (s/2, s/2, c, 4) windows, scan order
+        return bf16_last(name, s * s * c).view(s // 2, 2, s // 2, 2, c).permute(0, 2, 4, 1, 3).reshape(s // 2, s // 2, c, 4)
+
+    def c_mu():
+        work.mu[last, 31] += 1e-3 * clean["mu"].abs().max()
+
+    def c_zcat():
+        work.ws[off("zcat") + last * 33 + 32] += 0.5
+
+    def c_h():
+        v = bf16_last("h", K).view(-1, 256)
+        t = v[:, 3].clone()
+        v[:, 3] = v[:, 7]
+        v[:, 7] = t
+
+    def c_d_zcat():
+        row = work.ws[off("d_zcat") + last * 33:off("d_zcat") + B * 33]
+        row[int(row.abs().argmax())] = 0.0
+
+    def c_d_a3():
+        v = bf16_last("d_a3", K)
+        j = int(v.float().abs().argmax())
+        v[j] = (v[j].float() * 1.02).to(torch.bfloat16)
+
+    def c_dw_fc():                  # the last image's outer product a3 (x) bf16(dml) taken out of the fc weight gradient
+        dz = work.ws[off("d_zcat") + last * 33:off("d_zcat") + last * 33 + 32]
+        ex = 0.5 * eps[last] * torch.exp(0.5 * work.logvar[last])
+        dml = torch.cat((dz + work.d_mu[last], dz * ex + work.d_logvar[last])).to(torch.bfloat16).float()
+        o, n_ = h.layout["fc.w"]
+        work.grads[o:o + n_].view(K, 64).sub_(torch.outer(bf16_last("a3", K).float(), dml))
+
+    def c_d_logvar():
+        j = int(work.d_logvar[last].abs().argmax())
+        work.d_logvar[last, j] *= 1.01
+
+    def c_coef1():
+        cf = work.ws[off("coef1"):off("coef1") + 4 * 64].view(64, 4)
+        cf[int(cf[:, 2].abs().argmax()), 2] *= 1.005
+
+    def c_running_var2():
+        bn1[480 + 96 + 5] *= 1.001
+
+    def c_a2():                     # one pooled value of the last image taken from another window position
+        cf = work.ws[off("coef2"):off("coef2") + 4 * 128].view(128, 4)
+        nw = torch.relu(windows("y2", 16, 128).float() * cf[:, 0, None] + cf[:, 1, None])
+        srt = nw.sort(dim=-1, descending=True).values
+        j = int((srt[..., 0] - srt[..., 1]).flatten().argmax())
+        bf16_last("a2", 8 * 8 * 128)[j] = srt[..., 1].flatten()[j].to(torch.bfloat16)
+
+    def c_d_y2():                   # the last image's gradient moved between two positions of one window
+        w = windows("d_y2", 16, 128)
+        j = int((w[..., 0].float() - w[..., 1].float()).abs().flatten().argmax())
+        v = w.reshape(-1, 4)[j].clone()
+        wv = bf16_last("d_y2", 16 * 16 * 128).view(8, 2, 8, 2, 128)
+        py, px, c = j // (8 * 128), (j // 128) % 8, j % 128
+        wv[py, 0, px, 0, c], wv[py, 0, px, 1, c] = v[1], v[0]
+
+    def c_dgamma1():
+        o, _ = h.layout["enc1.gamma"]
+        g = work.grads[o:o + 64]
+        g[int(g.abs().argmax())] *= 1.1
+
+    cases = [("mu", c_mu), ("zcat", c_zcat), ("h", c_h), ("d_zcat", c_d_zcat), ("d_a3", c_d_a3), ("dW fc", c_dw_fc),
+             ("loss d_logvar", c_d_logvar), ("coef1 mean", c_coef1), ("running_var2", c_running_var2), ("a2", c_a2), ("d_y2", c_d_y2),
+             ("dgamma1", c_dgamma1)]
+    for link, corrupt in cases:
+        for k, v in clean.items():
+            getattr(work, k).copy_(v)
+        bn1.copy_(clean_bn)
+        corrupt()
+        torch.cuda.synchronize()
+        with pytest.raises(AssertionError) as ei:
+            check_bf16_stored_operands(h, work, B, x, pred, eps, theta, bn0, bn1)
+        assert str(ei.value).startswith(link), (link, str(ei.value)[:300])
+        print(f"{link}: {str(ei.value)[:160]}")
 
 
 @pytest.mark.parametrize("B", [40, 1029])      # 40: two ragged 32-image groups, four / two K slices;  1029: the large-batch paths

@@ -42,26 +42,66 @@ def recompute_d_y0(h, ws, B, width=64, bf16_storage=False, x=None, theta=None):
     return d_y0
 
 
-def check_bf16_stored_operands(h, ws, B, x, theta, grads, recon, d_recon, images=None, mult=1):
-    """After one bf16-mode step of B images on handle h (workspace ws, frames x, parameters theta, gradient buffer grads, recon and
-    d_recon as cvae_forward / cvae_loss wrote them): recompute every layer's result on the CPU in fp32 from the bf16 operands the
-    kernels stored (weights rounded to bf16 as the packed copies are) and compare.  Activations and activation gradients: up to the
-    bf16 rounding of the stored result (2^-8 of the tensor max); weight / bias gradients: up to fp32 summation order (2e-3).
+U32 = 2.0 ** -24          # fp32 unit roundoff
+BF16 = 2.0 ** -8          # one round-to-nearest bf16 rounding (8 significant bits): |bf16(v) - v| <= 2^-8 |v|
+FC_KS = 32                # fc.hip: K slices of latent_gemm, summed by fc_finish / decin_dz_finish
+BN_OFF = (0, 32, 96, 224)  # per-block channel offsets of the running means (bn_state[0:480]) and variances (bn_state[480:960])
+# BatchNorm forward statistics: every partial is an fp32 sum of at most 512 conv outputs, taken before the bf16 rounding (conv_epilogue.h:
+# per-tile sum / M2 of the accumulators; conv_thin.hip: the strip's raw S0 / Q0; conv_bf16_big.hip: M2 in double), with chains of at most
+# 128 additions plus a tree of 16: <= 144 u = 8.6e-6 of the sum of |terms|, merged in fp64 (bn_fwd_reduce / finalize).
+BN_STAT_REL = 1e-5
+
+
+def check_bf16_stored_operands(h, tr, B, x, pred, eps, theta, bn_before, bn_after, images=None, mult=1, ties=None):
+    """After one bf16-mode step of B images on handle h: recompute every link of the step on the CPU from the operands the kernels
+    stored and compare.  tr holds the step's buffers (ws, grads, mu, logvar, recon, d_recon, d_mu, d_logvar, scalars: a FusedTrainer
+    or anything with those attributes); x, pred, eps are the step's inputs, theta its parameters, bn_before / bn_after the BatchNorm
+    running statistics before and after the forward.  Operands are what each kernel reads: bf16 activations as stored, fp32 weights
+    where the kernel takes fp32 (latent_gemm, decin_fwd, fc_bwd_dflat), weights rounded to bf16 where the packed copies are.
+
+    Links, in the order the step computes them, so that a wrong stored result fails at the link that produced it before any link
+    that reads it (each assertion message starts with the link's name):
+      y{l}, coef{l} mean / var, running_mean{l} / running_var{l}, a{l}   per encoder block: the conv; the batch statistics of its fp32
+                  output (recomputed), the running statistics (unbiased over the WHOLE batch); act(maxpool(fma(y, scale, shift))) of
+                  the stored bf16 y and coef, one bf16 rounding
+      mu, logvar, zcat   a3 (NCHW flatten) . [fc_mu | fc_var]^T + b, fp32 summation order;  [mu + eps exp(logvar / 2) | pred]
+      h, o{i}, recon     zcat . Wd^T + bd, one bf16 rounding;  the decoder convs and D4
+      loss scalars, loss d_recon / d_mu / d_logvar   the oracle's MS-SSIM + KL on the stored recon / mu / logvar: scalars to 2e-5,
+                  gradients to 1e-4 of their max (the test_msssim bars)
+      dW / db dec4, d_o3, dW / db dec{i}, dW / db decoder_input, d_zcat (d_h . Wd), d_a3 (dml . Wfc, one bf16 rounding), dW / db fc
+      dgamma{l}, dbeta{l}, d_y{l} (l = 1..3), dW / db enc{l}, d_a{l-1}   per encoder block, last first: the bn.hip backward
+                  (gradient at the first window maximum), one bf16 rounding; the conv gradients
+    Activations and activation gradients: elementwise, one bf16 rounding of the stored result plus the bound of the fp32 arithmetic
+    that produced it; sums: the worst-case fp32 error depth * 2^-24 of the sum of |terms|, depth = the longest chain of additions
+    the kernel's fixed order takes.  Weight / bias gradients of the convs and fc layers: 2e-3 of the tensor max.
     images = (i0, i1): only images [i0, i1) are read and recomputed (default: all B).  mult: every image of the step occurs `mult`
-    times in it (a batch of replicas of those images, each bitwise equal to the one checked): the weight-gradient reference is mult
-    times the recomputation on the images checked."""
+    times in it (a batch of replicas of those images, each bitwise equal to the one checked): batch statistics are the images' own,
+    sums over the batch are mult times theirs, per-image loss gradients (i1 - i0) / B times the checked images' loss gradients.
+    Returns {link: largest err / allowed err} (<= 1 passes).  ties: a dict that receives, per d_y{l}, the number of windows whose two
+    largest normalised values are within 4 fp32 ulps (not equal): there only the window sum is compared, and the routed gradient must
+    sit at one of the near-tied positions."""
     import torch.nn.functional as F
     from critic_vae_amd import layout as L
+    from oracle import cvae_oracle as orc
+    ws, grads, recon, d_recon = tr.ws, tr.grads, tr.recon, tr.d_recon
     i0, i1 = images if images is not None else (0, B)
     n, W = i1 - i0, h.width
     m = W // 64
+    K = 4096 * m * m
     dev = ws.device
     ws16 = ws.view(torch.bfloat16)
+    worst = {}
+    ties = ties if ties is not None else {}
 
     def slot(name, per):            # images [i0, i1) of a stored bf16 tensor with `per` elements per image, as a flat fp32 view
         off = h.lib.cvae_ws_offset(h.h, B, name.encode())
         assert off >= 0, name
         return ws[off + i0 * per // 2:off + i1 * per // 2]
+
+    def f32slot(name, per):         # images [i0, i1) of a stored fp32 tensor, (n, per) float64 on the CPU
+        off = h.lib.cvae_ws_offset(h.h, B, name.encode())
+        assert off >= 0, name
+        return ws[off + i0 * per:off + i1 * per].view(n, per).double().cpu()
 
     # neither y0 nor block 0's dy is stored: both exist only inside the fused E1 weight-gradient kernel.  Recompute y0 of the images
     # with the stand-alone conv op, then their d_y0 with the stand-alone BatchNorm-backward op from the a0 / d_a0 / coef0 the step left
@@ -82,6 +122,8 @@ def check_bf16_stored_operands(h, ws, B, x, theta, grads, recon, d_recon, images
     def act(name, c, s):            # stored bf16 NHWC tensor -> fp32 NCHW on the CPU
         if name == "d_y0":
             return d_y0[:n * s * s * c].float().view(n, s, s, c).permute(0, 3, 1, 2).contiguous().cpu()
+        if name == "y0":
+            return y0.view(torch.bfloat16)[:n * s * s * c].float().view(n, s, s, c).permute(0, 3, 1, 2).contiguous().cpu()
         off = h.lib.cvae_ws_offset(h.h, B, name.encode())
         assert off >= 0, name
         per = s * s * c
@@ -89,39 +131,89 @@ def check_bf16_stored_operands(h, ws, B, x, theta, grads, recon, d_recon, images
 
     ref = L.native_to_ref(h.layout, theta.cpu())
     grd = L.native_to_ref(h.layout, grads.cpu())
-    bf = lambda t: t.to(torch.bfloat16).float()      # noqa: E731
+    bf = lambda t: t.to(torch.bfloat16).to(t.dtype)      # noqa: E731
     enc = [(3, 32, 64 * m), (32, 64, 32 * m), (64, 128, 16 * m), (128, 256, 8 * m)]
     dec = [(256, 128, 4 * m), (128, 64, 8 * m), (64, 32, 16 * m), (32, 32, 32 * m), (32, 3, 64 * m)]
-    worst = {}
 
     def close(got, want, what, rel):
         scale = want.abs().max().item()
         err = (got - want).abs().max().item()
-        worst[what] = err / max(scale, 1e-30)
+        worst[what] = err / max(rel * scale, 1e-30)
         assert err <= rel * scale + 1e-12, f"{what}: err {err:.3e} vs max {scale:.3e}"
+
+    def within(what, got, want, bound):     # elementwise |got - want| <= bound (NaN fails)
+        got, want, bound = got.double(), want.double(), bound.double()
+        assert got.shape == want.shape, (what, got.shape, want.shape)
+        err = (got - want).abs()
+        r = (err / bound.clamp_min(1e-300)).max().item() if err.numel() else 0.0
+        worst[what] = r
+        if not r <= 1.0:
+            k = int(torch.nan_to_num(err / bound.clamp_min(1e-300), nan=float("inf")).flatten().argmax())
+            raise AssertionError(f"{what}: err / allowed {r:.3e} (at flat index {k}: got {got.flatten()[k].item():.6e}, "
+                                 f"want {want.flatten()[k].item():.6e}, allowed {bound.flatten()[k].item():.3e})")
 
     def wgrad(inp, dout):           # dW (O,I,5,5), db of a 5x5 / pad 2 conv from its input and output gradient, times mult
         return (mult * torch.nn.grad.conv2d_weight(inp, (dout.shape[1], inp.shape[1], 5, 5), dout, padding=2),
                 mult * dout.sum(dim=(0, 2, 3)))
 
-    # ---- encoder: forward conv, weight / bias gradient, input gradient ----
+    # ---- encoder forward: per block the conv, its BatchNorm statistics and running statistics, BatchNorm / pool / act ----
+    bn0, bn1 = bn_before.double().cpu(), bn_after.double().cpu()
+
+    def windows(l, co, s):          # stored bf16 y of block l as 2x2 windows (scan order (0,0) (0,1) (1,0) (1,1)), coef, fmaf(y, sc, sh)
+        cf = h.ws_view(ws, B, f"coef{l}", 4 * co).double().cpu().view(co, 4)
+        c4 = [cf[:, k].view(1, co, 1, 1, 1) for k in range(4)]
+        yw = act(f"y{l}", co, s).double().view(n, co, s // 2, 2, s // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, co, s // 2, s // 2, 4)
+        return cf, c4, yw, (yw * c4[0] + c4[1]).float().double()      # fmaf: one fp32 rounding of the exact value
+
     for l, (ci, co, s) in enumerate(enc):
         inp = bf(x[i0:i1].cpu()) if l == 0 else act(f"a{l - 1}", ci, s)
         wk, bk = f"encoder.model.{4 * l}.weight", f"encoder.model.{4 * l}.bias"
         y = F.conv2d(inp, bf(ref[wk]), ref[bk], padding=2)
-        if l == 0:
-            close(y0.view(torch.bfloat16)[:n * s * s * co].float().view(n, s, s, co).permute(0, 3, 1, 2).cpu(), y, "y0", 2.0 ** -8)
-        else:
-            close(act(f"y{l}", co, s), y, f"y{l}", 2.0 ** -8)
-        dy = act(f"d_y{l}", co, s)
-        dw, db = wgrad(inp, dy)
-        close(grd[wk], dw, f"dW enc{l}", 2e-3)
-        # pre-BatchNorm bias: the true gradient cancels to ~0, so compare against the size of the summed terms
-        assert (grd[bk] - db).abs().max().item() <= 1e-5 * mult * dy.abs().sum(dim=(0, 2, 3)).max().item() + 1e-7, f"db enc{l}"
-        if l > 0:
-            da = F.conv_transpose2d(dy, bf(ref[wk]), padding=2)
-            close(act(f"d_a{l - 1}", ci, s), da, f"d_a{l - 1}", 2.0 ** -8)
-    # ---- decoder: D0 plain, D1..D3 behind a nearest-2x upsample (phase-collapsed in the kernels) ----
+        close(act(f"y{l}", co, s), y, f"y{l}", 2.0 ** -8)               # block 0: the y0 recomputed above
+        # -- statistics: the kernels sum the fp32 conv output before rounding it, so compare with the batch statistics of y --
+        cf, (sc, sh, mn, istd), yw, nwin = windows(l, co, s)
+        yd = y.double()
+        mean, var = yd.mean(dim=(0, 2, 3)), yd.var(dim=(0, 2, 3), unbiased=False)
+        sq = (yd ** 2).mean(dim=(0, 2, 3)) + ((yd - ref[bk].double().view(1, -1, 1, 1)) ** 2).mean(dim=(0, 2, 3))
+        within(f"coef{l} mean", cf[:, 2], mean, BN_STAT_REL * sq.sqrt())
+        # invstd = 1 / sqrtf(var + 1e-5) in fp32 (a few ulps: 16 u of var + eps); the E1 strips' M2 = Q0 - S0^2 / n is about the
+        # bias, the others' about the tile mean: bound against both second moments
+        var_b = 2 * BN_STAT_REL * sq + 16 * U32 * (var + 1e-5)
+        within(f"coef{l} var", 1.0 / cf[:, 3] ** 2 - 1e-5, var, var_b)
+        o = BN_OFF[l]
+        rm0, rv0 = bn0[o:o + co], bn0[480 + o:480 + o + co]
+        N = B * s * s                                                   # the WHOLE batch's pixel count
+        within(f"running_mean{l}", bn1[o:o + co], 0.9 * rm0 + 0.1 * cf[:, 2], 4 * U32 * (0.9 * rm0.abs() + 0.1 * cf[:, 2].abs()))
+        rv = 0.9 * rv0 + 0.1 * var * N / (N - 1)
+        within(f"running_var{l}", bn1[480 + o:480 + o + co], rv, 0.1 * var_b * N / (N - 1) + 4 * U32 * rv.abs())
+        # -- a = act(max over the 2x2 window of fmaf(y, scale, shift)) on the stored bf16 y, one bf16 rounding --
+        top = nwin.max(dim=-1).values
+        a_ref = torch.tanh(top) if l == 3 else top.clamp_min(0.0)
+        within(f"a{l}", act(f"a{l}", co, s // 2), a_ref, (BF16 + 4 * U32) * a_ref.abs())
+    # ---- fc_mu | fc_var (latent_gemm<false, bf16>: bf16 a3 x fp32 weights on the fp32 MFMA, FC_KS K slices) + fc_finish ----
+    mu_g, lv_g = tr.mu[i0:i1].cpu(), tr.logvar[i0:i1].cpu()
+    a3 = act("a3", 256, 4 * m).double().reshape(n, K)                   # NCHW flatten = the reference's view(-1, 256 * s * s)
+    wfc = torch.cat((ref["encoder.fc_mu.weight"], ref["encoder.fc_var.weight"]), 0).double()           # (64, K)
+    bfc = torch.cat((ref["encoder.fc_mu.bias"], ref["encoder.fc_var.bias"]), 0).double()
+    ml = a3 @ wfc.t() + bfc
+    # each slice: K / FC_KS products (a bf16 x fp32 product is rounded: +1) in series; then bias + FC_KS slabs in series
+    ml_abs = (a3.abs() @ wfc.abs().t() + bfc.abs()) * ((K // FC_KS + 1 + FC_KS + 1) * U32)
+    within("mu", mu_g, ml[:, :32], ml_abs[:, :32])
+    within("logvar", lv_g, ml[:, 32:], ml_abs[:, 32:])
+    zc = f32slot("zcat", 33)
+    e_, p_ = eps[i0:i1].double().cpu(), pred[i0:i1].double().cpu()
+    se = e_ * torch.exp(0.5 * lv_g.double())
+    # fp32: expf (a few ulps), the product and the sum: 8 ulps of the two terms
+    within("zcat", zc[:, :32], mu_g.double() + se, 8 * U32 * (mu_g.double().abs() + se.abs()))
+    assert torch.equal(zc[:, 32:], p_), "zcat: the pred column is not the step's pred"
+
+    # ---- decoder_input forward (decin_fwd<bf16>: fp32 zcat, fp32 Wd, fmaf from the bias over i = 0..32, bf16 store) ----
+    wd = ref["decoder.decoder_input.weight"].double()                   # (K, 33), rows in (C, H, W) order
+    bd = ref["decoder.decoder_input.bias"].double()
+    hr = (zc @ wd.t() + bd).view(n, 256, 4 * m, 4 * m)
+    hb = (zc.abs() @ wd.abs().t() + bd.abs()).view(n, 256, 4 * m, 4 * m) * (34 * U32)
+    within("h", act("h", 256, 4 * m), hr, BF16 * hr.abs() + (1 + BF16) * hb)
+    # ---- decoder forward: D0 plain, D1..D3 behind a nearest-2x upsample (phase-collapsed in the kernels) ----
     for i, (ci, co, s) in enumerate(dec[:4]):
         src = act("h", 256, 4 * m) if i == 0 else act(f"o{i - 1}", ci, s // 2)
         inp = src if i == 0 else F.interpolate(src, scale_factor=2, mode="nearest")
@@ -129,17 +221,6 @@ def check_bf16_stored_operands(h, ws, B, x, theta, grads, recon, d_recon, images
         o = torch.relu(F.conv2d(inp, bf(ref[wk]), ref[bk], padding=2))
         # D1..D3 round the PRE-SUMMED collapsed weights to bf16, not the 5x5 ones: allow one more bf16 rounding
         close(act(f"o{i}", co, s), o, f"o{i}", 2.0 ** -8 if i == 0 else 2.0 ** -6)
-        do = act(f"d_o{i}", co, s)
-        dw, db = wgrad(inp, do)
-        close(grd[wk], dw, f"dW dec{i}", 2e-3)
-        close(grd[bk], db, f"db dec{i}", 2e-3)
-    # ---- decoder_input: [zcat | 1]^T . d_h ----
-    off = h.lib.cvae_ws_offset(h.h, B, b"zcat")
-    zcat = ws[off + i0 * 33:off + i1 * 33].view(n, 33).cpu()
-    dh = act("d_h", 256, 4 * m)                                        # (n,256,4,4) = the reference's view(-1,256,4,4)
-    dwd = mult * (bf(zcat).t() @ dh.reshape(n, -1))                    # (33, 4096) in (C,H,W) column order
-    close(grd["decoder.decoder_input.weight"], dwd.t().contiguous(), "dW decoder_input", 2e-3)
-    close(grd["decoder.decoder_input.bias"], mult * dh.reshape(n, -1).sum(0), "db decoder_input", 2e-3)
     # ---- D4 (Upsample -> Conv(32->3) -> Tanh): forward on exact bf16 products; backward through G rounded to bf16 ----
     o3 = act("o3", 32, 32 * m)
     up3 = F.interpolate(o3, scale_factor=2, mode="nearest")
@@ -160,6 +241,21 @@ def check_bf16_stored_operands(h, ws, B, x, theta, grads, recon, d_recon, images
     rec = recon[i0:i1].cpu()
     close(rec, torch.tanh(pre), "recon", 1e-4)
     close(rec, torch.tanh(F.conv2d(up3, bf(w4), b4, padding=2)), "recon vs 5x5 weights", 2.0 ** -6)
+    # ---- loss (msssim.hip, shared with fp32 mode): the oracle on the stored recon, x, mu, logvar ----
+    rec = recon[i0:i1].cpu().clone().requires_grad_(True)
+    mu_r, lv_r = mu_g.clone().requires_grad_(True), lv_g.clone().requires_grad_(True)
+    lo = orc.vae_loss(x[i0:i1].cpu(), mu_r, lv_r, rec)
+    lo["total_loss"].backward()
+    want = torch.cat([torch.stack([lo["total_loss"], lo["recon_loss"], lo["KLD"]]).detach().float(), lo["ssim_levels"].float(),
+                      lo["cs_levels"].float()])
+    within("loss scalars", tr.scalars[:13].cpu(), want, torch.full((13,), 2e-5))
+    per = n / B                         # a batch-mean loss: the full batch's per-image gradient is n / B times the n images'
+    for what, got, g in (("loss d_recon", d_recon[i0:i1].cpu(), rec.grad), ("loss d_mu", tr.d_mu[i0:i1].cpu(), mu_r.grad),
+                         ("loss d_logvar", tr.d_logvar[i0:i1].cpu(), lv_r.grad)):
+        want = per * g.double()
+        within(what, got, want, torch.full_like(want, 1e-4 * want.abs().max().item()))
+
+    # ---- D4 backward ----
     dout = (d_recon[i0:i1] * (1.0 - recon[i0:i1] ** 2)).cpu()
     dw4, db4 = wgrad(up3, dout)
     close(grd["decoder.model.12.weight"], dw4, "dW dec4", 1e-2)         # the 2x2-block sums G are rounded to bf16
@@ -167,4 +263,103 @@ def check_bf16_stored_operands(h, ws, B, x, theta, grads, recon, d_recon, images
     d_up = F.conv_transpose2d(dout, bf(w4), padding=2)
     d_o3 = F.avg_pool2d(d_up, 2) * 4.0 * (o3 > 0).float()                # Upsample backward = 2x2 sum, then the ReLU mask
     close(act("d_o3", 32, 32 * m), d_o3, "d_o3", 2.0 ** -6)
+    # ---- decoder backward: D3..D0 weight / bias gradients ----
+    for i in (3, 2, 1, 0):
+        ci, co, s = dec[i]
+        src = act("h", 256, 4 * m) if i == 0 else act(f"o{i - 1}", ci, s // 2)
+        inp = src if i == 0 else F.interpolate(src, scale_factor=2, mode="nearest")
+        wk, bk = f"decoder.model.{3 * i}.weight", f"decoder.model.{3 * i}.bias"
+        dw, db = wgrad(inp, act(f"d_o{i}", co, s))
+        close(grd[wk], dw, f"dW dec{i}", 2e-3)
+        close(grd[bk], db, f"db dec{i}", 2e-3)
+    # ---- decoder_input: [zcat | 1]^T . d_h ----
+    dh = act("d_h", 256, 4 * m)                                        # (n,256,4,4) = the reference's view(-1,256,4,4)
+    dwd = mult * (bf(zc.float()).t() @ dh.reshape(n, -1))                    # (33, 4096) in (C,H,W) column order
+    close(grd["decoder.decoder_input.weight"], dwd.t().contiguous(), "dW decoder_input", 2e-3)
+    close(grd["decoder.decoder_input.bias"], mult * dh.reshape(n, -1).sum(0), "db decoder_input", 2e-3)
+    # ---- decoder_input input gradient (latent_gemm<true, bf16> + decin_dz_finish): d_h . Wd ----
+    dh_flat = act("d_h", 256, 4 * m).double().reshape(n, K)
+    dz = f32slot("d_zcat", 33)
+    within("d_zcat", dz, dh_flat @ wd, (dh_flat.abs() @ wd.abs()) * ((K // FC_KS + 1 + FC_KS) * U32))
+    # ---- fc backward: dml (fc_bwd_prep), d_a3 = dml . Wfc (fc_bwd_dflat<bf16>), dWfc = a3^T . bf16(dml), dbfc = colsum(dml) ----
+    lvd = lv_g.double()
+    ex = 0.5 * e_ * torch.exp(0.5 * lvd)
+    dml = torch.cat((dz[:, :32] + tr.d_mu[i0:i1].double().cpu(), dz[:, :32] * ex + tr.d_logvar[i0:i1].double().cpu()), 1)
+    dml_abs = torch.cat((dz[:, :32].abs() + tr.d_mu[i0:i1].double().cpu().abs(),
+                         (dz[:, :32] * ex).abs() + tr.d_logvar[i0:i1].double().cpu().abs()), 1)
+    da3 = (dml @ wfc).view(n, 256, 4 * m, 4 * m)
+    # dml: expf and three products, then 64 fmaf in series per output: 8 + 64 roundings of the terms
+    da3_b = (dml_abs @ wfc.abs()).view(n, 256, 4 * m, 4 * m) * ((64 + 8) * U32)
+    within("d_a3", act("d_a3", 256, 4 * m), da3, BF16 * da3.abs() + (1 + BF16) * da3_b)
+    dwfc = mult * (bf(dml).t() @ a3)                                    # the bf16 MFMA takes dml rounded to bf16
+    close(grd["encoder.fc_mu.weight"], dwfc[:32], "dW fc_mu", 2e-3)
+    close(grd["encoder.fc_var.weight"], dwfc[32:], "dW fc_var", 2e-3)
+    dbfc = mult * dml.sum(0)
+    close(grd["encoder.fc_mu.bias"], dbfc[:32], "db fc_mu", 2e-3)
+    close(grd["encoder.fc_var.bias"], dbfc[32:], "db fc_var", 2e-3)
+
+    # ---- encoder backward, last block first ----
+    for l in (3, 2, 1, 0):
+        ci, co, s = enc[l]
+        inp = bf(x[i0:i1].cpu()) if l == 0 else act(f"a{l - 1}", ci, s)
+        wk, bk = f"encoder.model.{4 * l}.weight", f"encoder.model.{4 * l}.bias"
+        cf, (sc, sh, mn, istd), yw, nw_ = windows(l, co, s)
+        a_st = act(f"a{l}", co, s // 2).double()
+        # -- backward statistics (bn_bwd_stats_relu_bf16 / bn_bwd_bf16<1, 0>) -> dgamma = s2, dbeta = s1, k = s / N --
+        da = act(f"d_a{l}", co, s // 2).double()
+        g = da * (1.0 - a_st ** 2) if l == 3 else da * (a_st > 0)
+        pos = nw_.argmax(dim=-1, keepdim=True)                         # first maximum in scan order, as the kernels take it
+        xw = (yw - mn) * istd
+        xm = xw.gather(-1, pos)[..., 0]
+        xw_abs = (yw.abs() + mn.abs()) * istd                          # the size of xhat's fp32 terms
+        xm_abs = xw_abs.gather(-1, pos)[..., 0]
+        gam = (sc / istd)[..., 0]
+        bet = (sh + mn * sc)[..., 0]
+        if l == 3:                                                      # tanh block: xhat from y at the argmax
+            xs, xs_abs = xm, xm_abs
+        else:                                                           # ReLU blocks: xhat = (a - beta) / gamma, unless |gamma| < 1e-2
+            tiny = gam.abs() < 1e-2
+            safe = torch.where(tiny, torch.ones_like(gam), gam)
+            xs = torch.where(tiny, xm, (a_st - bet) / safe)
+            xs_abs = torch.where(tiny, xm_abs, (a_st.abs() + bet.abs()) / safe.abs())
+        s1, s2 = g.sum(dim=(0, 2, 3)), (g * xs).sum(dim=(0, 2, 3))
+        t1, t2 = g.abs().sum(dim=(0, 2, 3)), (g.abs() * xs_abs).sum(dim=(0, 2, 3))     # + a few roundings per term: depth + 4
+        # depth of the fixed-order sums: pixels per thread, the workgroup's NSUB rows in series, then at most nblk partials
+        tot = B * (s // 2) ** 2
+        nblk = max(1, min(1024, tot // ((256 // co) * 8)))
+        nsub = 256 // (co // 8)
+        ppb = -(-tot // nblk)
+        depth = -(-ppb // nsub) + nsub + nblk + 4
+        gk, bek = f"encoder.model.{4 * l + 1}.weight", f"encoder.model.{4 * l + 1}.bias"
+        within(f"dgamma{l}", grd[gk], mult * s2, mult * depth * U32 * t2)
+        within(f"dbeta{l}", grd[bek], mult * s1, mult * depth * U32 * t1)
+        if l > 0:                   # -- the apply pass: dy = scale * ([p == argmax] g - k1 - xhat k2), bf16 --
+            Nk = n * s * s
+            k1, k2 = (s1 / Nk).view(1, co, 1, 1, 1), (s2 / Nk).view(1, co, 1, 1, 1)
+            dk1, dk2 = (depth * U32 * t1 / Nk).view(1, co, 1, 1, 1), (depth * U32 * t2 / Nk).view(1, co, 1, 1, 1)
+            sel = torch.zeros_like(xw).scatter_(-1, pos, g[..., None])
+            base = -k1 - xw * k2
+            d_ref = sc * (sel + base)
+            bnd = BF16 * d_ref.abs() + (1 + BF16) * sc.abs() * (dk1 + xw.abs() * dk2 + 4 * U32 * (sel.abs() + k1.abs() + xw_abs * k2.abs()))
+            d_st = act(f"d_y{l}", co, s).double().view(n, co, s // 2, 2, s // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, co, s // 2, s // 2, 4)
+            srt = nw_.sort(dim=-1, descending=True).values
+            gap = srt[..., 0] - srt[..., 1]
+            near = (gap > 0) & (gap <= 4 * 2.0 ** -23 * srt[..., 0].abs()) & (g != 0)
+            far = ~near
+            within(f"d_y{l}", d_st[far], d_ref[far], bnd[far])
+            ties[f"d_y{l}"] = int(near.sum())
+            if near.any():          # which near-tied position wins is not fixed by the operands: the window sum is, and the routed
+                within(f"d_y{l} near-tie window sums", d_st.sum(-1)[near], d_ref.sum(-1)[near], bnd.sum(-1)[near])
+                routed = (d_st - sc * base).abs().argmax(dim=-1, keepdim=True)      # gradient must sit at a near-tied position
+                nr = nw_.gather(-1, routed)[..., 0]
+                assert bool((nr[near] >= srt[..., 0][near] - 4 * 2.0 ** -23 * srt[..., 0][near].abs()).all()), \
+                    f"d_y{l}: a near-tie window routes its gradient to a position that is not near the maximum"
+        dy = act(f"d_y{l}", co, s)
+        dw, db = wgrad(inp, dy)
+        close(grd[wk], dw, f"dW enc{l}", 2e-3)
+        # pre-BatchNorm bias: the true gradient cancels to ~0, so compare against the size of the summed terms
+        assert (grd[bk] - db).abs().max().item() <= 1e-5 * mult * dy.abs().sum(dim=(0, 2, 3)).max().item() + 1e-7, f"db enc{l}"
+        if l > 0:
+            da_ = F.conv_transpose2d(dy, bf(ref[wk]), padding=2)
+            close(act(f"d_a{l - 1}", ci, s), da_, f"d_a{l - 1}", 2.0 ** -8)
     return worst
