@@ -97,10 +97,8 @@ struct cvae_handle_s {
     hipStream_t side = nullptr;
     hipEvent_t ev_ready[8] = {}, ev_side = nullptr;
     bool streams_ready = false;
-    bool e1_two_pass = false;        // bf16 mode: E1 forward as statistics pass + fused BatchNorm/pool pass (CVAE_E1_TWO_PASS=0: conv, then bn_pool_act_fwd)
     const void* xp_ws = nullptr;     // the workspace (and batch) whose packed bf16 frame the last train-mode forward wrote: the backward stages E1's strips from
     int xp_B = 0;                    // it only then (an eval-mode forward, or another workspace, leaves it stale -> the fp32 frame is staged instead)
-    bool fuse_e1 = true;             // block 0's BatchNorm backward applied inside E1's weight-gradient kernel (CVAE_FUSE_E1=0: separate apply pass, for A/B runs)
     ProbeState probe;
 };
 
@@ -140,9 +138,9 @@ static WsLayout carve(const cvae_handle_s* h, int B) {
         w.a[l] = act(B * (H / 2) * (H / 2) * C);
         w.coef[l] = take(C * 4);
         w.bnpart[l] = take((int64_t)2 * bn_num_tiles(l, W, B) * C);
-        // block 0's d_y exists only on the CVAE_FUSE_E1=0 path (E1's weight-gradient kernel applies the BatchNorm backward itself);
+        // block 0 has no d_y (E1's weight-gradient kernel applies the BatchNorm backward itself);
         // the slot keeps its offset entry (-1 -> "not allocated") for cvae_ws_offset
-        w.d_y[l] = (l == 0 && h->fuse_e1) ? -1 : act(B * H * H * C);
+        w.d_y[l] = l == 0 ? -1 : act(B * H * H * C);
         w.d_a[l] = act(B * (H / 2) * (H / 2) * C);
     }
     w.zcat = take((int64_t)B * 33);
@@ -195,8 +193,6 @@ int cvae_create(const cvae_config* cfg, cvae_handle* out) {
     if (cfg->precision < 0 || cfg->precision > 3) { cvae_set_error("cvae_create: precision %d not supported (0 = fp32, 1 = bf16 MFMA, 2 = fp32 emulated by 3-way bf16 splits)", cfg->precision); return CVAE_EUNSUPPORTED; }
     cvae_handle_s* h = new cvae_handle_s();
     h->cfg = *cfg;
-    { const char* e = getenv("CVAE_FUSE_E1"); h->fuse_e1 = !(e && e[0] == '0'); }
-    { const char* e = getenv("CVAE_E1_TWO_PASS"); h->e1_two_pass = cfg->precision == 1 && !(e && e[0] == '0'); }
     h->param_total = 0;
     h->K = 256 * (cfg->width / 16) * (cfg->width / 16);
     char nm[64];
@@ -316,23 +312,22 @@ int cvae_forward(cvae_handle h, int32_t B, const float* x, const float* pred, co
     RC(pack_bf16_weights(h, params, ws, w, st));
     for (int l = 0; l < 4; ++l) {
         int tpp = 1;                            // 128-pixel tiles per BatchNorm partial row, as reported by the conv kernel that ran
-        if (l == 0 && h->e1_two_pass) {
+        if (l == 0 && h->cfg.precision == 1) {
             // bf16 mode, block 0: conv (statistics only) -> merged statistics -> conv again with BatchNorm/pool/ReLU in its
-            // epilogue (writes y0 for the backward and a0); bn_pool_act_fwd's read of y0 is replaced by a second read of x
-            // the packed bf16 frame (slot xp) while it stays below 2 GiB (conv_route); past that every E1 pass stages the fp32 frame
+            // epilogue (writes a0); bn_pool_act_fwd's read of y0 is replaced by a second read of x, as the packed bf16 frame
+            // (slot xp) that the statistics pass writes while it stays below 2 GiB (conv_route); past that every E1 pass stages the fp32 frame
             float* xp = train && conv_route(1, 0, W, false, B).family == E1_PACKED_FRAME ? ws + w.xp : nullptr;
-            if (train) RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), nullptr, ws + w.bnpart[0], st, true, 1, nullptr, nullptr, true, xp));     // also writes xp
+            if (train) RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), nullptr, ws + w.bnpart[0], st, true, 1, nullptr, nullptr, xp));     // also writes xp
             h->xp_ws = xp ? wsv : nullptr; h->xp_B = B;
             RC(launch_bn_fwd_finalize(0, W, B, ws + w.bnpart[0], P_(h->enc_g[0]), P_(h->enc_be[0]), bn_state + kBnOff[0],
                                       bn_state + 480 + kBnOff[0], ws + w.coef[0], ws + w.scratch, train, st));
             { ProbeArm pa(h, 0, 0);
-              // y0 is written only for the CVAE_FUSE_E1=0 path (or, decided on the device, when a channel's gamma is tiny):
-              // the fused weight-gradient kernel recomputes it
+              // y0 is written only when a channel's gamma is tiny (decided on the device): the fused weight-gradient kernel recomputes it
               RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], nullptr, st, true, 2, ws + w.coef[0], ws + w.a[0],
-                               !h->fuse_e1, xp)); }          // eval mode (no statistics pass) or no packed frame: E1_POOL_X
+                               xp)); }               // eval mode (no statistics pass) or no packed frame: E1_POOL_X
             continue;
         }
-        if (l == 0) { ProbeArm pa(h, 0, 0); RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], ws + w.bnpart[0], st, h->cfg.precision == 1)); }
+        if (l == 0) { ProbeArm pa(h, 0, 0); RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], ws + w.bnpart[0], st)); }
         else if (use_bf16(h, l)) { ProbeArm pa(h, 0, l); RC(launch_conv_fwd_bf16(l, W, bf16_mode(h), B, ws + w.a[l - 1], ws + w.wpack, P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st, &tpp)); }
         else { ProbeArm pa(h, 0, l); RC(launch_conv_fwd(l, W, B, ws + w.a[l - 1], P_(h->enc_w[l]), P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st)); }
         RC(launch_bn_fwd_finalize(l, W, B, ws + w.bnpart[l], P_(h->enc_g[l]), P_(h->enc_be[l]), bn_state + kBnOff[l],
@@ -490,18 +485,17 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
     for (int l = 3; l >= 0; --l) {
         if (!(phase_mask & (l == 3 ? 2 : 4))) continue;
         // block 0: only the statistics pass runs here; E1's weight-gradient kernel applies the BatchNorm/pool/ReLU
-        // backward while it stages its tiles (d_y[0] is never written: nothing else would read it)
-        const bool fuse0 = l == 0 && h->fuse_e1;
+        // backward while it stages its tiles (there is no d_y[0]: nothing else would read it)
         { ProbeArm pa(h, 3, l);
           RC(launch_bn_pool_act_bwd(l, W, B, ws + w.y[l], ws + w.a[l], ws + w.d_a[l], ws + w.coef[l], P_(h->enc_g[l]),
-                                    fuse0 ? nullptr : ws + w.d_y[l], G_(h->enc_g[l]), G_(h->enc_be[l]), nullptr, sc, st, io_bf16(h))); }
+                                    l == 0 ? nullptr : ws + w.d_y[l], G_(h->enc_g[l]), G_(h->enc_be[l]), nullptr, sc, st, io_bf16(h))); }
         RC(fork(7 - l));
         if (l == 0) {
             const float* fu[7] = {ws + w.y[0], ws + w.a[0], ws + w.d_a[0], ws + w.coef[0], bn_bwd_bcoef(0, W, B, sc),
                                   P_(h->enc_w[0]), P_(h->enc_b[0])};
             { ProbeArm pa(h, 2, 0);
-              RC(launch_e1_wgrad(W, B, x, fuse0 ? nullptr : ws + w.d_y[0], G_(h->enc_w[0]), G_(h->enc_b[0]), scw, sd, h->cfg.precision == 1, fuse0 ? fu : nullptr,
-                                 (h->e1_two_pass && fuse0 && h->xp_ws == (const void*)ws && h->xp_B == B &&
+              RC(launch_e1_wgrad(W, B, x, nullptr, G_(h->enc_w[0]), G_(h->enc_b[0]), scw, sd, h->cfg.precision == 1, fu,
+                                 (h->cfg.precision == 1 && h->xp_ws == (const void*)ws && h->xp_B == B &&
                                   conv_route(1, 0, W, false, B).family == E1_PACKED_FRAME) ? ws + w.xp : nullptr)); }
         } else {
             { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, l, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd)); }

@@ -127,9 +127,8 @@ __global__ __launch_bounds__(256, THIN_F32_OCC) void e1_fwd_kernel(const float* 
 //              would compute from a stored y1, scale/shift -> first maximum of each 2x2 window in scan order -> ReLU -> a1.
 //              y1 ITSELF IS NOT WRITTEN (round 3): the only reader left in the step, E1's weight-gradient kernel, runs the
 //              75-tap conv a third time on the tile it stages (e1_wgrad_bf16_kernel<H, true>) — B*H*H*32*2 bytes less
-//              written here and read there (1.07 GB per step at B = 2048).  Exceptions: keepY != 0 (the CVAE_FUSE_E1=0
-//              A/B path, whose separate apply pass reads y1), and steps in which a channel has |gamma| < 1e-2: the
-//              BatchNorm-backward statistics kernel then takes xhat of that channel from y1 (bn.hip).
+//              written here and read there (1.07 GB per step at B = 2048).  Exception: steps in which a channel has
+//              |gamma| < 1e-2: the BatchNorm-backward statistics kernel then takes xhat of that channel from y1 (bn.hip).
 // K-packed form of the 75-tap contraction (round 3).  The staged strip holds bf16 pixels of 4 channels (r, g, b, 0), so the
 // four channels of one tap are one 8-byte LDS unit and an MFMA's K = 16 is FOUR taps (two per lane half): 25 taps -> 7
 // MFMAs (the kernel-row form padded each row's 5 taps to 8: 10 MFMAs).  Tap assignment — chosen so that lane half 1 reads
@@ -175,7 +174,7 @@ __global__ __launch_bounds__(256, PASS == 1 ? 3 : 2) void e1_fwd_bf16_kernel(   
                                                          const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ y,
                                                           float* __restrict__ bnpart, int B,
-                                                          const float* __restrict__ coef, float* __restrict__ a1, int numStrips, int keepY,
+                                                          const float* __restrict__ coef, float* __restrict__ a1, int numStrips,
                                                           bf16x4* __restrict__ xp) {
     // xp (round 5): the frame as packed bf16 pixels (r, g, b, 0) = the LDS unit of this kernel, 8 bytes per pixel, in the workspace.  The
     // statistics pass writes it from the strip it stages anyway (interior pixels: one 8-byte store per pixel and step); the pool pass and
@@ -197,7 +196,9 @@ __global__ __launch_bounds__(256, PASS == 1 ? 3 : 2) void e1_fwd_bf16_kernel(   
     bool wr_y = PASS != E1_STATS;
     if constexpr (POOL) {
         const float gam = coef[li * 4] / coef[li * 4 + 3];             // gamma = scale / invstd, as bn.hip's backward tests it
-        wr_y = keepY != 0 || __any(!(fabsf(gam) >= 1e-2f));           // the same answer in every wave (a wave spans all 32 channels)
+        // the same answer in every wave (a wave spans all 32 channels); as a scalar (readfirstlane) the compiler keeps the
+        // no-store path of the y1 loop below straight-line
+        wr_y = __builtin_amdgcn_readfirstlane(__any(!(fabsf(gam) >= 1e-2f))) != 0;
     }
     constexpr int NIT = (HR_ * HWX + 255) / 256;
     float v0[NIT], v1[NIT], v2[NIT];
@@ -551,8 +552,8 @@ __global__ __launch_bounds__(256, THIN_F32_OCC) void e1_wgrad_kernel(ThinWgradAr
 // registers instead of 64).  Wave w owns tile row w (32 pixels, 2 k-steps): 8 MFMAs per tile.
 // Slab row of a workgroup: [128 m'][32 co]; m' = 100 is the bias row (101..103 repeat it, 104.. are zero).
 static constexpr int E1W_ROW = 128 * 32;
-// FUSE (see E1Fuse): dy of block 0 is produced HERE from x, a0 and d_a0 alone — y1 is not read, it is not even stored by
-// the forward any more.  Per tile (4 rows x 32 columns):
+// dy of block 0 is produced HERE from x, a0 and d_a0 alone (the BatchNorm/pool/ReLU backward of E1Fuse) — y1 is not read, it
+// is not even stored by the forward any more.  Per tile (4 rows x 32 columns):
 //   1. each wave runs the forward's 75-tap conv (e1_wk_conv: the forward's operand fragments and accumulation order, so
 //      the fp32 sums, hence the bf16-rounded y values and the window argmax, are the forward's to the bit) on its 2-row x
 //      16-column quadrant: accumulator element v of lane (li, lh) is channel li of quadrant pixel m = (v&3) + 8(v>>2) + 4lh
@@ -565,17 +566,16 @@ static constexpr int E1W_ROW = 128 * 32;
 //      8ks .. 8ks+7 of every lane ARE its B fragment of k-step ks (quadrant row ks), and the transposed reads of the A operand
 //      fetch the pixels in that order (an earlier form stored dy to LDS channel-major and read it back behind a third barrier).
 constexpr int E1W_OCC = 3;          // workgroups per CU of the bf16 E1 weight-gradient kernel (VGPR budget 512 / (E1W_OCC) per lane; splits = E1W_OCC * CUs)
-template <int H, bool FUSE, bool XP>          // XP: the strip comes from the packed bf16 frame the forward's statistics pass left in the workspace (a.xp)
+template <int H, bool XP>          // XP: the strip comes from the packed bf16 frame the forward's statistics pass left in the workspace (a.xp)
 __global__ __launch_bounds__(256, E1W_OCC) void e1_wgrad_bf16_kernel(ThinWgradArgs a, E1Fuse fu) {
     using T = Tile<H>;
     static_assert(T::TW == 32 && T::TH == 4 && T::IMGS == 1, "one tile row per wave");
     constexpr int HWX = 40, HR_ = T::TH + 4, NPXH = HR_ * HWX, U_ONES = NPXH + 8, U_ZERO = NPXH + 9;
     __shared__ __attribute__((aligned(16))) bf16x4 lds_x[NPXH + 10];          // strip | 8 over-read pad units | ones | zeros
-    __shared__ __attribute__((aligned(16))) __bf16 lds_d[FUSE ? 8 : 128 * 32];               // !FUSE: dy tile [px][32] (FUSE: dy never leaves registers)
-    __shared__ __attribute__((aligned(16))) __bf16 lds_p[FUSE ? 2 * 32 * 32 : 8];             // FUSE: a0 | d_a0 tiles [pooled px][32]
+    __shared__ __attribute__((aligned(16))) __bf16 lds_p[2 * 32 * 32];             // a0 | d_a0 tiles [pooled px][32] (dy never leaves registers)
     __shared__ float red[3 * 1024];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int g = lane >> 4, h = g >> 1, qrow = (lane & 15) >> 2, cb = 16 * (g & 1) + 4 * (lane & 3);
+    const int g = lane >> 4, h = g >> 1, qrow = (lane & 15) >> 2;
     f32x16 acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -606,18 +606,15 @@ __global__ __launch_bounds__(256, E1W_OCC) void e1_wgrad_bf16_kernel(ThinWgradAr
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t rs_xp =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(a.xp)) - XP_BIAS, 0, (int)((size_t)a.B * H * H * 8 + XP_BIAS), 0x00020000);
     unsigned okm = 0u;                               // validity bit per staged strip unit
-    bf16x8 rd[2];
-    bf16x8 rp;                                       // FUSE: 8 channels of one pooled pixel of a0 (threads 0..127) / d_a0 (128..255)
-    bf16x8 bw[7];                                    // FUSE: the forward's K-packed B fragments
-    float bv = 0.f, bsc = 0.f, bsh = 0.f, bA = 0.f, bB = 0.f;         // this lane's channel li
-    if constexpr (FUSE) {
-        e1_wk_load(fu.w, li, lh, bw);
-        bv = fu.bias[li];
-        const float sc = fu.coef[li * 4], mean = fu.coef[li * 4 + 2], invstd = fu.coef[li * 4 + 3];
-        bsc = sc; bsh = fu.coef[li * 4 + 1];
-        bB = sc * fu.bcoef[li * 2 + 1] * invstd;
-        bA = sc * fu.bcoef[li * 2] - bB * mean;
-    }
+    bf16x8 rp;                                       // 8 channels of one pooled pixel of a0 (threads 0..127) / d_a0 (128..255)
+    bf16x8 bw[7];                                    // the forward's K-packed B fragments
+    e1_wk_load(fu.w, li, lh, bw);
+    // this lane's channel li
+    const float bv = fu.bias[li];
+    const float bsc = fu.coef[li * 4], mean = fu.coef[li * 4 + 2], invstd = fu.coef[li * 4 + 3];
+    const float bsh = fu.coef[li * 4 + 1];
+    const float bB = bsc * fu.bcoef[li * 2 + 1] * invstd;
+    const float bA = bsc * fu.bcoef[li * 2] - bB * mean;
     auto fetch = [&](int mt) {
         const int ib = mt / T::TILES_PER_IMG, tileInImg = mt % T::TILES_PER_IMG;
         const int ty0 = (tileInImg / T::TILES_X) * T::TH, tx0 = (tileInImg % T::TILES_X) * T::TW;
@@ -641,18 +638,9 @@ __global__ __launch_bounds__(256, E1W_OCC) void e1_wgrad_bf16_kernel(ThinWgradAr
             okm = ok ? (okm | (1u << i)) : (okm & ~(1u << i));
         }
         }
-        if constexpr (FUSE) {
-            const int t = tid & 127, pp = t >> 2, c8 = t & 3;            // pooled pixel pp = prow*16 + pcol of the tile's 2 x 16
-            const size_t pe = ((size_t)(ib * (H / 2) + ty0 / 2 + (pp >> 4)) * (H / 2) + tx0 / 2 + (pp & 15)) * 32 + c8 * 8;
-            rp = Act<__bf16>::ld8(tid < 128 ? fu.a : fu.da, pe);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int q = tid + i * 256, c8 = q & 3, mm = q >> 2;
-                const int gy = ty0 + mm / T::TW, gx = tx0 + mm % T::TW;
-                rd[i] = Act<__bf16>::ld8(a.a1, ((size_t)(ib * H + gy) * H + gx) * 32 + c8 * 8);
-            }
-        }
+        const int t = tid & 127, pp = t >> 2, c8 = t & 3;                // pooled pixel pp = prow*16 + pcol of the tile's 2 x 16
+        const size_t pe = ((size_t)(ib * (H / 2) + ty0 / 2 + (pp >> 4)) * (H / 2) + tx0 / 2 + (pp & 15)) * 32 + c8 * 8;
+        rp = Act<__bf16>::ld8(tid < 128 ? fu.a : fu.da, pe);
     };
     if (t0 < t1) fetch(t0);
     const __bf16* xs = reinterpret_cast<const __bf16*>(lds_x);
@@ -668,72 +656,52 @@ __global__ __launch_bounds__(256, E1W_OCC) void e1_wgrad_bf16_kernel(ThinWgradAr
                 if (q < NPXH) { bf16x4 u; u[0] = (__bf16)(ok ? rx[i][0] : 0.f); u[1] = (__bf16)(ok ? rx[i][1] : 0.f); u[2] = (__bf16)(ok ? rx[i][2] : 0.f); u[3] = (__bf16)0.f; lds_x[q] = u; }
             }
         }
-        if constexpr (FUSE) {
-            *reinterpret_cast<bf16x8*>(lds_p + (size_t)tid * 8) = rp;       // [a0 | d_a0][pp][32]: thread order IS the layout
-        } else {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) *reinterpret_cast<bf16x8*>(lds_d + (size_t)(tid + i * 256) * 8) = rd[i];
-        }
+        *reinterpret_cast<bf16x8*>(lds_p + (size_t)tid * 8) = rp;           // [a0 | d_a0][pp][32]: thread order IS the layout
         __syncthreads();
         if (mt + 1 < t1) fetch(mt + 1);
-        if constexpr (FUSE) {
-            // 1. the forward conv of this wave's quadrant: rows 2(wave>>1) + (li>>4), columns 16(wave&1) + (li&15)
-            const int qr = 2 * (wave >> 1), qc = 16 * (wave & 1);
-            const f32x16 cacc = e1_wk_conv<HWX>(lds_x + (qr + (li >> 4)) * HWX + qc + (li & 15), lh, bw);
-            // 2. BatchNorm / pool / ReLU backward of the lane's four windows (quadrant columns 4lh + {0,2,8,10}), channel li;
-            //    the two columns of a window row travel as one packed pair
-            const f32x2t bv2 = {bv, bv}, sc2 = {bsc, bsc}, sh2 = {bsh, bsh}, bA2 = {bA, bA}, bB2 = {bB, bB};
-            bf16x8 dyf[2];                           // [quadrant row = k-step]: dy of accumulator elements 8ks .. 8ks+7
-            // dy of the quadrant goes straight into the weight-gradient MFMA as its B operand (k = pixel, n = channel li): the
-            // contraction order over pixels is free, so k-step ks takes accumulator elements 8ks .. 8ks+7 of every lane as they
-            // are — lane half lh, element jj = quadrant row ks, column 4lh + (jj&3) + 8(jj>>2) — and the transposed reads of
-            // the A operand below fetch the pixels in that same order.  (Round 3 first wrote dy to LDS channel-major and read
-            // it back behind a third barrier.)
+        // 1. the forward conv of this wave's quadrant: rows 2(wave>>1) + (li>>4), columns 16(wave&1) + (li&15)
+        const int qr = 2 * (wave >> 1), qc = 16 * (wave & 1);
+        const f32x16 cacc = e1_wk_conv<HWX>(lds_x + (qr + (li >> 4)) * HWX + qc + (li & 15), lh, bw);
+        // 2. BatchNorm / pool / ReLU backward of the lane's four windows (quadrant columns 4lh + {0,2,8,10}), channel li;
+        //    the two columns of a window row travel as one packed pair
+        const f32x2t bv2 = {bv, bv}, sc2 = {bsc, bsc}, sh2 = {bsh, bsh}, bA2 = {bA, bA}, bB2 = {bB, bB};
+        bf16x8 dyf[2];                           // [quadrant row = k-step]: dy of accumulator elements 8ks .. 8ks+7
+        // dy of the quadrant goes straight into the weight-gradient MFMA as its B operand (k = pixel, n = channel li): the
+        // contraction order over pixels is free, so k-step ks takes accumulator elements 8ks .. 8ks+7 of every lane as they
+        // are — lane half lh, element jj = quadrant row ks, column 4lh + (jj&3) + 8(jj>>2) — and the transposed reads of
+        // the A operand below fetch the pixels in that same order.  (Round 3 first wrote dy to LDS channel-major and read
+        // it back behind a third barrier.)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int v = 2 * j, m0 = (v & 3) + 8 * (v >> 2) + 4 * lh;          // first column of the window
-                const int pp = (wave >> 1) * 16 + 8 * (wave & 1) + (m0 >> 1);
-                const float av = (float)lds_p[pp * 32 + li], gv = (float)lds_p[1024 + pp * 32 + li];
-                // the values the forward pooled: bf16(acc + bias), rows 0 / 1 of the window
-                const f32x2t s0 = f32x2t{cacc[v], cacc[v + 1]} + bv2, s1 = f32x2t{cacc[v + 8], cacc[v + 9]} + bv2;
-                const f32x2t y0 = {(float)(__bf16)s0.x, (float)(__bf16)s0.y}, y1 = {(float)(__bf16)s1.x, (float)(__bf16)s1.y};
-                const f32x2t n0 = __builtin_elementwise_fma(y0, sc2, sh2), n1 = __builtin_elementwise_fma(y1, sc2, sh2);
-                // first maximum in scan order (0, 1 | 2, 3): tournament with strict comparisons = the forward's sequential scan
-                const bool c01 = n0.y > n0.x, c23 = n1.y > n1.x;
-                const float m01 = c01 ? n0.y : n0.x, m23 = c23 ? n1.y : n1.x;
-                const bool hi = m23 > m01;
-                const float gs = av > 0.f ? gv * bsc : 0.f;
-                const f32x2t t0v = __builtin_elementwise_fma(bB2, y0, bA2), t1v = __builtin_elementwise_fma(bB2, y1, bA2);
-                const f32x2t sel0 = {(!hi && !c01) ? gs : 0.f, (!hi && c01) ? gs : 0.f};
-                const f32x2t sel1 = {(hi && !c23) ? gs : 0.f, (hi && c23) ? gs : 0.f};
-                const f32x2t d0 = sel0 - t0v, d1 = sel1 - t1v;
-                dyf[0][v] = (__bf16)d0.x; dyf[0][v + 1] = (__bf16)d0.y;          // elements v, v+1 (row 0) and v+8, v+9 (row 1)
-                dyf[1][v] = (__bf16)d1.x; dyf[1][v + 1] = (__bf16)d1.y;
-            }
-            // 3. weight gradient over the quadrant: k-step ks = quadrant row ks; transposed-read lane address: pixel column
-            //    4h + qrow for read 0, +8 for read 1 (K index 8h + 4*read + qrow <-> column 4h + qrow + 8*read, as dyf)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const __bf16* pb = xs + ((qr + ks) * HWX + qc + 4 * h + qrow) * 4;       // this lane's pixel in the strip (tap (0,0))
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const __bf16* ap = mconst[b] ? xs + moff[b] : pb + moff[b];
-                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(ap, mconst[b] ? ap : ap + 32), dyf[ks], acc[b], 0, 0, 0);
-                }
-            }
-        } else {
+        for (int j = 0; j < 4; ++j) {
+            const int v = 2 * j, m0 = (v & 3) + 8 * (v >> 2) + 4 * lh;          // first column of the window
+            const int pp = (wave >> 1) * 16 + 8 * (wave & 1) + (m0 >> 1);
+            const float av = (float)lds_p[pp * 32 + li], gv = (float)lds_p[1024 + pp * 32 + li];
+            // the values the forward pooled: bf16(acc + bias), rows 0 / 1 of the window
+            const f32x2t s0 = f32x2t{cacc[v], cacc[v + 1]} + bv2, s1 = f32x2t{cacc[v + 8], cacc[v + 9]} + bv2;
+            const f32x2t y0 = {(float)(__bf16)s0.x, (float)(__bf16)s0.y}, y1 = {(float)(__bf16)s1.x, (float)(__bf16)s1.y};
+            const f32x2t n0 = __builtin_elementwise_fma(y0, sc2, sh2), n1 = __builtin_elementwise_fma(y1, sc2, sh2);
+            // first maximum in scan order (0, 1 | 2, 3): tournament with strict comparisons = the forward's sequential scan
+            const bool c01 = n0.y > n0.x, c23 = n1.y > n1.x;
+            const float m01 = c01 ? n0.y : n0.x, m23 = c23 ? n1.y : n1.x;
+            const bool hi = m23 > m01;
+            const float gs = av > 0.f ? gv * bsc : 0.f;
+            const f32x2t t0v = __builtin_elementwise_fma(bB2, y0, bA2), t1v = __builtin_elementwise_fma(bB2, y1, bA2);
+            const f32x2t sel0 = {(!hi && !c01) ? gs : 0.f, (!hi && c01) ? gs : 0.f};
+            const f32x2t sel1 = {(hi && !c23) ? gs : 0.f, (hi && c23) ? gs : 0.f};
+            const f32x2t d0 = sel0 - t0v, d1 = sel1 - t1v;
+            dyf[0][v] = (__bf16)d0.x; dyf[0][v + 1] = (__bf16)d0.y;          // elements v, v+1 (row 0) and v+8, v+9 (row 1)
+            dyf[1][v] = (__bf16)d1.x; dyf[1][v + 1] = (__bf16)d1.y;
+        }
+        // 3. weight gradient over the quadrant: k-step ks = quadrant row ks; transposed-read lane address: pixel column
+        //    4h + qrow for read 0, +8 for read 1 (K index 8h + 4*read + qrow <-> column 4h + qrow + 8*read, as dyf)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const int px = 16 * ks + 8 * h + qrow;                       // this lane's block row (pixel) for read 0; read 1: +4
-            const __bf16* dp = lds_d + (wave * 32 + px) * 32 + cb;
-            const bf16x8 bvv = tr_frag(dp, dp + 4 * 32);
-            const __bf16* pb = xs + (wave * HWX + px) * 4;               // this lane's pixel in the strip (tap (0,0))
+            const __bf16* pb = xs + ((qr + ks) * HWX + qc + 4 * h + qrow) * 4;       // this lane's pixel in the strip (tap (0,0))
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const __bf16* ap = mconst[b] ? xs + moff[b] : pb + moff[b];
-                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(ap, mconst[b] ? ap : ap + 16), bvv, acc[b], 0, 0, 0);
+                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(ap, mconst[b] ? ap : ap + 32), dyf[ks], acc[b], 0, 0, 0);
             }
-        }
         }
     }
     // every wave contracted its own tile rows: fixed-order sum over the 4 waves, one accumulator at a time
@@ -822,9 +790,8 @@ int64_t e1_wgrad_ws_floats(int width, int B) {
 }
 
 int launch_e1_fwd(int width, int B, const float* x, const float* w, const float* bias, float* y,
-                  float* bnpart, hipStream_t st, bool bf16, int pass, const float* coef, float* a1, bool keep_y, float* xpf) {
+                  float* bnpart, hipStream_t st, bool bf16, int pass, const float* coef, float* a1, float* xpf) {
     bf16x4* xp = reinterpret_cast<bf16x4*>(xpf);          // packed bf16 frame (workspace): written by pass 1, read by pass 2; null: pass 2 is not available
-    const int keepY = keep_y ? 1 : 0;
     if (pass != 0 && !bf16) { cvae_set_error("e1_fwd: passes 1/2 exist in bf16 mode only"); return -2; }
     if (pass < 0 || pass > 2) { cvae_set_error("e1_fwd: pass %d", pass); return -2; }
     if (pass == 2 && !xp) pass = 3;                       // no packed frame (eval mode, or a frame of 2 GiB and more): the pool pass stages from the fp32 frame
@@ -834,14 +801,14 @@ int launch_e1_fwd(int width, int B, const float* x, const float* w, const float*
     const int ns64 = B * 8, ns128 = B * 32, cap = cvae_num_cus() * 3;      // persistent: 3 workgroups per CU (<= 168 VGPRs), one strip each per turn
     const dim3 g64(ns64 < cap ? ns64 : cap), g128(ns128 < cap ? ns128 : cap);
     cvae_probe_begin(st);
-    if (width == 64 && bf16 && pass == 1) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_STATS>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, keepY, xp);
-    else if (width == 64 && bf16 && pass == 2) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_POOL>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, keepY, xp);
-    else if (width == 128 && bf16 && pass == 1) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_STATS>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, keepY, xp);
-    else if (width == 128 && bf16 && pass == 2) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_POOL>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, keepY, xp);
-    else if (width == 64 && bf16 && pass == 3) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_POOL_X>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, keepY, xp);
-    else if (width == 128 && bf16 && pass == 3) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_POOL_X>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, keepY, xp);
-    else if (width == 64 && bf16) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_Y>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, keepY, xp);
-    else if (width == 128 && bf16) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_Y>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, keepY, xp);
+    if (width == 64 && bf16 && pass == 1) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_STATS>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, xp);
+    else if (width == 64 && bf16 && pass == 2) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_POOL>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, xp);
+    else if (width == 128 && bf16 && pass == 1) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_STATS>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, xp);
+    else if (width == 128 && bf16 && pass == 2) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_POOL>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, xp);
+    else if (width == 64 && bf16 && pass == 3) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_POOL_X>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, xp);
+    else if (width == 128 && bf16 && pass == 3) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_POOL_X>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, xp);
+    else if (width == 64 && bf16) hipLaunchKernelGGL((e1_fwd_bf16_kernel<64, E1_Y>), g64, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns64, xp);
+    else if (width == 128 && bf16) hipLaunchKernelGGL((e1_fwd_bf16_kernel<128, E1_Y>), g128, dim3(256), 0, st, x, w, bias, y, bnpart, xpB, coef, a1, ns128, xp);
     else if (width == 64) hipLaunchKernelGGL(e1_fwd_kernel<64>, dim3(B * 8), dim3(256), 0, st, x, w, bias, y, bnpart, B);
     else if (width == 128) hipLaunchKernelGGL(e1_fwd_kernel<128>, dim3(B * 32), dim3(256), 0, st, x, w, bias, y, bnpart, B);
     else { cvae_set_error("e1_fwd: width %d unsupported", width); return -2; }
@@ -858,15 +825,14 @@ int launch_e1_wgrad(int width, int B, const float* x, const float* dy, float* dw
     ThinWgradArgs a{x, nullptr, dy, nullptr, nullptr, ws, B, tiles, tps, xp};
     // fuse = {y0, a0, d_a0, coef0, bcoef0, w1, b1}: block 0's BatchNorm/pool/ReLU backward is applied while staging (no dy
     // tensor); the bf16 kernel recomputes y0 from x, w1, b1 and never reads fuse[0]
+    if (bf16 && !fuse) { cvae_set_error("e1_wgrad: the bf16 kernel exists in the fused form only (fuse is null)"); return -2; }
     const E1Fuse fu = fuse ? E1Fuse{fuse[0], fuse[1], fuse[2], fuse[3], fuse[4], fuse[5], fuse[6]} : E1Fuse{};
     cvae_probe_begin(st);
     if (bf16) {          // precision mode 1: transposed-read kernel, its own slab layout + a permuting finish
-        if (width == 64 && fuse && xp) hipLaunchKernelGGL((e1_wgrad_bf16_kernel<64, true, true>), dim3(S), dim3(256), 0, st, a, fu);
-        else if (width == 64 && fuse) hipLaunchKernelGGL((e1_wgrad_bf16_kernel<64, true, false>), dim3(S), dim3(256), 0, st, a, fu);
-        else if (width == 64) hipLaunchKernelGGL((e1_wgrad_bf16_kernel<64, false, false>), dim3(S), dim3(256), 0, st, a, fu);
-        else if (fuse && xp) hipLaunchKernelGGL((e1_wgrad_bf16_kernel<128, true, true>), dim3(S), dim3(256), 0, st, a, fu);
-        else if (fuse) hipLaunchKernelGGL((e1_wgrad_bf16_kernel<128, true, false>), dim3(S), dim3(256), 0, st, a, fu);
-        else hipLaunchKernelGGL((e1_wgrad_bf16_kernel<128, false, false>), dim3(S), dim3(256), 0, st, a, fu);
+        if (width == 64 && xp) hipLaunchKernelGGL((e1_wgrad_bf16_kernel<64, true>), dim3(S), dim3(256), 0, st, a, fu);
+        else if (width == 64) hipLaunchKernelGGL((e1_wgrad_bf16_kernel<64, false>), dim3(S), dim3(256), 0, st, a, fu);
+        else if (xp) hipLaunchKernelGGL((e1_wgrad_bf16_kernel<128, true>), dim3(S), dim3(256), 0, st, a, fu);
+        else hipLaunchKernelGGL((e1_wgrad_bf16_kernel<128, false>), dim3(S), dim3(256), 0, st, a, fu);
         cvae_probe_end(st);
         CVAE_CHECK_LAUNCH();
         float* red = ws + (size_t)S * E1W_ROW;

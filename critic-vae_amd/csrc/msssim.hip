@@ -13,7 +13,7 @@
 // Structure (round 2): the loss is L = 1 - prod(mean_l ^ w_l), so dL/dx_l = coef_l * F_l with
 //   F_l = win * u_mu + 2 x (win * u_11) + y (win * u_12),   u_* = d map_l / d (mu1, E[x^2], E[xy])
 // where only the scalar coef_l depends on the global means.  ONE forward kernel per level computes the five
-// filtered maps on the tile EXTENDED by the window radius, the SSIM/CS partial sums on the tile itself, the
+// filtered maps on the whole plane (streamed in bands at 128 wide), the SSIM/CS partial sums, the
 // three derivative maps in LDS (never in HBM), filters them again and stores the single field F_l plus the
 // 2x2 average for the next level.  Levels 16/8/4 run in one launch (one workgroup per plane, everything in
 // LDS).  The finalize runs on 32 workgroups; the last one to arrive (release/acquire ticket) merges their
@@ -22,7 +22,6 @@
 // HBM traffic: forward reads x, y once and writes F (+ 1/4-size pyramids); backward reads the F pyramid and
 // writes dx — 1.2x the algorithmic bytes (was 3.2x / 2.5x with the derivative maps stored).
 #include "common.h"
-#include <stdlib.h>
 #include <math.h>
 
 // The 11 normalised taps travel BY VALUE in every kernel's argument struct (scalar registers): no
@@ -38,15 +37,12 @@ static MsWin make_window() {
 }
 
 static constexpr int MS_NF = 32;            // finalize workgroups
-static constexpr int MS_NT = 768;           // threads of a tile workgroup: two workgroups per CU (80 KB of LDS each) = 6 waves per SIMD at <= 80 VGPRs;
-                                            // 768 runs the first horizontal pass (684 items at S = 64) in one round: 371 us against 392 (512) / 366 (1024) at B = 2048
-static constexpr int MS_VR = 2;             // output rows per item of the vertical passes (VR + 10 staged rows are read per item)
 
 // ------------------------------------------------------------------------------------------------
-// large levels (S = 128, 64, 32): one workgroup per (plane, RS x CS tile)
+// shared by the forward kernels: packed fp32, the argument struct, the SSIM point function, segment sums
 // ------------------------------------------------------------------------------------------------
 // Round 3: the four filter passes run on PACKED fp32 (v_pk_fma_f32 / v_pk_mul_f32: two lanes of arithmetic per VALU
-// issue — the kernel is VALU-bound, one wave64 VALU instruction holds its SIMD for 4 cycles).  What is packed is chosen
+// issue — the kernels are VALU-bound, one wave64 VALU instruction holds its SIMD for 4 cycles).  What is packed is chosen
 // so that every operand pair is already adjacent in registers AND in LDS, i.e. no v_mov shuffles:
 //   horizontal passes pair two PLANES of one pixel — the staged image interleaves (x, y) per pixel, so (x, y) -> (hx, hy)
 //     and (x^2, y^2) -> (hxx, hyy) are one packed chain each (xy -> hxy stays scalar); the derivative maps are kept as
@@ -57,29 +53,6 @@ static constexpr int MS_VR = 2;             // output rows per item of the verti
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 splat2(float v) { return f32x2{v, v}; }
-
-template <int S>
-struct MsT {
-    static constexpr int CS = S < 64 ? S : 64;             // tile columns
-    static constexpr int RS = S == 32 ? 32 : 16;           // tile rows (the 64- and 128-wide levels at 32: one workgroup per CU, 117 KB of LDS)
-    static constexpr int TX = S / CS, TY = S / RS, TILES = TX * TY;
-    static constexpr int ER = RS + 20;                      // input rows staged (tile + 2 window radii)
-    static constexpr int MR = RS + 10, MC = CS + 10;        // map region (tile + 1 window radius)
-    static constexpr int MCP = ((MC + 3) / 4) * 4;          // map row stride (4 outputs per H item)
-    static constexpr int ECP = MCP + 14;                    // input row stride: the last H item reads 14 columns; ECP / 2 is ODD
-    static constexpr int DAS = MCP + 2;                     // row stride of the (d_mu, d_11) image; DAS / 2 is ODD
-    // (an item of a horizontal pass reads 16-byte units 32 bytes apart from its neighbour's: with an odd row stride in
-    //  16-byte units, lanes that alternate between two rows cover all 16 slots of the 256-byte bank row: conflict-free)
-    static constexpr int LIN_IN = 2 * ER * ECP, LIN_D = 2 * MR * DAS + MR * MCP;
-    static constexpr int LIN = LIN_IN > LIN_D ? LIN_IN : LIN_D;   // floats: (x, y) pixels [ER][ECP]; later (d_mu, d_11) [MR][DAS] | d_12 [MR][MCP]
-    static constexpr int TMP = 5 * ER * MCP + 2 * MCP;      // floats: (hx, hy) | (hxx, hyy) | hxy, each [ER][MCP] (+2 rows: the last 4-row
-                                                            // group of the vertical pass reads past row ER-1); later (g0, g1) | g2, each [MR][CS]
-    static constexpr int SMEM = (LIN + TMP) * 4;
-    static_assert(2 * MR * DAS + MR * MCP <= LIN, "derivative maps must fit in the input halo buffer");
-    static_assert((ECP / 2) % 2 == 1 && (DAS / 2) % 2 == 1 && ER % 2 == 0 && MR % 2 == 0, "odd unit strides, even row counts");
-    static_assert(3 * MR * CS <= TMP, "row-filtered derivative maps must fit in the tmp buffer");
-    static_assert(MC % 2 == 0 && MR % 2 == 0, "2x2 blocking of the vertical passes");
-};
 
 struct MsFwdArgs {
     const float* x;       // img1 at this level (carries grad)
@@ -142,273 +115,15 @@ __device__ __forceinline__ float seg_sum_dpp(float v) {
     return v;
 }
 
-template <int S>
-__global__ __launch_bounds__(MS_NT, MS_NT / 128) void msssim_fwd_kernel(MsFwdArgs a) {
-    using T = MsT<S>;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float red[2 * (MS_NT / 64)];
-    float* lin = smem;                 // (x, y) pixels [ER][ECP][2]
-    float* tmp = smem + T::LIN;        // tmpA (hx, hy) [ER][MCP][2] | tmpB (hxx, hyy) [ER][MCP][2] | tmpC hxy [ER][MCP]
-    const int blk = xcd_tile(blockIdx.x, gridDim.x);
-    const int plane = blk / T::TILES, tile = blk % T::TILES;
-    const int r0 = (tile / T::TX) * T::RS, c0 = (tile % T::TX) * T::CS;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && a.ticket) *a.ticket = 0u;
-    float w[11];
-#pragma unroll
-    for (int t = 0; t < 11; ++t) w[t] = a.win.w[t];
-    // ---- stage the zero-padded input halos, (x, y) interleaved per pixel: image rows r0-10 .. r0+RS+9, columns c0-10 ..
-    //      (two pixels = one 16-byte LDS unit).  All global loads are issued before the first LDS write ----
-    {
-        constexpr int U = T::ECP / 2, NIT = (T::ER * U + MS_NT - 1) / MS_NT;
-        const float* px = a.x + (size_t)plane * S * S;
-        const float* py = a.y + (size_t)plane * S * S;
-        float2 vx[NIT], vy[NIT];
-#pragma unroll
-        for (int k = 0; k < NIT; ++k) {
-            const int q = threadIdx.x + k * MS_NT;
-            const int er = q / U, ec = (q % U) * 2;
-            const int gr = r0 - 10 + er, gc = c0 - 10 + ec;
-            // unconditional loads from a clamped address + select (a branch per element would serialise the loads)
-            const bool ok = q < T::ER * U && (unsigned)gr < (unsigned)S && (unsigned)gc < (unsigned)S && ec < T::MC + 10;
-            const int ga = ok ? gr * S + gc : 0;
-            const float2 lx = *reinterpret_cast<const float2*>(px + ga);
-            const float2 ly = *reinterpret_cast<const float2*>(py + ga);
-            vx[k] = ok ? lx : make_float2(0.f, 0.f);
-            vy[k] = ok ? ly : make_float2(0.f, 0.f);
-        }
-#pragma unroll
-        for (int k = 0; k < NIT; ++k) {
-            const int q = threadIdx.x + k * MS_NT;
-            if (q < T::ER * U) {
-                const int er = q / U, ec = (q % U) * 2;
-                *reinterpret_cast<f32x4*>(lin + (er * T::ECP + ec) * 2) = f32x4{vx[k].x, vy[k].x, vx[k].y, vy[k].y};
-            }
-        }
-    }
-    __syncthreads();
-    // ---- 2x2 average for the next level (avg_pool2d, vae_nets.py:232-233) ----
-    {
-        constexpr int SO = S / 2, PR = T::RS / 2, PC = T::CS / 2;
-        for (int q = threadIdx.x; q < PR * PC; q += MS_NT) {
-            const int pr = q / PC, pc = q % PC;
-            const f32x4 u = *reinterpret_cast<const f32x4*>(lin + ((10 + 2 * pr) * T::ECP + 10 + 2 * pc) * 2);      // (x0, y0, x1, y1)
-            const f32x4 d = *reinterpret_cast<const f32x4*>(lin + ((11 + 2 * pr) * T::ECP + 10 + 2 * pc) * 2);
-            const size_t o = ((size_t)plane * SO + r0 / 2 + pr) * SO + c0 / 2 + pc;
-            a.nx[o] = ((u[0] + u[2]) + (d[0] + d[2])) * 0.25f;
-            a.ny[o] = ((u[1] + u[3]) + (d[1] + d[3])) * 0.25f;
-        }
-    }
-    // ---- horizontal pass of {x, y, x^2, y^2, xy}: 4 adjacent outputs per item from a 14-wide register window ----
-    {
-        constexpr int J = T::MCP / 4, PT = T::ER * T::MCP;
-        float* tA = tmp; float* tB = tmp + 2 * PT; float* tC = tmp + 4 * PT;
-        for (int it = threadIdx.x; it < T::ER * J; it += MS_NT) {
-            const int r = 2 * (it / (2 * J)) + (it & 1), c = ((it % (2 * J)) >> 1) * 4;      // neighbouring lanes: the two rows of a pair
-            const float* p = lin + (r * T::ECP + c) * 2;
-            f32x2 xy[14];                      // (x, y) of the 14 window pixels
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                const f32x4 u = *reinterpret_cast<const f32x4*>(p + 4 * i);
-                xy[2 * i] = f32x2{u[0], u[1]}; xy[2 * i + 1] = f32x2{u[2], u[3]};
-            }
-            f32x2 hA[4], hB[4];
-            float hC[4];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                f32x2 sA = splat2(0.f), sB = splat2(0.f);
-                float sC = 0.f;
-#pragma unroll
-                for (int t = 0; t < 11; ++t) {
-                    const f32x2 v = xy[o + t];
-                    sA = pk_fma(splat2(w[t]), v, sA);
-                    sB = pk_fma(splat2(w[t]), v * v, sB);
-                    sC = fmaf(w[t], v.x * v.y, sC);
-                }
-                hA[o] = sA; hB[o] = sB; hC[o] = sC;
-            }
-            const int d = r * T::MCP + c;
-            *reinterpret_cast<f32x4*>(tA + 2 * d) = f32x4{hA[0].x, hA[0].y, hA[1].x, hA[1].y};
-            *reinterpret_cast<f32x4*>(tA + 2 * d + 4) = f32x4{hA[2].x, hA[2].y, hA[3].x, hA[3].y};
-            *reinterpret_cast<f32x4*>(tB + 2 * d) = f32x4{hB[0].x, hB[0].y, hB[1].x, hB[1].y};
-            *reinterpret_cast<f32x4*>(tB + 2 * d + 4) = f32x4{hB[2].x, hB[2].y, hB[3].x, hB[3].y};
-            *reinterpret_cast<f32x4*>(tC + d) = f32x4{hC[0], hC[1], hC[2], hC[3]};
-        }
-    }
-    __syncthreads();
-    // ---- vertical pass on the map region (VR rows x 2 columns per item: VR + 10 staged rows feed VR output rows) + SSIM/CS
-    //      maps + derivative maps (into the input buffer: dA = (d_mu, d_11) pairs, dC = d_12) ----
-    float s_ssim = 0.f, s_cs = 0.f;
-    {
-        constexpr int PT = T::ER * T::MCP, VR = MS_VR, G = (T::MR + VR - 1) / VR;
-        const float* tA = tmp; const float* tB = tmp + 2 * PT; const float* tC = tmp + 4 * PT;
-        float* dA = lin; float* dC = lin + 2 * T::MR * T::DAS;
-        for (int it = threadIdx.x; it < G * (T::MC / 2); it += MS_NT) {
-            const int mr = (it / (T::MC / 2)) * VR, mc = (it % (T::MC / 2)) * 2;
-            // staged rows mr .. mr+VR+9: the last group may read up to 2 rows past row ER-1 (the next image, or the pad rows
-            // behind the last one) for output rows >= MR, which are dropped
-            const int rb = mr * T::MCP + mc;
-            f32x2 mu[VR][2], aa[VR][2], a12[VR];       // [output row][column] (mu1, mu2) / (a11, a22); a12: [row] over the 2 columns
-#pragma unroll
-            for (int o = 0; o < VR; ++o) { mu[o][0] = mu[o][1] = aa[o][0] = aa[o][1] = a12[o] = splat2(0.f); }
-            // row-major over the VR + 10 staged rows: each row of the three images is read once, added into the (up to VR) output
-            // rows it belongs to and dropped; an output row is finished — SSIM point, derivative maps — as soon as its
-            // eleventh tap is in, so only the accumulators + one staged row are live.  Every output still sums its taps
-            // in the order t = 0..10.
-            const float* pA = tA + rb * 2; const float* pB = tB + rb * 2; const float* pC = tC + rb;      // rows at immediate offsets
-#pragma unroll
-            for (int i = 0; i < VR + 10; ++i) {
-                const f32x4 vA = *reinterpret_cast<const f32x4*>(pA + i * (T::MCP * 2));
-                const f32x4 vB = *reinterpret_cast<const f32x4*>(pB + i * (T::MCP * 2));
-                const f32x2 vC = *reinterpret_cast<const f32x2*>(pC + i * T::MCP);
-#pragma unroll
-                for (int o = 0; o < VR; ++o) {
-                    if (i - o < 0 || i - o > 10) continue;
-                    const f32x2 wt = splat2(w[i - o]);
-                    mu[o][0] = pk_fma(wt, f32x2{vA[0], vA[1]}, mu[o][0]);
-                    mu[o][1] = pk_fma(wt, f32x2{vA[2], vA[3]}, mu[o][1]);
-                    aa[o][0] = pk_fma(wt, f32x2{vB[0], vB[1]}, aa[o][0]);
-                    aa[o][1] = pk_fma(wt, f32x2{vB[2], vB[3]}, aa[o][1]);
-                    a12[o] = pk_fma(wt, vC, a12[o]);
-                }
-                if (i < 10) continue;
-                const int o = i - 10, r = mr + o;
-                if (r < T::MR) {
-                    f32x2 ss, cs, dmv, d11v, d12v;
-                    ms_point2(f32x2{mu[o][0].x, mu[o][1].x}, f32x2{mu[o][0].y, mu[o][1].y}, f32x2{aa[o][0].x, aa[o][1].x},
-                              f32x2{aa[o][0].y, aa[o][1].y}, a12[o], &ss, &cs, &dmv, &d11v, &d12v);
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int c = mc + e;
-                        const bool interior = r >= 5 && r < 5 + T::RS && c >= 5 && c < 5 + T::CS;
-                        if (interior) { s_ssim += ss[e]; s_cs += cs[e]; }
-                        const bool inside = (unsigned)(r0 - 5 + r) < (unsigned)S && (unsigned)(c0 - 5 + c) < (unsigned)S;
-                        if (!inside) { dmv[e] = 0.f; d11v[e] = 0.f; d12v[e] = 0.f; }      // conv2d zero-pads the maps it filters
-                    }
-                    *reinterpret_cast<f32x4*>(dA + (r * T::DAS + mc) * 2) = f32x4{dmv.x, d11v.x, dmv.y, d11v.y};
-                    *reinterpret_cast<f32x2*>(dC + r * T::MCP + mc) = d12v;
-                }
-            }
-        }
-    }
-    s_ssim = seg_sum_dpp<64>(s_ssim); s_cs = seg_sum_dpp<64>(s_cs);          // totals in lane 63
-    if ((threadIdx.x & 63) == 63) { red[(threadIdx.x >> 6) * 2] = s_ssim; red[(threadIdx.x >> 6) * 2 + 1] = s_cs; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < MS_NT / 64; ++k) { t0 += red[2 * k]; t1 += red[2 * k + 1]; }
-        a.part[(size_t)blk * 2] = t0;
-        a.part[(size_t)blk * 2 + 1] = t1;
-    }
-    if (!a.F) return;
-    // ---- the same separable filter over the three derivative maps: horizontal ((d_mu, d_11) packed, d_12 scalar) ... ----
-    {
-        constexpr int J = T::CS / 4, PT = T::MR * T::CS;
-        const float* dA = lin; const float* dC = lin + 2 * T::MR * T::DAS;
-        float* gA = tmp; float* gC = tmp + 2 * PT;
-        for (int it = threadIdx.x; it < T::MR * J; it += MS_NT) {
-            const int r = 2 * (it / (2 * J)) + (it & 1), c = ((it % (2 * J)) >> 1) * 4;      // neighbouring lanes: the two rows of a pair
-            f32x2 va[14];
-            float vc[16];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                const f32x4 u = *reinterpret_cast<const f32x4*>(dA + (r * T::DAS + c) * 2 + 4 * i);
-                va[2 * i] = f32x2{u[0], u[1]}; va[2 * i + 1] = f32x2{u[2], u[3]};
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x4 u = *reinterpret_cast<const f32x4*>(dC + r * T::MCP + c + 4 * i);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) vc[4 * i + e] = u[e];
-            }
-            f32x2 gAo[4];
-            f32x4 gCo;
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                f32x2 sA = splat2(0.f);
-                float sC = 0.f;
-#pragma unroll
-                for (int t = 0; t < 11; ++t) { sA = pk_fma(splat2(w[t]), va[o + t], sA); sC = fmaf(w[t], vc[o + t], sC); }
-                gAo[o] = sA; gCo[o] = sC;
-            }
-            const int d = r * T::CS + c;
-            *reinterpret_cast<f32x4*>(gA + 2 * d) = f32x4{gAo[0].x, gAo[0].y, gAo[1].x, gAo[1].y};
-            *reinterpret_cast<f32x4*>(gA + 2 * d + 4) = f32x4{gAo[2].x, gAo[2].y, gAo[3].x, gAo[3].y};
-            *reinterpret_cast<f32x4*>(gC + d) = gCo;
-        }
-    }
-    __syncthreads();
-    // ---- ... vertical (VR rows x 2 columns per item), then F = f0 + 2 x f1 + y f2 ----
-    {
-        constexpr int PT = T::MR * T::CS, VR = MS_VR;
-        static_assert(T::RS % VR == 0 && ((T::MR + VR - 1) / VR) * VR + 10 <= T::ER + 2, "whole items; over-read of the vertical pass <= 2 rows");
-        const float* gA = tmp; const float* gC = tmp + 2 * PT;
-        const float* px = a.x + (size_t)plane * S * S;
-        const float* py = a.y + (size_t)plane * S * S;
-        float* pf = a.F + (size_t)plane * S * S;
-        for (int it = threadIdx.x; it < (T::RS / VR) * (T::CS / 2); it += MS_NT) {
-            const int r = (it / (T::CS / 2)) * VR, c = (it % (T::CS / 2)) * 2;
-            const size_t g = (size_t)(r0 + r) * S + c0 + c;
-            float2 xv[VR], yv[VR];               // L2 hits, issued ahead of the filter
-#pragma unroll
-            for (int o = 0; o < VR; ++o) {
-                xv[o] = *reinterpret_cast<const float2*>(px + g + (size_t)o * S);
-                yv[o] = *reinterpret_cast<const float2*>(py + g + (size_t)o * S);
-            }
-            f32x2 f01[VR][2], f2[VR];         // [row][column] (f0, f1); f2: [row] over the 2 columns
-            {
-                // row-major over the VR + 10 staged rows: each row is read, used by the (up to VR) outputs it belongs to and dropped —
-                // every output still sums its taps in the order t = 0..10
-#pragma unroll
-                for (int o = 0; o < VR; ++o) { f01[o][0] = splat2(0.f); f01[o][1] = splat2(0.f); }
-                const float* pg = gA + (r * T::CS + c) * 2;
-#pragma unroll
-                for (int i = 0; i < VR + 10; ++i) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(pg + i * (T::CS * 2));
-#pragma unroll
-                    for (int o = 0; o < VR; ++o) {
-                        if (i - o < 0 || i - o > 10) continue;
-                        f01[o][0] = pk_fma(splat2(w[i - o]), f32x2{v[0], v[1]}, f01[o][0]);
-                        f01[o][1] = pk_fma(splat2(w[i - o]), f32x2{v[2], v[3]}, f01[o][1]);
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-#pragma unroll
-                for (int o = 0; o < VR; ++o) f2[o] = splat2(0.f);
-                const float* pg = gC + r * T::CS + c;
-#pragma unroll
-                for (int i = 0; i < VR + 10; ++i) {
-                    const f32x2 v = *reinterpret_cast<const f32x2*>(pg + i * T::CS);
-#pragma unroll
-                    for (int o = 0; o < VR; ++o) {
-                        if (i - o < 0 || i - o > 10) continue;
-                        f2[o] = pk_fma(splat2(w[i - o]), v, f2[o]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int o = 0; o < VR; ++o)
-                *reinterpret_cast<float2*>(pf + g + (size_t)o * S) =
-                    make_float2(f01[o][0].x + 2.0f * xv[o].x * f01[o][0].y + yv[o].x * f2[o].x,
-                                f01[o][1].x + 2.0f * xv[o].y * f01[o][1].y + yv[o].y * f2[o].y);
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// whole-plane levels (S = 64, 32): one workgroup per plane, S*S/4 threads, every pass exactly one item per thread
+// whole-plane levels (S <= 64): one workgroup per plane, S*S/4 threads, every pass exactly one item per thread
 // ------------------------------------------------------------------------------------------------
-// The tile kernel above computes its maps on the tile extended by the window radius (twice, for the fused backward):
-// 36 x 76 row-filtered and 26 x 74 map positions for a 16 x 64 tile, most of them outside the image at S = 64, where
-// conv2d's zero padding makes every one of those values a known zero.  With the whole plane in one workgroup nothing
-// outside the image is ever computed: the zero padding is literally zero rows / columns in LDS, each of the four filter
-// passes runs on S x S positions (2.7x / 1.9x / 1.6x fewer than the tiles'), no position needs an inside / interior
-// test, and every pass has exactly NT = S*S/4 items — all waves busy in every phase, which is what lets a single
-// 1024-thread workgroup per CU (152 KB of LDS at S = 64) work.  Arithmetic per output is the tile kernel's: the same
-// t = 0..10 fma chains over the same products, so F, the pyramid and the per-element SSIM / CS values are bit-identical
-// to it; only the order of the plane's partial sums differs.
+// With the whole plane in one workgroup nothing outside the image is ever computed: conv2d's zero padding is literally
+// zero rows / columns in LDS, each of the four filter passes runs on S x S positions, no position needs an inside /
+// interior test, and every pass has exactly NT = S*S/4 items — all waves busy in every phase, which is what lets a
+// single 1024-thread workgroup per CU (152 KB of LDS at S = 64) work.  Every output is the same t = 0..10 fma chain over
+// the same products as in the stream kernel below, so F, the pyramid and the per-element SSIM / CS values are
+// bit-identical between the two forms; only the order of a plane's partial sums differs.
 template <int S>
 struct MsP {
     static constexpr int NTP = S * S / 4;     // threads per plane
@@ -417,7 +132,10 @@ struct MsP {
     static constexpr int DAS = S + 14;        // row stride (pixels) of the (x, y) input image AND of the (d_mu, d_11) image that later
                                               // overlays it: 6 zero columns left (16-byte aligned stores and window reads; the
                                               // windows are read 16 wide), 8 right — the same columns in both uses, zeroed once
-                                              // per workgroup; DAS / 2 odd (see MsT)
+                                              // per workgroup.  DAS / 2 is ODD: an item of a horizontal pass reads
+                                              // 16-byte units 32 bytes apart from its neighbour's, and with an odd row
+                                              // stride in 16-byte units, lanes that alternate between two rows cover all
+                                              // 16 slots of the 256-byte bank row: conflict-free
     static constexpr int DCS = S + 12;        // d_12 row stride: 6 zero columns either side (behind the input image: zeroed once)
     static constexpr int TAS = S + 2;         // row stride (pixels) of the pair images in tmp: the two rows of a lane pair
                                               // land 16 bytes apart modulo 32 — their 16-byte stores interleave
@@ -680,8 +398,7 @@ __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
 // the 128-wide level (level 0 of BASELINE config 5's frames): one workgroup per plane, the plane STREAMED through LDS in bands
 // ------------------------------------------------------------------------------------------------
 // A whole 128 x 128 plane needs 4x the LDS of the 64-wide plane kernel, and strips with a halo pay for the halo in every one of the four
-// filter passes (a 16 x 128 strip filters 36 / 26 / 26 / 16 rows: 6.5 units of work per output row against the 16 x 64 tile kernel's 7.2
-// and the plane kernel's 4.0).  Streaming pays 4.5: the workgroup walks down its plane in bands of R = 16 rows and keeps, in LDS, the
+// filter passes (a 16 x 128 strip filters 36 / 26 / 26 / 16 rows: 6.5 units of work per output row against the plane kernel's 4.0).  Streaming pays 4.5: the workgroup walks down its plane in bands of R = 16 rows and keeps, in LDS, the
 // last R + 10 rows of every ROW-FILTERED field — {hx, hy, hxx, hyy, hxy} of the input (t1) and {g0, g1, g2} of the derivative maps (t2).
 // Per band (image rows b0 .. b0 + R - 1 arrive; b0 = 0, R, .., S, the last band carries zero rows to flush the two 5-row lags):
 //   stage the band's (x, y) rows                                    -> lin rows 0..R-1
@@ -690,8 +407,8 @@ __global__ __launch_bounds__(MsP<S>::NT) void msssim_plane_kernel(MsFwdArgs a) {
 //   h2: row-filter the derivative maps                              -> t2 rows 10..R+9        (t2 row j = map row b0 - 15 + j)
 //   v2: column-filter t2 rows i..i+10, F = f0 + 2 x f1 + y f2       -> F rows b0 - 10 + i      (x, y of those rows: fetched again, L2)
 //   the last 10 rows of t1 / t2 move to the top (rows outside the image are zero: conv2d's padding, never computed as maps).
-// Every pass has exactly R * S / 4 = 512 items = threads, with the plane kernel's item shapes and fma chains (values are the tile
-// kernel's: same t = 0..10 order over the same products; only the order of a plane's partial sums differs).  9 bands x 4 passes of 16
+// Every pass has exactly R * S / 4 = 512 items = threads, with the plane kernel's item shapes and fma chains (the same
+// t = 0..10 order over the same products, so values are the plane kernel's; only the order of a plane's partial sums differs).  9 bands x 4 passes of 16
 // rows = 4.5 units; 135 KB of LDS, one workgroup (8 waves) per CU, persistent over planes, the next band's pixels in flight in
 // registers during the passes.
 template <int S, int R>
@@ -1074,9 +791,7 @@ struct MsWs {
     int64_t pyrx[5], pyry[5], F[5], part[5], slab, coef, ticket, total;
     int nblk[5];
 };
-static int ms_tiles(int S) { return S == 128 ? MsT<128>::TILES : 1; }      // <= 64: msssim_plane_kernel, one partial pair per plane
-// 128-wide level: the band-streaming kernel (one partial pair per plane); CVAE_MS_STREAM=0 keeps the 16 x 64 tile kernel for A/B runs
-static bool ms_stream() { static const int v = [] { const char* e = getenv("CVAE_MS_STREAM"); return e ? atoi(e) : 1; }(); return v != 0; }
+// every level writes one partial pair per plane: msssim_stream_kernel at 128 wide, msssim_plane_kernel below
 static MsWs ms_carve(int width, int B) {
     MsWs w{};
     const int P = B * 3;
@@ -1087,7 +802,7 @@ static MsWs ms_carve(int width, int B) {
         const int64_t n = (int64_t)P * S * S;
         if (l > 0) { w.pyrx[l] = take(n); w.pyry[l] = take(n); }
         w.F[l] = take(n);
-        w.nblk[l] = P * ms_tiles(S);
+        w.nblk[l] = P;
     }
     for (int l = 0; l < 5; ++l) w.part[l] = take((int64_t)w.nblk[l] * 2);
     w.slab = take(MS_NF * 11 * 2);
@@ -1103,17 +818,10 @@ static int ms_fwd(const MsFwdArgs& a, hipStream_t st) {
     static DeviceOnce once;
     if (a.ticket) cvae_probe_begin(st);                 // level 0 only (the launch that also zeroes the ticket)
     if constexpr (S == 128) {
-        if (ms_stream()) {
-            using T = MsS<S, 16>;
-            static DeviceOnce once2;
-            { int rc = cvae_grant_lds(once2, reinterpret_cast<const void*>(msssim_stream_kernel<S, 16>), T::SMEM); if (rc) return rc; }
-            const int resident = cvae_num_cus();             // 135 KB of LDS: one workgroup per CU, persistent over the planes
-            hipLaunchKernelGGL((msssim_stream_kernel<S, 16>), dim3(a.P < resident ? a.P : resident), dim3(T::NT), T::SMEM, st, a);
-        } else {
-            using T = MsT<S>;
-            { int rc = cvae_grant_lds(once, reinterpret_cast<const void*>(msssim_fwd_kernel<S>), T::SMEM); if (rc) return rc; }
-            hipLaunchKernelGGL(msssim_fwd_kernel<S>, dim3(a.P * T::TILES), dim3(MS_NT), T::SMEM, st, a);
-        }
+        using T = MsS<S, 16>;
+        { int rc = cvae_grant_lds(once, reinterpret_cast<const void*>(msssim_stream_kernel<S, 16>), T::SMEM); if (rc) return rc; }
+        const int resident = cvae_num_cus();                 // 135 KB of LDS: one workgroup per CU, persistent over the planes
+        hipLaunchKernelGGL((msssim_stream_kernel<S, 16>), dim3(a.P < resident ? a.P : resident), dim3(T::NT), T::SMEM, st, a);
     } else {
         using T = MsP<S>;
         { int rc = cvae_grant_lds(once, reinterpret_cast<const void*>(msssim_plane_kernel<S, LAST>), T::SMEM); if (rc) return rc; }
@@ -1154,7 +862,7 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
     }
     MsFinArgs f{};
     for (int l = 0; l < 5; ++l) {
-        f.part[l] = ws + w.part[l]; f.nblk[l] = ((width >> l) == 128 && ms_stream()) ? P : w.nblk[l];
+        f.part[l] = ws + w.part[l]; f.nblk[l] = w.nblk[l];
         f.count[l] = (double)P * (width >> l) * (width >> l);
     }
     f.mu = mu; f.logvar = logvar; f.B = mu ? B : 0; f.scalars = scalars; f.coef = ws + w.coef;

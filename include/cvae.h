@@ -225,9 +225,9 @@ int cvae_dense_crf(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, cons
 
 /* float offset of a named saved tensor in the workspace ("y0".."y3", "a0".."a3", "o0".."o3",
  * "zcat", "h", "d_*" ...) for tests; -1 if unknown OR not allocated in this configuration: "d_y0" does not exist
- * (block 0's BatchNorm backward runs inside the E1 weight-gradient kernel; CVAE_FUSE_E1=0 restores it), and in
- * precision mode 1 "dout4" has no storage and the "y0" slot is STALE unless a block-0 |gamma| is < 1e-2 (the device
- * decides per step) or CVAE_FUSE_E1=0 — do not read it otherwise.  Slots hold bf16 elements in precision mode 1. */
+ * (block 0's BatchNorm backward runs inside the E1 weight-gradient kernel), and in precision mode 1 "dout4" has no
+ * storage and the "y0" slot is STALE unless a block-0 |gamma| is < 1e-2 (the device decides per step) — do not read it
+ * otherwise.  Slots hold bf16 elements in precision mode 1. */
 int64_t cvae_ws_offset(cvae_handle h, int32_t batch, const char* name);
 
 /* Which kernel family the forward (dgrad = 0) or input-gradient (dgrad = 1) pass of encoder conv layer 1..3 (E2..E4, nn.Conv2d at

@@ -437,28 +437,54 @@ def test_bn_pool_ops_follow_the_handle_storage_type():
     assert (dbeta - gq.sum(dim=(0, 1, 2))).abs().max() <= 1e-3 * gq.abs().sum(dim=(0, 1, 2)).max()
 
 
-def test_two_pass_e1_forward_is_bit_identical(monkeypatch):
+def _e1_per_op(h, B, W, x, theta, bn_state, train):
+    """Block 0's forward in the per-op form: op_conv_fwd(0) stores y0 (bf16) and the BatchNorm partials, op_bn_pool_act_fwd(0)
+    merges them and reads y0 back.  Returns (a0, coef0, running mean, running var); bn_state itself is not modified."""
+    from critic_vae_amd import layout as L
+    prm = {k: theta[o:o + n] for k, (o, n) in h.layout.items() if k.startswith("enc0.")}
+    y0 = torch.empty(B * W * W * 32 // 2, device=x.device)
+    part = torch.empty(h.op_bn_partial_floats(0, B), device=x.device)
+    h.op_conv_fwd(0, B, x, prm["enc0.w"], prm["enc0.b"], y0, part)
+    rm, rv = bn_state[:32].clone(), bn_state[L.BN_TOTAL:L.BN_TOTAL + 32].clone()
+    coef = torch.empty(128, device=x.device)
+    a0 = torch.empty(B * (W // 2) * (W // 2) * 32 // 2, device=x.device)
+    h.op_bn_pool_act_fwd(0, B, y0, part, prm["enc0.gamma"], prm["enc0.beta"], rm, rv, coef, a0,
+                         torch.empty(h.op_scratch_floats(B), device=x.device), train=train)
+    torch.cuda.synchronize()
+    return a0, coef, rm, rv
+
+
+def test_two_pass_e1_forward_is_bit_identical():
     """bf16 mode runs E1's forward twice (statistics pass, then conv + BatchNorm / pool / ReLU epilogue) instead of
-    conv -> bn_pool_act_fwd reading y1 back (CVAE_E1_TWO_PASS=0).  The epilogue pools the bf16-rounded values exactly
-    as the separate kernel pools the stored tensor, so losses, outputs and every gradient must agree to the bit —
-    train mode at both frame sizes, and the eval-mode encoder."""
+    conv -> bn_pool_act_fwd reading y1 back (the per-op form: op_conv_fwd(0), then op_bn_pool_act_fwd(0)).  The epilogue
+    pools the bf16-rounded values exactly as the separate kernel pools the stored tensor, so the step's a0, coef0 and
+    block-0 running statistics must equal the per-op form's on the same theta, x and pre-step running statistics to the
+    bit — at both frame sizes; and the eval-mode encoder's a0 must equal the same ops at train=False."""
+    from critic_vae_amd import layout as L
     from critic_vae_amd.nets import VariationalAutoencoder
     from critic_vae_amd.train import FusedTrainer
     dev = torch.device("cuda:0")
     for W, B in ((64, 8), (128, 3)):
         x, pred, eps = (torch.from_numpy(v).to(dev) for v in synth.make_batch(1234, 0, B, W))
-        res = {}
-        for two in ("1", "0"):
-            monkeypatch.setenv("CVAE_E1_TWO_PASS", two)
-            vae = VariationalAutoencoder(width=W, max_batch=B, seed=0, precision="bf16").to(dev)
-            tr = FusedTrainer(vae)
-            scal = tr.step(x, pred, eps).clone()
-            with torch.no_grad():
-                mu_eval, _ = vae.eval().encoder(x)
-            torch.cuda.synchronize()
-            res[two] = (scal, tr.recon[:B].clone(), tr.grads.clone(), vae.bn_state.clone(), mu_eval.clone())
-        for a, b in zip(res["1"], res["0"]):
-            assert torch.equal(a, b)
+        vae = VariationalAutoencoder(width=W, max_batch=B, seed=0, precision="bf16").to(dev)
+        h = vae.handle
+        tr = FusedTrainer(vae)
+        theta0, bn0 = vae.theta.data.clone(), vae.bn_state.clone()
+        tr.step(x, pred, eps)
+        torch.cuda.synchronize()
+        step_a0 = h.ws_view(tr.ws, B, "a0", B * (W // 2) * (W // 2) * 32 // 2).clone()
+        step_coef0 = h.ws_view(tr.ws, B, "coef0", 128).clone()
+        a0, coef, rm, rv = _e1_per_op(h, B, W, x, theta0, bn0, train=True)
+        assert torch.equal(step_a0.view(torch.int32), a0.view(torch.int32)), (W, "a0")
+        assert torch.equal(step_coef0, coef), (W, "coef0")
+        assert torch.equal(vae.bn_state[:32], rm), (W, "running mean 0")
+        assert torch.equal(vae.bn_state[L.BN_TOTAL:L.BN_TOTAL + 32], rv), (W, "running var 0")
+        with torch.no_grad():
+            vae.eval().encoder(x)
+        torch.cuda.synchronize()
+        eval_a0 = h.ws_view(tr.ws, B, "a0", a0.numel()).clone()
+        a0e, _, _, _ = _e1_per_op(h, B, W, x, vae.theta.data, vae.bn_state, train=False)
+        assert torch.equal(eval_a0.view(torch.int32), a0e.view(torch.int32)), (W, "eval a0")
 
 
 @pytest.mark.parametrize("B,vec_bound,tiny_bound", [(8, 0.35, 0.25), (512, 0.20, 0.10)])

@@ -362,30 +362,6 @@ def test_msssim_128_wide_streamed_level_against_oracle(B):
     check(d_a.view(B, 3, 128, 128), a_ref.grad, "msssim grad", rel=True)
 
 
-def test_msssim_128_wide_streamed_level_is_the_tile_kernel_bit_for_bit(tmp_path):
-    """The streamed level keeps the tile kernel's item shapes and fma chains: d_recon (the F fields of all five levels through the
-    backward pass) must be bit-identical to the 16 x 64 tile kernel's (CVAE_MS_STREAM=0) and the loss scalars equal to 1e-7 (the order
-    of the per-plane partial sums differs).  The switch is read once per process: two child processes run
-    profiles/experiments/ms_stream_check.py (B = 5 and 64) and the dumps are compared here."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = os.path.join(root, "profiles", "experiments", "ms_stream_check.py")
-    dumps = {}
-    for mode in ("1", "0"):
-        out = str(tmp_path / f"ms{mode}.npz")
-        env = dict(os.environ, CVAE_MS_STREAM=mode)
-        r = subprocess.run([sys.executable, script, out], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        dumps[mode] = np.load(out)
-    for k in dumps["1"].files:
-        if k.startswith("d_recon"):
-            assert np.array_equal(dumps["1"][k], dumps["0"][k]), k
-        else:
-            assert np.abs(dumps["1"][k] - dumps["0"][k]).max() < 1e-7, k
-
-
 def test_adam_matches_torch(H):
     n = 4096
     p0, g = rnd("ap", (n,)), rnd("ag", (n,), -1e-2, 1e-2)

@@ -179,30 +179,33 @@ def test_intermediates_against_oracle_taps():
         assert (got - g).abs().max() <= TOL * max(1.0, 0) + 1e-4 * g.abs().max(), f"d_y{l}"
 
 
-@pytest.mark.parametrize("prec,width,rel", [("f32", 64, 1e-6), ("f32", 128, 1e-6), ("bf16", 64, 2e-2)])
-def test_fused_e1_backward_equals_the_separate_apply_pass(monkeypatch, prec, width, rel):
-    """Block 0's BatchNorm / pool / ReLU backward runs inside E1's weight-gradient kernel (E1Fuse, the default) or as
-    bn.hip's apply pass that writes d_y0 (CVAE_FUSE_E1=0).  fp32: the same arithmetic per element, so dW1 / db1 agree to
-    fp32 summation noise; bf16: the fused form folds the per-channel constants before the bf16 rounding of dy."""
+@pytest.mark.parametrize("prec,width,rel", [("f32", 64, 1e-6), ("f32", 128, 1e-6)])
+def test_fused_e1_backward_equals_the_separate_apply_pass(prec, width, rel):
+    """Block 0's BatchNorm / pool / ReLU backward runs inside E1's weight-gradient kernel (E1Fuse).  The separate form is the
+    per-op one: bn.hip's apply pass writes d_y0 (ws_tools.recompute_d_y0, from the y0 / a0 / d_a0 / coef0 the step left), then
+    op_conv_wgrad(0) contracts it with x.  fp32: the same arithmetic per element, so dW1 / db1 agree to fp32 summation noise.
+    bf16 mode has no case here: check_bf16_stored_operands (test_gpu_bf16.py) holds its dW1 / db1 to tighter, per-element
+    bounds, recomputing d_y0 and dW1 from the stored operands."""
     from critic_vae_amd import layout as L
+    from ws_tools import recompute_d_y0
     B = 8
     x, pred, eps = (t.cuda() for t in _inputs(1234, 0, B, width=width))
-    grads = {}
-    for fuse in ("1", "0"):
-        monkeypatch.setenv("CVAE_FUSE_E1", fuse)
-        vae = VariationalAutoencoder(max_batch=B, seed=0, width=width, precision=prec).cuda()
-        vae.load_reference_params(synth.make_params(0, width))
-        tr = FusedTrainer(vae)
-        tr.step(x, pred, eps)
-        torch.cuda.synchronize()
-        grads[fuse] = {k: v.clone() for k, v in L.native_to_ref(vae.handle.layout, tr.grads.cpu()).items()}
-    for k in grads["1"]:
-        a, b = grads["1"][k], grads["0"][k]
-        if k.startswith("encoder.model.0."):
-            bound = rel * b.abs().max().item() + (1e-6 if k.endswith("bias") else 0.0)      # db1 cancels to ~0
-            assert (a - b).abs().max().item() <= bound, (k, (a - b).abs().max().item(), b.abs().max().item())
-        else:
-            assert torch.equal(a, b), k           # nothing else may change
+    vae = VariationalAutoencoder(max_batch=B, seed=0, width=width, precision=prec).cuda()
+    vae.load_reference_params(synth.make_params(0, width))
+    h = vae.handle
+    tr = FusedTrainer(vae)
+    tr.step(x, pred, eps)
+    d_y0 = recompute_d_y0(h, tr.ws, B, width=width)
+    sep = tr.grads.clone()
+    ow, nw = h.layout["enc0.w"]
+    ob, nb = h.layout["enc0.b"]
+    h.op_conv_wgrad(0, B, x, d_y0, sep[ow:ow + nw], sep[ob:ob + nb], torch.empty(h.op_scratch_floats(B), device=x.device))
+    torch.cuda.synchronize()
+    got, want = L.native_to_ref(h.layout, tr.grads.cpu()), L.native_to_ref(h.layout, sep.cpu())
+    for k in ("encoder.model.0.weight", "encoder.model.0.bias"):
+        a, b = got[k], want[k]
+        bound = rel * b.abs().max().item() + (1e-6 if k.endswith("bias") else 0.0)      # db1 cancels to ~0
+        assert (a - b).abs().max().item() <= bound, (k, (a - b).abs().max().item(), b.abs().max().item())
 
 
 @pytest.mark.parametrize("precision", ["f32", "bf16x9", "bf16x6"])
