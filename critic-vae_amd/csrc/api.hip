@@ -99,6 +99,9 @@ struct cvae_handle_s {
     bool streams_ready = false;
     const void* xp_ws = nullptr;     // the workspace (and batch) whose packed bf16 frame the last train-mode forward wrote: the backward stages E1's strips from
     int xp_B = 0;                    // it only then (an eval-mode forward, or another workspace, leaves it stale -> the fp32 frame is staged instead)
+    // staged (cross-rank) step: the stage the handle expects next — pass 0 forward (stages 0..4), 1 loss (0..1), 2 backward
+    // (0..4) — and the workspace, batch and record the step runs on.  Forward stage 0 may always start a new step.
+    struct { int pass = 0, next = 0, B = 0; const void* ws = nullptr; const double* rec = nullptr; } sync;
     ProbeState probe;
 };
 
@@ -256,6 +259,12 @@ int64_t cvae_ws_offset(cvae_handle h, int32_t batch, const char* name) {
 }
 
 static const int kBnOff[4] = {0, 32, 96, 224};
+// the fp64 sync record of the staged entry points (include/cvae.h): points 0..3 = forward blocks 0..3 (S, Q, M per channel;
+// point 0 ends with this rank's image count), 4 = the 11 loss sums, 5..8 = backward blocks 3..0 (sum g, sum g*xhat per channel)
+static const int64_t kSyncOff[9] = {0, 97, 289, 673, 1441, 1452, 1964, 2220, 2348};
+static const int64_t kSyncCnt[9] = {97, 192, 384, 768, 11, 512, 256, 128, 64};
+static const int64_t kSyncCount = 96;            // the image count inside point 0
+static_assert(2348 + 64 == CVAE_SYNC_DOUBLES, "sync record size");
 int cvae_decode(cvae_handle h, int32_t B, const float* zcat, const float* params, float* recon, void* wsv, void* stream);
 int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* pred, const float* eps, const float* params,
                          const float* logvar, const float* recon, const float* d_recon, const float* d_mu,
@@ -301,39 +310,63 @@ static int check(cvae_handle h, int32_t batch, const void* ws) {
     return 0;
 }
 
+// One encoder block of the forward in steps: conv (the conv and its BatchNorm partials; bf16 mode, block 0: the
+// statistics pass), stats (the statistics: finalized here, or this rank's record for the cross-rank path, whose finish
+// turns the summed record into coef) and apply (BatchNorm/pool/activation -> a[l]).
+struct FwdCtx {
+    cvae_handle h; int B, W, train; const float* x; const float* params; float* bn_state; float* ws; void* wsv; WsLayout w; hipStream_t st;
+    int tpp = 1;                 // 128-pixel tiles per BatchNorm partial row, as reported by the conv kernel that ran
+    // bf16 mode, block 0: both E1 passes stage the packed bf16 frame (slot xp) that the statistics pass writes while it stays
+    // below 2 GiB (conv_route); past that every E1 pass stages the fp32 frame
+    float* xp() const { return train && conv_route(1, 0, W, false, B).family == E1_PACKED_FRAME ? ws + w.xp : nullptr; }
+    bool two_pass(int l) const { return l == 0 && h->cfg.precision == 1; }
+    int conv(int l) {
+        tpp = 1;
+        if (two_pass(l)) {
+            // bf16 mode, block 0: conv (statistics only) -> merged statistics -> conv again with BatchNorm/pool/ReLU in its
+            // epilogue (writes a0); bn_pool_act_fwd's read of y0 is replaced by a second read of x
+            if (train) RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), nullptr, ws + w.bnpart[0], st, true, 1, nullptr, nullptr, xp()));     // also writes xp
+            h->xp_ws = xp() ? wsv : nullptr; h->xp_B = B;
+            return 0;
+        }
+        if (l == 0) { ProbeArm pa(h, 0, 0); RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], ws + w.bnpart[0], st)); }
+        else if (use_bf16(h, l)) { ProbeArm pa(h, 0, l); RC(launch_conv_fwd_bf16(l, W, bf16_mode(h), B, ws + w.a[l - 1], ws + w.wpack, P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st, &tpp)); }
+        else { ProbeArm pa(h, 0, l); RC(launch_conv_fwd(l, W, B, ws + w.a[l - 1], P_(h->enc_w[l]), P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st)); }
+        return 0;
+    }
+    int stats(int l, double* sync) {
+        if (sync) return launch_bn_fwd_record(l, W, B, ws + w.bnpart[l], ws + w.scratch, st, tpp, sync + kSyncOff[l], l == 0 ? sync + kSyncCount : nullptr);
+        return launch_bn_fwd_finalize(l, W, B, ws + w.bnpart[l], P_(h->enc_g[l]), P_(h->enc_be[l]), bn_state + kBnOff[l],
+                                      bn_state + 480 + kBnOff[l], ws + w.coef[l], ws + w.scratch, train, st, tpp);
+    }
+    int finish(int l, const double* sync) {
+        return launch_bn_fwd_finish(l, W, sync + kSyncOff[l], sync + kSyncCount, P_(h->enc_g[l]), P_(h->enc_be[l]), bn_state + kBnOff[l],
+                                    bn_state + 480 + kBnOff[l], ws + w.coef[l], st);
+    }
+    int apply(int l) {
+        if (two_pass(l)) {
+            ProbeArm pa(h, 0, 0);
+            // y0 is written only when a channel's gamma is tiny (decided on the device): the fused weight-gradient kernel recomputes it
+            return launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], nullptr, st, true, 2, ws + w.coef[0], ws + w.a[0],
+                                 xp());                // eval mode (no statistics pass) or no packed frame: E1_POOL_X
+        }
+        return launch_bn_pool_act_fwd(l, W, B, ws + w.y[l], ws + w.coef[l], ws + w.a[l], st, io_bf16(h));
+    }
+};
+
 int cvae_forward(cvae_handle h, int32_t B, const float* x, const float* pred, const float* eps, const float* params,
                  float* bn_state, float* mu, float* logvar, float* recon, void* wsv, int32_t train, void* stream) {
     RC(check(h, B, wsv));
-    if (B < 2 && train) { /* BatchNorm with one 1x1... still fine: B*H*W >= 2 */ }
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)wsv;
     const WsLayout w = carve(h, B);
     const int W = h->cfg.width;
     RC(pack_bf16_weights(h, params, ws, w, st));
+    FwdCtx f{h, B, W, train, x, params, bn_state, ws, wsv, w, st};
     for (int l = 0; l < 4; ++l) {
-        int tpp = 1;                            // 128-pixel tiles per BatchNorm partial row, as reported by the conv kernel that ran
-        if (l == 0 && h->cfg.precision == 1) {
-            // bf16 mode, block 0: conv (statistics only) -> merged statistics -> conv again with BatchNorm/pool/ReLU in its
-            // epilogue (writes a0); bn_pool_act_fwd's read of y0 is replaced by a second read of x, as the packed bf16 frame
-            // (slot xp) that the statistics pass writes while it stays below 2 GiB (conv_route); past that every E1 pass stages the fp32 frame
-            float* xp = train && conv_route(1, 0, W, false, B).family == E1_PACKED_FRAME ? ws + w.xp : nullptr;
-            if (train) RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), nullptr, ws + w.bnpart[0], st, true, 1, nullptr, nullptr, xp));     // also writes xp
-            h->xp_ws = xp ? wsv : nullptr; h->xp_B = B;
-            RC(launch_bn_fwd_finalize(0, W, B, ws + w.bnpart[0], P_(h->enc_g[0]), P_(h->enc_be[0]), bn_state + kBnOff[0],
-                                      bn_state + 480 + kBnOff[0], ws + w.coef[0], ws + w.scratch, train, st));
-            { ProbeArm pa(h, 0, 0);
-              // y0 is written only when a channel's gamma is tiny (decided on the device): the fused weight-gradient kernel recomputes it
-              RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], nullptr, st, true, 2, ws + w.coef[0], ws + w.a[0],
-                               xp)); }               // eval mode (no statistics pass) or no packed frame: E1_POOL_X
-            continue;
-        }
-        if (l == 0) { ProbeArm pa(h, 0, 0); RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], ws + w.bnpart[0], st)); }
-        else if (use_bf16(h, l)) { ProbeArm pa(h, 0, l); RC(launch_conv_fwd_bf16(l, W, bf16_mode(h), B, ws + w.a[l - 1], ws + w.wpack, P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st, &tpp)); }
-        else { ProbeArm pa(h, 0, l); RC(launch_conv_fwd(l, W, B, ws + w.a[l - 1], P_(h->enc_w[l]), P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st)); }
-        RC(launch_bn_fwd_finalize(l, W, B, ws + w.bnpart[l], P_(h->enc_g[l]), P_(h->enc_be[l]), bn_state + kBnOff[l],
-                                  bn_state + 480 + kBnOff[l], ws + w.coef[l], ws + w.scratch, train, st,
-                                  tpp));
-        RC(launch_bn_pool_act_fwd(l, W, B, ws + w.y[l], ws + w.coef[l], ws + w.a[l], st, io_bf16(h)));
+        RC(f.conv(l));
+        RC(f.stats(l, nullptr));
+        RC(f.apply(l));
     }
     RC(launch_fc_fwd(W, B, ws + w.a[3], P_(h->fc_w), P_(h->fc_b), eps, pred, mu, logvar, ws + w.zcat, ws + w.scratch, st, io_bf16(h)));
     if (!recon) return 0;                       // encode only (VariationalEncoder.forward)
@@ -410,6 +443,89 @@ int cvae_grad_bucket(cvae_handle h, int32_t phase, int64_t* offset, int64_t* num
     return 0;
 }
 
+#define HIPRC(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cvae_set_error("%s: %s", #call, hipGetErrorString(e_)); return (int)e_; } } while (0)
+// The backward in pieces shared by cvae_backward_phases and the staged entry points.  cfg.overlap_wgrad != 0: weight-gradient
+// work on a lower-priority side stream (bit-identical results; round 3: +1.5 % in bf16 mode at B = 2048, -3 % in fp32 mode at
+// B = 256); default: everything in order on the caller's stream.
+struct BwdCtx {
+    cvae_handle h; int B, W; const float* x; const float* eps; const float* params; const float* logvar; const float* recon;
+    const float* d_recon; const float* d_mu; const float* d_logvar; float* ws; float* grads; WsLayout w; hipStream_t st;
+    bool overlap = false; hipStream_t sd = nullptr; float* sc = nullptr; float* scw = nullptr;
+    int init() {
+        sc = ws + w.scratch; scw = ws + w.scratch_w;
+        overlap = h->cfg.overlap_wgrad != 0;
+        if (overlap) RC(ensure_streams(h));
+        sd = overlap ? h->side : st;
+        return 0;
+    }
+    // `ready k` = the gradient a weight-gradient kernel needs exists on the main stream; the side
+    // stream picks it up from there, so dW/db never delay the dgrad chain.
+    int fork(int idx) {
+        if (!overlap) return 0;
+        HIPRC(hipEventRecord(h->ev_ready[idx], st));
+        HIPRC(hipStreamWaitEvent(sd, h->ev_ready[idx], 0));
+        return 0;
+    }
+    int join() {                                        // side-stream work so far is complete on the caller's stream
+        if (!overlap) return 0;
+        HIPRC(hipEventRecord(h->ev_side, h->side));
+        HIPRC(hipStreamWaitEvent(st, h->ev_side, 0));
+        return 0;
+    }
+    int decoder() {                                     // decoder, last layer first, then the latent (phase 0)
+        { ProbeArm pa(h, 1, 8);
+          RC(launch_d4_bwd(W, B, ws + w.o[3], d_recon, recon, P_(h->dec_w[4]), ws + w.dout4, ws + w.d_o[3],
+                           G_(h->dec_w[4]), G_(h->dec_b[4]), sc, st, io_bf16(h))); }
+        for (int i = 3; i >= 0; --i) {
+            const int l = 4 + i;
+            const float* in = i == 0 ? ws + w.h : ws + w.o[i - 1];
+            RC(fork(3 - i));
+            if (i == 0) {
+                { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, 4, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd)); }
+                { ProbeArm pa(h, 1, l);
+                  if (use_bf16(h, 4)) RC(launch_conv_dgrad_bf16(4, W, bf16_mode(h), B, ws + w.d_o[0], ws + w.wpack, ws + w.d_h, ws + w.scratch, st));
+                  else RC(launch_conv_dgrad(l, W, B, ws + w.d_o[0], P_(h->dec_w[0]), nullptr, ws + w.d_h, ws + w.scratch, st)); }
+            } else {
+                { ProbeArm pa(h, 2, l);
+                  RC(launch_conv_up_wgrad(l, W, B, in, ws + w.d_o[i], G_(h->dec_w[i]), G_(h->dec_b[i]), scw, sd, use_bf16_wgrad(h, l))); }
+                { ProbeArm pa(h, 1, l);
+                  if (use_bf16(h, l)) RC(launch_conv_up_dgrad_bf16(l, W, bf16_mode(h), B, ws + w.d_o[i], ws + w.wpack, ws + w.o[i - 1], ws + w.d_o[i - 1], st));
+                  else RC(launch_conv_up_dgrad(l, W, B, ws + w.d_o[i], ws + w.wc[i - 1], ws + w.o[i - 1], ws + w.d_o[i - 1], sc, st)); }
+            }
+        }
+        RC(launch_decin_bwd(W, B, ws + w.zcat, ws + w.d_h, P_(h->di_w), G_(h->di_w), G_(h->di_b), ws + w.d_zcat, sc, st, io_bf16(h)));
+        return join();
+    }
+    int fc() {
+        return launch_fc_bwd(W, B, ws + w.a[3], P_(h->fc_w), ws + w.d_zcat, eps, logvar, d_mu, d_logvar, G_(h->fc_w),
+                             G_(h->fc_b), ws + w.d_a[3], sc, st, io_bf16(h));
+    }
+    // BatchNorm/pool/activation backward of block l: stage 0 whole, 1 statistics -> record `rec`, 2 finish from the summed
+    // record + apply.  Block 0: only the statistics run here; E1's weight-gradient kernel applies the BatchNorm/pool/ReLU
+    // backward while it stages its tiles (there is no d_y[0]: nothing else would read it)
+    int bn(int l, int stage, double* rec, const double* count) {
+        ProbeArm pa(h, 3, l);
+        return launch_bn_pool_act_bwd(l, W, B, ws + w.y[l], ws + w.a[l], ws + w.d_a[l], ws + w.coef[l], P_(h->enc_g[l]),
+                                      l == 0 ? nullptr : ws + w.d_y[l], G_(h->enc_g[l]), G_(h->enc_be[l]), nullptr, sc, st, io_bf16(h),
+                                      stage, rec, count);
+    }
+    int block_grads(int l) {                            // weight (side stream) and input gradients of block l, after bn(l)
+        RC(fork(7 - l));
+        if (l == 0) {
+            const float* fu[7] = {ws + w.y[0], ws + w.a[0], ws + w.d_a[0], ws + w.coef[0], bn_bwd_bcoef(0, W, B, sc),
+                                  P_(h->enc_w[0]), P_(h->enc_b[0])};
+            ProbeArm pa(h, 2, 0);
+            return launch_e1_wgrad(W, B, x, nullptr, G_(h->enc_w[0]), G_(h->enc_b[0]), scw, sd, h->cfg.precision == 1, fu,
+                                   (h->cfg.precision == 1 && h->xp_ws == (const void*)ws && h->xp_B == B &&
+                                    conv_route(1, 0, W, false, B).family == E1_PACKED_FRAME) ? ws + w.xp : nullptr);
+        }
+        { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, l, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd)); }
+        ProbeArm pa(h, 1, l);
+        if (use_bf16(h, l)) return launch_conv_dgrad_bf16(l, W, bf16_mode(h), B, ws + w.d_y[l], ws + w.wpack, ws + w.d_a[l - 1], ws + w.scratch, st);
+        return launch_conv_dgrad(l, W, B, ws + w.d_y[l], P_(h->enc_w[l]), nullptr, ws + w.d_a[l - 1], nullptr, st);
+    }
+};
+
 int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* pred, const float* eps, const float* params,
                          const float* logvar, const float* recon, const float* d_recon, const float* d_mu,
                          const float* d_logvar, void* wsv, float* grads, int32_t phase_mask, void* stream) {
@@ -427,87 +543,127 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
         }
         RC(launch_zero_gaps(grads, gaps, st));
     }
-    float* ws = (float*)wsv;
-    const WsLayout w = carve(h, B);
-    const int W = h->cfg.width;
-    float* sc = ws + w.scratch;
-    float* scw = ws + w.scratch_w;
-    // cfg.overlap_wgrad != 0: weight-gradient work on a lower-priority side stream (bit-identical results; round 3: +1.5 % in
-    // bf16 mode at B = 2048, -3 % in fp32 mode at B = 256); default: everything in order on the caller's stream.
-    const bool overlap = h->cfg.overlap_wgrad != 0;
-    if (overlap) RC(ensure_streams(h));
-    hipStream_t sd = overlap ? h->side : st;
-#define HIPRC(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cvae_set_error("%s: %s", #call, hipGetErrorString(e_)); return (int)e_; } } while (0)
-    // `ready k` = the gradient a weight-gradient kernel needs exists on the main stream; the side
-    // stream picks it up from there, so dW/db never delay the dgrad chain.
-    auto fork = [&](int idx) -> int {
-        if (!overlap) return 0;
-        HIPRC(hipEventRecord(h->ev_ready[idx], st));
-        HIPRC(hipStreamWaitEvent(sd, h->ev_ready[idx], 0));
-        return 0;
-    };
-    auto join = [&]() -> int {                          // side-stream work of this phase is complete on the caller's stream
-        if (!overlap) return 0;
-        HIPRC(hipEventRecord(h->ev_side, h->side));
-        HIPRC(hipStreamWaitEvent(st, h->ev_side, 0));
-        return 0;
-    };
-    if (phase_mask & 1) {
-    // decoder, last layer first
-    { ProbeArm pa(h, 1, 8);
-      RC(launch_d4_bwd(W, B, ws + w.o[3], d_recon, recon, P_(h->dec_w[4]), ws + w.dout4, ws + w.d_o[3],
-                       G_(h->dec_w[4]), G_(h->dec_b[4]), sc, st, io_bf16(h))); }
-    for (int i = 3; i >= 0; --i) {
-        const int l = 4 + i;
-        const float* in = i == 0 ? ws + w.h : ws + w.o[i - 1];
-        RC(fork(3 - i));
-        if (i == 0) {
-            { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, 4, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd)); }
-            { ProbeArm pa(h, 1, l);
-              if (use_bf16(h, 4)) RC(launch_conv_dgrad_bf16(4, W, bf16_mode(h), B, ws + w.d_o[0], ws + w.wpack, ws + w.d_h, ws + w.scratch, st));
-              else RC(launch_conv_dgrad(l, W, B, ws + w.d_o[0], P_(h->dec_w[0]), nullptr, ws + w.d_h, ws + w.scratch, st)); }
-        } else {
-            { ProbeArm pa(h, 2, l);
-              RC(launch_conv_up_wgrad(l, W, B, in, ws + w.d_o[i], G_(h->dec_w[i]), G_(h->dec_b[i]), scw, sd, use_bf16_wgrad(h, l))); }
-            { ProbeArm pa(h, 1, l);
-              if (use_bf16(h, l)) RC(launch_conv_up_dgrad_bf16(l, W, bf16_mode(h), B, ws + w.d_o[i], ws + w.wpack, ws + w.o[i - 1], ws + w.d_o[i - 1], st));
-              else RC(launch_conv_up_dgrad(l, W, B, ws + w.d_o[i], ws + w.wc[i - 1], ws + w.o[i - 1], ws + w.d_o[i - 1], sc, st)); }
-        }
-    }
-    // latent
-    RC(launch_decin_bwd(W, B, ws + w.zcat, ws + w.d_h, P_(h->di_w), G_(h->di_w), G_(h->di_b), ws + w.d_zcat, sc, st, io_bf16(h)));
-    RC(join());
-    }
-    if (phase_mask & 2)
-        RC(launch_fc_bwd(W, B, ws + w.a[3], P_(h->fc_w), ws + w.d_zcat, eps, logvar, d_mu, d_logvar, G_(h->fc_w),
-                         G_(h->fc_b), ws + w.d_a[3], sc, st, io_bf16(h)));
+    BwdCtx b{h, B, h->cfg.width, x, eps, params, logvar, recon, d_recon, d_mu, d_logvar, (float*)wsv, grads, carve(h, B), st};
+    RC(b.init());
+    if (phase_mask & 1) RC(b.decoder());
+    if (phase_mask & 2) RC(b.fc());
     // encoder
     for (int l = 3; l >= 0; --l) {
         if (!(phase_mask & (l == 3 ? 2 : 4))) continue;
-        // block 0: only the statistics pass runs here; E1's weight-gradient kernel applies the BatchNorm/pool/ReLU
-        // backward while it stages its tiles (there is no d_y[0]: nothing else would read it)
-        { ProbeArm pa(h, 3, l);
-          RC(launch_bn_pool_act_bwd(l, W, B, ws + w.y[l], ws + w.a[l], ws + w.d_a[l], ws + w.coef[l], P_(h->enc_g[l]),
-                                    l == 0 ? nullptr : ws + w.d_y[l], G_(h->enc_g[l]), G_(h->enc_be[l]), nullptr, sc, st, io_bf16(h))); }
-        RC(fork(7 - l));
-        if (l == 0) {
-            const float* fu[7] = {ws + w.y[0], ws + w.a[0], ws + w.d_a[0], ws + w.coef[0], bn_bwd_bcoef(0, W, B, sc),
-                                  P_(h->enc_w[0]), P_(h->enc_b[0])};
-            { ProbeArm pa(h, 2, 0);
-              RC(launch_e1_wgrad(W, B, x, nullptr, G_(h->enc_w[0]), G_(h->enc_b[0]), scw, sd, h->cfg.precision == 1, fu,
-                                 (h->cfg.precision == 1 && h->xp_ws == (const void*)ws && h->xp_B == B &&
-                                  conv_route(1, 0, W, false, B).family == E1_PACKED_FRAME) ? ws + w.xp : nullptr)); }
-        } else {
-            { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, l, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd)); }
-            { ProbeArm pa(h, 1, l);
-              if (use_bf16(h, l)) RC(launch_conv_dgrad_bf16(l, W, bf16_mode(h), B, ws + w.d_y[l], ws + w.wpack, ws + w.d_a[l - 1], ws + w.scratch, st));
-              else RC(launch_conv_dgrad(l, W, B, ws + w.d_y[l], P_(h->enc_w[l]), nullptr, ws + w.d_a[l - 1], nullptr, st)); }
-        }
-        if (l == 3 || l == 0) RC(join());               // end of phase 1 / phase 2
+        RC(b.bn(l, 0, nullptr, nullptr));
+        RC(b.block_grads(l));
+        if (l == 3 || l == 0) RC(b.join());             // end of phase 1 / phase 2
     }
-#undef HIPRC
     return 0;
 }
+
+// ---- staged step for cross-rank BatchNorm / loss statistics (include/cvae.h: cvae_sync_slot and the *_stage calls) ----
+int cvae_sync_slot(int32_t point, int64_t* offset, int64_t* count) {
+    if (point < 0 || point > 8 || !offset || !count) { cvae_set_error("cvae_sync_slot: point %d outside [0, 8] or null output", point); return CVAE_EINVAL; }
+    *offset = kSyncOff[point]; *count = kSyncCnt[point];
+    return 0;
+}
+
+static const char* kPassName[3] = {"cvae_forward_stage", "cvae_loss_stage", "cvae_backward_stage"};
+static const int kPassStages[3] = {5, 2, 5};
+// host-only checks of a staged call, before any device access: stage range, record, and the order of the step
+static int sync_check(cvae_handle h, int pass, int32_t B, const void* ws, const double* rec, int32_t stage) {
+    RC(check(h, B, ws));
+    if (!rec) { cvae_set_error("%s: null sync record", kPassName[pass]); return CVAE_EINVAL; }
+    if (stage < 0 || stage >= kPassStages[pass]) { cvae_set_error("%s: stage %d outside [0, %d]", kPassName[pass], stage, kPassStages[pass] - 1); return CVAE_EINVAL; }
+    if (pass == 0 && stage == 0) return 0;              // a new step may always start
+    const auto& s = h->sync;
+    if (s.pass != pass || s.next != stage || s.ws != ws || s.B != B || s.rec != rec) {
+        cvae_set_error("%s: stage %d out of order (the handle expects %s stage %d%s)", kPassName[pass], stage, kPassName[s.pass], s.next,
+                       s.ws ? " on the workspace, batch and record of the step in progress" : "; a step starts with cvae_forward_stage 0");
+        return CVAE_EINVAL;
+    }
+    return 0;
+}
+// after a stage: the next one the handle accepts (rc != 0: none but a new step)
+static int sync_advance(cvae_handle h, int pass, int32_t B, const void* ws, const double* rec, int32_t stage, int rc) {
+    auto& s = h->sync;
+    if (rc) { s.pass = 0; s.next = 0; s.ws = nullptr; s.rec = nullptr; s.B = 0; return rc; }
+    s.ws = ws; s.B = B; s.rec = rec;
+    if (stage + 1 < kPassStages[pass]) { s.pass = pass; s.next = stage + 1; }
+    else if (pass < 2) { s.pass = pass + 1; s.next = 0; }
+    else { s.pass = 0; s.next = 0; s.ws = nullptr; s.rec = nullptr; s.B = 0; }
+    return 0;
+}
+
+static int forward_stage(cvae_handle h, int32_t B, const float* x, const float* pred, const float* eps, const float* params,
+                         float* bn_state, float* mu, float* logvar, float* recon, void* wsv, double* sync, int32_t k, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)wsv;
+    const WsLayout w = carve(h, B);
+    const int W = h->cfg.width;
+    FwdCtx f{h, B, W, 1, x, params, bn_state, ws, wsv, w, st};
+    if (k == 0) RC(pack_bf16_weights(h, params, ws, w, st));
+    if (k > 0) {                                        // block k-1 from the summed record
+        RC(f.finish(k - 1, sync));
+        RC(f.apply(k - 1));
+    }
+    if (k < 4) {
+        RC(f.conv(k));
+        return f.stats(k, sync);
+    }
+    RC(launch_fc_fwd(W, B, ws + w.a[3], P_(h->fc_w), P_(h->fc_b), eps, pred, mu, logvar, ws + w.zcat, ws + w.scratch, st, io_bf16(h)));
+    if (!recon) return 0;
+    return cvae_decode(h, B, nullptr, params, recon, wsv, stream);
+}
+
+int cvae_forward_stage(cvae_handle h, int32_t B, const float* x, const float* pred, const float* eps, const float* params,
+                       float* bn_state, float* mu, float* logvar, float* recon, void* wsv, int32_t train, double* sync,
+                       int32_t stage, void* stream) {
+    RC(sync_check(h, 0, B, wsv, sync, stage));
+    if (train != 1) { cvae_set_error("cvae_forward_stage: train must be 1 (eval mode uses the running statistics: cvae_forward)"); return CVAE_EINVAL; }
+    const int rc = forward_stage(h, B, x, pred, eps, params, bn_state, mu, logvar, recon, wsv, sync, stage, stream);
+    return sync_advance(h, 0, B, wsv, sync, stage, rc);
+}
+
+int cvae_loss_stage(cvae_handle h, int32_t B, const float* x, const float* mu, const float* logvar, const float* recon,
+                    void* wsv, float* scalars, float* d_recon, float* d_mu, float* d_logvar, double* sync, int32_t stage,
+                    void* stream) {
+    RC(sync_check(h, 1, B, wsv, sync, stage));
+    if ((d_recon == nullptr) != (d_mu == nullptr) || (d_mu == nullptr) != (d_logvar == nullptr)) {
+        cvae_set_error("cvae_loss_stage: d_recon, d_mu, d_logvar must be all set or all null");
+        return CVAE_EINVAL;
+    }
+    float* ws = (float*)wsv;
+    const WsLayout w = carve(h, B);
+    int rc;
+    { ProbeArm pa(h, 3, 4);
+      rc = launch_msssim(h->cfg.width, B, recon, x, mu, logvar, ws + w.ms, scalars, d_recon, d_mu, d_logvar, (hipStream_t)stream,
+                         stage + 1, sync + kSyncOff[4], sync + kSyncCount); }
+    return sync_advance(h, 1, B, wsv, sync, stage, rc);
+}
+
+static int backward_stage(cvae_handle h, int32_t B, const float* x, const float* eps, const float* params, const float* logvar,
+                          const float* recon, const float* d_recon, const float* d_mu, const float* d_logvar, void* wsv,
+                          float* grads, double* sync, int32_t k, void* stream) {
+    BwdCtx b{h, B, h->cfg.width, x, eps, params, logvar, recon, d_recon, d_mu, d_logvar, (float*)wsv, grads, carve(h, B), (hipStream_t)stream};
+    RC(b.init());
+    const int l = 4 - k;                                // the block stage k applies (k >= 1); its statistics are point 8 - l
+    if (k == 0) {
+        RC(b.decoder());
+        RC(b.fc());
+    } else {
+        RC(b.bn(l, 2, sync + kSyncOff[8 - l], sync + kSyncCount));
+        RC(b.block_grads(l));
+    }
+    if (k < 4) RC(b.bn(3 - k, 1, sync + kSyncOff[5 + k], nullptr));      // the next block's statistics -> point 5 + k
+    return b.join();
+}
+
+int cvae_backward_stage(cvae_handle h, int32_t B, const float* x, const float* pred, const float* eps, const float* params,
+                        const float* logvar, const float* recon, const float* d_recon, const float* d_mu,
+                        const float* d_logvar, void* wsv, float* grads, double* sync, int32_t stage, void* stream) {
+    (void)pred;
+    RC(sync_check(h, 2, B, wsv, sync, stage));
+    const int rc = backward_stage(h, B, x, eps, params, logvar, recon, d_recon, d_mu, d_logvar, wsv, grads, sync, stage, stream);
+    return sync_advance(h, 2, B, wsv, sync, stage, rc);
+}
+#undef HIPRC
 
 int cvae_adam_step(cvae_handle h, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                    int32_t step, float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {

@@ -64,6 +64,34 @@ __global__ __launch_bounds__(256) void bn_fwd_reduce_kernel(const float* __restr
     }
 }
 
+// (S, Q, M) of channel c -> coef[c] = {scale, shift, mean, invstd} and the running-stat update (train), or coef from the
+// running stats (eval).  Shared by the single-rank finalize and the finish step of the cross-rank path.
+__device__ __forceinline__ void bn_fwd_coef(int c, double S, double Q, double M, double N, const float* __restrict__ gamma,
+                                            const float* __restrict__ beta, float* __restrict__ run_mean,
+                                            float* __restrict__ run_var, float* __restrict__ coef, int train) {
+    float mean, var;
+    if (train) {
+        const double mu = S / N;
+        double v = (M + Q - S * S / N) / N;          // biased variance
+        if (v < 0.0) v = 0.0;
+        mean = (float)mu; var = (float)v;
+        const float uvar = (float)(v * N / (N - 1.0));
+        {   // two roundings, never an fma: the value must not depend on how the compiler contracts it in each kernel
+#pragma clang fp contract(off)
+            run_mean[c] = 0.9f * run_mean[c] + 0.1f * mean;
+            run_var[c] = 0.9f * run_var[c] + 0.1f * uvar;
+        }
+    } else {
+        mean = run_mean[c]; var = run_var[c];
+    }
+    const float invstd = 1.0f / sqrtf(var + 1e-5f);
+    const float scale = gamma[c] * invstd;
+    coef[c * 4 + 0] = scale;
+    coef[c * 4 + 1] = beta[c] - mean * scale;
+    coef[c * 4 + 2] = mean;
+    coef[c * 4 + 3] = invstd;
+}
+
 // stage B: merge the RA chunk sums (fp64), emit coef[c] = {scale, shift, mean, invstd}, update running
 // stats.  32 lanes per channel (RA <= 32), two channels per wave.
 __global__ __launch_bounds__(64) void bn_fwd_finalize_kernel(const double* __restrict__ mid, int RA, int C, double N,
@@ -76,23 +104,34 @@ __global__ __launch_bounds__(64) void bn_fwd_finalize_kernel(const double* __res
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) { S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64); M += __shfl_xor(M, o, 64); }
     if (r != 0) return;
-    float mean, var;
-    if (train) {
-        const double mu = S / N;
-        double v = (M + Q - S * S / N) / N;          // biased variance
-        if (v < 0.0) v = 0.0;
-        mean = (float)mu; var = (float)v;
-        run_mean[c] = 0.9f * run_mean[c] + 0.1f * mean;
-        run_var[c] = 0.9f * run_var[c] + 0.1f * (float)(v * N / (N - 1.0));
-    } else {
-        mean = run_mean[c]; var = run_var[c];
-    }
-    const float invstd = 1.0f / sqrtf(var + 1e-5f);
-    const float scale = gamma[c] * invstd;
-    coef[c * 4 + 0] = scale;
-    coef[c * 4 + 1] = beta[c] - mean * scale;
-    coef[c * 4 + 2] = mean;
-    coef[c * 4 + 3] = invstd;
+    bn_fwd_coef(c, S, Q, M, N, gamma, beta, run_mean, run_var, coef, train);
+}
+
+// Cross-rank path, record step: the same merge of the RA chunk sums, in the same order, written to this layer's slot of the
+// sync record as rec[c] = S, rec[C + c] = Q, rec[2C + c] = M (fp64).  Every term is a sum over tiles, so the records of
+// several ranks add up to the record of their union.  count != null: also *count = this rank's image count.
+__global__ __launch_bounds__(64) void bn_fwd_record_kernel(const double* __restrict__ mid, int RA, int C, double* __restrict__ rec,
+                                                           double* __restrict__ count, double images) {
+    const int c = blockIdx.x * 2 + (threadIdx.x >> 5), r = threadIdx.x & 31;
+    double S = 0.0, Q = 0.0, M = 0.0;
+    if (r < RA) { S = mid[(size_t)r * 3 * C + c]; Q = mid[(size_t)r * 3 * C + C + c]; M = mid[(size_t)r * 3 * C + 2 * C + c]; }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) { S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64); M += __shfl_xor(M, o, 64); }
+    if (r != 0) return;
+    rec[c] = S; rec[C + c] = Q; rec[2 * C + c] = M;
+    if (count && c == 0) *count = images;
+}
+
+// Cross-rank path, finish step: coef and the running statistics from the summed record; N = (summed image count) * H * H,
+// so the running variance takes the global N / (N - 1).  One thread per channel.
+__global__ __launch_bounds__(64) void bn_fwd_finish_kernel(const double* __restrict__ rec, const double* __restrict__ count, int C, int H,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ run_mean, float* __restrict__ run_var,
+                                                           float* __restrict__ coef) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    const double N = count[0] * H * H;
+    bn_fwd_coef(c, rec[c], rec[C + c], rec[2 * C + c], N, gamma, beta, run_mean, run_var, coef, 1);
 }
 
 __device__ __forceinline__ float act_fwd(float v, int act) { return act ? tanhf(v) : fmaxf(v, 0.f); }
@@ -260,9 +299,12 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_relu_kernel(const float* __r
 }
 
 // rows[r] = [sum g | sum g*xhat] partials (R <= 64 rows left by launch_col_reduce_partial), summed
-// here in fixed order -> dgamma, dbeta, bcoef = (s1/N, s2/N)
+// here in fixed order -> dgamma, dbeta, bcoef = (s1/N, s2/N).  REC (cross-rank path): rec[c] = s1, rec[C + c] = s2
+// (fp64) instead of bcoef; dgamma / dbeta stay this rank's own (the gradient all-reduce sums them).
+template <bool REC>
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ rows, int R, int64_t stride, int C, float invN,
-                                                              float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ bcoef) {
+                                                              float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ bcoef,
+                                                              double* __restrict__ rec) {
     // 16 lanes per channel: lane q adds rows q, q+16, q+32, q+48, then a fixed xor-shuffle tree
     const int c = blockIdx.x * 16 + (threadIdx.x >> 4), q = threadIdx.x & 15;
     float s1 = 0.f, s2 = 0.f;
@@ -270,7 +312,23 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
         for (int r = q; r < R; r += 16) { s1 += rows[(size_t)r * stride + c]; s2 += rows[(size_t)r * stride + C + c]; }
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
-    if (c < C && q == 0) { dgamma[c] = s2; dbeta[c] = s1; bcoef[c * 2] = s1 * invN; bcoef[c * 2 + 1] = s2 * invN; }
+    if (c < C && q == 0) {
+        dgamma[c] = s2; dbeta[c] = s1;
+        if (REC) { rec[c] = (double)s1; rec[C + c] = (double)s2; }
+        else { bcoef[c * 2] = s1 * invN; bcoef[c * 2 + 1] = s2 * invN; }
+    }
+}
+
+// cross-rank path: bcoef from the summed record with the global 1/N, N = (summed image count) * H * H.  invN is the
+// correctly rounded fp32 1 / (float)N, as the single-rank launcher computes it on the host (a double quotient of two
+// floats rounds to the same float: 53 >= 2 * 24 + 2 bits), so that one rank reproduces it bit for bit.
+__global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const double* __restrict__ rec, const double* __restrict__ count, int C, int H,
+                                                            float* __restrict__ bcoef) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float invN = (float)(1.0 / (double)(float)(count[0] * H * H));
+    bcoef[c * 2] = (float)rec[c] * invN;
+    bcoef[c * 2 + 1] = (float)rec[C + c] * invN;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -461,8 +519,8 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_relu_bf16_kernel(const float
 static constexpr int BN_RA = 32;
 int64_t bn_fwd_ws_floats(int layer, int width) { (void)width; return (int64_t)2 * BN_RA * 3 * kLayers[layer].cout; }
 
-int launch_bn_fwd_finalize(int layer, int width, int B, const float* bnpart, const float* gamma, const float* beta,
-                           float* run_mean, float* run_var, float* coef, float* ws, int train, hipStream_t st, int tilesPerPartial) {
+// stage A of the forward statistics: the RA chunk rows of fp64 (S, Q, M) in `ws`; returns RA
+static int bn_fwd_reduce(int layer, int width, int B, const float* bnpart, float* ws, hipStream_t st, int tilesPerPartial, int* RA_out) {
     const BnGeom g = bn_geom(layer, width);
     int imgs, ppi, tpi;
     part_geom(layer, g.H, &imgs, &ppi, &tpi);
@@ -475,16 +533,45 @@ int launch_bn_fwd_finalize(int layer, int width, int B, const float* bnpart, con
         else imgs *= T;                                                 // T x imgs whole images
     }
     double* mid = reinterpret_cast<double*>(ws);
+    const int tpb = cdiv(numTiles, BN_RA);
+    const int RA = cdiv(numTiles, tpb);
+    hipLaunchKernelGGL(bn_fwd_reduce_kernel, dim3(g.C / 32, RA), dim3(256), 0, st, bnpart, numTiles, g.C, B, imgs,
+                       ppi, tpi, mid, tpb);
+    CVAE_CHECK_LAUNCH();
+    *RA_out = RA;
+    return 0;
+}
+
+int launch_bn_fwd_finalize(int layer, int width, int B, const float* bnpart, const float* gamma, const float* beta,
+                           float* run_mean, float* run_var, float* coef, float* ws, int train, hipStream_t st, int tilesPerPartial) {
+    const BnGeom g = bn_geom(layer, width);
+    double* mid = reinterpret_cast<double*>(ws);
     int RA = 0;
-    if (train) {
-        const int tpb = cdiv(numTiles, BN_RA);
-        RA = cdiv(numTiles, tpb);
-        hipLaunchKernelGGL(bn_fwd_reduce_kernel, dim3(g.C / 32, RA), dim3(256), 0, st, bnpart, numTiles, g.C, B, imgs,
-                           ppi, tpi, mid, tpb);
-        CVAE_CHECK_LAUNCH();
-    }
+    if (train) { int rc = bn_fwd_reduce(layer, width, B, bnpart, ws, st, tilesPerPartial, &RA); if (rc) return rc; }
     hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(g.C / 2), dim3(64), 0, st, mid, RA, g.C,
                        (double)B * g.H * g.H, gamma, beta, run_mean, run_var, coef, train);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+// cross-rank path (train mode): this rank's (S, Q, M) into rec[0, 3C) (+ its image count into *count when count != null) ...
+int launch_bn_fwd_record(int layer, int width, int B, const float* bnpart, float* ws, hipStream_t st, int tilesPerPartial,
+                         double* rec, double* count) {
+    const BnGeom g = bn_geom(layer, width);
+    int RA = 0;
+    { int rc = bn_fwd_reduce(layer, width, B, bnpart, ws, st, tilesPerPartial, &RA); if (rc) return rc; }
+    hipLaunchKernelGGL(bn_fwd_record_kernel, dim3(g.C / 2), dim3(64), 0, st, reinterpret_cast<const double*>(ws), RA, g.C,
+                       rec, count, (double)B);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+// ... and, once the caller has summed rec and count over the ranks, coef + running statistics from the sums
+int launch_bn_fwd_finish(int layer, int width, const double* rec, const double* count, const float* gamma, const float* beta,
+                         float* run_mean, float* run_var, float* coef, hipStream_t st) {
+    const BnGeom g = bn_geom(layer, width);
+    hipLaunchKernelGGL(bn_fwd_finish_kernel, dim3(cdiv(g.C, 64)), dim3(64), 0, st, rec, count, g.C, g.H, gamma, beta,
+                       run_mean, run_var, coef);
     CVAE_CHECK_LAUNCH();
     return 0;
 }
@@ -529,9 +616,12 @@ const float* bn_bwd_bcoef(int layer, int width, int B, const float* ws) {
 
 // dy == nullptr: statistics only (dgamma, dbeta and the (k1, k2) pair at bn_bwd_bcoef(ws)); the caller's next kernel
 // applies the backward itself (block 0: launch_e1_wgrad's fused staging).
+// stage (cross-rank path): 0 = everything above; 1 = the statistics only, dgamma / dbeta plus this rank's (sum g, sum g*xhat)
+// into rec[0, 2C) instead of (k1, k2); 2 = (k1, k2) from the summed rec and *count (the summed image count), then the
+// apply pass (dy != null) as stage 0 runs it.  Stages 1 and 2 run on the same ws, batch and tensors, in that order.
 int launch_bn_pool_act_bwd(int layer, int width, int B, const float* y, const float* a, const float* da,
                            const float* coef, const float* gamma, float* dy, float* dgamma, float* dbeta,
-                           float* dbias, float* ws, hipStream_t st, bool bf16io) {
+                           float* dbias, float* ws, hipStream_t st, bool bf16io, int stage, double* rec, const double* count) {
     (void)gamma;
     const BnGeom g = bn_geom(layer, width);
     const int64_t totalPx = (int64_t)B * (g.H / 2) * (g.H / 2);
@@ -542,15 +632,22 @@ int launch_bn_pool_act_bwd(int layer, int width, int B, const float* y, const fl
     float* red = bcoef + 2 * g.C;
     float* crws = red + 2 * g.C;
     const float invN = 1.0f / (float)((double)B * g.H * g.H);
-    if (bf16io && g.act) hipLaunchKernelGGL((bn_bwd_bf16_kernel<1, 0>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, nullptr, nullptr, part, g.C, g.H, totalPx, ppb);
-    else if (bf16io) hipLaunchKernelGGL(bn_bwd_stats_relu_bf16_kernel, dim3(nblk), dim3(256), 0, st, a, da, coef, part, g.C, totalPx, ppb, y, g.H);
-    else if (g.act) hipLaunchKernelGGL((bn_bwd_kernel<1, 0>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, nullptr, nullptr, part, g.C, g.H, totalPx, ppb);
-    else hipLaunchKernelGGL(bn_bwd_stats_relu_kernel, dim3(nblk), dim3(256), 0, st, a, da, coef, part, g.C, totalPx, ppb, y, g.H);
-    CVAE_CHECK_LAUNCH();
-    const float* rows; int R; int64_t rstride;
-    { int rc = launch_col_reduce_partial(part, nblk, 2 * g.C, 2 * g.C, crws, st, &rows, &R, &rstride); if (rc) return rc; }
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(g.C, 16)), dim3(256), 0, st, rows, R, rstride, g.C, invN, dgamma, dbeta, bcoef);
-    CVAE_CHECK_LAUNCH();
+    if (stage != 2) {
+        if (bf16io && g.act) hipLaunchKernelGGL((bn_bwd_bf16_kernel<1, 0>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, nullptr, nullptr, part, g.C, g.H, totalPx, ppb);
+        else if (bf16io) hipLaunchKernelGGL(bn_bwd_stats_relu_bf16_kernel, dim3(nblk), dim3(256), 0, st, a, da, coef, part, g.C, totalPx, ppb, y, g.H);
+        else if (g.act) hipLaunchKernelGGL((bn_bwd_kernel<1, 0>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, nullptr, nullptr, part, g.C, g.H, totalPx, ppb);
+        else hipLaunchKernelGGL(bn_bwd_stats_relu_kernel, dim3(nblk), dim3(256), 0, st, a, da, coef, part, g.C, totalPx, ppb, y, g.H);
+        CVAE_CHECK_LAUNCH();
+        const float* rows; int R; int64_t rstride;
+        { int rc = launch_col_reduce_partial(part, nblk, 2 * g.C, 2 * g.C, crws, st, &rows, &R, &rstride); if (rc) return rc; }
+        if (stage == 1) hipLaunchKernelGGL(bn_bwd_finalize_kernel<true>, dim3(cdiv(g.C, 16)), dim3(256), 0, st, rows, R, rstride, g.C, invN, dgamma, dbeta, nullptr, rec);
+        else hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(cdiv(g.C, 16)), dim3(256), 0, st, rows, R, rstride, g.C, invN, dgamma, dbeta, bcoef, nullptr);
+        CVAE_CHECK_LAUNCH();
+        if (stage == 1) return 0;
+    } else {
+        hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3(cdiv(g.C, 256)), dim3(256), 0, st, rec, count, g.C, g.H, bcoef);
+        CVAE_CHECK_LAUNCH();
+    }
     if (!dy) {
         if (dbias) { cvae_set_error("bn_bwd: dbias needs the apply pass (dy)"); return -2; }
         return 0;

@@ -255,13 +255,21 @@ int bn_num_tiles(int layer, int width, int B);
 int launch_bn_fwd_finalize(int layer, int width, int B, const float* bnpart, const float* gamma,
                            const float* beta, float* run_mean, float* run_var, float* coef,
                            float* ws, int train, hipStream_t st, int tilesPerPartial = 1);
+// cross-rank BatchNorm statistics (api.hip's staged entry points): this rank's fp64 (S, Q, M) record of the layer
+// (+ its image count) ...
+int launch_bn_fwd_record(int layer, int width, int B, const float* bnpart, float* ws, hipStream_t st, int tilesPerPartial,
+                         double* rec, double* count);
+// ... and coef + running statistics from the record summed over the ranks (count = the summed image count)
+int launch_bn_fwd_finish(int layer, int width, const double* rec, const double* count, const float* gamma, const float* beta,
+                         float* run_mean, float* run_var, float* coef, hipStream_t st);
 int64_t bn_fwd_ws_floats(int layer, int width);
 int launch_bn_pool_act_fwd(int layer, int width, int B, const float* y, const float* coef, float* a,
                            hipStream_t st, bool bf16io = false);
 int64_t bn_bwd_ws_floats(int layer, int width, int B);
 int launch_bn_pool_act_bwd(int layer, int width, int B, const float* y, const float* a,
                            const float* da, const float* coef, const float* gamma, float* dy,
-                           float* dgamma, float* dbeta, float* dbias, float* ws, hipStream_t st, bool bf16io = false);
+                           float* dgamma, float* dbeta, float* dbias, float* ws, hipStream_t st, bool bf16io = false,
+                           int stage = 0, double* rec = nullptr, const double* count = nullptr);     // stage 1 / 2: cross-rank split (bn.hip)
 // fc.hip
 int64_t fc_ws_floats(int width, int B);
 int launch_fc_fwd(int width, int B, const float* flat, const float* wfc, const float* bfc,
@@ -279,7 +287,8 @@ int launch_fc_bwd(int width, int B, const float* flat, const float* wfc, const f
 int64_t msssim_ws_floats(int width, int B);
 int launch_msssim(int width, int B, const float* img1, const float* img2, const float* mu,
                   const float* logvar, float* ws, float* scalars, float* d_img1, float* d_mu,
-                  float* d_logvar, hipStream_t st);
+                  float* d_logvar, hipStream_t st,
+                  int stage = 0, double* rec = nullptr, const double* images = nullptr);      // stage 1 / 2: cross-rank split
 // critic.hip
 int critic_param_count();
 int launch_critic_fwd(int width, int B, const float* x, const float* critic_params, float* pred, hipStream_t st);

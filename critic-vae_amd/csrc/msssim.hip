@@ -687,8 +687,44 @@ struct MsFinArgs {
     float* scalars;          // CVAE_N_SCALARS
     float* coef;             // [5] per-pixel gradient coefficient of each level's map
     float* d_mu; float* d_logvar;
+    double* rec;             // cross-rank path: the 11 sums (record mode writes them, the finish step reads the summed ones)
+    const double* images;    // cross-rank path, finish step: the summed image count (replaces B and count[])
 };
 
+// lanes 0-4: ssim_l, lanes 5-9: cs_l, lane 10: KLD sum — every lane finishes its own scalar from its fp64 sum t
+// (same operations and order as a serial evaluation), shuffles bring them together.  cnt: this lane's level count
+// B*3*S_l*S_l; Bd: the image count of the KLD mean.  Called by lanes 0..63 of one wave.
+__device__ __forceinline__ void ms_finish_scalars(int lane, double t, double cnt, double Bd, float* scalars, float* coef) {
+    const int l = lane % 5;
+    const float kw = 0.001f;
+    const float wts[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
+    const float meanf = (float)(t / cnt);
+    const float pw = powf(meanf, wts[l]);
+    const float p2 = __shfl(pw, 4, 64);
+    float out = 1.0f;
+    for (int q = 0; q < 4; ++q) out *= __shfl(pw, 5 + q, 64) * p2;              // vae_nets.py:243-246
+    const float recon = 1.0f - out;
+    const double k = __shfl(t, 10, 64);
+    const float kld = Bd > 0 ? (float)(-0.5 * k / Bd) * kw : 0.0f;
+    if (lane == 0) { scalars[0] = recon + kld; scalars[1] = recon; scalars[2] = kld; }
+    if (lane < 5) scalars[3 + lane] = meanf;
+    else if (lane < 10) scalars[8 + l] = meanf;
+    else if (lane < 13) scalars[13 + lane - 10] = 0.f;
+    // autograd of the reference also differentiates the terms `prod(pow1[:-1] * pow2[-1])` never uses — mssim ** weights and
+    // mcs ** weights are evaluated for all five levels (vae_nets.py:243-244) — with an incoming gradient of exactly 0:
+    // 0 * w * x^(w-1), which is 0 for x > 0 but NaN for x < 0 (fractional power) and for x == 0 (0 * inf).  A negative
+    // ssim level 0..3 (dark real frames against an untrained decoder) or cs level 4 therefore turns EVERY gradient that passes
+    // through recon into NaN while the loss itself stays finite (tests/golden/step_real_b68.npz, "seed0/").  Same arithmetic
+    // here: the poison term is added to the level's coefficient.
+    const float poison = 0.0f * (wts[l] * powf(meanf, wts[l] - 1.0f));          // lanes 0-4: ssim_l, lanes 5-9: cs_l
+    const float p_ssim = __shfl(poison, l, 64), p_cs4 = __shfl(poison, 9, 64);
+    if (lane >= 5 && lane < 9) coef[l] = (float)((double)(-out * wts[l] / meanf) / cnt) + p_ssim;
+    if (lane == 4) coef[4] = (float)((double)(-out * 4.0f * wts[4] / meanf) / cnt) + p_cs4;
+}
+
+// REC (cross-rank path): no d_mu / d_logvar (a.d_mu is null), and the last arriver writes its 11 sums to a.rec instead of
+// finishing — msssim_finish_kernel finishes from the sums of all ranks
+template <bool REC>
 __global__ __launch_bounds__(256) void msssim_finalize_kernel(MsFinArgs a) {
     __shared__ double red[11][4];
     __shared__ unsigned last_flag;
@@ -719,36 +755,28 @@ __global__ __launch_bounds__(256) void msssim_finalize_kernel(MsFinArgs a) {
     if (threadIdx.x < 11) a.slab[blockIdx.x * 11 + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
     if (!wg_arrive_last(a.ticket, MS_NF, &last_flag)) return;
     if (threadIdx.x < 64) {
-        // lanes 0-4: ssim_l, lanes 5-9: cs_l, lane 10: KLD sum — every lane finishes its own scalar
-        // (same operations and order as a serial evaluation), shuffles bring them together
-        const int lane = threadIdx.x, l = lane % 5;
-        const float wts[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
+        const int lane = threadIdx.x;
         double t = 0.0;
         if (lane < 11) for (int g = 0; g < MS_NF; ++g) t += a.slab[g * 11 + lane];
-        const double cnt = a.count[l];
-        const float meanf = (float)(t / cnt);
-        const float pw = powf(meanf, wts[l]);
-        const float p2 = __shfl(pw, 4, 64);
-        float out = 1.0f;
-        for (int q = 0; q < 4; ++q) out *= __shfl(pw, 5 + q, 64) * p2;              // vae_nets.py:243-246
-        const float recon = 1.0f - out;
-        const double k = __shfl(t, 10, 64);
-        const float kld = a.B > 0 ? (float)(-0.5 * k / (double)a.B) * kw : 0.0f;
-        if (lane == 0) { a.scalars[0] = recon + kld; a.scalars[1] = recon; a.scalars[2] = kld; }
-        if (lane < 5) a.scalars[3 + lane] = meanf;
-        else if (lane < 10) a.scalars[8 + l] = meanf;
-        else if (lane < 13) a.scalars[13 + lane - 10] = 0.f;
-        // autograd of the reference also differentiates the terms `prod(pow1[:-1] * pow2[-1])` never uses — mssim ** weights and
-        // mcs ** weights are evaluated for all five levels (vae_nets.py:243-244) — with an incoming gradient of exactly 0:
-        // 0 * w * x^(w-1), which is 0 for x > 0 but NaN for x < 0 (fractional power) and for x == 0 (0 * inf).  A negative
-        // ssim level 0..3 (dark real frames against an untrained decoder) or cs level 4 therefore turns EVERY gradient that passes
-        // through recon into NaN while the loss itself stays finite (tests/golden/step_real_b68.npz, "seed0/").  Same arithmetic
-        // here: the poison term is added to the level's coefficient.
-        const float poison = 0.0f * (wts[l] * powf(meanf, wts[l] - 1.0f));          // lanes 0-4: ssim_l, lanes 5-9: cs_l
-        const float p_ssim = __shfl(poison, l, 64), p_cs4 = __shfl(poison, 9, 64);
-        if (lane >= 5 && lane < 9) a.coef[l] = (float)((double)(-out * wts[l] / meanf) / cnt) + p_ssim;
-        if (lane == 4) a.coef[4] = (float)((double)(-out * 4.0f * wts[4] / meanf) / cnt) + p_cs4;
+        if (REC) { if (lane < 11) a.rec[lane] = t; return; }
+        ms_finish_scalars(lane, t, a.count[lane % 5], (double)a.B, a.scalars, a.coef);
     }
+}
+
+// cross-rank path, finish step: scalars and coef from the summed 11 sums with the global counts 3 * B_g * S_l^2, and d_mu /
+// d_logvar of this rank's a.B rows with the global 1 / B_g (B_g = *a.images).  Grid: ceil(a.B * 32 / 256) workgroups (>= 1).
+__global__ __launch_bounds__(256) void msssim_finish_kernel(MsFinArgs a, int width) {
+    const double Bg = a.images[0];
+    const float kw = 0.001f, invB = Bg > 0 ? 1.0f / (float)Bg : 0.f;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (a.d_mu && i < a.B * 32) {
+        const float m = a.mu[i], lv = a.logvar[i], e = expf(lv);
+        a.d_mu[i] = kw * m * invB; a.d_logvar[i] = kw * 0.5f * (e - 1.0f) * invB;
+    }
+    if (blockIdx.x != 0 || threadIdx.x >= 64) return;
+    const int lane = threadIdx.x, S = width >> (lane % 5);
+    const double t = lane < 11 ? a.rec[lane] : 0.0;
+    ms_finish_scalars(lane, t, 3.0 * Bg * S * S, Bg, a.scalars, a.coef);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -834,8 +862,12 @@ static int ms_fwd(const MsFwdArgs& a, hipStream_t st) {
     return 0;
 }
 
+// stage (cross-rank path): 0 = the whole loss; 1 = pyramid + partial sums, the 11 fp64 sums into rec[0, 11) (no
+// scalars, no gradients yet); 2 = finish from the summed rec and *images (the summed image count): scalars, coef,
+// d_mu / d_logvar of this rank's rows, then the backward pass.  Stages 1 and 2 run on the same ws and tensors, in order.
 int launch_msssim(int width, int B, const float* img1, const float* img2, const float* mu, const float* logvar,
-                  float* ws, float* scalars, float* d_img1, float* d_mu, float* d_logvar, hipStream_t st) {
+                  float* ws, float* scalars, float* d_img1, float* d_mu, float* d_logvar, hipStream_t st,
+                  int stage, double* rec, const double* images) {
     if (width != 64 && width != 128) { cvae_set_error("msssim: width %d unsupported", width); return -2; }
     int rc = 0;
     const MsWin win = make_window();
@@ -846,7 +878,7 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
     const float* lx[5]; const float* ly[5];
     lx[0] = img1; ly[0] = img2;
     for (int l = 1; l < 5; ++l) { lx[l] = ws + w.pyrx[l]; ly[l] = ws + w.pyry[l]; }
-    for (int l = 0; l < 5; ++l) {
+    for (int l = 0; l < 5 && stage != 2; ++l) {
         const bool last = l == 4;
         MsFwdArgs a{lx[l], ly[l], last ? nullptr : ws + w.pyrx[l + 1], last ? nullptr : ws + w.pyry[l + 1],
                     grad ? ws + w.F[l] : nullptr, ws + w.part[l], l == 0 ? ticket : nullptr, P, win};
@@ -868,9 +900,12 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
     f.mu = mu; f.logvar = logvar; f.B = mu ? B : 0; f.scalars = scalars; f.coef = ws + w.coef;
     f.slab = reinterpret_cast<double*>(ws + w.slab); f.ticket = ticket;
     f.d_mu = d_mu; f.d_logvar = d_logvar;
-    hipLaunchKernelGGL(msssim_finalize_kernel, dim3(MS_NF), dim3(256), 0, st, f);
+    f.rec = rec; f.images = images;
+    if (stage == 0) hipLaunchKernelGGL(msssim_finalize_kernel<false>, dim3(MS_NF), dim3(256), 0, st, f);
+    else if (stage == 1) { f.d_mu = f.d_logvar = nullptr; hipLaunchKernelGGL(msssim_finalize_kernel<true>, dim3(MS_NF), dim3(256), 0, st, f); }
+    else hipLaunchKernelGGL(msssim_finish_kernel, dim3(cdiv(f.B * 32, 256) > 1 ? cdiv(f.B * 32, 256) : 1), dim3(256), 0, st, f, width);
     CVAE_CHECK_LAUNCH();
-    if (!grad) return 0;
+    if (!grad || stage == 1) return 0;
     MsBwdArgs b{};
     for (int l = 0; l < 5; ++l) b.F[l] = ws + w.F[l];
     b.coef = ws + w.coef; b.dx = d_img1; b.total4 = (int64_t)P * width * width / 4;

@@ -12,6 +12,8 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVAE_LIB") or os.path.join(_HERE, "libcvae_hip.so")     # CVAE_LIB: A/B another build of the same sources
 N_SCALARS = 16
+SYNC_DOUBLES = 2412      # CVAE_SYNC_DOUBLES: the fp64 record of the staged (global-statistics) step
+SYNC_POINTS = 9
 
 
 class CvaeError(RuntimeError):
@@ -61,6 +63,10 @@ _SIGS = {
     "cvae_backward": (C.c_int, [_p, _i32] + [_p] * 12),
     "cvae_backward_phases": (C.c_int, [_p, _i32] + [_p] * 11 + [_i32, _p]),
     "cvae_grad_bucket": (C.c_int, [_p, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "cvae_sync_slot": (C.c_int, [_i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "cvae_forward_stage": (C.c_int, [_p, _i32] + [_p] * 9 + [_i32, _p, _i32, _p]),
+    "cvae_loss_stage": (C.c_int, [_p, _i32] + [_p] * 10 + [_i32, _p]),
+    "cvae_backward_stage": (C.c_int, [_p, _i32] + [_p] * 12 + [_i32, _p]),
     "cvae_scale_loss_grads": (C.c_int, [_p, _i32] + [_p] * 8),
     "cvae_adam_step": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _f, _f, _f, _f, _f, _p]),
     "cvae_grads_to_bf16": (C.c_int, [_p, _p, _p, _i64, _p]),
@@ -113,6 +119,23 @@ def _ptr(t):
     assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), \
         f"need a contiguous fp32 device tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}"
     return t.data_ptr()
+
+
+def _ptr64(t):
+    if t is None:
+        return None
+    assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous(), \
+        f"need a contiguous fp64 device tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}"
+    return t.data_ptr()
+
+
+def sync_slot(point):
+    """(offset, count) of sync point `point` (0..8) in the fp64 record of the staged step (include/cvae.h)."""
+    lib = load()
+    off, n = C.c_int64(), C.c_int64()
+    if lib.cvae_sync_slot(point, C.byref(off), C.byref(n)) != 0:
+        raise CvaeError(f"cvae_sync_slot: {lib.cvae_last_error().decode()}")
+    return off.value, n.value
 
 
 def _stream():
@@ -220,6 +243,26 @@ class Handle:
         off, n = C.c_int64(), C.c_int64()
         self._check(self.lib.cvae_grad_bucket(self.h, phase, C.byref(off), C.byref(n)))
         return off.value, n.value
+
+    # ---- the staged step (global-batch statistics across ranks; include/cvae.h) ----
+    # `sync`: a contiguous fp64 device tensor of SYNC_DOUBLES values.  After forward stages 0..3, loss stage 0 and backward
+    # stages 0..3, the caller sums slot sync_slot(point) over the ranks (in place) before the next stage.
+    sync_slot = staticmethod(sync_slot)
+
+    def forward_stage(self, stage, B, x, pred, eps, params, bn_state, mu, logvar, recon, ws, sync, train=True):
+        self._check(self.lib.cvae_forward_stage(self.h, B, _ptr(x), _ptr(pred), _ptr(eps), _ptr(params), _ptr(bn_state),
+                                                _ptr(mu), _ptr(logvar), _ptr(recon), _ptr(ws), int(train), _ptr64(sync),
+                                                stage, _stream()))
+
+    def loss_stage(self, stage, B, x, mu, logvar, recon, ws, scalars, d_recon, d_mu, d_logvar, sync):
+        self._check(self.lib.cvae_loss_stage(self.h, B, _ptr(x), _ptr(mu), _ptr(logvar), _ptr(recon), _ptr(ws),
+                                             _ptr(scalars), _ptr(d_recon), _ptr(d_mu), _ptr(d_logvar), _ptr64(sync),
+                                             stage, _stream()))
+
+    def backward_stage(self, stage, B, x, pred, eps, params, logvar, recon, d_recon, d_mu, d_logvar, ws, grads, sync):
+        self._check(self.lib.cvae_backward_stage(self.h, B, _ptr(x), _ptr(pred), _ptr(eps), _ptr(params), _ptr(logvar),
+                                                 _ptr(recon), _ptr(d_recon), _ptr(d_mu), _ptr(d_logvar), _ptr(ws),
+                                                 _ptr(grads), _ptr64(sync), stage, _stream()))
 
     def adam_step(self, params, grads, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0):
         self._check(self.lib.cvae_adam_step(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(),

@@ -19,6 +19,7 @@ import torch
 
 from . import params as P
 from . import synth
+from .lib import SYNC_DOUBLES, SYNC_POINTS
 from .nets import VariationalAutoencoder
 
 
@@ -73,14 +74,18 @@ class FusedTrainer:
     """One training step = forward + loss + backward + all-reduce + Adam on flat buffers."""
 
     def __init__(self, vae, lr=P.lr, betas=P.adam_betas, eps=P.adam_eps, process_group=None, world_size=1,
-                 overlap=None, reduce_dtype=None, sync=True):
+                 overlap=None, reduce_dtype=None, sync=True, global_stats=None):
         """Construction with world_size > 1 is a COLLECTIVE (sync_replicas: five broadcasts from rank 0) unless
         sync=False.
         overlap: all-reduce the gradient in three buckets while backward still runs (default for
         world_size > 1; CVAE_DP_OVERLAP=0 or overlap=False = one all-reduce after backward).
         reduce_dtype: "f32" (default; the contract of SURVEY 8e: reduced gradient == mean of the shard gradients
         within 1e-4) or "bf16" (CVAE_DP_REDUCE=bf16): the wire format of the all-reduce is bf16 — half the bytes,
-        the summed gradient carries a relative rounding of 2^-9 per rank, optimizer state stays fp32."""
+        the summed gradient carries a relative rounding of 2^-9 per rank, optimizer state stays fp32.
+        global_stats: global-batch semantics across ranks (CVAE_DP_GLOBAL_STATS=1; default off): the step runs in stages
+        (include/cvae.h) and all-reduces the fp64 BatchNorm and loss sums between them (SUM on process_group; no exchange at
+        world_size 1), so N ranks at B images train the model one rank trains at N*B — BatchNorm over the global batch,
+        global MS-SSIM / KLD means.  The summed gradient is then the global-batch gradient: Adam's grad_scale is 1."""
         self.vae = vae
         self.h = vae.handle
         if overlap is None:
@@ -91,6 +96,9 @@ class FusedTrainer:
         if reduce_dtype not in ("f32", "bf16"):
             raise ValueError(f"reduce_dtype {reduce_dtype!r}: 'f32' or 'bf16'")
         self.reduce_dtype = reduce_dtype
+        if global_stats is None:
+            global_stats = os.environ.get("CVAE_DP_GLOBAL_STATS") == "1"
+        self.global_stats = bool(global_stats)
         self.buckets = [self.h.grad_bucket(ph) for ph in range(3)]
         self.lr, self.betas, self.eps = lr, betas, eps
         self.world_size, self.pg = world_size, process_group
@@ -110,6 +118,8 @@ class FusedTrainer:
         self.d_logvar = torch.empty_like(self.mu)
         self.scalars = torch.empty(16, device=dev)
         self.ws = vae._workspace(B)
+        self.sync = torch.zeros(SYNC_DOUBLES, dtype=torch.float64, device=dev) if self.global_stats else None
+        self.sync_slots = [self.h.sync_slot(p) for p in range(SYNC_POINTS)]
         self.exposed_ms = []              # measure_exposed: device time the compute stream spent waiting for the all-reduce
         self.measure_exposed = False
         self._ev = None
@@ -135,6 +145,8 @@ class FusedTrainer:
 
     def step(self, x, pred, eps):
         """x (B,3,w,w), pred (B,1), eps (B,32): contiguous fp32 device tensors."""
+        if self.global_stats:
+            return self._step_global(x, pred, eps)
         v, h, B = self.vae, self.h, x.shape[0]
         theta = v.theta.data
         v._stamp_workspace()               # an autograd graph of the same VAE still pending is now stale (nets.py)
@@ -147,36 +159,83 @@ class FusedTrainer:
             for ph in range(3):
                 h.backward_phase(ph, B, x, pred, eps, theta, self.logvar, self.recon, self.d_recon, self.d_mu,
                                  self.d_logvar, self.ws, self.grads)
-                off, n = self.buckets[ph]
-                if self.grads16 is not None:
-                    h.grads_to_bf16(self.grads[off:off + n], self.grads16[off:off + n])
-                    works.append(torch.distributed.all_reduce(self.grads16[off:off + n], group=self.pg, async_op=True))
-                else:
-                    works.append(torch.distributed.all_reduce(self.grads[off:off + n], group=self.pg, async_op=True))
-            self._exposed_begin()
-            for wk in works:
-                wk.wait()                     # nccl: the compute stream waits for the collective's stream
-            self._exposed_end()
-            if self.grads16 is not None:
-                h.grads_from_bf16(self.grads16, self.grads)
+                works.append(self._reduce_bucket(ph))
+            self._wait_buckets(works)
         else:
             h.backward(B, x, pred, eps, theta, self.logvar, self.recon, self.d_recon, self.d_mu, self.d_logvar,
                        self.ws, self.grads)
-            if self.world_size > 1:
-                self._exposed_begin()
-                if self.grads16 is not None:
-                    h.grads_to_bf16(self.grads, self.grads16)
-                    torch.distributed.all_reduce(self.grads16, group=self.pg)
-                    h.grads_from_bf16(self.grads16, self.grads)
-                else:
-                    torch.distributed.all_reduce(self.grads, group=self.pg)      # one flat RCCL all-reduce (sum)
-                self._exposed_end()
+            self._reduce_all()
         self.step_count += 1
         v.num_batches_tracked += 1
         h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
                     self.eps, grad_scale=1.0 / self.world_size)
         return self.scalars
 
+    def _reduce_bucket(self, ph):
+        off, n = self.buckets[ph]
+        if self.grads16 is not None:
+            self.h.grads_to_bf16(self.grads[off:off + n], self.grads16[off:off + n])
+            return torch.distributed.all_reduce(self.grads16[off:off + n], group=self.pg, async_op=True)
+        return torch.distributed.all_reduce(self.grads[off:off + n], group=self.pg, async_op=True)
+
+    def _wait_buckets(self, works):
+        self._exposed_begin()
+        for wk in works:
+            wk.wait()                     # nccl: the compute stream waits for the collective's stream
+        self._exposed_end()
+        if self.grads16 is not None:
+            self.h.grads_from_bf16(self.grads16, self.grads)
+
+    def _reduce_all(self):
+        if self.world_size > 1:
+            self._exposed_begin()
+            if self.grads16 is not None:
+                self.h.grads_to_bf16(self.grads, self.grads16)
+                torch.distributed.all_reduce(self.grads16, group=self.pg)
+                self.h.grads_from_bf16(self.grads16, self.grads)
+            else:
+                torch.distributed.all_reduce(self.grads, group=self.pg)      # one flat RCCL all-reduce (sum)
+            self._exposed_end()
+
+    def _exchange(self, point):
+        """Sum sync point `point` of the record over the ranks, in place (nothing to do on one rank)."""
+        if self.world_size > 1:
+            off, n = self.sync_slots[point]
+            torch.distributed.all_reduce(self.sync[off:off + n], group=self.pg)
+
+    def _step_global(self, x, pred, eps):
+        """The step with global-batch statistics: forward / loss / backward in stages, the BatchNorm and loss sums
+        all-reduced between them; gradient buckets as in step()."""
+        v, h, B = self.vae, self.h, x.shape[0]
+        theta, rec = v.theta.data, self.sync
+        v._stamp_workspace()
+        for k in range(5):
+            h.forward_stage(k, B, x, pred, eps, theta, v.bn_state, self.mu, self.logvar, self.recon, self.ws, rec)
+            if k < 4:
+                self._exchange(k)
+        h.loss_stage(0, B, x, self.mu, self.logvar, self.recon, self.ws, self.scalars, self.d_recon, self.d_mu,
+                     self.d_logvar, rec)
+        self._exchange(4)
+        h.loss_stage(1, B, x, self.mu, self.logvar, self.recon, self.ws, self.scalars, self.d_recon, self.d_mu,
+                     self.d_logvar, rec)
+        bucketed = self.world_size > 1 and self.overlap
+        works = []
+        for k in range(5):
+            h.backward_stage(k, B, x, pred, eps, theta, self.logvar, self.recon, self.d_recon, self.d_mu, self.d_logvar,
+                             self.ws, self.grads, rec)
+            if bucketed and k in (0, 1, 4):                 # the stages that complete buckets 0, 1, 2
+                works.append(self._reduce_bucket(len(works)))
+            if k < 4:
+                self._exchange(5 + k)
+        if bucketed:
+            self._wait_buckets(works)
+        else:
+            self._reduce_all()
+        self.step_count += 1
+        v.num_batches_tracked += 1
+        h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
+                    self.eps, grad_scale=1.0)        # the summed gradient already is the global-batch gradient
+        return self.scalars
 
     def fit_u8(self, frames_u8, critic, batch_size, epochs=1, generator=None, shuffle=True):
         """The `-train` loop (vae.py:40-58) over a host uint8 dataset (N,w,w,3), fused step + overlapped feeder:

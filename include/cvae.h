@@ -136,6 +136,49 @@ int cvae_backward_phases(cvae_handle h, int32_t batch, const float* x, const flo
 int cvae_grad_bucket(cvae_handle h, int32_t phase, int64_t* offset, int64_t* numel);
 
 /*
+ * Global-batch data parallelism: the same step in stages, so that a data-parallel host can sum the BatchNorm statistics and the
+ * loss sums over its ranks (torch's SyncBatchNorm plus a global loss normaliser).  N ranks at B_r images each then train the
+ * model that one rank trains at batch sum(B_r): BatchNorm normalises over the global batch (forward statistics, running
+ * statistics with the global N / (N - 1), backward sums), MS-SSIM level means and the KLD mean are global, and d_mu / d_logvar
+ * carry 1 / B_global.  The summed gradient is then the global-batch gradient itself (Adam's grad_scale = 1, not 1 / world_size).
+ *
+ * The exchange is an fp64 record of CVAE_SYNC_DOUBLES values with 9 sync points; cvae_sync_slot returns the contiguous
+ * [offset, offset + count) of point `point` (host-only, no handle):
+ *   points 0..3: forward BatchNorm of encoder blocks 0..3, 3*C doubles each (C = 32, 64, 128, 256); point 0 ends with one
+ *                more double, this rank's image count (so ranks may hold different batch sizes, e.g. a ragged last batch);
+ *   point 4:     the loss, 11 sums (5 ssim levels, 5 cs levels, the KLD term);
+ *   points 5..8: backward BatchNorm of encoder blocks 3..0, 2*C doubles each.
+ * Stage k writes this rank's values into its point; the CALLER sums that slot over all ranks, in place, on the stream
+ * (torch.distributed / RCCL all_reduce, SUM), before the next stage reads it.  One rank skips the exchange: the stages then
+ * reproduce cvae_forward + cvae_loss + cvae_backward bit for bit.  The library itself stays collective-free.
+ *   cvae_forward_stage  k = 0..3 writes point k (stage k > 0 first finishes block k-1 from point k-1); stage 4 finishes
+ *                       block 3, then runs fc, reparametrize and the decoder (recon == NULL: stops after the encoder).
+ *                       train must be 1 (eval mode uses the running statistics and needs no exchange: cvae_forward).
+ *   cvae_loss_stage     stage 0 writes point 4; stage 1 finishes: scalars, d_recon, d_mu, d_logvar.
+ *   cvae_backward_stage stage 0: decoder, decoder_input, fc and block 3's statistics -> point 5; stages 1..3 apply block 4-k
+ *                       from its summed point, run its weight and input gradients and block 3-k's statistics -> point 5+k;
+ *                       stage 4: E1's fused apply + weight gradient.  The gradient buckets of cvae_grad_bucket complete at
+ *                       the ends of stages 0 (phase 0), 1 (phase 1) and 4 (phase 2).  dgamma / dbeta are this rank's own
+ *                       (the gradient all-reduce sums them).  `grads` is overwritten except its alignment padding.
+ * Each call takes the arguments of the call it splits plus the record `sync` and the stage index.  The step runs forward
+ * stages 0..4, loss stages 0..1, backward stages 0..4, in that order, on one workspace, batch and record; the handle tracks it
+ * and rejects any other order with CVAE_EINVAL (forward stage 0 may always start a new step; a failed stage ends the step).
+ * Every argument check happens before any device access.  Every stage joins the overlap_wgrad side stream before it returns.
+ */
+#define CVAE_SYNC_DOUBLES 2412
+int cvae_sync_slot(int32_t point, int64_t* offset, int64_t* count);
+int cvae_forward_stage(cvae_handle h, int32_t batch, const float* x, const float* pred, const float* eps,
+                       const float* params, float* bn_state, float* mu, float* logvar, float* recon, void* ws,
+                       int32_t train, double* sync, int32_t stage, void* stream);
+int cvae_loss_stage(cvae_handle h, int32_t batch, const float* x, const float* mu, const float* logvar,
+                    const float* recon, void* ws, float* scalars, float* d_recon, float* d_mu, float* d_logvar,
+                    double* sync, int32_t stage, void* stream);
+int cvae_backward_stage(cvae_handle h, int32_t batch, const float* x, const float* pred, const float* eps,
+                        const float* params, const float* logvar, const float* recon, const float* d_recon,
+                        const float* d_mu, const float* d_logvar, void* ws, float* grads, double* sync, int32_t stage,
+                        void* stream);
+
+/*
  * Chain-rule factor of total_loss.backward() (vae.py:57): d_*_out = d_* * gscale[0] for the three loss
  * gradients written by cvae_loss, in one launch; gscale is a DEVICE scalar (autograd's incoming gradient).
  */
