@@ -706,6 +706,57 @@ int cvae_preprocess_u8(cvae_handle h, int32_t B, const uint8_t* frames_hwc, floa
     return launch_preprocess_u8(h->cfg.width, B, frames_hwc, x, (hipStream_t)stream);
 }
 
+// ---- the training set on the device (load_minerl_data, vae_utility.py:393-461; kernels in dataset.hip) ----
+int cvae_curate_select(cvae_handle h, int32_t n_traj, const int64_t* traj_offsets, int64_t n_frames, const float* preds,
+                       int32_t collect, int64_t total_images, int64_t* running, int64_t* counts, int64_t* first,
+                       int64_t* span, int64_t* sel, void* stream) {
+    if (!h) { cvae_set_error("cvae_curate_select: null handle"); return CVAE_EINVAL; }
+    if (n_traj < 0 || n_frames < 0 || total_images < 0) {
+        cvae_set_error("cvae_curate_select: n_traj %d, n_frames %lld, total_images %lld must be >= 0", n_traj, (long long)n_frames,
+                       (long long)total_images);
+        return CVAE_EINVAL;
+    }
+    if (collect < 1) { cvae_set_error("cvae_curate_select: collect %d must be >= 1", collect); return CVAE_EINVAL; }
+    if (!running || !span || (n_traj > 0 && (!traj_offsets || !counts || !first)) || (n_frames > 0 && (!preds || !sel))) {
+        cvae_set_error("cvae_curate_select: null pointer"); return CVAE_EINVAL;
+    }
+    return launch_curate_select(n_traj, traj_offsets, n_frames, preds, collect, total_images, running, counts, first, span, sel,
+                                (hipStream_t)stream);
+}
+
+int cvae_gather_frames_u8(cvae_handle h, int32_t width, const uint8_t* src_frames, const float* src_preds, int64_t n_src,
+                          const int64_t* sel, int64_t max_count, const int64_t* span, uint8_t* dst_frames, float* dst_preds,
+                          int64_t capacity, void* stream) {
+    if (!h) { cvae_set_error("cvae_gather_frames_u8: null handle"); return CVAE_EINVAL; }
+    if (width != h->cfg.width) { cvae_set_error("cvae_gather_frames_u8: width %d, the handle's is %d", width, h->cfg.width); return CVAE_EINVAL; }
+    if (n_src < 0 || max_count < 0 || capacity < 0 || max_count > 0x7fffffffLL) {
+        cvae_set_error("cvae_gather_frames_u8: n_src %lld, max_count %lld, capacity %lld outside range", (long long)n_src,
+                       (long long)max_count, (long long)capacity);
+        return CVAE_EINVAL;
+    }
+    if (!span || (max_count > 0 && (!src_frames || !sel || !dst_frames)) || (!src_preds != !dst_preds)) {
+        cvae_set_error("cvae_gather_frames_u8: null pointer (src_preds and dst_preds go together)"); return CVAE_EINVAL;
+    }
+    if (((uintptr_t)src_frames & 15) || ((uintptr_t)dst_frames & 15)) {
+        cvae_set_error("cvae_gather_frames_u8: frame buffers must be 16-byte aligned"); return CVAE_EINVAL;
+    }
+    return launch_gather_frames_u8(width, src_frames, src_preds, n_src, sel, max_count, span, dst_frames, dst_preds, capacity,
+                                   (hipStream_t)stream);
+}
+
+int cvae_preprocess_u8_gather(cvae_handle h, int32_t batch, int32_t width, const uint8_t* frames_hwc, const float* preds,
+                              int64_t n_frames, const int64_t* idx, float* x, float* pred, void* stream) {
+    if (!h) { cvae_set_error("cvae_preprocess_u8_gather: null handle"); return CVAE_EINVAL; }
+    if (width != h->cfg.width) { cvae_set_error("cvae_preprocess_u8_gather: width %d, the handle's is %d", width, h->cfg.width); return CVAE_EINVAL; }
+    if (batch < 1 || batch > h->cfg.max_batch) { cvae_set_error("cvae_preprocess_u8_gather: batch %d outside [1, %d]", batch, h->cfg.max_batch); return CVAE_EINVAL; }
+    if (n_frames < 1) { cvae_set_error("cvae_preprocess_u8_gather: n_frames %lld must be >= 1", (long long)n_frames); return CVAE_EINVAL; }
+    if (!frames_hwc || !preds || !idx || !x || !pred) { cvae_set_error("cvae_preprocess_u8_gather: null pointer"); return CVAE_EINVAL; }
+    if (((uintptr_t)frames_hwc & 15) || ((uintptr_t)x & 15)) {
+        cvae_set_error("cvae_preprocess_u8_gather: frames and x must be 16-byte aligned"); return CVAE_EINVAL;
+    }
+    return launch_preprocess_u8_gather(width, batch, frames_hwc, preds, n_frames, idx, x, pred, (hipStream_t)stream);
+}
+
 // |recon_zero - recon_one| -> greyscale difference mask (get_diff_image, vae_utility.py:256-277), batched
 int cvae_diff_grey(cvae_handle h, int32_t B, const float* recon_one, const float* recon_zero, float* diff, void* stream) {
     if (!h || B < 1) { cvae_set_error("cvae_diff_grey: bad handle/batch"); return CVAE_EINVAL; }

@@ -293,6 +293,15 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
 int critic_param_count();
 int launch_critic_fwd(int width, int B, const float* x, const float* critic_params, float* pred, hipStream_t st);
 int launch_preprocess_u8(int width, int B, const uint8_t* u8, float* x, hipStream_t st);
+// dataset.hip
+int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
+                         int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* span,
+                         int64_t* sel, hipStream_t st);
+int launch_gather_frames_u8(int width, const uint8_t* src, const float* src_pred, int64_t n_src, const int64_t* sel,
+                            int64_t max_count, const int64_t* span, uint8_t* dst, float* dst_pred, int64_t capacity,
+                            hipStream_t st);
+int launch_preprocess_u8_gather(int width, int B, const uint8_t* frames, const float* preds, int64_t n, const int64_t* idx,
+                                float* x, float* pred, hipStream_t st);
 int launch_diff_grey(int width, int B, const float* a, const float* b, float* diff, hipStream_t st);
 // segment.hip
 int64_t crf_scratch_bytes(int width, int B);

@@ -1,0 +1,247 @@
+// dataset.hip — the training set of `-train` built on the device (load_minerl_data, vae_utility.py:393-461, non-recon
+// branch) and the per-step batch gather out of it.
+//
+//   curate_select         critic values of a chunk of whole trajectories -> the frames the reference keeps, in its order:
+//                         per trajectory at most `collect` frames in each of the bins mid [0.4, 0.6], high >= 0.7,
+//                         low <= 0.25 (tested in that order, fp32), and the global cut `len(dset) >= total_images` before
+//                         each trajectory against a running count held on the device across chunks.  Three launches:
+//                         per-trajectory bin counts, one fixed-order scan over the trajectories (the cut), the scatter.
+//   gather_frames_u8      the selected uint8 frames (and their critic values) into the dataset buffer at their slots.
+//   preprocess_u8_gather  x[b] = frames[idx[b]] / 255 as CHW fp32 and pred[b] = preds[idx[b]]: one training batch.
+//
+// Integer math only, no atomics: every result is deterministic.  Frame offsets are 64-bit (a 64x64 dataset passes
+// 2^31 bytes at 174 763 frames).
+#include "common.h"
+#include "../../include/cvae.h"
+
+namespace {
+
+constexpr int TPB = 256;
+constexpr int NWAVE = TPB / 64;
+
+// 0 mid, 1 high, 2 low, -1 none: vae_utility.py:450-459, float32 comparisons (NaN falls in no bin)
+__device__ __forceinline__ int bin_of(float p) {
+    if (p >= 0.4f && p <= 0.6f) return 0;
+    if (p >= 0.7f) return 1;
+    if (p <= 0.25f) return 2;
+    return -1;
+}
+
+__device__ __forceinline__ uint64_t lanes_below(int lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
+
+// frames [lo, hi) of trajectory t, clamped to the chunk
+__device__ __forceinline__ void traj_range(const int64_t* off, int t, int64_t n_frames, int64_t& lo, int64_t& hi) {
+    lo = off[t]; hi = off[t + 1];
+    lo = lo < 0 ? 0 : (lo > n_frames ? n_frames : lo);
+    hi = hi < lo ? lo : (hi > n_frames ? n_frames : hi);
+}
+
+// one workgroup per trajectory: counts[t][k] = min(#frames of bin k, collect)
+__global__ __launch_bounds__(TPB) void curate_count_kernel(const float* __restrict__ preds, const int64_t* __restrict__ off,
+                                                           int64_t n_frames, int collect, int64_t* __restrict__ counts) {
+    __shared__ int64_t part[NWAVE][3];
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int64_t lo, hi;
+    traj_range(off, t, n_frames, lo, hi);
+    int64_t c[3] = {0, 0, 0};
+    for (int64_t i = lo + tid; i < hi; i += TPB) {
+        const int k = bin_of(preds[i]);
+        c[0] += k == 0; c[1] += k == 1; c[2] += k == 2;
+    }
+    for (int k = 0; k < 3; ++k) {
+        int64_t v = c[k];
+        for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+        if (lane == 0) part[wv][k] = v;
+    }
+    __syncthreads();
+    if (tid < 3) {
+        int64_t v = 0;
+        for (int w = 0; w < NWAVE; ++w) v += part[w][tid];
+        counts[(int64_t)t * 3 + tid] = v < collect ? v : collect;
+    }
+}
+
+// one workgroup, trajectories in order: trajectory t is visited iff running + (frames selected by the visited ones
+// before it) < total_images — the running count only grows, so that is an exclusive prefix sum compared with the cut.
+// first[t] = its first dataset slot (the reference's len(dset) before it) or -1; counts of unvisited ones become 0.
+__global__ __launch_bounds__(TPB) void curate_cut_kernel(int n_traj, int64_t total_images, int64_t* __restrict__ running,
+                                                         int64_t* __restrict__ counts, int64_t* __restrict__ first,
+                                                         int64_t* __restrict__ span) {
+    __shared__ int64_t wsum[NWAVE];
+    __shared__ int64_t carry;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t r0 = *running;
+    if (tid == 0) carry = r0;
+    __syncthreads();
+    for (int t0 = 0; t0 < n_traj; t0 += TPB) {
+        const int t = t0 + tid;
+        const int64_t s = t < n_traj ? counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2] : 0;
+        int64_t incl = s;                                        // inclusive scan within the wave
+        for (int d = 1; d < 64; d <<= 1) {
+            const int64_t v = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += v;
+        }
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        int64_t before = carry;
+        for (int w = 0; w < wv; ++w) before += wsum[w];
+        before += incl - s;                                      // len(dset) before trajectory t
+        const int64_t block_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (t < n_traj) {
+            if (before < total_images) {
+                first[t] = before;
+            } else {
+                first[t] = -1;
+                counts[(int64_t)t * 3] = counts[(int64_t)t * 3 + 1] = counts[(int64_t)t * 3 + 2] = 0;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) carry += block_total;
+        __syncthreads();
+    }
+    // the visited trajectories are a prefix: the new running count is the last visited one's first + its selection
+    if (tid == 0) {
+        int64_t r = r0;
+        for (int t = n_traj - 1; t >= 0; --t)
+            if (first[t] >= 0) { r = first[t] + counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2]; break; }
+        span[0] = r0; span[1] = r - r0;
+        *running = r;
+    }
+}
+
+// one workgroup per visited trajectory: frames in order, a frame is kept iff it has a bin and fewer than `collect`
+// earlier frames of the trajectory fell in that bin; sel[first[t] - span[0] + rank] = its chunk frame index
+__global__ __launch_bounds__(TPB) void curate_scatter_kernel(const float* __restrict__ preds, const int64_t* __restrict__ off,
+                                                             int64_t n_frames, int collect, const int64_t* __restrict__ first,
+                                                             const int64_t* __restrict__ span, int64_t* __restrict__ sel) {
+    __shared__ int wcnt[NWAVE][4];
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t f = first[t];
+    if (f < 0) return;
+    int64_t lo, hi;
+    traj_range(off, t, n_frames, lo, hi);
+    const int64_t base = f - span[0];
+    int64_t carry[3] = {0, 0, 0}, taken = 0;                    // identical in every thread
+    const uint64_t below = lanes_below(lane);
+    for (int64_t b0 = lo; b0 < hi; b0 += TPB) {
+        if (carry[0] >= collect && carry[1] >= collect && carry[2] >= collect) break;
+        const int64_t i = b0 + tid;
+        const int k = i < hi ? bin_of(preds[i]) : -1;
+        int rank = 0;                                            // earlier frames of this block in bin k
+        for (int q = 0; q < 3; ++q) {
+            const uint64_t m = __ballot(k == q);
+            if (k == q) rank = __popcll(m & below);
+            if (lane == 0) wcnt[wv][q] = __popcll(m);
+        }
+        __syncthreads();
+        int64_t prev = 0;
+        if (k >= 0) {
+            prev = (k == 0 ? carry[0] : k == 1 ? carry[1] : carry[2]) + rank;
+            for (int w = 0; w < wv; ++w) prev += wcnt[w][k];
+        }
+        const bool keep = k >= 0 && prev < collect;
+        const uint64_t mk = __ballot(keep);
+        if (lane == 0) wcnt[wv][3] = __popcll(mk);
+        __syncthreads();
+        if (keep) {
+            int64_t pos = taken + __popcll(mk & below);
+            for (int w = 0; w < wv; ++w) pos += wcnt[w][3];
+            pos += base;
+            if (pos >= 0 && pos < n_frames) sel[pos] = i;
+        }
+        for (int q = 0; q < 4; ++q) {
+            int64_t s = 0;
+            for (int w = 0; w < NWAVE; ++w) s += wcnt[w][q];
+            if (q < 3) carry[q] += s; else taken += s;
+        }
+        __syncthreads();
+    }
+}
+
+// one workgroup per candidate k < span[1]: frame sel[k] of the chunk -> dataset slot span[0] + k, 16 bytes per thread
+__global__ __launch_bounds__(TPB) void gather_frames_kernel(const uint4* __restrict__ src, const float* __restrict__ src_pred,
+                                                            const int64_t* __restrict__ sel, const int64_t* __restrict__ span,
+                                                            int64_t n_src, uint4* __restrict__ dst, float* __restrict__ dst_pred,
+                                                            int64_t capacity, int units) {
+    const int64_t k = blockIdx.x;
+    if (k >= span[1]) return;
+    const int64_t s = sel[k], d = span[0] + k;
+    if (s < 0 || s >= n_src || d < 0 || d >= capacity) return;
+    const uint4* a = src + s * units;
+    uint4* b = dst + d * units;
+    for (int u = threadIdx.x; u < units; u += TPB) b[u] = a[u];
+    if (threadIdx.x == 0 && src_pred && dst_pred) dst_pred[d] = src_pred[s];
+}
+
+// 16 pixels per thread: three 16-byte loads of uint8 HWC, four float4 stores per plane.  (float)u8 / 255.0f exactly as
+// preprocess_u8_kernel (critic.hip).  An index outside [0, n) yields NaN (never read out of bounds).
+__global__ __launch_bounds__(TPB) void preprocess_u8_gather_kernel(const uint8_t* __restrict__ frames, const float* __restrict__ preds,
+                                                                   int64_t n, const int64_t* __restrict__ idx, float* __restrict__ x,
+                                                                   float* __restrict__ pred, int hw, int bpf) {
+    const int64_t b = blockIdx.x / bpf;
+    const int g = (int)(blockIdx.x % bpf) * TPB + threadIdx.x;   // 16-pixel group of the frame
+    const int64_t s = idx[b];
+    const bool ok = s >= 0 && s < n;
+    float* d = x + b * 3 * (int64_t)hw + (int64_t)g * 16;
+    if (g * 16 >= hw) return;
+    if (!ok) {
+        const float4 q = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
+        for (int c = 0; c < 3; ++c)
+            for (int j = 0; j < 4; ++j) reinterpret_cast<float4*>(d + (int64_t)c * hw)[j] = q;
+        if (g == 0) pred[b] = __builtin_nanf("");
+        return;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(frames + s * 3 * (int64_t)hw + (int64_t)g * 48);
+    const uint4 v0 = src[0], v1 = src[1], v2 = src[2];
+    const uint32_t wd[12] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w};
+    float o[3][16];
+#pragma unroll
+    for (int e = 0; e < 48; ++e) {
+        const float val = (float)((wd[e >> 2] >> ((e & 3) * 8)) & 0xffu) / 255.0f;
+        o[e % 3][e / 3] = val;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            reinterpret_cast<float4*>(d + (int64_t)c * hw)[j] = make_float4(o[c][4 * j], o[c][4 * j + 1], o[c][4 * j + 2], o[c][4 * j + 3]);
+    if (g == 0) pred[b] = preds[s];
+}
+
+}  // namespace
+
+int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
+                         int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* span,
+                         int64_t* sel, hipStream_t st) {
+    if (n_traj > 0) {
+        hipLaunchKernelGGL(curate_count_kernel, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, counts);
+        CVAE_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(curate_cut_kernel, dim3(1), dim3(TPB), 0, st, n_traj, total_images, running, counts, first, span);
+    CVAE_CHECK_LAUNCH();
+    if (n_traj > 0) {
+        hipLaunchKernelGGL(curate_scatter_kernel, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, first, span, sel);
+        CVAE_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int launch_gather_frames_u8(int width, const uint8_t* src, const float* src_pred, int64_t n_src, const int64_t* sel,
+                            int64_t max_count, const int64_t* span, uint8_t* dst, float* dst_pred, int64_t capacity,
+                            hipStream_t st) {
+    if (max_count == 0) return 0;
+    const int units = width * width * 3 / 16;
+    hipLaunchKernelGGL(gather_frames_kernel, dim3((unsigned)max_count), dim3(TPB), 0, st, (const uint4*)src, src_pred, sel, span,
+                       n_src, (uint4*)dst, dst_pred, capacity, units);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_preprocess_u8_gather(int width, int B, const uint8_t* frames, const float* preds, int64_t n, const int64_t* idx,
+                                float* x, float* pred, hipStream_t st) {
+    const int hw = width * width, bpf = hw / 16 / TPB;          // 1 workgroup per frame at 64x64, 4 at 128x128
+    hipLaunchKernelGGL(preprocess_u8_gather_kernel, dim3((unsigned)((int64_t)B * bpf)), dim3(TPB), 0, st, frames, preds, n, idx,
+                       x, pred, hw, bpf);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}

@@ -1,0 +1,259 @@
+"""The reference's training set from recorded trajectories (load_minerl_data(critic), vae_utility.py:393-461, non-recon
+branch), curated on the device and kept there for the training loop.
+
+A trajectory is one `.npy` file of uint8 frames (T, w, w, 3) — MineRL's `pov` observations, and the reference's own
+`minerl-episode/X.npy` format (segment.load_episode).  The selection rule (include/cvae.h, "The training set on the
+device"): trajectories in the reference's order (np.random.default_rng(seed=0).shuffle of the name list; here the sorted
+file names), frames in order, p = the critic value of preprocess_observation(frame); bins mid 0.4 <= p <= 0.6, then high
+p >= 0.7, then low p <= 0.25, compared in float32; at most `collect` frames per bin and trajectory; the walk stops before a
+trajectory once len(dset) >= total_images.
+
+    eps = load_episodes(["episodes/"])                       # (name, memory-mapped array) pairs, sorted by name
+    ds = curate(eps, critic)                                 # DeviceDataset: frames (N,w,w,3) uint8 + preds (N,1) on the GPU
+    FusedTrainer(vae).fit_device(ds, batch_size=128, epochs=7)
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import params as P
+from .critic import Critic
+from .lib import Handle
+
+# bin edges as the reference compares them: a float32 tensor against a Python float, in float32
+MID_LO, MID_HI = np.float32(P.bin_mid[0]), np.float32(P.bin_mid[1])
+HIGH, LOW = np.float32(P.bin_high), np.float32(P.bin_low)
+CURATE_PIECE = 1024          # frames per critic launch during curation (the curation handle's max_batch)
+
+
+def load_episodes(paths, width=P.w):
+    """`.npy` files, or directories of them (not recursive): one trajectory (T, width, width, 3) uint8 per file.
+    Returns [(name, array)] sorted by name (the file name without `.npy`); arrays are memory-mapped.
+    ValueError for a wrong dtype, rank, channel count or width, or for two files of the same name."""
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    files = []
+    for p in paths:
+        p = os.fspath(p)
+        if os.path.isdir(p):
+            files += [os.path.join(p, f) for f in os.listdir(p) if f.endswith(".npy")]
+        elif os.path.isfile(p):
+            files.append(p)
+        else:
+            raise FileNotFoundError(p)
+    out = {}
+    for f in files:
+        name = os.path.basename(f)[:-4] if f.endswith(".npy") else os.path.basename(f)
+        if name in out:
+            raise ValueError(f"two trajectories named {name!r}")
+        a = np.load(f, mmap_mode="r")
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3 or a.shape[1] != width or a.shape[2] != width:
+            raise ValueError(f"{f}: a trajectory must be uint8 (T, {width}, {width}, 3), got {a.dtype} {a.shape}")
+        out[name] = a
+    return sorted(out.items())
+
+
+def reference_order(names, seed=0):
+    """The reference's visiting order: np.random.default_rng(seed=0).shuffle of the name list (vae_utility.py:400-402)."""
+    names = list(names)
+    np.random.default_rng(seed=seed).shuffle(names)
+    return names
+
+
+def select_host(traj_preds, collect=P.collect, total_images=P.total_images):
+    """vae_utility.py:406-459 restated in plain Python over critic values (float32 comparisons, as torch makes them).
+    traj_preds: per visited-order trajectory, its frames' critic values.  Returns (sizes, selected, counts):
+    sizes = len(dset) before each visited trajectory (the reference's `total images = ...` prints), selected = [(t, i)]
+    in dataset order, counts (T, 3) int64 = frames taken per bin (mid, high, low), 0 for trajectories never visited."""
+    sizes, selected = [], []
+    counts = np.zeros((len(traj_preds), 3), np.int64)
+    for t, preds in enumerate(traj_preds):
+        if len(selected) >= total_images:
+            break
+        sizes.append(len(selected))
+        c_high = c_mid = c_low = 0
+        for i, pred in enumerate(np.asarray(preds, np.float32).reshape(-1)):
+            if c_high >= collect and c_low >= collect and c_mid >= collect:
+                break
+            elif MID_LO <= pred <= MID_HI and c_mid < collect:
+                selected.append((t, i))
+                c_mid += 1
+            elif pred >= HIGH and c_high < collect:
+                selected.append((t, i))
+                c_high += 1
+            elif pred <= LOW and c_low < collect:
+                selected.append((t, i))
+                c_low += 1
+        counts[t] = (c_mid, c_high, c_low)
+    return sizes, selected, counts
+
+
+class DeviceDataset:
+    """A training set on the device: frames (N, w, w, 3) uint8, preds (N, 1) fp32 (the critic's value of every frame),
+    source (N, 2) int64 host array (trajectory, frame).  curate() also fills `names` (visited trajectories, in order),
+    `sizes` (len(dset) before each) and `counts` (per visited trajectory, frames per bin mid / high / low)."""
+
+    def __init__(self, frames, preds, source, names=(), sizes=(), counts=None):
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3
+                and frames.shape[1] == frames.shape[2] and frames.is_contiguous()):
+            raise ValueError("frames must be a contiguous uint8 device tensor (N, w, w, 3)")
+        if not (preds.is_cuda and preds.dtype == torch.float32 and tuple(preds.shape) == (frames.shape[0], 1)
+                and preds.is_contiguous()):
+            raise ValueError("preds must be a contiguous fp32 device tensor (N, 1)")
+        self.frames, self.preds = frames, preds
+        self.source = np.asarray(source, np.int64).reshape(-1, 2)
+        self.names, self.sizes = list(names), list(sizes)
+        self.counts = np.zeros((0, 3), np.int64) if counts is None else np.asarray(counts, np.int64)
+
+    def __len__(self):
+        return self.frames.shape[0]
+
+    @property
+    def width(self):
+        return self.frames.shape[1]
+
+    @classmethod
+    def from_host(cls, frames_u8, critic=None, device="cuda:0"):
+        """From host uint8 frames (N, w, w, 3), w = 64 or 128.  critic: None (preds = 0), a Critic (its values, computed
+        on the device; 64x64 only), or the preds themselves (N or (N, 1) values)."""
+        frames_u8 = np.ascontiguousarray(frames_u8)
+        if frames_u8.dtype != np.uint8 or frames_u8.ndim != 4 or frames_u8.shape[3] != 3 or frames_u8.shape[1] != frames_u8.shape[2]:
+            raise ValueError(f"frames must be uint8 (N, w, w, 3), got {frames_u8.dtype} {frames_u8.shape}")
+        n = frames_u8.shape[0]
+        frames = torch.from_numpy(frames_u8).to(device)
+        if critic is None:
+            preds = torch.zeros(n, 1, device=device)
+        elif isinstance(critic, Critic):
+            preds = torch.empty(n, 1, device=device)
+            _critic_values(critic, frames, preds)
+        else:
+            preds = torch.as_tensor(np.asarray(critic, np.float32).reshape(n, 1)).to(device)
+        source = np.stack([np.zeros(n, np.int64), np.arange(n, dtype=np.int64)], 1)
+        return cls(frames, preds, source)
+
+
+def _critic_values(critic, frames_u8, out, handle=None, x=None):
+    """out[i] = critic.evaluate(preprocess_observation(frames_u8[i])) on the device, in pieces of the handle's max_batch."""
+    if frames_u8.shape[1] != 64:
+        raise ValueError("the critic is 64x64 only (critic_net.py)")
+    h = handle or Handle(64, CURATE_PIECE)
+    if x is None:
+        x = torch.empty(h.max_batch, 3, 64, 64, device=frames_u8.device)
+    for p in range(0, frames_u8.shape[0], h.max_batch):
+        nb = min(h.max_batch, frames_u8.shape[0] - p)
+        h.preprocess_u8(nb, frames_u8[p:p + nb], x[:nb])
+        h.critic_forward(nb, x[:nb], critic.flat, out[p:p + nb])
+
+
+def _chunks(lengths, chunk_frames):
+    """Consecutive runs of trajectories of at most chunk_frames frames (a longer trajectory is a chunk of its own)."""
+    out, cur, n = [], [], 0
+    for t, L in enumerate(lengths):
+        if cur and n + L > chunk_frames:
+            out.append(cur)
+            cur, n = [], 0
+        cur.append(t)
+        n += L
+    if cur:
+        out.append(cur)
+    return out
+
+
+def curate(episodes, critic, collect=P.collect, total_images=P.total_images, chunk_frames=8192, order=None,
+           device="cuda:0", log=print):
+    """load_minerl_data(critic) (vae_utility.py:393-461, non-recon branch) on the device.
+
+    episodes: [(name, array (T, 64, 64, 3) uint8)] (load_episodes).  order: None = reference_order of the names, or an
+    explicit list of names.  Chunks of whole trajectories (at most chunk_frames frames, unless one trajectory is longer)
+    stream through two pinned staging buffers, the copy of chunk i+1 on a side stream under chunk i's kernels; per chunk:
+    cvae_preprocess_u8 + cvae_critic_forward in pieces of CURATE_PIECE, cvae_curate_select (the running count stays on
+    the device) and cvae_gather_frames_u8 into the dataset buffer.  The running count is read once per chunk, to stop
+    streaming at the cut.  log gets the reference's progress lines (`total images = N` before each visited trajectory)
+    and the per-bin totals.  Returns a DeviceDataset."""
+    if not isinstance(critic, Critic):
+        raise TypeError("curate needs a critic_vae_amd.critic.Critic (the HIP critic)")
+    if collect < 1 or total_images < 0:
+        raise ValueError(f"collect {collect} must be >= 1 and total_images {total_images} >= 0")
+    episodes = list(episodes)
+    by_name = {}
+    for pos, (name, a) in enumerate(episodes):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 4 and a.shape[1:] == (64, 64, 3)):
+            raise ValueError(f"trajectory {name!r}: curation needs uint8 (T, 64, 64, 3) frames (the critic is 64x64 only)")
+        by_name[name] = pos
+    names = reference_order([n for n, _ in episodes]) if order is None else list(order)
+    walk = [by_name[n] for n in names]
+    device = torch.device(device)
+    # the cut overshoots by at most 3 * collect - 1 frames, and no walk selects more frames than the trajectories hold
+    cap = min(total_images - 1 + 3 * collect, sum(episodes[p][1].shape[0] for p in walk)) if total_images > 0 else 0
+    ds_frames = torch.empty(max(cap, 1), 64, 64, 3, dtype=torch.uint8, device=device)
+    ds_preds = torch.empty(max(cap, 1), 1, device=device)
+    log("loading episodes...")
+    if total_images == 0 or not walk:
+        return DeviceDataset(ds_frames[:0], ds_preds[:0], np.zeros((0, 2), np.int64))
+
+    lengths = [episodes[p][1].shape[0] for p in walk]
+    chunks = _chunks(lengths, chunk_frames)
+    biggest = max(sum(lengths[t] for t in c) for c in chunks)
+    h = Handle(64, CURATE_PIECE)
+    x = torch.empty(CURATE_PIECE, 3, 64, 64, device=device)
+    cpred = torch.empty(max(biggest, 1), device=device)
+    sel = torch.empty(max(biggest, 1), dtype=torch.int64, device=device)
+    running = torch.zeros(1, dtype=torch.int64, device=device)
+    span = torch.zeros(2, dtype=torch.int64, device=device)
+    copy_stream = torch.cuda.Stream(device=device)
+    sets = [{"pin": torch.empty(max(biggest, 1), 64, 64, 3, dtype=torch.uint8).pin_memory(),
+             "dev": torch.empty(max(biggest, 1), 64, 64, 3, dtype=torch.uint8, device=device),
+             "copied": torch.cuda.Event(), "consumed": torch.cuda.Event(), "used": False} for _ in range(2)]
+
+    def stage(s, c):
+        if s["used"]:
+            s["consumed"].synchronize()
+        pin, n = s["pin"].numpy(), 0
+        for t in c:
+            a = episodes[walk[t]][1]
+            pin[n:n + a.shape[0]] = a
+            n += a.shape[0]
+        with torch.cuda.stream(copy_stream):
+            s["dev"][:n].copy_(s["pin"][:n], non_blocking=True)
+            s["copied"].record(copy_stream)
+        s["used"], s["n"] = True, n
+
+    source, sizes, visited, counts = [], [], [], []
+    cur = torch.cuda.current_stream(device)
+    stage(sets[0], chunks[0])
+    for ci, c in enumerate(chunks):
+        s = sets[ci % 2]
+        n = s["n"]
+        cur.wait_event(s["copied"])
+        offs = np.concatenate([[0], np.cumsum([lengths[t] for t in c])]).astype(np.int64)
+        d_offs = torch.from_numpy(offs).to(device)
+        d_counts = torch.empty(len(c), 3, dtype=torch.int64, device=device)
+        d_first = torch.empty(len(c), dtype=torch.int64, device=device)
+        if n:
+            _critic_values(critic, s["dev"][:n], cpred[:n], handle=h, x=x)
+        h.curate_select(d_offs, cpred[:n], collect, total_images, running, d_counts, d_first, span, sel)
+        if n:
+            h.gather_frames_u8(s["dev"], cpred, sel, n, span, ds_frames, ds_preds)
+        s["consumed"].record(cur)
+        if ci + 1 < len(chunks):
+            stage(sets[(ci + 1) % 2], chunks[ci + 1])          # host fill + H2D of the next chunk under this one's kernels
+        first, cnt, sp = d_first.cpu().numpy(), d_counts.cpu().numpy(), span.cpu().numpy()
+        picked = sel[:int(sp[1])].cpu().numpy()
+        tr = np.searchsorted(offs, picked, side="right") - 1
+        source.append(np.stack([np.asarray(walk)[np.asarray(c)[tr]] if len(picked) else np.zeros(0, np.int64),
+                                picked - offs[tr]], 1))
+        for j, t in enumerate(c):
+            if first[j] >= 0:
+                log(f"total images = {first[j]}")
+                sizes.append(int(first[j]))
+                visited.append(names[t])
+                counts.append(cnt[j])
+        if sp[0] + sp[1] >= total_images:
+            break
+    torch.cuda.synchronize(device)
+    n = int(running.item())
+    counts = np.array(counts, np.int64).reshape(-1, 3)
+    tot = counts.sum(0)
+    log(f"dataset: {n} frames from {len(visited)} trajectories (mid {tot[0]}, high {tot[1]}, low {tot[2]})")
+    return DeviceDataset(ds_frames[:n], ds_preds[:n], np.concatenate(source).astype(np.int64), visited, sizes, counts)

@@ -75,6 +75,9 @@ _SIGS = {
     "cvae_critic_forward": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_preprocess_u8": (C.c_int, [_p, _i32, _p, _p, _p]),
     "cvae_diff_grey": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
+    "cvae_curate_select": (C.c_int, [_p, _i32, _p, _i64, _p, _i32, _i64] + [_p] * 6),
+    "cvae_gather_frames_u8": (C.c_int, [_p, _i32, _p, _p, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
+    "cvae_preprocess_u8_gather": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p]),
     "cvae_diff_normalize": (C.c_int, [_p, _i32, _p, C.c_double, C.c_double, _i32] + [_p] * 6),
     "cvae_mask_counts": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_crf_scratch_bytes": (_i64, [_p, _i32]),
@@ -278,6 +281,32 @@ class Handle:
 
     def diff_grey(self, B, recon_one, recon_zero, diff):
         self._check(self.lib.cvae_diff_grey(self.h, B, _ptr(recon_one), _ptr(recon_zero), _ptr(diff), _stream()))
+
+    # ---- the training set on the device (load_minerl_data, vae_utility.py:393-461; episodes.py) ----
+    def curate_select(self, offsets, preds, collect, total_images, running, counts, first, span, sel):
+        """One chunk of whole trajectories: offsets (n_traj+1) int64, preds (n_frames) fp32, running (1) int64 in/out,
+        counts (n_traj,3), first (n_traj), span (2), sel (>= n_frames) int64 — all device tensors (include/cvae.h)."""
+        n_traj = offsets.numel() - 1
+        n_frames = preds.numel()
+        assert sel.numel() >= n_frames and counts.numel() >= 3 * n_traj and first.numel() >= n_traj
+        self._check(self.lib.cvae_curate_select(self.h, n_traj, self._i64(offsets, "offsets"), n_frames, _ptr(preds),
+                                                int(collect), int(total_images), self._i64(running, "running"),
+                                                self._i64(counts, "counts"), self._i64(first, "first"),
+                                                self._i64(span, "span"), self._i64(sel, "sel"), _stream()))
+
+    def gather_frames_u8(self, src, src_preds, sel, max_count, span, dst, dst_preds):
+        """dst[span[0] + k] = src[sel[k]] (uint8 (N,W,W,3)) and dst_preds likewise, k < span[1] <= max_count."""
+        assert sel.numel() >= max_count
+        self._check(self.lib.cvae_gather_frames_u8(self.h, int(src.shape[1]), self._u8(src, "src"), _ptr(src_preds), src.shape[0],
+                                                   self._i64(sel, "sel"), int(max_count), self._i64(span, "span"),
+                                                   self._u8(dst, "dst"), _ptr(dst_preds), dst.shape[0], _stream()))
+
+    def preprocess_u8_gather(self, B, frames_u8, preds, idx, x, pred):
+        """x[b] = frames_u8[idx[b]] / 255 (CHW fp32), pred[b] = preds[idx[b]]; idx (>= B) int64 in [0, N) on the device."""
+        w = frames_u8.shape[1]
+        assert idx.numel() >= B and preds.numel() >= frames_u8.shape[0] and x.numel() >= B * 3 * w * w and pred.numel() >= B
+        self._check(self.lib.cvae_preprocess_u8_gather(self.h, B, int(frames_u8.shape[1]), self._u8(frames_u8, "frames"), _ptr(preds),
+                                                       frames_u8.shape[0], self._i64(idx, "idx"), _ptr(x), _ptr(pred), _stream()))
 
     # ---- segmentation evaluation (eval_textured_frames, vae_utility.py:162-212) ----
     @staticmethod

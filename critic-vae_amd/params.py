@@ -19,6 +19,12 @@ step = 1                # conv stride (vae_parameters.py:14)
 latent_dim = 32         # vae_parameters.py:16
 kld_weight = 0.001      # vae_parameters.py:17
 total_images = 50000    # vae_parameters.py:19
+collect = 150           # frames per critic-value bin and trajectory (vae_utility.py:404)
+# critic-value bins of load_minerl_data (vae_utility.py:450-459), tested in this order and compared in float32 (torch
+# compares a float32 tensor with a Python float in float32): mid [0.4, 0.6], high >= 0.7, low <= 0.25
+bin_mid = (0.4, 0.6)
+bin_high = 0.7
+bin_low = 0.25
 log_n = batch_size * 30  # vae_parameters.py:21
 inject_n = 6            # vae_parameters.py:22
 

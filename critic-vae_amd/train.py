@@ -9,6 +9,10 @@ Two drivers over the same C-ABI kernels:
     cvae_adam_step, all asynchronous on one stream.  This is what bench.py times.
 
     python -m critic_vae_amd.train -train --synthetic 1024 --batch 32 --epochs 1
+    python -m critic_vae_amd.train -train --episodes episodes/ --critic critic.pt --epochs 7 --save saved-networks
+
+With --episodes the training set is built as the reference's load_minerl_data(critic) builds it (episodes.py), on the
+device, and FusedTrainer.fit_device trains on it.
 """
 import argparse
 import os
@@ -254,6 +258,35 @@ class FusedTrainer:
                 scal = self.step(images, preds, eps)
         return scal
 
+    def fit_device(self, dataset, batch_size, epochs=1, generator=None, shuffle=True):
+        """The loop of fit_u8 over a DeviceDataset (episodes.py) that already lives on the device with its critic values:
+        per epoch np.random.shuffle of the host indices (uploaded once), slices of batch_size with the ragged last batch
+        kept, eps ~ N(0,1) from `generator`; each batch is one cvae_preprocess_u8_gather launch (x = frames[idx] / 255,
+        pred = preds[idx]) and step() — no host gather, no PCIe copy, no critic launch.  Returns the last step's scalars."""
+        dev = self.vae.theta.device
+        n = len(dataset)
+        if dataset.width != self.vae.width:
+            raise ValueError(f"the dataset holds {dataset.width}x{dataset.width} frames, the VAE takes {self.vae.width}x{self.vae.width}")
+        if not 1 <= int(batch_size) <= self.h.max_batch:
+            raise ValueError(f"batch_size {batch_size} outside 1..max_batch ({self.h.max_batch}) of the handle")
+        if dataset.frames.device != dev:
+            raise ValueError(f"the dataset is on {dataset.frames.device}, the VAE on {dev}")
+        B = int(batch_size)
+        x = torch.empty(B, P.ch, self.vae.width, self.vae.width, device=dev)
+        pred = torch.empty(B, 1, device=dev)
+        scal = None
+        for _ in range(epochs):
+            idx = np.arange(n)
+            if shuffle:
+                np.random.shuffle(idx)
+            d_idx = torch.from_numpy(idx).to(dev)          # indices of arange(n): in [0, n) by construction
+            for b in range(0, n, B):
+                nb = min(B, n - b)
+                self.h.preprocess_u8_gather(nb, dataset.frames, dataset.preds, d_idx[b:b + nb], x[:nb], pred[:nb])
+                eps = torch.randn(nb, P.latent_dim, device=dev, generator=generator)
+                scal = self.step(x[:nb], pred[:nb], eps)
+        return scal
+
     # time between "backward is done" and "the reduced gradient is usable" on the compute stream = the part
     # of the all-reduce that backward did not hide (bench.py: allreduce_exposed_us)
     def _exposed_begin(self):
@@ -315,11 +348,24 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=P.batch_size)
     ap.add_argument("--epochs", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--critic", default="random", help="'random' scalars (BASELINE config 1), 'synth' = the HIP "
-                    "critic with generator weights, or a path to a reference critic checkpoint (.pt)")
+    ap.add_argument("--critic", default=None, help="'random' scalars (BASELINE config 1; the default without --episodes), "
+                    "'synth' = the HIP critic with generator weights, or a path to a reference critic checkpoint (.pt)")
+    ap.add_argument("--episodes", nargs="+", metavar="PATH", default=None,
+                    help="train on recorded trajectories: .npy files (T,64,64,3) uint8 or directories of them, curated as "
+                         "load_minerl_data(critic) does (vae_utility.py:393-461); needs --critic")
+    ap.add_argument("--total-images", type=int, default=P.total_images, help="dataset size at which the walk over the "
+                    "trajectories stops (vae_parameters.py:19)")
+    ap.add_argument("--collect", type=int, default=P.collect, help="frames per critic-value bin and trajectory "
+                    "(vae_utility.py:404)")
     args = ap.parse_args(argv)
     if not args.train:
         ap.error("only -train is implemented (the hot path); see SURVEY.md §8 for scope")
+    if args.episodes is not None and args.critic in (None, "random"):
+        ap.error("--episodes needs --critic (a reference critic checkpoint, or 'synth'): the dataset is chosen by its values")
+    if args.critic is None:
+        args.critic = "random"
+    if args.episodes is not None:
+        return _train_episodes(args)
     if not torch.cuda.is_available():
         raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
     torch.manual_seed(args.seed)
@@ -330,12 +376,7 @@ def main(argv=None):
     if args.critic == "random":
         critic_fn = lambda im: torch.rand(im.shape[0], 1, device=im.device)      # noqa: E731
     else:                                  # critic.evaluate(images), vae.py:50 / vae_utility.py:363-370
-        from .critic import Critic
-        critic = Critic(handle=vae.handle).to(device)
-        sd = {k: torch.from_numpy(v) for k, v in synth.make_critic_params(args.seed).items()} \
-            if args.critic == "synth" else torch.load(args.critic, map_location="cpu")
-        critic.load_state_dict(sd)
-        critic_fn = critic.evaluate
+        critic_fn = _load_critic(args.critic, vae.handle, args.seed, device).evaluate
     t0 = time.time()
     _, hist = train(vae, dset, critic_fn, device,
                     epochs=args.epochs, batch_size=args.batch, log_n=args.batch * 8)
@@ -346,6 +387,48 @@ def main(argv=None):
         enc, dec = save_networks(vae, args.save)
         print(f"saved {enc} and {dec}")
     return hist
+
+
+def _load_critic(spec, handle, seed, device):
+    from .critic import Critic
+    critic = Critic(handle=handle).to(device)
+    sd = {k: torch.from_numpy(v) for k, v in synth.make_critic_params(seed).items()} \
+        if spec == "synth" else torch.load(spec, map_location="cpu")
+    critic.load_state_dict(sd)
+    return critic
+
+
+def _train_episodes(args):
+    """-train on recorded trajectories: curate (episodes.py) -> FusedTrainer.fit_device -> save_networks."""
+    from .episodes import curate, load_episodes
+    episodes = load_episodes(args.episodes)
+    if not torch.cuda.is_available():
+        raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    device = torch.device("cuda:0")
+    vae = VariationalAutoencoder(max_batch=args.batch, seed=args.seed).to(device)
+    critic = _load_critic(args.critic, vae.handle, args.seed, device)
+    t0 = time.time()
+    ds = curate(episodes, critic, collect=args.collect, total_images=args.total_images, device=device)
+    torch.cuda.synchronize()
+    print(f"curated {len(ds)} frames in {time.time() - t0:.2f} s")
+    if len(ds) == 0:
+        raise SystemExit("the curated dataset is empty: no frame of the trajectories falls in a critic-value bin")
+    trainer = FusedTrainer(vae)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(args.seed)
+    t0 = time.time()
+    scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    s = scal.cpu().numpy()
+    print(f"{args.epochs * len(ds) / dt:.1f} images/s over {args.epochs} epoch(s); last loss {s[0]:.6f} "
+          f"(recon {s[1]:.6f}, kld {s[2]:.6f})")
+    if args.save:
+        enc, dec = save_networks(vae, args.save)
+        print(f"saved {enc} and {dec}")
+    return ds
 
 
 if __name__ == "__main__":

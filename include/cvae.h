@@ -217,6 +217,56 @@ int cvae_critic_forward(cvae_handle h, int32_t batch, const float* x, const floa
  * (B,W,W,3) -> float (B,3,W,W) / 255, so that only 1 byte per value crosses PCIe. */
 int cvae_preprocess_u8(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, float* x, void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * The training set on the device: load_minerl_data(critic) (vae_utility.py:393-461, non-recon
+ * branch) over recorded trajectories, and the per-step batch gather out of the curated set.
+ *
+ * Selection rule (vae_utility.py:400-459).  Trajectories are walked in the caller's order
+ * (the reference: np.random.default_rng(seed=0).shuffle of the name list), frames in order;
+ * p = the critic value of the frame (preprocess_observation: fp32 CHW / 255).  Bins, tested in
+ * this order, all comparisons in float32 (edges fp32(0.4), fp32(0.6), fp32(0.7), 0.25):
+ *   mid 0.4 <= p <= 0.6, then high p >= 0.7, then low p <= 0.25; NaN falls in no bin.
+ * A frame is selected iff it has a bin and fewer than `collect` (150) earlier frames of its
+ * trajectory fell in the same bin (the reference's early break selects nothing extra).  Before
+ * each trajectory the walk stops if len(dset) >= total_images; the last trajectory taken may
+ * overshoot by up to 3*collect - 1, so a dataset of total_images - 1 + 3*collect frames always
+ * suffices.  Output order: trajectory order, then frame order.  Integer math, no atomics:
+ * deterministic.  Frame offsets are 64-bit.
+ * ---------------------------------------------------------------------------------------- */
+
+/* One chunk of whole trajectories: preds (n_frames) fp32 critic values, trajectory t = frames
+ * [traj_offsets[t], traj_offsets[t+1]) (int64, n_traj + 1 entries, traj_offsets[0] = 0, non-decreasing,
+ * last = n_frames).  running (int64, in/out): len(dset) before the chunk, advanced past it, so that
+ * consecutive calls reproduce one walk over all trajectories with no host round trip.  Outputs:
+ * counts (n_traj, 3) int64 = frames selected per bin (mid, high, low); first (n_traj) int64 = the
+ * trajectory's first dataset slot, i.e. len(dset) before it, or -1 if the cut came first (its
+ * counts are then 0); span (2) int64 = (first slot of the chunk, frames selected in it);
+ * sel[k] (k < span[1]; room for n_frames) = the chunk frame index of dataset slot span[0] + k.
+ * The handle only identifies the library; width is not used.  CVAE_EINVAL for null pointers,
+ * negative counts or collect < 1. */
+int cvae_curate_select(cvae_handle h, int32_t n_traj, const int64_t* traj_offsets, int64_t n_frames,
+                       const float* preds, int32_t collect, int64_t total_images, int64_t* running,
+                       int64_t* counts, int64_t* first, int64_t* span, int64_t* sel, void* stream);
+
+/* Copy the frames cvae_curate_select chose: dst_frames[span[0] + k] = src_frames[sel[k]] for
+ * k < span[1] (uint8 (.., W, W, 3), W = width = the handle's width, whole 16-byte loads and
+ * stores; both buffers 16-byte aligned), and dst_preds[span[0] + k] = src_preds[sel[k]] if both
+ * are given.  max_count (host) bounds span[1] (the chunk's n_frames); slots at or past `capacity`
+ * frames and sources outside [0, n_src) are skipped. */
+int cvae_gather_frames_u8(cvae_handle h, int32_t width, const uint8_t* src_frames, const float* src_preds_or_null,
+                          int64_t n_src, const int64_t* sel, int64_t max_count, const int64_t* span,
+                          uint8_t* dst_frames, float* dst_preds_or_null, int64_t capacity, void* stream);
+
+/* One training batch out of a device dataset: x[b] = frames_hwc[idx[b]] / 255 as (B, 3, W, W) fp32
+ * (bit-identical to cvae_preprocess_u8 on the gathered frames: (float)u8 / 255.0f) and pred[b] =
+ * preds[idx[b]], one launch.  frames_hwc (n_frames, W, W, 3) uint8, preds (n_frames) fp32, idx (B)
+ * int64 device; W = width = the handle's width, 1 <= batch <= max_batch, frames and x 16-byte aligned.
+ * Indices must already lie in [0, n_frames) (the caller validates them); one outside yields NaN
+ * for that image and is never read. */
+int cvae_preprocess_u8_gather(cvae_handle h, int32_t batch, int32_t width, const uint8_t* frames_hwc,
+                              const float* preds, int64_t n_frames, const int64_t* idx, float* x,
+                              float* pred, void* stream);
+
 /* Difference mask of the inference path (get_diff_image, vae_utility.py:256-277), batched:
  * diff (B,W,W) = 0.2989|dR| + 0.5870|dG| + 0.1140|dB| of recon_zero - recon_one (both (B,3,W,W)). */
 int cvae_diff_grey(cvae_handle h, int32_t batch, const float* recon_one, const float* recon_zero,
