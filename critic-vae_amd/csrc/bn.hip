@@ -11,6 +11,11 @@
 //           2x2 max (first maximum in scan order, like ATen) and the activation.
 // backward: g = da * act'(a) lives only at each window's argmax (recomputed from y), so
 //           sum(g) and sum(g*xhat) run over pooled pixels; dy = scale*(g - mean(g) - xhat*mean(g*xhat)).
+//
+// y, a, da, dy are fp32 or bf16 in HBM (precision mode 1); statistics, coefficients and partial sums stay fp32.  Each
+// elementwise pass is ONE kernel template over the storage type (Act<AT>, common.h): bn_pool_act_fwd_kernel<AT, ACT>,
+// bn_bwd_kernel<AT, ACT, MODE>, bn_bwd_stats_relu_kernel<AT>.  The types differ only in the channels a thread owns
+// (BnWidth<AT>) and in the access that loads them; mapping, summation order, tie rule and rounding points are shared.
 #include "common.h"
 
 struct BnGeom { int C, H, act; };                       // act: 0 relu, 1 tanh
@@ -18,18 +23,12 @@ static inline BnGeom bn_geom(int layer, int width) {
     const int s = width / 64;
     return BnGeom{kLayers[layer].cout, kLayers[layer].h * s, layer == 3 ? 1 : 0};
 }
-static inline void tile_geom(int H, int* imgs, int* pxPerImg, int* tilesPerImg) {
-    const int TW = H < 32 ? H : 32;
-    const int TH = (128 / TW) < H ? (128 / TW) : H;
-    *imgs = 128 / (TW * TH);
-    *pxPerImg = TW * TH;
-    *tilesPerImg = (H / TW) * (H / TH);
-}
 // geometry of the BatchNorm partials a layer's conv kernel emits: E1 (layer 0) reports one partial per
-// 16x32-pixel strip (conv_thin.hip), the others one per 128-pixel tile (conv_epilogue.h)
+// 16x32-pixel strip (conv_thin.hip), the others one per 128-pixel tile of Tile<H> (conv_epilogue.h; tile_geom, common.h)
 static inline void part_geom(int layer, int H, int* imgs, int* pxPerImg, int* tilesPerImg) {
     if (layer == 0) { *imgs = 1; *pxPerImg = 512; *tilesPerImg = (H / 16) * (H / 32); return; }
-    tile_geom(H, imgs, pxPerImg, tilesPerImg);
+    const TileGeom t = tile_geom(H);
+    *imgs = t.IMGS; *pxPerImg = t.PX_PER_IMG; *tilesPerImg = t.TILES_PER_IMG;
 }
 int bn_num_tiles(int layer, int width, int B) {
     const BnGeom g = bn_geom(layer, width);
@@ -92,33 +91,39 @@ __device__ __forceinline__ void bn_fwd_coef(int c, double S, double Q, double M,
     coef[c * 4 + 3] = invstd;
 }
 
-// stage B: merge the RA chunk sums (fp64), emit coef[c] = {scale, shift, mean, invstd}, update running
-// stats.  32 lanes per channel (RA <= 32), two channels per wave.
+// The RA chunk sums of channel c merged in fp64: lane r of 32 loads chunk r (RA <= 32), then a fixed xor-shuffle tree;
+// every lane ends with the sums.  The single-rank finalize and the cross-rank record both merge here, so that one rank
+// without an exchange reproduces the single-call step bit for bit.
+struct BnSums { double S, Q, M; };
+__device__ __forceinline__ BnSums bn_fwd_merge(const double* __restrict__ mid, int RA, int C, int c, int r) {
+    BnSums s{0.0, 0.0, 0.0};
+    if (r < RA) { s.S = mid[(size_t)r * 3 * C + c]; s.Q = mid[(size_t)r * 3 * C + C + c]; s.M = mid[(size_t)r * 3 * C + 2 * C + c]; }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) { s.S += __shfl_xor(s.S, o, 64); s.Q += __shfl_xor(s.Q, o, 64); s.M += __shfl_xor(s.M, o, 64); }
+    return s;
+}
+
+// stage B: merge the RA chunk sums, emit coef[c] = {scale, shift, mean, invstd}, update running stats.  32 lanes per
+// channel, two channels per wave.  Eval mode (train == 0): mid is not read, coef comes from the running statistics.
 __global__ __launch_bounds__(64) void bn_fwd_finalize_kernel(const double* __restrict__ mid, int RA, int C, double N,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              float* __restrict__ run_mean, float* __restrict__ run_var,
                                                              float* __restrict__ coef, int train) {
     const int c = blockIdx.x * 2 + (threadIdx.x >> 5), r = threadIdx.x & 31;
-    double S = 0.0, Q = 0.0, M = 0.0;
-    if (train && r < RA) { S = mid[(size_t)r * 3 * C + c]; Q = mid[(size_t)r * 3 * C + C + c]; M = mid[(size_t)r * 3 * C + 2 * C + c]; }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) { S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64); M += __shfl_xor(M, o, 64); }
+    const BnSums s = bn_fwd_merge(mid, train ? RA : 0, C, c, r);
     if (r != 0) return;
-    bn_fwd_coef(c, S, Q, M, N, gamma, beta, run_mean, run_var, coef, train);
+    bn_fwd_coef(c, s.S, s.Q, s.M, N, gamma, beta, run_mean, run_var, coef, train);
 }
 
-// Cross-rank path, record step: the same merge of the RA chunk sums, in the same order, written to this layer's slot of the
-// sync record as rec[c] = S, rec[C + c] = Q, rec[2C + c] = M (fp64).  Every term is a sum over tiles, so the records of
-// several ranks add up to the record of their union.  count != null: also *count = this rank's image count.
+// Cross-rank path, record step: the same merge, written to this layer's slot of the sync record as rec[c] = S,
+// rec[C + c] = Q, rec[2C + c] = M (fp64).  Every term is a sum over tiles, so the records of several ranks add up to the
+// record of their union.  count != null: also *count = this rank's image count.
 __global__ __launch_bounds__(64) void bn_fwd_record_kernel(const double* __restrict__ mid, int RA, int C, double* __restrict__ rec,
                                                            double* __restrict__ count, double images) {
     const int c = blockIdx.x * 2 + (threadIdx.x >> 5), r = threadIdx.x & 31;
-    double S = 0.0, Q = 0.0, M = 0.0;
-    if (r < RA) { S = mid[(size_t)r * 3 * C + c]; Q = mid[(size_t)r * 3 * C + C + c]; M = mid[(size_t)r * 3 * C + 2 * C + c]; }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) { S += __shfl_xor(S, o, 64); Q += __shfl_xor(Q, o, 64); M += __shfl_xor(M, o, 64); }
+    const BnSums s = bn_fwd_merge(mid, RA, C, c, r);
     if (r != 0) return;
-    rec[c] = S; rec[C + c] = Q; rec[2 * C + c] = M;
+    rec[c] = s.S; rec[C + c] = s.Q; rec[2 * C + c] = s.M;
     if (count && c == 0) *count = images;
 }
 
@@ -137,163 +142,210 @@ __global__ __launch_bounds__(64) void bn_fwd_finish_kernel(const double* __restr
 __device__ __forceinline__ float act_fwd(float v, int act) { return act ? tanhf(v) : fmaxf(v, 0.f); }
 __device__ __forceinline__ float act_bwd_from_out(float a, int act) { return act ? (1.f - a * a) : (a > 0.f ? 1.f : 0.f); }
 
-template <int ACT>
-__global__ __launch_bounds__(256) void bn_pool_act_fwd_kernel(const float* __restrict__ y, const float* __restrict__ coef,
-                                                              float* __restrict__ a, int C, int H, int64_t total) {
-    // grid-stride over (pooled pixel, channel quad): the stride (gridDim * 256) is a multiple of C/4, so a thread keeps its
-    // channel quad — scale / shift are loaded once per thread instead of once per output (8 extra loads beside 4 + 1 useful
-    // accesses: 4.6 TB/s against 5.6-5.9 for the backward apply pass); channel counts and frame sizes are powers of two
-    const int C4 = C / 4, HO = H / 2, csh = 31 - __builtin_clz(C4), hsh = 31 - __builtin_clz(HO);
-    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-    const int c4 = (int)(first & (C4 - 1));
-    float sc[4], sh[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const float2 cf = *reinterpret_cast<const float2*>(coef + (c4 * 4 + e) * 4); sc[e] = cf.x; sh[e] = cf.y; }
-    for (int64_t idx = first; idx < total; idx += stride) {
-        const int64_t pp = idx >> csh;
-        const int px = (int)(pp & (HO - 1)), py = (int)((pp >> hsh) & (HO - 1));
-        const int64_t ib = pp >> (2 * hsh);
-        const float* base = y + ((ib * H + 2 * py) * H + 2 * px) * C + c4 * 4;
-        float m[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const float4 v = *reinterpret_cast<const float4*>(base + ((p >> 1) * H + (p & 1)) * (int64_t)C);
-            const float n[4] = {fmaf(v.x, sc[0], sh[0]), fmaf(v.y, sc[1], sh[1]), fmaf(v.z, sc[2], sh[2]), fmaf(v.w, sc[3], sh[3])};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) m[e] = (p == 0 || n[e] > m[e]) ? n[e] : m[e];
-        }
-        float4 o = make_float4(act_fwd(m[0], ACT), act_fwd(m[1], ACT), act_fwd(m[2], ACT), act_fwd(m[3], ACT));
-        *reinterpret_cast<float4*>(a + pp * C + c4 * 4) = o;
-    }
-}
+// Channels a thread owns in the elementwise passes, per activation storage type (Act<AT>, common.h).  W: forward and
+// ReLU statistics, one 16-byte access per tensor row.  WB: backward; its fp32 form stays on per-lane scalar accesses
+// coalesced across the wave.  A::Vec<V> holds the stored form: elements widen to fp32 before any arithmetic ((float)v[e])
+// and round once where the result is packed (v[e] = (AT)x), whatever the type.
+template <typename AT> struct BnWidth;
+template <> struct BnWidth<float> { static constexpr int W = 4, WB = 1; };
+template <> struct BnWidth<__bf16> { static constexpr int W = 8, WB = 8; };
 
-// per pooled pixel / channel: g = da*act'(a) at the window argmax; returns argmax position and xhat there
-__device__ __forceinline__ void window_argmax(const float* base, int H, int C, int e, float sc, float sh, float mean,
-                                              float invstd, int* pos, float* xhat_max, float (&yv)[4]) {
-    float m = 0.f, ym = 0.f; int bp = 0;
+// element offset of channel 0 of the first pixel of pooled pixel pp's 2x2 window, and of window pixel p from there
+// (frame sizes are powers of two: no 64-bit divisions in the pixel loops)
+__device__ __forceinline__ size_t window_base(int64_t pp, int H, int C) {
+    const int HO = H / 2, hsh = 31 - __builtin_clz(HO);
+    const int px = (int)(pp & (HO - 1)), py = (int)((pp >> hsh) & (HO - 1));
+    const int64_t ib = pp >> (2 * hsh);
+    return (size_t)((ib * H + 2 * py) * H + 2 * px) * C;
+}
+__device__ __forceinline__ size_t window_px(int p, int H, int C) { return (size_t)((p >> 1) * H + (p & 1)) * C; }
+
+// one channel of a window: position of the first maximum of the normalised values in scan order (like ATen); returns y there
+__device__ __forceinline__ float window_argmax(const float (&yy)[4], float sc, float sh, int* pos) {
+    float m = 0.f, ym = 0.f;
+    *pos = 0;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        yv[p] = base[((p >> 1) * H + (p & 1)) * (int64_t)C + e];
-        const float n = fmaf(yv[p], sc, sh);
-        if (p == 0 || n > m) { m = n; bp = p; ym = yv[p]; }
+        const float n = fmaf(yy[p], sc, sh);
+        if (p == 0 || n > m) { m = n; *pos = p; ym = yy[p]; }
     }
-    *pos = bp;
-    *xhat_max = (ym - mean) * invstd;
+    return ym;
 }
 
+template <typename AT, int ACT>
+__global__ __launch_bounds__(256) void bn_pool_act_fwd_kernel(const float* __restrict__ y, const float* __restrict__ coef,
+                                                              float* __restrict__ a, int C, int H, int64_t total) {
+    using A = Act<AT>;
+    constexpr int V = BnWidth<AT>::W;
+    // grid-stride over (pooled pixel, channel group): the stride (gridDim * 256) is a multiple of C/V, so a thread keeps its
+    // channel group — scale / shift are loaded once per thread instead of once per output (fp32: 8 extra loads beside 4 + 1
+    // useful accesses, 4.6 TB/s against 5.6-5.9 for the backward apply pass); channel counts are powers of two
+    const int CV = C / V, csh = 31 - __builtin_clz(CV);
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const int cv = (int)(first & (CV - 1));
+    float sc[V], sh[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) { const float2 cf = *reinterpret_cast<const float2*>(coef + (cv * V + e) * 4); sc[e] = cf.x; sh[e] = cf.y; }
+    for (int64_t idx = first; idx < total; idx += stride) {
+        const int64_t pp = idx >> csh;
+        const size_t base = window_base(pp, H, C) + cv * V;
+        typename A::template Vec<V> yv[4], o;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) yv[p] = A::template ldv<V>(y, base + window_px(p, H, C));
+        float m[V];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const float n = fmaf((float)yv[p][e], sc[e], sh[e]);
+                m[e] = (p == 0 || n > m[e]) ? n : m[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) o[e] = (AT)act_fwd(m[e], ACT);
+        A::template stv<V>(a, (size_t)pp * C + cv * V, o);
+    }
+}
+
+// Backward over the pooled pixels: g = da*act'(a) at the window argmax (recomputed from y).
 // MODE 0: partial sums (sum g, sum g*xhat) per channel.  MODE 1: write dy, partial sums of dy.
-template <int ACT, int MODE>
+template <typename AT, int ACT, int MODE>
 __global__ __launch_bounds__(256) void bn_bwd_kernel(const float* __restrict__ y, const float* __restrict__ a,
                                                      const float* __restrict__ da, const float* __restrict__ coef,
                                                      const float* __restrict__ bcoef, float* __restrict__ dy,
                                                      float* __restrict__ part, int C, int H, int64_t totalPx, int64_t pxPerBlk) {
-    __shared__ float red[2][256];
-    const int HO = H / 2;
-    const int c = threadIdx.x % C, sub = threadIdx.x / C, NSUB = 256 / C;     // C <= 256, divides 256
-    const float sc = coef[c * 4], sh = coef[c * 4 + 1], mean = coef[c * 4 + 2], invstd = coef[c * 4 + 3];
-    float k1 = 0.f, k2 = 0.f;
-    if (MODE == 1) { k1 = bcoef[c * 2]; k2 = bcoef[c * 2 + 1]; }
+    using A = Act<AT>;
+    constexpr int V = BnWidth<AT>::WB;
+    __shared__ float red[2][256][V];
+    const int CV = C / V, cv = threadIdx.x % CV, sub = threadIdx.x / CV, NSUB = 256 / CV;     // C / V <= 256, divides 256
+    float sc[V], sh[V], mean[V], invstd[V], k1[V], k2[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        const int c = cv * V + e;
+        sc[e] = coef[c * 4]; sh[e] = coef[c * 4 + 1]; mean[e] = coef[c * 4 + 2]; invstd[e] = coef[c * 4 + 3];
+        k1[e] = MODE == 1 ? bcoef[c * 2] : 0.f; k2[e] = MODE == 1 ? bcoef[c * 2 + 1] : 0.f;
+    }
     const int64_t p0 = blockIdx.x * pxPerBlk;
     int64_t p1 = p0 + pxPerBlk; if (p1 > totalPx) p1 = totalPx;
-    float acc0 = 0.f, acc1 = 0.f;
-    for (int64_t pp = p0 + sub; pp < p1; pp += NSUB) {
-        const int hsh = 31 - __builtin_clz(HO);                        // HO is a power of two: no 64-bit divisions in the pixel loop
-        const int px = (int)(pp & (HO - 1)), py = (int)((pp >> hsh) & (HO - 1));
-        const int64_t ib = pp >> (2 * hsh);
-        const float* base = y + ((ib * H + 2 * py) * H + 2 * px) * C;
-        int pos; float xh; float yv[4];
-        window_argmax(base, H, C, c, sc, sh, mean, invstd, &pos, &xh, yv);
-        const float av = a[pp * C + c];
-        const float g = da[pp * C + c] * act_bwd_from_out(av, ACT);
-        if (MODE == 0) {
-            acc0 += g; acc1 += g * xh;
-        } else {
-            float* dbase = dy + ((ib * H + 2 * py) * H + 2 * px) * C;
+    float acc0[V], acc1[V];
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const float xhat = (yv[p] - mean) * invstd;
-                const float d = sc * ((p == pos ? g : 0.f) - k1 - xhat * k2);
-                dbase[((p >> 1) * H + (p & 1)) * (int64_t)C + c] = d;
-                acc0 += d;
+    for (int e = 0; e < V; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
+    for (int64_t pp = p0 + sub; pp < p1; pp += NSUB) {
+        const size_t base = window_base(pp, H, C) + cv * V;
+        typename A::template Vec<V> yv[4], out[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) yv[p] = A::template ldv<V>(y, base + window_px(p, H, C));
+        const auto av = A::template ldv<V>(a, (size_t)pp * C + cv * V), gv = A::template ldv<V>(da, (size_t)pp * C + cv * V);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float yy[4] = {(float)yv[0][e], (float)yv[1][e], (float)yv[2][e], (float)yv[3][e]};
+            int pos;
+            const float ym = window_argmax(yy, sc[e], sh[e], &pos);
+            const float g = (float)gv[e] * act_bwd_from_out((float)av[e], ACT);
+            if (MODE == 0) {
+                acc0[e] += g; acc1[e] += g * ((ym - mean[e]) * invstd[e]);
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const float xhat = (yy[p] - mean[e]) * invstd[e];
+                    const float d = sc[e] * ((p == pos ? g : 0.f) - k1[e] - xhat * k2[e]);
+                    out[p][e] = (AT)d;
+                    acc0[e] += d;
+                }
             }
         }
+        if (MODE == 1) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) A::template stv<V>(dy, base + window_px(p, H, C), out[p]);
+        }
     }
-    red[0][threadIdx.x] = acc0; red[1][threadIdx.x] = acc1;
+#pragma unroll
+    for (int e = 0; e < V; ++e) { red[0][threadIdx.x][e] = acc0[e]; red[1][threadIdx.x][e] = acc1[e]; }
     __syncthreads();
     if (sub == 0) {
-        for (int k = 1; k < NSUB; ++k) { acc0 += red[0][k * C + c]; acc1 += red[1][k * C + c]; }
-        if (MODE == 0) {
-            part[((size_t)blockIdx.x * 2) * C + c] = acc0;
-            part[((size_t)blockIdx.x * 2 + 1) * C + c] = acc1;
-        } else {
-            part[(size_t)blockIdx.x * C + c] = acc0;
+        for (int k = 1; k < NSUB; ++k)
+#pragma unroll
+            for (int e = 0; e < V; ++e) { acc0[e] += red[0][k * CV + cv][e]; acc1[e] += red[1][k * CV + cv][e]; }
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const int c = cv * V + e;
+            if (MODE == 0) {
+                part[((size_t)blockIdx.x * 2) * C + c] = acc0[e];
+                part[((size_t)blockIdx.x * 2 + 1) * C + c] = acc1[e];
+            } else {
+                part[(size_t)blockIdx.x * C + c] = acc0[e];
+            }
         }
     }
 }
 
 // ReLU blocks: the two backward sums need only the POOLED tensors.  g = da*[a>0]; at the window argmax
 // the normalised value is n = a (ReLU passed it through), and xhat = (n - beta)/gamma, so
-// sum(g) and sum(g*xhat) never touch the full-resolution y (3x less traffic than bn_bwd_kernel<0,0>).
-// Channels whose |gamma| is small (< 1e-2; exactly 0 included) cannot use that shortcut — the division
+// sum(g) and sum(g*xhat) never touch the full-resolution y (3x less traffic than bn_bwd_kernel<AT, 0, 0>).
+// Channels whose |gamma| is small (< 1e-2; exactly 0 and NaN included) cannot use that shortcut — the division
 // amplifies the rounding of a by 1/|gamma| and is undefined at 0 — and take xhat from y at the recomputed
-// argmax instead (the bn_bwd_kernel<0,0> formula), so dgamma stays correct and such a channel can recover.
-__global__ __launch_bounds__(256) void bn_bwd_stats_relu_kernel(const float* __restrict__ a, const float* __restrict__ da,
-                                                                const float* __restrict__ coef, float* __restrict__ part,
-                                                                int C, int64_t totalPx, int64_t pxPerBlk,
-                                                                const float* __restrict__ y, int H) {
-    __shared__ float red[2][256][4];
-    const int C4 = C / 4, c4 = threadIdx.x % C4, sub = threadIdx.x / C4, NSUB = 256 / C4, HO = H / 2;
-    float gam[4], bet[4];
-    bool tiny[4];
+// argmax instead (the bn_bwd_kernel<AT, 0, 0> formula), so dgamma stays correct and such a channel can recover.
+template <typename AT>
+__global__ __launch_bounds__(256) void bn_bwd_stats_relu_kernel(const float* __restrict__ y, const float* __restrict__ a,
+                                                                const float* __restrict__ da, const float* __restrict__ coef,
+                                                                const float*, float*,           // bcoef, dy: bn_bwd_kernel's parameter list
+                                                                float* __restrict__ part, int C, int H, int64_t totalPx, int64_t pxPerBlk) {
+    using A = Act<AT>;
+    constexpr int V = BnWidth<AT>::W;
+    __shared__ float red[2][256][V];
+    const int CV = C / V, cv = threadIdx.x % CV, sub = threadIdx.x / CV, NSUB = 256 / CV;
+    float gam[V], bet[V];
+    bool tiny[V], any_tiny = false;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = c4 * 4 + e;
+    for (int e = 0; e < V; ++e) {
+        const int c = cv * V + e;
         const float scale = coef[c * 4], shift = coef[c * 4 + 1], mean = coef[c * 4 + 2], invstd = coef[c * 4 + 3];
         const float g = scale / invstd;                       // gamma
         tiny[e] = !(fabsf(g) >= 1e-2f);
+        any_tiny = any_tiny || tiny[e];
         gam[e] = tiny[e] ? 0.f : 1.0f / g;
         bet[e] = shift + mean * scale;                        // beta
     }
-    const bool any_tiny = tiny[0] || tiny[1] || tiny[2] || tiny[3];
     const int64_t p0 = blockIdx.x * pxPerBlk;
     int64_t p1 = p0 + pxPerBlk; if (p1 > totalPx) p1 = totalPx;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t pp = p0 + sub; pp < p1; pp += NSUB) {
-        const float4 av = *reinterpret_cast<const float4*>(a + pp * C + c4 * 4);
-        const float4 gv = *reinterpret_cast<const float4*>(da + pp * C + c4 * 4);
-        const float aa[4] = {av.x, av.y, av.z, av.w}, gg[4] = {gv.x, gv.y, gv.z, gv.w};
+    float s1[V], s2[V];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float g = aa[e] > 0.f ? gg[e] : 0.f;
+    for (int e = 0; e < V; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+    for (int64_t pp = p0 + sub; pp < p1; pp += NSUB) {
+        const auto av = A::template ldv<V>(a, (size_t)pp * C + cv * V), gv = A::template ldv<V>(da, (size_t)pp * C + cv * V);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float aa = (float)av[e];
+            const float g = aa > 0.f ? (float)gv[e] : 0.f;
             s1[e] += g;
-            s2[e] += g * ((aa[e] - bet[e]) * gam[e]);
+            s2[e] += g * ((aa - bet[e]) * gam[e]);
         }
         if (any_tiny) {
-            const int hsh = 31 - __builtin_clz(HO);
-            const int px = (int)(pp & (HO - 1)), py = (int)((pp >> hsh) & (HO - 1));
-            const int64_t ib = pp >> (2 * hsh);
-            const float* base = y + ((ib * H + 2 * py) * H + 2 * px) * C;
+            const size_t base = window_base(pp, H, C);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
+            for (int e = 0; e < V; ++e) {
                 if (!tiny[e]) continue;
-                const int c = c4 * 4 + e;
-                int pos; float xh; float yv[4];
-                window_argmax(base, H, C, c, coef[c * 4], coef[c * 4 + 1], coef[c * 4 + 2], coef[c * 4 + 3], &pos, &xh, yv);
-                s2[e] += (aa[e] > 0.f ? gg[e] : 0.f) * xh;
+                const int c = cv * V + e;
+                float yy[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) yy[p] = A::ld(y, base + window_px(p, H, C) + c);
+                int pos;
+                const float ym = window_argmax(yy, coef[c * 4], coef[c * 4 + 1], &pos);
+                s2[e] += ((float)av[e] > 0.f ? (float)gv[e] : 0.f) * ((ym - coef[c * 4 + 2]) * coef[c * 4 + 3]);
             }
         }
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { red[0][threadIdx.x][e] = s1[e]; red[1][threadIdx.x][e] = s2[e]; }
+    for (int e = 0; e < V; ++e) { red[0][threadIdx.x][e] = s1[e]; red[1][threadIdx.x][e] = s2[e]; }
     __syncthreads();
     if (sub == 0) {
         for (int k = 1; k < NSUB; ++k)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { s1[e] += red[0][k * C4 + c4][e]; s2[e] += red[1][k * C4 + c4][e]; }
+            for (int e = 0; e < V; ++e) { s1[e] += red[0][k * CV + cv][e]; s2[e] += red[1][k * CV + cv][e]; }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            part[((size_t)blockIdx.x * 2) * C + c4 * 4 + e] = s1[e];
-            part[((size_t)blockIdx.x * 2 + 1) * C + c4 * 4 + e] = s2[e];
+        for (int e = 0; e < V; ++e) {
+            part[((size_t)blockIdx.x * 2) * C + cv * V + e] = s1[e];
+            part[((size_t)blockIdx.x * 2 + 1) * C + cv * V + e] = s2[e];
         }
     }
 }
@@ -329,191 +381,6 @@ __global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const double* __rest
     const float invN = (float)(1.0 / (double)(float)(count[0] * H * H));
     bcoef[c * 2] = (float)rec[c] * invN;
     bcoef[c * 2 + 1] = (float)rec[C + c] * invN;
-}
-
-// ------------------------------------------------------------------------------------------------
-// precision mode 1: y, a, da, dy are bf16 in HBM (statistics, coefficients and partial sums stay fp32).
-// One thread = 8 consecutive channels of one pooled pixel: every access is one 16-byte unit.
-// ------------------------------------------------------------------------------------------------
-template <int ACT>
-__global__ __launch_bounds__(256) void bn_pool_act_fwd_bf16_kernel(const float* __restrict__ y, const float* __restrict__ coef,
-                                                                   float* __restrict__ a, int C, int H, int64_t total) {
-    using A = Act<__bf16>;
-    // grid-stride, channel octet fixed per thread (see bn_pool_act_fwd_kernel): scale / shift loaded once per thread
-    const int C8 = C / 8, HO = H / 2, csh = 31 - __builtin_clz(C8), hsh = 31 - __builtin_clz(HO);
-    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-    const int c8 = (int)(first & (C8 - 1));
-    float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const float2 cf = *reinterpret_cast<const float2*>(coef + (c8 * 8 + e) * 4); sc[e] = cf.x; sh[e] = cf.y; }
-    for (int64_t idx = first; idx < total; idx += stride) {
-        const int64_t pp = idx >> csh;
-        const int px = (int)(pp & (HO - 1)), py = (int)((pp >> hsh) & (HO - 1));
-        const int64_t ib = pp >> (2 * hsh);
-        const size_t base = (size_t)((ib * H + 2 * py) * H + 2 * px) * C + c8 * 8;
-        bf16x8 v[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) v[p] = A::ld8(y, base + (size_t)((p >> 1) * H + (p & 1)) * C);
-        float m[8];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float n = fmaf((float)v[p][e], sc[e], sh[e]);
-                m[e] = (p == 0 || n > m[e]) ? n : m[e];
-            }
-        }
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (__bf16)act_fwd(m[e], ACT);
-        A::st8(a, (size_t)pp * C + c8 * 8, o);
-    }
-}
-
-// MODE 0: partial sums (sum g, sum g*xhat) per channel.  MODE 1: write dy, partial sums of dy.
-template <int ACT, int MODE>
-__global__ __launch_bounds__(256) void bn_bwd_bf16_kernel(const float* __restrict__ y, const float* __restrict__ a,
-                                                          const float* __restrict__ da, const float* __restrict__ coef,
-                                                          const float* __restrict__ bcoef, float* __restrict__ dy,
-                                                          float* __restrict__ part, int C, int H, int64_t totalPx, int64_t pxPerBlk) {
-    using A = Act<__bf16>;
-    __shared__ float red[2][256][8];
-    const int HO = H / 2, C8 = C / 8;
-    const int c8 = threadIdx.x % C8, sub = threadIdx.x / C8, NSUB = 256 / C8;
-    float sc[8], sh[8], mean[8], invstd[8], k1[8], k2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int c = c8 * 8 + e;
-        sc[e] = coef[c * 4]; sh[e] = coef[c * 4 + 1]; mean[e] = coef[c * 4 + 2]; invstd[e] = coef[c * 4 + 3];
-        k1[e] = MODE == 1 ? bcoef[c * 2] : 0.f; k2[e] = MODE == 1 ? bcoef[c * 2 + 1] : 0.f;
-    }
-    const int64_t p0 = blockIdx.x * pxPerBlk;
-    int64_t p1 = p0 + pxPerBlk; if (p1 > totalPx) p1 = totalPx;
-    float acc0[8], acc1[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
-    for (int64_t pp = p0 + sub; pp < p1; pp += NSUB) {
-        const int hsh = 31 - __builtin_clz(HO);                        // HO is a power of two: no 64-bit divisions in the pixel loop
-        const int px = (int)(pp & (HO - 1)), py = (int)((pp >> hsh) & (HO - 1));
-        const int64_t ib = pp >> (2 * hsh);
-        const size_t base = (size_t)((ib * H + 2 * py) * H + 2 * px) * C + c8 * 8;
-        bf16x8 yv[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) yv[p] = A::ld8(y, base + (size_t)((p >> 1) * H + (p & 1)) * C);
-        const bf16x8 av = A::ld8(a, (size_t)pp * C + c8 * 8), gv = A::ld8(da, (size_t)pp * C + c8 * 8);
-        bf16x8 out[4];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float mx = 0.f, ym = 0.f; int pos = 0;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const float yy = (float)yv[p][e], n = fmaf(yy, sc[e], sh[e]);
-                if (p == 0 || n > mx) { mx = n; pos = p; ym = yy; }
-            }
-            const float g = (float)gv[e] * act_bwd_from_out((float)av[e], ACT);
-            if (MODE == 0) {
-                acc0[e] += g; acc1[e] += g * ((ym - mean[e]) * invstd[e]);
-            } else {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float xhat = ((float)yv[p][e] - mean[e]) * invstd[e];
-                    const float d = sc[e] * ((p == pos ? g : 0.f) - k1[e] - xhat * k2[e]);
-                    out[p][e] = (__bf16)d;
-                    acc0[e] += d;
-                }
-            }
-        }
-        if (MODE == 1) {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) A::st8(dy, base + (size_t)((p >> 1) * H + (p & 1)) * C, out[p]);
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[0][threadIdx.x][e] = acc0[e]; red[1][threadIdx.x][e] = acc1[e]; }
-    __syncthreads();
-    if (sub == 0) {
-        for (int k = 1; k < NSUB; ++k)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { acc0[e] += red[0][k * C8 + c8][e]; acc1[e] += red[1][k * C8 + c8][e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int c = c8 * 8 + e;
-            if (MODE == 0) {
-                part[((size_t)blockIdx.x * 2) * C + c] = acc0[e];
-                part[((size_t)blockIdx.x * 2 + 1) * C + c] = acc1[e];
-            } else {
-                part[(size_t)blockIdx.x * C + c] = acc0[e];
-            }
-        }
-    }
-}
-
-// ReLU blocks, bf16 storage: the two backward sums from the pooled tensors alone (see bn_bwd_stats_relu_kernel)
-__global__ __launch_bounds__(256) void bn_bwd_stats_relu_bf16_kernel(const float* __restrict__ a, const float* __restrict__ da,
-                                                                     const float* __restrict__ coef, float* __restrict__ part,
-                                                                     int C, int64_t totalPx, int64_t pxPerBlk,
-                                                                     const float* __restrict__ y, int H) {
-    using A = Act<__bf16>;
-    __shared__ float red[2][256][8];
-    const int C8 = C / 8, c8 = threadIdx.x % C8, sub = threadIdx.x / C8, NSUB = 256 / C8, HO = H / 2;
-    float gam[8], bet[8];
-    bool tiny[8], any_tiny = false;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int c = c8 * 8 + e;
-        const float scale = coef[c * 4], shift = coef[c * 4 + 1], mean = coef[c * 4 + 2], invstd = coef[c * 4 + 3];
-        const float g = scale / invstd;
-        tiny[e] = !(fabsf(g) >= 1e-2f);
-        any_tiny = any_tiny || tiny[e];
-        gam[e] = tiny[e] ? 0.f : 1.0f / g;
-        bet[e] = shift + mean * scale;
-    }
-    const int64_t p0 = blockIdx.x * pxPerBlk;
-    int64_t p1 = p0 + pxPerBlk; if (p1 > totalPx) p1 = totalPx;
-    float s1[8], s2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    for (int64_t pp = p0 + sub; pp < p1; pp += NSUB) {
-        const bf16x8 av = A::ld8(a, (size_t)pp * C + c8 * 8), gv = A::ld8(da, (size_t)pp * C + c8 * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float aa = (float)av[e];
-            const float g = aa > 0.f ? (float)gv[e] : 0.f;
-            s1[e] += g;
-            s2[e] += g * ((aa - bet[e]) * gam[e]);
-        }
-        if (any_tiny) {
-            const int hsh = 31 - __builtin_clz(HO);
-            const int px = (int)(pp & (HO - 1)), py = (int)((pp >> hsh) & (HO - 1));
-            const int64_t ib = pp >> (2 * hsh);
-            const size_t base = (size_t)((ib * H + 2 * py) * H + 2 * px) * C;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if (!tiny[e]) continue;
-                const int c = c8 * 8 + e;
-                float mx = 0.f, ym = 0.f;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float yy = A::ld(y, base + (size_t)((p >> 1) * H + (p & 1)) * C + c), n = fmaf(yy, coef[c * 4], coef[c * 4 + 1]);
-                    if (p == 0 || n > mx) { mx = n; ym = yy; }
-                }
-                s2[e] += ((float)av[e] > 0.f ? (float)gv[e] : 0.f) * ((ym - coef[c * 4 + 2]) * coef[c * 4 + 3]);
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[0][threadIdx.x][e] = s1[e]; red[1][threadIdx.x][e] = s2[e]; }
-    __syncthreads();
-    if (sub == 0) {
-        for (int k = 1; k < NSUB; ++k)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] += red[0][k * C8 + c8][e]; s2[e] += red[1][k * C8 + c8][e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            part[((size_t)blockIdx.x * 2) * C + c8 * 8 + e] = s1[e];
-            part[((size_t)blockIdx.x * 2 + 1) * C + c8 * 8 + e] = s2[e];
-        }
-    }
 }
 
 static constexpr int BN_RA = 32;
@@ -576,24 +443,19 @@ int launch_bn_fwd_finish(int layer, int width, const double* rec, const double* 
     return 0;
 }
 
-int launch_bn_pool_act_fwd(int layer, int width, int B, const float* y, const float* coef, float* a, hipStream_t st, bool bf16io) {
-    const BnGeom g = bn_geom(layer, width);
-    if (bf16io) {
-        const int64_t total8 = (int64_t)B * (g.H / 2) * (g.H / 2) * (g.C / 8);
-        const int64_t want8 = (int64_t)cvae_num_cus() * 16;                  // grid-stride: 16 workgroups per CU
-        const unsigned grid8 = (unsigned)((total8 + 255) / 256 < want8 ? (total8 + 255) / 256 : want8);
-        if (g.act) hipLaunchKernelGGL(bn_pool_act_fwd_bf16_kernel<1>, dim3(grid8), dim3(256), 0, st, y, coef, a, g.C, g.H, total8);
-        else hipLaunchKernelGGL(bn_pool_act_fwd_bf16_kernel<0>, dim3(grid8), dim3(256), 0, st, y, coef, a, g.C, g.H, total8);
-        CVAE_CHECK_LAUNCH();
-        return 0;
-    }
-    const int64_t total = (int64_t)B * (g.H / 2) * (g.H / 2) * (g.C / 4);
-    const int64_t want = (int64_t)cvae_num_cus() * 16;
+template <typename AT, int ACT>
+static int bn_pool_act_fwd(const BnGeom& g, int B, const float* y, const float* coef, float* a, hipStream_t st) {
+    const int64_t total = (int64_t)B * (g.H / 2) * (g.H / 2) * (g.C / BnWidth<AT>::W);
+    const int64_t want = (int64_t)cvae_num_cus() * 16;                  // grid-stride: 16 workgroups per CU
     const unsigned grid = (unsigned)((total + 255) / 256 < want ? (total + 255) / 256 : want);
-    if (g.act) hipLaunchKernelGGL(bn_pool_act_fwd_kernel<1>, dim3(grid), dim3(256), 0, st, y, coef, a, g.C, g.H, total);
-    else hipLaunchKernelGGL(bn_pool_act_fwd_kernel<0>, dim3(grid), dim3(256), 0, st, y, coef, a, g.C, g.H, total);
+    hipLaunchKernelGGL((bn_pool_act_fwd_kernel<AT, ACT>), dim3(grid), dim3(256), 0, st, y, coef, a, g.C, g.H, total);
     CVAE_CHECK_LAUNCH();
     return 0;
+}
+int launch_bn_pool_act_fwd(int layer, int width, int B, const float* y, const float* coef, float* a, hipStream_t st, bool bf16io) {
+    const BnGeom g = bn_geom(layer, width);
+    if (bf16io) return g.act ? bn_pool_act_fwd<__bf16, 1>(g, B, y, coef, a, st) : bn_pool_act_fwd<__bf16, 0>(g, B, y, coef, a, st);
+    return g.act ? bn_pool_act_fwd<float, 1>(g, B, y, coef, a, st) : bn_pool_act_fwd<float, 0>(g, B, y, coef, a, st);
 }
 
 static inline int bn_bwd_blocks(int64_t totalPx, int C) {
@@ -614,6 +476,15 @@ const float* bn_bwd_bcoef(int layer, int width, int B, const float* ws) {
     return ws + (size_t)bn_bwd_blocks((int64_t)B * (g.H / 2) * (g.H / 2), g.C) * 2 * g.C;
 }
 
+// the two elementwise kernels of a backward, for one (storage type, activation): all take bn_bwd_kernel's parameters
+using BnBwdKernel = void (*)(const float*, const float*, const float*, const float*, const float*, float*, float*, int, int, int64_t, int64_t);
+struct BnBwdKernels { BnBwdKernel stats, apply; };
+template <typename AT, int ACT>
+static BnBwdKernels bn_bwd_kernels() {
+    if constexpr (ACT == 0) return {bn_bwd_stats_relu_kernel<AT>, bn_bwd_kernel<AT, 0, 1>};
+    else return {bn_bwd_kernel<AT, ACT, 0>, bn_bwd_kernel<AT, ACT, 1>};
+}
+
 // dy == nullptr: statistics only (dgamma, dbeta and the (k1, k2) pair at bn_bwd_bcoef(ws)); the caller's next kernel
 // applies the backward itself (block 0: launch_e1_wgrad's fused staging).
 // stage (cross-rank path): 0 = everything above; 1 = the statistics only, dgamma / dbeta plus this rank's (sum g, sum g*xhat)
@@ -632,11 +503,10 @@ int launch_bn_pool_act_bwd(int layer, int width, int B, const float* y, const fl
     float* red = bcoef + 2 * g.C;
     float* crws = red + 2 * g.C;
     const float invN = 1.0f / (float)((double)B * g.H * g.H);
+    const BnBwdKernels k = bf16io ? (g.act ? bn_bwd_kernels<__bf16, 1>() : bn_bwd_kernels<__bf16, 0>())
+                                  : (g.act ? bn_bwd_kernels<float, 1>() : bn_bwd_kernels<float, 0>());
     if (stage != 2) {
-        if (bf16io && g.act) hipLaunchKernelGGL((bn_bwd_bf16_kernel<1, 0>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, nullptr, nullptr, part, g.C, g.H, totalPx, ppb);
-        else if (bf16io) hipLaunchKernelGGL(bn_bwd_stats_relu_bf16_kernel, dim3(nblk), dim3(256), 0, st, a, da, coef, part, g.C, totalPx, ppb, y, g.H);
-        else if (g.act) hipLaunchKernelGGL((bn_bwd_kernel<1, 0>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, nullptr, nullptr, part, g.C, g.H, totalPx, ppb);
-        else hipLaunchKernelGGL(bn_bwd_stats_relu_kernel, dim3(nblk), dim3(256), 0, st, a, da, coef, part, g.C, totalPx, ppb, y, g.H);
+        hipLaunchKernelGGL(k.stats, dim3(nblk), dim3(256), 0, st, y, a, da, coef, nullptr, nullptr, part, g.C, g.H, totalPx, ppb);
         CVAE_CHECK_LAUNCH();
         const float* rows; int R; int64_t rstride;
         { int rc = launch_col_reduce_partial(part, nblk, 2 * g.C, 2 * g.C, crws, st, &rows, &R, &rstride); if (rc) return rc; }
@@ -653,10 +523,7 @@ int launch_bn_pool_act_bwd(int layer, int width, int B, const float* y, const fl
         return 0;
     }
     cvae_probe_begin(st);                       // the apply pass: reads y, a, da, writes dy — the step's largest HBM-bound kernel
-    if (bf16io && g.act) hipLaunchKernelGGL((bn_bwd_bf16_kernel<1, 1>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, bcoef, dy, part, g.C, g.H, totalPx, ppb);
-    else if (bf16io) hipLaunchKernelGGL((bn_bwd_bf16_kernel<0, 1>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, bcoef, dy, part, g.C, g.H, totalPx, ppb);
-    else if (g.act) hipLaunchKernelGGL((bn_bwd_kernel<1, 1>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, bcoef, dy, part, g.C, g.H, totalPx, ppb);
-    else hipLaunchKernelGGL((bn_bwd_kernel<0, 1>), dim3(nblk), dim3(256), 0, st, y, a, da, coef, bcoef, dy, part, g.C, g.H, totalPx, ppb);
+    hipLaunchKernelGGL(k.apply, dim3(nblk), dim3(256), 0, st, y, a, da, coef, bcoef, dy, part, g.C, g.H, totalPx, ppb);
     cvae_probe_end(st);
     CVAE_CHECK_LAUNCH();
     if (dbias) return launch_col_reduce(part, nblk, g.C, g.C, dbias, crws, st);   // else: the wgrad kernel provides it

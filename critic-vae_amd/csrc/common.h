@@ -21,6 +21,16 @@ template <> struct Act<float> {
     static __device__ __forceinline__ void st(float* p, size_t i, float v) { p[i] = v; }
     static __device__ __forceinline__ f32x4 ld4(const float* p, size_t i) { return *reinterpret_cast<const f32x4*>(p + i); }
     static __device__ __forceinline__ void st4(float* p, size_t i, f32x4 v) { *reinterpret_cast<f32x4*>(p + i) = v; }
+    // V consecutive elements in one access (bn.hip): a scalar or a float4.  v[e] reads / writes element e.
+    template <int V> using Vec = float __attribute__((ext_vector_type(V)));
+    template <int V> static __device__ __forceinline__ Vec<V> ldv(const float* p, size_t i) {
+        static_assert(V == 1 || V == 4, "fp32 storage: scalar or float4 accesses");
+        return *reinterpret_cast<const Vec<V>*>(p + i);
+    }
+    template <int V> static __device__ __forceinline__ void stv(float* p, size_t i, Vec<V> v) {
+        static_assert(V == 1 || V == 4, "fp32 storage: scalar or float4 accesses");
+        *reinterpret_cast<Vec<V>*>(p + i) = v;
+    }
 };
 template <> struct Act<__bf16> {
     static constexpr bool BF16 = true;
@@ -39,6 +49,16 @@ template <> struct Act<__bf16> {
     // 8 consecutive elements = one 16-byte unit
     static __device__ __forceinline__ bf16x8 ld8(const float* p, size_t i) { return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const __bf16*>(p) + i); }
     static __device__ __forceinline__ void st8(float* p, size_t i, bf16x8 v) { *reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(p) + i) = v; }
+    // V consecutive elements in one access (bn.hip): the 16-byte unit.  (float)v[e] widens, v[e] = (__bf16)x rounds.
+    template <int V> using Vec = __bf16 __attribute__((ext_vector_type(V)));
+    template <int V> static __device__ __forceinline__ Vec<V> ldv(const float* p, size_t i) {
+        static_assert(V == 8, "bf16 storage: 16-byte units of 8 elements");
+        return ld8(p, i);
+    }
+    template <int V> static __device__ __forceinline__ void stv(float* p, size_t i, Vec<V> v) {
+        static_assert(V == 8, "bf16 storage: 16-byte units of 8 elements");
+        st8(p, i, v);
+    }
 };
 
 // 8 k-values of this lane for one bf16 MFMA operand out of a row-major [k rows][channel columns] LDS image: two
@@ -66,17 +86,23 @@ static constexpr LayerDesc kLayers[9] = {
     {256, 128, 4, 0}, {128, 64, 8, 1}, {64, 32, 16, 1}, {32, 32, 32, 1}, {32, 3, 64, 1}};
 
 // ---- output-tile geometry shared by the conv kernels: 128 output pixels per workgroup ----
+// One arithmetic for the kernels (Tile<H>) and for the host side that sizes and reads the per-tile BatchNorm partials (bn.hip).
+struct TileGeom { int TW, TH, IMGS, PX_PER_IMG, TILES_PER_IMG; };
+__host__ __device__ constexpr TileGeom tile_geom(int H) {
+    const int TW = H < 32 ? H : 32;
+    const int TH = (128 / TW) < H ? (128 / TW) : H;
+    return TileGeom{TW, TH, 128 / (TW * TH), TW * TH, (H / TW) * (H / TH)};
+}
 template <int H>
 struct Tile {
-    static constexpr int TW = H < 32 ? H : 32;
-    static constexpr int TH = (128 / TW) < H ? (128 / TW) : H;
-    static constexpr int IMGS = 128 / (TW * TH);        // whole images per tile when H*H < 128
+    static constexpr int TW = tile_geom(H).TW, TH = tile_geom(H).TH;
+    static constexpr int IMGS = tile_geom(H).IMGS;       // whole images per tile when H*H < 128
     static constexpr int HTW = TW + 4, HTH = TH + 4;     // halo for the 5x5 window
     static constexpr int HPI = HTW * HTH;                // halo pixels per image
     static constexpr int HP = IMGS * HPI;
     static constexpr int PS = ((HP + 5) / 8) * 8 + 2;    // LDS plane stride, == 2 (mod 8), >= HP
     static constexpr int TILES_X = H / TW, TILES_Y = H / TH;
-    static constexpr int TILES_PER_IMG = TILES_X * TILES_Y;
+    static constexpr int TILES_PER_IMG = tile_geom(H).TILES_PER_IMG;
     static_assert(TW * TH * IMGS == 128, "tile must hold 128 pixels");
 };
 

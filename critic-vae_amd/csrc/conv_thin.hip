@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256, THIN_F32_OCC) void e1_fwd_kernel(const float* 
 // step's MFMA work, the tensor it produces is the step's largest):
 //   E1_Y     : y1 + BatchNorm partials (the stand-alone conv op).
 //   E1_STATS : BatchNorm partials only — nothing but x is read, 2 x 32 floats per strip are written.
-//   E1_POOL  : after the statistics are merged: on the bf16-rounded conv values, exactly as bn_pool_act_fwd_bf16_kernel<0>
+//   E1_POOL  : after the statistics are merged: on the bf16-rounded conv values, exactly as bn_pool_act_fwd_kernel<__bf16, 0>
 //              would compute from a stored y1, scale/shift -> first maximum of each 2x2 window in scan order -> ReLU -> a1.
 //              y1 ITSELF IS NOT WRITTEN (round 3): the only reader left in the step, E1's weight-gradient kernel, runs the
 //              75-tap conv a third time on the tile it stages (e1_wgrad_bf16_kernel<H, true>) — B*H*H*32*2 bytes less
@@ -401,7 +401,7 @@ __device__ __forceinline__ void thin_slab_out(f32x16 (&acc)[3], float* red, floa
 // FUSE: the weight-gradient kernels take E1's BatchNorm/MaxPool/ReLU backward in while they stage a tile, instead of
 // reading a dy tensor that bn.hip's apply pass wrote (nothing else reads dy of block 0 — E1 has no input gradient):
 // per 2x2 window and channel, dy[p] = scale*((p == argmax ? g : 0) - k1 - xhat[p]*k2) with g = da*[a > 0],
-// xhat = (y - mean)*invstd and (k1, k2) = bcoef — the arithmetic of bn_bwd_kernel<0,1>, so the result is the
+// xhat = (y - mean)*invstd and (k1, k2) = bcoef — the arithmetic of bn_bwd_kernel<AT, 0, 1>, so the result is the
 // same to the bit; the step saves one write and one read of the largest activation gradient (B x 64 x 64 x 32).
 struct E1Fuse { const float *y, *a, *da, *coef, *bcoef, *w, *bias; };     // w, bias: E1's conv parameters (bf16 mode recomputes y)
 

@@ -5,8 +5,8 @@
 
 bytes = 2 * FETCH_SIZE + WRITE_SIZE (both in KiB; FETCH_SIZE under-reports wide streaming reads by exactly 2x on gfx950 —
 MI355X_MICROARCH.md, HBM section), averaged over the launches in the pass.  The x2 is calibrated on this code's own
-access shapes by the BatchNorm apply kernels, whose byte counts are known exactly: fp32 `bn_bwd_kernel<0,1>` (16-byte
-float4 accesses) 168.1 MB counted vs 167.8 MB algorithmic, bf16 `bn_bwd_bf16_kernel<0,1>` (16-byte units of 8 bf16,
+access shapes by the BatchNorm apply kernels, whose byte counts are known exactly: fp32 `bn_bwd_kernel<float, 0, 1>` (per-lane
+scalar accesses, a wave covering whole 256-byte runs) 168.1 MB counted vs 167.8 MB algorithmic, bf16 `bn_bwd_kernel<__bf16, 0, 1>` (16-byte units of 8 bf16,
 4 lanes per 64-byte pixel row — the access shape of the bf16 conv / weight-gradient staging loads) 503.9 MB vs 503.3 MB.
 bench.py reads the result for `roofline.traffic` / `roofline_hbm.traffic` of the same workload (key = precision_bB_wW).
 """
@@ -74,8 +74,13 @@ def patterns(prec, width):
 
 
 def bn_names(prec):
-    base = "bn_bwd_kernel" if prec == "f32" else "bn_bwd_bf16_kernel"
-    return f"void {base}<0, 1>", f"void {base}<1, 1>"       # ReLU blocks 2, 1 (in launch order; block 0 is fused into E1's wgrad) / Tanh block 3
+    """regexes for the apply kernels bn_bwd_kernel<AT, ACT, 1> (bn.hip): ReLU blocks 2, 1 (in launch order; block 0 is fused
+    into E1's wgrad) / Tanh block 3.  The profiler's demangler does not know __bf16 (DF16b): it prints those names mangled,
+    or demangles them to `<bool _Accum, int, E, 1>`."""
+    if prec == "f32":
+        return r"void bn_bwd_kernel<float, 0, 1>", r"void bn_bwd_kernel<float, 1, 1>"
+    return (r"bn_bwd_kernel(<__bf16, 0, 1>|IDF16bLi0ELi1EE)",
+            r"bn_bwd_kernel(<__bf16, 1, 1>|IDF16bLi1ELi1EE|<bool _Accum, int, E, 1>)")
 
 
 def load(d, counter):
@@ -102,12 +107,12 @@ def one(prec, width, fdir, wdir):
         if f and w:
             out[name] = round(2 * sum(f) / len(f) + sum(w) / len(w))
     relu, tanh = bn_names(prec)
-    f, w = pick(fetch, re.escape(relu)), pick(write, re.escape(relu))
+    f, w = pick(fetch, relu), pick(write, relu)
     for i, layer in enumerate((2, 1)):
         fi, wi = f[i::2], w[i::2]
         if fi and wi:
             out[f"bn_pool_bwd_apply_L{layer}"] = round(2 * sum(fi) / len(fi) + sum(wi) / len(wi))
-    f, w = pick(fetch, re.escape(tanh)), pick(write, re.escape(tanh))
+    f, w = pick(fetch, tanh), pick(write, tanh)
     if f and w:
         out["bn_pool_bwd_apply_L3"] = round(2 * sum(f) / len(f) + sum(w) / len(w))
     return out

@@ -305,7 +305,7 @@ def check_bf16_stored_operands(h, tr, B, x, pred, eps, theta, bn_before, bn_afte
         wk, bk = f"encoder.model.{4 * l}.weight", f"encoder.model.{4 * l}.bias"
         cf, (sc, sh, mn, istd), yw, nw_ = windows(l, co, s)
         a_st = act(f"a{l}", co, s // 2).double()
-        # -- backward statistics (bn_bwd_stats_relu_bf16 / bn_bwd_bf16<1, 0>) -> dgamma = s2, dbeta = s1, k = s / N --
+        # -- backward statistics (bn_bwd_stats_relu_kernel<__bf16> / bn_bwd_kernel<__bf16, 1, 0>) -> dgamma = s2, dbeta = s1, k = s / N --
         da = act(f"d_a{l}", co, s // 2).double()
         g = da * (1.0 - a_st ** 2) if l == 3 else da * (a_st > 0)
         pos = nw_.argmax(dim=-1, keepdim=True)                         # first maximum in scan order, as the kernels take it
