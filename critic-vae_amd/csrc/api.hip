@@ -757,6 +757,50 @@ int cvae_preprocess_u8_gather(cvae_handle h, int32_t batch, int32_t width, const
     return launch_preprocess_u8_gather(width, batch, frames_hwc, preds, n_frames, idx, x, pred, (hipStream_t)stream);
 }
 
+// ---- the recon branch of the same walk (vae_utility.py:422-443): the second VAE's dataset ----
+int cvae_curate_select_recon(cvae_handle h, int32_t n_traj, const int64_t* traj_offsets, int64_t n_frames, const float* preds,
+                             int32_t collect, int64_t total_images, int64_t* running, int64_t* counts, int64_t* first,
+                             int64_t* sel_first, int64_t* span, int64_t* ent_frame, int32_t* ent_kind, int64_t* ent_sel,
+                             int64_t* sel, void* stream) {
+    if (!h) { cvae_set_error("cvae_curate_select_recon: null handle"); return CVAE_EINVAL; }
+    if (n_traj < 0 || n_frames < 0 || total_images < 0) {
+        cvae_set_error("cvae_curate_select_recon: n_traj %d, n_frames %lld, total_images %lld must be >= 0", n_traj,
+                       (long long)n_frames, (long long)total_images);
+        return CVAE_EINVAL;
+    }
+    if (collect < 1) { cvae_set_error("cvae_curate_select_recon: collect %d must be >= 1", collect); return CVAE_EINVAL; }
+    if (!running || !span || (n_traj > 0 && (!traj_offsets || !counts || !first || !sel_first)) ||
+        (n_frames > 0 && (!preds || !ent_frame || !ent_kind || !ent_sel || !sel))) {
+        cvae_set_error("cvae_curate_select_recon: null pointer"); return CVAE_EINVAL;
+    }
+    return launch_curate_select_recon(n_traj, traj_offsets, n_frames, preds, collect, total_images, running, counts, first,
+                                      sel_first, span, ent_frame, ent_kind, ent_sel, sel, (hipStream_t)stream);
+}
+
+int cvae_recon_zcat(cvae_handle h, int32_t n_entries, const int64_t* ent_sel, const int32_t* ent_kind, const float* mu,
+                    const float* sel_preds, int64_t n_sel, float* zcat, void* stream) {
+    if (!h) { cvae_set_error("cvae_recon_zcat: null handle"); return CVAE_EINVAL; }
+    if (n_entries < 1 || n_entries > h->cfg.max_batch) {
+        cvae_set_error("cvae_recon_zcat: n_entries %d outside [1, %d]", n_entries, h->cfg.max_batch); return CVAE_EINVAL;
+    }
+    if (n_sel < 1) { cvae_set_error("cvae_recon_zcat: n_sel %lld must be >= 1", (long long)n_sel); return CVAE_EINVAL; }
+    if (!ent_sel || !ent_kind || !mu || !sel_preds || !zcat) { cvae_set_error("cvae_recon_zcat: null pointer"); return CVAE_EINVAL; }
+    return launch_recon_zcat(n_entries, ent_sel, ent_kind, mu, sel_preds, n_sel, zcat, (hipStream_t)stream);
+}
+
+int cvae_gather_f32(cvae_handle h, int32_t batch, int32_t width, const float* frames, const float* preds, int64_t n_frames,
+                    const int64_t* idx, float* x, float* pred, void* stream) {
+    if (!h) { cvae_set_error("cvae_gather_f32: null handle"); return CVAE_EINVAL; }
+    if (width != h->cfg.width) { cvae_set_error("cvae_gather_f32: width %d, the handle's is %d", width, h->cfg.width); return CVAE_EINVAL; }
+    if (batch < 1 || batch > h->cfg.max_batch) { cvae_set_error("cvae_gather_f32: batch %d outside [1, %d]", batch, h->cfg.max_batch); return CVAE_EINVAL; }
+    if (n_frames < 1) { cvae_set_error("cvae_gather_f32: n_frames %lld must be >= 1", (long long)n_frames); return CVAE_EINVAL; }
+    if (!frames || !preds || !idx || !x || !pred) { cvae_set_error("cvae_gather_f32: null pointer"); return CVAE_EINVAL; }
+    if (((uintptr_t)frames & 15) || ((uintptr_t)x & 15)) {
+        cvae_set_error("cvae_gather_f32: frames and x must be 16-byte aligned"); return CVAE_EINVAL;
+    }
+    return launch_gather_f32(width, batch, frames, preds, n_frames, idx, x, pred, (hipStream_t)stream);
+}
+
 // |recon_zero - recon_one| -> greyscale difference mask (get_diff_image, vae_utility.py:256-277), batched
 int cvae_diff_grey(cvae_handle h, int32_t B, const float* recon_one, const float* recon_zero, float* diff, void* stream) {
     if (!h || B < 1) { cvae_set_error("cvae_diff_grey: bad handle/batch"); return CVAE_EINVAL; }

@@ -328,6 +328,14 @@ int launch_gather_frames_u8(int width, const uint8_t* src, const float* src_pred
                             hipStream_t st);
 int launch_preprocess_u8_gather(int width, int B, const uint8_t* frames, const float* preds, int64_t n, const int64_t* idx,
                                 float* x, float* pred, hipStream_t st);
+int launch_curate_select_recon(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
+                               int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* sel_first,
+                               int64_t* span, int64_t* ent_frame, int32_t* ent_kind, int64_t* ent_sel, int64_t* sel,
+                               hipStream_t st);
+int launch_recon_zcat(int n_entries, const int64_t* ent_sel, const int32_t* ent_kind, const float* mu, const float* sel_pred,
+                      int64_t n_sel, float* zcat, hipStream_t st);
+int launch_gather_f32(int width, int B, const float* frames, const float* preds, int64_t n, const int64_t* idx, float* x,
+                      float* pred, hipStream_t st);
 int launch_diff_grey(int width, int B, const float* a, const float* b, float* diff, hipStream_t st);
 // segment.hip
 int64_t crf_scratch_bytes(int width, int B);

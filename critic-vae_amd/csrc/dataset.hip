@@ -9,6 +9,15 @@
 //   gather_frames_u8      the selected uint8 frames (and their critic values) into the dataset buffer at their slots.
 //   preprocess_u8_gather  x[b] = frames[idx[b]] / 255 as CHW fp32 and pred[b] = preds[idx[b]]: one training batch.
 //
+// and the recon branch of the same walk (vae_utility.py:422-443: the dataset of the second VAE holds the first VAE's
+// eval-mode reconstructions, two entries for a mid frame):
+//
+//   curate_select_recon   the same three kernels with entry weight 2 / 1 / 1 (mid / high / low) in the cut and in the slot
+//                         positions (template parameter MIDW; MIDW = 1 is curate_select), plus per entry its frame and kind
+//                         and per selected frame its chunk index, so that the encoder runs once per selected frame.
+//   recon_zcat            zcat rows (mu of the entry's frame, its critic value or 0) for cvae_decode into the dataset slots.
+//   gather_f32            x[b] = frames[idx[b]] (fp32 CHW, bit copy) and pred[b] = preds[idx[b]]: one training batch.
+//
 // Integer math only, no atomics: every result is deterministic.  Frame offsets are 64-bit (a 64x64 dataset passes
 // 2^31 bytes at 174 763 frames).
 #include "common.h"
@@ -64,18 +73,23 @@ __global__ __launch_bounds__(TPB) void curate_count_kernel(const float* __restri
 // one workgroup, trajectories in order: trajectory t is visited iff running + (frames selected by the visited ones
 // before it) < total_images — the running count only grows, so that is an exclusive prefix sum compared with the cut.
 // first[t] = its first dataset slot (the reference's len(dset) before it) or -1; counts of unvisited ones become 0.
+// MIDW = the dataset entries of a mid frame (2 in the recon branch: vae_utility.py:434-435); the recon form also scans the
+// selected FRAMES of the chunk: ffirst[t] = frames selected in this chunk before trajectory t (or -1), span[2] = their total.
+template <int MIDW>
 __global__ __launch_bounds__(TPB) void curate_cut_kernel(int n_traj, int64_t total_images, int64_t* __restrict__ running,
                                                          int64_t* __restrict__ counts, int64_t* __restrict__ first,
-                                                         int64_t* __restrict__ span) {
+                                                         int64_t* __restrict__ span, int64_t* __restrict__ ffirst) {
     __shared__ int64_t wsum[NWAVE];
     __shared__ int64_t carry;
+    __shared__ int64_t fsum[NWAVE];                              // MIDW > 1 only: the same scan over frames
+    __shared__ int64_t fcarry;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t r0 = *running;
-    if (tid == 0) carry = r0;
+    if (tid == 0) { carry = r0; fcarry = 0; }
     __syncthreads();
     for (int t0 = 0; t0 < n_traj; t0 += TPB) {
         const int t = t0 + tid;
-        const int64_t s = t < n_traj ? counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2] : 0;
+        const int64_t s = t < n_traj ? MIDW * counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2] : 0;
         int64_t incl = s;                                        // inclusive scan within the wave
         for (int d = 1; d < 64; d <<= 1) {
             const int64_t v = __shfl_up(incl, d, 64);
@@ -87,34 +101,57 @@ __global__ __launch_bounds__(TPB) void curate_cut_kernel(int n_traj, int64_t tot
         for (int w = 0; w < wv; ++w) before += wsum[w];
         before += incl - s;                                      // len(dset) before trajectory t
         const int64_t block_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        const bool visited = t < n_traj && before < total_images;
         if (t < n_traj) {
-            if (before < total_images) {
+            if (visited) {
                 first[t] = before;
             } else {
                 first[t] = -1;
                 counts[(int64_t)t * 3] = counts[(int64_t)t * 3 + 1] = counts[(int64_t)t * 3 + 2] = 0;
             }
         }
+        int64_t fblock = 0;
+        if constexpr (MIDW > 1) {                                // visited trajectories are a prefix: unvisited ones add 0
+            const int64_t sf = visited ? counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2] : 0;
+            int64_t fi = sf;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int64_t v = __shfl_up(fi, d, 64);
+                if (lane >= d) fi += v;
+            }
+            if (lane == 63) fsum[wv] = fi;
+            __syncthreads();
+            int64_t fb = fcarry;
+            for (int w = 0; w < wv; ++w) fb += fsum[w];
+            if (t < n_traj) ffirst[t] = visited ? fb + fi - sf : -1;
+            fblock = fsum[0] + fsum[1] + fsum[2] + fsum[3];
+        }
         __syncthreads();
-        if (tid == 0) carry += block_total;
+        if (tid == 0) { carry += block_total; fcarry += fblock; }
         __syncthreads();
     }
     // the visited trajectories are a prefix: the new running count is the last visited one's first + its selection
     if (tid == 0) {
         int64_t r = r0;
         for (int t = n_traj - 1; t >= 0; --t)
-            if (first[t] >= 0) { r = first[t] + counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2]; break; }
+            if (first[t] >= 0) { r = first[t] + MIDW * counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2]; break; }
         span[0] = r0; span[1] = r - r0;
+        if constexpr (MIDW > 1) span[2] = fcarry;
         *running = r;
     }
 }
 
 // one workgroup per visited trajectory: frames in order, a frame is kept iff it has a bin and fewer than `collect`
-// earlier frames of the trajectory fell in that bin; sel[first[t] - span[0] + rank] = its chunk frame index
+// earlier frames of the trajectory fell in that bin; sel[first[t] - span[0] + rank] = its chunk frame index.
+// MIDW = 2 (recon branch): a kept mid frame owns two consecutive entries (kind 0, then kind 1), a high frame one of kind 0, a
+// low frame one of kind 1; per entry e (chunk-relative) sel[e] = the chunk frame index, kind[e], esel[e] = the frame's rank
+// among the chunk's selected frames, and fsel[that rank] = the chunk frame index.
+template <int MIDW>
 __global__ __launch_bounds__(TPB) void curate_scatter_kernel(const float* __restrict__ preds, const int64_t* __restrict__ off,
                                                              int64_t n_frames, int collect, const int64_t* __restrict__ first,
-                                                             const int64_t* __restrict__ span, int64_t* __restrict__ sel) {
-    __shared__ int wcnt[NWAVE][4];
+                                                             const int64_t* __restrict__ span, int64_t* __restrict__ sel,
+                                                             const int64_t* __restrict__ ffirst, int32_t* __restrict__ kind,
+                                                             int64_t* __restrict__ esel, int64_t* __restrict__ fsel) {
+    __shared__ int wcnt[NWAVE][5];
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t f = first[t];
     if (f < 0) return;
@@ -122,6 +159,7 @@ __global__ __launch_bounds__(TPB) void curate_scatter_kernel(const float* __rest
     traj_range(off, t, n_frames, lo, hi);
     const int64_t base = f - span[0];
     int64_t carry[3] = {0, 0, 0}, taken = 0;                    // identical in every thread
+    [[maybe_unused]] int64_t taken_mid = 0;                      // MIDW > 1: kept mid frames so far
     const uint64_t below = lanes_below(lane);
     for (int64_t b0 = lo; b0 < hi; b0 += TPB) {
         if (carry[0] >= collect && carry[1] >= collect && carry[2] >= collect) break;
@@ -142,18 +180,40 @@ __global__ __launch_bounds__(TPB) void curate_scatter_kernel(const float* __rest
         const bool keep = k >= 0 && prev < collect;
         const uint64_t mk = __ballot(keep);
         if (lane == 0) wcnt[wv][3] = __popcll(mk);
+        [[maybe_unused]] uint64_t mm = 0;
+        if constexpr (MIDW > 1) {
+            mm = __ballot(keep && k == 0);
+            if (lane == 0) wcnt[wv][4] = __popcll(mm);
+        }
         __syncthreads();
         if (keep) {
             int64_t pos = taken + __popcll(mk & below);
             for (int w = 0; w < wv; ++w) pos += wcnt[w][3];
-            pos += base;
-            if (pos >= 0 && pos < n_frames) sel[pos] = i;
+            if constexpr (MIDW == 1) {
+                pos += base;
+                if (pos >= 0 && pos < n_frames) sel[pos] = i;
+            } else {
+                int64_t mids = taken_mid + __popcll(mm & below);     // kept mid frames before this one
+                for (int w = 0; w < wv; ++w) mids += wcnt[w][4];
+                const int64_t fr = ffirst[t] + pos;                  // rank among the chunk's selected frames
+                const int64_t e = base + pos + (MIDW - 1) * mids;    // its first entry, chunk-relative
+                if (fr >= 0 && fr < n_frames) fsel[fr] = i;
+                const int ne = k == 0 ? MIDW : 1;
+                for (int j = 0; j < ne; ++j)
+                    if (fr >= 0 && fr < n_frames && e + j >= 0 && e + j < MIDW * n_frames) {
+                        sel[e + j] = i;
+                        kind[e + j] = k == 0 ? j : (k == 2);
+                        esel[e + j] = fr;
+                    }
+            }
         }
         for (int q = 0; q < 4; ++q) {
             int64_t s = 0;
             for (int w = 0; w < NWAVE; ++w) s += wcnt[w][q];
             if (q < 3) carry[q] += s; else taken += s;
         }
+        if constexpr (MIDW > 1)
+            for (int w = 0; w < NWAVE; ++w) taken_mid += wcnt[w][4];
         __syncthreads();
     }
 }
@@ -208,7 +268,85 @@ __global__ __launch_bounds__(TPB) void preprocess_u8_gather_kernel(const uint8_t
     if (g == 0) pred[b] = preds[s];
 }
 
+// one thread per zcat element: row e = (mu of selected frame esel[e], kind[e] == 0 ? that frame's critic value : 0);
+// an esel outside [0, n_sel) yields a NaN row (never read)
+__global__ __launch_bounds__(TPB) void recon_zcat_kernel(const int64_t* __restrict__ esel, const int32_t* __restrict__ kind,
+                                                         const float* __restrict__ mu, const float* __restrict__ spred,
+                                                         int64_t n_sel, int n_entries, float* __restrict__ zcat) {
+    const int64_t g = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (g >= (int64_t)n_entries * 33) return;
+    const int e = (int)(g / 33), c = (int)(g % 33);
+    const int64_t s = esel[e];
+    float v = __builtin_nanf("");
+    if (s >= 0 && s < n_sel) v = c < 32 ? mu[s * 32 + c] : (kind[e] == 0 ? spred[s] : 0.0f);
+    zcat[g] = v;
+}
+
+// GF32_PER 16-byte units per thread, all loaded before the first store: a wave keeps 4 KiB of one 48 KiB row in flight, a
+// workgroup 16 KiB (units / (TPB * GF32_PER) workgroups per image: 3 at 64x64, 12 at 128x128).  Every wave instruction
+// covers 1 KiB of contiguous bytes.  An index outside [0, n) yields NaN (never read out of bounds).
+constexpr int GF32_PER = 4;
+__global__ __launch_bounds__(TPB) void gather_f32_kernel(const uint4* __restrict__ frames, const float* __restrict__ preds, int64_t n,
+                                                         const int64_t* __restrict__ idx, uint4* __restrict__ x,
+                                                         float* __restrict__ pred, int units, int bpf) {
+    const int64_t b = blockIdx.x / bpf;
+    const int piece = (int)(blockIdx.x % bpf);
+    const int64_t s = idx[b];
+    const bool ok = s >= 0 && s < n;
+    const int u0 = piece * (TPB * GF32_PER) + threadIdx.x;
+    uint4* d = x + b * units + u0;
+    uint4 v[GF32_PER];
+    if (ok) {
+        const uint4* a = frames + s * units + u0;
+#pragma unroll
+        for (int j = 0; j < GF32_PER; ++j) v[j] = a[j * TPB];
+    } else {
+        const uint32_t q = 0x7fc00000u;
+#pragma unroll
+        for (int j = 0; j < GF32_PER; ++j) v[j] = make_uint4(q, q, q, q);
+    }
+#pragma unroll
+    for (int j = 0; j < GF32_PER; ++j) d[j * TPB] = v[j];
+    if (piece == 0 && threadIdx.x == 0) pred[b] = ok ? preds[s] : __builtin_nanf("");
+}
+
 }  // namespace
+
+int launch_curate_select_recon(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
+                               int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* sel_first,
+                               int64_t* span, int64_t* ent_frame, int32_t* ent_kind, int64_t* ent_sel, int64_t* sel,
+                               hipStream_t st) {
+    if (n_traj > 0) {
+        hipLaunchKernelGGL(curate_count_kernel, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, counts);
+        CVAE_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(curate_cut_kernel<2>, dim3(1), dim3(TPB), 0, st, n_traj, total_images, running, counts, first, span, sel_first);
+    CVAE_CHECK_LAUNCH();
+    if (n_traj > 0) {
+        hipLaunchKernelGGL(curate_scatter_kernel<2>, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, first,
+                           span, ent_frame, (const int64_t*)sel_first, ent_kind, ent_sel, sel);
+        CVAE_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int launch_recon_zcat(int n_entries, const int64_t* ent_sel, const int32_t* ent_kind, const float* mu, const float* sel_pred,
+                      int64_t n_sel, float* zcat, hipStream_t st) {
+    const int64_t total = (int64_t)n_entries * 33;
+    hipLaunchKernelGGL(recon_zcat_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, ent_sel, ent_kind, mu, sel_pred,
+                       n_sel, n_entries, zcat);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_gather_f32(int width, int B, const float* frames, const float* preds, int64_t n, const int64_t* idx, float* x,
+                      float* pred, hipStream_t st) {
+    const int units = width * width * 3 / 4, bpf = units / (TPB * GF32_PER);
+    hipLaunchKernelGGL(gather_f32_kernel, dim3((unsigned)((int64_t)B * bpf)), dim3(TPB), 0, st, (const uint4*)frames, preds, n, idx,
+                       (uint4*)x, pred, units, bpf);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
 
 int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
                          int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* span,
@@ -217,10 +355,12 @@ int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const
         hipLaunchKernelGGL(curate_count_kernel, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, counts);
         CVAE_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(curate_cut_kernel, dim3(1), dim3(TPB), 0, st, n_traj, total_images, running, counts, first, span);
+    hipLaunchKernelGGL(curate_cut_kernel<1>, dim3(1), dim3(TPB), 0, st, n_traj, total_images, running, counts, first, span,
+                       (int64_t*)nullptr);
     CVAE_CHECK_LAUNCH();
     if (n_traj > 0) {
-        hipLaunchKernelGGL(curate_scatter_kernel, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, first, span, sel);
+        hipLaunchKernelGGL(curate_scatter_kernel<1>, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, first, span,
+                           sel, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr);
         CVAE_CHECK_LAUNCH();
     }
     return 0;

@@ -11,6 +11,13 @@ trajectory once len(dset) >= total_images.
     eps = load_episodes(["episodes/"])                       # (name, memory-mapped array) pairs, sorted by name
     ds = curate(eps, critic)                                 # DeviceDataset: frames (N,w,w,3) uint8 + preds (N,1) on the GPU
     FusedTrainer(vae).fit_device(ds, batch_size=128, epochs=7)
+
+The recon branch of the same function (load_minerl_data(critic, recon_dset=True, vae=vae), vae_utility.py:422-443) builds
+the dataset of the SECOND VAE: instead of the frame, the first VAE's eval-mode reconstructions vae.evaluate(obs, p) and / or
+vae.evaluate(obs, 0) — two entries for a mid frame, one for a high (at p) or low (at 0) frame:
+
+    rd = curate_recon(eps, critic, vae)                      # ReconDataset: frames (N,3,w,w) fp32 + preds (N,1) on the GPU
+    FusedTrainer(vae2).fit_device(rd, batch_size=128, epochs=7)
 """
 import os
 
@@ -87,6 +94,35 @@ def select_host(traj_preds, collect=P.collect, total_images=P.total_images):
                 c_low += 1
         counts[t] = (c_mid, c_high, c_low)
     return sizes, selected, counts
+
+
+def select_recon_host(traj_preds, collect=P.collect, total_images=P.total_images):
+    """The recon branch, vae_utility.py:406-443, restated like select_host: a mid frame appends two entries (kind 0 = decoded
+    at its critic value, then kind 1 = decoded at 0) and counts once against the mid cap, a high frame one entry of kind 0, a
+    low frame one of kind 1; len(dset) — the cut and the sizes — counts entries.  Returns (sizes, entries, counts): entries =
+    [(t, i, kind)] in dataset order, counts (T, 3) = FRAMES taken per bin."""
+    sizes, entries = [], []
+    counts = np.zeros((len(traj_preds), 3), np.int64)
+    for t, preds in enumerate(traj_preds):
+        if len(entries) >= total_images:
+            break
+        sizes.append(len(entries))
+        c_high = c_mid = c_low = 0
+        for i, pred in enumerate(np.asarray(preds, np.float32).reshape(-1)):
+            if c_high >= collect and c_low >= collect and c_mid >= collect:
+                break
+            elif MID_LO <= pred <= MID_HI and c_mid < collect:
+                entries.append((t, i, 0))
+                entries.append((t, i, 1))
+                c_mid += 1
+            elif pred >= HIGH and c_high < collect:
+                entries.append((t, i, 0))
+                c_high += 1
+            elif pred <= LOW and c_low < collect:
+                entries.append((t, i, 1))
+                c_low += 1
+        counts[t] = (c_mid, c_high, c_low)
+    return sizes, entries, counts
 
 
 class DeviceDataset:
@@ -257,3 +293,183 @@ def curate(episodes, critic, collect=P.collect, total_images=P.total_images, chu
     tot = counts.sum(0)
     log(f"dataset: {n} frames from {len(visited)} trajectories (mid {tot[0]}, high {tot[1]}, low {tot[2]})")
     return DeviceDataset(ds_frames[:n], ds_preds[:n], np.concatenate(source).astype(np.int64), visited, sizes, counts)
+
+
+class ReconDataset:
+    """The second VAE's training set on the device: frames (N, 3, w, w) fp32 = the first VAE's eval-mode reconstructions
+    (Tanh range), preds (N, 1) fp32 = the critic's value OF THE RECONSTRUCTION (train() evaluates the critic on what it
+    trains on, vae.py:50; the critic is frozen, so the value is computed once), source (N, 3) int64 host array (trajectory,
+    frame, kind: 0 = decoded at the frame's critic value, 1 = decoded at 0).  names / sizes / counts as DeviceDataset has
+    them (sizes count entries, counts frames per bin); stats = what curate_recon ran (walked / encoded / decoded)."""
+
+    def __init__(self, frames, preds, source, names=(), sizes=(), counts=None, stats=None):
+        if not (frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 4 and frames.shape[1] == 3
+                and frames.shape[2] == frames.shape[3] and frames.is_contiguous()):
+            raise ValueError("frames must be a contiguous fp32 device tensor (N, 3, w, w)")
+        if not (preds.is_cuda and preds.dtype == torch.float32 and tuple(preds.shape) == (frames.shape[0], 1)
+                and preds.is_contiguous()):
+            raise ValueError("preds must be a contiguous fp32 device tensor (N, 1)")
+        self.frames, self.preds = frames, preds
+        self.source = np.asarray(source, np.int64).reshape(-1, 3)
+        self.names, self.sizes = list(names), list(sizes)
+        self.counts = np.zeros((0, 3), np.int64) if counts is None else np.asarray(counts, np.int64)
+        self.stats = dict(stats or {})
+
+    def __len__(self):
+        return self.frames.shape[0]
+
+    @property
+    def width(self):
+        return self.frames.shape[2]
+
+    def save(self, path):
+        """Plain arrays (numpy .npz, uncompressed): frames, preds, source, names, sizes, counts."""
+        with open(path, "wb") as f:
+            np.savez(f, frames=self.frames.cpu().numpy(), preds=self.preds.cpu().numpy(), source=self.source,
+                     names=np.array(self.names, dtype=str), sizes=np.array(self.sizes, np.int64), counts=self.counts)
+
+    @classmethod
+    def load(cls, path, device="cuda:0"):
+        with np.load(path, allow_pickle=False) as z:
+            frames = torch.from_numpy(np.ascontiguousarray(z["frames"], np.float32)).to(device)
+            preds = torch.from_numpy(np.ascontiguousarray(z["preds"], np.float32).reshape(-1, 1)).to(device)
+            return cls(frames, preds, z["source"], z["names"].tolist(), z["sizes"].tolist(), z["counts"])
+
+    def to_reference_list(self):
+        """The reference's recon dset: [(1, 3, w, w) float32 ndarray, ...] (pickle.dump of it is recon-dataset.pickle)."""
+        a = self.frames.cpu().numpy()
+        return [a[i:i + 1].copy() for i in range(a.shape[0])]
+
+
+def curate_recon(episodes, critic, vae, collect=P.collect, total_images=P.total_images, chunk_frames=8192, order=None,
+                 device="cuda:0", log=print):
+    """load_minerl_data(critic, recon_dset=True, vae=vae) (vae_utility.py:393-443) on the device.
+
+    The streaming structure of curate().  Per chunk: the critic values of all frames, cvae_curate_select_recon (running
+    ENTRY count on the device), one host read of span; then for the selected frames only, in pieces of the VAE handle's
+    max_batch: cvae_preprocess_u8_gather (x and the frames' critic values) and the eval-mode encoder
+    (cvae_forward(recon=NULL, train=0): running BatchNorm statistics, mu) — once per selected frame, also when the frame owns
+    two entries; for the entries, in pieces: cvae_recon_zcat and cvae_decode straight into the dataset slots (no staging
+    copy), then cvae_critic_forward on the finished entries for preds.  Unselected frames cost the critic launch only.
+    The VAE is put in eval mode and must be 64 x 64.  Returns a ReconDataset."""
+    if not isinstance(critic, Critic):
+        raise TypeError("curate_recon needs a critic_vae_amd.critic.Critic (the HIP critic)")
+    if collect < 1 or total_images < 0:
+        raise ValueError(f"collect {collect} must be >= 1 and total_images {total_images} >= 0")
+    if vae.width != 64:
+        raise ValueError("curate_recon needs a 64x64 VAE (the critic is 64x64 only)")
+    vae.eval()
+    episodes = list(episodes)
+    by_name = {}
+    for pos, (name, a) in enumerate(episodes):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 4 and a.shape[1:] == (64, 64, 3)):
+            raise ValueError(f"trajectory {name!r}: curation needs uint8 (T, 64, 64, 3) frames (the critic is 64x64 only)")
+        by_name[name] = pos
+    names = reference_order([n for n, _ in episodes]) if order is None else list(order)
+    walk = [by_name[n] for n in names]
+    device = torch.device(device)
+    if vae.theta.device != device:
+        raise ValueError(f"the VAE is on {vae.theta.device}, the dataset goes to {device}")
+    # the cut overshoots by at most 4 * collect - 1 entries, and no frame yields more than two
+    cap = min(total_images - 1 + 4 * collect, 2 * sum(episodes[p][1].shape[0] for p in walk)) if total_images > 0 else 0
+    ds_frames = torch.empty(max(cap, 1), 3, 64, 64, device=device)
+    ds_preds = torch.empty(max(cap, 1), 1, device=device)
+    stats = {"walked": 0, "encoded": 0, "decoded": 0}
+    log("loading episodes...")
+    if total_images == 0 or not walk:
+        return ReconDataset(ds_frames[:0], ds_preds[:0], np.zeros((0, 3), np.int64), stats=stats)
+
+    lengths = [episodes[p][1].shape[0] for p in walk]
+    chunks = _chunks(lengths, chunk_frames)
+    biggest = max(max(sum(lengths[t] for t in c) for c in chunks), 1)
+    h, vh, VB = Handle(64, CURATE_PIECE), vae.handle, vae.max_batch
+    theta, ws = vae.theta.data, vae._workspace(VB)
+    x = torch.empty(max(CURATE_PIECE, VB), 3, 64, 64, device=device)
+    cpred = torch.empty(biggest, device=device)
+    sel = torch.empty(biggest, dtype=torch.int64, device=device)
+    ent_frame = torch.empty(2 * biggest, dtype=torch.int64, device=device)
+    ent_sel = torch.empty(2 * biggest, dtype=torch.int64, device=device)
+    ent_kind = torch.empty(2 * biggest, dtype=torch.int32, device=device)
+    mu = torch.empty(biggest, P.latent_dim, device=device)
+    spred = torch.empty(biggest, 1, device=device)
+    logvar = torch.empty(VB, P.latent_dim, device=device)
+    zeros = torch.zeros(VB, P.latent_dim, device=device)
+    zcat = torch.empty(VB, P.latent_dim + 1, device=device)
+    running = torch.zeros(1, dtype=torch.int64, device=device)
+    span = torch.zeros(3, dtype=torch.int64, device=device)
+    copy_stream = torch.cuda.Stream(device=device)
+    sets = [{"pin": torch.empty(biggest, 64, 64, 3, dtype=torch.uint8).pin_memory(),
+             "dev": torch.empty(biggest, 64, 64, 3, dtype=torch.uint8, device=device),
+             "copied": torch.cuda.Event(), "consumed": torch.cuda.Event(), "used": False} for _ in range(2)]
+
+    def stage(s, c):
+        if s["used"]:
+            s["consumed"].synchronize()
+        pin, n = s["pin"].numpy(), 0
+        for t in c:
+            a = episodes[walk[t]][1]
+            pin[n:n + a.shape[0]] = a
+            n += a.shape[0]
+        with torch.cuda.stream(copy_stream):
+            s["dev"][:n].copy_(s["pin"][:n], non_blocking=True)
+            s["copied"].record(copy_stream)
+        s["used"], s["n"] = True, n
+
+    source, sizes, visited, counts = [], [], [], []
+    cur = torch.cuda.current_stream(device)
+    stage(sets[0], chunks[0])
+    for ci, c in enumerate(chunks):
+        s = sets[ci % 2]
+        n = s["n"]
+        cur.wait_event(s["copied"])
+        offs = np.concatenate([[0], np.cumsum([lengths[t] for t in c])]).astype(np.int64)
+        d_offs = torch.from_numpy(offs).to(device)
+        d_counts = torch.empty(len(c), 3, dtype=torch.int64, device=device)
+        d_first = torch.empty(len(c), dtype=torch.int64, device=device)
+        d_sfirst = torch.empty(len(c), dtype=torch.int64, device=device)
+        if n:
+            _critic_values(critic, s["dev"][:n], cpred[:n], handle=h, x=x)
+        h.curate_select_recon(d_offs, cpred[:n], collect, total_images, running, d_counts, d_first, d_sfirst, span,
+                              ent_frame, ent_kind, ent_sel, sel)
+        if ci + 1 < len(chunks):
+            stage(sets[(ci + 1) % 2], chunks[ci + 1])          # host fill + H2D of the next chunk under this one's kernels
+        sp = span.cpu().numpy()                                # the one host read of the chunk: sizes the launches below
+        e0, ne, ns = int(sp[0]), int(sp[1]), int(sp[2])
+        if e0 + ne > cap or ns > n:
+            raise RuntimeError(f"curate_recon: chunk {ci} claims entries [{e0}, {e0 + ne}) of {cap} and {ns} of {n} frames")
+        for p in range(0, ns, VB):                             # the encoder, once per selected frame
+            nb = min(VB, ns - p)
+            vh.preprocess_u8_gather(nb, s["dev"], cpred, sel[p:p + nb], x[:nb], spred[p:p + nb])
+            vh.forward(nb, x[:nb], spred[p:p + nb], zeros[:nb], theta, vae.bn_state, mu[p:p + nb], logvar[:nb], None, ws,
+                       train=False)
+        s["consumed"].record(cur)
+        for p in range(0, ne, VB):                             # the decoder, once per entry, into the dataset slots
+            nb = min(VB, ne - p)
+            vh.recon_zcat(nb, ent_sel[p:p + nb], ent_kind[p:p + nb], mu[:ns], spred[:ns], zcat[:nb])
+            vh.decode(nb, zcat[:nb], theta, ds_frames[e0 + p:e0 + p + nb], ws)
+        for p in range(0, ne, CURATE_PIECE):                   # train() evaluates the critic on the reconstructions
+            nb = min(CURATE_PIECE, ne - p)
+            h.critic_forward(nb, ds_frames[e0 + p:e0 + p + nb], critic.flat, ds_preds[e0 + p:e0 + p + nb])
+        vae._stamp_workspace()
+        stats["walked"] += n
+        stats["encoded"] += ns
+        stats["decoded"] += ne
+        first, cnt = d_first.cpu().numpy(), d_counts.cpu().numpy()
+        ef, ek = ent_frame[:ne].cpu().numpy(), ent_kind[:ne].cpu().numpy().astype(np.int64)
+        tr = np.searchsorted(offs, ef, side="right") - 1
+        source.append(np.stack([np.asarray(walk)[np.asarray(c)[tr]] if ne else np.zeros(0, np.int64), ef - offs[tr], ek], 1))
+        for j, t in enumerate(c):
+            if first[j] >= 0:
+                log(f"total images = {first[j]}")
+                sizes.append(int(first[j]))
+                visited.append(names[t])
+                counts.append(cnt[j])
+        if e0 + ne >= total_images:
+            break
+    torch.cuda.synchronize(device)
+    n = int(running.item())
+    counts = np.array(counts, np.int64).reshape(-1, 3)
+    tot = counts.sum(0)
+    log(f"recon dataset: {n} entries from {stats['encoded']} frames of {len(visited)} trajectories "
+        f"(mid {tot[0]}, high {tot[1]}, low {tot[2]})")
+    return ReconDataset(ds_frames[:n], ds_preds[:n], np.concatenate(source).astype(np.int64), visited, sizes, counts, stats)

@@ -78,6 +78,9 @@ _SIGS = {
     "cvae_curate_select": (C.c_int, [_p, _i32, _p, _i64, _p, _i32, _i64] + [_p] * 6),
     "cvae_gather_frames_u8": (C.c_int, [_p, _i32, _p, _p, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
     "cvae_preprocess_u8_gather": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p]),
+    "cvae_curate_select_recon": (C.c_int, [_p, _i32, _p, _i64, _p, _i32, _i64] + [_p] * 10),
+    "cvae_recon_zcat": (C.c_int, [_p, _i32, _p, _p, _p, _p, _i64, _p, _p]),
+    "cvae_gather_f32": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p]),
     "cvae_diff_normalize": (C.c_int, [_p, _i32, _p, C.c_double, C.c_double, _i32] + [_p] * 6),
     "cvae_mask_counts": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_crf_scratch_bytes": (_i64, [_p, _i32]),
@@ -307,6 +310,39 @@ class Handle:
         assert idx.numel() >= B and preds.numel() >= frames_u8.shape[0] and x.numel() >= B * 3 * w * w and pred.numel() >= B
         self._check(self.lib.cvae_preprocess_u8_gather(self.h, B, int(frames_u8.shape[1]), self._u8(frames_u8, "frames"), _ptr(preds),
                                                        frames_u8.shape[0], self._i64(idx, "idx"), _ptr(x), _ptr(pred), _stream()))
+
+    # ---- the recon branch (the second VAE's dataset, vae_utility.py:422-443) ----
+    def curate_select_recon(self, offsets, preds, collect, total_images, running, counts, first, sel_first, span,
+                            ent_frame, ent_kind, ent_sel, sel):
+        """curate_select with two entries per mid frame: running / first / span[0..1] count entries; sel_first (n_traj),
+        span (3), ent_frame / ent_sel (>= 2 n_frames) int64, ent_kind (>= 2 n_frames) int32, sel (>= n_frames) int64."""
+        n_traj = offsets.numel() - 1
+        n_frames = preds.numel()
+        assert sel.numel() >= n_frames and counts.numel() >= 3 * n_traj and first.numel() >= n_traj and span.numel() >= 3
+        assert sel_first.numel() >= n_traj and min(ent_frame.numel(), ent_kind.numel(), ent_sel.numel()) >= 2 * n_frames
+        assert ent_kind.is_cuda and ent_kind.dtype == torch.int32 and ent_kind.is_contiguous()
+        self._check(self.lib.cvae_curate_select_recon(
+            self.h, n_traj, self._i64(offsets, "offsets"), n_frames, _ptr(preds), int(collect), int(total_images),
+            self._i64(running, "running"), self._i64(counts, "counts"), self._i64(first, "first"),
+            self._i64(sel_first, "sel_first"), self._i64(span, "span"), self._i64(ent_frame, "ent_frame"),
+            ent_kind.data_ptr(), self._i64(ent_sel, "ent_sel"), self._i64(sel, "sel"), _stream()))
+
+    def recon_zcat(self, n_entries, ent_sel, ent_kind, mu, sel_preds, zcat):
+        """zcat[e] = (mu[ent_sel[e]], ent_kind[e] == 0 ? sel_preds[ent_sel[e]] : 0) for a run of n_entries entries."""
+        assert ent_sel.numel() >= n_entries and ent_kind.numel() >= n_entries and zcat.numel() >= 33 * n_entries
+        assert ent_kind.is_cuda and ent_kind.dtype == torch.int32 and ent_kind.is_contiguous()
+        n_sel = sel_preds.numel()
+        assert mu.numel() >= 32 * n_sel
+        self._check(self.lib.cvae_recon_zcat(self.h, n_entries, self._i64(ent_sel, "ent_sel"), ent_kind.data_ptr(), _ptr(mu),
+                                             _ptr(sel_preds), n_sel, _ptr(zcat), _stream()))
+
+    def gather_f32(self, B, frames, preds, idx, x, pred):
+        """x[b] = frames[idx[b]] ((N,3,W,W) fp32, bit copy), pred[b] = preds[idx[b]]; idx (>= B) int64 in [0, N) on the device."""
+        w = frames.shape[2]
+        assert frames.dim() == 4 and frames.shape[1] == 3 and frames.shape[3] == w
+        assert idx.numel() >= B and preds.numel() >= frames.shape[0] and x.numel() >= B * 3 * w * w and pred.numel() >= B
+        self._check(self.lib.cvae_gather_f32(self.h, B, int(w), _ptr(frames), _ptr(preds), frames.shape[0],
+                                             self._i64(idx, "idx"), _ptr(x), _ptr(pred), _stream()))
 
     # ---- segmentation evaluation (eval_textured_frames, vae_utility.py:162-212) ----
     @staticmethod

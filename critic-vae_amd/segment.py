@@ -280,9 +280,12 @@ def parse_args(argv=None):
     ap.add_argument("--networks", default="saved-networks", help=f"directory with {ENCODER_FILE} and {DECODER_FILE}")
     ap.add_argument("--critic", default=None, help=f"critic checkpoint (default: NETWORKS/{CRITIC_FILE})")
     ap.add_argument("--chunk", type=int, default=256, help="frames per VAE launch")
+    ap.add_argument("--second", action="store_true", help="evaluate the second VAE: NETWORKS/vae2_encoder.pt and "
+                    "vae2_decoder.pt (the reference's -evalsecond; written by train.py -second)")
     args = ap.parse_args(argv)
     if not args.video:
-        ap.error("-video is required (-dataset, -second, -evalsecond and -inject are not part of this tool)")
+        ap.error("-video is required (-dataset and -second are modes of critic_vae_amd.train, -evalsecond is -video --second; "
+                 "-inject is not part of this tool)")
     if args.chunk < 1:
         ap.error("--chunk must be >= 1")
     if args.critic is None:
@@ -296,8 +299,8 @@ def main(argv=None):
     from .nets import VariationalAutoencoder
     frames, gt = load_episode(args.frames, args.gt)
     vae = VariationalAutoencoder(max_batch=args.chunk).to("cuda")
-    vae.encoder.load_state_dict(torch.load(os.path.join(args.networks, ENCODER_FILE), map_location="cpu"))
-    vae.decoder.load_state_dict(torch.load(os.path.join(args.networks, DECODER_FILE), map_location="cpu"))
+    from .train import load_networks
+    load_networks(vae, args.networks, second=args.second)
     critic = Critic(64, handle=Handle(64, args.chunk)).to("cuda")
     critic.load_state_dict(torch.load(args.critic, map_location="cpu"))
     if args.thresh:

@@ -13,6 +13,11 @@ Two drivers over the same C-ABI kernels:
 
 With --episodes the training set is built as the reference's load_minerl_data(critic) builds it (episodes.py), on the
 device, and FusedTrainer.fit_device trains on it.
+
+The second stage of the reference's experiment (vae.py:130-153):
+
+    python -m critic_vae_amd.train -dataset --episodes episodes/ --critic critic.pt --networks saved-networks --out recon.npz
+    python -m critic_vae_amd.train -second --dataset recon.npz --critic critic.pt --epochs 7 --save saved-networks
 """
 import argparse
 import os
@@ -262,7 +267,9 @@ class FusedTrainer:
         """The loop of fit_u8 over a DeviceDataset (episodes.py) that already lives on the device with its critic values:
         per epoch np.random.shuffle of the host indices (uploaded once), slices of batch_size with the ragged last batch
         kept, eps ~ N(0,1) from `generator`; each batch is one cvae_preprocess_u8_gather launch (x = frames[idx] / 255,
-        pred = preds[idx]) and step() — no host gather, no PCIe copy, no critic launch.  Returns the last step's scalars."""
+        pred = preds[idx]) and step() — no host gather, no PCIe copy, no critic launch.  A ReconDataset (fp32 entries, the
+        second VAE's training set) runs the identical loop with cvae_gather_f32 as the batch launch.  Returns the last step's
+        scalars."""
         dev = self.vae.theta.device
         n = len(dataset)
         if dataset.width != self.vae.width:
@@ -275,6 +282,8 @@ class FusedTrainer:
         x = torch.empty(B, P.ch, self.vae.width, self.vae.width, device=dev)
         pred = torch.empty(B, 1, device=dev)
         scal = None
+        # a ReconDataset holds fp32 CHW entries: the batch is a bit copy (cvae_gather_f32)
+        gather = self.h.gather_f32 if dataset.frames.dtype == torch.float32 else self.h.preprocess_u8_gather
         for _ in range(epochs):
             idx = np.arange(n)
             if shuffle:
@@ -282,7 +291,7 @@ class FusedTrainer:
             d_idx = torch.from_numpy(idx).to(dev)          # indices of arange(n): in [0, n) by construction
             for b in range(0, n, B):
                 nb = min(B, n - b)
-                self.h.preprocess_u8_gather(nb, dataset.frames, dataset.preds, d_idx[b:b + nb], x[:nb], pred[:nb])
+                gather(nb, dataset.frames, dataset.preds, d_idx[b:b + nb], x[:nb], pred[:nb])
                 eps = torch.randn(nb, P.latent_dim, device=dev, generator=generator)
                 scal = self.step(x[:nb], pred[:nb], eps)
         return scal
@@ -317,24 +326,32 @@ def synthetic_dataset(n_frames, width=P.w, seed=1234):
 
 
 ENCODER_FILE, DECODER_FILE = "vae_encoder.pt", "vae_decoder.pt"      # vae_parameters.py:25-26 (under saved-networks/)
+SECOND_ENCODER_FILE, SECOND_DECODER_FILE = "vae2_encoder.pt", "vae2_decoder.pt"      # SECOND_*_PATH, vae_parameters.py
 
 
-def save_networks(vae, directory):
+def _network_files(directory, second):
+    enc, dec = (SECOND_ENCODER_FILE, SECOND_DECODER_FILE) if second else (ENCODER_FILE, DECODER_FILE)
+    return os.path.join(directory, enc), os.path.join(directory, dec)
+
+
+def save_networks(vae, directory, second=False):
     """End of `-train` (vae.py:162-163): torch.save(vae.encoder.state_dict(), ENCODER_PATH) and the same for the decoder —
     the reference's key names and layouts (OIHW conv weights, (C,H,W)-ordered fc columns / decoder_input rows, BatchNorm
     running statistics), so the two files load into the reference's own modules with strict=True and into
-    `VariationalAutoencoder.encoder / .decoder.load_state_dict` here.  Returns the two paths."""
+    `VariationalAutoencoder.encoder / .decoder.load_state_dict` here.  second: the second VAE's file names (vae.py:151-152).
+    Returns the two paths."""
     os.makedirs(directory, exist_ok=True)
-    enc, dec = os.path.join(directory, ENCODER_FILE), os.path.join(directory, DECODER_FILE)
+    enc, dec = _network_files(directory, second)
     torch.save({k: v.detach().cpu() for k, v in vae.encoder.state_dict().items()}, enc)
     torch.save({k: v.detach().cpu() for k, v in vae.decoder.state_dict().items()}, dec)
     return enc, dec
 
 
-def load_networks(vae, directory, device=None):
+def load_networks(vae, directory, device=None, second=False):
     """load_vae_network (vae_utility.py:345-361) for the two files save_networks / the reference wrote."""
-    vae.encoder.load_state_dict(torch.load(os.path.join(directory, ENCODER_FILE), map_location=device or "cpu"))
-    vae.decoder.load_state_dict(torch.load(os.path.join(directory, DECODER_FILE), map_location=device or "cpu"))
+    enc, dec = _network_files(directory, second)
+    vae.encoder.load_state_dict(torch.load(enc, map_location=device or "cpu"))
+    vae.decoder.load_state_dict(torch.load(dec, map_location=device or "cpu"))
     return vae
 
 
@@ -344,6 +361,18 @@ def main(argv=None):
                     help="write DIR/vae_encoder.pt and DIR/vae_decoder.pt when training ends (vae.py:162-163; the reference's "
                          "DIR is saved-networks/)")
     ap.add_argument("-train", action="store_true")
+    ap.add_argument("-dataset", dest="dataset_mode", action="store_true",
+                    help="build the second VAE's training set (vae.py:130-140): the first VAE's eval-mode reconstructions of "
+                         "the curated frames; needs --episodes, --critic, --networks, --out")
+    ap.add_argument("-second", action="store_true",
+                    help="train a fresh VAE on that set (vae.py:142-153); needs --dataset and --critic (the critic\'s values of "
+                         "the entries are cached in the dataset; the checkpoint names the critic it was built with); --save DIR writes "
+                         "DIR/vae2_encoder.pt and DIR/vae2_decoder.pt")
+    ap.add_argument("--networks", metavar="DIR", default="saved-networks", help="-dataset: directory with the first VAE's "
+                    f"{ENCODER_FILE} and {DECODER_FILE}")
+    ap.add_argument("--out", metavar="FILE", default=None, help="-dataset: where the recon dataset goes (plain arrays)")
+    ap.add_argument("--pickle", metavar="FILE", default=None, help="-dataset: also write the reference's recon-dataset.pickle")
+    ap.add_argument("--dataset", metavar="FILE", default=None, help="-second: the file -dataset --out wrote")
     ap.add_argument("--synthetic", type=int, default=1024, help="number of synthetic frames")
     ap.add_argument("--batch", type=int, default=P.batch_size)
     ap.add_argument("--epochs", type=int, default=1)
@@ -358,8 +387,16 @@ def main(argv=None):
     ap.add_argument("--collect", type=int, default=P.collect, help="frames per critic-value bin and trajectory "
                     "(vae_utility.py:404)")
     args = ap.parse_args(argv)
-    if not args.train:
-        ap.error("only -train is implemented (the hot path); see SURVEY.md §8 for scope")
+    if args.train + args.dataset_mode + args.second != 1:
+        ap.error("exactly one of -train, -dataset, -second (segment.py has -video [-thresh] [--second]); see SURVEY.md §8 for scope")
+    if args.dataset_mode:
+        if args.episodes is None or args.critic in (None, "random") or args.out is None:
+            ap.error("-dataset needs --episodes, --critic (a checkpoint or 'synth') and --out")
+        return _build_recon_dataset(args)
+    if args.second:
+        if args.dataset is None or args.critic in (None, "random"):
+            ap.error("-second needs --dataset (written by -dataset --out) and --critic")
+        return _train_second(args)
     if args.episodes is not None and args.critic in (None, "random"):
         ap.error("--episodes needs --critic (a reference critic checkpoint, or 'synth'): the dataset is chosen by its values")
     if args.critic is None:
@@ -427,6 +464,57 @@ def _train_episodes(args):
           f"(recon {s[1]:.6f}, kld {s[2]:.6f})")
     if args.save:
         enc, dec = save_networks(vae, args.save)
+        print(f"saved {enc} and {dec}")
+    return ds
+
+
+def _build_recon_dataset(args):
+    """-dataset (vae.py:130-140): load_networks -> curate_recon (episodes.py) -> ReconDataset.save."""
+    from .episodes import curate_recon, load_episodes
+    episodes = load_episodes(args.episodes)
+    if not torch.cuda.is_available():
+        raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
+    device = torch.device("cuda:0")
+    vae = load_networks(VariationalAutoencoder(max_batch=max(args.batch, 256), seed=args.seed).to(device), args.networks)
+    critic = _load_critic(args.critic, vae.handle, args.seed, device)
+    t0 = time.time()
+    ds = curate_recon(episodes, critic, vae, collect=args.collect, total_images=args.total_images, device=device)
+    torch.cuda.synchronize()
+    print(f"built {len(ds)} entries from {ds.stats['encoded']} of {ds.stats['walked']} walked frames in {time.time() - t0:.2f} s")
+    ds.save(args.out)
+    print(f"saved {args.out}")
+    if args.pickle:
+        import pickle
+        with open(args.pickle, "wb") as f:
+            pickle.dump(ds.to_reference_list(), f)
+        print(f"saved {args.pickle}")
+    return ds
+
+
+def _train_second(args):
+    """-second (vae.py:142-153): a fresh VAE, FusedTrainer.fit_device on the recon dataset, saved as vae2_*.pt."""
+    from .episodes import ReconDataset
+    if not torch.cuda.is_available():
+        raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    device = torch.device("cuda:0")
+    ds = ReconDataset.load(args.dataset, device)
+    if len(ds) == 0:
+        raise SystemExit("the recon dataset is empty")
+    vae = VariationalAutoencoder(max_batch=args.batch, seed=args.seed).to(device)
+    trainer = FusedTrainer(vae)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(args.seed)
+    t0 = time.time()
+    scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    s = scal.cpu().numpy()
+    print(f"{args.epochs * len(ds) / dt:.1f} images/s over {args.epochs} epoch(s); last loss {s[0]:.6f} "
+          f"(recon {s[1]:.6f}, kld {s[2]:.6f})")
+    if args.save:
+        enc, dec = save_networks(vae, args.save, second=True)
         print(f"saved {enc} and {dec}")
     return ds
 

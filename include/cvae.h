@@ -267,6 +267,46 @@ int cvae_preprocess_u8_gather(cvae_handle h, int32_t batch, int32_t width, const
                               const float* preds, int64_t n_frames, const int64_t* idx, float* x,
                               float* pred, void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * The recon branch of the same walk: load_minerl_data(critic, recon_dset=True, vae=vae)
+ * (vae_utility.py:422-443), the dataset of the second VAE.  Same walk, order, bins, float32 edges,
+ * per-bin cap and cut as above, but the dataset holds ENTRIES, the first VAE's eval-mode
+ * reconstructions (fp32 (3, W, W) NCHW in the Tanh range), not frames:
+ *   a mid frame appends two entries, in this order: kind 0 = vae.evaluate(obs, p), kind 1 =
+ *   vae.evaluate(obs, 0); it counts once against the mid cap.  A high frame appends one entry of
+ *   kind 0, a low frame one of kind 1.
+ * len(dset) counts entries, so the cut sees mid frames twice and the last trajectory taken may
+ * overshoot by up to 4*collect - 1: a dataset of total_images - 1 + 4*collect entries suffices.
+ * ---------------------------------------------------------------------------------------- */
+
+/* cvae_curate_select with entry weights 2 / 1 / 1 (mid / high / low) in the cut and in the slot positions (the same three
+ * kernels, instantiated for that weight).  Arguments as cvae_curate_select, with running / first / span[0..1] counting
+ * ENTRIES and counts still FRAMES per bin.  Further outputs: sel_first (n_traj) int64 = selected frames of this chunk before
+ * the trajectory, or -1 past the cut; span (3) int64 = (first entry slot of the chunk, entries in it, selected frames in
+ * it); per entry e < span[1] (room for 2 * n_frames each): ent_frame[e] int64 = its chunk frame index, ent_kind[e] int32 =
+ * 0 (decode at the frame's critic value) or 1 (decode at 0), ent_sel[e] int64 = the rank s of its frame among the chunk's
+ * selected frames; and sel[s] (s < span[2]; room for n_frames) int64 = the chunk frame index of selected frame s, in walk
+ * order, so that the encoder runs once per selected frame (cvae_preprocess_u8_gather with sel as the index).
+ * CVAE_EINVAL for null pointers, negative counts or collect < 1. */
+int cvae_curate_select_recon(cvae_handle h, int32_t n_traj, const int64_t* traj_offsets, int64_t n_frames,
+                             const float* preds, int32_t collect, int64_t total_images, int64_t* running,
+                             int64_t* counts, int64_t* first, int64_t* sel_first, int64_t* span, int64_t* ent_frame,
+                             int32_t* ent_kind, int64_t* ent_sel, int64_t* sel, void* stream);
+
+/* Decoder input of a run of entries: row e of zcat (n_entries, 33) = (mu[ent_sel[e]] (32 values), ent_kind[e] == 0 ?
+ * sel_preds[ent_sel[e]] : 0).  mu (n_sel, 32) = the eval-mode encoder's mu of the chunk's selected frames, sel_preds (n_sel)
+ * their critic values.  cvae_decode(zcat, recon = the dataset buffer at the run's first slot) then writes the
+ * reconstructions into their slots.  1 <= n_entries <= max_batch; an ent_sel outside [0, n_sel) yields a NaN row. */
+int cvae_recon_zcat(cvae_handle h, int32_t n_entries, const int64_t* ent_sel, const int32_t* ent_kind, const float* mu,
+                    const float* sel_preds, int64_t n_sel, float* zcat, void* stream);
+
+/* One training batch out of an fp32 device dataset: x[b] = frames[idx[b]] ((n_frames, 3, W, W) fp32, bit copy: 16-byte
+ * loads and stores) and pred[b] = preds[idx[b]], one launch.  Same contract as cvae_preprocess_u8_gather: W = width = the
+ * handle's width, 1 <= batch <= max_batch, frames and x 16-byte aligned, 64-bit frame offsets (50 000 entries of 64 x 64
+ * pass 2^31 bytes); an index outside [0, n_frames) yields NaN for that image and its pred, and is never read. */
+int cvae_gather_f32(cvae_handle h, int32_t batch, int32_t width, const float* frames, const float* preds,
+                    int64_t n_frames, const int64_t* idx, float* x, float* pred, void* stream);
+
 /* Difference mask of the inference path (get_diff_image, vae_utility.py:256-277), batched:
  * diff (B,W,W) = 0.2989|dR| + 0.5870|dG| + 0.1140|dB| of recon_zero - recon_one (both (B,3,W,W)). */
 int cvae_diff_grey(cvae_handle h, int32_t batch, const float* recon_one, const float* recon_zero,
