@@ -788,6 +788,15 @@ int cvae_recon_zcat(cvae_handle h, int32_t n_entries, const int64_t* ent_sel, co
     return launch_recon_zcat(n_entries, ent_sel, ent_kind, mu, sel_preds, n_sel, zcat, (hipStream_t)stream);
 }
 
+int cvae_inject_zcat(cvae_handle h, int32_t n_images, int32_t n_rewards, const float* mu, const float* rewards, float* zcat, void* stream) {
+    if (!h) { cvae_set_error("cvae_inject_zcat: null handle"); return CVAE_EINVAL; }
+    if (n_images < 1 || n_rewards < 1 || (int64_t)n_images * n_rewards > h->cfg.max_batch) {
+        cvae_set_error("cvae_inject_zcat: %d images x %d rewards outside [1, max_batch %d]", n_images, n_rewards, h->cfg.max_batch); return CVAE_EINVAL;
+    }
+    if (!mu || !rewards || !zcat) { cvae_set_error("cvae_inject_zcat: null pointer"); return CVAE_EINVAL; }
+    return launch_inject_zcat(n_images, n_rewards, mu, rewards, zcat, (hipStream_t)stream);
+}
+
 int cvae_gather_f32(cvae_handle h, int32_t batch, int32_t width, const float* frames, const float* preds, int64_t n_frames,
                     const int64_t* idx, float* x, float* pred, void* stream) {
     if (!h) { cvae_set_error("cvae_gather_f32: null handle"); return CVAE_EINVAL; }
@@ -853,6 +862,39 @@ int cvae_mask_counts(cvae_handle h, int32_t B, const uint8_t* mask, const uint8_
     if (!seg_batch_ok(h, B, "cvae_mask_counts")) return CVAE_EINVAL;
     if (!mask || !gt || !counts) { cvae_set_error("cvae_mask_counts: null mask, gt or frame_counts"); return CVAE_EINVAL; }
     return launch_mask_counts(h->cfg.width, B, mask, gt, counts, (hipStream_t)stream);
+}
+
+// ---- the reference's pictures (get_final_frame / get_injected_img, vae_utility.py:240-322; kernel in render.hip) ----
+int cvae_compose_frames(cvae_handle h, int32_t B, int32_t n_panels, const cvae_panel* panels, int32_t row_offset, int32_t flags,
+                        const uint8_t* overlay, const uint8_t* atlas, int32_t n_labels, int32_t label_h, int32_t label_w,
+                        const int32_t* label_idx, int32_t label_x, int32_t label_y, uint8_t* out, void* stream) {
+    if (!h) { cvae_set_error("cvae_compose_frames: null handle"); return CVAE_EINVAL; }
+    const int W = h->cfg.width;
+    if (W != 64 && W != 128) { cvae_set_error("cvae_compose_frames: width %d not supported (64 or 128)", W); return CVAE_EINVAL; }
+    if (B < 1) { cvae_set_error("cvae_compose_frames: batch %d must be >= 1", B); return CVAE_EINVAL; }
+    if (n_panels < 1 || n_panels > CVAE_MAX_PANELS || !panels) {
+        cvae_set_error("cvae_compose_frames: n_panels %d outside [1, %d] or null panels", n_panels, CVAE_MAX_PANELS); return CVAE_EINVAL;
+    }
+    if (row_offset < 0 || row_offset > 2 * W) { cvae_set_error("cvae_compose_frames: row_offset %d outside [0, %d]", row_offset, 2 * W); return CVAE_EINVAL; }
+    if (flags & ~CVAE_COMPOSE_CLAMP) { cvae_set_error("cvae_compose_frames: unknown flags %d", flags); return CVAE_EINVAL; }
+    for (int i = 0; i < n_panels; ++i) {
+        const cvae_panel& p = panels[i];
+        if (p.kind < CVAE_PANEL_F32_CHW || p.kind > CVAE_PANEL_MASK) { cvae_set_error("cvae_compose_frames: panel %d has unknown kind %d", i, p.kind); return CVAE_EINVAL; }
+        if (!p.data || ((uintptr_t)p.data & 15)) { cvae_set_error("cvae_compose_frames: panel %d data is null or not 16-byte aligned", i); return CVAE_EINVAL; }
+        if (p.batch_stride < 0 || p.batch_stride % (p.kind == CVAE_PANEL_U8_HWC ? 16 : 4)) {
+            cvae_set_error("cvae_compose_frames: panel %d batch_stride %lld must be >= 0 and a multiple of %d", i, (long long)p.batch_stride,
+                           p.kind == CVAE_PANEL_U8_HWC ? 16 : 4);
+            return CVAE_EINVAL;
+        }
+    }
+    if (!out || ((uintptr_t)out & 15) || ((uintptr_t)overlay & 15)) { cvae_set_error("cvae_compose_frames: out is null, or out / overlay not 16-byte aligned"); return CVAE_EINVAL; }
+    if (atlas && (!label_idx || n_labels < 1 || label_h < 1 || label_w < 1 || label_h > 4096 || label_w > 4096 ||
+                  label_x < -4096 || label_x > 65536 || label_y < -4096 || label_y > 65536)) {
+        cvae_set_error("cvae_compose_frames: an atlas needs label_idx, n_labels >= 1, a label size in [1, 4096]^2 and a position near the picture");
+        return CVAE_EINVAL;
+    }
+    return launch_compose_frames(W, B, n_panels, panels, row_offset, flags & CVAE_COMPOSE_CLAMP, overlay, atlas, n_labels, label_h, label_w,
+                                 label_idx, label_x, label_y, out, (hipStream_t)stream);
 }
 
 // ---- probe API: bracket chosen conv kernels of the real step with HIP events (bench.py roofline) ----

@@ -334,6 +334,7 @@ int launch_curate_select_recon(int n_traj, const int64_t* off, int64_t n_frames,
                                hipStream_t st);
 int launch_recon_zcat(int n_entries, const int64_t* ent_sel, const int32_t* ent_kind, const float* mu, const float* sel_pred,
                       int64_t n_sel, float* zcat, hipStream_t st);
+int launch_inject_zcat(int n_images, int n_rewards, const float* mu, const float* rewards, float* zcat, hipStream_t st);
 int launch_gather_f32(int width, int B, const float* frames, const float* preds, int64_t n, const int64_t* idx, float* x,
                       float* pred, hipStream_t st);
 int launch_diff_grey(int width, int B, const float* a, const float* b, float* diff, hipStream_t st);
@@ -344,6 +345,10 @@ int launch_dense_crf(int width, int B, const uint8_t* frames, const float* prob1
 int launch_diff_normalize(int width, int B, const float* diff, double mean_max, double factor, int thr, const uint8_t* gt,
                           uint8_t* u8, uint8_t* mask, int64_t* counts, int64_t* hist, hipStream_t st);
 int launch_mask_counts(int width, int B, const uint8_t* mask, const uint8_t* gt, int64_t* counts, hipStream_t st);
+// render.hip
+int launch_compose_frames(int width, int B, int n_panels, const struct cvae_panel* panels, int ih, int clamp, const uint8_t* overlay,
+                          const uint8_t* atlas, int n_labels, int lh, int lw, const int32_t* label_idx, int lx, int ly,
+                          uint8_t* out, hipStream_t st);
 // adam.hip
 int launch_grads_bf16(const float* src_f32, void* bf16_buf, float* dst_f32, int64_t n, hipStream_t st);   // src set: pack; else unpack
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1,

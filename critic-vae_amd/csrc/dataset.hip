@@ -17,6 +17,7 @@
 //                         and per selected frame its chunk index, so that the encoder runs once per selected frame.
 //   recon_zcat            zcat rows (mu of the entry's frame, its critic value or 0) for cvae_decode into the dataset slots.
 //   gather_f32            x[b] = frames[idx[b]] (fp32 CHW, bit copy) and pred[b] = preds[idx[b]]: one training batch.
+//   inject_zcat           zcat rows (mu of image b, reward r) of the batched -inject: one decoder call for all of them.
 //
 // Integer math only, no atomics: every result is deterministic.  Frame offsets are 64-bit (a 64x64 dataset passes
 // 2^31 bytes at 174 763 frames).
@@ -282,6 +283,15 @@ __global__ __launch_bounds__(TPB) void recon_zcat_kernel(const int64_t* __restri
     zcat[g] = v;
 }
 
+// one thread per zcat element: row b * R + r = (mu of image b, rewards[r]) — the batch form of vae.py -inject (vae_nets.py:31-40)
+__global__ __launch_bounds__(TPB) void inject_zcat_kernel(const float* __restrict__ mu, const float* __restrict__ rewards, int n_rewards,
+                                                          int n_rows, float* __restrict__ zcat) {
+    const int64_t g = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (g >= (int64_t)n_rows * 33) return;
+    const int e = (int)(g / 33), c = (int)(g % 33);
+    zcat[g] = c < 32 ? mu[(int64_t)(e / n_rewards) * 32 + c] : rewards[e % n_rewards];
+}
+
 // GF32_PER 16-byte units per thread, all loaded before the first store: a wave keeps 4 KiB of one 48 KiB row in flight, a
 // workgroup 16 KiB (units / (TPB * GF32_PER) workgroups per image: 3 at 64x64, 12 at 128x128).  Every wave instruction
 // covers 1 KiB of contiguous bytes.  An index outside [0, n) yields NaN (never read out of bounds).
@@ -335,6 +345,14 @@ int launch_recon_zcat(int n_entries, const int64_t* ent_sel, const int32_t* ent_
     const int64_t total = (int64_t)n_entries * 33;
     hipLaunchKernelGGL(recon_zcat_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, ent_sel, ent_kind, mu, sel_pred,
                        n_sel, n_entries, zcat);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_inject_zcat(int n_images, int n_rewards, const float* mu, const float* rewards, float* zcat, hipStream_t st) {
+    const int n_rows = n_images * n_rewards;
+    const int64_t total = (int64_t)n_rows * 33;
+    hipLaunchKernelGGL(inject_zcat_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, mu, rewards, n_rewards, n_rows, zcat);
     CVAE_CHECK_LAUNCH();
     return 0;
 }

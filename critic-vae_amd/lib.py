@@ -31,6 +31,16 @@ class CrfParams(C.Structure):
                 ("gamma", C.c_float), ("p_floor", C.c_float), ("iterations", C.c_int32)]
 
 
+class Panel(C.Structure):
+    """cvae_panel (include/cvae.h): one w x w panel of cvae_compose_frames."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("data", C.c_void_p), ("batch_stride", C.c_int64)]
+
+
+PANEL_F32_CHW, PANEL_U8_HWC, PANEL_U8_GREY, PANEL_MASK = 0, 1, 2, 3
+MAX_PANELS = 8
+COMPOSE_CLAMP = 1
+
+
 def build(verbose=False):
     """Compile the HIP sources for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     r = subprocess.run(["make", "-j8", "-C", os.path.join(_HERE, "csrc")],
@@ -85,6 +95,8 @@ _SIGS = {
     "cvae_mask_counts": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_crf_scratch_bytes": (_i64, [_p, _i32]),
     "cvae_dense_crf": (C.c_int, [_p, _i32, _p, _p, C.POINTER(CrfParams), _p, _p, _p, _p]),
+    "cvae_compose_frames": (C.c_int, [_p, _i32, _i32, C.POINTER(Panel), _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _p, _p]),
+    "cvae_inject_zcat": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p]),
     "cvae_probe_config": (C.c_int, [_p, C.c_uint32]),
     "cvae_probe_read": (C.c_int, [_p, _i32, C.POINTER(C.c_float), _i32]),
     "cvae_op_scratch_floats": (_i64, [_p, _i32]),
@@ -380,6 +392,40 @@ class Handle:
         assert scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= self.crf_scratch_bytes(B)
         self._check(self.lib.cvae_dense_crf(self.h, B, self._u8(frames_u8, "frames"), _ptr(prob1), C.byref(params),
                                             self._u8(labels, "labels"), _ptr(q1), scratch.data_ptr(), _stream()))
+
+    # ---- the reference's pictures (get_final_frame / get_injected_img, vae_utility.py:240-322; render.py) ----
+    def compose_frames(self, B, panels, row_offset, out, overlay=None, atlas=None, label_idx=None, label_xy=(0, 0), clamp=False):
+        """panels: [(kind, device tensor, batch stride in elements), ...] of w x w panels side by side -> out
+        (B, row_offset + w, len(panels) * w, 3) uint8.  overlay (row_offset + w, len(panels) * w) uint8 and atlas (L, lh, lw) uint8
+        with label_idx (B) int32 draw white text (include/cvae.h)."""
+        w, n = self.width, len(panels)
+        if not 1 <= n <= MAX_PANELS:
+            raise ValueError(f"{n} panels, need 1..{MAX_PANELS}")
+        need = {PANEL_F32_CHW: (torch.float32, 3 * w * w), PANEL_U8_HWC: (torch.uint8, 3 * w * w),
+                PANEL_U8_GREY: (torch.uint8, w * w), PANEL_MASK: (torch.uint8, w * w)}
+        arr = (Panel * n)()
+        for i, (kind, t, stride) in enumerate(panels):
+            dtype, numel = need[kind]
+            assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), f"panel {i}: need a contiguous {dtype} device tensor"
+            assert stride >= 0 and t.numel() >= (B - 1) * stride + numel, f"panel {i}: {t.numel()} elements for {B} pictures at stride {stride}"
+            arr[i] = Panel(kind, 0, t.data_ptr(), stride)
+        assert out.numel() == B * (row_offset + w) * n * w * 3, "out: wrong size"
+        if overlay is not None:
+            assert overlay.numel() == (row_offset + w) * n * w, "overlay: wrong size"
+        L = lh = lw = 0
+        if atlas is not None:
+            L, lh, lw = atlas.shape
+            assert label_idx is not None and label_idx.is_cuda and label_idx.dtype == torch.int32 and label_idx.is_contiguous() \
+                and label_idx.numel() >= B, "label_idx: need a contiguous int32 device tensor of B entries"
+        self._check(self.lib.cvae_compose_frames(self.h, B, n, arr, int(row_offset), COMPOSE_CLAMP if clamp else 0,
+                                                 self._u8(overlay, "overlay"), self._u8(atlas, "atlas"), L, lh, lw,
+                                                 None if atlas is None else label_idx.data_ptr(), int(label_xy[0]), int(label_xy[1]),
+                                                 self._u8(out, "out"), _stream()))
+
+    def inject_zcat(self, n_images, n_rewards, mu, rewards, zcat):
+        """zcat[b * n_rewards + r] = (mu[b], rewards[r]): the decoder input of the batched -inject."""
+        assert mu.numel() >= 32 * n_images and rewards.numel() >= n_rewards and zcat.numel() >= 33 * n_images * n_rewards
+        self._check(self.lib.cvae_inject_zcat(self.h, n_images, n_rewards, _ptr(mu), _ptr(rewards), _ptr(zcat), _stream()))
 
     # ---- in-step kernel probe (bench.py roofline) ----
     def probe_config(self, ids):

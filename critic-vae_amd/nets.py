@@ -283,6 +283,34 @@ class VariationalAutoencoder(nn.Module):
         mu, _ = self.encoder(x)
         return [self.decoder(mu, reward[i].view(1), evalu=True) for i in range(P.inject_n)]
 
+    def inject_images(self, x, rewards=(0, .2, .4, .6, .8, 1)):
+        """vae.py -inject for a whole batch (get_injected_img, vae_utility.py:240-254): the eval-mode encoder once, then ONE
+        decoder call over all len(rewards) * B rows (several when they exceed max_batch), whose (len(rewards) * B, 33) input
+        cvae_inject_zcat builds on the device.  Returns (B, len(rewards), 3, w, w): [b, r] = inject(x[b:b + 1])[r]."""
+        x = self._prep(x)
+        B, dev = x.shape[0], x.device
+        rw = torch.as_tensor(rewards, dtype=torch.float32).reshape(-1).to(dev)
+        R = rw.numel()
+        per = self.max_batch // R
+        if per < 1:
+            raise ValueError(f"{R} rewards > max_batch {self.max_batch}")
+        mu = torch.empty(B, P.latent_dim, device=dev)
+        logvar = torch.empty_like(mu)
+        z = torch.zeros_like(mu)
+        out = torch.empty(B, R, P.ch, self.width, self.width, device=dev)
+        zcat = torch.empty(min(B, per) * R, P.latent_dim + 1, device=dev)
+        with torch.no_grad():
+            for s in range(0, B, self.max_batch):
+                n = min(B - s, self.max_batch)
+                self.handle.forward(n, x[s:s + n], z[:n].reshape(-1)[:n], z[:n], self.theta, self.bn_state, mu[s:s + n], logvar[s:s + n], None,
+                                    self._workspace(n), train=False)
+            for s in range(0, B, per):
+                n = min(B - s, per)
+                self.handle.inject_zcat(n, R, mu[s:s + n], rw, zcat)
+                self.handle.decode(n * R, zcat, self.theta, out[s:s + n], self._workspace(n * R))
+            self._stamp_workspace()
+        return out
+
     def evaluate(self, x, pred):
         """vae_nets.py:42-46."""
         mu, _ = self.encoder(x)

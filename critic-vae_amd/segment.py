@@ -4,7 +4,8 @@ vae_utility.py:162-212) on the MI355X.
 Per frame the critic value and the difference mask (VariationalAutoencoder.diff_images); over the whole set the
 normalisation by the mean of the per-frame maxima, the uint8 mask and its threshold (cvae_diff_normalize), the
 IoU against the ground truth, a dense CRF that refines every thresholded mask (cvae_dense_crf) and a second IoU,
-and the per-critic-value-bin statistics of save_bin_info.  PIL frame composition and the GIF are not reproduced.
+and the per-critic-value-bin statistics of save_bin_info.  The 7-panel pictures of get_final_frame are composed on the
+device by critic_vae_amd.render (`--out DIR` writes them, `--gif` also the GIF).
 
 The CRF is an EXACT mean-field solution of the model SimpleCRF's denseCRF.densecrf names (include/cvae.h): every
 pairwise sum runs over all pixel pairs, where the densecrf library approximates the bilateral filter with a
@@ -12,6 +13,7 @@ permutohedral lattice.  Its unary clamps probabilities at `p_floor` (default 1e-
 unary_from_softmax helper); whether SimpleCRF clamps a 0/1 mask the same way has not been checked against SimpleCRF.
 
     python -m critic_vae_amd.segment -video [-thresh] --frames X.npy --gt Y.npy --networks DIR [--critic CKPT]
+                                     [--out DIR [--gif] [--no-text]]
 """
 import argparse
 import os
@@ -178,9 +180,10 @@ def write_bin_info(path, bins):
 
 
 # ---- the pipeline ----
-def _infer(frames_u8, vae, critic, preds, chunk):
+def _infer(frames_u8, vae, critic, preds, chunk, keep_recons=False):
     """critic values + difference masks of every frame, in chunks of at most vae.max_batch:
-    (preds (B,) fp32, diff (B,W,W) fp32 on the device, per-frame maxima (B,) fp32)."""
+    (preds (B,) fp32, diff (B,W,W) fp32 on the device, per-frame maxima (B,) fp32); with keep_recons also the two
+    reconstructions (B,3,W,W) the masks came from."""
     if (critic is None) == (preds is None):
         raise ValueError("pass exactly one of critic and preds")
     vae.eval()                                   # load_vae_network (vae_utility.py:345-361)
@@ -199,6 +202,8 @@ def _infer(frames_u8, vae, critic, preds, chunk):
     diff = torch.empty(B, W, W, device=frames.device)
     maxv = torch.empty(B, device=frames.device)
     x = torch.empty(chunk, 3, W, W, device=frames.device)
+    ro = torch.empty(B, 3, W, W, device=frames.device) if keep_recons else None
+    rz = torch.empty_like(ro) if keep_recons else None
     for s in range(0, B, chunk):
         e = min(B, s + chunk)
         xs = x[:e - s]
@@ -209,10 +214,13 @@ def _infer(frames_u8, vae, critic, preds, chunk):
                 out_p[s + c0:s + min(e - s, c0 + cb)] = critic.evaluate(xs[c0:c0 + cb]).reshape(-1)
         else:
             out_p[s:e] = preds[s:e]
-        _, _, d, m = vae.diff_images(xs, out_p[s:e])
+        r1, r0, d, m = vae.diff_images(xs, out_p[s:e])
         diff[s:e] = d
         maxv[s:e] = m
-    return out_p, diff, maxv
+        if keep_recons:
+            ro[s:e] = r1
+            rz[s:e] = r0
+    return (out_p, diff, maxv, ro, rz) if keep_recons else (out_p, diff, maxv)
 
 
 def _crf_counts(frames, thr_mask, gt, crf_params_, p_floor):
@@ -222,13 +230,15 @@ def _crf_counts(frames, thr_mask, gt, crf_params_, p_floor):
 
 
 def eval_frames(frames_u8, vae, gt, critic=None, preds=None, t=THRESHOLD, crf_params=CRF_REF, chunk=None,
-                p_floor=P_FLOOR):
+                p_floor=P_FLOOR, keep_device=False):
     """eval_textured_frames (vae_utility.py:162-212) without the PIL frames.  frames_u8 (B,W,W,3) uint8, gt (B,W,W)
     bool; either a critic (64x64 only, as the reference's) or explicit preds (B,).  The VAE runs in eval mode in
     chunks of at most vae.max_batch; normalisation, threshold, CRF and IoU run over the whole set at once.
     Returns a dict: preds, diff (fp32), max_values, diff_u8, thr_masks, crf_masks (host arrays), thr_iou, crf_iou,
-    bins, mean_max, hist (the (2,256) histograms of diff_u8)."""
-    p, diff, maxv = _infer(frames_u8, vae, critic, preds, chunk)
+    bins, mean_max, hist (the (2,256) histograms of diff_u8).  keep_device=True adds "device": what render.video_frames
+    composes the pictures from, left on the device (frames, gt, preds, recon_one, recon_zero, diff_u8, thr_masks, crf_masks;
+    the masks as uint8 0/1)."""
+    p, diff, maxv, *recons = _infer(frames_u8, vae, critic, preds, chunk, keep_recons=keep_device)
     frames = _cuda(frames_u8, torch.uint8)
     gt_d = _cuda(_np(gt).astype(np.uint8), torch.uint8)
     hist = torch.zeros(2, 256, dtype=torch.int64, device=frames.device)
@@ -237,8 +247,12 @@ def eval_frames(frames_u8, vae, gt, critic=None, preds=None, t=THRESHOLD, crf_pa
     crf, crf_iou = _crf_counts(frames, m, gt_d, crf_params, p_floor)
     thr_np = _np(m).astype(bool)
     preds_np = _np(p)
-    return {"preds": preds_np, "diff": _np(diff), "max_values": _np(maxv), "diff_u8": _np(u8), "thr_masks": thr_np, "crf_masks": _np(crf), "thr_iou": thr_iou,
-            "crf_iou": crf_iou, "bins": bin_info(preds_np, gt, thr_np), "mean_max": mean_max, "hist": _np(hist)}
+    r = {"preds": preds_np, "diff": _np(diff), "max_values": _np(maxv), "diff_u8": _np(u8), "thr_masks": thr_np, "crf_masks": _np(crf), "thr_iou": thr_iou,
+         "crf_iou": crf_iou, "bins": bin_info(preds_np, gt, thr_np), "mean_max": mean_max, "hist": _np(hist)}
+    if keep_device:
+        r["device"] = {"frames": frames, "gt": gt_d, "preds": p, "recon_one": recons[0], "recon_zero": recons[1], "diff_u8": u8,
+                       "thr_masks": m, "crf_masks": crf.to(torch.uint8)}
+    return r
 
 
 def threshold_sweep(frames_u8, vae, gt, critic=None, preds=None, thresholds=SWEEP, crf_params=CRF_REF, chunk=None,
@@ -281,11 +295,20 @@ def parse_args(argv=None):
     ap.add_argument("--critic", default=None, help=f"critic checkpoint (default: NETWORKS/{CRITIC_FILE})")
     ap.add_argument("--chunk", type=int, default=256, help="frames per VAE launch")
     ap.add_argument("--second", action="store_true", help="evaluate the second VAE: NETWORKS/vae2_encoder.pt and "
-                    "vae2_decoder.pt (the reference's -evalsecond; written by train.py -second)")
+                    "vae2_decoder.pt (written by train.py -second).  The reference's -evalsecond is the folder evaluation "
+                    "of that VAE: python -m critic_vae_amd.render --second")
+    ap.add_argument("--out", default=None, help="write the 7-panel pictures of get_final_frame to DIR (image-000.png, ...; "
+                    "frames.npy without PIL)")
+    ap.add_argument("--gif", action="store_true", help=f"with --out: also DIR/video-threshold={THRESHOLD}.gif (needs PIL)")
+    ap.add_argument("--no-text", dest="text", action="store_false", help="with --out: bare panels, no titles, IoUs or critic value")
     args = ap.parse_args(argv)
     if not args.video:
-        ap.error("-video is required (-dataset and -second are modes of critic_vae_amd.train, -evalsecond is -video --second; "
-                 "-inject is not part of this tool)")
+        ap.error("-video is required (-dataset and -second are modes of critic_vae_amd.train; -inject and the folder "
+                 "evaluation of -evalsecond are python -m critic_vae_amd.render)")
+    if args.out is None and (args.gif or not args.text):
+        ap.error("--gif and --no-text need --out")
+    if args.out is not None and args.thresh:
+        ap.error("--out writes the pictures of one evaluation: not with -thresh")
     if args.chunk < 1:
         ap.error("--chunk must be >= 1")
     if args.critic is None:
@@ -308,9 +331,15 @@ def main(argv=None):
         for t, thr_iou, crf_iou in threshold_sweep(frames, vae, gt, critic=critic, chunk=args.chunk):
             print(f"thr={t}, thr_iou={thr_iou}, crf_iou={crf_iou}")
     else:
-        r = eval_frames(frames, vae, gt, critic=critic, chunk=args.chunk)
+        r = eval_frames(frames, vae, gt, critic=critic, chunk=args.chunk, keep_device=args.out is not None)
         print(f"thr_iou={r['thr_iou']}")
         print(f"crf_iou={r['crf_iou']}")
+        if args.out is not None:
+            from . import render
+            pictures = render.video_frames(r, text=args.text).cpu().numpy()
+            render.save_pngs(args.out, pictures)
+            if args.gif:
+                render.save_gif(os.path.join(args.out, f"video-threshold={THRESHOLD}.gif"), pictures)
     return 0
 
 

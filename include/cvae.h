@@ -356,6 +356,54 @@ int cvae_dense_crf(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, cons
                    const cvae_crf_params* params, uint8_t* labels, float* q1_or_null, void* scratch,
                    void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * The reference's pictures: the PNG strips of image_evaluate (vae.py:68-108) and get_injected_img
+ * (vae_utility.py:240-254) and the 7-panel video frames of get_final_frame (vae_utility.py:286-322).
+ * ---------------------------------------------------------------------------------------- */
+
+/* One panel of w x w pixels (w = the handle's width).  Picture b reads `data` + b * batch_stride ELEMENTS (floats for
+ * F32_CHW, bytes otherwise; 0 shows the same panel in every picture).  Pixel rules, each what the reference's host code does:
+ *   F32_CHW  fp32 (3,w,w) in the range of Tanh: prepare_rgb_image's (img * 255).astype(np.uint8) = ONE fp32 multiply rounded
+ *            to nearest, truncation toward zero to int32, the low 8 bits (two's-complement wrap: -0.3 -> 180, -0.99 -> 4, 1.0
+ *            -> 255; the reference's pictures show negative reconstruction pixels wrapped); NaN, +-inf and |v * 255| >= 2^31
+ *            give 0.  With CVAE_COMPOSE_CLAMP the truncated value saturates to [0, 255] instead.
+ *   U8_HWC   uint8 (w,w,3), copied (the episode frames).
+ *   U8_GREY  uint8 (w,w), replicated to r, g, b (PIL mode L pasted into RGB: diff_u8).
+ *   MASK     uint8 (w,w), nonzero -> 255, else 0, replicated (PIL mode 1 pasted into RGB: thr, crf, gt masks).
+ * `data`: 16-byte aligned, batch_stride a multiple of 4 (F32_CHW, U8_GREY, MASK) or 16 (U8_HWC) elements. */
+enum { CVAE_PANEL_F32_CHW = 0, CVAE_PANEL_U8_HWC = 1, CVAE_PANEL_U8_GREY = 2, CVAE_PANEL_MASK = 3 };
+#define CVAE_MAX_PANELS 8
+#define CVAE_COMPOSE_CLAMP 1
+typedef struct cvae_panel {
+    int32_t kind;
+    int32_t reserved;        /* 0 */
+    const void* data;        /* device */
+    int64_t batch_stride;    /* elements, >= 0 */
+} cvae_panel;
+
+/* out (batch, row_offset + w, n_panels * w, 3) uint8 HWC: the panels side by side from row `row_offset` down (0 for the
+ * strips, w for the video frames whose upper half holds the titles); rows above it are black.  `panels`: HOST array of
+ * n_panels (1..CVAE_MAX_PANELS) descriptors.  Text, white over whatever the panel holds:
+ *   overlay_or_null (row_offset + w, n_panels * w) uint8, shared by every picture: nonzero = white pixel;
+ *   atlas_or_null (n_labels, label_h, label_w) uint8 with label_idx (batch) int32: picture b shows label label_idx[b] with its
+ *   top left corner at column label_x, row label_y (clipped at the picture's edges; an index outside [0, n_labels) shows
+ *   none and is never read).
+ * One launch on the caller's stream, 16 output bytes per thread, no scratch, no atomics: a picture's bytes depend on its own
+ * inputs alone, whatever the batch.  Picture offsets are 64-bit (2 450 video frames at 128 x 128 are 0.8 GB); batch >= 1,
+ * 0 <= row_offset <= 2 * w; CVAE_EINVAL for a bad argument or a batch whose workgroup count does not fit one launch
+ * (batch * ceil((row_offset + w) * n_panels * w * 3 / 4096) >= 2^31).  out and overlay 16-byte aligned. */
+int cvae_compose_frames(cvae_handle h, int32_t batch, int32_t n_panels, const cvae_panel* panels, int32_t row_offset,
+                        int32_t flags, const uint8_t* overlay_or_null, const uint8_t* atlas_or_null, int32_t n_labels,
+                        int32_t label_h, int32_t label_w, const int32_t* label_idx, int32_t label_x, int32_t label_y,
+                        uint8_t* out, void* stream);
+
+/* Decoder input of `vae.py -inject` for a batch (VariationalAutoencoder.inject, vae_nets.py:31-40): row b * n_rewards + r of
+ * zcat (n_images * n_rewards, 33) = (mu[b] (32 values), rewards[r]).  mu (n_images, 32) = the eval-mode encoder's mu,
+ * rewards (n_rewards) fp32 on the device.  cvae_decode(zcat) then gives (n_images, n_rewards, 3, W, W).
+ * n_images, n_rewards >= 1 and n_images * n_rewards <= max_batch. */
+int cvae_inject_zcat(cvae_handle h, int32_t n_images, int32_t n_rewards, const float* mu, const float* rewards,
+                     float* zcat, void* stream);
+
 /* float offset of a named saved tensor in the workspace ("y0".."y3", "a0".."a3", "o0".."o3",
  * "zcat", "h", "d_*" ...) for tests; -1 if unknown OR not allocated in this configuration: "d_y0" does not exist
  * (block 0's BatchNorm backward runs inside the E1 weight-gradient kernel), and in precision mode 1 "dout4" has no
