@@ -707,16 +707,22 @@ int cvae_preprocess_u8(cvae_handle h, int32_t B, const uint8_t* frames_hwc, floa
 }
 
 // ---- the training set on the device (load_minerl_data, vae_utility.py:393-461; kernels in dataset.hip) ----
+// the scalar arguments both selection entry points share; `who` = the calling function
+static bool curate_args_ok(cvae_handle h, int32_t n_traj, int64_t n_frames, int32_t collect, int64_t total_images, const char* who) {
+    if (!h) { cvae_set_error("%s: null handle", who); return false; }
+    if (n_traj < 0 || n_frames < 0 || total_images < 0) {
+        cvae_set_error("%s: n_traj %d, n_frames %lld, total_images %lld must be >= 0", who, n_traj, (long long)n_frames,
+                       (long long)total_images);
+        return false;
+    }
+    if (collect < 1) { cvae_set_error("%s: collect %d must be >= 1", who, collect); return false; }
+    return true;
+}
+
 int cvae_curate_select(cvae_handle h, int32_t n_traj, const int64_t* traj_offsets, int64_t n_frames, const float* preds,
                        int32_t collect, int64_t total_images, int64_t* running, int64_t* counts, int64_t* first,
                        int64_t* span, int64_t* sel, void* stream) {
-    if (!h) { cvae_set_error("cvae_curate_select: null handle"); return CVAE_EINVAL; }
-    if (n_traj < 0 || n_frames < 0 || total_images < 0) {
-        cvae_set_error("cvae_curate_select: n_traj %d, n_frames %lld, total_images %lld must be >= 0", n_traj, (long long)n_frames,
-                       (long long)total_images);
-        return CVAE_EINVAL;
-    }
-    if (collect < 1) { cvae_set_error("cvae_curate_select: collect %d must be >= 1", collect); return CVAE_EINVAL; }
+    if (!curate_args_ok(h, n_traj, n_frames, collect, total_images, "cvae_curate_select")) return CVAE_EINVAL;
     if (!running || !span || (n_traj > 0 && (!traj_offsets || !counts || !first)) || (n_frames > 0 && (!preds || !sel))) {
         cvae_set_error("cvae_curate_select: null pointer"); return CVAE_EINVAL;
     }
@@ -744,16 +750,21 @@ int cvae_gather_frames_u8(cvae_handle h, int32_t width, const uint8_t* src_frame
                                    (hipStream_t)stream);
 }
 
+// what the two batch gathers check alike; `who` = the calling function, frames = the dataset's frame buffer
+static bool batch_gather_ok(cvae_handle h, int32_t batch, int32_t width, const void* frames, const float* preds, int64_t n_frames,
+                            const int64_t* idx, const float* x, const float* pred, const char* who) {
+    if (!h) { cvae_set_error("%s: null handle", who); return false; }
+    if (width != h->cfg.width) { cvae_set_error("%s: width %d, the handle's is %d", who, width, h->cfg.width); return false; }
+    if (batch < 1 || batch > h->cfg.max_batch) { cvae_set_error("%s: batch %d outside [1, %d]", who, batch, h->cfg.max_batch); return false; }
+    if (n_frames < 1) { cvae_set_error("%s: n_frames %lld must be >= 1", who, (long long)n_frames); return false; }
+    if (!frames || !preds || !idx || !x || !pred) { cvae_set_error("%s: null pointer", who); return false; }
+    if (((uintptr_t)frames & 15) || ((uintptr_t)x & 15)) { cvae_set_error("%s: frames and x must be 16-byte aligned", who); return false; }
+    return true;
+}
+
 int cvae_preprocess_u8_gather(cvae_handle h, int32_t batch, int32_t width, const uint8_t* frames_hwc, const float* preds,
                               int64_t n_frames, const int64_t* idx, float* x, float* pred, void* stream) {
-    if (!h) { cvae_set_error("cvae_preprocess_u8_gather: null handle"); return CVAE_EINVAL; }
-    if (width != h->cfg.width) { cvae_set_error("cvae_preprocess_u8_gather: width %d, the handle's is %d", width, h->cfg.width); return CVAE_EINVAL; }
-    if (batch < 1 || batch > h->cfg.max_batch) { cvae_set_error("cvae_preprocess_u8_gather: batch %d outside [1, %d]", batch, h->cfg.max_batch); return CVAE_EINVAL; }
-    if (n_frames < 1) { cvae_set_error("cvae_preprocess_u8_gather: n_frames %lld must be >= 1", (long long)n_frames); return CVAE_EINVAL; }
-    if (!frames_hwc || !preds || !idx || !x || !pred) { cvae_set_error("cvae_preprocess_u8_gather: null pointer"); return CVAE_EINVAL; }
-    if (((uintptr_t)frames_hwc & 15) || ((uintptr_t)x & 15)) {
-        cvae_set_error("cvae_preprocess_u8_gather: frames and x must be 16-byte aligned"); return CVAE_EINVAL;
-    }
+    if (!batch_gather_ok(h, batch, width, frames_hwc, preds, n_frames, idx, x, pred, "cvae_preprocess_u8_gather")) return CVAE_EINVAL;
     return launch_preprocess_u8_gather(width, batch, frames_hwc, preds, n_frames, idx, x, pred, (hipStream_t)stream);
 }
 
@@ -762,13 +773,7 @@ int cvae_curate_select_recon(cvae_handle h, int32_t n_traj, const int64_t* traj_
                              int32_t collect, int64_t total_images, int64_t* running, int64_t* counts, int64_t* first,
                              int64_t* sel_first, int64_t* span, int64_t* ent_frame, int32_t* ent_kind, int64_t* ent_sel,
                              int64_t* sel, void* stream) {
-    if (!h) { cvae_set_error("cvae_curate_select_recon: null handle"); return CVAE_EINVAL; }
-    if (n_traj < 0 || n_frames < 0 || total_images < 0) {
-        cvae_set_error("cvae_curate_select_recon: n_traj %d, n_frames %lld, total_images %lld must be >= 0", n_traj,
-                       (long long)n_frames, (long long)total_images);
-        return CVAE_EINVAL;
-    }
-    if (collect < 1) { cvae_set_error("cvae_curate_select_recon: collect %d must be >= 1", collect); return CVAE_EINVAL; }
+    if (!curate_args_ok(h, n_traj, n_frames, collect, total_images, "cvae_curate_select_recon")) return CVAE_EINVAL;
     if (!running || !span || (n_traj > 0 && (!traj_offsets || !counts || !first || !sel_first)) ||
         (n_frames > 0 && (!preds || !ent_frame || !ent_kind || !ent_sel || !sel))) {
         cvae_set_error("cvae_curate_select_recon: null pointer"); return CVAE_EINVAL;
@@ -799,14 +804,7 @@ int cvae_inject_zcat(cvae_handle h, int32_t n_images, int32_t n_rewards, const f
 
 int cvae_gather_f32(cvae_handle h, int32_t batch, int32_t width, const float* frames, const float* preds, int64_t n_frames,
                     const int64_t* idx, float* x, float* pred, void* stream) {
-    if (!h) { cvae_set_error("cvae_gather_f32: null handle"); return CVAE_EINVAL; }
-    if (width != h->cfg.width) { cvae_set_error("cvae_gather_f32: width %d, the handle's is %d", width, h->cfg.width); return CVAE_EINVAL; }
-    if (batch < 1 || batch > h->cfg.max_batch) { cvae_set_error("cvae_gather_f32: batch %d outside [1, %d]", batch, h->cfg.max_batch); return CVAE_EINVAL; }
-    if (n_frames < 1) { cvae_set_error("cvae_gather_f32: n_frames %lld must be >= 1", (long long)n_frames); return CVAE_EINVAL; }
-    if (!frames || !preds || !idx || !x || !pred) { cvae_set_error("cvae_gather_f32: null pointer"); return CVAE_EINVAL; }
-    if (((uintptr_t)frames & 15) || ((uintptr_t)x & 15)) {
-        cvae_set_error("cvae_gather_f32: frames and x must be 16-byte aligned"); return CVAE_EINVAL;
-    }
+    if (!batch_gather_ok(h, batch, width, frames, preds, n_frames, idx, x, pred, "cvae_gather_f32")) return CVAE_EINVAL;
     return launch_gather_f32(width, batch, frames, preds, n_frames, idx, x, pred, (hipStream_t)stream);
 }
 

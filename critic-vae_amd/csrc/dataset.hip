@@ -71,6 +71,26 @@ __global__ __launch_bounds__(TPB) void curate_count_kernel(const float* __restri
     }
 }
 
+// exclusive scan of v over the workgroup's threads on top of `carry`; total = the workgroup's sum.  wsum is written here and
+// read after the barrier inside: the caller puts a barrier before the next call on the same wsum.
+__device__ __forceinline__ int64_t block_scan_excl(int64_t v, int64_t* wsum, int64_t carry, int64_t& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int64_t incl = v;                                            // inclusive scan within the wave
+    for (int d = 1; d < 64; d <<= 1) {
+        const int64_t u = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += u;
+    }
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    int64_t before = carry + incl - v;
+    total = 0;
+    for (int w = 0; w < NWAVE; ++w) {
+        if (w < wv) before += wsum[w];
+        total += wsum[w];
+    }
+    return before;
+}
+
 // one workgroup, trajectories in order: trajectory t is visited iff running + (frames selected by the visited ones
 // before it) < total_images — the running count only grows, so that is an exclusive prefix sum compared with the cut.
 // first[t] = its first dataset slot (the reference's len(dset) before it) or -1; counts of unvisited ones become 0.
@@ -81,27 +101,16 @@ __global__ __launch_bounds__(TPB) void curate_cut_kernel(int n_traj, int64_t tot
                                                          int64_t* __restrict__ counts, int64_t* __restrict__ first,
                                                          int64_t* __restrict__ span, int64_t* __restrict__ ffirst) {
     __shared__ int64_t wsum[NWAVE];
-    __shared__ int64_t carry;
     __shared__ int64_t fsum[NWAVE];                              // MIDW > 1 only: the same scan over frames
-    __shared__ int64_t fcarry;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t r0 = *running;
-    if (tid == 0) { carry = r0; fcarry = 0; }
-    __syncthreads();
+    int64_t carry = r0, fcarry = 0;                              // identical in every thread
     for (int t0 = 0; t0 < n_traj; t0 += TPB) {
         const int t = t0 + tid;
         const int64_t s = t < n_traj ? MIDW * counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2] : 0;
-        int64_t incl = s;                                        // inclusive scan within the wave
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t v = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += v;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        int64_t before = carry;
-        for (int w = 0; w < wv; ++w) before += wsum[w];
-        before += incl - s;                                      // len(dset) before trajectory t
-        const int64_t block_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        int64_t total;
+        const int64_t before = block_scan_excl(s, wsum, carry, total);      // len(dset) before trajectory t
+        carry += total;
         const bool visited = t < n_traj && before < total_images;
         if (t < n_traj) {
             if (visited) {
@@ -111,24 +120,13 @@ __global__ __launch_bounds__(TPB) void curate_cut_kernel(int n_traj, int64_t tot
                 counts[(int64_t)t * 3] = counts[(int64_t)t * 3 + 1] = counts[(int64_t)t * 3 + 2] = 0;
             }
         }
-        int64_t fblock = 0;
         if constexpr (MIDW > 1) {                                // visited trajectories are a prefix: unvisited ones add 0
             const int64_t sf = visited ? counts[(int64_t)t * 3] + counts[(int64_t)t * 3 + 1] + counts[(int64_t)t * 3 + 2] : 0;
-            int64_t fi = sf;
-            for (int d = 1; d < 64; d <<= 1) {
-                const int64_t v = __shfl_up(fi, d, 64);
-                if (lane >= d) fi += v;
-            }
-            if (lane == 63) fsum[wv] = fi;
-            __syncthreads();
-            int64_t fb = fcarry;
-            for (int w = 0; w < wv; ++w) fb += fsum[w];
-            if (t < n_traj) ffirst[t] = visited ? fb + fi - sf : -1;
-            fblock = fsum[0] + fsum[1] + fsum[2] + fsum[3];
+            const int64_t fbefore = block_scan_excl(sf, fsum, fcarry, total);
+            fcarry += total;
+            if (t < n_traj) ffirst[t] = visited ? fbefore : -1;
         }
-        __syncthreads();
-        if (tid == 0) { carry += block_total; fcarry += fblock; }
-        __syncthreads();
+        __syncthreads();                                         // the next round rewrites wsum / fsum; tid 0 reads first / counts below
     }
     // the visited trajectories are a prefix: the new running count is the last visited one's first + its selection
     if (tid == 0) {
@@ -320,24 +318,40 @@ __global__ __launch_bounds__(TPB) void gather_f32_kernel(const uint4* __restrict
     if (piece == 0 && threadIdx.x == 0) pred[b] = ok ? preds[s] : __builtin_nanf("");
 }
 
+// the three launches of one chunk's selection; the recon-only outputs are null at MIDW = 1
+template <int MIDW>
+int launch_curate(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect, int64_t total_images,
+                  int64_t* running, int64_t* counts, int64_t* first, int64_t* sel_first, int64_t* span, int64_t* ent_frame,
+                  int32_t* ent_kind, int64_t* ent_sel, int64_t* sel, hipStream_t st) {
+    if (n_traj > 0) {
+        hipLaunchKernelGGL(curate_count_kernel, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, counts);
+        CVAE_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(curate_cut_kernel<MIDW>, dim3(1), dim3(TPB), 0, st, n_traj, total_images, running, counts, first, span, sel_first);
+    CVAE_CHECK_LAUNCH();
+    if (n_traj > 0) {
+        hipLaunchKernelGGL(curate_scatter_kernel<MIDW>, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, first,
+                           span, ent_frame, (const int64_t*)sel_first, ent_kind, ent_sel, sel);
+        CVAE_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
 }  // namespace
+
+int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
+                         int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* span,
+                         int64_t* sel, hipStream_t st) {
+    return launch_curate<1>(n_traj, off, n_frames, preds, collect, total_images, running, counts, first, nullptr, span, sel,
+                            nullptr, nullptr, nullptr, st);
+}
 
 int launch_curate_select_recon(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
                                int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* sel_first,
                                int64_t* span, int64_t* ent_frame, int32_t* ent_kind, int64_t* ent_sel, int64_t* sel,
                                hipStream_t st) {
-    if (n_traj > 0) {
-        hipLaunchKernelGGL(curate_count_kernel, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, counts);
-        CVAE_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(curate_cut_kernel<2>, dim3(1), dim3(TPB), 0, st, n_traj, total_images, running, counts, first, span, sel_first);
-    CVAE_CHECK_LAUNCH();
-    if (n_traj > 0) {
-        hipLaunchKernelGGL(curate_scatter_kernel<2>, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, first,
-                           span, ent_frame, (const int64_t*)sel_first, ent_kind, ent_sel, sel);
-        CVAE_CHECK_LAUNCH();
-    }
-    return 0;
+    return launch_curate<2>(n_traj, off, n_frames, preds, collect, total_images, running, counts, first, sel_first, span,
+                            ent_frame, ent_kind, ent_sel, sel, st);
 }
 
 int launch_recon_zcat(int n_entries, const int64_t* ent_sel, const int32_t* ent_kind, const float* mu, const float* sel_pred,
@@ -363,24 +377,6 @@ int launch_gather_f32(int width, int B, const float* frames, const float* preds,
     hipLaunchKernelGGL(gather_f32_kernel, dim3((unsigned)((int64_t)B * bpf)), dim3(TPB), 0, st, (const uint4*)frames, preds, n, idx,
                        (uint4*)x, pred, units, bpf);
     CVAE_CHECK_LAUNCH();
-    return 0;
-}
-
-int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
-                         int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* span,
-                         int64_t* sel, hipStream_t st) {
-    if (n_traj > 0) {
-        hipLaunchKernelGGL(curate_count_kernel, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, counts);
-        CVAE_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(curate_cut_kernel<1>, dim3(1), dim3(TPB), 0, st, n_traj, total_images, running, counts, first, span,
-                       (int64_t*)nullptr);
-    CVAE_CHECK_LAUNCH();
-    if (n_traj > 0) {
-        hipLaunchKernelGGL(curate_scatter_kernel<1>, dim3((unsigned)n_traj), dim3(TPB), 0, st, preds, off, n_frames, collect, first, span,
-                           sel, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr);
-        CVAE_CHECK_LAUNCH();
-    }
     return 0;
 }
 

@@ -20,12 +20,14 @@ vae.evaluate(obs, 0) — two entries for a mid frame, one for a high (at p) or l
     FusedTrainer(vae2).fit_device(rd, batch_size=128, epochs=7)
 """
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import params as P
 from .critic import Critic
+from .feeder import StagingSet
 from .lib import Handle
 
 # bin edges as the reference compares them: a float32 tensor against a Python float, in float32
@@ -68,32 +70,40 @@ def reference_order(names, seed=0):
     return names
 
 
-def select_host(traj_preds, collect=P.collect, total_images=P.total_images):
-    """vae_utility.py:406-459 restated in plain Python over critic values (float32 comparisons, as torch makes them).
-    traj_preds: per visited-order trajectory, its frames' critic values.  Returns (sizes, selected, counts):
-    sizes = len(dset) before each visited trajectory (the reference's `total images = ...` prints), selected = [(t, i)]
-    in dataset order, counts (T, 3) int64 = frames taken per bin (mid, high, low), 0 for trajectories never visited."""
-    sizes, selected = [], []
+def _select_walk(traj_preds, collect, total_images, mid, high, low):
+    """vae_utility.py:406-459 in plain Python over critic values (float32 comparisons, as torch makes them).  mid / high /
+    low (t, i) -> the dataset rows a kept frame of that bin appends; len(dset) — the cut and the sizes — counts rows."""
+    sizes, rows = [], []
     counts = np.zeros((len(traj_preds), 3), np.int64)
     for t, preds in enumerate(traj_preds):
-        if len(selected) >= total_images:
+        if len(rows) >= total_images:
             break
-        sizes.append(len(selected))
+        sizes.append(len(rows))
         c_high = c_mid = c_low = 0
         for i, pred in enumerate(np.asarray(preds, np.float32).reshape(-1)):
             if c_high >= collect and c_low >= collect and c_mid >= collect:
                 break
             elif MID_LO <= pred <= MID_HI and c_mid < collect:
-                selected.append((t, i))
+                rows += mid(t, i)
                 c_mid += 1
             elif pred >= HIGH and c_high < collect:
-                selected.append((t, i))
+                rows += high(t, i)
                 c_high += 1
             elif pred <= LOW and c_low < collect:
-                selected.append((t, i))
+                rows += low(t, i)
                 c_low += 1
         counts[t] = (c_mid, c_high, c_low)
-    return sizes, selected, counts
+    return sizes, rows, counts
+
+
+def select_host(traj_preds, collect=P.collect, total_images=P.total_images):
+    """vae_utility.py:406-459 restated in plain Python over critic values (float32 comparisons, as torch makes them).
+    traj_preds: per visited-order trajectory, its frames' critic values.  Returns (sizes, selected, counts):
+    sizes = len(dset) before each visited trajectory (the reference's `total images = ...` prints), selected = [(t, i)]
+    in dataset order, counts (T, 3) int64 = frames taken per bin (mid, high, low), 0 for trajectories never visited."""
+    def frame(t, i):
+        return [(t, i)]
+    return _select_walk(traj_preds, collect, total_images, frame, frame, frame)
 
 
 def select_recon_host(traj_preds, collect=P.collect, total_images=P.total_images):
@@ -101,53 +111,45 @@ def select_recon_host(traj_preds, collect=P.collect, total_images=P.total_images
     at its critic value, then kind 1 = decoded at 0) and counts once against the mid cap, a high frame one entry of kind 0, a
     low frame one of kind 1; len(dset) — the cut and the sizes — counts entries.  Returns (sizes, entries, counts): entries =
     [(t, i, kind)] in dataset order, counts (T, 3) = FRAMES taken per bin."""
-    sizes, entries = [], []
-    counts = np.zeros((len(traj_preds), 3), np.int64)
-    for t, preds in enumerate(traj_preds):
-        if len(entries) >= total_images:
-            break
-        sizes.append(len(entries))
-        c_high = c_mid = c_low = 0
-        for i, pred in enumerate(np.asarray(preds, np.float32).reshape(-1)):
-            if c_high >= collect and c_low >= collect and c_mid >= collect:
-                break
-            elif MID_LO <= pred <= MID_HI and c_mid < collect:
-                entries.append((t, i, 0))
-                entries.append((t, i, 1))
-                c_mid += 1
-            elif pred >= HIGH and c_high < collect:
-                entries.append((t, i, 0))
-                c_high += 1
-            elif pred <= LOW and c_low < collect:
-                entries.append((t, i, 1))
-                c_low += 1
-        counts[t] = (c_mid, c_high, c_low)
-    return sizes, entries, counts
+    return _select_walk(traj_preds, collect, total_images, lambda t, i: [(t, i, 0), (t, i, 1)],
+                        lambda t, i: [(t, i, 0)], lambda t, i: [(t, i, 1)])
 
 
-class DeviceDataset:
-    """A training set on the device: frames (N, w, w, 3) uint8, preds (N, 1) fp32 (the critic's value of every frame),
-    source (N, 2) int64 host array (trajectory, frame).  curate() also fills `names` (visited trajectories, in order),
-    `sizes` (len(dset) before each) and `counts` (per visited trajectory, frames per bin mid / high / low)."""
+class _CuratedDataset:
+    """What DeviceDataset and ReconDataset share: preds beside the frames, source (N, SOURCE_COLS), names / sizes / counts."""
 
-    def __init__(self, frames, preds, source, names=(), sizes=(), counts=None):
-        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3
-                and frames.shape[1] == frames.shape[2] and frames.is_contiguous()):
-            raise ValueError("frames must be a contiguous uint8 device tensor (N, w, w, 3)")
+    def __init__(self, frames, preds, source, names, sizes, counts):
         if not (preds.is_cuda and preds.dtype == torch.float32 and tuple(preds.shape) == (frames.shape[0], 1)
                 and preds.is_contiguous()):
             raise ValueError("preds must be a contiguous fp32 device tensor (N, 1)")
         self.frames, self.preds = frames, preds
-        self.source = np.asarray(source, np.int64).reshape(-1, 2)
+        self.source = np.asarray(source, np.int64).reshape(-1, self.SOURCE_COLS)
         self.names, self.sizes = list(names), list(sizes)
         self.counts = np.zeros((0, 3), np.int64) if counts is None else np.asarray(counts, np.int64)
 
     def __len__(self):
         return self.frames.shape[0]
 
+
+class DeviceDataset(_CuratedDataset):
+    """A training set on the device: frames (N, w, w, 3) uint8, preds (N, 1) fp32 (the critic's value of every frame),
+    source (N, 2) int64 host array (trajectory, frame).  curate() also fills `names` (visited trajectories, in order),
+    `sizes` (len(dset) before each) and `counts` (per visited trajectory, frames per bin mid / high / low)."""
+    SOURCE_COLS = 2
+
+    def __init__(self, frames, preds, source, names=(), sizes=(), counts=None):
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3
+                and frames.shape[1] == frames.shape[2] and frames.is_contiguous()):
+            raise ValueError("frames must be a contiguous uint8 device tensor (N, w, w, 3)")
+        super().__init__(frames, preds, source, names, sizes, counts)
+
     @property
     def width(self):
         return self.frames.shape[1]
+
+    def gather(self, handle, nb, idx, x, pred):
+        """One training batch: x = frames[idx] / 255 as CHW fp32, pred = preds[idx] (cvae_preprocess_u8_gather)."""
+        handle.preprocess_u8_gather(nb, self.frames, self.preds, idx, x, pred)
 
     @classmethod
     def from_host(cls, frames_u8, critic=None, device="cuda:0"):
@@ -196,6 +198,118 @@ def _chunks(lengths, chunk_frames):
     return out
 
 
+class _PlainPlan:
+    """What curate() adds to the walk: one uint8 entry per kept frame, gathered out of the chunk on the device."""
+    who, per_frame, per_traj, x_rows = "curate", 1, 3, 0        # a trajectory adds at most per_traj * collect entries
+
+    def validate(self, device):
+        pass
+
+    def allocate(self, cap, biggest, device):
+        self.frames = torch.empty(max(cap, 1), 64, 64, 3, dtype=torch.uint8, device=device)
+        self.preds = torch.empty(max(cap, 1), 1, device=device)
+        self.sel = torch.empty(biggest, dtype=torch.int64, device=device)
+        self.span = torch.zeros(2, dtype=torch.int64, device=device)
+
+    def enqueue(self, w, ch):
+        w.h.curate_select(ch.d_offs, w.cpred[:ch.n], w.collect, w.total_images, w.running, ch.d_counts, ch.d_first, self.span,
+                          self.sel)
+        if ch.n:
+            w.h.gather_frames_u8(ch.set.dev, w.cpred, self.sel, ch.n, self.span, self.frames, self.preds)
+        ch.set.release(w.stream)
+
+    def collect(self, w, ch):
+        sp = self.span.cpu().numpy()
+        return int(sp[0] + sp[1]), self.sel[:int(sp[1])].cpu().numpy(), []
+
+    def summary(self, n, n_traj, tot):
+        return f"dataset: {n} frames from {n_traj} trajectories (mid {tot[0]}, high {tot[1]}, low {tot[2]})"
+
+    def dataset(self, n, source, names, sizes, counts):
+        return DeviceDataset(self.frames[:n], self.preds[:n], source, names, sizes, counts)
+
+
+def _walk(plan, episodes, critic, collect, total_images, chunk_frames, order, device, log):
+    """The walk of curate() and curate_recon().  Per chunk: the critic pass, plan.enqueue (the selection and what needs no host
+    read), the staging of the next chunk, plan.collect (the host reads and what they size) -> (len(dset) after the chunk, the
+    chunk frame index of every new entry, further source columns), the per-trajectory records and the cut."""
+    if not isinstance(critic, Critic):
+        raise TypeError(f"{plan.who} needs a critic_vae_amd.critic.Critic (the HIP critic)")
+    if collect < 1 or total_images < 0:
+        raise ValueError(f"collect {collect} must be >= 1 and total_images {total_images} >= 0")
+    device = torch.device(device)
+    plan.validate(device)
+    episodes = list(episodes)
+    by_name = {}
+    for pos, (name, a) in enumerate(episodes):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 4 and a.shape[1:] == (64, 64, 3)):
+            raise ValueError(f"trajectory {name!r}: curation needs uint8 (T, 64, 64, 3) frames (the critic is 64x64 only)")
+        by_name[name] = pos
+    names = reference_order([n for n, _ in episodes]) if order is None else list(order)
+    walk = [by_name[n] for n in names]
+    lengths = [episodes[p][1].shape[0] for p in walk]
+    # the cut overshoots by at most per_traj * collect - 1 entries, and no walk selects more than the trajectories can yield
+    cap = min(total_images - 1 + plan.per_traj * collect, plan.per_frame * sum(lengths)) if total_images > 0 else 0
+    log("loading episodes...")
+    if total_images == 0 or not walk:
+        plan.allocate(0, 1, device)
+        return plan.dataset(0, [], [], [], None)
+
+    chunks = _chunks(lengths, chunk_frames)
+    biggest = max(max(sum(lengths[t] for t in c) for c in chunks), 1)
+    plan.allocate(cap, biggest, device)
+    w = SimpleNamespace(h=Handle(64, CURATE_PIECE), critic=critic, collect=collect, total_images=total_images, cap=cap,
+                        x=torch.empty(max(CURATE_PIECE, plan.x_rows), 3, 64, 64, device=device),
+                        cpred=torch.empty(biggest, device=device),
+                        running=torch.zeros(1, dtype=torch.int64, device=device),
+                        stream=torch.cuda.current_stream(device))
+    copy_stream = torch.cuda.Stream(device=device)
+    sets = [StagingSet(biggest, 64, device, copy_stream) for _ in range(2)]
+
+    def rows_of(c):
+        def fill(pin):
+            n = 0
+            for t in c:
+                a = episodes[walk[t]][1]
+                pin[n:n + a.shape[0]] = a
+                n += a.shape[0]
+            return n
+        return fill
+
+    source, sizes, visited, counts = [], [], [], []
+    sets[0].stage(rows_of(chunks[0]))
+    for ci, c in enumerate(chunks):
+        s = sets[ci % 2]
+        s.wait_copied(w.stream)
+        offs = np.concatenate([[0], np.cumsum([lengths[t] for t in c])]).astype(np.int64)
+        ch = SimpleNamespace(index=ci, set=s, n=s.n, d_offs=torch.from_numpy(offs).to(device),
+                             d_counts=torch.empty(len(c), 3, dtype=torch.int64, device=device),
+                             d_first=torch.empty(len(c), dtype=torch.int64, device=device))
+        if s.n:
+            _critic_values(critic, s.dev[:s.n], w.cpred[:s.n], handle=w.h, x=w.x)
+        plan.enqueue(w, ch)
+        if ci + 1 < len(chunks):
+            sets[(ci + 1) % 2].stage(rows_of(chunks[ci + 1]))  # host fill + H2D of the next chunk under this one's kernels
+        end, picked, extra = plan.collect(w, ch)
+        first, cnt = ch.d_first.cpu().numpy(), ch.d_counts.cpu().numpy()
+        tr = np.searchsorted(offs, picked, side="right") - 1
+        source.append(np.stack([np.asarray(walk)[np.asarray(c)[tr]] if len(picked) else np.zeros(0, np.int64),
+                                picked - offs[tr]] + extra, 1))
+        for j, t in enumerate(c):
+            if first[j] >= 0:
+                log(f"total images = {first[j]}")
+                sizes.append(int(first[j]))
+                visited.append(names[t])
+                counts.append(cnt[j])
+        if end >= total_images:
+            break
+    torch.cuda.synchronize(device)
+    n = int(w.running.item())
+    counts = np.array(counts, np.int64).reshape(-1, 3)
+    log(plan.summary(n, len(visited), counts.sum(0)))
+    return plan.dataset(n, np.concatenate(source).astype(np.int64), visited, sizes, counts)
+
+
 def curate(episodes, critic, collect=P.collect, total_images=P.total_images, chunk_frames=8192, order=None,
            device="cuda:0", log=print):
     """load_minerl_data(critic) (vae_utility.py:393-461, non-recon branch) on the device.
@@ -207,120 +321,31 @@ def curate(episodes, critic, collect=P.collect, total_images=P.total_images, chu
     the device) and cvae_gather_frames_u8 into the dataset buffer.  The running count is read once per chunk, to stop
     streaming at the cut.  log gets the reference's progress lines (`total images = N` before each visited trajectory)
     and the per-bin totals.  Returns a DeviceDataset."""
-    if not isinstance(critic, Critic):
-        raise TypeError("curate needs a critic_vae_amd.critic.Critic (the HIP critic)")
-    if collect < 1 or total_images < 0:
-        raise ValueError(f"collect {collect} must be >= 1 and total_images {total_images} >= 0")
-    episodes = list(episodes)
-    by_name = {}
-    for pos, (name, a) in enumerate(episodes):
-        if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 4 and a.shape[1:] == (64, 64, 3)):
-            raise ValueError(f"trajectory {name!r}: curation needs uint8 (T, 64, 64, 3) frames (the critic is 64x64 only)")
-        by_name[name] = pos
-    names = reference_order([n for n, _ in episodes]) if order is None else list(order)
-    walk = [by_name[n] for n in names]
-    device = torch.device(device)
-    # the cut overshoots by at most 3 * collect - 1 frames, and no walk selects more frames than the trajectories hold
-    cap = min(total_images - 1 + 3 * collect, sum(episodes[p][1].shape[0] for p in walk)) if total_images > 0 else 0
-    ds_frames = torch.empty(max(cap, 1), 64, 64, 3, dtype=torch.uint8, device=device)
-    ds_preds = torch.empty(max(cap, 1), 1, device=device)
-    log("loading episodes...")
-    if total_images == 0 or not walk:
-        return DeviceDataset(ds_frames[:0], ds_preds[:0], np.zeros((0, 2), np.int64))
-
-    lengths = [episodes[p][1].shape[0] for p in walk]
-    chunks = _chunks(lengths, chunk_frames)
-    biggest = max(sum(lengths[t] for t in c) for c in chunks)
-    h = Handle(64, CURATE_PIECE)
-    x = torch.empty(CURATE_PIECE, 3, 64, 64, device=device)
-    cpred = torch.empty(max(biggest, 1), device=device)
-    sel = torch.empty(max(biggest, 1), dtype=torch.int64, device=device)
-    running = torch.zeros(1, dtype=torch.int64, device=device)
-    span = torch.zeros(2, dtype=torch.int64, device=device)
-    copy_stream = torch.cuda.Stream(device=device)
-    sets = [{"pin": torch.empty(max(biggest, 1), 64, 64, 3, dtype=torch.uint8).pin_memory(),
-             "dev": torch.empty(max(biggest, 1), 64, 64, 3, dtype=torch.uint8, device=device),
-             "copied": torch.cuda.Event(), "consumed": torch.cuda.Event(), "used": False} for _ in range(2)]
-
-    def stage(s, c):
-        if s["used"]:
-            s["consumed"].synchronize()
-        pin, n = s["pin"].numpy(), 0
-        for t in c:
-            a = episodes[walk[t]][1]
-            pin[n:n + a.shape[0]] = a
-            n += a.shape[0]
-        with torch.cuda.stream(copy_stream):
-            s["dev"][:n].copy_(s["pin"][:n], non_blocking=True)
-            s["copied"].record(copy_stream)
-        s["used"], s["n"] = True, n
-
-    source, sizes, visited, counts = [], [], [], []
-    cur = torch.cuda.current_stream(device)
-    stage(sets[0], chunks[0])
-    for ci, c in enumerate(chunks):
-        s = sets[ci % 2]
-        n = s["n"]
-        cur.wait_event(s["copied"])
-        offs = np.concatenate([[0], np.cumsum([lengths[t] for t in c])]).astype(np.int64)
-        d_offs = torch.from_numpy(offs).to(device)
-        d_counts = torch.empty(len(c), 3, dtype=torch.int64, device=device)
-        d_first = torch.empty(len(c), dtype=torch.int64, device=device)
-        if n:
-            _critic_values(critic, s["dev"][:n], cpred[:n], handle=h, x=x)
-        h.curate_select(d_offs, cpred[:n], collect, total_images, running, d_counts, d_first, span, sel)
-        if n:
-            h.gather_frames_u8(s["dev"], cpred, sel, n, span, ds_frames, ds_preds)
-        s["consumed"].record(cur)
-        if ci + 1 < len(chunks):
-            stage(sets[(ci + 1) % 2], chunks[ci + 1])          # host fill + H2D of the next chunk under this one's kernels
-        first, cnt, sp = d_first.cpu().numpy(), d_counts.cpu().numpy(), span.cpu().numpy()
-        picked = sel[:int(sp[1])].cpu().numpy()
-        tr = np.searchsorted(offs, picked, side="right") - 1
-        source.append(np.stack([np.asarray(walk)[np.asarray(c)[tr]] if len(picked) else np.zeros(0, np.int64),
-                                picked - offs[tr]], 1))
-        for j, t in enumerate(c):
-            if first[j] >= 0:
-                log(f"total images = {first[j]}")
-                sizes.append(int(first[j]))
-                visited.append(names[t])
-                counts.append(cnt[j])
-        if sp[0] + sp[1] >= total_images:
-            break
-    torch.cuda.synchronize(device)
-    n = int(running.item())
-    counts = np.array(counts, np.int64).reshape(-1, 3)
-    tot = counts.sum(0)
-    log(f"dataset: {n} frames from {len(visited)} trajectories (mid {tot[0]}, high {tot[1]}, low {tot[2]})")
-    return DeviceDataset(ds_frames[:n], ds_preds[:n], np.concatenate(source).astype(np.int64), visited, sizes, counts)
+    return _walk(_PlainPlan(), episodes, critic, collect, total_images, chunk_frames, order, device, log)
 
 
-class ReconDataset:
+class ReconDataset(_CuratedDataset):
     """The second VAE's training set on the device: frames (N, 3, w, w) fp32 = the first VAE's eval-mode reconstructions
     (Tanh range), preds (N, 1) fp32 = the critic's value OF THE RECONSTRUCTION (train() evaluates the critic on what it
     trains on, vae.py:50; the critic is frozen, so the value is computed once), source (N, 3) int64 host array (trajectory,
     frame, kind: 0 = decoded at the frame's critic value, 1 = decoded at 0).  names / sizes / counts as DeviceDataset has
     them (sizes count entries, counts frames per bin); stats = what curate_recon ran (walked / encoded / decoded)."""
+    SOURCE_COLS = 3
 
     def __init__(self, frames, preds, source, names=(), sizes=(), counts=None, stats=None):
         if not (frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 4 and frames.shape[1] == 3
                 and frames.shape[2] == frames.shape[3] and frames.is_contiguous()):
             raise ValueError("frames must be a contiguous fp32 device tensor (N, 3, w, w)")
-        if not (preds.is_cuda and preds.dtype == torch.float32 and tuple(preds.shape) == (frames.shape[0], 1)
-                and preds.is_contiguous()):
-            raise ValueError("preds must be a contiguous fp32 device tensor (N, 1)")
-        self.frames, self.preds = frames, preds
-        self.source = np.asarray(source, np.int64).reshape(-1, 3)
-        self.names, self.sizes = list(names), list(sizes)
-        self.counts = np.zeros((0, 3), np.int64) if counts is None else np.asarray(counts, np.int64)
+        super().__init__(frames, preds, source, names, sizes, counts)
         self.stats = dict(stats or {})
-
-    def __len__(self):
-        return self.frames.shape[0]
 
     @property
     def width(self):
         return self.frames.shape[2]
+
+    def gather(self, handle, nb, idx, x, pred):
+        """One training batch: x = frames[idx] (a bit copy), pred = preds[idx] (cvae_gather_f32)."""
+        handle.gather_f32(nb, self.frames, self.preds, idx, x, pred)
 
     def save(self, path):
         """Plain arrays (numpy .npz, uncompressed): frames, preds, source, names, sizes, counts."""
@@ -341,6 +366,75 @@ class ReconDataset:
         return [a[i:i + 1].copy() for i in range(a.shape[0])]
 
 
+class _ReconPlan:
+    """What curate_recon() adds to the walk: the first VAE's reconstructions of the kept frames, two entries for a mid frame."""
+    who, per_frame, per_traj = "curate_recon", 2, 4               # a trajectory adds at most per_traj * collect entries
+
+    def __init__(self, vae):
+        self.vae, self.x_rows = vae, vae.max_batch
+        self.stats = {"walked": 0, "encoded": 0, "decoded": 0}
+
+    def validate(self, device):
+        if self.vae.width != 64:
+            raise ValueError("curate_recon needs a 64x64 VAE (the critic is 64x64 only)")
+        self.vae.eval()
+        if self.vae.theta.device != device:
+            raise ValueError(f"the VAE is on {self.vae.theta.device}, the dataset goes to {device}")
+
+    def allocate(self, cap, biggest, device):
+        VB = self.vae.max_batch
+        self.frames = torch.empty(max(cap, 1), 3, 64, 64, device=device)
+        self.preds = torch.empty(max(cap, 1), 1, device=device)
+        self.ws = self.vae._workspace(VB)
+        self.sel = torch.empty(biggest, dtype=torch.int64, device=device)
+        self.ent_frame = torch.empty(2 * biggest, dtype=torch.int64, device=device)
+        self.ent_sel = torch.empty(2 * biggest, dtype=torch.int64, device=device)
+        self.ent_kind = torch.empty(2 * biggest, dtype=torch.int32, device=device)
+        self.mu = torch.empty(biggest, P.latent_dim, device=device)
+        self.spred = torch.empty(biggest, 1, device=device)
+        self.logvar = torch.empty(VB, P.latent_dim, device=device)
+        self.zeros = torch.zeros(VB, P.latent_dim, device=device)
+        self.zcat = torch.empty(VB, P.latent_dim + 1, device=device)
+        self.span = torch.zeros(3, dtype=torch.int64, device=device)
+
+    def enqueue(self, w, ch):
+        d_sfirst = torch.empty(ch.d_first.shape[0], dtype=torch.int64, device=ch.d_first.device)
+        w.h.curate_select_recon(ch.d_offs, w.cpred[:ch.n], w.collect, w.total_images, w.running, ch.d_counts, ch.d_first,
+                                d_sfirst, self.span, self.ent_frame, self.ent_kind, self.ent_sel, self.sel)
+
+    def collect(self, w, ch):
+        vae, vh, VB, theta = self.vae, self.vae.handle, self.vae.max_batch, self.vae.theta.data
+        sp = self.span.cpu().numpy()                           # the one host read of the chunk: sizes the launches below
+        e0, ne, ns = int(sp[0]), int(sp[1]), int(sp[2])
+        if e0 + ne > w.cap or ns > ch.n:
+            raise RuntimeError(f"curate_recon: chunk {ch.index} claims entries [{e0}, {e0 + ne}) of {w.cap} and {ns} of {ch.n} frames")
+        for p in range(0, ns, VB):                             # the encoder, once per selected frame
+            nb = min(VB, ns - p)
+            vh.preprocess_u8_gather(nb, ch.set.dev, w.cpred, self.sel[p:p + nb], w.x[:nb], self.spred[p:p + nb])
+            vh.forward(nb, w.x[:nb], self.spred[p:p + nb], self.zeros[:nb], theta, vae.bn_state, self.mu[p:p + nb],
+                       self.logvar[:nb], None, self.ws, train=False)
+        ch.set.release(w.stream)
+        for p in range(0, ne, VB):                             # the decoder, once per entry, into the dataset slots
+            nb = min(VB, ne - p)
+            vh.recon_zcat(nb, self.ent_sel[p:p + nb], self.ent_kind[p:p + nb], self.mu[:ns], self.spred[:ns], self.zcat[:nb])
+            vh.decode(nb, self.zcat[:nb], theta, self.frames[e0 + p:e0 + p + nb], self.ws)
+        for p in range(0, ne, CURATE_PIECE):                   # train() evaluates the critic on the reconstructions
+            nb = min(CURATE_PIECE, ne - p)
+            w.h.critic_forward(nb, self.frames[e0 + p:e0 + p + nb], w.critic.flat, self.preds[e0 + p:e0 + p + nb])
+        vae._stamp_workspace()
+        self.stats["walked"] += ch.n
+        self.stats["encoded"] += ns
+        self.stats["decoded"] += ne
+        return e0 + ne, self.ent_frame[:ne].cpu().numpy(), [self.ent_kind[:ne].cpu().numpy().astype(np.int64)]
+
+    def summary(self, n, n_traj, tot):
+        return (f"recon dataset: {n} entries from {self.stats['encoded']} frames of {n_traj} trajectories "
+                f"(mid {tot[0]}, high {tot[1]}, low {tot[2]})")
+
+    def dataset(self, n, source, names, sizes, counts):
+        return ReconDataset(self.frames[:n], self.preds[:n], source, names, sizes, counts, self.stats)
+
+
 def curate_recon(episodes, critic, vae, collect=P.collect, total_images=P.total_images, chunk_frames=8192, order=None,
                  device="cuda:0", log=print):
     """load_minerl_data(critic, recon_dset=True, vae=vae) (vae_utility.py:393-443) on the device.
@@ -352,124 +446,4 @@ def curate_recon(episodes, critic, vae, collect=P.collect, total_images=P.total_
     two entries; for the entries, in pieces: cvae_recon_zcat and cvae_decode straight into the dataset slots (no staging
     copy), then cvae_critic_forward on the finished entries for preds.  Unselected frames cost the critic launch only.
     The VAE is put in eval mode and must be 64 x 64.  Returns a ReconDataset."""
-    if not isinstance(critic, Critic):
-        raise TypeError("curate_recon needs a critic_vae_amd.critic.Critic (the HIP critic)")
-    if collect < 1 or total_images < 0:
-        raise ValueError(f"collect {collect} must be >= 1 and total_images {total_images} >= 0")
-    if vae.width != 64:
-        raise ValueError("curate_recon needs a 64x64 VAE (the critic is 64x64 only)")
-    vae.eval()
-    episodes = list(episodes)
-    by_name = {}
-    for pos, (name, a) in enumerate(episodes):
-        if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 4 and a.shape[1:] == (64, 64, 3)):
-            raise ValueError(f"trajectory {name!r}: curation needs uint8 (T, 64, 64, 3) frames (the critic is 64x64 only)")
-        by_name[name] = pos
-    names = reference_order([n for n, _ in episodes]) if order is None else list(order)
-    walk = [by_name[n] for n in names]
-    device = torch.device(device)
-    if vae.theta.device != device:
-        raise ValueError(f"the VAE is on {vae.theta.device}, the dataset goes to {device}")
-    # the cut overshoots by at most 4 * collect - 1 entries, and no frame yields more than two
-    cap = min(total_images - 1 + 4 * collect, 2 * sum(episodes[p][1].shape[0] for p in walk)) if total_images > 0 else 0
-    ds_frames = torch.empty(max(cap, 1), 3, 64, 64, device=device)
-    ds_preds = torch.empty(max(cap, 1), 1, device=device)
-    stats = {"walked": 0, "encoded": 0, "decoded": 0}
-    log("loading episodes...")
-    if total_images == 0 or not walk:
-        return ReconDataset(ds_frames[:0], ds_preds[:0], np.zeros((0, 3), np.int64), stats=stats)
-
-    lengths = [episodes[p][1].shape[0] for p in walk]
-    chunks = _chunks(lengths, chunk_frames)
-    biggest = max(max(sum(lengths[t] for t in c) for c in chunks), 1)
-    h, vh, VB = Handle(64, CURATE_PIECE), vae.handle, vae.max_batch
-    theta, ws = vae.theta.data, vae._workspace(VB)
-    x = torch.empty(max(CURATE_PIECE, VB), 3, 64, 64, device=device)
-    cpred = torch.empty(biggest, device=device)
-    sel = torch.empty(biggest, dtype=torch.int64, device=device)
-    ent_frame = torch.empty(2 * biggest, dtype=torch.int64, device=device)
-    ent_sel = torch.empty(2 * biggest, dtype=torch.int64, device=device)
-    ent_kind = torch.empty(2 * biggest, dtype=torch.int32, device=device)
-    mu = torch.empty(biggest, P.latent_dim, device=device)
-    spred = torch.empty(biggest, 1, device=device)
-    logvar = torch.empty(VB, P.latent_dim, device=device)
-    zeros = torch.zeros(VB, P.latent_dim, device=device)
-    zcat = torch.empty(VB, P.latent_dim + 1, device=device)
-    running = torch.zeros(1, dtype=torch.int64, device=device)
-    span = torch.zeros(3, dtype=torch.int64, device=device)
-    copy_stream = torch.cuda.Stream(device=device)
-    sets = [{"pin": torch.empty(biggest, 64, 64, 3, dtype=torch.uint8).pin_memory(),
-             "dev": torch.empty(biggest, 64, 64, 3, dtype=torch.uint8, device=device),
-             "copied": torch.cuda.Event(), "consumed": torch.cuda.Event(), "used": False} for _ in range(2)]
-
-    def stage(s, c):
-        if s["used"]:
-            s["consumed"].synchronize()
-        pin, n = s["pin"].numpy(), 0
-        for t in c:
-            a = episodes[walk[t]][1]
-            pin[n:n + a.shape[0]] = a
-            n += a.shape[0]
-        with torch.cuda.stream(copy_stream):
-            s["dev"][:n].copy_(s["pin"][:n], non_blocking=True)
-            s["copied"].record(copy_stream)
-        s["used"], s["n"] = True, n
-
-    source, sizes, visited, counts = [], [], [], []
-    cur = torch.cuda.current_stream(device)
-    stage(sets[0], chunks[0])
-    for ci, c in enumerate(chunks):
-        s = sets[ci % 2]
-        n = s["n"]
-        cur.wait_event(s["copied"])
-        offs = np.concatenate([[0], np.cumsum([lengths[t] for t in c])]).astype(np.int64)
-        d_offs = torch.from_numpy(offs).to(device)
-        d_counts = torch.empty(len(c), 3, dtype=torch.int64, device=device)
-        d_first = torch.empty(len(c), dtype=torch.int64, device=device)
-        d_sfirst = torch.empty(len(c), dtype=torch.int64, device=device)
-        if n:
-            _critic_values(critic, s["dev"][:n], cpred[:n], handle=h, x=x)
-        h.curate_select_recon(d_offs, cpred[:n], collect, total_images, running, d_counts, d_first, d_sfirst, span,
-                              ent_frame, ent_kind, ent_sel, sel)
-        if ci + 1 < len(chunks):
-            stage(sets[(ci + 1) % 2], chunks[ci + 1])          # host fill + H2D of the next chunk under this one's kernels
-        sp = span.cpu().numpy()                                # the one host read of the chunk: sizes the launches below
-        e0, ne, ns = int(sp[0]), int(sp[1]), int(sp[2])
-        if e0 + ne > cap or ns > n:
-            raise RuntimeError(f"curate_recon: chunk {ci} claims entries [{e0}, {e0 + ne}) of {cap} and {ns} of {n} frames")
-        for p in range(0, ns, VB):                             # the encoder, once per selected frame
-            nb = min(VB, ns - p)
-            vh.preprocess_u8_gather(nb, s["dev"], cpred, sel[p:p + nb], x[:nb], spred[p:p + nb])
-            vh.forward(nb, x[:nb], spred[p:p + nb], zeros[:nb], theta, vae.bn_state, mu[p:p + nb], logvar[:nb], None, ws,
-                       train=False)
-        s["consumed"].record(cur)
-        for p in range(0, ne, VB):                             # the decoder, once per entry, into the dataset slots
-            nb = min(VB, ne - p)
-            vh.recon_zcat(nb, ent_sel[p:p + nb], ent_kind[p:p + nb], mu[:ns], spred[:ns], zcat[:nb])
-            vh.decode(nb, zcat[:nb], theta, ds_frames[e0 + p:e0 + p + nb], ws)
-        for p in range(0, ne, CURATE_PIECE):                   # train() evaluates the critic on the reconstructions
-            nb = min(CURATE_PIECE, ne - p)
-            h.critic_forward(nb, ds_frames[e0 + p:e0 + p + nb], critic.flat, ds_preds[e0 + p:e0 + p + nb])
-        vae._stamp_workspace()
-        stats["walked"] += n
-        stats["encoded"] += ns
-        stats["decoded"] += ne
-        first, cnt = d_first.cpu().numpy(), d_counts.cpu().numpy()
-        ef, ek = ent_frame[:ne].cpu().numpy(), ent_kind[:ne].cpu().numpy().astype(np.int64)
-        tr = np.searchsorted(offs, ef, side="right") - 1
-        source.append(np.stack([np.asarray(walk)[np.asarray(c)[tr]] if ne else np.zeros(0, np.int64), ef - offs[tr], ek], 1))
-        for j, t in enumerate(c):
-            if first[j] >= 0:
-                log(f"total images = {first[j]}")
-                sizes.append(int(first[j]))
-                visited.append(names[t])
-                counts.append(cnt[j])
-        if e0 + ne >= total_images:
-            break
-    torch.cuda.synchronize(device)
-    n = int(running.item())
-    counts = np.array(counts, np.int64).reshape(-1, 3)
-    tot = counts.sum(0)
-    log(f"recon dataset: {n} entries from {stats['encoded']} frames of {len(visited)} trajectories "
-        f"(mid {tot[0]}, high {tot[1]}, low {tot[2]})")
-    return ReconDataset(ds_frames[:n], ds_preds[:n], np.concatenate(source).astype(np.int64), visited, sizes, counts, stats)
+    return _walk(_ReconPlan(vae), episodes, critic, collect, total_images, chunk_frames, order, device, log)

@@ -18,6 +18,38 @@ import torch
 from .critic import Critic
 
 
+class StagingSet:
+    """One pinned host buffer of uint8 frames and its device twin, handed back and forth by two events: `copied` (the side
+    stream has brought the host rows over) and `consumed` (the compute stream has read the device rows, so both buffers
+    may be overwritten).  n = the rows of the current occupant."""
+
+    def __init__(self, rows, width, device, copy_stream):
+        self.pin = torch.empty((rows, width, width, 3), dtype=torch.uint8).pin_memory()
+        self.pin_np = self.pin.numpy()
+        self.dev = torch.empty((rows, width, width, 3), dtype=torch.uint8, device=device)
+        self.copy_stream = copy_stream
+        self.copied, self.consumed = torch.cuda.Event(), torch.cuda.Event()
+        self.n, self.used = 0, False
+
+    def stage(self, fill):
+        """Wait until the previous occupant has been consumed, let fill(pinned numpy view) write the rows and return their
+        number, and start the non-blocking H2D copy on the side stream."""
+        if self.used:
+            self.consumed.synchronize()
+        n = fill(self.pin_np)
+        with torch.cuda.stream(self.copy_stream):
+            self.dev[:n].copy_(self.pin[:n], non_blocking=True)
+            self.copied.record(self.copy_stream)
+        self.n, self.used = n, True
+
+    def wait_copied(self, stream):
+        stream.wait_event(self.copied)
+
+    def release(self, stream):
+        """Everything `stream` has been given so far is the last reader of this occupant."""
+        self.consumed.record(stream)
+
+
 class FrameFeeder:
     """Iterate `(images, preds)` device batches over a host uint8 dataset.
 
@@ -44,40 +76,31 @@ class FrameFeeder:
         self.device = torch.device(device)
         self.critic = critic
         self.copy_stream = torch.cuda.Stream(device=self.device)
-        self.sets = []
-        for _ in range(depth):
-            pin = torch.empty((self.B, self.W, self.W, 3), dtype=torch.uint8).pin_memory()
-            self.sets.append({
-                "pin": pin, "pin_np": pin.numpy(),
-                "dev_u8": torch.empty((self.B, self.W, self.W, 3), dtype=torch.uint8, device=self.device),
-                "x": torch.empty((self.B, 3, self.W, self.W), device=self.device),
-                "pred": torch.zeros((self.B, 1), device=self.device),
-                "copied": torch.cuda.Event(), "consumed": torch.cuda.Event(), "n": 0, "used": False})
+        self.sets = [StagingSet(self.B, self.W, self.device, self.copy_stream) for _ in range(depth)]
+        self.x = [torch.empty((self.B, 3, self.W, self.W), device=self.device) for _ in range(depth)]
+        self.pred = [torch.zeros((self.B, 1), device=self.device) for _ in range(depth)]
         self._handle = handle
 
-    # -- stage 1 (host + side stream): gather into pinned memory, async H2D
-    def _stage(self, s, idx):
-        n = len(idx)
-        if s["used"]:
-            s["consumed"].synchronize()          # the previous occupant of this set has been pre-processed
-        np.take(self.frames, idx, axis=0, out=s["pin_np"][:n])
-        with torch.cuda.stream(self.copy_stream):
-            s["dev_u8"][:n].copy_(s["pin"][:n], non_blocking=True)
-            s["copied"].record(self.copy_stream)
-        s["n"], s["used"] = n, True
+    # -- stage 1 (host + side stream): gather into pinned memory (the fill of StagingSet.stage), async H2D
+    def _take(self, idx):
+        def fill(pin):
+            np.take(self.frames, idx, axis=0, out=pin[:len(idx)])
+            return len(idx)
+        return fill
 
     # -- stage 2 (compute stream): uint8 HWC -> fp32 CHW/255, critic
-    def _finish(self, s):
-        n = s["n"]
+    def _finish(self, k):
+        s = self.sets[k]
+        n = s.n
         cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(s["copied"])
-        x = s["x"][:n]
-        self._handle.preprocess_u8(n, s["dev_u8"][:n], x)
-        s["consumed"].record(cur)
+        s.wait_copied(cur)
+        x = self.x[k][:n]
+        self._handle.preprocess_u8(n, s.dev[:n], x)
+        s.release(cur)                           # x holds the batch now: the uint8 set may be refilled
         if self.critic is None:
-            pred = s["pred"][:n]
+            pred = self.pred[k][:n]
         elif isinstance(self.critic, Critic):
-            pred = s["pred"][:n]
+            pred = self.pred[k][:n]
             self._handle.critic_forward(n, x, self.critic.flat, pred)
         else:
             pred = self.critic(x)
@@ -91,9 +114,9 @@ class FrameFeeder:
         if not order:
             return
         k = len(self.sets)
-        self._stage(self.sets[0], order[0])
+        self.sets[0].stage(self._take(order[0]))
         for i in range(len(order)):
-            out = self._finish(self.sets[i % k])
+            out = self._finish(i % k)
             yield out
             if i + 1 < len(order):
-                self._stage(self.sets[(i + 1) % k], order[i + 1])
+                self.sets[(i + 1) % k].stage(self._take(order[i + 1]))

@@ -129,22 +129,24 @@ def load():
     return lib
 
 
-def _ptr(t):
-    if t is None:
-        return None
-    if isinstance(t, int):
+_DTYPE_NAMES = {torch.float32: "fp32", torch.float64: "fp64", torch.uint8: "uint8", torch.int64: "int64", torch.int32: "int32"}
+
+
+def _dev_ptr(t, dtype, what):
+    """The address of a contiguous device tensor of `dtype`; None stays None (a NULL argument), an int is an address already."""
+    if t is None or isinstance(t, int):
         return t
-    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), \
-        f"need a contiguous fp32 device tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}"
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), \
+        f"{what}: need a contiguous {_DTYPE_NAMES[dtype]} device tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}"
     return t.data_ptr()
+
+
+def _ptr(t):
+    return _dev_ptr(t, torch.float32, "argument")
 
 
 def _ptr64(t):
-    if t is None:
-        return None
-    assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous(), \
-        f"need a contiguous fp64 device tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}"
-    return t.data_ptr()
+    return _dev_ptr(t, torch.float64, "argument")
 
 
 def sync_slot(point):
@@ -164,6 +166,9 @@ class Handle:
     """Opaque library handle + the flat-parameter layout it reports."""
 
     PRECISIONS = {"f32": 0, "bf16": 1, "bf16x9": 2, "bf16x6": 3}
+    _u8 = staticmethod(lambda t, what: _dev_ptr(t, torch.uint8, what))
+    _i32 = staticmethod(lambda t, what: _dev_ptr(t, torch.int32, what))
+    _i64 = staticmethod(lambda t, what: _dev_ptr(t, torch.int64, what))
 
     def __init__(self, width=64, max_batch=256, overlap_wgrad=None, precision="f32"):
         """precision "f32": every contraction on the exact-fp32 MFMA (the 1e-4 parity path).
@@ -291,19 +296,23 @@ class Handle:
         self._check(self.lib.cvae_critic_forward(self.h, B, _ptr(x), _ptr(critic_params), _ptr(pred), _stream()))
 
     def preprocess_u8(self, B, frames_u8, x):
-        assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
-        self._check(self.lib.cvae_preprocess_u8(self.h, B, frames_u8.data_ptr(), _ptr(x), _stream()))
+        self._check(self.lib.cvae_preprocess_u8(self.h, B, self._u8(frames_u8, "frames"), _ptr(x), _stream()))
 
     def diff_grey(self, B, recon_one, recon_zero, diff):
         self._check(self.lib.cvae_diff_grey(self.h, B, _ptr(recon_one), _ptr(recon_zero), _ptr(diff), _stream()))
 
     # ---- the training set on the device (load_minerl_data, vae_utility.py:393-461; episodes.py) ----
+    @staticmethod
+    def _curate_sizes(offsets, preds, counts, first, sel):
+        """(n_traj, n_frames) of one chunk, after the size checks both selection calls share."""
+        n_traj, n_frames = offsets.numel() - 1, preds.numel()
+        assert sel.numel() >= n_frames and counts.numel() >= 3 * n_traj and first.numel() >= n_traj
+        return n_traj, n_frames
+
     def curate_select(self, offsets, preds, collect, total_images, running, counts, first, span, sel):
         """One chunk of whole trajectories: offsets (n_traj+1) int64, preds (n_frames) fp32, running (1) int64 in/out,
         counts (n_traj,3), first (n_traj), span (2), sel (>= n_frames) int64 — all device tensors (include/cvae.h)."""
-        n_traj = offsets.numel() - 1
-        n_frames = preds.numel()
-        assert sel.numel() >= n_frames and counts.numel() >= 3 * n_traj and first.numel() >= n_traj
+        n_traj, n_frames = self._curate_sizes(offsets, preds, counts, first, sel)
         self._check(self.lib.cvae_curate_select(self.h, n_traj, self._i64(offsets, "offsets"), n_frames, _ptr(preds),
                                                 int(collect), int(total_images), self._i64(running, "running"),
                                                 self._i64(counts, "counts"), self._i64(first, "first"),
@@ -328,24 +337,21 @@ class Handle:
                             ent_frame, ent_kind, ent_sel, sel):
         """curate_select with two entries per mid frame: running / first / span[0..1] count entries; sel_first (n_traj),
         span (3), ent_frame / ent_sel (>= 2 n_frames) int64, ent_kind (>= 2 n_frames) int32, sel (>= n_frames) int64."""
-        n_traj = offsets.numel() - 1
-        n_frames = preds.numel()
-        assert sel.numel() >= n_frames and counts.numel() >= 3 * n_traj and first.numel() >= n_traj and span.numel() >= 3
-        assert sel_first.numel() >= n_traj and min(ent_frame.numel(), ent_kind.numel(), ent_sel.numel()) >= 2 * n_frames
-        assert ent_kind.is_cuda and ent_kind.dtype == torch.int32 and ent_kind.is_contiguous()
+        n_traj, n_frames = self._curate_sizes(offsets, preds, counts, first, sel)
+        assert span.numel() >= 3 and sel_first.numel() >= n_traj
+        assert min(ent_frame.numel(), ent_kind.numel(), ent_sel.numel()) >= 2 * n_frames
         self._check(self.lib.cvae_curate_select_recon(
             self.h, n_traj, self._i64(offsets, "offsets"), n_frames, _ptr(preds), int(collect), int(total_images),
             self._i64(running, "running"), self._i64(counts, "counts"), self._i64(first, "first"),
             self._i64(sel_first, "sel_first"), self._i64(span, "span"), self._i64(ent_frame, "ent_frame"),
-            ent_kind.data_ptr(), self._i64(ent_sel, "ent_sel"), self._i64(sel, "sel"), _stream()))
+            self._i32(ent_kind, "ent_kind"), self._i64(ent_sel, "ent_sel"), self._i64(sel, "sel"), _stream()))
 
     def recon_zcat(self, n_entries, ent_sel, ent_kind, mu, sel_preds, zcat):
         """zcat[e] = (mu[ent_sel[e]], ent_kind[e] == 0 ? sel_preds[ent_sel[e]] : 0) for a run of n_entries entries."""
         assert ent_sel.numel() >= n_entries and ent_kind.numel() >= n_entries and zcat.numel() >= 33 * n_entries
-        assert ent_kind.is_cuda and ent_kind.dtype == torch.int32 and ent_kind.is_contiguous()
         n_sel = sel_preds.numel()
         assert mu.numel() >= 32 * n_sel
-        self._check(self.lib.cvae_recon_zcat(self.h, n_entries, self._i64(ent_sel, "ent_sel"), ent_kind.data_ptr(), _ptr(mu),
+        self._check(self.lib.cvae_recon_zcat(self.h, n_entries, self._i64(ent_sel, "ent_sel"), self._i32(ent_kind, "ent_kind"), _ptr(mu),
                                              _ptr(sel_preds), n_sel, _ptr(zcat), _stream()))
 
     def gather_f32(self, B, frames, preds, idx, x, pred):
@@ -357,20 +363,6 @@ class Handle:
                                              self._i64(idx, "idx"), _ptr(x), _ptr(pred), _stream()))
 
     # ---- segmentation evaluation (eval_textured_frames, vae_utility.py:162-212) ----
-    @staticmethod
-    def _u8(t, what):
-        if t is None:
-            return None
-        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous(), f"{what}: need a contiguous uint8 device tensor"
-        return t.data_ptr()
-
-    @staticmethod
-    def _i64(t, what):
-        if t is None:
-            return None
-        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous(), f"{what}: need a contiguous int64 device tensor"
-        return t.data_ptr()
-
     def diff_normalize(self, B, diff, mean_max, diff_factor, thr, gt, diff_u8, mask=None, counts=None, hist=None):
         """uint8 masks of the set-wide normalisation; counts (B,3) (tp, fn, fp); hist (2,256) is ADDED to."""
         self._check(self.lib.cvae_diff_normalize(self.h, B, _ptr(diff), float(mean_max), float(diff_factor), int(thr),
@@ -406,20 +398,19 @@ class Handle:
         arr = (Panel * n)()
         for i, (kind, t, stride) in enumerate(panels):
             dtype, numel = need[kind]
-            assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), f"panel {i}: need a contiguous {dtype} device tensor"
+            ptr = _dev_ptr(t, dtype, f"panel {i}")
             assert stride >= 0 and t.numel() >= (B - 1) * stride + numel, f"panel {i}: {t.numel()} elements for {B} pictures at stride {stride}"
-            arr[i] = Panel(kind, 0, t.data_ptr(), stride)
+            arr[i] = Panel(kind, 0, ptr, stride)
         assert out.numel() == B * (row_offset + w) * n * w * 3, "out: wrong size"
         if overlay is not None:
             assert overlay.numel() == (row_offset + w) * n * w, "overlay: wrong size"
         L = lh = lw = 0
         if atlas is not None:
             L, lh, lw = atlas.shape
-            assert label_idx is not None and label_idx.is_cuda and label_idx.dtype == torch.int32 and label_idx.is_contiguous() \
-                and label_idx.numel() >= B, "label_idx: need a contiguous int32 device tensor of B entries"
+            assert label_idx is not None and label_idx.numel() >= B, "label_idx: need a contiguous int32 device tensor of B entries"
         self._check(self.lib.cvae_compose_frames(self.h, B, n, arr, int(row_offset), COMPOSE_CLAMP if clamp else 0,
                                                  self._u8(overlay, "overlay"), self._u8(atlas, "atlas"), L, lh, lw,
-                                                 None if atlas is None else label_idx.data_ptr(), int(label_xy[0]), int(label_xy[1]),
+                                                 None if atlas is None else self._i32(label_idx, "label_idx"), int(label_xy[0]), int(label_xy[1]),
                                                  self._u8(out, "out"), _stream()))
 
     def inject_zcat(self, n_images, n_rewards, mu, rewards, zcat):

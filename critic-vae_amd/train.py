@@ -282,8 +282,6 @@ class FusedTrainer:
         x = torch.empty(B, P.ch, self.vae.width, self.vae.width, device=dev)
         pred = torch.empty(B, 1, device=dev)
         scal = None
-        # a ReconDataset holds fp32 CHW entries: the batch is a bit copy (cvae_gather_f32)
-        gather = self.h.gather_f32 if dataset.frames.dtype == torch.float32 else self.h.preprocess_u8_gather
         for _ in range(epochs):
             idx = np.arange(n)
             if shuffle:
@@ -291,7 +289,7 @@ class FusedTrainer:
             d_idx = torch.from_numpy(idx).to(dev)          # indices of arange(n): in [0, n) by construction
             for b in range(0, n, B):
                 nb = min(B, n - b)
-                gather(nb, dataset.frames, dataset.preds, d_idx[b:b + nb], x[:nb], pred[:nb])
+                dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], pred[:nb])
                 eps = torch.randn(nb, P.latent_dim, device=dev, generator=generator)
                 scal = self.step(x[:nb], pred[:nb], eps)
         return scal
@@ -403,11 +401,9 @@ def main(argv=None):
         args.critic = "random"
     if args.episodes is not None:
         return _train_episodes(args)
-    if not torch.cuda.is_available():
-        raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
+    device = _device()
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
-    device = torch.device("cuda:0")
     vae = VariationalAutoencoder(max_batch=args.batch, seed=args.seed).to(device)
     dset = synthetic_dataset(args.synthetic)
     if args.critic == "random":
@@ -426,6 +422,34 @@ def main(argv=None):
     return hist
 
 
+def _device():
+    """cuda:0, or the exit every mode takes without a GPU."""
+    if not torch.cuda.is_available():
+        raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
+    return torch.device("cuda:0")
+
+
+def _fit_and_save(args, vae, ds, second):
+    """What -train --episodes and -second share once the dataset is on the device: seeds, FusedTrainer.fit_device, the rate
+    line, save_networks.  Nothing before it draws from the global generators (the networks are built from args.seed)."""
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    trainer = FusedTrainer(vae)
+    gen = torch.Generator(device=vae.theta.device)
+    gen.manual_seed(args.seed)
+    t0 = time.time()
+    scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    s = scal.cpu().numpy()
+    print(f"{args.epochs * len(ds) / dt:.1f} images/s over {args.epochs} epoch(s); last loss {s[0]:.6f} "
+          f"(recon {s[1]:.6f}, kld {s[2]:.6f})")
+    if args.save:
+        enc, dec = save_networks(vae, args.save, second=second)
+        print(f"saved {enc} and {dec}")
+    return ds
+
+
 def _load_critic(spec, handle, seed, device):
     from .critic import Critic
     critic = Critic(handle=handle).to(device)
@@ -439,11 +463,7 @@ def _train_episodes(args):
     """-train on recorded trajectories: curate (episodes.py) -> FusedTrainer.fit_device -> save_networks."""
     from .episodes import curate, load_episodes
     episodes = load_episodes(args.episodes)
-    if not torch.cuda.is_available():
-        raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
-    torch.manual_seed(args.seed)
-    np.random.seed(args.seed)
-    device = torch.device("cuda:0")
+    device = _device()
     vae = VariationalAutoencoder(max_batch=args.batch, seed=args.seed).to(device)
     critic = _load_critic(args.critic, vae.handle, args.seed, device)
     t0 = time.time()
@@ -452,29 +472,14 @@ def _train_episodes(args):
     print(f"curated {len(ds)} frames in {time.time() - t0:.2f} s")
     if len(ds) == 0:
         raise SystemExit("the curated dataset is empty: no frame of the trajectories falls in a critic-value bin")
-    trainer = FusedTrainer(vae)
-    gen = torch.Generator(device=device)
-    gen.manual_seed(args.seed)
-    t0 = time.time()
-    scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen)
-    torch.cuda.synchronize()
-    dt = time.time() - t0
-    s = scal.cpu().numpy()
-    print(f"{args.epochs * len(ds) / dt:.1f} images/s over {args.epochs} epoch(s); last loss {s[0]:.6f} "
-          f"(recon {s[1]:.6f}, kld {s[2]:.6f})")
-    if args.save:
-        enc, dec = save_networks(vae, args.save)
-        print(f"saved {enc} and {dec}")
-    return ds
+    return _fit_and_save(args, vae, ds, second=False)
 
 
 def _build_recon_dataset(args):
     """-dataset (vae.py:130-140): load_networks -> curate_recon (episodes.py) -> ReconDataset.save."""
     from .episodes import curate_recon, load_episodes
     episodes = load_episodes(args.episodes)
-    if not torch.cuda.is_available():
-        raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
-    device = torch.device("cuda:0")
+    device = _device()
     vae = load_networks(VariationalAutoencoder(max_batch=max(args.batch, 256), seed=args.seed).to(device), args.networks)
     critic = _load_critic(args.critic, vae.handle, args.seed, device)
     t0 = time.time()
@@ -494,29 +499,12 @@ def _build_recon_dataset(args):
 def _train_second(args):
     """-second (vae.py:142-153): a fresh VAE, FusedTrainer.fit_device on the recon dataset, saved as vae2_*.pt."""
     from .episodes import ReconDataset
-    if not torch.cuda.is_available():
-        raise SystemExit("critic-vae_amd needs an MI355X: the HIP library has no CPU fallback")
-    torch.manual_seed(args.seed)
-    np.random.seed(args.seed)
-    device = torch.device("cuda:0")
+    device = _device()
     ds = ReconDataset.load(args.dataset, device)
     if len(ds) == 0:
         raise SystemExit("the recon dataset is empty")
     vae = VariationalAutoencoder(max_batch=args.batch, seed=args.seed).to(device)
-    trainer = FusedTrainer(vae)
-    gen = torch.Generator(device=device)
-    gen.manual_seed(args.seed)
-    t0 = time.time()
-    scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen)
-    torch.cuda.synchronize()
-    dt = time.time() - t0
-    s = scal.cpu().numpy()
-    print(f"{args.epochs * len(ds) / dt:.1f} images/s over {args.epochs} epoch(s); last loss {s[0]:.6f} "
-          f"(recon {s[1]:.6f}, kld {s[2]:.6f})")
-    if args.save:
-        enc, dec = save_networks(vae, args.save, second=True)
-        print(f"saved {enc} and {dec}")
-    return ds
+    return _fit_and_save(args, vae, ds, second=True)
 
 
 if __name__ == "__main__":

@@ -14,6 +14,7 @@ from critic_vae_amd.critic import Critic
 from critic_vae_amd.lib import Handle
 from critic_vae_amd.nets import VariationalAutoencoder
 from critic_vae_amd.train import FusedTrainer
+from recon_tools import first_vae_params
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -144,12 +145,24 @@ def test_curate_matches_the_reference(fx, pool, critic_sd, chunk_frames):
     np.testing.assert_array_equal(ds.preds.cpu().numpy()[:, 0], hip[content])
 
 
-def test_curate_empty_and_zero_total(pool, critic_sd):
+@pytest.mark.parametrize("kind", ["plain", "recon"])
+def test_curate_empty_and_zero_total(pool, critic_sd, kind):
     critic = real_critic(critic_sd)
+    if kind == "plain":
+        def walk(eps, total):
+            return E.curate(eps, critic, total_images=total, log=lambda s: None)
+    else:
+        vae = VariationalAutoencoder(max_batch=8, seed=7).to(DEV)
+        vae.load_reference_params(first_vae_params(7))
+
+        def walk(eps, total):
+            return E.curate_recon(eps, critic, vae, total_images=total, log=lambda s: None)
     eps = [("a", pool[:0]), ("b", pool[:5])]
-    assert len(E.curate(eps, critic, total_images=0, log=lambda s: None)) == 0
-    ds = E.curate([("a", pool[:0])], critic, total_images=10, log=lambda s: None)
+    assert len(walk(eps, 0)) == 0
+    ds = walk([("a", pool[:0])], 10)
     assert len(ds) == 0 and ds.sizes == [0]
+    if kind == "recon":
+        assert ds.source.shape == (0, 3) and ds.stats == {"walked": 0, "encoded": 0, "decoded": 0}
 
 
 # ---- 3. gathers ----
