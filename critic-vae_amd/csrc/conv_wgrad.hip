@@ -22,11 +22,74 @@ struct WgradArgs {
     int tilesPerSplit;
 };
 
+// One tile row of an interior image row (2 <= gy <= H-3) without padding tests.  No tap leaves the image through the top or
+// the bottom there, and it leaves through the sides only on the row's first pixel pair (gx = 0: the taps s = 0 read the
+// padding twice) and on its last (gx = H-2: the taps s = 4), so which MFMAs wgrad_body's tests skip is known when the kernel
+// is compiled and the whole row is one straight line (77% of the k-steps at 32x32 and 56% at 16x16 carry all their MFMAs).
+// LEAD: the tile holds the image row's first pair (else, at two x-tiles per row, its last).  [J0, J1): the accumulators of
+// this pass, the six taps of every row (0, 6) or tap 24 on the rows this wave owns it (6, 7).
+// Software pipeline, written out: the operands of step i+1 are requested before the MFMAs of step i (two register sets) and
+// the order is pinned with sched_group_barrier, one read behind each MFMA.  Inside the tests the compiler issues
+// read -> s_waitcnt lgkmcnt(0) -> MFMA for every MFMA, and two waves per SIMD do not hide an LDS round trip per 64-cycle MFMA.
+// Every accumulator receives the MFMAs of the tested form, in the same order: results are bitwise those of the tested form.
+template <int H, int W, int J0, int J1, bool LEAD>
+__device__ __forceinline__ void wgrad_interior_row(f32x16 (&acc)[7], float& bsum, const float* inrow, const float* drow) {
+    using T = Tile<H>;
+    constexpr int CS = 32, NK = T::TW / 2;
+    constexpr bool ONE = T::TILES_X == 1;
+    auto live = [](int i, int j) {                       // does step i carry MFMA j
+        const int s = j == 6 ? 4 : (4 * j + W) % 5;
+        if (j < J0 || j >= J1) return false;
+        if (i == 0 && (ONE || LEAD) && s == 0) return false;
+        if (i == NK - 1 && (ONE || !LEAD) && s == 4) return false;
+        return true;
+    };
+    float af[2][7], bf[2];
+    auto ld = [&](int i, int b) {
+        bf[b] = drow[(2 * i) * 32];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const int tap = j == 6 ? 24 : 4 * j + W, r = tap / 5, s = tap % 5;
+            if (live(i, j)) af[b][j] = inrow[(r * T::HTW + s + 2 * i) * CS];
+        }
+    };
+    ld(0, 0);
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+        if (live(0, j)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+        if (i + 1 < NK) ld(i + 1, (i + 1) & 1);
+        if (W == 0 && J0 == 0) bsum += bf[i & 1];          // column sums of dout = the conv's bias gradient, for free
+#pragma unroll
+        for (int j = 0; j < 7; ++j)
+            if (live(i, j)) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i & 1][j], bf[i & 1], acc[j], 0, 0, 0);
+        // the next step's reads (its live MFMAs + 1): one behind each MFMA of this step, the rest behind the last
+        int reads = 1;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) reads += i + 1 < NK && live(i + 1, j);
+        if (i + 1 >= NK) reads = 0;
+#pragma unroll
+        for (int j = 0; j < 7; ++j)
+            if (live(i, j)) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                if (reads > 0) { __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); --reads; }
+            }
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (q < reads) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_barrier(0);      // a step's reads stay in their step: hoisted further they cost registers (spills)
+    }
+}
+
 // One wave's share of a staged tile: taps W, W+4, .., W+20 over every pixel, plus tap 24 over rows
 // rho == W (mod 4) (the 25th tap is split over the 4 waves so all MFMA pipes carry 6.25 taps).
 // MFMAs whose two input pixels both fall into the zero padding are skipped (wave-uniform test):
 // at 8x8 / 4x4 images that is 23% / 44% of the work; the interleaved tap assignment keeps the
-// four waves' remaining work balanced.
+// four waves' remaining work balanced.  At H >= 16 interior image rows go through wgrad_interior_row,
+// which skips the same MFMAs without testing; the two top and two bottom rows keep the tested form,
+// and so does every row at 8x8 (4 k-steps per row: the untested rows measured 168.5 against 164.9 us).
 template <int H, int W>
 __device__ __forceinline__ void wgrad_body(f32x16 (&acc)[7], float& bsum, const float* lds_in, const float* lds_d, int li,
                                            int lh, int ty0, int tx0) {
@@ -37,9 +100,17 @@ __device__ __forceinline__ void wgrad_body(f32x16 (&acc)[7], float& bsum, const 
         const float* inrow = lds_in + ((img * T::HTH + ty) * T::HTW + lh) * CS + li;
         const float* drow = lds_d + (rho * T::TW + lh) * 32 + li;
         const bool extra = (rho & 3) == W && gy + 2 < H;
+        // if-then only (the tested loop runs 0 steps on an interior row): an if / else around the accumulators is structurised
+        // into guarded blocks that carry a second copy of all seven and spill the tile staging registers
+        const bool inner = H >= 16 && gy >= 2 && gy + 3 <= H, lead = T::TILES_X == 1 || tx0 == 0;
+        if (inner && lead) wgrad_interior_row<H, W, 0, 6, true>(acc, bsum, inrow, drow);
+        if (inner && !lead) wgrad_interior_row<H, W, 0, 6, false>(acc, bsum, inrow, drow);
+        if (inner && extra && lead) wgrad_interior_row<H, W, 6, 7, true>(acc, bsum, inrow, drow);
+        if (inner && extra && !lead) wgrad_interior_row<H, W, 6, 7, false>(acc, bsum, inrow, drow);
+        const int nk = inner ? 0 : T::TW / 2;
         constexpr int KKU = T::TW / 2 < 8 ? T::TW / 2 : 8;      // full unroll of 16 k-steps (H >= 32) spills registers
 #pragma unroll KKU
-        for (int kk = 0; kk < T::TW / 2; ++kk) {
+        for (int kk = 0; kk < nk; ++kk) {
             const float bv = drow[(2 * kk) * 32];
             const int gx = tx0 + 2 * kk;                     // this k-step covers pixels gx, gx+1
             if (W == 0) bsum += bv;          // column sums of dout = the conv's bias gradient, for free
@@ -68,6 +139,7 @@ __global__ __launch_bounds__(256, 2) void conv5x5_wgrad_kernel(WgradArgs a) {
     const int li = lane & 31, lh = lane >> 5;
     const int split = blockIdx.x, ci0 = blockIdx.y * 32, n0 = blockIdx.z * 32;
     constexpr int HS = UP ? H / 2 : H;
+    constexpr bool LAUNDER = H == 4;      // see fetch
 
     f32x16 acc[7];
     float bsum = 0.f;
@@ -83,6 +155,10 @@ __global__ __launch_bounds__(256, 2) void conv5x5_wgrad_kernel(WgradArgs a) {
     constexpr int IQ = (T::HP * 8 + 255) / 256;
     f32x4 rin[IQ], rdo[4];
     auto fetch = [&](int mt) {
+        // H = 4 (9 staging loads of 8 half-empty images): the addresses are worked out again for every tile (`tid` made
+        // opaque); hoisted out of the tile loop they stay live across the MFMA loop and 38 registers spill (D0: 48 -> 42 us)
+        int tid = threadIdx.x;
+        if (LAUNDER) asm volatile("" : "+v"(tid));
         const int tileInImg = mt % T::TILES_PER_IMG;
         const int img0 = (mt / T::TILES_PER_IMG) * T::IMGS;
         const int ty0 = (tileInImg / T::TILES_X) * T::TH, tx0 = (tileInImg % T::TILES_X) * T::TW;
