@@ -848,9 +848,10 @@ int launch_e1_wgrad(int width, int B, const float* x, const float* dy, float* dw
     cvae_probe_end(st);
     CVAE_CHECK_LAUNCH();
     // slab row = [75 x 32 weights | 32 zeros (K pad) | 32 bias partials]: in the flat buffer enc0.b sits at
-    // enc0.w + 2432 (2400 weights padded to 64 floats), so ONE column reduction fills both
+    // enc0.w + 2432 (2400 weights padded to 64 floats), so ONE column reduction fills both; the 32 columns between them are the
+    // caller's alignment padding, which the backward leaves as it was (include/cvae.h)
     if (dbias == dw + 2432)
-        return launch_col_reduce(ws, S, 2464, 3072, dw, ws + (size_t)S * 3072, st);
+        return launch_col_reduce(ws, S, 2464, 3072, dw, ws + (size_t)S * 3072, st, 2400);
     int rc = launch_col_reduce(ws, S, 2400, 3072, dw, ws + (size_t)S * 3072, st);
     if (rc || !dbias) return rc;
     return launch_col_reduce(ws + 2432, S, 32, 3072, dbias, ws + (size_t)S * 3072, st);

@@ -13,6 +13,13 @@
  *   - Process-wide state is limited to two caches that never change results: a THREAD-LOCAL error string
  *     (cvae_last_error() reports the calling thread's last failure) and a per-device compute-unit count queried
  *     once (it sizes persistent grids).  Everything else lives in the handle; distinct handles are independent.
+ *   - What the workspace, a scratch buffer or an output holds ON ENTRY does not matter: they may be uninitialised memory (NaNs,
+ *     huge values, the leavings of a call at another batch size), and are never cleared by the caller.  Every slot a kernel reads
+ *     (split-K slabs, BatchNorm and reduction partials, the MS-SSIM partials and its arrival ticket, packed weights) is written
+ *     earlier in the same call.  What must be kept is the workspace BETWEEN a cvae_forward and the cvae_loss and cvae_backward
+ *     that belong to it (it carries the saved activations; the stages of one staged step likewise).  Every output is fully
+ *     written for the `batch` rows of the call: mu, logvar, recon, the first 13 scalars, d_recon, d_mu, d_logvar and every
+ *     tensor of `grads`; only the alignment padding between the tensors of `grads` is the caller's (see cvae_backward_phases).
  *   - All work is enqueued on the caller's hipStream_t (passed as void*).
  *   - Return: 0 = OK, <0 = library error (cvae_last_error()), >0 = hipError_t passthrough.
  *   - Layouts: frames x / recon / d_recon are NCHW (B,3,W,W) exactly as the reference holds

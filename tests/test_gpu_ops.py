@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from critic_vae_amd import lib as cvlib
 from critic_vae_amd import synth
 from oracle import cvae_oracle as orc
+from ws_tools import ALL_ONES, poison
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -135,7 +136,8 @@ def test_conv_fwd(W, B, layer):
         ref = torch.tanh(ref)
     xin = dev(x) if layer == 0 else nhwc(x)
     out = torch.full((B * h * h * cout,), float("nan"), device="cuda")
-    part = torch.zeros(max(H.op_bn_partial_floats(min(layer, 3), B), 1), device="cuda") if layer < 4 else None
+    # the BatchNorm partials come back fully written: uninitialised memory, filled with NaNs (ws_tools.ALL_ONES)
+    part = poison(torch.empty(max(H.op_bn_partial_floats(min(layer, 3), B), 1), device="cuda"), ALL_ONES) if layer < 4 else None
     H.op_conv_fwd(layer, B, xin, wnat(w), dev(b), out, part, torch.empty(H.op_scratch_floats(B), device="cuda"))
     torch.cuda.synchronize()
     got = out.view(B, cout, h, h).cpu() if layer == 8 else to_nchw(out, B, h, cout)
@@ -188,7 +190,7 @@ def test_bn_pool_act_fwd_bwd(W, layer, B, ties):
         beta[0], beta[5], beta[9] = 0.3, 0.5, 0.2          # ReLU lets these channels through
     # conv on the GPU provides y and the BatchNorm partials; the reference starts from that same fp32 y
     y = torch.empty(B * h * h * C, device="cuda")
-    part = torch.zeros(H.op_bn_partial_floats(layer, B), device="cuda")
+    part = poison(torch.empty(H.op_bn_partial_floats(layer, B), device="cuda"), ALL_ONES)
     H.op_conv_fwd(layer, B, dev(x) if layer == 0 else nhwc(x), wnat(w), dev(b), y, part)
     y_ref = f64(to_nchw(y, B, h, C)).requires_grad_(True)
     g_ref, b_ref = f64(gamma).requires_grad_(True), f64(beta).requires_grad_(True)
