@@ -274,8 +274,9 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
 #define G_(idx) (grads + h->params[(idx)].offset)
 #define RC(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
-// cvae_config.precision: 1 = bf16-MFMA kernels for every pass of E2..E4 / D0..D3 (conv_bf16.hip); 2 = the same
-// forward / input-gradient kernels with 3-way split operands (exact fp32 products, 9 MFMAs each), fp32 wgrad
+// cvae_config.precision: 1 = bf16-MFMA kernels for every pass of E2..E4 / D0..D3 (conv_bf16.hip); 2 / 3 = E2..E4 / D0 on the same
+// forward / input-gradient kernels with 3-way split operands (exact fp32 products, 9 / the 6 leading MFMAs each) and their weight
+// gradients on the split-operand bf16-MFMA kernel (conv_wgrad_split.hip)
 static bool use_bf16(cvae_handle h, int layer) {
     if (h->cfg.precision >= 2 && layer > 4) return false;     // D1..D3: the fp32 phase-collapsed kernels beat nine bf16 MFMAs per block
     return h->cfg.precision != 0 && conv_bf16_supported(layer, h->cfg.width);
@@ -930,6 +931,17 @@ int cvae_probe_read(cvae_handle h, int32_t id, float* ms_host, int32_t cap) {
 }
 
 // ------------------------------ per-op entry points ------------------------------
+// Layers 1..4 follow the handle's precision in the fp32-emulation modes (2, 3): the kernels the step runs there, on fp32 tensors.
+// Their scratch is [packed 3-split weights (the step's wpack block, only the layer's own slots written) | everything else].
+static bool op_emulated(cvae_handle h, int layer) { return h->cfg.precision >= 2 && layer >= 1 && layer <= 4 && use_bf16(h, layer); }
+static int64_t op_pack_floats(cvae_handle h) { return h->cfg.precision >= 2 ? align_up(conv_bf16_pack_floats(3), 64) : 0; }
+static int op_pack_layer(cvae_handle h, int layer, const float* wt, void* scratch, hipStream_t st) {
+    if (!scratch) { cvae_set_error("per-op conv, layer %d: the fp32-emulation modes pack the weights into scratch (null)", layer); return CVAE_EINVAL; }
+    const float* wl[4] = {nullptr, nullptr, nullptr, nullptr};          // the packer skips the layers it is not given
+    wl[layer - 1] = wt;
+    return launch_pack_w_bf16(wl, (float*)scratch, bf16_splits(h), st);
+}
+
 int cvae_op_conv_fwd(cvae_handle h, int32_t layer, int32_t B, const float* in, const float* wt, const float* bias,
                      float* out, float* bn_partials, void* scratch, void* stream) {
     const int W = h->cfg.width;
@@ -939,6 +951,10 @@ int cvae_op_conv_fwd(cvae_handle h, int32_t layer, int32_t B, const float* in, c
         float* wc = (float*)scratch;
         RC(launch_collapse_w(layer, wt, wc, (hipStream_t)stream));
         return launch_conv_up_fwd(layer, W, B, in, wc, bias, out, wc + conv_up_wc_floats(layer), (hipStream_t)stream);
+    }
+    if (op_emulated(h, layer)) {
+        RC(op_pack_layer(h, layer, wt, scratch, (hipStream_t)stream));
+        return launch_conv_fwd_bf16(layer, W, bf16_mode(h), B, in, (float*)scratch, bias, out, bn_partials, (float*)scratch + op_pack_floats(h), (hipStream_t)stream, nullptr);
     }
     return launch_conv_fwd(layer, W, B, in, wt, bias, out, bn_partials, (float*)scratch, (hipStream_t)stream);
 }
@@ -950,12 +966,16 @@ int cvae_op_conv_dgrad(cvae_handle h, int32_t layer, int32_t B, const float* dou
         RC(launch_collapse_w(layer, wt, wc, (hipStream_t)stream));
         return launch_conv_up_dgrad(layer, h->cfg.width, B, dout, wc, mask_src, din, wc + conv_up_wc_floats(layer), (hipStream_t)stream);
     }
+    if (op_emulated(h, layer)) {
+        RC(op_pack_layer(h, layer, wt, scratch, (hipStream_t)stream));
+        return launch_conv_dgrad_bf16(layer, h->cfg.width, bf16_mode(h), B, dout, (float*)scratch, din, (float*)scratch + op_pack_floats(h), (hipStream_t)stream);
+    }
     return launch_conv_dgrad(layer, h->cfg.width, B, dout, wt, mask_src, din, (float*)scratch, (hipStream_t)stream);
 }
 
 int64_t cvae_op_scratch_floats(cvae_handle h, int32_t B) {
     const WsLayout w = carve(h, B);
-    return w.total - w.scratch;
+    return w.total - w.scratch + op_pack_floats(h);
 }
 
 int cvae_op_conv_wgrad(cvae_handle h, int32_t layer, int32_t B, const float* in, const float* dout, float* dw,
@@ -965,6 +985,10 @@ int cvae_op_conv_wgrad(cvae_handle h, int32_t layer, int32_t B, const float* in,
     float* sc = (float*)scratch;
     if (layer == 0) return launch_e1_wgrad(W, B, in, dout, dw, dbias, sc, st);
     if (layer >= 5) return launch_conv_up_wgrad(layer, W, B, in, dout, dw, dbias, sc, st);
+    if (op_emulated(h, layer)) {
+        if (!sc) { cvae_set_error("per-op conv_wgrad, layer %d: null scratch", layer); return CVAE_EINVAL; }
+        return conv_wgrad(h, layer, B, in, dout, dw, dbias, sc, st);
+    }
     return launch_conv_wgrad(layer, W, B, in, dout, dw, dbias, sc, st);
 }
 

@@ -176,7 +176,7 @@ class Handle:
         fp32 tensors in HBM; BASELINE.json configs 3-5).
         "bf16x9": fp32 emulation — forward / input-gradient convs on the bf16 MFMA with both operands split
         exactly into three bf16 parts (nine exact partial products per fp32 product, fp32 accumulate);
-        weight gradients on the fp32 MFMA.  Meets the same 1e-4 parity bar as "f32".
+        weight gradients of E2..E4 / D0 on the bf16 MFMA with the same exact splits.  Meets the same 1e-4 parity bar as "f32".
         "bf16x6": as "bf16x9" with the six leading partial products (drops <= 3*2^-24 of each product)."""
         self.lib = load()
         if precision not in self.PRECISIONS:
@@ -431,6 +431,7 @@ class Handle:
         return [buf[i] for i in range(n)]
 
     # ---- per-op entry points (tests, roofline probe) ----
+    # "bf16x9" / "bf16x6" handles: the conv ops of layers 1..4 run the step's split-operand kernels and need `scratch`
     def op_scratch_floats(self, B):
         return self.lib.cvae_op_scratch_floats(self.h, B)
 

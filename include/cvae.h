@@ -445,6 +445,12 @@ int cvae_probe_read(cvae_handle h, int32_t id, float* ms_host, int32_t cap);
  * encoder conv blocks E1..E4 (vae_nets.py:69,74,79,84), 4..8 = decoder convs D0..D4
  * (vae_nets.py:117,121,125,129,133).  Activations are NHWC except x/recon (NCHW); decoder
  * layers 5..8 read the stored (pre-Upsample) tensor.  `scratch` needs cvae_op_scratch_floats().
+ * On a handle of the fp32-emulation modes (precision 2, 3) the conv ops of layers 1..4 run the kernels
+ * the step runs there: forward and input gradient on the bf16 MFMA with 3-way split operands (the
+ * fp32 weight is packed into `scratch` first), weight gradient on the split-operand kernel.  All
+ * tensors stay fp32; cvae_op_scratch_floats() includes the packed copy, and a null `scratch` on
+ * these paths is CVAE_EINVAL.  Every other layer of these handles, and every layer of precision 0
+ * and 1, runs the fp32 kernels.
  * ---------------------------------------------------------------------------------------- */
 int64_t cvae_op_scratch_floats(cvae_handle h, int32_t batch);
 int64_t cvae_op_bn_partial_floats(cvae_handle h, int32_t layer, int32_t batch);

@@ -256,9 +256,17 @@ def _empty(n, dtype=torch.float32):
 @op_shapes
 def test_conv_ops_do_not_depend_on_scratch_partials_or_outputs(W, B):
     """op_conv_fwd (all nine layers, with the BatchNorm partials of the encoder layers), op_conv_dgrad (1..7), op_conv_wgrad (0..7) and
-    op_d4_bwd with the scratch, the partials and every output under the three fills."""
-    H = handle(W, B)
-    for layer in range(9):
+    op_d4_bwd with the scratch, the partials and every output under the three fills.  At B = 3 also layers 1..4 on handles of the two
+    fp32-emulation modes, whose ops run the step's split-operand kernels: the packed weights and D0's split-K slabs sit in the scratch."""
+    _conv_ops_under_fills(handle(W, B), W, B, range(9))
+    if B == 3:
+        for mode in ("bf16x9", "bf16x6"):
+            _conv_ops_under_fills(cvlib.Handle(W, B, precision=mode), W, B, range(1, 5))
+    _d4_bwd_under_fills(handle(W, B), W, B)
+
+
+def _conv_ops_under_fills(H, W, B, layers):
+    for layer in layers:
         cin, cout, h, up, hs = geom(layer, W)
         x, w, b = rnd(f"x{layer}", (B, cin, hs, hs)), rnd(f"w{layer}", (cout, cin, 5, 5), -0.1, 0.1), rnd(f"b{layer}", (cout,))
         dout = rnd(f"do{layer}", (B, cout, h, h))
@@ -276,6 +284,9 @@ def test_conv_ops_do_not_depend_on_scratch_partials_or_outputs(W, B):
             if layer >= 4:
                 bufs["dbias"] = _empty(cout)
             _under_fills(lambda: H.op_conv_wgrad(layer, B, xin, dn, bufs["dw"], bufs.get("dbias"), bufs["scratch"]), bufs)
+
+
+def _d4_bwd_under_fills(H, W, B):
     o3 = torch.relu(nhwc(rnd("pre8", (B, 32, W // 2, W // 2))))
     d_recon, recon, w8 = dev(rnd("dr8", (B, 3, W, W))), dev(rnd("rc8", (B, 3, W, W), -0.9, 0.9)), wnat(rnd("w8", (3, 32, 5, 5), -0.1, 0.1))
     bufs = {"dout": _empty(B * 3 * W * W), "d_o3": _empty(B * 32 * (W // 2) ** 2), "dw": _empty(2400), "db": _empty(3),
