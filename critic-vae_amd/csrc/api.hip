@@ -672,6 +672,25 @@ int cvae_adam_step(cvae_handle h, float* params, const float* grads, float* exp_
     return launch_adam(params, grads, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, grad_scale, (hipStream_t)stream);
 }
 
+int64_t cvae_guard_state_bytes(void) { return guard_state_bytes(); }
+int cvae_guard_init(cvae_handle h, void* state, int64_t applied, int64_t skipped, void* stream) {
+    if (!h || !state || applied < 0 || skipped < 0) { cvae_set_error("cvae_guard_init: bad handle, null state or negative counter"); return CVAE_EINVAL; }
+    return launch_guard_init(state, applied, skipped, (hipStream_t)stream);
+}
+int cvae_grad_stats(cvae_handle h, const float* grads, int64_t n, float grad_scale, float max_norm, int32_t skip_nonfinite,
+                    float lr, float beta1, float beta2, void* state, void* stream) {
+    if (!h || !grads || !state) { cvae_set_error("cvae_grad_stats: bad handle or null pointer"); return CVAE_EINVAL; }
+    if (n < 0 || n % 4 != 0) { cvae_set_error("cvae_grad_stats: n = %lld must be a non-negative multiple of 4", (long long)n); return CVAE_EINVAL; }
+    if (!(max_norm > 0.f)) { cvae_set_error("cvae_grad_stats: max_norm = %g must be positive (+inf = no clipping)", (double)max_norm); return CVAE_EINVAL; }
+    return launch_grad_stats(grads, n, grad_scale, max_norm, skip_nonfinite != 0, lr, beta1, beta2, state, (hipStream_t)stream);
+}
+int cvae_adam_step_guarded(cvae_handle h, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                           float eps, const void* state, void* stream) {
+    if (!h || !params || !grads || !exp_avg || !exp_avg_sq || !state) { cvae_set_error("cvae_adam_step_guarded: bad handle or null pointer"); return CVAE_EINVAL; }
+    if (n < 0 || n % 4 != 0) { cvae_set_error("cvae_adam_step_guarded: n = %lld must be a non-negative multiple of 4", (long long)n); return CVAE_EINVAL; }
+    return launch_adam_guarded(params, grads, exp_avg, exp_avg_sq, n, eps, state, (hipStream_t)stream);
+}
+
 int cvae_grads_to_bf16(cvae_handle h, const float* grads, void* out_bf16, int64_t n, void* stream) {
     if (h && n == 0) return 0;                       // empty range (its pointers may be null): nothing to do
     if (!h || !grads || !out_bf16 || n < 0) { cvae_set_error("cvae_grads_to_bf16: bad argument"); return CVAE_EINVAL; }

@@ -353,6 +353,12 @@ int launch_compose_frames(int width, int B, int n_panels, const struct cvae_pane
 int launch_grads_bf16(const float* src_f32, void* bf16_buf, float* dst_f32, int64_t n, hipStream_t st);   // src set: pack; else unpack
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1,
                 float b2, float eps, float gscale, hipStream_t st);
+// guarded step: the layout of `state` is cvae_guard_record + partials (include/cvae.h)
+int64_t guard_state_bytes();
+int launch_guard_init(void* state, int64_t applied, int64_t skipped, hipStream_t st);
+int launch_grad_stats(const float* g, int64_t n, float gscale, float max_norm, int skip_nonfinite, float lr, float b1, float b2,
+                      void* state, hipStream_t st);
+int launch_adam_guarded(float* p, const float* g, float* m, float* v, int64_t n, float eps, const void* state, hipStream_t st);
 int launch_zero(float* p, int64_t n, hipStream_t st);
 struct PadGaps { int64_t off[32]; int len[32]; int n; };
 int launch_zero_gaps(float* grads, const PadGaps& gaps, hipStream_t st);

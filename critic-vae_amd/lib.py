@@ -31,6 +31,14 @@ class CrfParams(C.Structure):
                 ("gamma", C.c_float), ("p_floor", C.c_float), ("iterations", C.c_int32)]
 
 
+class GuardRecord(C.Structure):
+    """cvae_guard_record (include/cvae.h): the decision record at offset 0 of a guard state."""
+    _fields_ = [("apply", C.c_int32), ("nonfinite", C.c_uint32), ("coef", C.c_float), ("norm", C.c_float),
+                ("norm64", C.c_double), ("t", C.c_int64), ("skipped", C.c_int64), ("step_size", C.c_float),
+                ("sqrt_bc2", C.c_float), ("gscale", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("ticket", C.c_uint32)]
+
+
 class Panel(C.Structure):
     """cvae_panel (include/cvae.h): one w x w panel of cvae_compose_frames."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("data", C.c_void_p), ("batch_stride", C.c_int64)]
@@ -79,6 +87,10 @@ _SIGS = {
     "cvae_backward_stage": (C.c_int, [_p, _i32] + [_p] * 12 + [_i32, _p]),
     "cvae_scale_loss_grads": (C.c_int, [_p, _i32] + [_p] * 8),
     "cvae_adam_step": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _f, _f, _f, _f, _f, _p]),
+    "cvae_guard_state_bytes": (_i64, []),
+    "cvae_guard_init": (C.c_int, [_p, _p, _i64, _i64, _p]),
+    "cvae_grad_stats": (C.c_int, [_p, _p, _i64, _f, _f, _i32, _f, _f, _f, _p, _p]),
+    "cvae_adam_step_guarded": (C.c_int, [_p, _p, _p, _p, _p, _i64, _f, _p, _p]),
     "cvae_grads_to_bf16": (C.c_int, [_p, _p, _p, _i64, _p]),
     "cvae_grads_from_bf16": (C.c_int, [_p, _p, _p, _i64, _p]),
     "cvae_critic_param_count": (_i32, []),
@@ -290,6 +302,36 @@ class Handle:
     def adam_step(self, params, grads, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0):
         self._check(self.lib.cvae_adam_step(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(),
                                             step, lr, b1, b2, eps, grad_scale, _stream()))
+
+    # ---- the guarded step (include/cvae.h): statistics of the reduced gradient -> decision record -> Adam that obeys it ----
+    def guard_state(self, device, applied=0, skipped=0):
+        """A fresh guard state on `device` (an int64 tensor: 8-byte aligned), counters as given."""
+        state = torch.empty((self.lib.cvae_guard_state_bytes() + 7) // 8, dtype=torch.int64, device=device)
+        self.guard_init(state, applied, skipped)
+        return state
+
+    def guard_init(self, state, applied=0, skipped=0):
+        self._check(self.lib.cvae_guard_init(self.h, self._guard_ptr(state), int(applied), int(skipped), _stream()))
+
+    def _guard_ptr(self, state):
+        ptr = self._i64(state, "guard state")
+        assert isinstance(state, int) or state.numel() * 8 >= self.lib.cvae_guard_state_bytes(), "guard state: too small"
+        return ptr
+
+    def grad_stats(self, grads, state, grad_scale=1.0, max_norm=float("inf"), skip_nonfinite=True, lr=0.0, b1=0.9, b2=0.999,
+                   n=None):
+        self._check(self.lib.cvae_grad_stats(self.h, _ptr(grads), grads.numel() if n is None else n, grad_scale, max_norm,
+                                             int(bool(skip_nonfinite)), lr, b1, b2, self._guard_ptr(state), _stream()))
+
+    def adam_step_guarded(self, params, grads, m, v, state, eps=1e-8, n=None):
+        self._check(self.lib.cvae_adam_step_guarded(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v),
+                                                    params.numel() if n is None else n, eps, self._guard_ptr(state), _stream()))
+
+    @staticmethod
+    def guard_record(state):
+        """The record of `state` on the host (one device -> host copy: a sync)."""
+        raw = state[:C.sizeof(GuardRecord) // 8].cpu().numpy().tobytes()
+        return GuardRecord.from_buffer_copy(raw)
 
     # ---- critic + input pipeline ----
     def critic_forward(self, B, x, critic_params, pred):

@@ -83,7 +83,7 @@ class FusedTrainer:
     """One training step = forward + loss + backward + all-reduce + Adam on flat buffers."""
 
     def __init__(self, vae, lr=P.lr, betas=P.adam_betas, eps=P.adam_eps, process_group=None, world_size=1,
-                 overlap=None, reduce_dtype=None, sync=True, global_stats=None):
+                 overlap=None, reduce_dtype=None, sync=True, global_stats=None, skip_nonfinite=False, max_grad_norm=None):
         """Construction with world_size > 1 is a COLLECTIVE (sync_replicas: five broadcasts from rank 0) unless
         sync=False.
         overlap: all-reduce the gradient in three buckets while backward still runs (default for
@@ -94,7 +94,16 @@ class FusedTrainer:
         global_stats: global-batch semantics across ranks (CVAE_DP_GLOBAL_STATS=1; default off): the step runs in stages
         (include/cvae.h) and all-reduces the fp64 BatchNorm and loss sums between them (SUM on process_group; no exchange at
         world_size 1), so N ranks at B images train the model one rank trains at N*B — BatchNorm over the global batch,
-        global MS-SSIM / KLD means.  The summed gradient is then the global-batch gradient: Adam's grad_scale is 1."""
+        global MS-SSIM / KLD means.  The summed gradient is then the global-batch gradient: Adam's grad_scale is 1.
+        skip_nonfinite / max_grad_norm: the guarded step (both off by default: the step then launches what it always did).
+        The step ends in cvae_grad_stats + cvae_adam_step_guarded instead of cvae_adam_step: one pass over the REDUCED
+        gradient (after the all-reduce and the bf16 unpack, with Adam's grad_scale) decides on the device — no host read —
+        whether the update is applied (skip_nonfinite: not when the gradient holds an Inf or a NaN, torch's GradScaler rule;
+        theta, m and v then keep their bits) and by how much it is scaled (max_grad_norm: torch's clip_grad_norm_ over the
+        whole flat gradient).  Every rank reads the same reduced gradient, so every rank decides alike and the replicas
+        stay bit-identical.  step_count keeps counting calls of step(); Adam's bias correction uses the device's count of
+        APPLIED steps.  A skipped step still ran forward in training mode: num_batches_tracked and the BatchNorm running
+        statistics are whatever forward wrote, as with a step torch's GradScaler skips."""
         self.vae = vae
         self.h = vae.handle
         if overlap is None:
@@ -110,6 +119,13 @@ class FusedTrainer:
         self.global_stats = bool(global_stats)
         self.buckets = [self.h.grad_bucket(ph) for ph in range(3)]
         self.lr, self.betas, self.eps = lr, betas, eps
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm {max_grad_norm!r}: a positive number (inf = no clipping) or None")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.guarded = self.skip_nonfinite or self.max_grad_norm is not None
+        self.guard = None                 # the device guard state, created by the first guarded step ...
+        self._guard_counts = (0, 0)       # ... from these (applied, skipped): what load_state_dict / sync_replicas left
         self.world_size, self.pg = world_size, process_group
         dev = vae.theta.device
         n = vae.theta.numel()
@@ -148,9 +164,13 @@ class FusedTrainer:
         dist = torch.distributed
         for t in (self.vae.theta.data, self.vae.bn_state, self.m, self.v):
             dist.broadcast(t, src=src, group=self.pg)
-        meta = torch.tensor([self.step_count, self.vae.num_batches_tracked], dtype=torch.int64, device=self.m.device)
+        counts = list(self._guard_read()) if self.guarded else []
+        meta = torch.tensor([self.step_count, self.vae.num_batches_tracked] + counts, dtype=torch.int64, device=self.m.device)
         dist.broadcast(meta, src=src, group=self.pg)
-        self.step_count, self.vae.num_batches_tracked = int(meta[0].item()), int(meta[1].item())
+        meta = meta.tolist()
+        self.step_count, self.vae.num_batches_tracked = meta[0], meta[1]
+        if self.guarded:
+            self._guard_write(meta[2], meta[3])
 
     def step(self, x, pred, eps):
         """x (B,3,w,w), pred (B,1), eps (B,32): contiguous fp32 device tensors."""
@@ -176,6 +196,8 @@ class FusedTrainer:
             self._reduce_all()
         self.step_count += 1
         v.num_batches_tracked += 1
+        if self.guarded:
+            return self._guarded_update(theta, 1.0 / self.world_size)
         h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
                     self.eps, grad_scale=1.0 / self.world_size)
         return self.scalars
@@ -242,9 +264,68 @@ class FusedTrainer:
             self._reduce_all()
         self.step_count += 1
         v.num_batches_tracked += 1
+        if self.guarded:
+            return self._guarded_update(theta, 1.0)
         h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
                     self.eps, grad_scale=1.0)        # the summed gradient already is the global-batch gradient
         return self.scalars
+
+    # ---- the guarded step ----
+    def _guarded_update(self, theta, grad_scale):
+        """Statistics of the reduced gradient -> decision record -> the Adam launch that obeys it; nothing comes back to the host."""
+        if self.guard is None:
+            self.guard = self.h.guard_state(self.m.device, *self._guard_counts)
+        self.h.grad_stats(self.grads, self.guard, grad_scale, float("inf") if self.max_grad_norm is None else self.max_grad_norm,
+                          self.skip_nonfinite, self.lr, self.betas[0], self.betas[1])
+        self.h.adam_step_guarded(theta, self.grads, self.m, self.v, self.guard, self.eps)
+        return self.scalars
+
+    def _guard_read(self):
+        """(applied, skipped) of a guarded trainer; one sync once the device state exists."""
+        if self.guard is None:
+            return self._guard_counts
+        rec = self.h.guard_record(self.guard)
+        return int(rec.t), int(rec.skipped)
+
+    def _guard_write(self, applied, skipped):
+        self._guard_counts = (int(applied), int(skipped))
+        if self.guard is not None:
+            self.h.guard_init(self.guard, *self._guard_counts)
+
+    def guard_stats(self):
+        """dict(applied, skipped, norm, coef) of a guarded trainer: the two counters, and the global gradient norm (after
+        grad_scale) and clip coefficient of the LAST step — norm 0 and coef 1, what cvae_guard_init writes, before the first step
+        and right after a load_state_dict / sync_replicas.  One device -> host copy, i.e. one sync; the trainer itself never calls it."""
+        if not self.guarded:
+            raise RuntimeError("guard_stats(): this trainer has no guard (skip_nonfinite / max_grad_norm)")
+        if self.guard is None:
+            return dict(applied=self._guard_counts[0], skipped=self._guard_counts[1], norm=0.0, coef=1.0)
+        rec = self.h.guard_record(self.guard)
+        return dict(applied=int(rec.t), skipped=int(rec.skipped), norm=float(rec.norm64), coef=float(rec.coef))
+
+    # ---- checkpoint ----
+    def state_dict(self):
+        """What a restart needs beside the two network files: the Adam moments (CPU copies), step_count, the applied / skipped
+        counters (an unguarded trainer applied every step) and the VAE's num_batches_tracked.  With the networks restored by
+        load_networks, a resumed run is exact at the step() level — the caller supplies eps; the generators that fit_* draw
+        shuffles and eps from are not saved."""
+        applied, skipped = self._guard_read() if self.guarded else (self.step_count, 0)
+        return {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(), "step_count": int(self.step_count),
+                "applied": applied, "skipped": skipped, "num_batches_tracked": int(self.vae.num_batches_tracked)}
+
+    def load_state_dict(self, state):
+        if state["m"].numel() != self.m.numel() or state["v"].numel() != self.v.numel():
+            raise ValueError(f"trainer state of {state['m'].numel()} parameters, this trainer has {self.m.numel()}")
+        applied, skipped, steps = int(state["applied"]), int(state["skipped"]), int(state["step_count"])
+        if not self.guarded and applied != steps:
+            raise ValueError(f"the state skipped {skipped} of {steps} steps: an unguarded trainer corrects Adam's bias by step_count "
+                             "and cannot continue it; construct the trainer with skip_nonfinite=True")
+        self.m.copy_(state["m"])
+        self.v.copy_(state["v"])
+        self.step_count = steps
+        self.vae.num_batches_tracked = int(state["num_batches_tracked"])
+        if self.guarded:
+            self._guard_write(applied, skipped)
 
     def fit_u8(self, frames_u8, critic, batch_size, epochs=1, generator=None, shuffle=True):
         """The `-train` loop (vae.py:40-58) over a host uint8 dataset (N,w,w,3), fused step + overlapped feeder:
@@ -353,6 +434,21 @@ def load_networks(vae, directory, device=None, second=False):
     return vae
 
 
+TRAINER_FILE = "trainer.pt"
+
+
+def save_trainer(trainer, path):
+    """FusedTrainer.state_dict() -> `path` (torch.save; the CLI writes DIR/trainer.pt beside the two network files)."""
+    torch.save(trainer.state_dict(), path)
+    return path
+
+
+def load_trainer(trainer, path):
+    """The counterpart of save_trainer; load the networks (load_networks) as well to continue a run."""
+    trainer.load_state_dict(torch.load(path, map_location="cpu"))
+    return trainer
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Critic-VAE -train on synthetic frames (vae.py:154-163)")
     ap.add_argument("--save", metavar="DIR", default=None,
@@ -384,7 +480,15 @@ def main(argv=None):
                     "trajectories stops (vae_parameters.py:19)")
     ap.add_argument("--collect", type=int, default=P.collect, help="frames per critic-value bin and trajectory "
                     "(vae_utility.py:404)")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="fused trainer (--episodes, -second): skip the update of a step "
+                    "whose gradient holds an Inf or a NaN (decided on the device)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="C", help="fused trainer: clip the gradient to global "
+                    "norm C (torch.nn.utils.clip_grad_norm_)")
+    ap.add_argument("--resume", metavar="DIR", default=None, help=f"fused trainer: continue from DIR's network files and {TRAINER_FILE} "
+                    "(what --save wrote)")
     args = ap.parse_args(argv)
+    if args.max_grad_norm is not None and not args.max_grad_norm > 0:
+        ap.error("--max-grad-norm needs a positive number")
     if args.train + args.dataset_mode + args.second != 1:
         ap.error("exactly one of -train, -dataset, -second (segment.py has -video [-thresh] [--second]); see SURVEY.md §8 for scope")
     if args.dataset_mode:
@@ -401,6 +505,9 @@ def main(argv=None):
         args.critic = "random"
     if args.episodes is not None:
         return _train_episodes(args)
+    if args.skip_nonfinite or args.max_grad_norm is not None or args.resume:
+        ap.error("--skip-nonfinite, --max-grad-norm and --resume belong to the fused trainer (-train --episodes, -second); "
+                 "the synthetic -train loop is the reference's own, with torch.optim.Adam")
     device = _device()
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
@@ -434,7 +541,11 @@ def _fit_and_save(args, vae, ds, second):
     line, save_networks.  Nothing before it draws from the global generators (the networks are built from args.seed)."""
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
-    trainer = FusedTrainer(vae)
+    trainer = FusedTrainer(vae, skip_nonfinite=args.skip_nonfinite, max_grad_norm=args.max_grad_norm)
+    if args.resume:
+        load_networks(vae, args.resume, second=second)
+        load_trainer(trainer, os.path.join(args.resume, TRAINER_FILE))
+        print(f"resumed from {args.resume} at step {trainer.step_count}")
     gen = torch.Generator(device=vae.theta.device)
     gen.manual_seed(args.seed)
     t0 = time.time()
@@ -447,6 +558,10 @@ def _fit_and_save(args, vae, ds, second):
     if args.save:
         enc, dec = save_networks(vae, args.save, second=second)
         print(f"saved {enc} and {dec}")
+        print(f"saved {save_trainer(trainer, os.path.join(args.save, TRAINER_FILE))}")
+    if trainer.guarded:
+        st = trainer.guard_stats()
+        print(f"guard: {st['applied']} steps applied, {st['skipped']} skipped")
     return ds
 
 

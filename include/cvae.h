@@ -211,6 +211,56 @@ int cvae_adam_step(cvae_handle h, float* params, const float* grads, float* exp_
                    float eps, float grad_scale, void* stream);
 
 /*
+ * Guarded optimizer step (opt-in): skip the update when the gradient is non-finite (torch's GradScaler rule) and / or clip it by
+ * its global norm (torch.nn.utils.clip_grad_norm_), decided ON THE DEVICE — no host read between backward and Adam.
+ *
+ * The caller owns one guard state of cvae_guard_state_bytes() bytes (8-byte aligned): a cvae_guard_record followed by the
+ * per-workgroup partials of the statistics pass.  cvae_guard_init writes it once (all zero, applied / skipped counters as
+ * given: 0, 0 for a new run, the saved values for a resumed one).  Each step is then
+ *     cvae_grad_stats (one pass over the reduced gradient, writes the record)  ->  cvae_adam_step_guarded (reads it),
+ * two launches where cvae_adam_step is one.
+ *
+ * cvae_grad_stats: n % 4 == 0.  norm = sqrt(sum (g_i * grad_scale)^2), accumulated in fp64 (elements near FLT_MAX give a
+ * finite norm64); nonfinite = some g_i has all exponent bits set (Inf or NaN) — taken from the bits, not from the sum.
+ * Per-workgroup partials are merged in a fixed order by the last workgroup to arrive: no floating-point atomics, the same
+ * buffer gives the same record bit for bit.  Then
+ *     apply = !(skip_nonfinite && nonfinite)
+ *     coef  = min(1, max_norm / (norm + 1e-6))        (max_norm = +inf: no clipping, coef = 1)
+ *     apply ? ++t : ++skipped
+ *     step_size = lr / (1 - beta1^t), sqrt_bc2 = sqrt(1 - beta2^t)     (fp64, rounded to float; 0 when apply == 0)
+ * With skip_nonfinite == 0 a non-finite gradient is applied.  max_norm = +inf: coef = 1 and the update is cvae_adam_step's at step t
+ * (the same arithmetic).  Finite max_norm: an Inf element makes norm = +inf and coef = 0, so the Inf elements become NaN (inf * 0) and the finite ones
+ * contribute 0, as clip_grad_norm_ does; a NaN element makes norm NaN and coef = 1 (the min drops the NaN quotient), so only the NaN
+ * elements reach the state as NaN, where clip_grad_norm_ would spread the NaN to every element.  Either way the state is non-finite
+ * from then on: skip_nonfinite is the protection, the clip is not.
+ * max_norm <= 0 or NaN, n % 4 != 0, n < 0 or a null pointer: CVAE_EINVAL, cvae_last_error() set, nothing launched.
+ *
+ * cvae_adam_step_guarded: cvae_adam_step's arithmetic with gradient scale `gscale` (= grad_scale * coef, one fp32 product),
+ * step_size, sqrt_bc2 and the betas taken from the record; when apply == 0 it writes nothing — params, exp_avg and
+ * exp_avg_sq keep their bits.  It never writes the record.
+ */
+typedef struct cvae_guard_record {      /* 64 bytes at offset 0 of the guard state; device memory                        */
+    int32_t  apply;                     /*  0: 1 = this step updates, 0 = skipped                                         */
+    uint32_t nonfinite;                 /*  4: 1 = the gradient holds an Inf or a NaN                                     */
+    float    coef;                      /*  8: clip coefficient in (0, 1]                                                 */
+    float    norm;                      /* 12: (float)norm64 — +inf where the fp64 norm exceeds FLT_MAX                   */
+    double   norm64;                    /* 16: global norm of grads * grad_scale                                          */
+    int64_t  t;                         /* 24: applied steps so far (Adam's bias-correction step)                         */
+    int64_t  skipped;                   /* 32: skipped steps so far                                                       */
+    float    step_size;                 /* 40: lr / (1 - beta1^t)                                                         */
+    float    sqrt_bc2;                  /* 44: sqrt(1 - beta2^t)                                                          */
+    float    gscale;                    /* 48: grad_scale * coef                                                          */
+    float    beta1, beta2;              /* 52, 56: Adam's betas, as cvae_grad_stats was given them                        */
+    uint32_t ticket;                    /* 60: arrival counter of the statistics pass; 0 between launches                 */
+} cvae_guard_record;
+int64_t cvae_guard_state_bytes(void);
+int cvae_guard_init(cvae_handle h, void* state, int64_t applied, int64_t skipped, void* stream);
+int cvae_grad_stats(cvae_handle h, const float* grads, int64_t n, float grad_scale, float max_norm, int32_t skip_nonfinite,
+                    float lr, float beta1, float beta2, void* state, void* stream);
+int cvae_adam_step_guarded(cvae_handle h, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                           float eps, const void* state, void* stream);
+
+/*
  * Critic.evaluate (critic_net.py:66-69; eval mode) on frames x (B,3,64,64) in [0,1] -> pred (B,1),
  * the `preds` of vae.py:50.  critic_params: cvae_critic_param_count() (= 11 873) floats in the
  * reference's own state_dict order and layouts (features.{0,3,6,10,14}.{weight,bias},
