@@ -1,5 +1,5 @@
 """Host-side mirror of the reference's frozen critic (critic_net.py:5-69) for the training loop:
-`preds = critic.evaluate(images)` (vae.py:50).  Inference only; parameters are kept as one flat
+`preds = critic.evaluate(images)` (vae.py:50).  Inference here, training in critic_train.py; parameters are kept as one flat
 buffer in the reference's state_dict order (what cvae_critic_forward reads)."""
 import torch
 from torch import nn

@@ -720,6 +720,32 @@ int cvae_critic_forward(cvae_handle h, int32_t B, const float* x, const float* c
     return launch_critic_fwd(h->cfg.width, B, x, critic_params, pred, (hipStream_t)stream);
 }
 
+// ---- critic training step (critic_train.hip) ----
+static constexpr int32_t kCriticGradMaxBatch = 65536;
+int64_t cvae_critic_train_floats(void) { return critic_train_floats(); }
+
+int64_t cvae_critic_grad_scratch_bytes(cvae_handle h, int32_t batch) {
+    if (!h || batch < 1 || batch > kCriticGradMaxBatch) { cvae_set_error("cvae_critic_grad_scratch_bytes: null handle, or batch %d outside [1, %d]", batch, kCriticGradMaxBatch); return -1; }
+    return critic_grad_scratch_bytes(batch);
+}
+
+int cvae_critic_grad(cvae_handle h, int32_t B, const float* x, const float* target, const uint8_t* keep_or_null, float dropout_p,
+                     int32_t loss_kind, const float* critic_params, float* grads, float* pred, float* loss_scalars,
+                     uint8_t* decisions_or_null, void* scratch, void* stream) {
+    if (!h) { cvae_set_error("cvae_critic_grad: null handle"); return CVAE_EINVAL; }
+    if (h->cfg.width != 64) { cvae_set_error("cvae_critic_grad: width %d unsupported (the reference critic is 64x64 only)", h->cfg.width); return CVAE_EUNSUPPORTED; }
+    if (B < 1 || B > kCriticGradMaxBatch) { cvae_set_error("cvae_critic_grad: batch %d outside [1, %d]", B, kCriticGradMaxBatch); return CVAE_EINVAL; }
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) { cvae_set_error("cvae_critic_grad: dropout_p %g outside [0, 1)", (double)dropout_p); return CVAE_EINVAL; }
+    if (loss_kind != CVAE_CRITIC_LOSS_BCE && loss_kind != CVAE_CRITIC_LOSS_MSE) { cvae_set_error("cvae_critic_grad: loss_kind %d (0 = BCE, 1 = MSE)", loss_kind); return CVAE_EINVAL; }
+    if (!x || !target || !critic_params || !grads || !pred || !loss_scalars || !scratch) { cvae_set_error("cvae_critic_grad: null pointer"); return CVAE_EINVAL; }
+    if (((uintptr_t)x & 15) || ((uintptr_t)scratch & 15) || ((uintptr_t)decisions_or_null & 3)) {
+        cvae_set_error("cvae_critic_grad: x and scratch must be 16-byte aligned, decisions 4-byte aligned"); return CVAE_EINVAL;
+    }
+    const float scale = (float)(1.0 / (1.0 - (double)dropout_p));
+    return launch_critic_grad(h->cfg.width, B, x, target, keep_or_null, scale, loss_kind, critic_params, grads, pred, loss_scalars,
+                              decisions_or_null, scratch, (hipStream_t)stream);
+}
+
 int cvae_preprocess_u8(cvae_handle h, int32_t B, const uint8_t* frames_hwc, float* x, void* stream) {
     if (!h || B < 1 || !frames_hwc || !x) { cvae_set_error("cvae_preprocess_u8: bad handle/batch/pointer"); return CVAE_EINVAL; }
     if (B > h->cfg.max_batch) { cvae_set_error("cvae_preprocess_u8: batch %d outside [1, %d]", B, h->cfg.max_batch); return CVAE_EINVAL; }

@@ -315,10 +315,21 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
                   const float* logvar, float* ws, float* scalars, float* d_img1, float* d_mu,
                   float* d_logvar, hipStream_t st,
                   int stage = 0, double* rec = nullptr, const double* images = nullptr);      // stage 1 / 2: cross-rank split
-// critic.hip
+// critic.hip, critic_train.hip: float offsets into the flat critic parameter block (reference state_dict order)
+namespace critic_layout {
+constexpr int CW1 = 0, CB1 = 216, CW2 = 224, CB2 = 800, CW3 = 808, CB3 = 1384, CW4 = 1392, CB4 = 2544,
+              CW5 = 2560, CB5 = 10752, CF1W = 10784, CF1B = 11808, CF2W = 11840, CF2B = 11872;
+constexpr int CRITIC_PARAMS = 11873;
+}
 int critic_param_count();
 int launch_critic_fwd(int width, int B, const float* x, const float* critic_params, float* pred, hipStream_t st);
 int launch_preprocess_u8(int width, int B, const uint8_t* u8, float* x, hipStream_t st);
+// critic_train.hip
+int critic_train_floats();
+int64_t critic_grad_scratch_bytes(int B);
+int launch_critic_grad(int width, int B, const float* x, const float* target, const uint8_t* keep, float scale, int loss_kind,
+                       const float* critic_params, float* grads, float* pred, float* loss_scalars, uint8_t* decisions,
+                       void* scratch, hipStream_t st);
 // dataset.hip
 int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
                          int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* span,

@@ -7,13 +7,9 @@
 //   Linear(32,1) Sigmoid                                  (3.4 MFLOP / image, 11 873 parameters)
 // called once per step at vae.py:50, and adjust_values + HWC->CHW of preprocess_observation
 // (vae_utility.py:324-343).  One workgroup per image, every activation lives in LDS; weights are
-// read in the reference's own state_dict order / OIHW layout (the critic is never trained here).
+// read in the reference's own state_dict order / OIHW layout (critic_train.hip trains that same block).
 #include "common.h"
-
-// float offsets into the flat critic parameter block (reference state_dict order)
-static constexpr int CW1 = 0, CB1 = 216, CW2 = 224, CB2 = 800, CW3 = 808, CB3 = 1384, CW4 = 1392, CB4 = 2544,
-                     CW5 = 2560, CB5 = 10752, CF1W = 10784, CF1B = 11808, CF2W = 11840, CF2B = 11872;
-static constexpr int CRITIC_PARAMS = 11873;
+using namespace critic_layout;
 
 // 3x3/pad-1 conv + ReLU + 2x2 max-pool from zero-bordered LDS planes in[CI][S+2][S+2] to zero-bordered
 // LDS planes out[CO][S/2+2][S/2+2] (or un-bordered when BORDER_OUT == 0)

@@ -447,3 +447,129 @@ def curate_recon(episodes, critic, vae, collect=P.collect, total_images=P.total_
     copy), then cvae_critic_forward on the finished entries for preds.  Unselected frames cost the critic launch only.
     The VAE is put in eval mode and must be 64 x 64.  Returns a ReconDataset."""
     return _walk(_ReconPlan(vae), episodes, critic, collect, total_images, chunk_frames, order, device, log)
+
+
+# ---- the critic's own training set: frames + discounted reward targets (critic_train.CriticTrainer) ----
+CRITIC_CHUNK = 4096          # frames per staged host -> device copy of critic_dataset
+
+
+def discounted_targets(rewards, gamma=0.98, shift=12, clip=1.0):
+    """Value targets of one trajectory from its (T,) reward array — THIS PROJECT's definition: the reference ships only a
+    trained checkpoint (its file name carries `shift=12`) and no critic training code, so nothing pins it.
+        r'_t = r_{t+shift}  (0 past the end),   v_t = r'_t + gamma * v_{t+1}  (v_T = 0, computed backwards),   target = min(v, clip)
+    in float64, returned as float32 (T,).  With rewards >= 0 and clip = 1 the targets lie in [0, 1], what the BCE loss needs."""
+    r = np.asarray(rewards, dtype=np.float64).reshape(-1)
+    if shift < 0:
+        raise ValueError(f"shift {shift} must be >= 0")
+    T = r.shape[0]
+    rs = np.zeros(T, np.float64)
+    if shift < T:
+        rs[:T - shift] = r[shift:]
+    v = np.zeros(T, np.float64)
+    nxt = 0.0
+    for t in range(T - 1, -1, -1):
+        nxt = rs[t] + gamma * nxt
+        v[t] = nxt
+    return np.minimum(v, clip).astype(np.float32)
+
+
+def load_rewards(paths, episodes=None):
+    """`.npy` files, or directories of them: one (T,) reward array per trajectory, named as the trajectory's frame file and
+    kept in a directory of its own (load_episodes takes every `.npy` of a directory).  Returns [(name, float64 array)] sorted
+    by name.  With `episodes` (load_episodes' result): ValueError for a trajectory without rewards or of another length;
+    the result then holds exactly the episodes' names, in their order."""
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    files = []
+    for p in paths:
+        p = os.fspath(p)
+        if os.path.isdir(p):
+            files += [os.path.join(p, f) for f in os.listdir(p) if f.endswith(".npy")]
+        elif os.path.isfile(p):
+            files.append(p)
+        else:
+            raise FileNotFoundError(p)
+    out = {}
+    for f in files:
+        name = os.path.basename(f)[:-4] if f.endswith(".npy") else os.path.basename(f)
+        if name in out:
+            raise ValueError(f"two reward files named {name!r}")
+        a = np.load(f)
+        if a.ndim != 1 or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"{f}: rewards must be a numeric (T,) array, got {a.dtype} {a.shape}")
+        out[name] = a.astype(np.float64)
+    if episodes is None:
+        return sorted(out.items())
+    return _match_rewards(episodes, out)
+
+
+def _match_rewards(episodes, rewards):
+    rewards = dict(rewards)
+    matched = []
+    for name, frames in episodes:
+        if name not in rewards:
+            raise ValueError(f"trajectory {name!r} has no reward file")
+        r = np.asarray(rewards[name])
+        if r.ndim != 1 or r.shape[0] != frames.shape[0]:
+            raise ValueError(f"trajectory {name!r}: {frames.shape[0]} frames but rewards of shape {r.shape}")
+        matched.append((name, r))
+    return matched
+
+
+def critic_dataset_indices(lengths, size=None, seed=0):
+    """The draw of critic_dataset: `size` (default: all) of the sum(lengths) frames without replacement, in drawn order
+    (np.random.default_rng(seed).permutation) -> (trajectory, frame) int64 (size, 2)."""
+    lengths = np.asarray(lengths, np.int64)
+    total = int(lengths.sum())
+    size = total if size is None else int(size)
+    if not 0 <= size <= total:
+        raise ValueError(f"size {size} outside [0, {total}] (the trajectories' frames)")
+    pick = np.random.default_rng(seed).permutation(total)[:size]
+    offs = np.concatenate([[0], np.cumsum(lengths)])
+    traj = np.searchsorted(offs, pick, side="right") - 1
+    return np.stack([traj, pick - offs[traj]], 1).astype(np.int64)
+
+
+def critic_dataset(episodes, rewards, size=None, seed=0, gamma=0.98, shift=12, clip=1.0, device="cuda:0"):
+    """The critic's training set on the device: `size` frames drawn over all trajectories (critic_dataset_indices) with
+    discounted_targets(rewards of their trajectory) in the `preds` slot of a DeviceDataset, so CriticTrainer.fit_device
+    gathers (frame, target) batches with cvae_preprocess_u8_gather.  episodes: load_episodes' pairs; rewards: load_rewards'
+    pairs or a dict.  Frames travel in chunks of CRITIC_CHUNK through two StagingSets (pinned, side stream)."""
+    episodes = list(episodes)
+    matched = _match_rewards(episodes, rewards)
+    for name, a in episodes:
+        if not (a.dtype == np.uint8 and a.ndim == 4 and a.shape[1:] == (64, 64, 3)):
+            raise ValueError(f"trajectory {name!r}: the critic needs uint8 (T, 64, 64, 3) frames")
+    device = torch.device(device)
+    source = critic_dataset_indices([a.shape[0] for _, a in episodes], size, seed)
+    n = source.shape[0]
+    targets = [discounted_targets(r, gamma, shift, clip) for _, r in matched]
+    offs = np.concatenate([[0], np.cumsum([len(t) for t in targets])])
+    tg = np.concatenate(targets + [np.zeros(0, np.float32)])[offs[source[:, 0]] + source[:, 1]].astype(np.float32).reshape(n, 1)
+    frames = torch.empty(max(n, 1), 64, 64, 3, dtype=torch.uint8, device=device)[:n]
+    preds = torch.from_numpy(tg).to(device)
+    if n:
+        stream = torch.cuda.current_stream(device)
+        copy_stream = torch.cuda.Stream(device=device)
+        sets = [StagingSet(min(CRITIC_CHUNK, n), 64, device, copy_stream) for _ in range(2)]
+
+        def rows_of(lo):
+            def fill(pin):
+                part = source[lo:lo + CRITIC_CHUNK]
+                for t in np.unique(part[:, 0]):
+                    pos = np.nonzero(part[:, 0] == t)[0]
+                    pin[pos] = episodes[t][1][part[pos, 1]]
+                return part.shape[0]
+            return fill
+
+        starts = list(range(0, n, CRITIC_CHUNK))
+        sets[0].stage(rows_of(0))
+        for ci, lo in enumerate(starts):
+            s = sets[ci % 2]
+            s.wait_copied(stream)
+            frames[lo:lo + s.n].copy_(s.dev[:s.n])
+            s.release(stream)
+            if ci + 1 < len(starts):
+                sets[(ci + 1) % 2].stage(rows_of(starts[ci + 1]))
+        torch.cuda.synchronize(device)
+    return DeviceDataset(frames, preds, source, names=[name for name, _ in episodes])

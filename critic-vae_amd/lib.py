@@ -47,6 +47,8 @@ class Panel(C.Structure):
 PANEL_F32_CHW, PANEL_U8_HWC, PANEL_U8_GREY, PANEL_MASK = 0, 1, 2, 3
 MAX_PANELS = 8
 COMPOSE_CLAMP = 1
+CRITIC_KEEP, CRITIC_DECISIONS, CRITIC_TRAIN_FLOATS = 800, 11072, 11876      # include/cvae.h: cvae_critic_grad
+CRITIC_LOSS = {"bce": 0, "mse": 1}
 
 
 def build(verbose=False):
@@ -95,6 +97,9 @@ _SIGS = {
     "cvae_grads_from_bf16": (C.c_int, [_p, _p, _p, _i64, _p]),
     "cvae_critic_param_count": (_i32, []),
     "cvae_critic_forward": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
+    "cvae_critic_train_floats": (_i64, []),
+    "cvae_critic_grad_scratch_bytes": (_i64, [_p, _i32]),
+    "cvae_critic_grad": (C.c_int, [_p, _i32, _p, _p, _p, _f, _i32] + [_p] * 7),
     "cvae_preprocess_u8": (C.c_int, [_p, _i32, _p, _p, _p]),
     "cvae_diff_grey": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_curate_select": (C.c_int, [_p, _i32, _p, _i64, _p, _i32, _i64] + [_p] * 6),
@@ -336,6 +341,23 @@ class Handle:
     # ---- critic + input pipeline ----
     def critic_forward(self, B, x, critic_params, pred):
         self._check(self.lib.cvae_critic_forward(self.h, B, _ptr(x), _ptr(critic_params), _ptr(pred), _stream()))
+
+    def critic_grad_scratch_bytes(self, B):
+        n = self.lib.cvae_critic_grad_scratch_bytes(self.h, B)
+        if n < 0:
+            raise CvaeError(f"cvae_critic_grad_scratch_bytes: {self.lib.cvae_last_error().decode()}")
+        return n
+
+    def critic_grad(self, B, x, target, keep, dropout_p, loss_kind, critic_params, grads, pred, loss_scalars, scratch, decisions=None):
+        """One critic training step without the optimizer (include/cvae.h): keep (B, 800) uint8 or None, loss_kind 0 = BCE,
+        1 = MSE; grads cvae_critic_train_floats() floats, loss_scalars 4, decisions (B, 11072) uint8 or None."""
+        assert grads.numel() >= CRITIC_TRAIN_FLOATS and pred.numel() >= B and loss_scalars.numel() >= 4 and target.numel() >= B
+        assert keep is None or keep.numel() >= B * CRITIC_KEEP
+        assert decisions is None or decisions.numel() >= B * CRITIC_DECISIONS
+        assert scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= self.critic_grad_scratch_bytes(B)
+        self._check(self.lib.cvae_critic_grad(self.h, B, _ptr(x), _ptr(target), self._u8(keep, "keep"), float(dropout_p), int(loss_kind),
+                                              _ptr(critic_params), _ptr(grads), _ptr(pred), _ptr(loss_scalars),
+                                              self._u8(decisions, "decisions"), scratch.data_ptr(), _stream()))
 
     def preprocess_u8(self, B, frames_u8, x):
         self._check(self.lib.cvae_preprocess_u8(self.h, B, self._u8(frames_u8, "frames"), _ptr(x), _stream()))

@@ -462,6 +462,18 @@ def main(argv=None):
                     help="train a fresh VAE on that set (vae.py:142-153); needs --dataset and --critic (the critic\'s values of "
                          "the entries are cached in the dataset; the checkpoint names the critic it was built with); --save DIR writes "
                          "DIR/vae2_encoder.pt and DIR/vae2_decoder.pt")
+    ap.add_argument("-critic", dest="critic_mode", action="store_true",
+                    help="train the critic itself on recorded trajectories and their rewards (critic_train.py); needs --episodes, "
+                         "--rewards and --save; writes DIR/critic.pt in the reference's checkpoint format, which --critic of the "
+                         "other modes loads")
+    ap.add_argument("--rewards", nargs="+", metavar="PATH", default=None,
+                    help="-critic: .npy files (T,) or directories of them, one per trajectory, named as the trajectory's frame file")
+    ap.add_argument("--lr", type=float, default=1e-4, help="-critic: Adam's learning rate")
+    ap.add_argument("--dropout", type=float, default=0.3, help="-critic: p of the critic's three Dropout layers")
+    ap.add_argument("--loss", choices=("bce", "mse"), default="bce", help="-critic: the loss on the sigmoid output")
+    ap.add_argument("--gamma", type=float, default=0.98, help="-critic: discount of the value targets (episodes.discounted_targets)")
+    ap.add_argument("--shift", type=int, default=12, help="-critic: frames by which the rewards are moved earlier")
+    ap.add_argument("--datasize", type=int, default=None, metavar="N", help="-critic: frames drawn over all trajectories (default: all)")
     ap.add_argument("--networks", metavar="DIR", default="saved-networks", help="-dataset: directory with the first VAE's "
                     f"{ENCODER_FILE} and {DECODER_FILE}")
     ap.add_argument("--out", metavar="FILE", default=None, help="-dataset: where the recon dataset goes (plain arrays)")
@@ -469,7 +481,7 @@ def main(argv=None):
     ap.add_argument("--dataset", metavar="FILE", default=None, help="-second: the file -dataset --out wrote")
     ap.add_argument("--synthetic", type=int, default=1024, help="number of synthetic frames")
     ap.add_argument("--batch", type=int, default=P.batch_size)
-    ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--epochs", type=int, default=None, help="default 1; -critic: 15")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--critic", default=None, help="'random' scalars (BASELINE config 1; the default without --episodes), "
                     "'synth' = the HIP critic with generator weights, or a path to a reference critic checkpoint (.pt)")
@@ -489,8 +501,16 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.max_grad_norm is not None and not args.max_grad_norm > 0:
         ap.error("--max-grad-norm needs a positive number")
-    if args.train + args.dataset_mode + args.second != 1:
-        ap.error("exactly one of -train, -dataset, -second (segment.py has -video [-thresh] [--second]); see SURVEY.md §8 for scope")
+    if args.train + args.dataset_mode + args.second + args.critic_mode != 1:
+        ap.error("exactly one of -train, -dataset, -second, -critic (segment.py has -video [-thresh] [--second]); see SURVEY.md §8 for scope")
+    if args.critic_mode:
+        if args.episodes is None or args.rewards is None or args.save is None:
+            ap.error("-critic needs --episodes, --rewards and --save")
+        if args.epochs is None:
+            args.epochs = 15
+        return _train_critic(args)
+    if args.epochs is None:
+        args.epochs = 1
     if args.dataset_mode:
         if args.episodes is None or args.critic in (None, "random") or args.out is None:
             ap.error("-dataset needs --episodes, --critic (a checkpoint or 'synth') and --out")
@@ -588,6 +608,47 @@ def _train_episodes(args):
     if len(ds) == 0:
         raise SystemExit("the curated dataset is empty: no frame of the trajectories falls in a critic-value bin")
     return _fit_and_save(args, vae, ds, second=False)
+
+
+CRITIC_FILE = "critic.pt"
+
+
+def _train_critic(args):
+    """-critic: load_episodes + load_rewards -> critic_dataset (discounted targets) -> CriticTrainer.fit_device -> DIR/critic.pt."""
+    from .critic import Critic
+    from .critic_train import CriticTrainer, initial_state_dict
+    from .episodes import critic_dataset, load_episodes, load_rewards
+    from .lib import Handle
+    episodes = load_episodes(args.episodes)
+    rewards = load_rewards(args.rewards, episodes)
+    device = _device()
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    critic = Critic(handle=Handle(64, max(args.batch, 1))).to(device)
+    critic.load_state_dict(initial_state_dict(args.seed))
+    ds = critic_dataset(episodes, rewards, size=args.datasize, seed=args.seed, gamma=args.gamma, shift=args.shift, device=device)
+    if len(ds) == 0:
+        raise SystemExit("the critic's dataset is empty")
+    trainer = CriticTrainer(critic, lr=args.lr, dropout=args.dropout, loss=args.loss, skip_nonfinite=args.skip_nonfinite,
+                            max_grad_norm=args.max_grad_norm)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(args.seed)
+    t0 = time.time()
+    log = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    s = log.cpu().numpy()
+    per_epoch = s.shape[0] // args.epochs
+    print(f"{args.epochs * len(ds) / dt:.1f} images/s over {args.epochs} epoch(s) of {len(ds)} frames; {args.loss} loss "
+          f"{s[:per_epoch, 0].mean():.6f} (first epoch) -> {s[-per_epoch:, 0].mean():.6f} (last)")
+    os.makedirs(args.save, exist_ok=True)
+    path = os.path.join(args.save, CRITIC_FILE)
+    torch.save({k: v.detach().cpu() for k, v in critic.state_dict().items()}, path)
+    print(f"saved {path}")
+    if trainer.guarded:
+        st = trainer.guard_stats()
+        print(f"guard: {st['applied']} steps applied, {st['skipped']} skipped")
+    return critic
 
 
 def _build_recon_dataset(args):

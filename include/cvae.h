@@ -270,6 +270,46 @@ int32_t cvae_critic_param_count(void);
 int cvae_critic_forward(cvae_handle h, int32_t batch, const float* x, const float* critic_params,
                         float* pred, void* stream);
 
+/*
+ * One training step of the critic: Critic.forward in TRAIN mode (critic_net.py:15-59, default arguments: width 64,
+ * dims [8,8,8,16], bottleneck 32, ReLU, max-pool; fp32), the loss against `target`, and the gradient of every parameter.
+ * Caller-owned buffers, the caller's stream, no allocation, no sync; every argument is checked before any device access.
+ *
+ * x (B,3,64,64) in [0,1], 16-byte aligned; target (B) in [0,1]; 1 <= batch <= 65 536, independent of the handle's max_batch
+ * (scratch is sized by cvae_critic_grad_scratch_bytes(batch): at most 256 per-workgroup gradient partials + 2 floats per image).
+ * A handle of another width than 64: CVAE_EUNSUPPORTED.  critic_params: the 11 873 floats cvae_critic_forward reads.
+ * grads: cvae_critic_train_floats() (= 11 876) floats, the same order and OIHW layouts, the mean over the batch; the three
+ * padding floats are written as 0, so cvae_adam_step / cvae_grad_stats / cvae_adam_step_guarded (n % 4 == 0) take the block.
+ * Every output is fully written; scratch (16-byte aligned) may hold anything on entry.
+ *
+ * Dropout is explicit, as eps is for the VAE: keep (B, CVAE_CRITIC_KEEP) uint8, nonzero = kept; a row holds the sites
+ * features.9 (512, on the pooled (8,8,8) tensor), features.13 (256, on (16,4,4)), crit.3 (32), each in (c,h,w) order.
+ * Kept elements are multiplied by (float)(1.0 / (1.0 - (double)dropout_p)), 0 <= dropout_p < 1.  keep == NULL: every
+ * element kept (and scaled); with dropout_p == 0 that is the eval-mode forward, pred equal to cvae_critic_forward's.
+ * Max-pool follows ReLU and takes the first maximum of its window in scan order (strict >), as torch does.
+ *
+ * loss_kind CVAE_CRITIC_LOSS_BCE: mean over B of -(t * max(log p, -100) + (1 - t) * max(log(1 - p), -100)) (torch's
+ * binary_cross_entropy); CVAE_CRITIC_LOSS_MSE: mean (p - t)^2; anything else CVAE_EINVAL.  loss_scalars: 4 device floats,
+ * [0] the chosen loss, [1] BCE, [2] MSE, [3] 0; per-image terms are summed in a fixed order in fp64.
+ * Backward in torch's arithmetic: BCE d_p = (p - t) / max(p (1 - p), 1e-12) / B, then d_z = d_p * p (1 - p), so a
+ * sigmoid saturated to exactly 1 contributes a zero gradient; MSE d_p = 2 (p - t) / B.
+ * No floating-point atomics: per-workgroup partials in scratch, merged in workgroup order; the same inputs give the same
+ * bits (the grid, and with it the summation order, depends on batch, the device's compute units and CVAE_PERSIST_MAXWG).
+ *
+ * decisions (optional, (B, CVAE_CRITIC_DECISIONS) uint8, 4-byte aligned): the discrete choices of the forward.  Per
+ * pooled output in (c,py,px) order, blocks 1..4 in turn (8*32*32, 8*16*16, 8*8*8, 16*4*4): 0..3 = 2*dy+dx of the selected
+ * element, 4 = the window's maximum was <= 0 (output 0, no gradient); then 32 bytes features.14 pre-activation > 0, then
+ * 32 bytes crit.1 pre-activation > 0.
+ */
+#define CVAE_CRITIC_KEEP      800
+#define CVAE_CRITIC_DECISIONS 11072
+enum { CVAE_CRITIC_LOSS_BCE = 0, CVAE_CRITIC_LOSS_MSE = 1 };
+int64_t cvae_critic_train_floats(void);
+int64_t cvae_critic_grad_scratch_bytes(cvae_handle h, int32_t batch);       /* host-only; -1 for a bad argument */
+int cvae_critic_grad(cvae_handle h, int32_t batch, const float* x, const float* target, const uint8_t* keep_or_null,
+                     float dropout_p, int32_t loss_kind, const float* critic_params, float* grads, float* pred,
+                     float* loss_scalars, uint8_t* decisions_or_null, void* scratch, void* stream);
+
 /* adjust_values + HWC->CHW of preprocess_observation (vae_utility.py:324-343): uint8 frames
  * (B,W,W,3) -> float (B,3,W,W) / 255, so that only 1 byte per value crosses PCIe. */
 int cvae_preprocess_u8(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, float* x, void* stream);
