@@ -1069,4 +1069,42 @@ int cvae_op_msssim(cvae_handle h, int32_t B, const float* img1, const float* img
                          (hipStream_t)stream);
 }
 
+// The latent-layer launchers of fc.hip, one per entry point.  flat / h_out / dh / dflat are in the handle's storage type.
+static int latent_check(cvae_handle h, int32_t B, const char* who, bool pointers_ok) {
+    if (!h) { cvae_set_error("%s: null handle", who); return CVAE_EINVAL; }
+    if (B < 1 || B > h->cfg.max_batch) { cvae_set_error("%s: batch %d outside [1, %d]", who, B, h->cfg.max_batch); return CVAE_EINVAL; }
+    if (!pointers_ok) { cvae_set_error("%s: null pointer", who); return CVAE_EINVAL; }
+    return 0;
+}
+
+int64_t cvae_op_latent_scratch_floats(cvae_handle h, int32_t B) {
+    if (!h || B < 1 || B > h->cfg.max_batch) { cvae_set_error("cvae_op_latent_scratch_floats: bad handle, or batch %d outside [1, max_batch]", B); return CVAE_EINVAL; }
+    return fc_ws_floats(h->cfg.width, B);
+}
+
+int cvae_op_fc_fwd(cvae_handle h, int32_t B, const float* flat, const float* wfc, const float* bfc, const float* eps,
+                   const float* pred, float* mu, float* logvar, float* zcat, void* scratch, void* stream) {
+    RC(latent_check(h, B, "cvae_op_fc_fwd", flat && wfc && bfc && eps && pred && mu && logvar && zcat && scratch));
+    return launch_fc_fwd(h->cfg.width, B, flat, wfc, bfc, eps, pred, mu, logvar, zcat, (float*)scratch, (hipStream_t)stream, io_bf16(h));
+}
+
+int cvae_op_decin_fwd(cvae_handle h, int32_t B, const float* zcat, const float* wd, const float* bd, float* h_out, void* stream) {
+    RC(latent_check(h, B, "cvae_op_decin_fwd", zcat && wd && bd && h_out));
+    return launch_decin_fwd(h->cfg.width, B, zcat, wd, bd, h_out, (hipStream_t)stream, io_bf16(h));
+}
+
+int cvae_op_decin_bwd(cvae_handle h, int32_t B, const float* zcat, const float* dh, const float* wd, float* dwd, float* dbd,
+                      float* dzcat, void* scratch, void* stream) {
+    RC(latent_check(h, B, "cvae_op_decin_bwd", zcat && dh && wd && dwd && dbd && dzcat && scratch));
+    return launch_decin_bwd(h->cfg.width, B, zcat, dh, wd, dwd, dbd, dzcat, (float*)scratch, (hipStream_t)stream, io_bf16(h));
+}
+
+int cvae_op_fc_bwd(cvae_handle h, int32_t B, const float* flat, const float* wfc, const float* dzcat, const float* eps,
+                   const float* logvar, const float* dmu_loss, const float* dlv_loss, float* dwfc, float* dbfc, float* dflat,
+                   void* scratch, void* stream) {
+    RC(latent_check(h, B, "cvae_op_fc_bwd", flat && wfc && dzcat && eps && logvar && dmu_loss && dlv_loss && dwfc && dbfc && dflat && scratch));
+    return launch_fc_bwd(h->cfg.width, B, flat, wfc, dzcat, eps, logvar, dmu_loss, dlv_loss, dwfc, dbfc, dflat, (float*)scratch,
+                         (hipStream_t)stream, io_bf16(h));
+}
+
 }  // extern "C"

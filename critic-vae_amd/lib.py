@@ -126,6 +126,11 @@ _SIGS = {
     "cvae_op_bn_pool_act_fwd": (C.c_int, [_p, _i32, _i32] + [_p] * 9 + [_i32, _p]),
     "cvae_op_bn_pool_act_bwd": (C.c_int, [_p, _i32, _i32] + [_p] * 11),
     "cvae_op_msssim": (C.c_int, [_p, _i32] + [_p] * 6),
+    "cvae_op_latent_scratch_floats": (_i64, [_p, _i32]),
+    "cvae_op_fc_fwd": (C.c_int, [_p, _i32] + [_p] * 10),
+    "cvae_op_decin_fwd": (C.c_int, [_p, _i32] + [_p] * 5),
+    "cvae_op_decin_bwd": (C.c_int, [_p, _i32] + [_p] * 8),
+    "cvae_op_fc_bwd": (C.c_int, [_p, _i32] + [_p] * 12),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -534,3 +539,27 @@ class Handle:
     def op_msssim(self, B, img1, img2, ws, scalars, d_img1=None):
         self._check(self.lib.cvae_op_msssim(self.h, B, _ptr(img1), _ptr(img2), _ptr(ws), _ptr(scalars),
                                             _ptr(d_img1), _stream()))
+
+    # the latent layers (fc.hip): flat / h_out / dh / dflat in the handle's storage type (bf16 elements packed two per float on a
+    # "bf16" handle), native weights Wfc [K][64] and Wd [33][K]; scratch: op_latent_scratch_floats(B) floats
+    def op_latent_scratch_floats(self, B):
+        n = self.lib.cvae_op_latent_scratch_floats(self.h, B)
+        if n < 0:
+            self._check(int(n))
+        return n
+
+    def op_fc_fwd(self, B, flat, wfc, bfc, eps, pred, mu, logvar, zcat, scratch):
+        self._check(self.lib.cvae_op_fc_fwd(self.h, B, _ptr(flat), _ptr(wfc), _ptr(bfc), _ptr(eps), _ptr(pred), _ptr(mu),
+                                            _ptr(logvar), _ptr(zcat), _ptr(scratch), _stream()))
+
+    def op_decin_fwd(self, B, zcat, wd, bd, h_out):
+        self._check(self.lib.cvae_op_decin_fwd(self.h, B, _ptr(zcat), _ptr(wd), _ptr(bd), _ptr(h_out), _stream()))
+
+    def op_decin_bwd(self, B, zcat, dh, wd, dwd, dbd, dzcat, scratch):
+        self._check(self.lib.cvae_op_decin_bwd(self.h, B, _ptr(zcat), _ptr(dh), _ptr(wd), _ptr(dwd), _ptr(dbd), _ptr(dzcat),
+                                               _ptr(scratch), _stream()))
+
+    def op_fc_bwd(self, B, flat, wfc, dzcat, eps, logvar, dmu_loss, dlv_loss, dwfc, dbfc, dflat, scratch):
+        self._check(self.lib.cvae_op_fc_bwd(self.h, B, _ptr(flat), _ptr(wfc), _ptr(dzcat), _ptr(eps), _ptr(logvar),
+                                            _ptr(dmu_loss), _ptr(dlv_loss), _ptr(dwfc), _ptr(dbfc), _ptr(dflat),
+                                            _ptr(scratch), _stream()))

@@ -574,6 +574,31 @@ int cvae_op_bn_pool_act_bwd(cvae_handle h, int32_t layer, int32_t batch, const f
 int cvae_op_msssim(cvae_handle h, int32_t batch, const float* img1, const float* img2, void* ws,
                    float* scalars, float* d_img1, void* stream);
 
+/*
+ * The latent layers (fc.hip), one entry point per launcher of the step.  Weights in the native layouts: Wfc [K][64]
+ * (columns 0..31 = fc_mu, 32..63 = fc_var), Wd [33][K], K = 256 (width/16)^2 in (h,w,c) order, i.e. `flat`, `h_out`, `dh`
+ * and `dflat` are (batch, K) NHWC activations in the handle's storage type (bf16 elements on a precision 1 handle, fp32
+ * otherwise); every other tensor is fp32.  `scratch` needs cvae_op_latent_scratch_floats(batch) floats; its contents on
+ * entry do not matter.  batch < 1, batch > max_batch or a null pointer is CVAE_EINVAL (the size query returns it too).
+ */
+int64_t cvae_op_latent_scratch_floats(cvae_handle h, int32_t batch);
+/* flatten + fc_mu | fc_var + reparametrize + cat (vae_nets.py:105-109, :48-51, :143): mu, logvar (batch,32) = flat . Wfc + bfc,
+ * zcat (batch,33) = [mu + eps * exp(logvar / 2) | pred] */
+int cvae_op_fc_fwd(cvae_handle h, int32_t batch, const float* flat, const float* wfc, const float* bfc,
+                   const float* eps, const float* pred, float* mu, float* logvar, float* zcat,
+                   void* scratch, void* stream);
+/* decoder_input Linear(33, K) (vae_nets.py:143-144): h_out (batch,K) = zcat . Wd + bd */
+int cvae_op_decin_fwd(cvae_handle h, int32_t batch, const float* zcat, const float* wd, const float* bd,
+                      float* h_out, void* stream);
+/* its backward: dwd [33][K] = zcat^T . dh, dbd [K] = column sums of dh, dzcat (batch,33) = dh . Wd^T */
+int cvae_op_decin_bwd(cvae_handle h, int32_t batch, const float* zcat, const float* dh, const float* wd,
+                      float* dwd, float* dbd, float* dzcat, void* scratch, void* stream);
+/* backward of cvae_op_fc_fwd: dml (batch,64) = [dz + dmu_loss | dz * eps * exp(logvar / 2) / 2 + dlv_loss] with dz =
+ * dzcat[:, :32]; dwfc [K][64] = flat^T . dml, dbfc [64] = column sums of dml, dflat (batch,K) = dml . Wfc^T */
+int cvae_op_fc_bwd(cvae_handle h, int32_t batch, const float* flat, const float* wfc, const float* dzcat,
+                   const float* eps, const float* logvar, const float* dmu_loss, const float* dlv_loss,
+                   float* dwfc, float* dbfc, float* dflat, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

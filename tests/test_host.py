@@ -133,6 +133,28 @@ print("ok")
         assert got == dict(want if per_tile == "0" else {k: ["00000"] * 6 for k in want}, **xp), (per_tile, got)
 
 
+def test_latent_ops_refuse_bad_batches_and_null_scratch():
+    """cvae_op_fc_fwd / decin_fwd / decin_bwd / fc_bwd and their scratch query: batch < 1, batch > max_batch or a null scratch is
+    CVAE_EINVAL before anything is launched (the pointers here are not device memory)."""
+    h = cvlib.Handle(64, 8)
+    p = 0x1000
+    for B in (0, -1, 9):
+        assert h.lib.cvae_op_latent_scratch_floats(h.h, B) == -1
+        assert h.lib.cvae_op_fc_fwd(h.h, B, *[p] * 9, None) == -1
+        assert h.lib.cvae_op_decin_fwd(h.h, B, *[p] * 4, None) == -1
+        assert h.lib.cvae_op_decin_bwd(h.h, B, *[p] * 7, None) == -1
+        assert h.lib.cvae_op_fc_bwd(h.h, B, *[p] * 11, None) == -1
+        assert b"batch" in h.lib.cvae_last_error()
+    assert h.lib.cvae_op_fc_fwd(h.h, 8, *[p] * 8, None, None) == -1
+    assert h.lib.cvae_op_decin_bwd(h.h, 8, *[p] * 6, None, None) == -1
+    assert h.lib.cvae_op_fc_bwd(h.h, 8, *[p] * 10, None, None) == -1
+    with pytest.raises(cvlib.CvaeError):
+        h.op_latent_scratch_floats(9)
+    # fc.hip: the larger of the FC_KS forward slabs and the decoder_input slabs, then dml and its column sums
+    for B in (1, 8):
+        assert h.op_latent_scratch_floats(B) >= max(32 * B * 64, 34 * 4096) + B * 64
+
+
 def test_two_handles_do_not_share_state():
     """include/cvae.h: one handle per device / configuration, no global state."""
     a, b = cvlib.Handle(64, 4), cvlib.Handle(128, 2, precision="bf16")

@@ -175,6 +175,44 @@ BN_OFF = (0, 32, 96, 224)  # per-block channel offsets of the running means (bn_
 BN_STAT_REL = 1e-5
 
 
+def within(what, got, want, bound, worst=None):
+    """Elementwise |got - want| <= bound, every element, a NaN fails.  Returns the largest err / allowed (<= 1 passes) and, when
+    `worst` is a dict, records it there under `what` before it asserts."""
+    got, want, bound = got.double(), want.double(), bound.double()
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    err = (got - want).abs()
+    r = (err / bound.clamp_min(1e-300)).max().item() if err.numel() else 0.0
+    if worst is not None:
+        worst[what] = r
+    if not r <= 1.0:
+        k = int(torch.nan_to_num(err / bound.clamp_min(1e-300), nan=float("inf")).flatten().argmax())
+        raise AssertionError(f"{what}: err / allowed {r:.3e} (at flat index {k}: got {got.flatten()[k].item():.6e}, "
+                             f"want {want.flatten()[k].item():.6e}, allowed {bound.flatten()[k].item():.3e})")
+    return r
+
+
+# ---- term counts of the latent-layer links (fc.hip): the worst-case fp32 error of a sum is (terms) * U32 * sum |addends| ----
+def fc_split_terms(K, bias):
+    """latent_gemm + fc_finish / decin_dz_finish: each of the FC_KS slices sums K / FC_KS products in series (a product is rounded: +1),
+    then the FC_KS slabs are added in series, after the bias where there is one (+1)."""
+    return K // FC_KS + 1 + FC_KS + (1 if bias else 0)
+
+
+DECIN_TERMS = 33 + 1      # decin_fwd: fmaf from the bias over i = 0..32
+DML_TERMS = 8             # fc_bwd_prep: expf (a few ulps), three products and the sum, per element of dml
+DFLAT_TERMS = 64 + DML_TERMS      # fc_bwd_dflat: 64 fmaf in series per output, on a dml that carries DML_TERMS roundings of its terms
+ZCAT_TERMS = 8            # fc_finish: expf (a few ulps), the product and the sum: 8 ulps of the two terms
+
+
+def batch_terms(B):
+    """The batch-contracted sums (bgemm_*: dW fc, dW / db decoder_input; colsum: db fc): at most B additions in any order, the
+    three partial-tile additions of the last stage, one product rounding."""
+    return B + 4
+
+
+_within = within          # check_bf16_stored_operands binds the name to its own record of worst ratios
+
+
 def check_bf16_stored_operands(h, tr, B, x, pred, eps, theta, bn_before, bn_after, images=None, mult=1, ties=None):
     """After one bf16-mode step of B images on handle h: recompute every link of the step on the CPU from the operands the kernels
     stored and compare.  tr holds the step's buffers (ws, grads, mu, logvar, recon, d_recon, d_mu, d_logvar, scalars: a FusedTrainer
@@ -264,16 +302,8 @@ def check_bf16_stored_operands(h, tr, B, x, pred, eps, theta, bn_before, bn_afte
         worst[what] = err / max(rel * scale, 1e-30)
         assert err <= rel * scale + 1e-12, f"{what}: err {err:.3e} vs max {scale:.3e}"
 
-    def within(what, got, want, bound):     # elementwise |got - want| <= bound (NaN fails)
-        got, want, bound = got.double(), want.double(), bound.double()
-        assert got.shape == want.shape, (what, got.shape, want.shape)
-        err = (got - want).abs()
-        r = (err / bound.clamp_min(1e-300)).max().item() if err.numel() else 0.0
-        worst[what] = r
-        if not r <= 1.0:
-            k = int(torch.nan_to_num(err / bound.clamp_min(1e-300), nan=float("inf")).flatten().argmax())
-            raise AssertionError(f"{what}: err / allowed {r:.3e} (at flat index {k}: got {got.flatten()[k].item():.6e}, "
-                                 f"want {want.flatten()[k].item():.6e}, allowed {bound.flatten()[k].item():.3e})")
+    def within(what, got, want, bound):     # elementwise |got - want| <= bound (NaN fails), recorded in `worst`
+        return _within(what, got, want, bound, worst)
 
     def wgrad(inp, dout):           # dW (O,I,5,5), db of a 5x5 / pad 2 conv from its input and output gradient, times mult
         return (mult * torch.nn.grad.conv2d_weight(inp, (dout.shape[1], inp.shape[1], 5, 5), dout, padding=2),
@@ -319,22 +349,20 @@ def check_bf16_stored_operands(h, tr, B, x, pred, eps, theta, bn_before, bn_afte
     wfc = torch.cat((ref["encoder.fc_mu.weight"], ref["encoder.fc_var.weight"]), 0).double()           # (64, K)
     bfc = torch.cat((ref["encoder.fc_mu.bias"], ref["encoder.fc_var.bias"]), 0).double()
     ml = a3 @ wfc.t() + bfc
-    # each slice: K / FC_KS products (a bf16 x fp32 product is rounded: +1) in series; then bias + FC_KS slabs in series
-    ml_abs = (a3.abs() @ wfc.abs().t() + bfc.abs()) * ((K // FC_KS + 1 + FC_KS + 1) * U32)
+    ml_abs = (a3.abs() @ wfc.abs().t() + bfc.abs()) * (fc_split_terms(K, bias=True) * U32)
     within("mu", mu_g, ml[:, :32], ml_abs[:, :32])
     within("logvar", lv_g, ml[:, 32:], ml_abs[:, 32:])
     zc = f32slot("zcat", 33)
     e_, p_ = eps[i0:i1].double().cpu(), pred[i0:i1].double().cpu()
     se = e_ * torch.exp(0.5 * lv_g.double())
-    # fp32: expf (a few ulps), the product and the sum: 8 ulps of the two terms
-    within("zcat", zc[:, :32], mu_g.double() + se, 8 * U32 * (mu_g.double().abs() + se.abs()))
+    within("zcat", zc[:, :32], mu_g.double() + se, ZCAT_TERMS * U32 * (mu_g.double().abs() + se.abs()))
     assert torch.equal(zc[:, 32:], p_), "zcat: the pred column is not the step's pred"
 
     # ---- decoder_input forward (decin_fwd<bf16>: fp32 zcat, fp32 Wd, fmaf from the bias over i = 0..32, bf16 store) ----
     wd = ref["decoder.decoder_input.weight"].double()                   # (K, 33), rows in (C, H, W) order
     bd = ref["decoder.decoder_input.bias"].double()
     hr = (zc @ wd.t() + bd).view(n, 256, 4 * m, 4 * m)
-    hb = (zc.abs() @ wd.abs().t() + bd.abs()).view(n, 256, 4 * m, 4 * m) * (34 * U32)
+    hb = (zc.abs() @ wd.abs().t() + bd.abs()).view(n, 256, 4 * m, 4 * m) * (DECIN_TERMS * U32)
     within("h", act("h", 256, 4 * m), hr, BF16 * hr.abs() + (1 + BF16) * hb)
     # ---- decoder forward: D0 plain, D1..D3 behind a nearest-2x upsample (phase-collapsed in the kernels) ----
     for i, (ci, co, s) in enumerate(dec[:4]):
@@ -403,7 +431,7 @@ def check_bf16_stored_operands(h, tr, B, x, pred, eps, theta, bn_before, bn_afte
     # ---- decoder_input input gradient (latent_gemm<true, bf16> + decin_dz_finish): d_h . Wd ----
     dh_flat = act("d_h", 256, 4 * m).double().reshape(n, K)
     dz = f32slot("d_zcat", 33)
-    within("d_zcat", dz, dh_flat @ wd, (dh_flat.abs() @ wd.abs()) * ((K // FC_KS + 1 + FC_KS) * U32))
+    within("d_zcat", dz, dh_flat @ wd, (dh_flat.abs() @ wd.abs()) * (fc_split_terms(K, bias=False) * U32))
     # ---- fc backward: dml (fc_bwd_prep), d_a3 = dml . Wfc (fc_bwd_dflat<bf16>), dWfc = a3^T . bf16(dml), dbfc = colsum(dml) ----
     lvd = lv_g.double()
     ex = 0.5 * e_ * torch.exp(0.5 * lvd)
@@ -411,8 +439,7 @@ def check_bf16_stored_operands(h, tr, B, x, pred, eps, theta, bn_before, bn_afte
     dml_abs = torch.cat((dz[:, :32].abs() + tr.d_mu[i0:i1].double().cpu().abs(),
                          (dz[:, :32] * ex).abs() + tr.d_logvar[i0:i1].double().cpu().abs()), 1)
     da3 = (dml @ wfc).view(n, 256, 4 * m, 4 * m)
-    # dml: expf and three products, then 64 fmaf in series per output: 8 + 64 roundings of the terms
-    da3_b = (dml_abs @ wfc.abs()).view(n, 256, 4 * m, 4 * m) * ((64 + 8) * U32)
+    da3_b = (dml_abs @ wfc.abs()).view(n, 256, 4 * m, 4 * m) * (DFLAT_TERMS * U32)
     within("d_a3", act("d_a3", 256, 4 * m), da3, BF16 * da3.abs() + (1 + BF16) * da3_b)
     dwfc = mult * (bf(dml).t() @ a3)                                    # the bf16 MFMA takes dml rounded to bf16
     close(grd["encoder.fc_mu.weight"], dwfc[:32], "dW fc_mu", 2e-3)
