@@ -426,6 +426,31 @@ int cvae_loss(cvae_handle h, int32_t B, const float* x, const float* mu, const f
     return launch_msssim(h->cfg.width, B, recon, x, mu, logvar, ws + w.ms, scalars, d_recon, d_mu, d_logvar, (hipStream_t)stream);
 }
 
+// ---- per-image scores and the pooled record of a held-out set (score.hip) ----
+int32_t cvae_score_cols(void) { return CVAE_SCORE_COLS; }
+int64_t cvae_score_state_bytes(void) { return score_state_bytes(); }
+int cvae_score_init(cvae_handle h, void* state, void* stream) {
+    if (!h || !state || ((uintptr_t)state & 7)) { cvae_set_error("cvae_score_init: bad handle, null or misaligned state"); return CVAE_EINVAL; }
+    return launch_score_init(state, (hipStream_t)stream);
+}
+int cvae_score(cvae_handle h, int32_t B, const float* x, const float* mu, const float* logvar, const float* recon, void* wsv,
+               float* per_image, void* state, void* stream) {
+    RC(check(h, B, wsv));
+    if (!x || !mu || !logvar || !recon) { cvae_set_error("cvae_score: null tensor"); return CVAE_EINVAL; }
+    if (!per_image && !state) { cvae_set_error("cvae_score: per_image and state are both null: nothing to write"); return CVAE_EINVAL; }
+    if (((uintptr_t)x & 15) || ((uintptr_t)recon & 15) || ((uintptr_t)state & 7)) {
+        cvae_set_error("cvae_score: x and recon must be 16-byte aligned, state 8-byte aligned"); return CVAE_EINVAL;
+    }
+    float* ws = (float*)wsv;
+    const WsLayout w = carve(h, B);
+    return launch_score(h->cfg.width, B, x, mu, logvar, recon, ws + w.ms, per_image, state, (hipStream_t)stream);
+}
+int cvae_score_finish(cvae_handle h, int32_t width, void* state, float* scalars, void* stream) {
+    if (!h || !state || !scalars || ((uintptr_t)state & 7)) { cvae_set_error("cvae_score_finish: bad handle, null pointer or misaligned state"); return CVAE_EINVAL; }
+    if (width != 64 && width != 128) { cvae_set_error("cvae_score_finish: width %d unsupported", width); return CVAE_EINVAL; }
+    return launch_score_finish(width, state, scalars, (hipStream_t)stream);
+}
+
 int cvae_backward(cvae_handle h, int32_t B, const float* x, const float* pred, const float* eps, const float* params,
                   const float* logvar, const float* recon, const float* d_recon, const float* d_mu,
                   const float* d_logvar, void* wsv, float* grads, void* stream) {

@@ -315,6 +315,14 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
                   const float* logvar, float* ws, float* scalars, float* d_img1, float* d_mu,
                   float* d_logvar, hipStream_t st,
                   int stage = 0, double* rec = nullptr, const double* images = nullptr);      // stage 1 / 2: cross-rank split
+void msssim_score_slots(int width, int B, int64_t part[5], int64_t* scratch);      // score.hip: partial pairs and a free region of a values-only pyramid
+int launch_msssim_finish_rec(int width, const double* rec, const double* images, float* scalars, float* coef, hipStream_t st);
+// score.hip: per-image scores and the pooled record (layout: include/cvae.h)
+int64_t score_state_bytes();
+int launch_score_init(void* state, hipStream_t st);
+int launch_score(int width, int B, const float* x, const float* mu, const float* logvar, const float* recon, float* ms,
+                 float* per_image, void* state, hipStream_t st);
+int launch_score_finish(int width, void* state, float* scalars, hipStream_t st);
 // critic.hip, critic_train.hip: float offsets into the flat critic parameter block (reference state_dict order)
 namespace critic_layout {
 constexpr int CW1 = 0, CB1 = 216, CW2 = 224, CB2 = 800, CW3 = 808, CB3 = 1384, CW4 = 1392, CB4 = 2544,

@@ -22,6 +22,7 @@
 // HBM traffic: forward reads x, y once and writes F (+ 1/4-size pyramids); backward reads the F pyramid and
 // writes dx — 1.2x the algorithmic bytes (was 3.2x / 2.5x with the derivative maps stored).
 #include "common.h"
+#include "msssim_finish.h"
 #include <math.h>
 
 // The 11 normalised taps travel BY VALUE in every kernel's argument struct (scalar registers): no
@@ -691,37 +692,6 @@ struct MsFinArgs {
     const double* images;    // cross-rank path, finish step: the summed image count (replaces B and count[])
 };
 
-// lanes 0-4: ssim_l, lanes 5-9: cs_l, lane 10: KLD sum — every lane finishes its own scalar from its fp64 sum t
-// (same operations and order as a serial evaluation), shuffles bring them together.  cnt: this lane's level count
-// B*3*S_l*S_l; Bd: the image count of the KLD mean.  Called by lanes 0..63 of one wave.
-__device__ __forceinline__ void ms_finish_scalars(int lane, double t, double cnt, double Bd, float* scalars, float* coef) {
-    const int l = lane % 5;
-    const float kw = 0.001f;
-    const float wts[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
-    const float meanf = (float)(t / cnt);
-    const float pw = powf(meanf, wts[l]);
-    const float p2 = __shfl(pw, 4, 64);
-    float out = 1.0f;
-    for (int q = 0; q < 4; ++q) out *= __shfl(pw, 5 + q, 64) * p2;              // vae_nets.py:243-246
-    const float recon = 1.0f - out;
-    const double k = __shfl(t, 10, 64);
-    const float kld = Bd > 0 ? (float)(-0.5 * k / Bd) * kw : 0.0f;
-    if (lane == 0) { scalars[0] = recon + kld; scalars[1] = recon; scalars[2] = kld; }
-    if (lane < 5) scalars[3 + lane] = meanf;
-    else if (lane < 10) scalars[8 + l] = meanf;
-    else if (lane < 13) scalars[13 + lane - 10] = 0.f;
-    // autograd of the reference also differentiates the terms `prod(pow1[:-1] * pow2[-1])` never uses — mssim ** weights and
-    // mcs ** weights are evaluated for all five levels (vae_nets.py:243-244) — with an incoming gradient of exactly 0:
-    // 0 * w * x^(w-1), which is 0 for x > 0 but NaN for x < 0 (fractional power) and for x == 0 (0 * inf).  A negative
-    // ssim level 0..3 (dark real frames against an untrained decoder) or cs level 4 therefore turns EVERY gradient that passes
-    // through recon into NaN while the loss itself stays finite (tests/golden/step_real_b68.npz, "seed0/").  Same arithmetic
-    // here: the poison term is added to the level's coefficient.
-    const float poison = 0.0f * (wts[l] * powf(meanf, wts[l] - 1.0f));          // lanes 0-4: ssim_l, lanes 5-9: cs_l
-    const float p_ssim = __shfl(poison, l, 64), p_cs4 = __shfl(poison, 9, 64);
-    if (lane >= 5 && lane < 9) coef[l] = (float)((double)(-out * wts[l] / meanf) / cnt) + p_ssim;
-    if (lane == 4) coef[4] = (float)((double)(-out * 4.0f * wts[4] / meanf) / cnt) + p_cs4;
-}
-
 // REC (cross-rank path): no d_mu / d_logvar (a.d_mu is null), and the last arriver writes its 11 sums to a.rec instead of
 // finishing — msssim_finish_kernel finishes from the sums of all ranks
 template <bool REC>
@@ -912,6 +882,28 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
     const unsigned grid = (unsigned)((b.total4 + 255) / 256);
     if (width == 64) hipLaunchKernelGGL(msssim_bwd_kernel<64>, dim3(grid), dim3(256), 0, st, b);
     else hipLaunchKernelGGL(msssim_bwd_kernel<128>, dim3(grid), dim3(256), 0, st, b);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// what score.hip needs: where a values-only pyramid (launch_msssim, stage 1, no gradients) leaves its per-plane partial
+// pairs, a scratch region it never touches, and the finish step on a caller-held record
+// ------------------------------------------------------------------------------------------------
+// part[l]: float offset of level l's (ssim, cs) pairs, 3 planes per image in image order; *scratch: the level-0 field F,
+// which no kernel writes when d_img1 is null (3 * B * width^2 floats, 256-byte aligned like every slot)
+void msssim_score_slots(int width, int B, int64_t part[5], int64_t* scratch) {
+    const MsWs w = ms_carve(width, B);
+    for (int l = 0; l < 5; ++l) part[l] = w.part[l];
+    *scratch = w.F[0];
+}
+// msssim_finish_kernel on a pooled record: rec = 11 sums, *images = the image count they cover; writes CVAE_N_SCALARS
+// scalars and the 5 coefficients (coef: 8 floats of the caller's)
+int launch_msssim_finish_rec(int width, const double* rec, const double* images, float* scalars, float* coef, hipStream_t st) {
+    if (width != 64 && width != 128) { cvae_set_error("msssim: width %d unsupported", width); return -2; }
+    MsFinArgs f{};
+    f.rec = const_cast<double*>(rec); f.images = images; f.scalars = scalars; f.coef = coef;
+    hipLaunchKernelGGL(msssim_finish_kernel, dim3(1), dim3(256), 0, st, f, width);
     CVAE_CHECK_LAUNCH();
     return 0;
 }

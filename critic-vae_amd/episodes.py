@@ -171,6 +171,72 @@ class DeviceDataset(_CuratedDataset):
         return cls(frames, preds, source)
 
 
+def split_indices(source, fraction, seed=0):
+    """The index logic of split_by_trajectory on a host `source` array (N, >= 2) whose column 0 is the trajectory:
+    (train rows, val rows, val trajectories), rows in dataset order.  Trajectories are taken in the order of
+    np.random.default_rng(seed).permutation over the sorted trajectory indices until val holds at least fraction * N rows."""
+    source = np.asarray(source, np.int64)
+    if source.ndim != 2 or source.shape[1] < 2:
+        raise ValueError("source must be (N, >= 2): trajectory, frame, ...")
+    if not 0.0 < float(fraction) < 1.0:
+        raise ValueError(f"fraction {fraction!r} must lie in (0, 1)")
+    traj = source[:, 0]
+    ids, per = np.unique(traj, return_counts=True)
+    if ids.size < 2:
+        raise ValueError(f"a split by trajectory needs at least two trajectories, the dataset has {ids.size}")
+    order = np.random.default_rng(seed).permutation(ids.size)
+    need, have, taken = float(fraction) * traj.size, 0, []
+    for k in order:
+        if have >= need:
+            break
+        taken.append(int(ids[k]))
+        have += int(per[k])
+    if have == traj.size:
+        raise ValueError(f"holding out {fraction} of {traj.size} entries by whole trajectories leaves no training entry")
+    in_val = np.isin(traj, np.asarray(taken, np.int64))
+    return np.flatnonzero(~in_val), np.flatnonzero(in_val), sorted(taken)
+
+
+def subset_meta(source, names, sizes, counts, rows):
+    """Host bookkeeping of a subset of whole trajectories: (source, names, sizes, counts) of the entries `rows` (ascending
+    host indices).  names / sizes / counts keep the visited trajectories whose entries stayed, in their order, with sizes =
+    entries of the subset before each; a visited trajectory that contributed no entry belongs to neither half and is dropped."""
+    rows = np.asarray(rows, np.int64)
+    source = np.asarray(source, np.int64)
+    out_names, out_sizes, out_counts = [], [], []
+    for j, start in enumerate(sizes):
+        end = sizes[j + 1] if j + 1 < len(sizes) else len(source)
+        k = int(np.searchsorted(rows, start))
+        if end <= start or k >= rows.size or rows[k] != start:
+            continue
+        out_names.append(names[j])
+        out_sizes.append(k)
+        if len(counts) > j:
+            out_counts.append(counts[j])
+    return source[rows], out_names, out_sizes, np.asarray(out_counts, np.int64).reshape(-1, 3)
+
+
+def _subset(dataset, rows):
+    """`dataset` restricted to `rows`: the same class, frames / preds copied on the device, bookkeeping by subset_meta."""
+    rows = np.asarray(rows, np.int64)
+    idx = torch.from_numpy(rows).to(dataset.frames.device)
+    source, names, sizes, counts = subset_meta(dataset.source, dataset.names, dataset.sizes, dataset.counts, rows)
+    kw = dict(names=names, sizes=sizes, counts=counts if len(counts) else None)
+    if isinstance(dataset, ReconDataset):
+        kw["stats"] = dataset.stats
+    return type(dataset)(dataset.frames[idx].contiguous(), dataset.preds[idx].contiguous(), source, **kw)
+
+
+def split_by_trajectory(dataset, fraction, seed=0):
+    """(train, val) of a DeviceDataset or ReconDataset, each of the dataset's own class.  WHOLE trajectories are held out:
+    consecutive frames of a trajectory are near-duplicates, so a split by frame would put a validation frame's neighbours in
+    the training set and the held-out loss would measure memorisation.  Trajectories are taken in a seeded order
+    (split_indices) until val holds at least `fraction` of the entries; no trajectory index appears in both halves.
+    ValueError for fewer than two trajectories, a fraction outside (0, 1) or an empty half."""
+    tr, va, _ = split_indices(dataset.source, fraction, seed)
+    return _subset(dataset, tr), _subset(dataset, va)
+
+
 def _critic_values(critic, frames_u8, out, handle=None, x=None):
     """out[i] = critic.evaluate(preprocess_observation(frames_u8[i])) on the device, in pieces of the handle's max_batch."""
     if frames_u8.shape[1] != 64:

@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("CVAE_LIB") or os.path.join(_HERE, "libcvae_hip.so")  
 N_SCALARS = 16
 SYNC_DOUBLES = 2412      # CVAE_SYNC_DOUBLES: the fp64 record of the staged (global-statistics) step
 SYNC_POINTS = 9
+SCORE_COLS = 8            # CVAE_SCORE_COLS: floats per image row of cvae_score
+SCORE_STATE_DOUBLES = 24  # CVAE_SCORE_STATE_DOUBLES: the pooled fp64 record of cvae_score
 
 
 class CvaeError(RuntimeError):
@@ -89,6 +91,11 @@ _SIGS = {
     "cvae_backward_stage": (C.c_int, [_p, _i32] + [_p] * 12 + [_i32, _p]),
     "cvae_scale_loss_grads": (C.c_int, [_p, _i32] + [_p] * 8),
     "cvae_adam_step": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _f, _f, _f, _f, _f, _p]),
+    "cvae_score_cols": (_i32, []),
+    "cvae_score_state_bytes": (_i64, []),
+    "cvae_score_init": (C.c_int, [_p, _p, _p]),
+    "cvae_score": (C.c_int, [_p, _i32] + [_p] * 8),
+    "cvae_score_finish": (C.c_int, [_p, _i32, _p, _p, _p]),
     "cvae_guard_state_bytes": (_i64, []),
     "cvae_guard_init": (C.c_int, [_p, _p, _i64, _i64, _p]),
     "cvae_grad_stats": (C.c_int, [_p, _p, _i64, _f, _f, _i32, _f, _f, _f, _p, _p]),
@@ -312,6 +319,39 @@ class Handle:
     def adam_step(self, params, grads, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0):
         self._check(self.lib.cvae_adam_step(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(),
                                             step, lr, b1, b2, eps, grad_scale, _stream()))
+
+    # ---- per-image scores and the pooled record of a held-out set (include/cvae.h) ----
+    def score_cols(self):
+        return self.lib.cvae_score_cols()
+
+    def score_state_bytes(self):
+        return self.lib.cvae_score_state_bytes()
+
+    def score_state(self, device):
+        """A fresh pooled record on `device`: a float64 tensor of SCORE_STATE_DOUBLES values, initialised."""
+        state = torch.empty(self.lib.cvae_score_state_bytes() // 8, dtype=torch.float64, device=device)
+        self.score_init(state)
+        return state
+
+    def _score_ptr(self, state):
+        if state is None:
+            return None
+        ptr = _ptr64(state)
+        assert isinstance(state, int) or state.numel() * 8 >= self.lib.cvae_score_state_bytes(), "score state: too small"
+        return ptr
+
+    def score_init(self, state):
+        self._check(self.lib.cvae_score_init(self.h, self._score_ptr(state), _stream()))
+
+    def score(self, B, x, mu, logvar, recon, ws, per_image=None, state=None):
+        """Rows (B, SCORE_COLS) into `per_image` and / or the batch into the pooled record `state`."""
+        self._check(self.lib.cvae_score(self.h, B, _ptr(x), _ptr(mu), _ptr(logvar), _ptr(recon), _ptr(ws), _ptr(per_image),
+                                        self._score_ptr(state), _stream()))
+
+    def score_finish(self, state, scalars, width=None):
+        """The 16 loss scalars of everything pooled in `state` since score_init: cvae_loss of all of it as one batch."""
+        self._check(self.lib.cvae_score_finish(self.h, self.width if width is None else width, self._score_ptr(state),
+                                               _ptr(scalars), _stream()))
 
     # ---- the guarded step (include/cvae.h): statistics of the reduced gradient -> decision record -> Adam that obeys it ----
     def guard_state(self, device, applied=0, skipped=0):

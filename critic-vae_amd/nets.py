@@ -21,7 +21,7 @@ from torch import nn
 from . import layout as L
 from . import params as P
 from . import synth
-from .lib import Handle, N_SCALARS
+from .lib import Handle, N_SCALARS, SCORE_COLS
 
 
 class _ForwardFn(torch.autograd.Function):
@@ -315,6 +315,30 @@ class VariationalAutoencoder(nn.Module):
         """vae_nets.py:42-46."""
         mu, _ = self.encoder(x)
         return self.decoder(mu, pred.view(1), evalu=True)
+
+    def score(self, x, pred):
+        """Per-image scores of held-out frames (cvae_score, include/cvae.h): the eval-mode forward with z = mu (eps = 0) —
+        BatchNorm on its running statistics, bn_state and num_batches_tracked untouched — then one row of SCORE_COLS values per
+        image: total, MSSIM of the image alone, weighted KLD, mse, max |recon - x|, ssim level 0, ssim level 4, 0.
+        x (N,3,w,w), pred (N) or (N,1); N may exceed max_batch (pieces of max_batch).  Returns the (N, 8) device tensor."""
+        x = self._prep(x)
+        N, dev = x.shape[0], x.device
+        pred = pred.to(torch.float32).reshape(N, 1).contiguous()
+        rows = torch.empty(N, SCORE_COLS, device=dev)
+        mb = min(N, self.max_batch)
+        mu = torch.empty(mb, P.latent_dim, device=dev)
+        logvar = torch.empty_like(mu)
+        zero = torch.zeros_like(mu)
+        recon = torch.empty(mb, P.ch, self.width, self.width, device=dev)
+        with torch.no_grad():
+            for s in range(0, N, self.max_batch):
+                n = min(N - s, self.max_batch)
+                ws = self._workspace(n)
+                self.handle.forward(n, x[s:s + n], pred[s:s + n], zero[:n], self.theta, self.bn_state, mu[:n], logvar[:n], recon[:n],
+                                    ws, train=False)
+                self.handle.score(n, x[s:s + n], mu[:n], logvar[:n], recon[:n], ws, rows[s:s + n], None)
+            self._stamp_workspace()
+        return rows
 
     def diff_images(self, x, pred, one=False):
         """get_diff_image (vae_utility.py:256-277) for a whole batch at once: the encoder runs once,

@@ -28,7 +28,7 @@ import torch
 
 from . import params as P
 from . import synth
-from .lib import SYNC_DOUBLES, SYNC_POINTS
+from .lib import N_SCALARS, SCORE_COLS, SYNC_DOUBLES, SYNC_POINTS
 from .nets import VariationalAutoencoder
 
 
@@ -134,6 +134,9 @@ class FusedTrainer:
         self.m = torch.zeros(n, device=dev)
         self.v = torch.zeros(n, device=dev)
         self.step_count = 0
+        self.val_history = []             # (step_count, result of evaluate()) per evaluation that fit_device(val=...) ran
+        self.best_val = None              # the lowest finite pooled validation total_loss seen (the CLI's --keep-best / --patience)
+        self.val_stale = 0                # evaluations in a row since it last improved
         B = vae.max_batch
         self.mu = torch.empty(B, P.latent_dim, device=dev)
         self.logvar = torch.empty_like(self.mu)
@@ -311,7 +314,9 @@ class FusedTrainer:
         shuffles and eps from are not saved."""
         applied, skipped = self._guard_read() if self.guarded else (self.step_count, 0)
         return {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(), "step_count": int(self.step_count),
-                "applied": applied, "skipped": skipped, "num_batches_tracked": int(self.vae.num_batches_tracked)}
+                "applied": applied, "skipped": skipped, "num_batches_tracked": int(self.vae.num_batches_tracked),
+                "val_history": [(int(t), dict(r)) for t, r in self.val_history], "best_val": self.best_val,
+                "val_stale": int(self.val_stale)}
 
     def load_state_dict(self, state):
         if state["m"].numel() != self.m.numel() or state["v"].numel() != self.v.numel():
@@ -324,6 +329,9 @@ class FusedTrainer:
         self.v.copy_(state["v"])
         self.step_count = steps
         self.vae.num_batches_tracked = int(state["num_batches_tracked"])
+        self.val_history = [(int(t), dict(r)) for t, r in state.get("val_history", [])]      # absent in states written before validation existed
+        self.best_val = state.get("best_val")
+        self.val_stale = int(state.get("val_stale", 0))
         if self.guarded:
             self._guard_write(applied, skipped)
 
@@ -344,22 +352,91 @@ class FusedTrainer:
                 scal = self.step(images, preds, eps)
         return scal
 
-    def fit_device(self, dataset, batch_size, epochs=1, generator=None, shuffle=True):
-        """The loop of fit_u8 over a DeviceDataset (episodes.py) that already lives on the device with its critic values:
-        per epoch np.random.shuffle of the host indices (uploaded once), slices of batch_size with the ragged last batch
-        kept, eps ~ N(0,1) from `generator`; each batch is one cvae_preprocess_u8_gather launch (x = frames[idx] / 255,
-        pred = preds[idx]) and step() — no host gather, no PCIe copy, no critic launch.  A ReconDataset (fp32 entries, the
-        second VAE's training set) runs the identical loop with cvae_gather_f32 as the batch launch.  Returns the last step's
-        scalars."""
+    def _check_dataset(self, dataset, batch_size):
         dev = self.vae.theta.device
-        n = len(dataset)
         if dataset.width != self.vae.width:
             raise ValueError(f"the dataset holds {dataset.width}x{dataset.width} frames, the VAE takes {self.vae.width}x{self.vae.width}")
         if not 1 <= int(batch_size) <= self.h.max_batch:
             raise ValueError(f"batch_size {batch_size} outside 1..max_batch ({self.h.max_batch}) of the handle")
         if dataset.frames.device != dev:
             raise ValueError(f"the dataset is on {dataset.frames.device}, the VAE on {dev}")
-        B = int(batch_size)
+        return dev, int(batch_size)
+
+    def evaluate(self, dataset, batch_size, per_image=False):
+        """The model on a held-out DeviceDataset / ReconDataset: per batch one gather launch, the EVAL-mode forward (BatchNorm
+        on its running statistics, z = mu, i.e. eps = 0, the entries' own critic values) and cvae_score into ONE pooled device
+        record; the host reads once, at the end.  Returns a dict of host values:
+          total_loss, recon_loss, KLD, ssim_levels (5), cs_levels (5): POOLED — the scalars cvae_loss would give had the whole
+            set been one batch (global level means over all images, KLD mean over all images); not a mean of batch losses, so
+            the value does not depend on batch_size;
+          images, finite_images: entries seen, and those whose per-image total is finite (a negative per-image level mean makes
+            an image's MS-SSIM NaN, as in the reference; such an image is counted, not hidden);
+          mean_total, mean_msssim, mean_kld, mean_mse: means of the per-image scores over the finite images; psnr = 10 log10(1 /
+            mean_mse) (frames in [0, 1]); worst: the largest finite per-image total;
+          per_image (only with per_image=True): the (N, 8) device tensor of cvae_score's rows, in dataset order.
+        Draws nothing from any random generator and leaves parameters, Adam state, bn_state, num_batches_tracked, step_count
+        and the guard record untouched; it overwrites the workspace and the trainer's mu / logvar / recon buffers, which a
+        step() rewrites before reading.  With world_size > 1 every rank evaluates the dataset IT is given and no collective
+        runs: give every rank the same set (identical results on identical replicas) or reduce the per-rank results yourself."""
+        dev, B = self._check_dataset(dataset, batch_size)
+        v, h, n = self.vae, self.h, len(dataset)
+        if n < 1:
+            raise ValueError("evaluate(): the dataset is empty")
+        x = torch.empty(B, P.ch, v.width, v.width, device=dev)
+        pred = torch.empty(B, 1, device=dev)
+        zero = torch.zeros(B, P.latent_dim, device=dev)
+        rows = torch.empty(n, SCORE_COLS, device=dev) if per_image else None
+        state = h.score_state(dev)
+        d_idx = torch.arange(n, dtype=torch.int64, device=dev)
+        theta = v.theta.data
+        v._stamp_workspace()
+        for b in range(0, n, B):
+            nb = min(B, n - b)
+            dataset.gather(h, nb, d_idx[b:b + nb], x[:nb], pred[:nb])
+            h.forward(nb, x[:nb], pred[:nb], zero[:nb], theta, v.bn_state, self.mu, self.logvar, self.recon, self.ws, train=False)
+            h.score(nb, x[:nb], self.mu, self.logvar, self.recon, self.ws, None if rows is None else rows[b:b + nb], state)
+        scal = torch.empty(N_SCALARS, device=dev)
+        h.score_finish(state, scal)
+        host = torch.cat([state[:18], scal.to(torch.float64)]).cpu().numpy()        # the one host read
+        rec, sc = host[:18], host[18:]
+        fin = int(rec[12])
+        mean = (lambda k: float(rec[k] / fin)) if fin else (lambda k: float("nan"))
+        out = {"total_loss": float(sc[0]), "recon_loss": float(sc[1]), "KLD": float(sc[2]),
+               "ssim_levels": [float(t) for t in sc[3:8]], "cs_levels": [float(t) for t in sc[8:13]],
+               "images": int(rec[11]), "finite_images": fin,
+               "mean_total": mean(13), "mean_msssim": mean(14), "mean_kld": mean(15), "mean_mse": mean(16),
+               "worst": float(rec[17]) if fin else float("nan")}
+        out["psnr"] = float(10.0 * np.log10(1.0 / out["mean_mse"])) if fin and out["mean_mse"] > 0 else float("inf" if fin else "nan")
+        if per_image:
+            out["per_image"] = rows
+        return out
+
+    def _validate(self, val, batch_size, on_val):
+        """One evaluation inside fit_device: history entry, callback; True = the callback asked to stop."""
+        result = self.evaluate(val, min(int(batch_size), self.h.max_batch))
+        self.val_history.append((int(self.step_count), result))
+        return bool(on_val(self, result)) if on_val is not None else False
+
+    def fit_device(self, dataset, batch_size, epochs=1, generator=None, shuffle=True, val=None, val_every=None, on_val=None):
+        """The loop of fit_u8 over a DeviceDataset (episodes.py) that already lives on the device with its critic values:
+        per epoch np.random.shuffle of the host indices (uploaded once), slices of batch_size with the ragged last batch
+        kept, eps ~ N(0,1) from `generator`; each batch is one cvae_preprocess_u8_gather launch (x = frames[idx] / 255,
+        pred = preds[idx]) and step() — no host gather, no PCIe copy, no critic launch.  A ReconDataset (fp32 entries, the
+        second VAE's training set) runs the identical loop with cvae_gather_f32 as the batch launch.  Returns the last step's
+        scalars.
+        val: a held-out dataset of the same kind (episodes.split_by_trajectory).  It is evaluated (evaluate(val, batch_size))
+        after every `val_every` optimizer steps — default: at the end of every epoch —, (step_count, result) is appended to
+        self.val_history and on_val(trainer, result) is called; a true return value ends the fit there.  The evaluation draws
+        no random number and touches no training state, so the training run is bit for bit the one without it.  val=None:
+        the loop and its launches are exactly the ones above."""
+        dev, B = self._check_dataset(dataset, batch_size)
+        n = len(dataset)
+        if val is not None:
+            self._check_dataset(val, batch_size)
+            if val_every is not None and int(val_every) < 1:
+                raise ValueError(f"val_every {val_every!r}: a positive number of optimizer steps, or None for once per epoch")
+        elif val_every is not None or on_val is not None:
+            raise ValueError("val_every / on_val need val, the held-out dataset")
         x = torch.empty(B, P.ch, self.vae.width, self.vae.width, device=dev)
         pred = torch.empty(B, 1, device=dev)
         scal = None
@@ -373,6 +450,11 @@ class FusedTrainer:
                 dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], pred[:nb])
                 eps = torch.randn(nb, P.latent_dim, device=dev, generator=generator)
                 scal = self.step(x[:nb], pred[:nb], eps)
+                if val is not None and val_every is not None and self.step_count % int(val_every) == 0 \
+                        and self._validate(val, B, on_val):
+                    return scal
+            if val is not None and val_every is None and self._validate(val, B, on_val):
+                return scal
         return scal
 
     # time between "backward is done" and "the reduced gradient is usable" on the compute stream = the part
@@ -449,7 +531,8 @@ def load_trainer(trainer, path):
     return trainer
 
 
-def main(argv=None):
+def build_parser():
+    """The command line of this module (main() parses with it; host tests read it without a GPU)."""
     ap = argparse.ArgumentParser(description="Critic-VAE -train on synthetic frames (vae.py:154-163)")
     ap.add_argument("--save", metavar="DIR", default=None,
                     help="write DIR/vae_encoder.pt and DIR/vae_decoder.pt when training ends (vae.py:162-163; the reference's "
@@ -498,9 +581,34 @@ def main(argv=None):
                     "norm C (torch.nn.utils.clip_grad_norm_)")
     ap.add_argument("--resume", metavar="DIR", default=None, help=f"fused trainer: continue from DIR's network files and {TRAINER_FILE} "
                     "(what --save wrote)")
+    ap.add_argument("--val-fraction", type=float, default=None, metavar="F", help="fused trainer: hold out whole trajectories until "
+                    "they make up at least F of the curated entries (episodes.split_by_trajectory, seeded by --seed) and evaluate on them")
+    ap.add_argument("--val-every", type=int, default=None, metavar="N", help="with --val-fraction: evaluate after every N optimizer "
+                    "steps (default: at the end of every epoch)")
+    ap.add_argument("--keep-best", action="store_true", help="with --val-fraction and --save DIR: write the network files under "
+                    "DIR/best/ whenever the pooled validation total_loss improves (a non-finite value never does)")
+    ap.add_argument("--patience", type=int, default=None, metavar="K", help="with --val-fraction: stop after K evaluations in a row "
+                    "without an improvement")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.max_grad_norm is not None and not args.max_grad_norm > 0:
         ap.error("--max-grad-norm needs a positive number")
+    if args.val_fraction is None:
+        if args.val_every is not None or args.keep_best or args.patience is not None:
+            ap.error("--val-every, --keep-best and --patience need --val-fraction")
+    else:
+        if not 0.0 < args.val_fraction < 1.0:
+            ap.error("--val-fraction needs a number in (0, 1)")
+        if (args.val_every is not None and args.val_every < 1) or (args.patience is not None and args.patience < 1):
+            ap.error("--val-every and --patience need positive integers")
+        if args.keep_best and args.save is None:
+            ap.error("--keep-best needs --save DIR (the best networks go to DIR/best/)")
+        if not (args.second or (args.train and args.episodes is not None)):
+            ap.error("--val-fraction belongs to the fused trainer (-train --episodes, -second)")
     if args.train + args.dataset_mode + args.second + args.critic_mode != 1:
         ap.error("exactly one of -train, -dataset, -second, -critic (segment.py has -video [-thresh] [--second]); see SURVEY.md §8 for scope")
     if args.critic_mode:
@@ -568,8 +676,16 @@ def _fit_and_save(args, vae, ds, second):
         print(f"resumed from {args.resume} at step {trainer.step_count}")
     gen = torch.Generator(device=vae.theta.device)
     gen.manual_seed(args.seed)
+    val_kw = {}
+    if args.val_fraction is not None:
+        from .episodes import split_by_trajectory
+        n_all = len(ds)
+        ds, val = split_by_trajectory(ds, args.val_fraction, seed=args.seed)
+        print(f"held out {len(val)} of {n_all} entries ({len(val.names) or len(np.unique(val.source[:, 0]))} whole trajectories); "
+              f"training on {len(ds)}")
+        val_kw = dict(val=val, val_every=args.val_every, on_val=_ValidationLog(args, second))
     t0 = time.time()
-    scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen)
+    scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen, **val_kw)
     torch.cuda.synchronize()
     dt = time.time() - t0
     s = scal.cpu().numpy()
@@ -583,6 +699,35 @@ def _fit_and_save(args, vae, ds, second):
         st = trainer.guard_stats()
         print(f"guard: {st['applied']} steps applied, {st['skipped']} skipped")
     return ds
+
+
+BEST_DIR = "best"
+
+
+class _ValidationLog:
+    """on_val of the command line: one line per evaluation, --keep-best and --patience.  The best value and the count of
+    evaluations since it improved live in the trainer (best_val, val_stale: saved and resumed with it); a non-finite pooled
+    loss never counts as an improvement."""
+
+    def __init__(self, args, second):
+        self.args, self.second = args, second
+
+    def __call__(self, trainer, r):
+        loss = r["total_loss"]
+        better = np.isfinite(loss) and (trainer.best_val is None or loss < trainer.best_val)
+        print(f"val @ step {trainer.step_count}: loss {loss:.6f} (recon {r['recon_loss']:.6f}, kld {r['KLD']:.6f}) over {r['images']} images, "
+              f"{r['images'] - r['finite_images']} non-finite; per image: mean {r['mean_total']:.6f} worst {r['worst']:.6f} "
+              f"psnr {r['psnr']:.2f} dB{' *' if better else ''}")
+        if better:
+            trainer.best_val, trainer.val_stale = float(loss), 0
+            if self.args.keep_best:
+                save_networks(trainer.vae, os.path.join(self.args.save, BEST_DIR), second=self.second)
+        else:
+            trainer.val_stale += 1
+        if self.args.patience is not None and trainer.val_stale >= self.args.patience:
+            print(f"no improvement in {trainer.val_stale} evaluations: stopping at step {trainer.step_count}")
+            return True
+        return False
 
 
 def _load_critic(spec, handle, seed, device):

@@ -111,6 +111,42 @@ int cvae_loss(cvae_handle h, int32_t batch, const float* x, const float* mu, con
               float* d_logvar, void* stream);
 
 /*
+ * Per-image scores and the pooled loss of a held-out set (no reference counterpart: vae.py never evaluates; the values are the
+ * reference's own MSSIM.forward (vae_nets.py:217-247) and KLD (:57-60) applied per image and to the whole set).
+ *
+ * cvae_score runs the MS-SSIM pyramid WITHOUT its derivative passes, then one launch that scores every image of the batch.
+ * per_image_or_null: (batch, cvae_score_cols() = CVAE_SCORE_COLS = 8) floats, row i:
+ *   [0] total = [1] + [2], exactly that fp32 sum
+ *   [1] MSSIM.forward(recon[i:i+1], x[i:i+1]): 1 - prod_{l<4}(cs_l^w_l * ssim_4^w_4) over THIS image's level means (each over
+ *       3 * S_l^2 values), with the code cvae_loss runs at batch 1 (equal to 1e-6); a negative used level mean gives NaN, as there
+ *   [2] 0.001 * (-0.5 * sum_j (1 + logvar - mu^2 - exp(logvar))) of row i
+ *   [3] mean over the 3 * W * W elements of (recon - x)^2      (differences and squares fp32, sum fp64)
+ *   [4] max |recon - x|                                        (NaN if a difference is NaN)
+ *   [5] this image's level-0 ssim mean      [6] its level-4 ssim mean      [7] reserved, written as 0
+ * state_or_null: the pooled record, cvae_score_state_bytes() = 8 * CVAE_SCORE_STATE_DOUBLES bytes, 8-byte aligned, fp64:
+ *   [0..4] ssim sums of levels 0..4, [5..9] cs sums, [10] the KLD sum — over every image since cvae_score_init
+ *   [11]   images seen                     [12] images whose [0] is finite
+ *   [13..16] sums of [0], [1], [2], [3] over the finite images        [17] maximum of [0] over them (-inf: none yet)
+ *   [18..23] library scratch (the arrival counter of the pooling step lives here: do not write between calls)
+ * cvae_score_init writes the record once; every cvae_score with a state ADDS its batch: the 11 sums as the cross-rank path
+ * records them, the rows in a fixed order by the last workgroup to arrive.  No floating-point atomics, nothing depends on the order
+ * of arrival: the same calls give the same bits.  At least one of per_image / state must be given; x and recon 16-byte aligned;
+ * ws: cvae_workspace_bytes(h, batch), contents on entry irrelevant (the call overwrites the MS-SSIM region: not between a
+ * cvae_forward and its cvae_backward).  cvae_score_finish writes the CVAE_N_SCALARS loss scalars of the pooled set — what
+ * cvae_loss would give had every image since the init been ONE batch (global level means, KLD mean over all images) — with the
+ * finish step of the cross-rank path; width: 64 or 128, the width of the frames pooled.  An empty record gives NaN scalars.
+ * Every argument is checked before any device access; nothing allocates or synchronises.
+ */
+#define CVAE_SCORE_COLS 8
+#define CVAE_SCORE_STATE_DOUBLES 24
+int32_t cvae_score_cols(void);
+int64_t cvae_score_state_bytes(void);
+int cvae_score_init(cvae_handle h, void* state, void* stream);
+int cvae_score(cvae_handle h, int32_t batch, const float* x, const float* mu, const float* logvar, const float* recon,
+               void* ws, float* per_image_or_null, void* state_or_null, void* stream);
+int cvae_score_finish(cvae_handle h, int32_t width, void* state, float* scalars, void* stream);
+
+/*
  * Backward: loss.backward() (vae.py:57) for everything cvae_forward computed, given the loss
  * gradients w.r.t. its outputs (and logvar/recon as returned by cvae_forward).  Overwrites the
  * flat gradient buffer `grads` (same layout as `params`).
