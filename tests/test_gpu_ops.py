@@ -159,7 +159,8 @@ def test_conv_fwd_d0_image_major_tiles(H, B):
     check(to_nchw(out, B, h, cout), ref, "conv_fwd L4 (ragged image groups)")
 
 
-BN_CASES = [(W, B, ties) for W in (64, 128) for B, ties in [(3, False), (8, True), (5, "tiny_gamma")]]
+# (64, 33), (128, 9): conv-emitted partials past the 32 chunks of bn_fwd_reduce and partial rows past the 64 of launch_col_reduce_partial
+BN_CASES = [(W, B, ties) for W in (64, 128) for B, ties in [(3, False), (8, True), (5, "tiny_gamma")]] + [(64, 33, False), (128, 9, False)]
 
 
 @pytest.mark.parametrize("layer", range(4))

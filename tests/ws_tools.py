@@ -513,3 +513,236 @@ def check_bf16_stored_operands(h, tr, B, x, pred, eps, theta, bn_before, bn_afte
             da_ = F.conv_transpose2d(dy, bf(ref[wk]), padding=2)
             close(act(f"d_a{l - 1}", ci, s), da_, f"d_a{l - 1}", 2.0 ** -8)
     return worst
+
+
+# ---- BatchNorm / pool / activation (bn.hip, reduce.hip): launch geometry, term counts, inputs and float64 references ----
+BN_CH = (32, 64, 128, 256)        # channels of the four encoder blocks; their conv output is 64, 32, 16, 8 pixels wide at 64 x 64 frames
+TANH_ULPS = 5                     # tanhf of the device library: the OpenCL bound it is built to; an fp32 ulp is at most 2 U32 |v|
+DY_ULPS = 6                       # bn_bwd_kernel<.., 1>: the longest chain of roundings a term of dy passes through (test_gpu_bn_ops.py)
+XS_ULPS = 8                       # bn_bwd_stats_relu_kernel: roundings behind the numerator and 1 / gamma of xhat = (a - beta) (1 / gamma)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def bn_layer(layer, W):
+    """(C, H) of encoder block `layer` at W x W frames: bn_geom."""
+    return BN_CH[layer], (64 >> layer) * (W // 64)
+
+
+def bn_part_geom(layer, H):
+    """(images per tile, pixels per image, tiles per image) of the partials a block's conv emits: part_geom / tile_geom."""
+    if layer == 0:
+        return 1, 512, (H // 16) * (H // 32)
+    tw = min(H, 32)
+    th = min(128 // tw, H)
+    return 128 // (tw * th), tw * th, (H // tw) * (H // th)
+
+
+def bn_num_tiles(layer, H, B):
+    imgs, _, tpi = bn_part_geom(layer, H)
+    return _cdiv(B, imgs) * tpi
+
+
+def bn_fwd_chunks(num_tiles):
+    """(tiles per chunk, chunks) of bn_fwd_reduce: tpb = cdiv(numTiles, 32), RA = cdiv(numTiles, tpb)."""
+    tpb = _cdiv(num_tiles, 32)
+    return tpb, _cdiv(num_tiles, tpb)
+
+
+def bn_bwd_blocks(total_px, C):
+    """Workgroups of the backward passes: at least 8 pooled pixels per thread, between 1 and 1024."""
+    return max(1, min(1024, total_px // ((256 // C) * 8)))
+
+
+def bn_bwd_ppb(total_px, C):
+    """Pooled pixels per workgroup of the backward passes."""
+    return _cdiv(total_px, bn_bwd_blocks(total_px, C))
+
+
+def bn_sweep_items(cus):
+    """Items one sweep of bn_pool_act_fwd's grid covers: 16 workgroups of 256 threads per compute unit."""
+    return 16 * cus * 256
+
+
+def bn_width(bf16, apply=False):
+    """Channels per thread (BnWidth): W of the forward and the ReLU statistics, WB of bn_bwd_kernel (apply = True)."""
+    return 8 if bf16 else (1 if apply else 4)
+
+
+def bn_facts(W, layer, B, bf16, cus=256):
+    """Every batch-dependent launch decision of one (frame size, block, batch, storage type)."""
+    C, H = bn_layer(layer, W)
+    imgs, ppi, tpi = bn_part_geom(layer, H)
+    nt = bn_num_tiles(layer, H, B)
+    tpb, RA = bn_fwd_chunks(nt)
+    px = B * (H // 2) ** 2
+    nblk, ppb = bn_bwd_blocks(px, C), bn_bwd_ppb(px, C)
+    total = px * C // bn_width(bf16)
+    return dict(C=C, H=H, N=B * H * H, imgs=imgs, ppi=ppi, tpi=tpi, tiles=nt, tpb=tpb, RA=RA, last_chunk=nt - (RA - 1) * tpb,
+                last_ni=B - (_cdiv(B, imgs) - 1) * imgs, px=px, nblk=nblk, ppb=ppb, live=_cdiv(px, ppb), total=total,
+                sweeps=_cdiv(total, bn_sweep_items(cus)))
+
+
+# the edges of ISSUE / LABNOTES, each as a predicate on bn_facts; a case runs at the smallest batch that meets it ("below": the largest
+# batch that does not) and asserts it again on the device it runs on
+BN_EDGES = {
+    "n64": lambda f: f["N"] == 64,                                              # the smallest count: N / (N - 1) at its largest
+    "one-tile": lambda f: f["tiles"] == 1 and f["last_ni"] == f["imgs"],
+    "rows64": lambda f: f["nblk"] == 64,                                        # 64 partial rows: straight into the finalize
+    "rows65": lambda f: f["nblk"] > 64,                                         # rows_sum_kernel first, ragged last chunk; rows_sum_1024
+    "tiles32": lambda f: f["tiles"] == 32 and f["tpb"] == 1,                    # the last batch inside 32 one-tile chunks
+    "tiles33": lambda f: f["tiles"] > 32,                                       # two tiles per chunk, RA < 32
+    "wrap": lambda f: f["tpb"] >= 9,                                            # the eight row groups take a second tile
+    "sweep": lambda f: f["sweeps"] > 1,                                         # the forward's grid-stride loop runs
+}
+BN_BELOW = {"below-sweep": "sweep"}
+# (W, layer, edge, storage types)
+BN_CASES = ([(64, 3, e, ("f32", "bf16")) for e in ("n64", "one-tile", "rows64", "rows65", "tiles32", "tiles33", "wrap")]
+            + [(64, 0, e, ("f32", "bf16")) for e in ("rows64", "rows65", "wrap")]
+            + [(64, 2, e, ("f32", "bf16")) for e in ("tiles32", "tiles33", "wrap")]
+            + [(64, 1, "tiles33", ("f32", "bf16"))]
+            + [(128, l, e, ("f32", "bf16")) for l in (0, 3) for e in ("below-sweep", "sweep")]
+            + [(64, 2, "tiles33", ("bf16x6",))])
+
+
+def bn_case_batch(W, layer, edge, bf16, cus=256):
+    """The batch of a case: the smallest that meets the edge's predicate, or the largest below it."""
+    pred = BN_EDGES[BN_BELOW.get(edge, edge)]
+    B = next(b for b in range(1, 1 << 14) if pred(bn_facts(W, layer, b, bf16, cus)))
+    return B - 1 if edge in BN_BELOW else B
+
+
+def bn_assert_edge(W, layer, edge, B, bf16, cus):
+    """The case still sits on the edge it is named for, on this device's compute-unit count."""
+    f = bn_facts(W, layer, B, bf16, cus)
+    if edge in BN_BELOW:
+        ok = not BN_EDGES[BN_BELOW[edge]](f) and BN_EDGES[BN_BELOW[edge]](bn_facts(W, layer, B + 1, bf16, cus))
+    else:
+        ok = BN_EDGES[edge](f)
+    assert ok, f"{W} x {W}, block {layer}, B = {B}: not on the edge '{edge}' with {cus} compute units: {f}"
+    return f
+
+
+def _rows_chain(R, finalize):
+    """Additions a workgroup's partial row passes through on its way to the channel sum.  finalize: launch_col_reduce_partial
+    (rows_sum_kernel above 64 rows: cdiv(rpb, 8) rows per row group, then the 8 LDS rows) and bn_bwd_finalize_kernel (cdiv(R, 16) rows
+    per lane, 4 shuffle levels); else launch_col_reduce (rows_sum_1024_kernel for 64 < R <= 2048: cdiv(R, 32) rows per lane, then the 32
+    LDS rows; one rows_sum_kernel workgroup up to 64 rows)."""
+    if finalize:
+        n = 0
+        if R > 64:
+            rpb = _cdiv(R, 32)
+            n, R = _cdiv(rpb, 8) + 8, _cdiv(R, rpb)
+        return n + _cdiv(R, 16) + 4
+    assert R <= 2048
+    return _cdiv(R, 32) + 32 if R > 64 else _cdiv(R, 8) + 8
+
+
+def bn_bwd_chain(nblk, ppb, C, V, finalize, per_px=1):
+    """n of the (n + c) 2^-24 sum |terms| bounds: the longest chain of additions a term of a backward sum passes through in this
+    launch.  A thread owns V channels and every NSUB-th pixel of its workgroup's ppb (NSUB = 256 / (C / V)), per_px additions each;
+    then the NSUB LDS rows in series; then the rows of reduce.hip (_rows_chain)."""
+    nsub = 256 // (C // V)
+    return _cdiv(ppb, nsub) * per_px + nsub + _rows_chain(nblk, finalize)
+
+
+def bn_windows(t, B, H, C):
+    """(B, H, H, C) -> (B, H/2, H/2, 4, C): the 2x2 windows in the kernels' scan order (0,0) (0,1) (1,0) (1,1)."""
+    return t.reshape(B, H // 2, 2, H // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H // 2, H // 2, 4, C)
+
+
+def bn_gen_y(gen, layer, W, B, bf16, device="cpu"):
+    """y (B, H, H, C) fp32 whose four values in every pooling window differ by at least 2^-6, per channel: 2^-6 times (a per-window
+    integer offset + a random permutation of {0, 2, 4, 6} + a per-channel shift), |y| < 2, so every value has at most 8 significant
+    bits (bf16-representable); fp32 storage adds a jitter in [0, 2^-6) below that, which keeps neighbours 2^-6 apart."""
+    C, H = bn_layer(layer, W)
+    HO = H // 2
+    off = torch.randint(-90, 85, (B, HO, HO, 1, C), generator=gen, device=device)
+    perm = torch.rand((B, HO, HO, 4, C), generator=gen, device=device).argsort(dim=3) * 2
+    shift = torch.randint(-20, 21, (C,), generator=gen, device=device)
+    k = (off + perm + shift).float()
+    if not bf16:
+        k = k + torch.rand(k.shape, generator=gen, device=device)
+    k = k / 64.0
+    return k.reshape(B, HO, HO, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, H, C).contiguous()
+
+
+def bn_gen_params(gen, C, device="cpu"):
+    """gamma with |gamma| in [0.5, 1.5], every third channel negative; beta in [-0.5, 0.5]; running_mean in [-0.3, 0.3], running_var
+    in [0.5, 1.5]."""
+    u = lambda lo, hi: torch.rand(C, generator=gen, device=device) * (hi - lo) + lo      # noqa: E731
+    gamma = u(0.5, 1.5)
+    gamma[::3] *= -1
+    return gamma, u(-0.5, 0.5), u(-0.3, 0.3), u(0.5, 1.5)
+
+
+def synth_bn_partials(y, layer, B, n_floats=None):
+    """The conv epilogue's BatchNorm partials, built from the stored y (B, H, H, C) widened to float64: row t holds the sum of
+    ni * pxPerImg pixels of images img0 .. img0 + ni - 1, img0 = (t // tilesPerImg) * imgsPerTile (the images' pixels in storage
+    order, cut into tilesPerImg equal runs: any partition with those counts is valid, the Chan merge only needs the counts), row
+    numTiles + t their M2 about that row's own mean; each rounded once to fp32.  Returns the fp32 buffer (n_floats long, default
+    2 numTiles C; whatever lies behind the rows holds ALL_ONES) and the float64 (sum, M2, count) per row."""
+    C, H = y.shape[3], y.shape[1]
+    imgs, ppi, tpi = bn_part_geom(layer, H)
+    nt = bn_num_tiles(layer, H, B)
+    y64 = y.double().reshape(B, H * H, C)
+    sums, m2s, cnt = [], [], []
+    full = B // imgs
+    for i0, groups, ni in ((0, full, imgs), (full * imgs, 1 if B % imgs else 0, B % imgs)):
+        if groups == 0:
+            continue
+        v = y64[i0:i0 + groups * ni].reshape(groups, ni, tpi, ppi, C).permute(0, 2, 1, 3, 4).reshape(groups * tpi, ni * ppi, C)
+        s = v.sum(1)
+        sums.append(s)
+        m2s.append(((v - (s / (ni * ppi))[:, None]) ** 2).sum(1))
+        cnt.append(torch.full((groups * tpi,), float(ni * ppi), dtype=torch.float64, device=y.device))
+    s, m2, cnt = torch.cat(sums).float(), torch.cat(m2s).float(), torch.cat(cnt)
+    assert s.shape == (nt, C)
+    n_floats = 2 * nt * C if n_floats is None else n_floats
+    part = torch.empty(n_floats, device=y.device)
+    if y.is_cuda:
+        poison(part, ALL_ONES)
+    else:
+        part.view(torch.int32).fill_(-1)
+    part[:nt * C] = s.reshape(-1)
+    part[nt * C:2 * nt * C] = m2.reshape(-1)
+    return part, s.double(), m2.double(), cnt
+
+
+def bn_stats_ref(y, s, m2, cnt):
+    """float64 batch statistics of the stored y and the bounds the fp32 roundings of the partials allow (the merge itself runs in fp64:
+    2^-45 of the summed terms covers it).  mean: each s_t carries U32 |s_t|, the cast U32 |mu|.  var = (sum m_t + sum s_t^2 / n_t - S^2 / N)
+    / N: d var / d s_t = 2 (s_t / n_t - mu) / N, m_t carries U32 m_t, the cast U32 var.  Returns mean, var, mean bound, var bound."""
+    N = cnt.sum()
+    y64 = y.double().reshape(-1, y.shape[-1])
+    mu, var = y64.mean(0), y64.var(0, unbiased=False)
+    sa, n_t = s.abs().sum(0), cnt[:, None]
+    mb = U32 * (sa / N + mu.abs()) + 2.0 ** -45 * sa / N
+    vb = (U32 * (m2.sum(0) + (2 * (s / n_t - mu).abs() * s.abs()).sum(0)) / N + U32 * var
+          + 2.0 ** -45 * (m2.sum(0) + (s * s / n_t).sum(0)) / N)
+    return mu, var, mb, vb
+
+
+def bn_first_max(nw):
+    """Position of the first maximum along dim 3 (the kernels' and ATen's tie rule), whatever torch.argmax does with ties."""
+    top = nw.max(dim=3, keepdim=True).values
+    rank = torch.tensor([4, 3, 2, 1], device=nw.device).view(1, 1, 1, 4, 1)
+    return ((nw == top) * rank).argmax(dim=3, keepdim=True)
+
+
+def bn_fwd_ref(yw, coef, tanh, bf16):
+    """float64 a = act(max over the window of y scale + shift) from the coefficients the kernel returned, and its bound: one fma
+    rounding of |n| (the largest of the window), TANH_ULPS ulps of tanhf (Tanh block), one bf16 rounding of the result (bf16 storage),
+    and the rounding of this float64 evaluation itself (the fma can sit on its bound exactly).
+    yw (B, HO, HO, 4, C) float64, coef (C, 4) float64.  Returns a, bound, n (the window's normalised values), first-max position."""
+    nw = yw * coef[:, 0] + coef[:, 1]
+    pos = bn_first_max(nw)
+    top = nw.gather(3, pos)[:, :, :, 0]
+    want = torch.tanh(top) if tanh else top.clamp_min(0.0)
+    b = U32 * nw.abs().max(dim=3).values + (2 * TANH_ULPS * U32 * want.abs() if tanh else 0.0)
+    b = b + 2.0 ** -50 * ((yw * coef[:, 0]).abs() + coef[:, 1].abs()).max(dim=3).values      # the float64 reference's own rounding
+    if bf16:
+        b = BF16 * want.abs() + (1 + BF16) * b
+    return want, b, nw, pos
