@@ -1107,6 +1107,21 @@ int64_t cvae_op_latent_scratch_floats(cvae_handle h, int32_t B) {
     return fc_ws_floats(h->cfg.width, B);
 }
 
+// include/cvae.h: the grids of the latent launches at a batch, from the function the launchers call (host logic only, no device access)
+int32_t cvae_op_latent_plan(int32_t width, int32_t B, int32_t num_cus, int32_t* out) {
+    if ((width != 64 && width != 128) || B < 1 || num_cus < 1 || !out) {
+        cvae_set_error("cvae_op_latent_plan: width %d not 64 / 128, batch %d or compute units %d below 1, or null pointer", width, B, num_cus);
+        return CVAE_EINVAL;
+    }
+    const LatentPlan p = latent_plan(width, B, num_cus);
+    const int dfl0 = p.fb_split ? 0 : p.fb_bgemm, cs0 = p.fb_bgemm + (p.fb_split ? 0 : p.fb_dflat);
+    const int v[CVAE_LATENT_PLAN_INTS] = {p.fc_fwd_gemm, p.di_imgs, p.di_blocks,
+                                          0, p.db_bgemm, p.db_bgemm, p.db_bgemm + p.db_gemm,
+                                          p.df_imgs, 0, p.fb_bgemm, dfl0, dfl0 + p.fb_dflat, cs0, cs0 + p.fb_colsum, p.fb_split};
+    for (int i = 0; i < CVAE_LATENT_PLAN_INTS; ++i) out[i] = v[i];
+    return 0;
+}
+
 int cvae_op_fc_fwd(cvae_handle h, int32_t B, const float* flat, const float* wfc, const float* bfc, const float* eps,
                    const float* pred, float* mu, float* logvar, float* zcat, void* scratch, void* stream) {
     RC(latent_check(h, B, "cvae_op_fc_fwd", flat && wfc && bfc && eps && pred && mu && logvar && zcat && scratch));

@@ -239,6 +239,25 @@ int launch_reduce_slabs(const float* slab, float* dst, int64_t n, int S, int64_t
                         float* mid = nullptr, bool out_bf16 = false);
 int launch_colsum(const float* src, int64_t rows, int C, float* dst, float* ws, hipStream_t st);
 int64_t colsum_ws_floats(int64_t rows, int C);
+// Stage 1 of the column sum as block `blk` of `nblk` (colsum_stage1, and the column-sum job of fc.hip's fc_bwd launch):
+// part[blk][c] = sum of this block's rows.  thread -> (channel c = tid % C, row lane rl = tid / C); requires C <= 256 and
+// 256 % C == 0; red: 256 floats of LDS.  launch_colsum runs min(CS_BLOCKS, rows) blocks.
+static constexpr int CS_BLOCKS = 128;
+__device__ __forceinline__ void colsum_stage1_block(const float* __restrict__ src, int64_t rows, int C, float* __restrict__ part,
+                                                    int blk, int nblk, float* red) {
+    const int c = threadIdx.x % C, rl = threadIdx.x / C, RL = 256 / C;
+    const int64_t per = (rows + nblk - 1) / nblk;
+    const int64_t r0 = blk * per;
+    int64_t r1 = r0 + per; if (r1 > rows) r1 = rows;
+    float acc = 0.f;
+    for (int64_t r = r0 + rl; r < r1; r += RL) acc += src[r * C + c];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    if (rl == 0) {
+        for (int k = 1; k < RL; ++k) acc += red[k * C + c];
+        part[(size_t)blk * C + c] = acc;
+    }
+}
 // reduce.hip
 int64_t col_reduce_ws_floats(int W);
 int launch_col_reduce_partial(const float* in, int R, int W, int64_t stride, float* ws, hipStream_t st,
@@ -297,6 +316,17 @@ int launch_bn_pool_act_bwd(int layer, int width, int B, const float* y, const fl
                            float* dgamma, float* dbeta, float* dbias, float* ws, hipStream_t st, bool bf16io = false,
                            int stage = 0, double* rec = nullptr, const double* count = nullptr);     // stage 1 / 2: cross-rank split (bn.hip)
 // fc.hip
+// Grids of the latent launches at a batch: host arithmetic only; the launchers and cvae_op_latent_plan both read it.
+// A merged launch runs its jobs over consecutive blockIdx.x ranges in the order of the fields.
+struct LatentPlan {
+    int fc_fwd_gemm;                            // launch_fc_fwd: latent_gemm blocks, cdiv(B, 128) * 32 K-slices
+    int di_imgs, di_blocks;                     // launch_decin_fwd: images per workgroup, (K / 1024) * cdiv(B, di_imgs) blocks
+    int db_bgemm, db_gemm;                      // launch_decin_bwd: dWd | dbd (K / 32), then the d_zcat slabs (cdiv(B, 128) * 32)
+    int df_imgs, fb_bgemm, fb_dflat, fb_colsum; // launch_fc_bwd: images per dflat workgroup; dWfc (K / 32), dflat ((K / 256) *
+                                                // cdiv(B, df_imgs)), dbfc stage 1 (min(B, CS_BLOCKS))
+    int fb_split;                               // 1: dflat runs in a launch of its own behind dWfc | dbfc stage 1 (K / 32 > num_cus)
+};
+LatentPlan latent_plan(int width, int B, int num_cus);
 int64_t fc_ws_floats(int width, int B);
 int launch_fc_fwd(int width, int B, const float* flat, const float* wfc, const float* bfc,
                   const float* eps, const float* pred, float* mu, float* logvar, float* zcat,

@@ -379,24 +379,10 @@ int launch_conv_wgrad(int layer, int width, int B, const float* in, const float*
 // column sums: dst[c] = sum_rows src[row][c]  (conv bias gradients: db = sum over pixels of dout)
 // two fixed-order stages -> reproducible.
 // --------------------------------------------------------------------------------------------
-static constexpr int CS_BLOCKS = 128;
-
 __global__ __launch_bounds__(256) void colsum_stage1(const float* __restrict__ src, int64_t rows, int C,
                                                      float* __restrict__ part) {
-    // thread -> (channel c = tid % C, row lane rl = tid / C); requires C <= 256 and 256 % C == 0
     __shared__ float red[256];
-    const int c = threadIdx.x % C, rl = threadIdx.x / C, RL = 256 / C;
-    const int64_t per = (rows + gridDim.x - 1) / gridDim.x;
-    const int64_t r0 = blockIdx.x * per;
-    int64_t r1 = r0 + per; if (r1 > rows) r1 = rows;
-    float acc = 0.f;
-    for (int64_t r = r0 + rl; r < r1; r += RL) acc += src[r * C + c];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (rl == 0) {
-        for (int k = 1; k < RL; ++k) acc += red[k * C + c];
-        part[(size_t)blockIdx.x * C + c] = acc;
-    }
+    colsum_stage1_block(src, rows, C, part, blockIdx.x, gridDim.x, red);      // common.h
 }
 
 int64_t colsum_ws_floats(int64_t rows, int C) { (void)rows; return (int64_t)CS_BLOCKS * C + col_reduce_ws_floats(C); }

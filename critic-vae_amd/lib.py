@@ -134,6 +134,7 @@ _SIGS = {
     "cvae_op_bn_pool_act_bwd": (C.c_int, [_p, _i32, _i32] + [_p] * 11),
     "cvae_op_msssim": (C.c_int, [_p, _i32] + [_p] * 6),
     "cvae_op_latent_scratch_floats": (_i64, [_p, _i32]),
+    "cvae_op_latent_plan": (_i32, [_i32, _i32, _i32, C.POINTER(C.c_int32)]),
     "cvae_op_fc_fwd": (C.c_int, [_p, _i32] + [_p] * 10),
     "cvae_op_decin_fwd": (C.c_int, [_p, _i32] + [_p] * 5),
     "cvae_op_decin_bwd": (C.c_int, [_p, _i32] + [_p] * 8),
@@ -185,6 +186,25 @@ def sync_slot(point):
     if lib.cvae_sync_slot(point, C.byref(off), C.byref(n)) != 0:
         raise CvaeError(f"cvae_sync_slot: {lib.cvae_last_error().decode()}")
     return off.value, n.value
+
+
+LATENT_PLAN_INTS = 15     # CVAE_LATENT_PLAN_INTS
+
+
+def latent_plan(width, B, num_cus):
+    """cvae_op_latent_plan (host logic only): the grids of the latent launches at batch B on a device of num_cus compute
+    units.  Job ranges are (begin, end) over blockIdx.x in launch order; `grid` is the launch's block count.  fc_bwd with
+    `split`: dflat has a launch of its own ((0, n) there) behind the launch of `grid` blocks that holds the other two jobs."""
+    lib = load()
+    out = (C.c_int32 * LATENT_PLAN_INTS)()
+    if lib.cvae_op_latent_plan(width, B, num_cus, out) != 0:
+        raise CvaeError(f"cvae_op_latent_plan: {lib.cvae_last_error().decode()}")
+    v = list(out)
+    return {"fc_fwd": {"gemm": v[0]},
+            "decin_fwd": {"imgs": v[1], "grid": v[2]},
+            "decin_bwd": {"jobs": {"bgemm": (v[3], v[4]), "gemm": (v[5], v[6])}, "grid": v[6]},
+            "fc_bwd": {"imgs": v[7], "jobs": {"bgemm": (v[8], v[9]), "dflat": (v[10], v[11]), "colsum": (v[12], v[13])},
+                       "grid": v[13], "split": bool(v[14])}}
 
 
 def _stream():

@@ -618,6 +618,20 @@ int cvae_op_msssim(cvae_handle h, int32_t batch, const float* img1, const float*
  * entry do not matter.  batch < 1, batch > max_batch or a null pointer is CVAE_EINVAL (the size query returns it too).
  */
 int64_t cvae_op_latent_scratch_floats(cvae_handle h, int32_t batch);
+/* Host logic only (no handle, no device access): the grids the four launchers below use at `batch` on a device of `num_cus`
+ * compute units, from the function the launchers themselves call (they pass the current device's count).  A merged launch runs
+ * its jobs over consecutive blockIdx.x ranges [begin, end).  out[0..CVAE_LATENT_PLAN_INTS):
+ *   [0]      fc_fwd: blocks of the fc_mu | fc_var GEMM, ceil(batch / 128) row blocks x 32 K-slices
+ *   [1] [2]  decin_fwd: images per workgroup (16, 8 or 4), blocks = (K / 1024) * ceil(batch / images)
+ *   [3] [4]  decin_bwd, job 0: dWd | dbd, K / 32 blocks        [5] [6]  job 1: the d_zcat slabs, ceil(batch / 128) * 32 blocks
+ *   [7]      fc_bwd: images per dflat workgroup (32, 16 or 8)
+ *   [8] [9]  fc_bwd, job 0: dWfc, K / 32 blocks                [10] [11] job 1: dflat, (K / 256) * ceil(batch / images) blocks
+ *   [12] [13] job 2: first stage of dbfc, min(batch, 128) blocks
+ *   [14]     0: the three jobs of fc_bwd share one launch of [13] blocks.  1 (K / 32 > num_cus: the dWfc workgroups fill the
+ *            device by themselves): dflat runs in a launch of its own of [11] blocks, [10] = 0, behind dWfc and dbfc ([13] blocks)
+ * [6] is the grid of decin_bwd's launch.  Width other than 64 / 128, batch or num_cus below 1, or a null pointer: CVAE_EINVAL. */
+#define CVAE_LATENT_PLAN_INTS 15
+int32_t cvae_op_latent_plan(int32_t width, int32_t batch, int32_t num_cus, int32_t* out);
 /* flatten + fc_mu | fc_var + reparametrize + cat (vae_nets.py:105-109, :48-51, :143): mu, logvar (batch,32) = flat . Wfc + bfc,
  * zcat (batch,33) = [mu + eps * exp(logvar / 2) | pred] */
 int cvae_op_fc_fwd(cvae_handle h, int32_t batch, const float* flat, const float* wfc, const float* bfc,
