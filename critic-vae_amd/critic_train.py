@@ -10,20 +10,79 @@ csrc/critic_train.hip) and the flat Adam kernels the VAE trainer uses.
 
 critic.flat holds the trained values after every step: critic.evaluate, critic.state_dict(), curate(), segment and render
 use the critic as they use a loaded checkpoint.
+
+Held-out validation (cvae_critic_score, csrc/critic_score.hip: uint8 frame -> eval-mode forward -> one row per frame and a
+pooled fp64 record, one launch per batch):
+
+    train, val = episodes.split_by_trajectory(ds, 0.2)
+    trainer.fit_device(train, 128, epochs=15, val=val)          # trainer.val_history: (step, evaluate(val)) per epoch
+    trainer.evaluate(val, 2048)["bin_agreement"]                # the share of frames whose value lands in its target's bin
 """
 import numpy as np
 import torch
 
 from . import params as P
 from . import synth
-from .lib import CRITIC_DECISIONS, CRITIC_KEEP, CRITIC_LOSS, CRITIC_TRAIN_FLOATS
+from .lib import CRITIC_DECISIONS, CRITIC_KEEP, CRITIC_LOSS, CRITIC_SCORE_COLS, CRITIC_SCORE_STATE_DOUBLES, CRITIC_TRAIN_FLOATS
 
-MAX_BATCH = 65536            # cvae_critic_grad's own cap (include/cvae.h)
+MAX_BATCH = 65536            # cvae_critic_grad's and cvae_critic_score's own cap (include/cvae.h)
+RECORD_DOUBLES = 27          # the documented part of cvae_critic_score's pooled record: counts, sums, maximum, confusion
 
 
 def initial_state_dict(seed=0):
     """Fresh critic weights: the reference class's shapes with PyTorch's default init bounds (synth.make_critic_params)."""
     return {k: torch.from_numpy(v) for k, v in synth.make_critic_params(seed).items()}
+
+
+def score_frames(critic, frames_u8, targets, idx=None):
+    """cvae_critic_score's rows, (B, 8) fp32 on the device, of frames_u8[idx] ((N,64,64,3) uint8 device tensor) against
+    targets[idx] ((N) or (N,1) fp32): [0] the critic's value p, [1] the target t, [2] the BCE term, [3] (p - t)^2, [4] |p - t|,
+    [5] / [6] the bin of p / of t (0 mid, 1 high, 2 low, 3 none: episodes.value_bins), [7] 0.  idx: int64 device tensor, or None =
+    every frame in order; an index outside [0, N) gives a NaN row.  Batches above MAX_BATCH run in pieces."""
+    h, dev = critic.handle, frames_u8.device
+    B = frames_u8.shape[0] if idx is None else idx.numel()
+    rows = torch.empty(B, CRITIC_SCORE_COLS, device=dev)
+    for b in range(0, B, MAX_BATCH):
+        nb = min(MAX_BATCH, B - b)
+        if idx is None:
+            h.critic_score(nb, frames_u8[b:b + nb], targets[b:b + nb], critic.flat, per_frame=rows[b:b + nb])
+        else:
+            h.critic_score(nb, frames_u8, targets, critic.flat, idx=idx[b:b + nb], per_frame=rows[b:b + nb])
+    return rows
+
+
+def summarize_record(rec, loss="bce"):
+    """The pooled record of cvae_critic_score (include/cvae.h; at least its first 27 doubles, on the host) -> the dict
+    CriticTrainer.evaluate returns, in float64:
+      frames, finite_frames: frames seen, and those whose row is finite (a NaN target or value is counted, not hidden);
+      bce, mse, mae, mean_pred, mean_target: means over the finite frames; loss: bce or mse, as `loss` names it;
+      pearson: Pearson's r of value and target over the finite frames, NaN when either variance is 0 (a variance below 1e-12
+        of the mean square is cancellation noise of the fp64 sums and counts as 0);
+      bin_agreement: the share of finite frames whose value falls in the bin of its target (the trace of `confusion` over the
+        finite frames); confusion: (4, 4) int64, row = the target's bin, column = the value's (mid, high, low, none);
+      worst: the largest |p - t|.  An empty record gives NaN everywhere and a zero confusion matrix."""
+    if loss not in CRITIC_LOSS:
+        raise ValueError(f"loss {loss!r}: one of {sorted(CRITIC_LOSS)}")
+    rec = np.asarray(rec, np.float64).reshape(-1)
+    if rec.size < RECORD_DOUBLES:
+        raise ValueError(f"a record of {rec.size} doubles, need at least {RECORD_DOUBLES}")
+    nan = float("nan")
+    fin = int(rec[1])
+    conf = np.rint(rec[11:27]).astype(np.int64).reshape(4, 4)
+    out = {"frames": int(rec[0]), "finite_frames": fin, "confusion": conf}
+    if fin == 0:
+        out.update(bce=nan, mse=nan, mae=nan, loss=nan, pearson=nan, bin_agreement=nan, mean_pred=nan, mean_target=nan, worst=nan)
+        return out
+    s_bce, s_se, s_ae, s_p, s_t, s_pp, s_tt, s_pt = (float(v) for v in rec[2:10])
+    out.update(bce=s_bce / fin, mse=s_se / fin, mae=s_ae / fin, mean_pred=s_p / fin, mean_target=s_t / fin, worst=float(rec[10]))
+    out["loss"] = out[loss]
+    var_p, var_t, cov = s_pp - s_p * s_p / fin, s_tt - s_t * s_t / fin, s_pt - s_p * s_t / fin
+    if var_p <= 1e-12 * s_pp or var_t <= 1e-12 * s_tt:
+        out["pearson"] = nan
+    else:
+        out["pearson"] = float(cov / np.sqrt(var_p * var_t))
+    out["bin_agreement"] = float(np.trace(conf)) / fin
+    return out
 
 
 class CriticTrainer:
@@ -65,6 +124,9 @@ class CriticTrainer:
         self.v = torch.zeros_like(self.theta)
         self.scalars = torch.zeros(4, device=dev)
         self.step_count = 0
+        self.val_history = []             # (step_count, result of evaluate()) per evaluation that fit_device(val=...) ran
+        self.best_val = None              # the lowest finite validation loss seen (the CLI's --keep-best / --patience)
+        self.val_stale = 0                # evaluations in a row since it last improved
         self._scratch, self._pred = None, None
 
     def _buffers(self, B):
@@ -106,19 +168,66 @@ class CriticTrainer:
                              self.eps)
         return self.scalars
 
-    def fit_device(self, dataset, batch_size, epochs=1, generator=None, shuffle=True):
+    def _check_dataset(self, dataset, batch_size, cap):
+        dev = self.theta.device
+        if dataset.width != 64:
+            raise ValueError(f"the dataset holds {dataset.width}x{dataset.width} frames, the critic takes 64x64")
+        if dataset.frames.dtype != torch.uint8:
+            raise ValueError("the critic's dataset holds uint8 frames (episodes.critic_dataset)")
+        if not 1 <= int(batch_size) <= cap:
+            raise ValueError(f"batch_size {batch_size} outside 1..{cap}")
+        if dataset.frames.device != dev:
+            raise ValueError(f"the dataset is on {dataset.frames.device}, the critic on {dev}")
+        return dev, int(batch_size)
+
+    def evaluate(self, dataset, batch_size, per_frame=False):
+        """The critic on a held-out DeviceDataset whose `preds` slot holds the targets (episodes.critic_dataset,
+        split_by_trajectory): the dataset in order, one cvae_critic_score launch per batch — uint8 frame, EVAL-mode forward
+        (Dropout = identity), row, pooling — into ONE fp64 device record that the host reads once, at the end.  Returns
+        summarize_record's dict (loss = this trainer's chosen loss), plus per_frame = the (N, 8) device rows when asked for.
+        batch_size: 1..65 536, whatever the handle's max_batch.  Draws nothing from any random generator and leaves the
+        parameters, the Adam state, the step count and the guard record untouched."""
+        dev, B = self._check_dataset(dataset, batch_size, MAX_BATCH)
+        h, n = self.h, len(dataset)
+        if n < 1:
+            raise ValueError("evaluate(): the dataset is empty")
+        rows = torch.empty(n, CRITIC_SCORE_COLS, device=dev) if per_frame else None
+        scratch = None if per_frame else torch.empty(h.critic_score_scratch_bytes(min(B, n)), dtype=torch.uint8, device=dev)
+        state = h.critic_score_state(dev)
+        targets = dataset.preds.view(-1)
+        for b in range(0, n, B):
+            nb = min(B, n - b)
+            h.critic_score(nb, dataset.frames[b:b + nb], targets[b:b + nb], self.theta, state=state, scratch=scratch,
+                           per_frame=None if rows is None else rows[b:b + nb])
+        out = summarize_record(state[:RECORD_DOUBLES].cpu().numpy(), self.loss)        # the one host read
+        if per_frame:
+            out["per_frame"] = rows
+        return out
+
+    def _validate(self, val, batch_size, on_val):
+        """One evaluation inside fit_device: history entry, callback; True = the callback asked to stop."""
+        result = self.evaluate(val, batch_size)
+        self.val_history.append((int(self.step_count), result))
+        return bool(on_val(self, result)) if on_val is not None else False
+
+    def fit_device(self, dataset, batch_size, epochs=1, generator=None, shuffle=True, val=None, val_every=None, on_val=None):
         """The loop of FusedTrainer.fit_device over a DeviceDataset whose `preds` slot holds the targets
         (episodes.critic_dataset): per epoch np.random.shuffle of the host indices, slices of batch_size with the ragged last
         batch kept, one cvae_preprocess_u8_gather launch per batch (x = frames[idx] / 255, target = preds[idx]), keep masks from
-        `generator`.  Returns the loss scalars of every step, (steps, 4), on the device."""
-        dev = self.theta.device
-        n, B = len(dataset), int(batch_size)
-        if dataset.width != 64:
-            raise ValueError(f"the dataset holds {dataset.width}x{dataset.width} frames, the critic takes 64x64")
-        if not 1 <= B <= min(self.h.max_batch, MAX_BATCH):
-            raise ValueError(f"batch_size {batch_size} outside 1..max_batch ({self.h.max_batch}) of the critic's handle")
-        if dataset.frames.device != dev:
-            raise ValueError(f"the dataset is on {dataset.frames.device}, the critic on {dev}")
+        `generator`.  Returns the loss scalars of every step taken, (steps, 4), on the device.
+        val: a held-out dataset of the same kind (episodes.split_by_trajectory).  It is evaluated (evaluate(val, batch_size))
+        after every `val_every` optimizer steps — default: at the end of every epoch —, (step_count, result) is appended to
+        self.val_history and on_val(trainer, result) is called; a true return value ends the fit there.  The evaluation draws
+        no random number and touches no training state, so the training run is bit for bit the one without it.  val=None:
+        the loop and its launches are exactly the ones above."""
+        dev, B = self._check_dataset(dataset, batch_size, min(self.h.max_batch, MAX_BATCH))
+        n = len(dataset)
+        if val is not None:
+            self._check_dataset(val, B, MAX_BATCH)
+            if val_every is not None and int(val_every) < 1:
+                raise ValueError(f"val_every {val_every!r}: a positive number of optimizer steps, or None for once per epoch")
+        elif val_every is not None or on_val is not None:
+            raise ValueError("val_every / on_val need val, the held-out dataset")
         x = torch.empty(B, 3, 64, 64, device=dev)
         target = torch.empty(B, 1, device=dev)
         log = torch.zeros(epochs * ((n + B - 1) // B), 4, device=dev)
@@ -133,6 +242,11 @@ class CriticTrainer:
                 dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], target[:nb])
                 log[k].copy_(self.step(x[:nb], target[:nb], generator=generator))
                 k += 1
+                if val is not None and val_every is not None and self.step_count % int(val_every) == 0 \
+                        and self._validate(val, B, on_val):
+                    return log[:k]
+            if val is not None and val_every is None and self._validate(val, B, on_val):
+                return log[:k]
         return log
 
     # ---- the guard's counters, as FusedTrainer ----
@@ -146,7 +260,8 @@ class CriticTrainer:
         return dict(applied=int(rec.t), skipped=int(rec.skipped), norm=float(rec.norm64), coef=float(rec.coef))
 
     def state_dict(self):
-        """Parameters (the 11 873 floats, flat), Adam moments, step count and the guard's counters, as CPU copies."""
+        """Parameters (the 11 873 floats, flat), Adam moments, step count and the guard's counters, as CPU copies; the
+        validation history (confusion matrices as nested lists), best_val and val_stale."""
         if self.guarded:
             st = self.guard_stats()
             applied, skipped = st["applied"], st["skipped"]
@@ -154,7 +269,10 @@ class CriticTrainer:
             applied, skipped = self.step_count, 0
         n = self.critic.flat.numel()
         return {"flat": self.theta[:n].detach().cpu().clone(), "m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(),
-                "step_count": int(self.step_count), "applied": applied, "skipped": skipped}
+                "step_count": int(self.step_count), "applied": applied, "skipped": skipped,
+                "val_history": [(int(t), {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in r.items() if k != "per_frame"})
+                                for t, r in self.val_history],
+                "best_val": self.best_val, "val_stale": int(self.val_stale)}
 
     def load_state_dict(self, state):
         n = self.critic.flat.numel()
@@ -169,8 +287,11 @@ class CriticTrainer:
         self.v.copy_(state["v"])
         self.step_count = steps
         self._guard_counts = (applied, skipped)
+        self.val_history = [(int(t), dict(r)) for t, r in state.get("val_history", [])]      # absent in states written before validation existed
+        self.best_val = state.get("best_val")
+        self.val_stale = int(state.get("val_stale", 0))
         if self.guarded and self.guard is not None:
             self.h.guard_init(self.guard, applied, skipped)
 
 
-__all__ = ["CriticTrainer", "initial_state_dict", "CRITIC_KEEP", "CRITIC_DECISIONS", "CRITIC_TRAIN_FLOATS", "MAX_BATCH"]
+__all__ = ["CriticTrainer", "initial_state_dict", "score_frames", "summarize_record", "CRITIC_SCORE_COLS", "CRITIC_SCORE_STATE_DOUBLES", "CRITIC_KEEP", "CRITIC_DECISIONS", "CRITIC_TRAIN_FLOATS", "MAX_BATCH"]

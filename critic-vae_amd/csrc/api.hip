@@ -771,6 +771,38 @@ int cvae_critic_grad(cvae_handle h, int32_t B, const float* x, const float* targ
                               decisions_or_null, scratch, (hipStream_t)stream);
 }
 
+// ---- per-frame scores of the critic against its targets and the pooled record (critic_score.hip) ----
+int64_t cvae_critic_score_state_bytes(void) { return critic_score_state_bytes(); }
+
+int64_t cvae_critic_score_scratch_bytes(cvae_handle h, int32_t batch) {
+    if (!h || batch < 1 || batch > kCriticGradMaxBatch) { cvae_set_error("cvae_critic_score_scratch_bytes: null handle, or batch %d outside [1, %d]", batch, kCriticGradMaxBatch); return -1; }
+    return critic_score_scratch_bytes(batch);
+}
+
+int cvae_critic_score_init(cvae_handle h, void* state, void* stream) {
+    if (!h || !state || ((uintptr_t)state & 7)) { cvae_set_error("cvae_critic_score_init: bad handle, null or misaligned state"); return CVAE_EINVAL; }
+    return launch_critic_score_init(state, (hipStream_t)stream);
+}
+
+int cvae_critic_score(cvae_handle h, int32_t B, const uint8_t* frames_hwc, const float* targets, int64_t n_frames,
+                      const int64_t* idx_or_null, const float* critic_params, float* per_frame_or_null, void* state_or_null,
+                      void* scratch, void* stream) {
+    if (!h) { cvae_set_error("cvae_critic_score: null handle"); return CVAE_EINVAL; }
+    if (h->cfg.width != 64) { cvae_set_error("cvae_critic_score: width %d unsupported (the reference critic is 64x64 only)", h->cfg.width); return CVAE_EUNSUPPORTED; }
+    if (B < 1 || B > kCriticGradMaxBatch) { cvae_set_error("cvae_critic_score: batch %d outside [1, %d]", B, kCriticGradMaxBatch); return CVAE_EINVAL; }
+    if (n_frames < 1) { cvae_set_error("cvae_critic_score: n_frames %lld must be >= 1", (long long)n_frames); return CVAE_EINVAL; }
+    if (!frames_hwc || !targets || !critic_params) { cvae_set_error("cvae_critic_score: null pointer"); return CVAE_EINVAL; }
+    if (!per_frame_or_null && !state_or_null) { cvae_set_error("cvae_critic_score: per_frame and state are both null: nothing to write"); return CVAE_EINVAL; }
+    if (!per_frame_or_null && !scratch) { cvae_set_error("cvae_critic_score: without per_frame the rows go to scratch, which is null"); return CVAE_EINVAL; }
+    if (!idx_or_null && B > n_frames) { cvae_set_error("cvae_critic_score: batch %d of %lld frames without idx", B, (long long)n_frames); return CVAE_EINVAL; }
+    float* rows = per_frame_or_null ? per_frame_or_null : static_cast<float*>(scratch);
+    if (((uintptr_t)frames_hwc & 15) || ((uintptr_t)state_or_null & 7) || ((uintptr_t)idx_or_null & 7) || ((uintptr_t)rows & 3) ||
+        ((uintptr_t)targets & 3) || ((uintptr_t)critic_params & 3)) {
+        cvae_set_error("cvae_critic_score: frames must be 16-byte aligned, state and idx 8-byte, the float arrays 4-byte"); return CVAE_EINVAL;
+    }
+    return launch_critic_score(B, frames_hwc, targets, n_frames, idx_or_null, critic_params, rows, state_or_null, (hipStream_t)stream);
+}
+
 int cvae_preprocess_u8(cvae_handle h, int32_t B, const uint8_t* frames_hwc, float* x, void* stream) {
     if (!h || B < 1 || !frames_hwc || !x) { cvae_set_error("cvae_preprocess_u8: bad handle/batch/pointer"); return CVAE_EINVAL; }
     if (B > h->cfg.max_batch) { cvae_set_error("cvae_preprocess_u8: batch %d outside [1, %d]", B, h->cfg.max_batch); return CVAE_EINVAL; }

@@ -368,6 +368,12 @@ int64_t critic_grad_scratch_bytes(int B);
 int launch_critic_grad(int width, int B, const float* x, const float* target, const uint8_t* keep, float scale, int loss_kind,
                        const float* critic_params, float* grads, float* pred, float* loss_scalars, uint8_t* decisions,
                        void* scratch, hipStream_t st);
+// critic_score.hip: per-frame scores against the targets and the pooled record (layout: include/cvae.h)
+int64_t critic_score_state_bytes();
+int64_t critic_score_scratch_bytes(int B);
+int launch_critic_score_init(void* state, hipStream_t st);
+int launch_critic_score(int B, const uint8_t* frames, const float* targets, int64_t n, const int64_t* idx, const float* critic_params,
+                        float* rows, void* state, hipStream_t st);
 // dataset.hip
 int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
                          int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* span,

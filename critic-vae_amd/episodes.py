@@ -36,6 +36,15 @@ HIGH, LOW = np.float32(P.bin_high), np.float32(P.bin_low)
 CURATE_PIECE = 1024          # frames per critic launch during curation (the curation handle's max_batch)
 
 
+def value_bins(values):
+    """The bin of every critic value (or target), as the selection walk and cvae_critic_score assign it: 0 = mid
+    (MID_LO <= v <= MID_HI), 1 = high (v >= HIGH), 2 = low (v <= LOW), 3 = none; tested in that order, the value taken to
+    float32 and compared against the float32 edges; NaN falls in no bin.  Returns int64 of the input's shape."""
+    v = np.asarray(values, np.float32)
+    mid = (v >= MID_LO) & (v <= MID_HI)
+    return np.where(mid, 0, np.where(v >= HIGH, 1, np.where(v <= LOW, 2, 3))).astype(np.int64)
+
+
 def load_episodes(paths, width=P.w):
     """`.npy` files, or directories of them (not recursive): one trajectory (T, width, width, 3) uint8 per file.
     Returns [(name, array)] sorted by name (the file name without `.npy`); arrays are memory-mapped.

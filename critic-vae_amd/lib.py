@@ -51,6 +51,8 @@ MAX_PANELS = 8
 COMPOSE_CLAMP = 1
 CRITIC_KEEP, CRITIC_DECISIONS, CRITIC_TRAIN_FLOATS = 800, 11072, 11876      # include/cvae.h: cvae_critic_grad
 CRITIC_LOSS = {"bce": 0, "mse": 1}
+CRITIC_SCORE_COLS = 8             # CVAE_CRITIC_SCORE_COLS: floats per frame row of cvae_critic_score
+CRITIC_SCORE_STATE_DOUBLES = 40   # CVAE_CRITIC_SCORE_STATE_DOUBLES: the pooled fp64 record of cvae_critic_score
 
 
 def build(verbose=False):
@@ -107,6 +109,10 @@ _SIGS = {
     "cvae_critic_train_floats": (_i64, []),
     "cvae_critic_grad_scratch_bytes": (_i64, [_p, _i32]),
     "cvae_critic_grad": (C.c_int, [_p, _i32, _p, _p, _p, _f, _i32] + [_p] * 7),
+    "cvae_critic_score_state_bytes": (_i64, []),
+    "cvae_critic_score_scratch_bytes": (_i64, [_p, _i32]),
+    "cvae_critic_score_init": (C.c_int, [_p, _p, _p]),
+    "cvae_critic_score": (C.c_int, [_p, _i32, _p, _p, _i64] + [_p] * 6),
     "cvae_preprocess_u8": (C.c_int, [_p, _i32, _p, _p, _p]),
     "cvae_diff_grey": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_curate_select": (C.c_int, [_p, _i32, _p, _i64, _p, _i32, _i64] + [_p] * 6),
@@ -423,6 +429,43 @@ class Handle:
         self._check(self.lib.cvae_critic_grad(self.h, B, _ptr(x), _ptr(target), self._u8(keep, "keep"), float(dropout_p), int(loss_kind),
                                               _ptr(critic_params), _ptr(grads), _ptr(pred), _ptr(loss_scalars),
                                               self._u8(decisions, "decisions"), scratch.data_ptr(), _stream()))
+
+    # ---- per-frame critic scores and the pooled record of a held-out set (include/cvae.h) ----
+    def critic_score_state(self, device):
+        """A fresh pooled record on `device`: a float64 tensor of CRITIC_SCORE_STATE_DOUBLES values, initialised."""
+        state = torch.empty(self.lib.cvae_critic_score_state_bytes() // 8, dtype=torch.float64, device=device)
+        self.critic_score_init(state)
+        return state
+
+    def _critic_score_ptr(self, state):
+        if state is None:
+            return None
+        ptr = _ptr64(state)
+        assert isinstance(state, int) or state.numel() * 8 >= self.lib.cvae_critic_score_state_bytes(), "critic score state: too small"
+        return ptr
+
+    def critic_score_init(self, state):
+        self._check(self.lib.cvae_critic_score_init(self.h, self._critic_score_ptr(state), _stream()))
+
+    def critic_score_scratch_bytes(self, B):
+        n = self.lib.cvae_critic_score_scratch_bytes(self.h, B)
+        if n < 0:
+            raise CvaeError(f"cvae_critic_score_scratch_bytes: {self.lib.cvae_last_error().decode()}")
+        return n
+
+    def critic_score(self, B, frames_u8, targets, critic_params, idx=None, per_frame=None, state=None, scratch=None):
+        """One launch (include/cvae.h): rows (B, CRITIC_SCORE_COLS) of frames_u8[idx] ((N,64,64,3) uint8) against targets[idx]
+        into `per_frame` and / or the batch into the pooled record `state`; idx (>= B) int64 on the device, or None = the first
+        B frames; scratch (critic_score_scratch_bytes(B) bytes) holds the rows when per_frame is None."""
+        n = frames_u8.shape[0]
+        assert tuple(frames_u8.shape[1:]) == (64, 64, 3) and targets.numel() >= n
+        assert idx is None or idx.numel() >= B
+        assert per_frame is None or per_frame.numel() >= B * CRITIC_SCORE_COLS
+        assert scratch is None or (scratch.is_cuda and scratch.is_contiguous()
+                                   and scratch.numel() * scratch.element_size() >= self.critic_score_scratch_bytes(B))
+        self._check(self.lib.cvae_critic_score(self.h, B, self._u8(frames_u8, "frames"), _ptr(targets), n, self._i64(idx, "idx"),
+                                               _ptr(critic_params), _ptr(per_frame), self._critic_score_ptr(state),
+                                               None if scratch is None else scratch.data_ptr(), _stream()))
 
     def preprocess_u8(self, B, frames_u8, x):
         self._check(self.lib.cvae_preprocess_u8(self.h, B, self._u8(frames_u8, "frames"), _ptr(x), _stream()))

@@ -548,7 +548,11 @@ def build_parser():
     ap.add_argument("-critic", dest="critic_mode", action="store_true",
                     help="train the critic itself on recorded trajectories and their rewards (critic_train.py); needs --episodes, "
                          "--rewards and --save; writes DIR/critic.pt in the reference's checkpoint format, which --critic of the "
-                         "other modes loads")
+                         "other modes loads; --critic CKPT starts from a checkpoint instead of fresh weights; takes --val-fraction, "
+                         "--val-every, --keep-best (DIR/best/critic.pt) and --patience, judged by the chosen --loss on held-out trajectories")
+    ap.add_argument("--eval-only", action="store_true",
+                    help="-critic: train nothing; evaluate the checkpoint --critic on ALL frames of --episodes / --rewards under this "
+                         "project's target recipe (--gamma, --shift) and print the result; writes nothing, needs no --save")
     ap.add_argument("--rewards", nargs="+", metavar="PATH", default=None,
                     help="-critic: .npy files (T,) or directories of them, one per trajectory, named as the trajectory's frame file")
     ap.add_argument("--lr", type=float, default=1e-4, help="-critic: Adam's learning rate")
@@ -607,13 +611,25 @@ def main(argv=None):
             ap.error("--val-every and --patience need positive integers")
         if args.keep_best and args.save is None:
             ap.error("--keep-best needs --save DIR (the best networks go to DIR/best/)")
-        if not (args.second or (args.train and args.episodes is not None)):
+        if not (args.second or (args.train and args.episodes is not None) or args.critic_mode):
             ap.error("--val-fraction belongs to the fused trainer (-train --episodes, -second)")
     if args.train + args.dataset_mode + args.second + args.critic_mode != 1:
         ap.error("exactly one of -train, -dataset, -second, -critic (segment.py has -video [-thresh] [--second]); see SURVEY.md §8 for scope")
+    if args.eval_only and not args.critic_mode:
+        ap.error("--eval-only belongs to -critic")
     if args.critic_mode:
+        if args.eval_only:
+            if args.critic in (None, "random"):
+                ap.error("--eval-only needs --critic (the checkpoint to evaluate)")
+            if args.episodes is None or args.rewards is None:
+                ap.error("-critic --eval-only needs --episodes and --rewards")
+            if args.val_fraction is not None:
+                ap.error("--eval-only evaluates every frame: it takes no --val-fraction")
+            return _eval_critic(args)
         if args.episodes is None or args.rewards is None or args.save is None:
             ap.error("-critic needs --episodes, --rewards and --save")
+        if args.critic == "random":
+            ap.error("-critic --critic takes a checkpoint or 'synth'")
         if args.epochs is None:
             args.epochs = 15
         return _train_critic(args)
@@ -758,10 +774,44 @@ def _train_episodes(args):
 CRITIC_FILE = "critic.pt"
 
 
-def _train_critic(args):
-    """-critic: load_episodes + load_rewards -> critic_dataset (discounted targets) -> CriticTrainer.fit_device -> DIR/critic.pt."""
+class _CriticValidationLog:
+    """on_val of `-critic`: one line per evaluation, --keep-best and --patience, as _ValidationLog.  The value judged is the
+    trainer's chosen loss on the held-out frames; a non-finite value never counts as an improvement."""
+
+    def __init__(self, args):
+        self.args = args
+
+    def __call__(self, trainer, r):
+        loss = r["loss"]
+        better = bool(np.isfinite(loss)) and (trainer.best_val is None or loss < trainer.best_val)
+        print(f"val @ step {trainer.step_count}: {trainer.loss} {loss:.6f} (bce {r['bce']:.6f}, mse {r['mse']:.6f}, mae {r['mae']:.6f}) "
+              f"pearson {r['pearson']:.4f} bin agreement {r['bin_agreement']:.4f} worst {r['worst']:.4f} over {r['frames']} frames, "
+              f"{r['frames'] - r['finite_frames']} non-finite{' *' if better else ''}")
+        if better:
+            trainer.best_val, trainer.val_stale = float(loss), 0
+            if self.args.keep_best:
+                print(f"saved {_save_critic(trainer.critic, os.path.join(self.args.save, BEST_DIR))}")
+        else:
+            trainer.val_stale += 1
+        if self.args.patience is not None and trainer.val_stale >= self.args.patience:
+            print(f"no improvement in {trainer.val_stale} evaluations: stopping at step {trainer.step_count}")
+            return True
+        return False
+
+
+def _save_critic(critic, directory):
+    """DIR/critic.pt in the reference's checkpoint format (what --critic of every mode loads)."""
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, CRITIC_FILE)
+    torch.save({k: v.detach().cpu() for k, v in critic.state_dict().items()}, path)
+    return path
+
+
+def _critic_and_dataset(args, size):
+    """What -critic and its --eval-only share: the trajectories with their rewards, the critic (fresh from --seed, or --critic)
+    on a handle of its own, and the (frame, discounted target) dataset on the device."""
     from .critic import Critic
-    from .critic_train import CriticTrainer, initial_state_dict
+    from .critic_train import initial_state_dict
     from .episodes import critic_dataset, load_episodes, load_rewards
     from .lib import Handle
     episodes = load_episodes(args.episodes)
@@ -769,31 +819,58 @@ def _train_critic(args):
     device = _device()
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
-    critic = Critic(handle=Handle(64, max(args.batch, 1))).to(device)
-    critic.load_state_dict(initial_state_dict(args.seed))
-    ds = critic_dataset(episodes, rewards, size=args.datasize, seed=args.seed, gamma=args.gamma, shift=args.shift, device=device)
+    handle = Handle(64, max(args.batch, 1))
+    if args.critic is None:
+        critic = Critic(handle=handle).to(device)
+        critic.load_state_dict(initial_state_dict(args.seed))
+    else:
+        critic = _load_critic(args.critic, handle, args.seed, device)
+    ds = critic_dataset(episodes, rewards, size=size, seed=args.seed, gamma=args.gamma, shift=args.shift, device=device)
     if len(ds) == 0:
         raise SystemExit("the critic's dataset is empty")
+    return critic, ds, device
+
+
+def _train_critic(args):
+    """-critic: load_episodes + load_rewards -> critic_dataset (discounted targets) -> CriticTrainer.fit_device -> DIR/critic.pt."""
+    from .critic_train import CriticTrainer
+    critic, ds, device = _critic_and_dataset(args, args.datasize)
     trainer = CriticTrainer(critic, lr=args.lr, dropout=args.dropout, loss=args.loss, skip_nonfinite=args.skip_nonfinite,
                             max_grad_norm=args.max_grad_norm)
     gen = torch.Generator(device=device)
     gen.manual_seed(args.seed)
+    val_kw = {}
+    if args.val_fraction is not None:
+        from .episodes import split_by_trajectory
+        n_all = len(ds)
+        ds, val = split_by_trajectory(ds, args.val_fraction, seed=args.seed)
+        print(f"held out {len(val)} of {n_all} frames ({len(np.unique(val.source[:, 0]))} whole trajectories); training on {len(ds)}")
+        val_kw = dict(val=val, val_every=args.val_every, on_val=_CriticValidationLog(args))
     t0 = time.time()
-    log = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen)
+    log = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen, **val_kw)
     torch.cuda.synchronize()
     dt = time.time() - t0
     s = log.cpu().numpy()
-    per_epoch = s.shape[0] // args.epochs
-    print(f"{args.epochs * len(ds) / dt:.1f} images/s over {args.epochs} epoch(s) of {len(ds)} frames; {args.loss} loss "
+    steps, per_epoch = s.shape[0], (len(ds) + args.batch - 1) // args.batch
+    images = steps // per_epoch * len(ds) + steps % per_epoch * args.batch          # a fit that --patience ended took fewer steps
+    span = f"{args.epochs} epoch(s)" if steps == args.epochs * per_epoch else f"{steps} steps"
+    per_epoch = min(per_epoch, steps)
+    print(f"{images / dt:.1f} images/s over {span} of {len(ds)} frames; {args.loss} loss "
           f"{s[:per_epoch, 0].mean():.6f} (first epoch) -> {s[-per_epoch:, 0].mean():.6f} (last)")
-    os.makedirs(args.save, exist_ok=True)
-    path = os.path.join(args.save, CRITIC_FILE)
-    torch.save({k: v.detach().cpu() for k, v in critic.state_dict().items()}, path)
-    print(f"saved {path}")
+    print(f"saved {_save_critic(critic, args.save)}")
     if trainer.guarded:
         st = trainer.guard_stats()
         print(f"guard: {st['applied']} steps applied, {st['skipped']} skipped")
     return critic
+
+
+def _eval_critic(args):
+    """-critic --eval-only: the checkpoint --critic on every frame of the trajectories, against discounted_targets."""
+    from .critic_train import MAX_BATCH, CriticTrainer
+    critic, ds, _ = _critic_and_dataset(args, None)
+    result = CriticTrainer(critic, loss=args.loss).evaluate(ds, min(max(args.batch, 1), MAX_BATCH))
+    print({k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in result.items()})
+    return result
 
 
 def _build_recon_dataset(args):

@@ -346,6 +346,52 @@ int cvae_critic_grad(cvae_handle h, int32_t batch, const float* x, const float* 
                      float dropout_p, int32_t loss_kind, const float* critic_params, float* grads, float* pred,
                      float* loss_scalars, uint8_t* decisions_or_null, void* scratch, void* stream);
 
+/*
+ * Per-frame scores of the critic against its targets and the pooled record of a held-out set (no reference counterpart: the
+ * reference ships no critic training code; the forward is Critic.evaluate, the loss terms are those of cvae_critic_grad).
+ *
+ * cvae_critic_score is ONE launch.  frames_hwc: (n_frames, 64, 64, 3) uint8, 16-byte aligned; targets: (n_frames) fp32.
+ * Frame i of the batch is idx[i] (int64), or i when idx is null (then batch <= n_frames).  A workgroup stages the uint8 frame
+ * straight into on-chip memory as (float)u8 / 255.0f — cvae_preprocess_u8_gather's arithmetic, no fp32 frame is written — and
+ * runs the eval-mode forward with the device code of cvae_critic_forward: p is bit-equal to cvae_preprocess_u8_gather +
+ * cvae_critic_forward on the same indices.  per_frame_or_null: (batch, CVAE_CRITIC_SCORE_COLS = 8) floats, row i:
+ *   [0] p, the critic's value of the frame          [1] t = targets[idx[i]]
+ *   [2] -(t * max(logf(p), -100) + (1 - t) * max(logf(1 - p), -100))   torch's binary_cross_entropy term; every operation is
+ *       rounded to fp32 on its own
+ *   [3] (p - t)^2 and [4] |p - t|, exactly the fp32 results
+ *   [5] the bin of p, [6] the bin of t: 0 = mid (0.4 <= v <= 0.6), 1 = high (v >= 0.7), 2 = low (v <= 0.25), 3 = none — the
+ *       selection rule of "The training set on the device" below: tested in the order mid, high, low, float32 comparisons
+ *       against fp32(0.4), fp32(0.6), fp32(0.7), 0.25; NaN falls in no bin
+ *   [7] reserved, written as 0
+ * An index outside [0, n_frames) is never dereferenced: its row is NaN in [0..4], 3 in [5] and [6], 0 in [7].
+ * Without per_frame the rows go to `scratch` (cvae_critic_score_scratch_bytes(h, batch) bytes, 4-byte aligned, contents on
+ * entry irrelevant); with per_frame scratch may be null.
+ * state_or_null: the pooled record, cvae_critic_score_state_bytes() = 8 * CVAE_CRITIC_SCORE_STATE_DOUBLES bytes, 8-byte
+ * aligned, fp64:
+ *   [0]      frames seen                    [1] frames whose row is finite in [0..4] ("finite frames")
+ *   [2..9]   sums over the finite frames of [2] (BCE), [3] (squared error), [4] (absolute error), p, t, p^2, t^2, p t
+ *            (the three products in fp64)
+ *   [10]     maximum of [4] over the finite frames (-inf: none yet)
+ *   [11..26] the 4 x 4 confusion counts over the finite frames, [11 + 4 * (bin of t) + (bin of p)]
+ *   [27..31] reserved, zero
+ *   [32..39] library scratch (the arrival counter of the pooling step lives here: do not write between calls)
+ * cvae_critic_score_init writes the record once; every cvae_critic_score with a state ADDS its batch, by the last workgroup
+ * to arrive, rows in a fixed order.  No floating-point atomics, nothing depends on the order of arrival: the same calls give
+ * the same bits.  There is no finish call: mean BCE = [2] / [1], Pearson's r from [5..9], bin agreement = ([11] + [16] + [21]
+ * + [26]) / [1] are host arithmetic on the record, read once (critic_train.summarize_record).
+ * 1 <= batch <= 65 536, independent of the handle's max_batch; a handle of another width than 64: CVAE_EUNSUPPORTED.  At
+ * least one of per_frame / state must be given.  Every argument is checked before any device access; nothing allocates or
+ * synchronises.
+ */
+#define CVAE_CRITIC_SCORE_COLS 8
+#define CVAE_CRITIC_SCORE_STATE_DOUBLES 40
+int64_t cvae_critic_score_state_bytes(void);
+int64_t cvae_critic_score_scratch_bytes(cvae_handle h, int32_t batch);      /* host-only; -1 for a bad argument */
+int cvae_critic_score_init(cvae_handle h, void* state, void* stream);
+int cvae_critic_score(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, const float* targets, int64_t n_frames,
+                      const int64_t* idx_or_null, const float* critic_params, float* per_frame_or_null,
+                      void* state_or_null, void* scratch, void* stream);
+
 /* adjust_values + HWC->CHW of preprocess_observation (vae_utility.py:324-343): uint8 frames
  * (B,W,W,3) -> float (B,3,W,W) / 255, so that only 1 byte per value crosses PCIe. */
 int cvae_preprocess_u8(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, float* x, void* stream);
