@@ -1,7 +1,8 @@
 """Training the critic on the device: the reference ships only a trained `critic-*.pt` and points its users at "another
 value network" (vae.py:50); CriticTrainer trains the reference's Critic class (critic_net.py:5-69, default arguments) from
 frames and targets, with cvae_critic_grad (forward in train mode with explicit Dropout masks, loss, every gradient:
-csrc/critic_train.hip) and the flat Adam kernels the VAE trainer uses.
+csrc/critic_train.hip) and the flat Adam kernels the VAE trainer uses.  The optimizer launches (plain or guarded), the
+guard's counters, the validation fields and the loop of fit_device are DeviceTrainer's (fit.py), shared with FusedTrainer.
 
     critic = Critic(handle=Handle(64, 128)).to("cuda:0"); critic.load_state_dict(initial_state_dict(seed=0))
     ds = episodes.critic_dataset(load_episodes(["episodes/"]), load_rewards(["rewards/"]))      # frames + discounted targets
@@ -23,6 +24,7 @@ import torch
 
 from . import params as P
 from . import synth
+from .fit import DeviceTrainer
 from .lib import CRITIC_DECISIONS, CRITIC_KEEP, CRITIC_LOSS, CRITIC_SCORE_COLS, CRITIC_SCORE_STATE_DOUBLES, CRITIC_TRAIN_FLOATS
 
 MAX_BATCH = 65536            # cvae_critic_grad's and cvae_critic_score's own cap (include/cvae.h)
@@ -85,7 +87,7 @@ def summarize_record(rec, loss="bce"):
     return out
 
 
-class CriticTrainer:
+class CriticTrainer(DeviceTrainer):
     """One step = cvae_critic_grad + cvae_adam_step (or the guarded pair) on the critic's flat parameter block.
 
     Owns the padded parameters (the critic's 11 873 floats + 3 zeros, so the Adam kernels' n % 4 == 0 holds), the gradient,
@@ -102,15 +104,10 @@ class CriticTrainer:
             raise ValueError(f"loss {loss!r}: one of {sorted(CRITIC_LOSS)}")
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout {dropout!r} outside [0, 1)")
-        if max_grad_norm is not None and not float(max_grad_norm) > 0:
-            raise ValueError(f"max_grad_norm {max_grad_norm!r}: a positive number (inf = no clipping) or None")
+        self._init_shared(skip_nonfinite, max_grad_norm)      # guard fields, step_count, val_history / best_val / val_stale
         self.critic, self.h = critic, critic.handle
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
         self.dropout, self.loss = float(dropout), loss
-        self.skip_nonfinite = bool(skip_nonfinite)
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.guarded = self.skip_nonfinite or self.max_grad_norm is not None
-        self.guard, self._guard_counts = None, (0, 0)
         dev = critic.flat.device
         if dev.type != "cuda":
             raise ValueError("CriticTrainer needs the critic on the device (critic.to('cuda:0')): there is no CPU path")
@@ -123,10 +120,6 @@ class CriticTrainer:
         self.m = torch.zeros_like(self.theta)
         self.v = torch.zeros_like(self.theta)
         self.scalars = torch.zeros(4, device=dev)
-        self.step_count = 0
-        self.val_history = []             # (step_count, result of evaluate()) per evaluation that fit_device(val=...) ran
-        self.best_val = None              # the lowest finite validation loss seen (the CLI's --keep-best / --patience)
-        self.val_stale = 0                # evaluations in a row since it last improved
         self._scratch, self._pred = None, None
 
     def _buffers(self, B):
@@ -157,15 +150,7 @@ class CriticTrainer:
                            self.scalars, scratch, decisions=decisions)
         self.pred = pred
         self.step_count += 1
-        if self.guarded:
-            if self.guard is None:
-                self.guard = self.h.guard_state(self.theta.device, *self._guard_counts)
-            self.h.grad_stats(self.grads, self.guard, 1.0, float("inf") if self.max_grad_norm is None else self.max_grad_norm,
-                              self.skip_nonfinite, self.lr, self.betas[0], self.betas[1])
-            self.h.adam_step_guarded(self.theta, self.grads, self.m, self.v, self.guard, self.eps)
-        else:
-            self.h.adam_step(self.theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
-                             self.eps)
+        self._update(self.theta, 1.0)
         return self.scalars
 
     def _check_dataset(self, dataset, batch_size, cap):
@@ -204,94 +189,44 @@ class CriticTrainer:
             out["per_frame"] = rows
         return out
 
-    def _validate(self, val, batch_size, on_val):
-        """One evaluation inside fit_device: history entry, callback; True = the callback asked to stop."""
-        result = self.evaluate(val, batch_size)
-        self.val_history.append((int(self.step_count), result))
-        return bool(on_val(self, result)) if on_val is not None else False
-
     def fit_device(self, dataset, batch_size, epochs=1, generator=None, shuffle=True, val=None, val_every=None, on_val=None):
         """The loop of FusedTrainer.fit_device over a DeviceDataset whose `preds` slot holds the targets
         (episodes.critic_dataset): per epoch np.random.shuffle of the host indices, slices of batch_size with the ragged last
         batch kept, one cvae_preprocess_u8_gather launch per batch (x = frames[idx] / 255, target = preds[idx]), keep masks from
         `generator`.  Returns the loss scalars of every step taken, (steps, 4), on the device.
-        val: a held-out dataset of the same kind (episodes.split_by_trajectory).  It is evaluated (evaluate(val, batch_size))
-        after every `val_every` optimizer steps — default: at the end of every epoch —, (step_count, result) is appended to
-        self.val_history and on_val(trainer, result) is called; a true return value ends the fit there.  The evaluation draws
-        no random number and touches no training state, so the training run is bit for bit the one without it.  val=None:
-        the loop and its launches are exactly the ones above."""
+        val, val_every, on_val: held-out validation as in FusedTrainer.fit_device (the shared loop, fit.py), with this
+        trainer's evaluate(val, batch_size); a fit that on_val ended returns the rows of the steps it took."""
         dev, B = self._check_dataset(dataset, batch_size, min(self.h.max_batch, MAX_BATCH))
         n = len(dataset)
         if val is not None:
             self._check_dataset(val, B, MAX_BATCH)
-            if val_every is not None and int(val_every) < 1:
-                raise ValueError(f"val_every {val_every!r}: a positive number of optimizer steps, or None for once per epoch")
-        elif val_every is not None or on_val is not None:
-            raise ValueError("val_every / on_val need val, the held-out dataset")
         x = torch.empty(B, 3, 64, 64, device=dev)
         target = torch.empty(B, 1, device=dev)
         log = torch.zeros(epochs * ((n + B - 1) // B), 4, device=dev)
-        k = 0
-        for _ in range(epochs):
-            idx = np.arange(n)
-            if shuffle:
-                np.random.shuffle(idx)
-            d_idx = torch.from_numpy(idx).to(dev)
-            for b in range(0, n, B):
-                nb = min(B, n - b)
-                dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], target[:nb])
-                log[k].copy_(self.step(x[:nb], target[:nb], generator=generator))
-                k += 1
-                if val is not None and val_every is not None and self.step_count % int(val_every) == 0 \
-                        and self._validate(val, B, on_val):
-                    return log[:k]
-            if val is not None and val_every is None and self._validate(val, B, on_val):
-                return log[:k]
-        return log
+        first = self.step_count
 
-    # ---- the guard's counters, as FusedTrainer ----
-    def guard_stats(self):
-        """dict(applied, skipped, norm, coef) of a guarded trainer (one device -> host copy)."""
-        if not self.guarded:
-            raise RuntimeError("guard_stats(): this trainer has no guard (skip_nonfinite / max_grad_norm)")
-        if self.guard is None:
-            return dict(applied=self._guard_counts[0], skipped=self._guard_counts[1], norm=0.0, coef=1.0)
-        rec = self.h.guard_record(self.guard)
-        return dict(applied=int(rec.t), skipped=int(rec.skipped), norm=float(rec.norm64), coef=float(rec.coef))
+        def batch(xb, targetb):                            # the keep mask is drawn inside step()
+            row = log[self.step_count - first]
+            row.copy_(self.step(xb, targetb, generator=generator))
+
+        self._fit(dataset, B, epochs, shuffle, x, target, batch, val, val_every, on_val, B)
+        return log[:self.step_count - first]
 
     def state_dict(self):
         """Parameters (the 11 873 floats, flat), Adam moments, step count and the guard's counters, as CPU copies; the
         validation history (confusion matrices as nested lists), best_val and val_stale."""
-        if self.guarded:
-            st = self.guard_stats()
-            applied, skipped = st["applied"], st["skipped"]
-        else:
-            applied, skipped = self.step_count, 0
         n = self.critic.flat.numel()
         return {"flat": self.theta[:n].detach().cpu().clone(), "m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(),
-                "step_count": int(self.step_count), "applied": applied, "skipped": skipped,
-                "val_history": [(int(t), {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in r.items() if k != "per_frame"})
-                                for t, r in self.val_history],
-                "best_val": self.best_val, "val_stale": int(self.val_stale)}
+                **self._shared_state()}
 
     def load_state_dict(self, state):
         n = self.critic.flat.numel()
         if state["flat"].numel() != n or state["m"].numel() != self.m.numel() or state["v"].numel() != self.v.numel():
             raise ValueError("trainer state of another parameter count")
-        applied, skipped, steps = int(state["applied"]), int(state["skipped"]), int(state["step_count"])
-        if not self.guarded and applied != steps:
-            raise ValueError(f"the state skipped {skipped} of {steps} steps: an unguarded trainer corrects Adam's bias by step_count "
-                             "and cannot continue it; construct the trainer with skip_nonfinite=True")
+        self._load_shared_state(state)
         self.theta[:n].copy_(state["flat"])
         self.m.copy_(state["m"])
         self.v.copy_(state["v"])
-        self.step_count = steps
-        self._guard_counts = (applied, skipped)
-        self.val_history = [(int(t), dict(r)) for t, r in state.get("val_history", [])]      # absent in states written before validation existed
-        self.best_val = state.get("best_val")
-        self.val_stale = int(state.get("val_stale", 0))
-        if self.guarded and self.guard is not None:
-            self.h.guard_init(self.guard, applied, skipped)
 
 
 __all__ = ["CriticTrainer", "initial_state_dict", "score_frames", "summarize_record", "CRITIC_SCORE_COLS", "CRITIC_SCORE_STATE_DOUBLES", "CRITIC_KEEP", "CRITIC_DECISIONS", "CRITIC_TRAIN_FLOATS", "MAX_BATCH"]

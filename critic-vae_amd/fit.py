@@ -1,0 +1,119 @@
+"""What FusedTrainer (train.py) and CriticTrainer (critic_train.py) share: the guard's setup and counters, the optimizer
+launch pair, the validation fields with their part of the trainer state, and the loop of fit_device.  Host Python only;
+every launch goes through the subclass's Handle (`h`).
+
+A subclass owns `h`, `lr`, `betas`, `eps`, the flat `grads`, `m`, `v`, `step_count`, its `step()` and its `evaluate()`.
+Everything here is a plain attribute of the trainer, so a test can build one with __new__ and set what it needs."""
+import numpy as np
+import torch
+
+
+class DeviceTrainer:
+    def _init_shared(self, skip_nonfinite, max_grad_norm):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm {max_grad_norm!r}: a positive number (inf = no clipping) or None")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.guarded = self.skip_nonfinite or self.max_grad_norm is not None
+        self.guard = None                 # the device guard state, created by the first guarded step ...
+        self._guard_counts = (0, 0)       # ... from these (applied, skipped): what load_state_dict / sync_replicas left
+        self.step_count = 0
+        self.val_history = []             # (step_count, result of evaluate()) per evaluation that fit_device(val=...) ran
+        self.best_val = None              # the lowest finite validation loss seen (the CLI's --keep-best / --patience)
+        self.val_stale = 0                # evaluations in a row since it last improved
+
+    # ---- the optimizer launches ----
+    def _update(self, theta, grad_scale):
+        """cvae_adam_step, or the guarded pair: statistics of the reduced gradient -> decision record -> the Adam launch that
+        obeys it; nothing comes back to the host."""
+        h = self.h
+        if not self.guarded:
+            h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
+                        grad_scale=grad_scale)
+            return
+        if self.guard is None:
+            self.guard = h.guard_state(self.m.device, *self._guard_counts)
+        h.grad_stats(self.grads, self.guard, grad_scale, float("inf") if self.max_grad_norm is None else self.max_grad_norm,
+                     self.skip_nonfinite, self.lr, self.betas[0], self.betas[1])
+        h.adam_step_guarded(theta, self.grads, self.m, self.v, self.guard, self.eps)
+
+    # ---- the guard's counters ----
+    def _guard_read(self):
+        """(applied, skipped) of a guarded trainer; one sync once the device state exists."""
+        if self.guard is None:
+            return self._guard_counts
+        rec = self.h.guard_record(self.guard)
+        return int(rec.t), int(rec.skipped)
+
+    def _guard_write(self, applied, skipped):
+        self._guard_counts = (int(applied), int(skipped))
+        if self.guard is not None:
+            self.h.guard_init(self.guard, *self._guard_counts)
+
+    def guard_stats(self):
+        """dict(applied, skipped, norm, coef) of a guarded trainer: the two counters, and the global gradient norm (after
+        grad_scale) and clip coefficient of the LAST step — norm 0 and coef 1, what cvae_guard_init writes, before the first step
+        and right after a load_state_dict / sync_replicas.  One device -> host copy, i.e. one sync; the trainer itself never calls it."""
+        if not self.guarded:
+            raise RuntimeError("guard_stats(): this trainer has no guard (skip_nonfinite / max_grad_norm)")
+        if self.guard is None:
+            return dict(applied=self._guard_counts[0], skipped=self._guard_counts[1], norm=0.0, coef=1.0)
+        rec = self.h.guard_record(self.guard)
+        return dict(applied=int(rec.t), skipped=int(rec.skipped), norm=float(rec.norm64), coef=float(rec.coef))
+
+    # ---- the shared part of state_dict / load_state_dict ----
+    def _shared_state(self):
+        """step_count, the applied / skipped counters (an unguarded trainer applied every step) and the validation fields; a
+        result in val_history is saved with its arrays as nested lists and without its device rows (per_image / per_frame)."""
+        applied, skipped = self._guard_read() if self.guarded else (self.step_count, 0)
+        history = [(int(t), {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in r.items() if k not in ("per_image", "per_frame")})
+                   for t, r in self.val_history]
+        return {"step_count": int(self.step_count), "applied": applied, "skipped": skipped, "val_history": history,
+                "best_val": self.best_val, "val_stale": int(self.val_stale)}
+
+    def _load_shared_state(self, state):
+        """The counterpart; raises before it changes anything."""
+        applied, skipped, steps = int(state["applied"]), int(state["skipped"]), int(state["step_count"])
+        if not self.guarded and applied != steps:
+            raise ValueError(f"the state skipped {skipped} of {steps} steps: an unguarded trainer corrects Adam's bias by step_count "
+                             "and cannot continue it; construct the trainer with skip_nonfinite=True")
+        self.step_count = steps
+        self.val_history = [(int(t), dict(r)) for t, r in state.get("val_history", [])]      # absent in states written before validation existed
+        self.best_val = state.get("best_val")
+        self.val_stale = int(state.get("val_stale", 0))
+        if self.guarded:
+            self._guard_write(applied, skipped)
+
+    # ---- the loop of fit_device ----
+    def _validate(self, val, batch_size, on_val):
+        """One evaluation inside fit_device: history entry, callback; True = the callback asked to stop."""
+        result = self.evaluate(val, batch_size)
+        self.val_history.append((int(self.step_count), result))
+        return bool(on_val(self, result)) if on_val is not None else False
+
+    def _fit(self, dataset, B, epochs, shuffle, x, pred, batch, val=None, val_every=None, on_val=None, val_batch=None):
+        """Per epoch np.random.shuffle of the host indices (one draw; uploaded once), slices of B with the ragged last one kept;
+        per slice one dataset.gather launch into x / pred and batch(x[:nb], pred[:nb]), which takes the step.  val is evaluated
+        (at val_batch) after every val_every steps, or at the end of every epoch; a true return value of on_val ends the fit.
+        Returns what the last batch() returned, None if none ran."""
+        if val is not None:
+            if val_every is not None and int(val_every) < 1:
+                raise ValueError(f"val_every {val_every!r}: a positive number of optimizer steps, or None for once per epoch")
+        elif val_every is not None or on_val is not None:
+            raise ValueError("val_every / on_val need val, the held-out dataset")
+        n, dev, last = len(dataset), self.m.device, None
+        for _ in range(epochs):
+            idx = np.arange(n)
+            if shuffle:
+                np.random.shuffle(idx)
+            d_idx = torch.from_numpy(idx).to(dev)          # indices of arange(n): in [0, n) by construction
+            for b in range(0, n, B):
+                nb = min(B, n - b)
+                dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], pred[:nb])
+                last = batch(x[:nb], pred[:nb])
+                if val is not None and val_every is not None and self.step_count % int(val_every) == 0 \
+                        and self._validate(val, val_batch, on_val):
+                    return last
+            if val is not None and val_every is None and self._validate(val, val_batch, on_val):
+                return last
+        return last

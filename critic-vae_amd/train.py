@@ -6,7 +6,9 @@ Two drivers over the same C-ABI kernels:
     autoencoder.parameters(), np.random.shuffle per epoch, short tail batch kept, log every log_n).
   * FusedTrainer                          — the same step without autograd/optimizer objects: direct
     cvae_forward -> cvae_loss -> cvae_backward -> (RCCL all-reduce of the flat gradient) ->
-    cvae_adam_step, all asynchronous on one stream.  This is what bench.py times.
+    cvae_adam_step, all asynchronous on one stream.  This is what bench.py times.  The optimizer launches (plain or
+    guarded), the guard's counters, the validation fields and the loop of fit_device are DeviceTrainer's (fit.py), which
+    CriticTrainer (critic_train.py) shares.
 
     python -m critic_vae_amd.train -train --synthetic 1024 --batch 32 --epochs 1
     python -m critic_vae_amd.train -train --episodes episodes/ --critic critic.pt --epochs 7 --save saved-networks
@@ -28,6 +30,7 @@ import torch
 
 from . import params as P
 from . import synth
+from .fit import DeviceTrainer
 from .lib import N_SCALARS, SCORE_COLS, SYNC_DOUBLES, SYNC_POINTS
 from .nets import VariationalAutoencoder
 
@@ -79,7 +82,7 @@ def train(autoencoder, dset, critic_fn, device, epochs=P.epochs, batch_size=P.ba
     return autoencoder, history
 
 
-class FusedTrainer:
+class FusedTrainer(DeviceTrainer):
     """One training step = forward + loss + backward + all-reduce + Adam on flat buffers."""
 
     def __init__(self, vae, lr=P.lr, betas=P.adam_betas, eps=P.adam_eps, process_group=None, world_size=1,
@@ -119,13 +122,7 @@ class FusedTrainer:
         self.global_stats = bool(global_stats)
         self.buckets = [self.h.grad_bucket(ph) for ph in range(3)]
         self.lr, self.betas, self.eps = lr, betas, eps
-        if max_grad_norm is not None and not float(max_grad_norm) > 0:
-            raise ValueError(f"max_grad_norm {max_grad_norm!r}: a positive number (inf = no clipping) or None")
-        self.skip_nonfinite = bool(skip_nonfinite)
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.guarded = self.skip_nonfinite or self.max_grad_norm is not None
-        self.guard = None                 # the device guard state, created by the first guarded step ...
-        self._guard_counts = (0, 0)       # ... from these (applied, skipped): what load_state_dict / sync_replicas left
+        self._init_shared(skip_nonfinite, max_grad_norm)      # guard fields, step_count, val_history / best_val / val_stale
         self.world_size, self.pg = world_size, process_group
         dev = vae.theta.device
         n = vae.theta.numel()
@@ -133,10 +130,6 @@ class FusedTrainer:
         self.grads16 = torch.empty(n, dtype=torch.bfloat16, device=dev) if (reduce_dtype == "bf16" and world_size > 1) else None
         self.m = torch.zeros(n, device=dev)
         self.v = torch.zeros(n, device=dev)
-        self.step_count = 0
-        self.val_history = []             # (step_count, result of evaluate()) per evaluation that fit_device(val=...) ran
-        self.best_val = None              # the lowest finite pooled validation total_loss seen (the CLI's --keep-best / --patience)
-        self.val_stale = 0                # evaluations in a row since it last improved
         B = vae.max_batch
         self.mu = torch.empty(B, P.latent_dim, device=dev)
         self.logvar = torch.empty_like(self.mu)
@@ -199,10 +192,7 @@ class FusedTrainer:
             self._reduce_all()
         self.step_count += 1
         v.num_batches_tracked += 1
-        if self.guarded:
-            return self._guarded_update(theta, 1.0 / self.world_size)
-        h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
-                    self.eps, grad_scale=1.0 / self.world_size)
+        self._update(theta, 1.0 / self.world_size)
         return self.scalars
 
     def _reduce_bucket(self, ph):
@@ -267,44 +257,8 @@ class FusedTrainer:
             self._reduce_all()
         self.step_count += 1
         v.num_batches_tracked += 1
-        if self.guarded:
-            return self._guarded_update(theta, 1.0)
-        h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
-                    self.eps, grad_scale=1.0)        # the summed gradient already is the global-batch gradient
+        self._update(theta, 1.0)                     # the summed gradient already is the global-batch gradient
         return self.scalars
-
-    # ---- the guarded step ----
-    def _guarded_update(self, theta, grad_scale):
-        """Statistics of the reduced gradient -> decision record -> the Adam launch that obeys it; nothing comes back to the host."""
-        if self.guard is None:
-            self.guard = self.h.guard_state(self.m.device, *self._guard_counts)
-        self.h.grad_stats(self.grads, self.guard, grad_scale, float("inf") if self.max_grad_norm is None else self.max_grad_norm,
-                          self.skip_nonfinite, self.lr, self.betas[0], self.betas[1])
-        self.h.adam_step_guarded(theta, self.grads, self.m, self.v, self.guard, self.eps)
-        return self.scalars
-
-    def _guard_read(self):
-        """(applied, skipped) of a guarded trainer; one sync once the device state exists."""
-        if self.guard is None:
-            return self._guard_counts
-        rec = self.h.guard_record(self.guard)
-        return int(rec.t), int(rec.skipped)
-
-    def _guard_write(self, applied, skipped):
-        self._guard_counts = (int(applied), int(skipped))
-        if self.guard is not None:
-            self.h.guard_init(self.guard, *self._guard_counts)
-
-    def guard_stats(self):
-        """dict(applied, skipped, norm, coef) of a guarded trainer: the two counters, and the global gradient norm (after
-        grad_scale) and clip coefficient of the LAST step — norm 0 and coef 1, what cvae_guard_init writes, before the first step
-        and right after a load_state_dict / sync_replicas.  One device -> host copy, i.e. one sync; the trainer itself never calls it."""
-        if not self.guarded:
-            raise RuntimeError("guard_stats(): this trainer has no guard (skip_nonfinite / max_grad_norm)")
-        if self.guard is None:
-            return dict(applied=self._guard_counts[0], skipped=self._guard_counts[1], norm=0.0, coef=1.0)
-        rec = self.h.guard_record(self.guard)
-        return dict(applied=int(rec.t), skipped=int(rec.skipped), norm=float(rec.norm64), coef=float(rec.coef))
 
     # ---- checkpoint ----
     def state_dict(self):
@@ -312,28 +266,16 @@ class FusedTrainer:
         counters (an unguarded trainer applied every step) and the VAE's num_batches_tracked.  With the networks restored by
         load_networks, a resumed run is exact at the step() level — the caller supplies eps; the generators that fit_* draw
         shuffles and eps from are not saved."""
-        applied, skipped = self._guard_read() if self.guarded else (self.step_count, 0)
-        return {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(), "step_count": int(self.step_count),
-                "applied": applied, "skipped": skipped, "num_batches_tracked": int(self.vae.num_batches_tracked),
-                "val_history": [(int(t), dict(r)) for t, r in self.val_history], "best_val": self.best_val,
-                "val_stale": int(self.val_stale)}
+        return {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(),
+                "num_batches_tracked": int(self.vae.num_batches_tracked), **self._shared_state()}
 
     def load_state_dict(self, state):
         if state["m"].numel() != self.m.numel() or state["v"].numel() != self.v.numel():
             raise ValueError(f"trainer state of {state['m'].numel()} parameters, this trainer has {self.m.numel()}")
-        applied, skipped, steps = int(state["applied"]), int(state["skipped"]), int(state["step_count"])
-        if not self.guarded and applied != steps:
-            raise ValueError(f"the state skipped {skipped} of {steps} steps: an unguarded trainer corrects Adam's bias by step_count "
-                             "and cannot continue it; construct the trainer with skip_nonfinite=True")
+        self._load_shared_state(state)
         self.m.copy_(state["m"])
         self.v.copy_(state["v"])
-        self.step_count = steps
         self.vae.num_batches_tracked = int(state["num_batches_tracked"])
-        self.val_history = [(int(t), dict(r)) for t, r in state.get("val_history", [])]      # absent in states written before validation existed
-        self.best_val = state.get("best_val")
-        self.val_stale = int(state.get("val_stale", 0))
-        if self.guarded:
-            self._guard_write(applied, skipped)
 
     def fit_u8(self, frames_u8, critic, batch_size, epochs=1, generator=None, shuffle=True):
         """The `-train` loop (vae.py:40-58) over a host uint8 dataset (N,w,w,3), fused step + overlapped feeder:
@@ -411,12 +353,6 @@ class FusedTrainer:
             out["per_image"] = rows
         return out
 
-    def _validate(self, val, batch_size, on_val):
-        """One evaluation inside fit_device: history entry, callback; True = the callback asked to stop."""
-        result = self.evaluate(val, min(int(batch_size), self.h.max_batch))
-        self.val_history.append((int(self.step_count), result))
-        return bool(on_val(self, result)) if on_val is not None else False
-
     def fit_device(self, dataset, batch_size, epochs=1, generator=None, shuffle=True, val=None, val_every=None, on_val=None):
         """The loop of fit_u8 over a DeviceDataset (episodes.py) that already lives on the device with its critic values:
         per epoch np.random.shuffle of the host indices (uploaded once), slices of batch_size with the ragged last batch
@@ -430,32 +366,15 @@ class FusedTrainer:
         no random number and touches no training state, so the training run is bit for bit the one without it.  val=None:
         the loop and its launches are exactly the ones above."""
         dev, B = self._check_dataset(dataset, batch_size)
-        n = len(dataset)
         if val is not None:
             self._check_dataset(val, batch_size)
-            if val_every is not None and int(val_every) < 1:
-                raise ValueError(f"val_every {val_every!r}: a positive number of optimizer steps, or None for once per epoch")
-        elif val_every is not None or on_val is not None:
-            raise ValueError("val_every / on_val need val, the held-out dataset")
         x = torch.empty(B, P.ch, self.vae.width, self.vae.width, device=dev)
         pred = torch.empty(B, 1, device=dev)
-        scal = None
-        for _ in range(epochs):
-            idx = np.arange(n)
-            if shuffle:
-                np.random.shuffle(idx)
-            d_idx = torch.from_numpy(idx).to(dev)          # indices of arange(n): in [0, n) by construction
-            for b in range(0, n, B):
-                nb = min(B, n - b)
-                dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], pred[:nb])
-                eps = torch.randn(nb, P.latent_dim, device=dev, generator=generator)
-                scal = self.step(x[:nb], pred[:nb], eps)
-                if val is not None and val_every is not None and self.step_count % int(val_every) == 0 \
-                        and self._validate(val, B, on_val):
-                    return scal
-            if val is not None and val_every is None and self._validate(val, B, on_val):
-                return scal
-        return scal
+
+        def batch(xb, predb):                              # eps is drawn after the gather, before the step
+            return self.step(xb, predb, torch.randn(xb.shape[0], P.latent_dim, device=dev, generator=generator))
+
+        return self._fit(dataset, B, epochs, shuffle, x, pred, batch, val, val_every, on_val, min(B, self.h.max_batch))
 
     # time between "backward is done" and "the reduced gradient is usable" on the compute stream = the part
     # of the all-reduce that backward did not hide (bench.py: allreduce_exposed_us)
@@ -692,14 +611,7 @@ def _fit_and_save(args, vae, ds, second):
         print(f"resumed from {args.resume} at step {trainer.step_count}")
     gen = torch.Generator(device=vae.theta.device)
     gen.manual_seed(args.seed)
-    val_kw = {}
-    if args.val_fraction is not None:
-        from .episodes import split_by_trajectory
-        n_all = len(ds)
-        ds, val = split_by_trajectory(ds, args.val_fraction, seed=args.seed)
-        print(f"held out {len(val)} of {n_all} entries ({len(val.names) or len(np.unique(val.source[:, 0]))} whole trajectories); "
-              f"training on {len(ds)}")
-        val_kw = dict(val=val, val_every=args.val_every, on_val=_ValidationLog(args, second))
+    ds, val_kw = _hold_out(args, ds, _ValidationLog(args, second), "entries", curated=True)
     t0 = time.time()
     scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen, **val_kw)
     torch.cuda.synchronize()
@@ -711,39 +623,70 @@ def _fit_and_save(args, vae, ds, second):
         enc, dec = save_networks(vae, args.save, second=second)
         print(f"saved {enc} and {dec}")
         print(f"saved {save_trainer(trainer, os.path.join(args.save, TRAINER_FILE))}")
-    if trainer.guarded:
-        st = trainer.guard_stats()
-        print(f"guard: {st['applied']} steps applied, {st['skipped']} skipped")
+    _print_guard(trainer)
     return ds
 
 
 BEST_DIR = "best"
 
 
-class _ValidationLog:
-    """on_val of the command line: one line per evaluation, --keep-best and --patience.  The best value and the count of
-    evaluations since it improved live in the trainer (best_val, val_stale: saved and resumed with it); a non-finite pooled
-    loss never counts as an improvement."""
+def _hold_out(args, ds, on_val, noun, curated):
+    """--val-fraction: (the training part of ds, fit_device's val / val_every / on_val); without it (ds, {}).  curated: the
+    dataset's names list the trajectories that gave entries (curate, curate_recon), not every trajectory (critic_dataset)."""
+    if args.val_fraction is None:
+        return ds, {}
+    from .episodes import split_by_trajectory
+    n_all = len(ds)
+    ds, val = split_by_trajectory(ds, args.val_fraction, seed=args.seed)
+    whole = (len(val.names) if curated else 0) or len(np.unique(val.source[:, 0]))
+    print(f"held out {len(val)} of {n_all} {noun} ({whole} whole trajectories); training on {len(ds)}")
+    return ds, dict(val=val, val_every=args.val_every, on_val=on_val)
 
-    def __init__(self, args, second):
-        self.args, self.second = args, second
+
+def _print_guard(trainer):
+    if trainer.guarded:
+        st = trainer.guard_stats()
+        print(f"guard: {st['applied']} steps applied, {st['skipped']} skipped")
+
+
+class _KeepBestLog:
+    """on_val of the command line: one line per evaluation, --keep-best and --patience.  The best value and the count of
+    evaluations since it improved live in the trainer (best_val, val_stale: saved and resumed with it); a non-finite
+    value never counts as an improvement.  A subclass names the judged entry of the result (`key`), writes the line and saves."""
+
+    def __init__(self, args):
+        self.args = args
 
     def __call__(self, trainer, r):
-        loss = r["total_loss"]
-        better = np.isfinite(loss) and (trainer.best_val is None or loss < trainer.best_val)
-        print(f"val @ step {trainer.step_count}: loss {loss:.6f} (recon {r['recon_loss']:.6f}, kld {r['KLD']:.6f}) over {r['images']} images, "
-              f"{r['images'] - r['finite_images']} non-finite; per image: mean {r['mean_total']:.6f} worst {r['worst']:.6f} "
-              f"psnr {r['psnr']:.2f} dB{' *' if better else ''}")
+        loss = r[self.key]
+        better = bool(np.isfinite(loss)) and (trainer.best_val is None or loss < trainer.best_val)
+        print(f"val @ step {trainer.step_count}: {self.line(trainer, r)}{' *' if better else ''}")
         if better:
             trainer.best_val, trainer.val_stale = float(loss), 0
             if self.args.keep_best:
-                save_networks(trainer.vae, os.path.join(self.args.save, BEST_DIR), second=self.second)
+                self.save(trainer, os.path.join(self.args.save, BEST_DIR))
         else:
             trainer.val_stale += 1
         if self.args.patience is not None and trainer.val_stale >= self.args.patience:
             print(f"no improvement in {trainer.val_stale} evaluations: stopping at step {trainer.step_count}")
             return True
         return False
+
+
+class _ValidationLog(_KeepBestLog):
+    """The VAE's: judged by the pooled total_loss; --keep-best writes the two network files."""
+    key = "total_loss"
+
+    def __init__(self, args, second):
+        self.args, self.second = args, second
+
+    def line(self, trainer, r):
+        return (f"loss {r['total_loss']:.6f} (recon {r['recon_loss']:.6f}, kld {r['KLD']:.6f}) over {r['images']} images, "
+                f"{r['images'] - r['finite_images']} non-finite; per image: mean {r['mean_total']:.6f} worst {r['worst']:.6f} "
+                f"psnr {r['psnr']:.2f} dB")
+
+    def save(self, trainer, directory):
+        save_networks(trainer.vae, directory, second=self.second)
 
 
 def _load_critic(spec, handle, seed, device):
@@ -774,29 +717,17 @@ def _train_episodes(args):
 CRITIC_FILE = "critic.pt"
 
 
-class _CriticValidationLog:
-    """on_val of `-critic`: one line per evaluation, --keep-best and --patience, as _ValidationLog.  The value judged is the
-    trainer's chosen loss on the held-out frames; a non-finite value never counts as an improvement."""
+class _CriticValidationLog(_KeepBestLog):
+    """`-critic`'s: judged by the trainer's chosen loss on the held-out frames; --keep-best writes DIR/best/critic.pt."""
+    key = "loss"
 
-    def __init__(self, args):
-        self.args = args
+    def line(self, trainer, r):
+        return (f"{trainer.loss} {r['loss']:.6f} (bce {r['bce']:.6f}, mse {r['mse']:.6f}, mae {r['mae']:.6f}) "
+                f"pearson {r['pearson']:.4f} bin agreement {r['bin_agreement']:.4f} worst {r['worst']:.4f} over {r['frames']} frames, "
+                f"{r['frames'] - r['finite_frames']} non-finite")
 
-    def __call__(self, trainer, r):
-        loss = r["loss"]
-        better = bool(np.isfinite(loss)) and (trainer.best_val is None or loss < trainer.best_val)
-        print(f"val @ step {trainer.step_count}: {trainer.loss} {loss:.6f} (bce {r['bce']:.6f}, mse {r['mse']:.6f}, mae {r['mae']:.6f}) "
-              f"pearson {r['pearson']:.4f} bin agreement {r['bin_agreement']:.4f} worst {r['worst']:.4f} over {r['frames']} frames, "
-              f"{r['frames'] - r['finite_frames']} non-finite{' *' if better else ''}")
-        if better:
-            trainer.best_val, trainer.val_stale = float(loss), 0
-            if self.args.keep_best:
-                print(f"saved {_save_critic(trainer.critic, os.path.join(self.args.save, BEST_DIR))}")
-        else:
-            trainer.val_stale += 1
-        if self.args.patience is not None and trainer.val_stale >= self.args.patience:
-            print(f"no improvement in {trainer.val_stale} evaluations: stopping at step {trainer.step_count}")
-            return True
-        return False
+    def save(self, trainer, directory):
+        print(f"saved {_save_critic(trainer.critic, directory)}")
 
 
 def _save_critic(critic, directory):
@@ -839,13 +770,7 @@ def _train_critic(args):
                             max_grad_norm=args.max_grad_norm)
     gen = torch.Generator(device=device)
     gen.manual_seed(args.seed)
-    val_kw = {}
-    if args.val_fraction is not None:
-        from .episodes import split_by_trajectory
-        n_all = len(ds)
-        ds, val = split_by_trajectory(ds, args.val_fraction, seed=args.seed)
-        print(f"held out {len(val)} of {n_all} frames ({len(np.unique(val.source[:, 0]))} whole trajectories); training on {len(ds)}")
-        val_kw = dict(val=val, val_every=args.val_every, on_val=_CriticValidationLog(args))
+    ds, val_kw = _hold_out(args, ds, _CriticValidationLog(args), "frames", curated=False)
     t0 = time.time()
     log = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen, **val_kw)
     torch.cuda.synchronize()
@@ -858,9 +783,7 @@ def _train_critic(args):
     print(f"{images / dt:.1f} images/s over {span} of {len(ds)} frames; {args.loss} loss "
           f"{s[:per_epoch, 0].mean():.6f} (first epoch) -> {s[-per_epoch:, 0].mean():.6f} (last)")
     print(f"saved {_save_critic(critic, args.save)}")
-    if trainer.guarded:
-        st = trainer.guard_stats()
-        print(f"guard: {st['applied']} steps applied, {st['skipped']} skipped")
+    _print_guard(trainer)
     return critic
 
 

@@ -1,0 +1,44 @@
+"""Three default-argument steps plus one evaluate() of a FusedTrainer (f32) and of a CriticTrainer (B = 64), of the source
+tree given as argv[1]: the workload of a kernel trace that shows which kernels the trainers launch, on this tree and on
+a built checkout of its parent.
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT_A -- python profiles/experiments/fit_refactor_trace.py .
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT_B -- python profiles/experiments/fit_refactor_trace.py PARENT_TREE
+    python profiles/experiments/kernel_list_compare.py OUT_B OUT_A
+"""
+import os, sys
+root = os.path.abspath(sys.argv[1])
+sys.path.insert(0, root)
+import numpy as np
+import torch
+import critic_vae_amd
+from critic_vae_amd import synth
+from critic_vae_amd.critic import Critic
+from critic_vae_amd.critic_train import CriticTrainer, initial_state_dict
+from critic_vae_amd.episodes import DeviceDataset
+from critic_vae_amd.lib import Handle
+from critic_vae_amd.nets import VariationalAutoencoder
+from critic_vae_amd.train import FusedTrainer
+assert os.path.abspath(critic_vae_amd.__file__).startswith(root), critic_vae_amd.__file__
+dev = torch.device("cuda:0")
+B = 64
+x, pred, _ = synth.make_batch(1234, 0, B)
+u8 = np.ascontiguousarray(np.rint(x * 255.0).astype(np.uint8).transpose(0, 2, 3, 1))
+ds = DeviceDataset(torch.from_numpy(u8).to(dev), torch.from_numpy(pred.reshape(B, 1).copy()).to(dev),
+                   np.stack([np.zeros(B, np.int64), np.arange(B, dtype=np.int64)], 1))
+
+vae = VariationalAutoencoder(max_batch=B, seed=0).to(dev)
+tr = FusedTrainer(vae)
+for s in range(3):
+    tr.step(*(torch.from_numpy(a).to(dev) for a in synth.make_batch(1234, s, B)))
+print("vae loss", tr.evaluate(ds, B)["total_loss"], "theta sum", vae.theta.data.double().sum().item())
+
+critic = Critic(handle=Handle(64, B)).to(dev)
+critic.load_state_dict(initial_state_dict(0))
+ct = CriticTrainer(critic)
+gen = torch.Generator(device=dev)
+gen.manual_seed(0)
+for s in range(3):
+    xb, target, _ = synth.make_batch(1234, s, B)
+    ct.step(torch.from_numpy(xb).to(dev), torch.from_numpy(target).to(dev), generator=gen)
+print("critic loss", ct.evaluate(ds, B)["loss"], "theta sum", ct.theta.double().sum().item())
