@@ -254,6 +254,7 @@ int64_t cvae_ws_offset(cvae_handle h, int32_t batch, const char* name) {
     if (!strcmp(name, "d_h")) return w.d_h;
     if (!strcmp(name, "dout4")) return w.dout4;
     if (!strcmp(name, "scratch")) return w.scratch;
+    if (!strcmp(name, "ms")) return w.ms;      // the MS-SSIM region: cvae_op_msssim_ws_floats(batch) floats, level fields first, the 832 floats of slab / coef / ticket last
     if (!strcmp(name, "xp")) return h->cfg.precision == 1 ? w.xp : -1;      // packed bf16 frame (precision mode 1)
     return -1;
 }
@@ -424,6 +425,42 @@ int cvae_loss(cvae_handle h, int32_t B, const float* x, const float* mu, const f
     const WsLayout w = carve(h, B);
     ProbeArm pa(h, 3, 4);            // id 31: the level-0 tile kernel
     return launch_msssim(h->cfg.width, B, recon, x, mu, logvar, ws + w.ms, scalars, d_recon, d_mu, d_logvar, (hipStream_t)stream);
+}
+
+// cvae_loss under a caller-chosen objective.  The reference objective {1, 0, 0.001f, 0} takes exactly cvae_loss's launches.
+int cvae_loss_obj(cvae_handle h, int32_t B, const float* x, const float* mu, const float* logvar, const float* recon,
+                  void* wsv, const cvae_objective* obj, float* scalars, float* d_recon, float* d_mu, float* d_logvar, void* stream) {
+    RC(check(h, B, wsv));
+    if (!obj) { cvae_set_error("cvae_loss_obj: null objective"); return CVAE_EINVAL; }
+    if (!x || !mu || !logvar || !recon || !scalars) { cvae_set_error("cvae_loss_obj: null tensor"); return CVAE_EINVAL; }
+    if ((d_recon == nullptr) != (d_mu == nullptr) || (d_mu == nullptr) != (d_logvar == nullptr)) {
+        cvae_set_error("cvae_loss_obj: d_recon, d_mu, d_logvar must be all set or all null");
+        return CVAE_EINVAL;
+    }
+    if ((((uintptr_t)x | (uintptr_t)recon | (uintptr_t)d_recon) & 15) != 0) {
+        cvae_set_error("cvae_loss_obj: x, recon and d_recon must be 16-byte aligned");
+        return CVAE_EINVAL;
+    }
+    const float wts[3] = {obj->msssim_weight, obj->mse_weight, obj->kld_weight};
+    for (int i = 0; i < 3; ++i)
+        if (!(wts[i] >= 0.0f) || !(wts[i] <= 3.402823466e38f)) {      // NaN fails both comparisons
+            cvae_set_error("cvae_loss_obj: weight %d is %g: every weight must be finite and >= 0", i, (double)wts[i]);
+            return CVAE_EINVAL;
+        }
+    if (!((double)obj->msssim_weight + (double)obj->mse_weight > 0.0)) {      // fp64: two large finite weights do not overflow the test
+        cvae_set_error("cvae_loss_obj: msssim_weight + mse_weight must be > 0 (no reconstruction term)");
+        return CVAE_EINVAL;
+    }
+    if (obj->msssim_grad != CVAE_MSGRAD_REFERENCE && obj->msssim_grad != CVAE_MSGRAD_USED) {
+        cvae_set_error("cvae_loss_obj: msssim_grad %d is neither CVAE_MSGRAD_REFERENCE nor CVAE_MSGRAD_USED", obj->msssim_grad);
+        return CVAE_EINVAL;
+    }
+    float* ws = (float*)wsv;
+    const WsLayout w = carve(h, B);
+    const LossObjective o{obj->msssim_weight, obj->mse_weight, obj->kld_weight, obj->msssim_grad == CVAE_MSGRAD_USED ? 1 : 0};
+    ProbeArm pa(h, 3, 4);            // id 31: the level-0 tile kernel (not launched at msssim_weight 0)
+    return launch_msssim(h->cfg.width, B, recon, x, mu, logvar, ws + w.ms, scalars, d_recon, d_mu, d_logvar, (hipStream_t)stream,
+                         0, nullptr, nullptr, &o);
 }
 
 // ---- per-image scores and the pooled record of a held-out set (score.hip) ----

@@ -339,12 +339,24 @@ int launch_fc_bwd(int width, int B, const float* flat, const float* wfc, const f
                   const float* eps, const float* logvar, const float* dmu_loss,
                   const float* dlv_loss, float* dwfc, float* dbfc, float* dflat, float* ws,
                   hipStream_t st, bool bf16io = false);
+// the objective of cvae_loss_obj (include/cvae.h), validated by the entry point: weights of the MS-SSIM, pixel (MSE) and KLD
+// terms; used != 0: MS-SSIM gradient over the terms the product uses only.  The reference objective is {1, 0, 0.001f, 0}.
+struct LossObjective { float w_ms, w_mse, kw; int used; };
+// objective.hip: the pixel pass.  F non-null (mixed objective): d_x = coef-weighted MS-SSIM chain + the pixel gradient, and
+// the merging workgroup adds w_mse * [13] to the scalars the finalize wrote.  F null (pure MSE): no chain, and the pass
+// also does the KLD (mu, logvar -> d_mu, d_logvar, scalars[2]) and writes every scalar.  slab: MSSSIM_SLAB_DOUBLES
+// doubles, *ticket 0 at launch.  dx null: values only.
+constexpr int MSSSIM_SLAB_DOUBLES = 32 * 11;
+int launch_objective_pixels(int width, int B, const float* recon, const float* x, const float* const* F, const float* coef,
+                            float* dx, const float* mu, const float* logvar, float* d_mu, float* d_logvar,
+                            LossObjective obj, double* slab, unsigned* ticket, float* scalars, hipStream_t st);
 // msssim.hip
 int64_t msssim_ws_floats(int width, int B);
 int launch_msssim(int width, int B, const float* img1, const float* img2, const float* mu,
                   const float* logvar, float* ws, float* scalars, float* d_img1, float* d_mu,
                   float* d_logvar, hipStream_t st,
-                  int stage = 0, double* rec = nullptr, const double* images = nullptr);      // stage 1 / 2: cross-rank split
+                  int stage = 0, double* rec = nullptr, const double* images = nullptr,       // stage 1 / 2: cross-rank split
+                  const LossObjective* obj = nullptr);                                        // null: the reference objective (stage 0 only otherwise)
 void msssim_score_slots(int width, int B, int64_t part[5], int64_t* scratch);      // score.hip: partial pairs and a free region of a values-only pyramid
 int launch_msssim_finish_rec(int width, const double* rec, const double* images, float* scalars, float* coef, hipStream_t st);
 // score.hip: per-image scores and the pooled record (layout: include/cvae.h)

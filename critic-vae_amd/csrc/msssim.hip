@@ -38,6 +38,7 @@ static MsWin make_window() {
 }
 
 static constexpr int MS_NF = 32;            // finalize workgroups
+static_assert(MS_NF * 11 == MSSSIM_SLAB_DOUBLES, "objective.hip reuses the slab once the finalize has run");
 
 // ------------------------------------------------------------------------------------------------
 // shared by the forward kernels: packed fp32, the argument struct, the SSIM point function, segment sums
@@ -690,6 +691,8 @@ struct MsFinArgs {
     float* d_mu; float* d_logvar;
     double* rec;             // cross-rank path: the 11 sums (record mode writes them, the finish step reads the summed ones)
     const double* images;    // cross-rank path, finish step: the summed image count (replaces B and count[])
+    float kw, w_ms;          // the objective: KLD weight, MS-SSIM weight (MS_REF_KW, 1 everywhere but under cvae_loss_obj)
+    int used;                // gradient over the used terms only (msssim_finish.h)
 };
 
 // REC (cross-rank path): no d_mu / d_logvar (a.d_mu is null), and the last arriver writes its 11 sums to a.rec instead of
@@ -710,7 +713,7 @@ __global__ __launch_bounds__(256) void msssim_finalize_kernel(MsFinArgs a) {
             acc[l] += (double)a.part[l][(size_t)i * 2];
             acc[5 + l] += (double)a.part[l][(size_t)i * 2 + 1];
         }
-    const float kw = 0.001f, invB = a.B > 0 ? 1.0f / (float)a.B : 0.f;
+    const float kw = a.kw, invB = a.B > 0 ? 1.0f / (float)a.B : 0.f;
     for (int i = gtid; i < a.B * 32; i += gstride) {
         const float m = a.mu[i], lv = a.logvar[i], e = expf(lv);
         acc[10] += (double)(1.0f + lv - m * m - e);
@@ -729,7 +732,7 @@ __global__ __launch_bounds__(256) void msssim_finalize_kernel(MsFinArgs a) {
         double t = 0.0;
         if (lane < 11) for (int g = 0; g < MS_NF; ++g) t += a.slab[g * 11 + lane];
         if (REC) { if (lane < 11) a.rec[lane] = t; return; }
-        ms_finish_scalars(lane, t, a.count[lane % 5], (double)a.B, a.scalars, a.coef);
+        ms_finish_scalars(lane, t, a.count[lane % 5], (double)a.B, a.scalars, a.coef, kw, a.used != 0, a.w_ms);
     }
 }
 
@@ -737,7 +740,7 @@ __global__ __launch_bounds__(256) void msssim_finalize_kernel(MsFinArgs a) {
 // d_logvar of this rank's a.B rows with the global 1 / B_g (B_g = *a.images).  Grid: ceil(a.B * 32 / 256) workgroups (>= 1).
 __global__ __launch_bounds__(256) void msssim_finish_kernel(MsFinArgs a, int width) {
     const double Bg = a.images[0];
-    const float kw = 0.001f, invB = Bg > 0 ? 1.0f / (float)Bg : 0.f;
+    const float kw = MS_REF_KW, invB = Bg > 0 ? 1.0f / (float)Bg : 0.f;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (a.d_mu && i < a.B * 32) {
         const float m = a.mu[i], lv = a.logvar[i], e = expf(lv);
@@ -746,7 +749,7 @@ __global__ __launch_bounds__(256) void msssim_finish_kernel(MsFinArgs a, int wid
     if (blockIdx.x != 0 || threadIdx.x >= 64) return;
     const int lane = threadIdx.x, S = width >> (lane % 5);
     const double t = lane < 11 ? a.rec[lane] : 0.0;
-    ms_finish_scalars(lane, t, 3.0 * Bg * S * S, Bg, a.scalars, a.coef);
+    ms_finish_scalars(lane, t, 3.0 * Bg * S * S, Bg, a.scalars, a.coef, MS_REF_KW, false, 1.0f);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -837,7 +840,7 @@ static int ms_fwd(const MsFwdArgs& a, hipStream_t st) {
 // d_mu / d_logvar of this rank's rows, then the backward pass.  Stages 1 and 2 run on the same ws and tensors, in order.
 int launch_msssim(int width, int B, const float* img1, const float* img2, const float* mu, const float* logvar,
                   float* ws, float* scalars, float* d_img1, float* d_mu, float* d_logvar, hipStream_t st,
-                  int stage, double* rec, const double* images) {
+                  int stage, double* rec, const double* images, const LossObjective* obj) {
     if (width != 64 && width != 128) { cvae_set_error("msssim: width %d unsupported", width); return -2; }
     int rc = 0;
     const MsWin win = make_window();
@@ -845,6 +848,15 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
     const int P = B * 3;
     const bool grad = d_img1 != nullptr;
     unsigned* ticket = reinterpret_cast<unsigned*>(ws + w.ticket);
+    const LossObjective o = obj ? *obj : LossObjective{1.0f, 0.0f, MS_REF_KW, 0};
+    // an MS-SSIM weight of exactly 0: no pyramid, no finalize, no F fields — the pixel pass finishes the KLD too.  Its
+    // partials go to the slab and it draws from the ticket, which no earlier launch of this call has zeroed.
+    if (o.w_ms == 0.0f) {
+        hipError_t e = hipMemsetAsync(ticket, 0, sizeof(unsigned), st);
+        if (e != hipSuccess) { cvae_set_error("msssim: ticket reset failed: %s", hipGetErrorString(e)); return (int)e; }
+        return launch_objective_pixels(width, B, img1, img2, nullptr, nullptr, d_img1, mu, logvar, d_mu, d_logvar, o,
+                                       reinterpret_cast<double*>(ws + w.slab), ticket, scalars, st);
+    }
     const float* lx[5]; const float* ly[5];
     lx[0] = img1; ly[0] = img2;
     for (int l = 1; l < 5; ++l) { lx[l] = ws + w.pyrx[l]; ly[l] = ws + w.pyry[l]; }
@@ -871,10 +883,19 @@ int launch_msssim(int width, int B, const float* img1, const float* img2, const 
     f.slab = reinterpret_cast<double*>(ws + w.slab); f.ticket = ticket;
     f.d_mu = d_mu; f.d_logvar = d_logvar;
     f.rec = rec; f.images = images;
+    f.kw = o.kw; f.w_ms = o.w_ms; f.used = o.used;
     if (stage == 0) hipLaunchKernelGGL(msssim_finalize_kernel<false>, dim3(MS_NF), dim3(256), 0, st, f);
     else if (stage == 1) { f.d_mu = f.d_logvar = nullptr; hipLaunchKernelGGL(msssim_finalize_kernel<true>, dim3(MS_NF), dim3(256), 0, st, f); }
     else hipLaunchKernelGGL(msssim_finish_kernel, dim3(cdiv(f.B * 32, 256) > 1 ? cdiv(f.B * 32, 256) : 1), dim3(256), 0, st, f, width);
     CVAE_CHECK_LAUNCH();
+    // mixed objective: the pixel pass writes d_img1 (MS-SSIM chain + pixel gradient), the squared-error sum and the final
+    // scalars [0] and [13].  The slab and the ticket are free again: the finalize's last arriver left the ticket at 0.
+    if (o.w_mse != 0.0f) {
+        const float* F[5];
+        for (int l = 0; l < 5; ++l) F[l] = ws + w.F[l];
+        return launch_objective_pixels(width, B, img1, img2, F, ws + w.coef, d_img1, nullptr, nullptr, nullptr, nullptr, o,
+                                       reinterpret_cast<double*>(ws + w.slab), ticket, scalars, st);
+    }
     if (!grad || stage == 1) return 0;
     MsBwdArgs b{};
     for (int l = 0; l < 5; ++l) b.F[l] = ws + w.F[l];

@@ -9,9 +9,15 @@
 // lanes 0-4: ssim_l, lanes 5-9: cs_l, lane 10: KLD sum — every lane finishes its own scalar from its fp64 sum t
 // (same operations and order as a serial evaluation), shuffles bring them together.  cnt: this lane's level count
 // B*3*S_l*S_l; Bd: the image count of the KLD mean.  Called by lanes 0..63 of one wave.
-__device__ __forceinline__ void ms_finish_scalars(int lane, double t, double cnt, double Bd, float* scalars, float* coef) {
+// The objective (cvae_loss_obj): kw is the KLD weight, w_ms the weight of the MS-SSIM term — scalars[1] stays the unweighted
+// 1 - prod, scalars[0] = w_ms * [1] + [2] and w_ms is folded into coef, so the backward chain needs no second multiply —
+// and `used` selects the gradient over the terms the product uses (no poison term below).  The reference objective is
+// (MS_REF_KW, false, 1.0f): an fp32 multiply by 1.0f is exact (also inside a contracted fma), so every caller that passes it
+// computes the bits it computed before these were arguments.
+constexpr float MS_REF_KW = 0.001f;          // vae_parameters.py:17
+__device__ __forceinline__ void ms_finish_scalars(int lane, double t, double cnt, double Bd, float* scalars, float* coef,
+                                                  float kw, bool used, float w_ms) {
     const int l = lane % 5;
-    const float kw = 0.001f;
     const float wts[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
     const float meanf = (float)(t / cnt);
     const float pw = powf(meanf, wts[l]);
@@ -21,7 +27,7 @@ __device__ __forceinline__ void ms_finish_scalars(int lane, double t, double cnt
     const float recon = 1.0f - out;
     const double k = __shfl(t, 10, 64);
     const float kld = Bd > 0 ? (float)(-0.5 * k / Bd) * kw : 0.0f;
-    if (lane == 0) { scalars[0] = recon + kld; scalars[1] = recon; scalars[2] = kld; }
+    if (lane == 0) { scalars[0] = w_ms * recon + kld; scalars[1] = recon; scalars[2] = kld; }
     if (lane < 5) scalars[3 + lane] = meanf;
     else if (lane < 10) scalars[8 + l] = meanf;
     else if (lane < 13) scalars[13 + lane - 10] = 0.f;
@@ -33,6 +39,14 @@ __device__ __forceinline__ void ms_finish_scalars(int lane, double t, double cnt
     // here: the poison term is added to the level's coefficient.
     const float poison = 0.0f * (wts[l] * powf(meanf, wts[l] - 1.0f));          // lanes 0-4: ssim_l, lanes 5-9: cs_l
     const float p_ssim = __shfl(poison, l, 64), p_cs4 = __shfl(poison, 9, 64);
-    if (lane >= 5 && lane < 9) coef[l] = (float)((double)(-out * wts[l] / meanf) / cnt) + p_ssim;
-    if (lane == 4) coef[4] = (float)((double)(-out * 4.0f * wts[4] / meanf) / cnt) + p_cs4;
+    // `used`: the derivative of prod(cs_0..3 ^ w) * ssim_4 ^ (4 w_4) alone — same value, and a negative UNUSED level mean no
+    // longer reaches the gradient (a negative used one still gives NaN, as in the reference)
+    if (lane >= 5 && lane < 9) {
+        const float c = (float)((double)(-out * wts[l] / meanf) / cnt);
+        coef[l] = w_ms * (used ? c : c + p_ssim);
+    }
+    if (lane == 4) {
+        const float c = (float)((double)(-out * 4.0f * wts[4] / meanf) / cnt);
+        coef[4] = w_ms * (used ? c : c + p_cs4);
+    }
 }

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void score_image_kernel(ScoreArgs a) {
         k = wave_sum_d(k);
         if (lane == 10) t = k;
         const int S = W >> (lane % 5);
-        ms_finish_scalars(lane, t, 3.0 * S * S, 1.0, sc, cf);
+        ms_finish_scalars(lane, t, 3.0 * S * S, 1.0, sc, cf, MS_REF_KW, false, 1.0f);
     }
     __syncthreads();
     if (tid == 0) {

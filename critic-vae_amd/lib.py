@@ -41,6 +41,15 @@ class GuardRecord(C.Structure):
                 ("ticket", C.c_uint32)]
 
 
+class Objective(C.Structure):
+    """cvae_objective (include/cvae.h): the weights of cvae_loss_obj and its MS-SSIM gradient mode."""
+    _fields_ = [("msssim_weight", C.c_float), ("mse_weight", C.c_float), ("kld_weight", C.c_float),
+                ("msssim_grad", C.c_int32)]
+
+
+MSGRAD_REFERENCE, MSGRAD_USED = 0, 1
+
+
 class Panel(C.Structure):
     """cvae_panel (include/cvae.h): one w x w panel of cvae_compose_frames."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("data", C.c_void_p), ("batch_stride", C.c_int64)]
@@ -84,6 +93,7 @@ _SIGS = {
     "cvae_forward": (C.c_int, [_p, _i32] + [_p] * 9 + [_i32, _p]),
     "cvae_decode": (C.c_int, [_p, _i32] + [_p] * 5),
     "cvae_loss": (C.c_int, [_p, _i32] + [_p] * 10),
+    "cvae_loss_obj": (C.c_int, [_p, _i32] + [_p] * 5 + [C.POINTER(Objective)] + [_p] * 5),
     "cvae_backward": (C.c_int, [_p, _i32] + [_p] * 12),
     "cvae_backward_phases": (C.c_int, [_p, _i32] + [_p] * 11 + [_i32, _p]),
     "cvae_grad_bucket": (C.c_int, [_p, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -285,6 +295,15 @@ class Handle:
     def loss(self, B, x, mu, logvar, recon, ws, scalars, d_recon=None, d_mu=None, d_logvar=None):
         self._check(self.lib.cvae_loss(self.h, B, _ptr(x), _ptr(mu), _ptr(logvar), _ptr(recon), _ptr(ws),
                                        _ptr(scalars), _ptr(d_recon), _ptr(d_mu), _ptr(d_logvar), _stream()))
+
+    def loss_obj(self, B, x, mu, logvar, recon, ws, obj, scalars, d_recon=None, d_mu=None, d_logvar=None):
+        """cvae_loss under an objective: `obj` is an `Objective` structure, a (msssim, mse, kld, msssim_grad) tuple as
+        objective.Objective.at() returns it, or None (a null pointer: CVAE_EINVAL)."""
+        if obj is not None and not isinstance(obj, Objective):
+            obj = Objective(*obj)
+        self._check(self.lib.cvae_loss_obj(self.h, B, _ptr(x), _ptr(mu), _ptr(logvar), _ptr(recon), _ptr(ws),
+                                           None if obj is None else C.byref(obj), _ptr(scalars), _ptr(d_recon),
+                                           _ptr(d_mu), _ptr(d_logvar), _stream()))
 
     def backward(self, B, x, pred, eps, params, logvar, recon, d_recon, d_mu, d_logvar, ws, grads, zero_padding=False):
         """zero_padding: `grads` is uninitialised memory — also write 0 into the alignment gaps (phase bit 3)."""

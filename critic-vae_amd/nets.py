@@ -66,15 +66,20 @@ class _ForwardFn(torch.autograd.Function):
 
 
 class _LossFn(torch.autograd.Function):
-    """cvae_loss behind autograd (VariationalAutoencoder.vae_loss, :53-62)."""
+    """cvae_loss behind autograd (VariationalAutoencoder.vae_loss, :53-62); obj: None, or the four values of an
+    objective.Objective (cvae_loss_obj)."""
 
     @staticmethod
-    def forward(ctx, vae, x, mu, logvar, recon):
+    def forward(ctx, vae, x, mu, logvar, recon, obj=None):
         B = x.shape[0]
         scalars = torch.empty(N_SCALARS, device=x.device)
         d_recon, d_mu, d_logvar = torch.empty_like(recon), torch.empty_like(mu), torch.empty_like(logvar)
-        vae.handle.loss(B, x, mu.contiguous(), logvar.contiguous(), recon.contiguous(), vae._workspace(B), scalars,
-                        d_recon, d_mu, d_logvar)
+        if obj is None:
+            vae.handle.loss(B, x, mu.contiguous(), logvar.contiguous(), recon.contiguous(), vae._workspace(B), scalars,
+                            d_recon, d_mu, d_logvar)
+        else:
+            vae.handle.loss_obj(B, x, mu.contiguous(), logvar.contiguous(), recon.contiguous(), vae._workspace(B), obj, scalars,
+                                d_recon, d_mu, d_logvar)
         ctx.save_for_backward(d_recon, d_mu, d_logvar)
         ctx.vae = vae
         vae.last_scalars = scalars
@@ -86,7 +91,7 @@ class _LossFn(torch.autograd.Function):
         o_recon, o_mu, o_logvar = torch.empty_like(d_recon), torch.empty_like(d_mu), torch.empty_like(d_logvar)
         ctx.vae.handle.scale_loss_grads(d_mu.shape[0], g.to(torch.float32).contiguous(), d_recon, d_mu, d_logvar,
                                         o_recon, o_mu, o_logvar)         # one launch, g stays on the device
-        return None, None, o_mu, o_logvar, o_recon
+        return None, None, o_mu, o_logvar, o_recon, None
 
 
 class VariationalEncoder(nn.Module):
@@ -175,6 +180,7 @@ class VariationalAutoencoder(nn.Module):
         bn[L.BN_TOTAL:] = 1.0
         self.register_buffer("bn_state", bn)
         self.num_batches_tracked = 0
+        self.objective = None      # an objective.Objective: vae_loss then runs cvae_loss_obj with its final() weights
         self.encoder = VariationalEncoder(self)
         self.decoder = Decoder(self)
         self.mssim_loss = MSSIM(self)
@@ -265,10 +271,16 @@ class VariationalAutoencoder(nn.Module):
         return mu + torch.randn_like(std) * std
 
     def vae_loss(self, x, mu, logvar, recon):
-        """vae_nets.py:53-62 (no empty_cache(): the library never allocates)."""
-        total = _LossFn.apply(self, self._prep(x), mu, logvar, recon)
+        """vae_nets.py:53-62 (no empty_cache(): the library never allocates).  With self.objective set (default None: the
+        reference's loss) the total is the objective's, with its final() weights — the autograd path follows no schedule —
+        recon_loss stays the unweighted MS-SSIM loss (0 at weight 0), KLD is weighted, and 'MSE' is F.mse_loss(recon, x)."""
+        if self.objective is None:
+            total = _LossFn.apply(self, self._prep(x), mu, logvar, recon)
+            s = self.last_scalars
+            return {"total_loss": total, "recon_loss": s[1].detach(), "KLD": s[2].detach()}
+        total = _LossFn.apply(self, self._prep(x), mu, logvar, recon, self.objective.final())
         s = self.last_scalars
-        return {"total_loss": total, "recon_loss": s[1].detach(), "KLD": s[2].detach()}
+        return {"total_loss": total, "recon_loss": s[1].detach(), "KLD": s[2].detach(), "MSE": s[13].detach()}
 
     def recon_samples(self, x, reward):
         """vae_nets.py:21-29."""

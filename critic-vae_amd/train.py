@@ -33,6 +33,7 @@ from . import synth
 from .fit import DeviceTrainer
 from .lib import N_SCALARS, SCORE_COLS, SYNC_DOUBLES, SYNC_POINTS
 from .nets import VariationalAutoencoder
+from .objective import Objective, compose
 
 
 def _reference_batches(dset, epoch_indices, starts, batch_size, device, critic_fn):
@@ -86,7 +87,8 @@ class FusedTrainer(DeviceTrainer):
     """One training step = forward + loss + backward + all-reduce + Adam on flat buffers."""
 
     def __init__(self, vae, lr=P.lr, betas=P.adam_betas, eps=P.adam_eps, process_group=None, world_size=1,
-                 overlap=None, reduce_dtype=None, sync=True, global_stats=None, skip_nonfinite=False, max_grad_norm=None):
+                 overlap=None, reduce_dtype=None, sync=True, global_stats=None, skip_nonfinite=False, max_grad_norm=None,
+                 objective=None):
         """Construction with world_size > 1 is a COLLECTIVE (sync_replicas: five broadcasts from rank 0) unless
         sync=False.
         overlap: all-reduce the gradient in three buckets while backward still runs (default for
@@ -106,7 +108,12 @@ class FusedTrainer(DeviceTrainer):
         whole flat gradient).  Every rank reads the same reduced gradient, so every rank decides alike and the replicas
         stay bit-identical.  step_count keeps counting calls of step(); Adam's bias correction uses the device's count of
         APPLIED steps.  A skipped step still ran forward in training mode: num_batches_tracked and the BatchNorm running
-        statistics are whatever forward wrote, as with a step torch's GradScaler skips."""
+        statistics are whatever forward wrote, as with a step torch's GradScaler skips.
+        objective: an objective.Objective, or None = the reference's MS-SSIM + 0.001 * KLD through cvae_loss, with the launches
+        and bits the step always had.  Otherwise the step calls cvae_loss_obj with objective.at(step_count): the four values
+        travel by value in the launch, a schedule costs no copy and no synchronisation.  The objective is saved and restored
+        with the trainer, so a run resumed in the middle of a warm-up continues exactly.  Not with global_stats: the fp64
+        record of the staged step has no slot for the squared-error sum, and its finish step carries the reference weights."""
         self.vae = vae
         self.h = vae.handle
         if overlap is None:
@@ -120,6 +127,13 @@ class FusedTrainer(DeviceTrainer):
         if global_stats is None:
             global_stats = os.environ.get("CVAE_DP_GLOBAL_STATS") == "1"
         self.global_stats = bool(global_stats)
+        if objective is not None and not isinstance(objective, Objective):
+            raise ValueError(f"objective {objective!r}: an objective.Objective or None")
+        if objective is not None and self.global_stats:
+            raise ValueError("objective with global_stats=True: the staged cross-rank step (cvae_loss_stage) sums a fixed fp64 "
+                             "record of the 11 MS-SSIM / KLD sums and finishes it with the reference weights; it has no slot for "
+                             "the squared-error sum.  Use per-rank losses (global_stats=False) or objective=None")
+        self.objective = objective
         self.buckets = [self.h.grad_bucket(ph) for ph in range(3)]
         self.lr, self.betas, self.eps = lr, betas, eps
         self._init_shared(skip_nonfinite, max_grad_norm)      # guard fields, step_count, val_history / best_val / val_stale
@@ -176,7 +190,11 @@ class FusedTrainer(DeviceTrainer):
         theta = v.theta.data
         v._stamp_workspace()               # an autograd graph of the same VAE still pending is now stale (nets.py)
         h.forward(B, x, pred, eps, theta, v.bn_state, self.mu, self.logvar, self.recon, self.ws, train=True)
-        h.loss(B, x, self.mu, self.logvar, self.recon, self.ws, self.scalars, self.d_recon, self.d_mu, self.d_logvar)
+        if self.objective is None:
+            h.loss(B, x, self.mu, self.logvar, self.recon, self.ws, self.scalars, self.d_recon, self.d_mu, self.d_logvar)
+        else:
+            h.loss_obj(B, x, self.mu, self.logvar, self.recon, self.ws, self.objective.at(self.step_count), self.scalars,
+                       self.d_recon, self.d_mu, self.d_logvar)
         if self.world_size > 1 and self.overlap:
             # bucketed all-reduce overlapped with backward (torch DDP's scheme on the flat buffer): the
             # three buckets are contiguous ranges, each reduced (sum, RCCL) while the next phase computes
@@ -265,14 +283,23 @@ class FusedTrainer(DeviceTrainer):
         """What a restart needs beside the two network files: the Adam moments (CPU copies), step_count, the applied / skipped
         counters (an unguarded trainer applied every step) and the VAE's num_batches_tracked.  With the networks restored by
         load_networks, a resumed run is exact at the step() level — the caller supplies eps; the generators that fit_* draw
-        shuffles and eps from are not saved."""
-        return {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(),
-                "num_batches_tracked": int(self.vae.num_batches_tracked), **self._shared_state()}
+        shuffles and eps from are not saved.  "objective": the objective's state_dict (absent with objective=None)."""
+        state = {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(),
+                 "num_batches_tracked": int(self.vae.num_batches_tracked), **self._shared_state()}
+        if self.objective is not None:
+            state["objective"] = self.objective.state_dict()
+        return state
 
     def load_state_dict(self, state):
         if state["m"].numel() != self.m.numel() or state["v"].numel() != self.v.numel():
             raise ValueError(f"trainer state of {state['m'].numel()} parameters, this trainer has {self.m.numel()}")
+        saved = state.get("objective")
+        if saved is not None and self.global_stats:
+            raise ValueError("the state carries an objective, this trainer runs the staged cross-rank step (global_stats=True)")
+        restored = None if saved is None else Objective().load_state_dict(saved)      # raises before anything changes
         self._load_shared_state(state)
+        if restored is not None:           # a state without one keeps what the trainer was built with
+            self.objective = restored
         self.m.copy_(state["m"])
         self.v.copy_(state["v"])
         self.vae.num_batches_tracked = int(state["num_batches_tracked"])
@@ -316,6 +343,11 @@ class FusedTrainer(DeviceTrainer):
           mean_total, mean_msssim, mean_kld, mean_mse: means of the per-image scores over the finite images; psnr = 10 log10(1 /
             mean_mse) (frames in [0, 1]); worst: the largest finite per-image total;
           per_image (only with per_image=True): the (N, 8) device tensor of cvae_score's rows, in dataset order.
+          objective, kld_raw (only when the trainer has an objective): objective.compose on this result — with the FINAL weights
+            (objective.final()), so that values from different steps of a warm-up compare: msssim * recon_loss (pooled; omitted,
+            not multiplied, at weight 0) + mse * mean_mse + kld * kld_raw, kld_raw = -0.5 * rec[10] / rec[11], the pooled KLD mean
+            without its weight.  mean_mse is the record's mean over finite_images ONLY: an image whose per-image MS-SSIM is NaN
+            is left out of it, also under a pure-MSE objective.  Computed on the host from the same one read.
         Draws nothing from any random generator and leaves parameters, Adam state, bn_state, num_batches_tracked, step_count
         and the guard record untouched; it overwrites the workspace and the trainer's mu / logvar / recon buffers, which a
         step() rewrites before reading.  With world_size > 1 every rank evaluates the dataset IT is given and no collective
@@ -349,6 +381,9 @@ class FusedTrainer(DeviceTrainer):
                "mean_total": mean(13), "mean_msssim": mean(14), "mean_kld": mean(15), "mean_mse": mean(16),
                "worst": float(rec[17]) if fin else float("nan")}
         out["psnr"] = float(10.0 * np.log10(1.0 / out["mean_mse"])) if fin and out["mean_mse"] > 0 else float("inf" if fin else "nan")
+        if self.objective is not None:
+            out["kld_raw"] = float(-0.5 * rec[10] / rec[11]) if rec[11] > 0 else float("nan")
+            out["objective"] = compose(self.objective, out)
         if per_image:
             out["per_image"] = rows
         return out
@@ -503,7 +538,8 @@ def build_parser():
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="C", help="fused trainer: clip the gradient to global "
                     "norm C (torch.nn.utils.clip_grad_norm_)")
     ap.add_argument("--resume", metavar="DIR", default=None, help=f"fused trainer: continue from DIR's network files and {TRAINER_FILE} "
-                    "(what --save wrote)")
+                    "(what --save wrote); the run continues under the objective saved there — objective flags are not needed, and "
+                    "flags that describe another objective are refused")
     ap.add_argument("--val-fraction", type=float, default=None, metavar="F", help="fused trainer: hold out whole trajectories until "
                     "they make up at least F of the curated entries (episodes.split_by_trajectory, seeded by --seed) and evaluate on them")
     ap.add_argument("--val-every", type=int, default=None, metavar="N", help="with --val-fraction: evaluate after every N optimizer "
@@ -512,12 +548,40 @@ def build_parser():
                     "DIR/best/ whenever the pooled validation total_loss improves (a non-finite value never does)")
     ap.add_argument("--patience", type=int, default=None, metavar="K", help="with --val-fraction: stop after K evaluations in a row "
                     "without an improvement")
+    ap.add_argument("--msssim-weight", type=float, default=None, metavar="W", help="-train, -second: weight of the MS-SSIM term "
+                    "(reference: 1).  Any of these six flags switches the loss to cvae_loss_obj; validation is then judged by the objective")
+    ap.add_argument("--mse-weight", type=float, default=None, metavar="W", help="weight of F.mse_loss(recon, x), the reference's "
+                    "commented-out reconstruction term (vae_nets.py:54; reference: 0)")
+    ap.add_argument("--kld-weight", type=float, default=None, metavar="BETA", help=f"weight of the KLD (reference: {P.kld_weight})")
+    ap.add_argument("--msssim-grad", choices=("reference", "used"), default=None, help="'used': differentiate only the level terms the "
+                    "MS-SSIM product uses — the same loss, and no NaN gradient from a negative unused level mean (README)")
+    ap.add_argument("--kld-warmup", type=int, default=None, metavar="N", help="fused trainer: KLD weight * min(1, (step + 1) / N)")
+    ap.add_argument("--msssim-from", type=int, default=None, metavar="N", help="fused trainer: no MS-SSIM term (and no pyramid) before "
+                    "optimizer step N; needs --mse-weight > 0")
     return ap
+
+
+def objective_from_args(args):
+    """The Objective the six objective flags describe, or None when none of them is given (the reference loss through cvae_loss).
+    Raises ValueError as Objective does."""
+    given = {"msssim": args.msssim_weight, "mse": args.mse_weight, "kld": args.kld_weight, "msssim_grad": args.msssim_grad,
+             "kld_warmup": args.kld_warmup, "msssim_from": args.msssim_from}
+    given = {k: v for k, v in given.items() if v is not None}
+    return Objective(**given) if given else None
 
 
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
+    try:
+        args.objective = objective_from_args(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if args.objective is not None and not (args.train or args.second):
+        ap.error("--msssim-weight, --mse-weight, --kld-weight, --msssim-grad, --kld-warmup and --msssim-from belong to -train and -second")
+    if args.objective is not None and args.train and args.episodes is None and (args.objective.kld_warmup or args.objective.msssim_from):
+        ap.error("--kld-warmup and --msssim-from belong to the fused trainer (-train --episodes, -second): the synthetic -train "
+                 "loop is the reference's own and follows no schedule")
     if args.max_grad_norm is not None and not args.max_grad_norm > 0:
         ap.error("--max-grad-norm needs a positive number")
     if args.val_fraction is None:
@@ -575,6 +639,9 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     vae = VariationalAutoencoder(max_batch=args.batch, seed=args.seed).to(device)
+    if args.objective is not None:
+        vae.objective = args.objective
+        print(args.objective.describe())
     dset = synthetic_dataset(args.synthetic)
     if args.critic == "random":
         critic_fn = lambda im: torch.rand(im.shape[0], 1, device=im.device)      # noqa: E731
@@ -604,14 +671,19 @@ def _fit_and_save(args, vae, ds, second):
     line, save_networks.  Nothing before it draws from the global generators (the networks are built from args.seed)."""
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
-    trainer = FusedTrainer(vae, skip_nonfinite=args.skip_nonfinite, max_grad_norm=args.max_grad_norm)
+    trainer = FusedTrainer(vae, skip_nonfinite=args.skip_nonfinite, max_grad_norm=args.max_grad_norm,
+                           objective=getattr(args, "objective", None))
     if args.resume:
+        given = trainer.objective
         load_networks(vae, args.resume, second=second)
         load_trainer(trainer, os.path.join(args.resume, TRAINER_FILE))
         print(f"resumed from {args.resume} at step {trainer.step_count}")
+        _check_resumed_objective(given, trainer, args.resume)
+    if trainer.objective is not None:
+        print(trainer.objective.describe())
     gen = torch.Generator(device=vae.theta.device)
     gen.manual_seed(args.seed)
-    ds, val_kw = _hold_out(args, ds, _ValidationLog(args, second), "entries", curated=True)
+    ds, val_kw = _hold_out(args, ds, _ValidationLog(args, second, by_objective=trainer.objective is not None), "entries", curated=True)
     t0 = time.time()
     scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen, **val_kw)
     torch.cuda.synchronize()
@@ -625,6 +697,22 @@ def _fit_and_save(args, vae, ds, second):
         print(f"saved {save_trainer(trainer, os.path.join(args.save, TRAINER_FILE))}")
     _print_guard(trainer)
     return ds
+
+
+def _check_resumed_objective(given, trainer, directory):
+    """--resume with objective flags: the checkpoint's objective must be the one the flags describe.  A run continues under the
+    objective it was started with — its schedules count from step 0 of that run, and best_val / val_stale were judged by that
+    objective's validation entry (total_loss for a run without one) — so a different one is refused, not silently replaced in
+    either direction.  Without flags the checkpoint's objective (or none) continues, with a line that says so."""
+    saved = trainer.objective if trainer.objective is not given else None       # load_trainer replaced it only if the state carried one
+    if given is None:
+        if trainer.objective is not None:
+            print(f"continuing with the objective saved in {directory}")
+        return
+    if saved is None or saved != given:
+        was = "none (the reference loss through cvae_loss, validation judged by total_loss)" if saved is None else repr(saved)
+        raise SystemExit(f"--resume {directory}: the checkpoint's objective is {was}, the flags give {given!r}.  A resumed run keeps "
+                         "its objective (schedules, best_val and --patience refer to it): drop the objective flags, or repeat the run's own")
 
 
 BEST_DIR = "best"
@@ -674,14 +762,18 @@ class _KeepBestLog:
 
 
 class _ValidationLog(_KeepBestLog):
-    """The VAE's: judged by the pooled total_loss; --keep-best writes the two network files."""
+    """The VAE's: judged by the pooled total_loss — by the result's "objective" entry when the run has an objective;
+    --keep-best writes the two network files."""
     key = "total_loss"
 
-    def __init__(self, args, second):
+    def __init__(self, args, second, by_objective=False):
         self.args, self.second = args, second
+        if by_objective:
+            self.key = "objective"
 
     def line(self, trainer, r):
-        return (f"loss {r['total_loss']:.6f} (recon {r['recon_loss']:.6f}, kld {r['KLD']:.6f}) over {r['images']} images, "
+        head = f"objective {r['objective']:.6f} " if self.key == "objective" else ""
+        return (f"{head}loss {r['total_loss']:.6f} (recon {r['recon_loss']:.6f}, kld {r['KLD']:.6f}) over {r['images']} images, "
                 f"{r['images'] - r['finite_images']} non-finite; per image: mean {r['mean_total']:.6f} worst {r['worst']:.6f} "
                 f"psnr {r['psnr']:.2f} dB")
 

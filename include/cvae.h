@@ -57,7 +57,8 @@ typedef struct cvae_config {
 enum { CVAE_OK = 0, CVAE_EINVAL = -1, CVAE_EUNSUPPORTED = -2, CVAE_ENOWS = -3 };
 
 /* number of loss scalars written by cvae_loss: [0]=total [1]=recon(MS-SSIM) [2]=KLD(weighted)
- * [3..7]=ssim level means [8..12]=cs level means [13..15]=reserved                           */
+ * [3..7]=ssim level means [8..12]=cs level means [13..15]=reserved (written as 0; cvae_loss_obj
+ * writes F.mse_loss(recon, x) to [13])                                                         */
 #define CVAE_N_SCALARS 16
 
 const char* cvae_version(void);
@@ -109,6 +110,43 @@ int cvae_decode(cvae_handle h, int32_t batch, const float* zcat, const float* pa
 int cvae_loss(cvae_handle h, int32_t batch, const float* x, const float* mu, const float* logvar,
               const float* recon, void* ws, float* scalars, float* d_recon, float* d_mu,
               float* d_logvar, void* stream);
+
+/*
+ * cvae_loss under a caller-chosen objective:
+ *   total = msssim_weight * MSSIM.forward(recon, x) + mse_weight * F.mse_loss(recon, x) + kld_weight * KLD
+ * (F.mse_loss is the reference's own commented-out reconstruction term, vae_nets.py:54; kld_weight is the beta of a beta-VAE).
+ * `obj` is HOST memory, read during the call and passed to the kernels by value: a per-step schedule costs no copy and no
+ * synchronisation.  Arguments, alignment (x, recon, d_recon 16-byte aligned) and null gradients as in cvae_loss.
+ * Scalars: [1] the UNWEIGHTED MS-SSIM loss 1 - prod, [3..12] the level means, [2] kld_weight * the raw KLD mean,
+ *   [13] F.mse_loss(recon, x): the mean over all 3 * batch * W^2 elements (differences and squares fp32, the sum fp64: one fp64
+ *   partial per workgroup, merged in a fixed order by the last workgroup to arrive — no floating-point atomics, the same call
+ *   gives the same bits), [0] = msssim_weight * [1] + mse_weight * [13] + [2] in fp32, [14], [15] = 0.
+ * Gradients: d_recon = msssim_weight * d[1]/d recon + mse_weight * 2 (recon - x) / (3 * batch * W^2), written once;
+ *   d_mu, d_logvar as cvae_loss with kld_weight in place of 0.001.
+ * msssim_grad: CVAE_MSGRAD_REFERENCE is autograd of vae_nets.py:243-247 as the reference runs it, including the 0 * w * x^(w-1)
+ *   of the level terms the product never uses (ssim_0..3, cs_4): NaN in EVERY element of d_recon as soon as one of those means
+ *   is negative, while the loss stays finite.  CVAE_MSGRAD_USED differentiates prod(cs_0..3 ^ w) * ssim_4 ^ (4 w_4) alone: the
+ *   same loss value (bit for bit), and only a negative USED level mean still gives NaN (loss and gradients, as in the reference).
+ * A term whose weight is exactly 0 is NOT COMPUTED, never multiplied by 0: at msssim_weight == 0 no pyramid kernel runs, no
+ *   level field of ws is touched, [1] and [3..12] are written as 0 (also where MS-SSIM would have been NaN), and one pixel
+ *   pass does the MSE, the KLD and their gradients; at mse_weight == 0 there is no pixel pass and [13] is 0.  With both
+ *   non-zero the pixel gradient and the squared-error sum are folded into the pass that writes d_recon.
+ * The reference objective {1, 0, 0.001f, CVAE_MSGRAD_REFERENCE} launches what cvae_loss launches and writes the same bits.
+ * CVAE_EINVAL: null obj, a weight that is NaN, infinite or negative, msssim_weight + mse_weight == 0, msssim_grad outside
+ * {0, 1}.  Every argument is checked before any device access; nothing allocates or synchronises.
+ * Out of scope: the staged cross-rank path (cvae_loss_stage keeps the reference objective: its fp64 record has no slot for the
+ * squared-error sum), an L1 term, and — in validation — a per-image MSE over non-finite images.
+ */
+typedef struct cvae_objective {
+    float   msssim_weight;   /* reference: 1     */
+    float   mse_weight;      /* reference: 0     */
+    float   kld_weight;      /* reference: 0.001 */
+    int32_t msssim_grad;     /* CVAE_MSGRAD_REFERENCE or CVAE_MSGRAD_USED */
+} cvae_objective;
+enum { CVAE_MSGRAD_REFERENCE = 0, CVAE_MSGRAD_USED = 1 };
+int cvae_loss_obj(cvae_handle h, int32_t batch, const float* x, const float* mu, const float* logvar,
+                  const float* recon, void* ws, const cvae_objective* obj, float* scalars, float* d_recon,
+                  float* d_mu, float* d_logvar, void* stream);
 
 /*
  * Per-image scores and the pooled loss of a held-out set (no reference counterpart: vae.py never evaluates; the values are the
@@ -587,7 +625,9 @@ int cvae_inject_zcat(cvae_handle h, int32_t n_images, int32_t n_rewards, const f
  * "zcat", "h", "d_*" ...) for tests; -1 if unknown OR not allocated in this configuration: "d_y0" does not exist
  * (block 0's BatchNorm backward runs inside the E1 weight-gradient kernel), and in precision mode 1 "dout4" has no
  * storage and the "y0" slot is STALE unless a block-0 |gamma| is < 1e-2 (the device decides per step) — do not read it
- * otherwise.  Slots hold bf16 elements in precision mode 1. */
+ * otherwise.  Slots hold bf16 elements in precision mode 1.  "ms": the MS-SSIM region of cvae_loss / cvae_loss_obj / cvae_score,
+ * cvae_op_msssim_ws_floats(batch) floats: the level pyramids, fields and partials, then — its last 832 floats — the fp64 slab
+ * (704), the coefficients (64) and the arrival ticket (64), which is all a cvae_loss_obj at msssim_weight 0 touches. */
 int64_t cvae_ws_offset(cvae_handle h, int32_t batch, const char* name);
 
 /* Which kernel family the forward (dgrad = 0) or input-gradient (dgrad = 1) pass of encoder conv layer 1..3 (E2..E4, nn.Conv2d at
