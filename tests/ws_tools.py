@@ -746,3 +746,227 @@ def bn_fwd_ref(yw, coef, tanh, bf16):
     if bf16:
         b = BF16 * want.abs() + (1 + BF16) * b
     return want, b, nw, pos
+
+
+# ---- MS-SSIM / KLD / scores (msssim.hip, msssim_finish.h, score.hip): launch geometry, replica inputs and float64 references ----
+MS_LDS = 160 * 1024               # LDS of a compute unit (msssim.hip: byLds = 160 KiB / (SMEM + 256))
+MS_BASES = 5                      # base pairs of a replica batch: image i is base[i % MS_BASES]
+# recon = a x + (1 - a) u per base pair, u uniform on [0, MS_NOISE_TOP).  With u on [0, 1) every pair has the brightness of its x, and the
+# levels of 8 and 4 pixels, where the zero padding and C2 outweigh the image, are 1 - 1e-5 for EVERY a: a plane taken from the neighbouring
+# image moves no level mean by even one fp32 ulp at the large batches (tests/test_host_msssim_tools.py, condition (c)).  A dim u makes the
+# brightness ratio a + MS_NOISE_TOP (1 - a) differ per pair; a spread over [0.1, 0.9] in steps of 0.2, ordered so that neighbours in the
+# batch (k, k + 1 mod 5) are two steps apart, then moves some mean of every level by 11 ulps or more at B = 5462.
+MS_ALPHAS = (0.9, 0.5, 0.1, 0.7, 0.3)
+MS_NOISE_TOP = 0.1
+MS_CONFIG_BATCH = {64: 2048, 128: 1024}    # the bf16 configs' batches
+EXPF_ULPS = 3                     # expf of the device library: the OpenCL bound it is built to; an fp32 ulp is at most 2 U32 |v|
+
+
+def ms_plane_geom(S):
+    """MsP<S> of msssim.hip: the whole-plane kernel's threads per plane, planes per workgroup and LDS bytes."""
+    NTP = S * S // 4
+    PPW = 1 if NTP >= 256 else 256 // NTP
+    DAS, DCS, TAS, TR = S + 14, S + 12, S + 2, S + 10
+    LIN = S * (2 * DAS + DCS)
+    TA = 2 * TR * TAS
+    TMP = 2 * TA + TR * S
+    return dict(NTP=NTP, PPW=PPW, NT=NTP * PPW, LIN=LIN, TA=TA, TMP=TMP, SMEM=PPW * (LIN + TMP) * 4)
+
+
+def ms_resident_groups(S, cus):
+    """Workgroups of msssim_plane_kernel<S> in one residency of the chip: ms_fwd's grid cap."""
+    g = ms_plane_geom(S)
+    return cus * min(MS_LDS // (g["SMEM"] + 256), 2048 // g["NT"])
+
+
+def ms_level_facts(W, B, cus=256):
+    """Per pyramid level of a batch of B frames W wide: the kernel, plane groups, grid and the trips of the busiest (and idlest)
+    workgroup.  128-wide level 0 is msssim_stream_kernel: one plane per group, one workgroup per compute unit."""
+    P, out = 3 * B, []
+    for l in range(5):
+        S = W >> l
+        if S == 128:
+            ppw, resident, kernel = 1, cus, "stream"
+        else:
+            ppw, resident, kernel = ms_plane_geom(S)["PPW"], ms_resident_groups(S, cus), "plane"
+        groups = _cdiv(P, ppw)
+        grid = min(groups, resident)
+        out.append(dict(level=l, S=S, kernel=kernel, PPW=ppw, P=P, groups=groups, resident=resident, grid=grid,
+                        trips=_cdiv(groups, grid), min_trips=groups // grid, last_group=P - (groups - 1) * ppw))
+    return out
+
+
+# edges: "below" = the largest batch whose level still runs one group per workgroup, "loops" = the first batch at which a workgroup
+# walks a second group; "config" = the bf16 configs' batch (MS_CONFIG_BATCH), level = the deepest level that loops there
+MS_EDGES = ("below", "loops", "config")
+MS_CASES = ([(64, l, e) for l in range(5) for e in ("below", "loops")] + [(64, 3, "config")]
+            + [(128, l, e) for l in range(1, 5) for e in ("below", "loops")] + [(128, 3, "config")])
+MS_RAGGED = (1, 21, 22, 43, 64)   # P = 3, 63, 66, 129, 192: one short of a 64-group, two over, one plane in the last group at 4 / 16 / 64, all full
+
+
+def ms_case_batch(W, level, edge, cus=256):
+    """The batch of a case, from this device's compute-unit count."""
+    assert edge in MS_EDGES, edge
+    if edge == "config":
+        return MS_CONFIG_BATCH[W]
+    B = next(b for b in range(1, 1 << 15) if ms_level_facts(W, b, cus)[level]["trips"] > 1)
+    return B - 1 if edge == "below" else B
+
+
+def ms_assert_edge(W, level, edge, B, cus):
+    """The case still sits on the edge it is named for, on this device's compute-unit count.  Returns ms_level_facts."""
+    f = ms_level_facts(W, B, cus)
+    if edge == "below":
+        ok = f[level]["trips"] == 1 and ms_level_facts(W, B + 1, cus)[level]["trips"] == 2
+    elif edge == "loops":
+        ok = f[level]["trips"] == 2 and ms_level_facts(W, B - 1, cus)[level]["trips"] == 1
+    else:               # four levels loop, `level` is the deepest of them and its workgroups end unevenly
+        looping = [x["level"] for x in f if x["trips"] > 1]
+        ok = looping == [0, 1, 2, 3] and level == 3 and f[level]["groups"] % f[level]["grid"] != 0 and f[level]["min_trips"] < f[level]["trips"]
+    if W == 128 and level == 1 and edge != "config":      # the stream kernel's edge is the 64-wide plane kernel's
+        ok = ok and f[0]["trips"] == f[1]["trips"] and f[0]["kernel"] == "stream"
+    assert ok, f"{W} wide, level {level}, B = {B}: not on the edge '{edge}' with {cus} compute units: {f}"
+    return f
+
+
+def ms_counts(B, n=MS_BASES):
+    """Occurrences of each base image in a replica batch of B (image i is base i % n), float64."""
+    return torch.tensor([(B - k + n - 1) // n for k in range(n)], dtype=torch.float64)
+
+
+def ms_base_pairs(W, seed=0):
+    """MS_BASES base pairs built the way test_gpu_objective.smooth_case builds a batch, recon = a x + (1 - a) u with a = MS_ALPHAS[k]
+    (u dimmer than x, see MS_ALPHAS), and a latent per base image: x, mu, logvar, recon as CPU fp32 tensors."""
+    g = torch.Generator().manual_seed(77000 + 10 * W + seed)
+    x = torch.rand(MS_BASES, 3, W, W, generator=g)
+    u = torch.rand(MS_BASES, 3, W, W, generator=g) * MS_NOISE_TOP
+    a = torch.tensor(MS_ALPHAS).view(-1, 1, 1, 1)
+    recon = (a * x + (1 - a) * u).contiguous()
+    mu = torch.randn(MS_BASES, 32, generator=g) * 0.5
+    logvar = torch.randn(MS_BASES, 32, generator=g) * 0.3
+    return x, mu, logvar, recon
+
+
+def ms_inputs(tag, W, B):
+    """The "pos" / "neg" / "nan" pairs of test_gpu_ops._ms_inputs at any shape (img1, img2), and "unused": a pair whose ssim means of the
+    fine levels are negative while every cs mean and ssim_4 stay positive (only levels the product never uses are negative)."""
+    from critic_vae_amd import synth
+    b = torch.from_numpy(synth.uniform(5, f"ms/{tag}/b", (B, 3, W, W)))
+    if tag == "unused":               # left half flipped (bright, anti-correlated: cs < 0 where lum = 1), right half centred (cs = 1 where lum = 0)
+        a = torch.cat((1 - b[..., :W // 2], b[..., W // 2:] - 0.5), dim=-1)
+        return a.clone(), b
+    if tag == "nan":
+        a = 0.5 - b + 0.01 * torch.from_numpy(synth.uniform(5, f"ms/{tag}/a", (B, 3, W, W)))
+    else:
+        a = torch.from_numpy(synth.uniform(5, f"ms/{tag}/a", (B, 3, W, W), -1.0 if tag == "neg" else 0.0, 1.0))
+    return a.clone(), b
+
+
+def ms_oracle64(img1, img2):
+    """oracle.cvae_oracle.msssim in float64: its level function and window on double tensors.  Returns (loss, ssim[5], cs[5])."""
+    import torch.nn.functional as F
+    from oracle import cvae_oracle as orc
+    window = orc.ms_window_2d(img1.shape[1]).double()
+    w = torch.tensor(orc.MS_WEIGHTS, dtype=torch.float32).double()
+    a, b, sims, css = img1.double(), img2.double(), [], []
+    for _ in range(5):
+        s, c = orc.ssim_level(a, b, window)
+        sims.append(s)
+        css.append(c)
+        a, b = F.avg_pool2d(a, (2, 2)), F.avg_pool2d(b, (2, 2))
+    sims, css = torch.stack(sims), torch.stack(css)
+    return 1 - torch.prod((css ** w)[:-1] * (sims ** w)[-1]), sims, css
+
+
+def ms_plane_means64(img1, img2):
+    """The oracle's five levels restated per plane, float64: (ssim, cs), each (N, 3, 5) = the mean of the level's map over one plane."""
+    import torch.nn.functional as F
+    from oracle import cvae_oracle as orc
+    a, b = img1.double(), img2.double()
+    c = a.shape[1]
+    window = orc.ms_window_2d(c).double()
+    conv = lambda t: F.conv2d(t, window, padding=orc.MS_WINDOW // 2, groups=c)      # noqa: E731
+    ps, pc = [], []
+    for _ in range(5):
+        mu1, mu2 = conv(a), conv(b)
+        s1, s2, s12 = conv(a * a) - mu1 * mu1, conv(b * b) - mu2 * mu2, conv(a * b) - mu1 * mu2
+        v1, v2 = 2.0 * s12 + orc.C2, s1 + s2 + orc.C2
+        pc.append((v1 / v2).mean(dim=(2, 3)))
+        ps.append((((2 * mu1 * mu2 + orc.C1) * v1) / ((mu1 * mu1 + mu2 * mu2 + orc.C1) * v2)).mean(dim=(2, 3)))
+        a, b = F.avg_pool2d(a, (2, 2)), F.avg_pool2d(b, (2, 2))
+    return torch.stack(ps, 2), torch.stack(pc, 2)
+
+
+def ms_loss_from_means(sims, css):
+    """1 - prod_{l<4}(cs_l^w_l * ssim_4^w_4): the oracle's product, on float64 batch means."""
+    from oracle import cvae_oracle as orc
+    w = torch.tensor(orc.MS_WEIGHTS, dtype=torch.float32).double()
+    return 1 - torch.prod((css ** w)[:-1] * (sims ** w)[-1])
+
+
+def ms_replica_ref(recon, x, counts=None):
+    """float64 MS-SSIM loss of the batch in which pair k = (recon[k], x[k]) occurs counts[k] times (default: once each): the batch mean
+    of level l is sum_k n_k m[k, l] / B with m the per-image level means.  Returns loss, ssim[5], cs[5] (batch means), grad (the gradient
+    of ONE occurrence of each pair w.r.t. its recon: autograd's gradient of the base image divided by n_k; zero rows where n_k = 0),
+    plane_ssim / plane_cs (N, 3, 5)."""
+    n = torch.ones(recon.shape[0], dtype=torch.float64) if counts is None else counts.double()
+    r = recon.double().clone().requires_grad_(True)
+    ps, pc = ms_plane_means64(r, x)
+    B = n.sum()
+    sims = (n[:, None] * ps.mean(1)).sum(0) / B
+    css = (n[:, None] * pc.mean(1)).sum(0) / B
+    loss = ms_loss_from_means(sims, css)
+    loss.backward()
+    grad = r.grad / n.clamp_min(1.0).view(-1, 1, 1, 1)
+    return dict(loss=loss.detach(), ssim=sims.detach(), cs=css.detach(), grad=grad, plane_ssim=ps.detach(), plane_cs=pc.detach())
+
+
+def f32_ulp(v):
+    """The spacing of fp32 at |v| (float64 tensor), at least the smallest normal's."""
+    v = torch.as_tensor(v, dtype=torch.float64).abs().clamp_min(2.0 ** -126)
+    return 2.0 ** (torch.floor(torch.log2(v)) - 23)
+
+
+def ms_swap_shift(ref, counts):
+    """Condition (c) of the replica inputs: at the batch with these counts, compute ONE plane of an occurrence of base image k from the
+    same plane of image k + 1 (its neighbour in the batch) at level l.  Returns (MS_BASES, 3, 5): the larger of the two shifts of that
+    level's batch means (ssim, cs) in fp32 ulps of the mean."""
+    B3 = 3.0 * counts.sum()
+    out = []
+    for p, m in ((ref["plane_ssim"], ref["ssim"]), (ref["plane_cs"], ref["cs"])):
+        out.append(((torch.roll(p, -1, 0) - p).abs() / B3) / f32_ulp(m))
+    return torch.maximum(out[0], out[1])
+
+
+# ---- KLD (msssim_finalize_kernel): inputs, float64 reference and the bounds of the kernel's fp32 arithmetic ----
+KW32 = 0.0010000000474974513      # MS_REF_KW = 0.001f as the kernel holds it
+
+
+def kld_case(B, seed=0):
+    """mu ~ 0.5 N(0, 1), logvar ~ U(-1, 1), every image distinct: CPU fp32 (B, 32)."""
+    g = torch.Generator().manual_seed(88000 + 7 * B + seed)
+    return torch.randn(B, 32, generator=g) * 0.5, torch.rand(B, 32, generator=g) * 2 - 1
+
+
+def kld_ref(mu, logvar, kw=KW32):
+    """float64 weighted KLD, d_mu, d_logvar and what the kernel's arithmetic may be off by (tests/test_gpu_msssim_ops.py, (f)).
+      term   t = 1.0f + lv - m * m - e, e = expf(lv): the sum 1 + lv, the product (none if contracted), the difference, expf's
+             EXPF_ULPS ulps (<= 2 U32 e each), the last difference: U32 (|1 + lv| + m^2 + |1 + lv - m^2| + |t|) + 2 EXPF_ULPS U32 e
+      KLD    (float)(-0.5 k / B) * kw on the fp64 sum k of the fp32 terms: the terms' errors, 2^-45 of sum |t| for the fp64
+             additions in any order, then the cast and the product: 2 U32 |KLD|
+      d_mu   kw * m * (1.0f / (float)B): the reciprocal, two products: 3 U32 |d_mu|
+      d_lv   kw * 0.5f * (e - 1.0f) * (1.0f / (float)B): expf's error enters e - 1 in full (the cancellation near lv = 0), then the
+             difference, the reciprocal and two products (kw * 0.5f is exact): kw / (2 B) 2 EXPF_ULPS U32 e + 4 U32 |d_lv|
+    Returns a dict; `terms` (B,) is each image's float64 sum of its 32 terms."""
+    m, lv = mu.double(), logvar.double()
+    B = m.shape[0]
+    e = lv.exp()
+    t = 1 + lv - m * m - e
+    kld = kw * -0.5 * t.sum() / B
+    t_err = U32 * ((1 + lv).abs() + m * m + (1 + lv - m * m).abs() + t.abs()) + 2 * EXPF_ULPS * U32 * e
+    kld_b = 0.5 * kw / B * (t_err.sum() + 2.0 ** -45 * t.abs().sum()) + 2 * U32 * kld.abs()
+    d_mu, d_lv = kw * m / B, kw * 0.5 * (e - 1) / B
+    slack = 1 + 2.0 ** -20            # second-order terms of the products of roundings
+    return dict(kld=kld, kld_bound=kld_b * slack, d_mu=d_mu, d_mu_bound=3 * U32 * d_mu.abs() * slack + 2.0 ** -149,
+                d_logvar=d_lv, d_logvar_bound=(0.5 * kw / B * 2 * EXPF_ULPS * U32 * e + 4 * U32 * d_lv.abs()) * slack + 2.0 ** -149,
+                terms=t.sum(1))
