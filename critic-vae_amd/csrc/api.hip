@@ -1072,46 +1072,79 @@ int cvae_probe_read(cvae_handle h, int32_t id, float* ms_host, int32_t cap) {
 // ------------------------------ per-op entry points ------------------------------
 // Layers 1..4 follow the handle's precision in the fp32-emulation modes (2, 3): the kernels the step runs there, on fp32 tensors.
 // Their scratch is [packed 3-split weights (the step's wpack block, only the layer's own slots written) | everything else].
+// bf16 mode (1): layers 1..8 run what the step runs, on tensors in the handle's storage type (bf16 activations and activation
+// gradients; fp32 weights, biases, their gradients and recon / d_recon).  Scratch = [packed bf16 weights (the step's wpack block,
+// only the layer's own slots written) | collapsed weights of D1..D3 | everything else].
 static bool op_emulated(cvae_handle h, int layer) { return h->cfg.precision >= 2 && layer >= 1 && layer <= 4 && use_bf16(h, layer); }
-static int64_t op_pack_floats(cvae_handle h) { return h->cfg.precision >= 2 ? align_up(conv_bf16_pack_floats(3), 64) : 0; }
+static bool op_bf16(cvae_handle h, int layer) { return h->cfg.precision == 1 && layer >= 1 && layer <= 7 && use_bf16(h, layer); }
+static int64_t op_pack_floats(cvae_handle h) { return h->cfg.precision != 0 ? align_up(conv_bf16_pack_floats(bf16_splits(h)), 64) : 0; }
 static int op_pack_layer(cvae_handle h, int layer, const float* wt, void* scratch, hipStream_t st) {
-    if (!scratch) { cvae_set_error("per-op conv, layer %d: the fp32-emulation modes pack the weights into scratch (null)", layer); return CVAE_EINVAL; }
+    if (!scratch) { cvae_set_error("per-op conv, layer %d: the bf16 and fp32-emulation modes pack the weights into scratch (null)", layer); return CVAE_EINVAL; }
     const float* wl[4] = {nullptr, nullptr, nullptr, nullptr};          // the packer skips the layers it is not given
     wl[layer - 1] = wt;
     return launch_pack_w_bf16(wl, (float*)scratch, bf16_splits(h), st);
+}
+// bf16 mode, D1..D3: collapse the layer's 5x5 weights into the scratch behind the pack block, then pack them (both orientations)
+static int op_pack_up_layer(cvae_handle h, int layer, const float* wt, void* scratch, hipStream_t st) {
+    if (!scratch) { cvae_set_error("per-op conv, layer %d: bf16 mode collapses and packs the weights into scratch (null)", layer); return CVAE_EINVAL; }
+    float* wc = (float*)scratch + op_pack_floats(h);
+    RC(launch_collapse_w(layer, wt, wc, st));
+    const float* wcs[3] = {nullptr, nullptr, nullptr};
+    wcs[layer - 5] = wc;
+    return launch_pack_up_bf16(wcs, (float*)scratch, bf16_splits(h), st);
 }
 
 int cvae_op_conv_fwd(cvae_handle h, int32_t layer, int32_t B, const float* in, const float* wt, const float* bias,
                      float* out, float* bn_partials, void* scratch, void* stream) {
     const int W = h->cfg.width;
-    if (layer == 0) return launch_e1_fwd(W, B, in, wt, bias, out, bn_partials, (hipStream_t)stream, io_bf16(h));   // y in the handle's storage type
-    if (layer == 8) return launch_d4_fwd(W, B, in, wt, bias, out, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (layer == 0) return launch_e1_fwd(W, B, in, wt, bias, out, bn_partials, st, io_bf16(h));   // y in the handle's storage type
+    if (layer == 8) return launch_d4_fwd(W, B, in, wt, bias, out, st, io_bf16(h));                // o3 in the handle's storage type
+    if (op_bf16(h, layer)) {
+        if (layer >= 5) {
+            RC(op_pack_up_layer(h, layer, wt, scratch, st));
+            return launch_conv_up_fwd_bf16(layer, W, 1, B, in, (float*)scratch, bias, out, st);
+        }
+        RC(op_pack_layer(h, layer, wt, scratch, st));          // fails on a null scratch, before any pointer is formed from it
+        return launch_conv_fwd_bf16(layer, W, 1, B, in, (float*)scratch, bias, out, bn_partials, (float*)scratch + op_pack_floats(h), st, nullptr);
+    }
     if (layer >= 5) {
         float* wc = (float*)scratch;
-        RC(launch_collapse_w(layer, wt, wc, (hipStream_t)stream));
-        return launch_conv_up_fwd(layer, W, B, in, wc, bias, out, wc + conv_up_wc_floats(layer), (hipStream_t)stream);
+        RC(launch_collapse_w(layer, wt, wc, st));
+        return launch_conv_up_fwd(layer, W, B, in, wc, bias, out, wc + conv_up_wc_floats(layer), st);
     }
     if (op_emulated(h, layer)) {
-        RC(op_pack_layer(h, layer, wt, scratch, (hipStream_t)stream));
-        return launch_conv_fwd_bf16(layer, W, bf16_mode(h), B, in, (float*)scratch, bias, out, bn_partials, (float*)scratch + op_pack_floats(h), (hipStream_t)stream, nullptr);
+        RC(op_pack_layer(h, layer, wt, scratch, st));
+        return launch_conv_fwd_bf16(layer, W, bf16_mode(h), B, in, (float*)scratch, bias, out, bn_partials, (float*)scratch + op_pack_floats(h), st, nullptr);
     }
-    return launch_conv_fwd(layer, W, B, in, wt, bias, out, bn_partials, (float*)scratch, (hipStream_t)stream);
+    return launch_conv_fwd(layer, W, B, in, wt, bias, out, bn_partials, (float*)scratch, st);
 }
 
 int cvae_op_conv_dgrad(cvae_handle h, int32_t layer, int32_t B, const float* dout, const float* wt,
                        const float* mask_src, float* din, void* scratch, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (op_bf16(h, layer)) {
+        if (layer >= 5) {
+            RC(op_pack_up_layer(h, layer, wt, scratch, st));
+            return launch_conv_up_dgrad_bf16(layer, h->cfg.width, 1, B, dout, (float*)scratch, mask_src, din, st);
+        }
+        RC(op_pack_layer(h, layer, wt, scratch, st));
+        return launch_conv_dgrad_bf16(layer, h->cfg.width, 1, B, dout, (float*)scratch, din, (float*)scratch + op_pack_floats(h), st);
+    }
     if (layer >= 5) {
         float* wc = (float*)scratch;
-        RC(launch_collapse_w(layer, wt, wc, (hipStream_t)stream));
-        return launch_conv_up_dgrad(layer, h->cfg.width, B, dout, wc, mask_src, din, wc + conv_up_wc_floats(layer), (hipStream_t)stream);
+        RC(launch_collapse_w(layer, wt, wc, st));
+        return launch_conv_up_dgrad(layer, h->cfg.width, B, dout, wc, mask_src, din, wc + conv_up_wc_floats(layer), st);
     }
     if (op_emulated(h, layer)) {
-        RC(op_pack_layer(h, layer, wt, scratch, (hipStream_t)stream));
-        return launch_conv_dgrad_bf16(layer, h->cfg.width, bf16_mode(h), B, dout, (float*)scratch, din, (float*)scratch + op_pack_floats(h), (hipStream_t)stream);
+        RC(op_pack_layer(h, layer, wt, scratch, st));
+        return launch_conv_dgrad_bf16(layer, h->cfg.width, bf16_mode(h), B, dout, (float*)scratch, din, (float*)scratch + op_pack_floats(h), st);
     }
-    return launch_conv_dgrad(layer, h->cfg.width, B, dout, wt, mask_src, din, (float*)scratch, (hipStream_t)stream);
+    return launch_conv_dgrad(layer, h->cfg.width, B, dout, wt, mask_src, din, (float*)scratch, st);
 }
 
+// [pack block | the step's scratch, which starts with room for one layer's collapsed weights and covers the split-K and weight-gradient
+// slabs of every precision's launchers and d4_bwd's workspace (carve)]
 int64_t cvae_op_scratch_floats(cvae_handle h, int32_t B) {
     const WsLayout w = carve(h, B);
     return w.total - w.scratch + op_pack_floats(h);
@@ -1123,17 +1156,47 @@ int cvae_op_conv_wgrad(cvae_handle h, int32_t layer, int32_t B, const float* in,
     hipStream_t st = (hipStream_t)stream;
     float* sc = (float*)scratch;
     if (layer == 0) return launch_e1_wgrad(W, B, in, dout, dw, dbias, sc, st);
-    if (layer >= 5) return launch_conv_up_wgrad(layer, W, B, in, dout, dw, dbias, sc, st);
-    if (op_emulated(h, layer)) {
-        if (!sc) { cvae_set_error("per-op conv_wgrad, layer %d: null scratch", layer); return CVAE_EINVAL; }
-        return conv_wgrad(h, layer, B, in, dout, dw, dbias, sc, st);
-    }
+    if ((op_emulated(h, layer) || op_bf16(h, layer)) && !sc) { cvae_set_error("per-op conv_wgrad, layer %d: null scratch", layer); return CVAE_EINVAL; }
+    if (layer >= 5) return launch_conv_up_wgrad(layer, W, B, in, dout, dw, dbias, sc, st, use_bf16_wgrad(h, layer));      // bf16 mode: the step's bf16 kernel
+    if (op_emulated(h, layer) || op_bf16(h, layer)) return conv_wgrad(h, layer, B, in, dout, dw, dbias, sc, st);
     return launch_conv_wgrad(layer, W, B, in, dout, dw, dbias, sc, st);
 }
 
+// bf16 mode: o3 / d_o3 in bf16, the Tanh backward applied while the kernel stages (`dout` is not written and may be null)
 int cvae_op_d4_bwd(cvae_handle h, int32_t B, const float* o3, const float* d_recon, const float* recon, const float* wt,
                    float* dout, float* d_o3, float* dw, float* db, void* scratch, void* stream) {
-    return launch_d4_bwd(h->cfg.width, B, o3, d_recon, recon, wt, dout, d_o3, dw, db, (float*)scratch, (hipStream_t)stream);
+    return launch_d4_bwd(h->cfg.width, B, o3, d_recon, recon, wt, dout, d_o3, dw, db, (float*)scratch, (hipStream_t)stream, io_bf16(h));
+}
+
+// 128-pixel tiles behind one BatchNorm partial row of cvae_op_conv_fwd (the route table's; 1 for the per-tile kernels and layer 0)
+int32_t cvae_op_conv_tiles_per_partial(cvae_handle h, int32_t layer, int32_t B) {
+    if (!h || layer < 0 || layer > 3 || B < 1) { cvae_set_error("cvae_op_conv_tiles_per_partial: null handle, layer %d outside [0, 3] or batch %d below 1", layer, B); return CVAE_EINVAL; }
+    if (layer == 0 || !use_bf16(h, layer)) return 1;
+    return conv_route(h->cfg.precision, layer, h->cfg.width, false, B).tilesPerPartial;
+}
+
+// (tiles, splits, tiles per split) of cvae_op_conv_wgrad's kernel on a bf16 handle, from the launchers' own split arithmetic (no launch)
+int cvae_op_conv_wgrad_plan(cvae_handle h, int32_t layer, int32_t B, int32_t* out) {
+    if (!h || !out || B < 1) { cvae_set_error("cvae_op_conv_wgrad_plan: null handle or output, or batch %d below 1", B); return CVAE_EINVAL; }
+    if (!op_bf16(h, layer)) { cvae_set_error("cvae_op_conv_wgrad_plan: layer %d on this handle does not run a bf16 weight-gradient kernel (bf16 handles, layers 1..7)", layer); return CVAE_EUNSUPPORTED; }
+    int plan[3] = {0, 0, 0};
+    RC(layer >= 5 ? conv_up_wgrad_bf16_plan(layer, h->cfg.width, B, plan) : conv_wgrad_bf16_plan(layer, h->cfg.width, B, plan));
+    for (int i = 0; i < 3; ++i) out[i] = plan[i];
+    return CVAE_OK;
+}
+
+// the statistics half of cvae_op_bn_pool_act_fwd, on partial rows of `tiles_per_partial` tiles each
+int cvae_op_bn_fwd_finalize(cvae_handle h, int32_t layer, int32_t B, const float* bn_partials, int32_t tiles_per_partial,
+                            const float* gamma, const float* beta, float* run_mean, float* run_var, float* coef,
+                            void* scratch, int32_t train, void* stream) {
+    if (!h || layer < 0 || layer > 3 || B < 1 || !gamma || !beta || !run_mean || !run_var || !coef || !scratch || (train && !bn_partials)) {
+        cvae_set_error("cvae_op_bn_fwd_finalize: null argument, layer %d outside [0, 3] or batch %d below 1", layer, B); return CVAE_EINVAL;
+    }
+    if (tiles_per_partial != 1 && tiles_per_partial != 2 && tiles_per_partial != 4 && tiles_per_partial != 8) {
+        cvae_set_error("cvae_op_bn_fwd_finalize: %d tiles per partial (1, 2, 4 or 8)", tiles_per_partial); return CVAE_EINVAL;
+    }
+    return launch_bn_fwd_finalize(layer, h->cfg.width, B, bn_partials, gamma, beta, run_mean, run_var, coef, (float*)scratch, train,
+                                  (hipStream_t)stream, tiles_per_partial);
 }
 
 int cvae_op_bn_pool_act_fwd(cvae_handle h, int32_t layer, int32_t B, const float* y, const float* bn_partials,

@@ -294,7 +294,11 @@ int launch_conv_up_dgrad(int layer, int width, int B, const float* dout, const f
 int64_t conv_up_wgrad_ws_floats(int layer, int width, int B);
 int launch_conv_up_wgrad(int layer, int width, int B, const float* in, const float* dout, float* dw,
                          float* dbias, float* ws, hipStream_t st, bool bf16 = false);
-int launch_up_wgrad_bf16_main(int layer, int width, int B, const float* in, const float* dout, float* slab, int Smax, int* S_out, hipStream_t st);
+int launch_up_wgrad_bf16_main(int layer, int width, int B, const float* in, const float* dout, float* slab, int Smax, int* S_out, hipStream_t st,
+                              int* plan = nullptr);      // plan != null: no launch, plan = (tiles, splits, tiles per split)
+// (tiles, splits, tiles per split) of the bf16 weight-gradient kernels at a batch, from the launchers' own arithmetic (no launch; layers 5..7 ask the device's CU count)
+int conv_wgrad_bf16_plan(int layer, int width, int B, int plan[3]);       // layers 1..4
+int conv_up_wgrad_bf16_plan(int layer, int width, int B, int plan[3]);    // layers 5..7
 // bn.hip
 int bn_num_tiles(int layer, int width, int B);
 int launch_bn_fwd_finalize(int layer, int width, int B, const float* bnpart, const float* gamma,

@@ -1051,7 +1051,7 @@ static int wgrad_bf16_splits(int B, int blocksPerSplit, int targetWgs, int* tile
 
 template <int CIN, int COUT, int H>
 static int run_wgrad_bf16(int B, const float* in, const float* dout, float* dw, float* dbias, float* ws, hipStream_t st,
-                          int64_t* need) {
+                          int64_t* need, int* plan = nullptr) {
     using T = WtTile<H>;
     int tps, numTiles;
     constexpr int COB = (CIN == 32 && COUT == 64) ? 2 : 1;              // E2: both output-channel halves in one workgroup
@@ -1059,6 +1059,9 @@ static int run_wgrad_bf16(int B, const float* in, const float* dout, float* dw, 
     // (195.6 instead of 207.1 us at B = 2048, and half the slab traffic: 52 instead of 105 MB written and re-read; profiles/r05_o_wgrad_split_count.txt)
     const int S = wgrad_bf16_splits<H>(B, (CIN / 32) * (COUT / (32 * COB)), CIN == 32 ? 256 : 512, &tps, &numTiles);
     const int64_t n = (int64_t)25 * CIN * COUT, row = n + COUT;
+    // plan (no launch): the (tiles, splits, tiles per split) of this batch; tests/bf16_ops_tools.py mirrors this arithmetic (wgrad_geometry)
+    // and test_gpu_bf16_ops.py holds the mirror to it
+    if (plan) { plan[0] = numTiles; plan[1] = S; plan[2] = tps; return 0; }
     if (need) { *need = (int64_t)(S + 16) * row; return 0; }
     WgradBf16Args a{in, dout, ws, B, numTiles, tps};
     constexpr int WT_NW = CIN == 32 ? 8 : 4, WT_NT = WT_NW * 64;
@@ -1079,20 +1082,20 @@ static int run_wgrad_bf16(int B, const float* in, const float* dout, float* dw, 
 }
 
 static int dispatch_wgrad_bf16(int layer, int width, int B, const float* in, const float* dout, float* dw, float* dbias, float* ws,
-                               hipStream_t st, int64_t* need) {
+                               hipStream_t st, int64_t* need, int* plan = nullptr) {
     if (width == 64) {
         switch (layer) {
-            case 1: return run_wgrad_bf16<32, 64, 32>(B, in, dout, dw, dbias, ws, st, need);
-            case 2: return run_wgrad_bf16<64, 128, 16>(B, in, dout, dw, dbias, ws, st, need);
-            case 3: return run_wgrad_bf16<128, 256, 8>(B, in, dout, dw, dbias, ws, st, need);
-            case 4: return run_wgrad_bf16<256, 128, 4>(B, in, dout, dw, dbias, ws, st, need);
+            case 1: return run_wgrad_bf16<32, 64, 32>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 2: return run_wgrad_bf16<64, 128, 16>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 3: return run_wgrad_bf16<128, 256, 8>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 4: return run_wgrad_bf16<256, 128, 4>(B, in, dout, dw, dbias, ws, st, need, plan);
         }
     } else if (width == 128) {
         switch (layer) {
-            case 1: return run_wgrad_bf16<32, 64, 64>(B, in, dout, dw, dbias, ws, st, need);
-            case 2: return run_wgrad_bf16<64, 128, 32>(B, in, dout, dw, dbias, ws, st, need);
-            case 3: return run_wgrad_bf16<128, 256, 16>(B, in, dout, dw, dbias, ws, st, need);
-            case 4: return run_wgrad_bf16<256, 128, 8>(B, in, dout, dw, dbias, ws, st, need);
+            case 1: return run_wgrad_bf16<32, 64, 64>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 2: return run_wgrad_bf16<64, 128, 32>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 3: return run_wgrad_bf16<128, 256, 16>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 4: return run_wgrad_bf16<256, 128, 8>(B, in, dout, dw, dbias, ws, st, need, plan);
         }
     }
     cvae_set_error("conv_wgrad_bf16: unsupported layer %d at width %d", layer, width);
@@ -1102,6 +1105,9 @@ int64_t wgrad_bf16_ws_floats(int layer, int width, int B) {
     int64_t need = 0;
     if (dispatch_wgrad_bf16(layer, width, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need) != 0) return 0;
     return need;
+}
+int conv_wgrad_bf16_plan(int layer, int width, int B, int plan[3]) {
+    return dispatch_wgrad_bf16(layer, width, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, plan);
 }
 int launch_conv_wgrad_bf16(int layer, int width, int B, const float* in, const float* dout, float* dw, float* dbias, float* ws, hipStream_t st) {
     return dispatch_wgrad_bf16(layer, width, B, in, dout, dw, dbias, ws, st, nullptr);
@@ -1225,7 +1231,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_wgrad_bf16_kernel(WgradBf16Arg
 }
 
 template <int CIN, int COUT, int HS>
-static int run_up_wgrad_bf16_main(int B, const float* in, const float* dout, float* slab, int Smax, int* S_out, hipStream_t st) {
+static int run_up_wgrad_bf16_main(int B, const float* in, const float* dout, float* slab, int Smax, int* S_out, hipStream_t st, int* plan) {
     using T = UpWgTile<HS>;
     const int numTiles = cdiv(B, T::IMGS) * T::TPI;
     int S = cdiv(2 * cvae_num_cus(), (CIN / 32) * (COUT / 32));     // two resident workgroups per CU, equal tile counts
@@ -1234,6 +1240,7 @@ static int run_up_wgrad_bf16_main(int B, const float* in, const float* dout, flo
     if (S < 1) S = 1;
     const int tps = cdiv(numTiles, S);
     S = cdiv(numTiles, tps);
+    if (plan) { plan[0] = numTiles; plan[1] = S; plan[2] = tps; *S_out = S; return 0; }      // no launch: conv_up_wgrad_bf16_plan
     WgradBf16Args a{in, dout, slab, B, numTiles, tps};
     cvae_probe_begin(st);
     hipLaunchKernelGGL((conv_up_wgrad_bf16_kernel<CIN, COUT, HS>), dim3(S, CIN / 32, COUT / 32), dim3(256), 0, st, a);
@@ -1244,18 +1251,18 @@ static int run_up_wgrad_bf16_main(int B, const float* in, const float* dout, flo
 }
 
 // main kernel only: writes S (<= Smax) slab rows [36][CIN][COUT] | bias[COUT]; conv_up.hip reduces and expands them
-int launch_up_wgrad_bf16_main(int layer, int width, int B, const float* in, const float* dout, float* slab, int Smax, int* S_out, hipStream_t st) {
+int launch_up_wgrad_bf16_main(int layer, int width, int B, const float* in, const float* dout, float* slab, int Smax, int* S_out, hipStream_t st, int* plan) {
     if (width == 64) {
         switch (layer) {
-            case 5: return run_up_wgrad_bf16_main<128, 64, 4>(B, in, dout, slab, Smax, S_out, st);
-            case 6: return run_up_wgrad_bf16_main<64, 32, 8>(B, in, dout, slab, Smax, S_out, st);
-            case 7: return run_up_wgrad_bf16_main<32, 32, 16>(B, in, dout, slab, Smax, S_out, st);
+            case 5: return run_up_wgrad_bf16_main<128, 64, 4>(B, in, dout, slab, Smax, S_out, st, plan);
+            case 6: return run_up_wgrad_bf16_main<64, 32, 8>(B, in, dout, slab, Smax, S_out, st, plan);
+            case 7: return run_up_wgrad_bf16_main<32, 32, 16>(B, in, dout, slab, Smax, S_out, st, plan);
         }
     } else if (width == 128) {
         switch (layer) {
-            case 5: return run_up_wgrad_bf16_main<128, 64, 8>(B, in, dout, slab, Smax, S_out, st);
-            case 6: return run_up_wgrad_bf16_main<64, 32, 16>(B, in, dout, slab, Smax, S_out, st);
-            case 7: return run_up_wgrad_bf16_main<32, 32, 32>(B, in, dout, slab, Smax, S_out, st);
+            case 5: return run_up_wgrad_bf16_main<128, 64, 8>(B, in, dout, slab, Smax, S_out, st, plan);
+            case 6: return run_up_wgrad_bf16_main<64, 32, 16>(B, in, dout, slab, Smax, S_out, st, plan);
+            case 7: return run_up_wgrad_bf16_main<32, 32, 32>(B, in, dout, slab, Smax, S_out, st, plan);
         }
     }
     cvae_set_error("conv_up_wgrad_bf16: unsupported layer %d at width %d", layer, width);

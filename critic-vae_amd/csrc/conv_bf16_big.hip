@@ -584,6 +584,8 @@ static int run_big(const ConvBf16Args& a, hipStream_t st) {
     auto kern = conv5x5_bf16_big_kernel<KCH, NCH, H, NT, MT, KB, EPI, TDB, IMGL, ALLC>;
     static DeviceOnce once;
     { int rc = cvae_grant_lds(once, reinterpret_cast<const void*>(kern), SMEM); if (rc) return rc; }
+    // (tests/bf16_ops_tools.py, big_geometry and BIG_MT_NT, mirrors this item count, the MT / NT of launch_conv_bf16_big's instantiations and
+    // persistent_grid: the capped run of tests/test_gpu_bf16_ops.py asserts "several items per workgroup" on the mirror — keep it in step)
     const int numTiles = cdiv(a.B, T::IMGS) * T::TILES_PER_IMG, numGroups = cdiv(numTiles, MT);
     const int G = persistent_grid(1, 8 * cdiv(numGroups, 8) * NY);
     cvae_probe_begin(st);

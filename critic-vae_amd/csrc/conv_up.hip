@@ -582,7 +582,7 @@ int launch_conv_up_dgrad(int layer, int width, int B, const float* dout, const f
 
 template <int CIN, int COUT, int HS>
 static int run_up_wgrad(int B, const float* in, const float* dout, float* dw, float* dbias, float* ws, hipStream_t st,
-                        int64_t* need, int bf16_layer = 0, int bf16_width = 64) {
+                        int64_t* need, int bf16_layer = 0, int bf16_width = 64, int* plan = nullptr) {
     using T = UpTile64<HS>;
     const int numTiles = cdiv(B, T::IMGS) * T::TILES_PER_IMG;
     const int bps = (CIN / 32) * (COUT / 32);
@@ -596,6 +596,9 @@ static int run_up_wgrad(int B, const float* in, const float* dout, float* dw, fl
     const int tps = cdiv(numTiles, S);
     S = cdiv(numTiles, tps);
     const int64_t nc = (int64_t)36 * CIN * COUT, row = nc + COUT;
+    // plan (bf16 mode, no launch): the (tiles, splits, tiles per split) the bf16 main kernel would run with under this cap; tests/bf16_ops_tools.py
+    // mirrors this arithmetic (wgrad_geometry) and test_gpu_bf16_ops.py holds the mirror to it
+    if (plan) return launch_up_wgrad_bf16_main(bf16_layer, bf16_width, B, nullptr, nullptr, nullptr, Scap, &S, st, plan);
     // ws = [S slabs | 16 mid rows | reduced row]
     if (need) { *need = (int64_t)(Scap + 17) * row; return 0; }
     if (bf16_layer) {          // precision mode 1: same slab rows from the bf16-MFMA kernel (conv_bf16.hip), S' <= S of them
@@ -620,19 +623,19 @@ static int run_up_wgrad(int B, const float* in, const float* dout, float* dw, fl
 }
 
 static int dispatch_up_wgrad(int layer, int width, int B, const float* in, const float* dout, float* dw, float* dbias,
-                             float* ws, hipStream_t st, int64_t* need, bool bf16 = false) {
+                             float* ws, hipStream_t st, int64_t* need, bool bf16 = false, int* plan = nullptr) {
     if (width == 64) {
         switch (layer) {
-            case 5: return run_up_wgrad<128, 64, 4>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 5 : 0);
-            case 6: return run_up_wgrad<64, 32, 8>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 6 : 0);
-            case 7: return run_up_wgrad<32, 32, 16>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 7 : 0);
+            case 5: return run_up_wgrad<128, 64, 4>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 5 : 0, 64, plan);
+            case 6: return run_up_wgrad<64, 32, 8>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 6 : 0, 64, plan);
+            case 7: return run_up_wgrad<32, 32, 16>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 7 : 0, 64, plan);
         }
     }
     if (width == 128) {
         switch (layer) {
-            case 5: return run_up_wgrad<128, 64, 8>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 5 : 0, 128);
-            case 6: return run_up_wgrad<64, 32, 16>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 6 : 0, 128);
-            case 7: return run_up_wgrad<32, 32, 32>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 7 : 0, 128);
+            case 5: return run_up_wgrad<128, 64, 8>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 5 : 0, 128, plan);
+            case 6: return run_up_wgrad<64, 32, 16>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 6 : 0, 128, plan);
+            case 7: return run_up_wgrad<32, 32, 32>(B, in, dout, dw, dbias, ws, st, need, bf16 ? 7 : 0, 128, plan);
         }
     }
     cvae_set_error("conv_up_wgrad: unsupported layer %d at width %d", layer, width);
@@ -642,6 +645,9 @@ int64_t conv_up_wgrad_ws_floats(int layer, int width, int B) {
     int64_t need = 0;
     if (dispatch_up_wgrad(layer, width, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need)) return 0;
     return need;
+}
+int conv_up_wgrad_bf16_plan(int layer, int width, int B, int plan[3]) {
+    return dispatch_up_wgrad(layer, width, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, plan);
 }
 int launch_conv_up_wgrad(int layer, int width, int B, const float* in, const float* dout, float* dw, float* dbias,
                          float* ws, hipStream_t st, bool bf16) {

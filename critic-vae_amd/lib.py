@@ -148,6 +148,9 @@ _SIGS = {
     "cvae_op_d4_bwd": (C.c_int, [_p, _i32] + [_p] * 10),
     "cvae_op_bn_pool_act_fwd": (C.c_int, [_p, _i32, _i32] + [_p] * 9 + [_i32, _p]),
     "cvae_op_bn_pool_act_bwd": (C.c_int, [_p, _i32, _i32] + [_p] * 11),
+    "cvae_op_conv_tiles_per_partial": (_i32, [_p, _i32, _i32]),
+    "cvae_op_conv_wgrad_plan": (C.c_int, [_p, _i32, _i32, C.POINTER(C.c_int32)]),
+    "cvae_op_bn_fwd_finalize": (C.c_int, [_p, _i32, _i32, _p, _i32] + [_p] * 6 + [_i32, _p]),
     "cvae_op_msssim": (C.c_int, [_p, _i32] + [_p] * 6),
     "cvae_op_latent_scratch_floats": (_i64, [_p, _i32]),
     "cvae_op_latent_plan": (_i32, [_i32, _i32, _i32, C.POINTER(C.c_int32)]),
@@ -623,6 +626,8 @@ class Handle:
 
     # ---- per-op entry points (tests, roofline probe) ----
     # "bf16x9" / "bf16x6" handles: the conv ops of layers 1..4 run the step's split-operand kernels and need `scratch`
+    # "bf16" handles: the conv ops of layers 1..8 and op_d4_bwd run the step's bf16 kernels on bf16 activations (passed as the
+    # fp32 tensors that hold them, two elements per float) and fp32 weights; they need `scratch`
     def op_scratch_floats(self, B):
         return self.lib.cvae_op_scratch_floats(self.h, B)
 
@@ -657,6 +662,22 @@ class Handle:
         self._check(self.lib.cvae_op_bn_pool_act_bwd(self.h, layer, B, _ptr(y), _ptr(a), _ptr(da), _ptr(coef),
                                                      _ptr(gamma), _ptr(dy), _ptr(dgamma), _ptr(dbeta), _ptr(dbias),
                                                      _ptr(scratch), _stream()))
+
+    def op_conv_tiles_per_partial(self, layer, B):
+        n = self.lib.cvae_op_conv_tiles_per_partial(self.h, layer, B)
+        if n < 1:
+            raise CvaeError(f"cvae_op_conv_tiles_per_partial: {self.lib.cvae_last_error().decode()}")
+        return n
+
+    def op_conv_wgrad_plan(self, layer, B):
+        """(tiles, splits, tiles per split) of op_conv_wgrad's kernel on a bf16 handle, from the launchers (no launch)."""
+        out = (C.c_int32 * 3)()
+        self._check(self.lib.cvae_op_conv_wgrad_plan(self.h, layer, B, out))
+        return tuple(out)
+
+    def op_bn_fwd_finalize(self, layer, B, bn_partials, tiles_per_partial, gamma, beta, run_mean, run_var, coef, scratch, train=True):
+        self._check(self.lib.cvae_op_bn_fwd_finalize(self.h, layer, B, _ptr(bn_partials), tiles_per_partial, _ptr(gamma), _ptr(beta),
+                                                     _ptr(run_mean), _ptr(run_var), _ptr(coef), _ptr(scratch), int(train), _stream()))
 
     def op_msssim(self, B, img1, img2, ws, scalars, d_img1=None):
         self._check(self.lib.cvae_op_msssim(self.h, B, _ptr(img1), _ptr(img2), _ptr(ws), _ptr(scalars),

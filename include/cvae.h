@@ -661,8 +661,18 @@ int cvae_probe_read(cvae_handle h, int32_t id, float* ms_host, int32_t cap);
  * the step runs there: forward and input gradient on the bf16 MFMA with 3-way split operands (the
  * fp32 weight is packed into `scratch` first), weight gradient on the split-operand kernel.  All
  * tensors stay fp32; cvae_op_scratch_floats() includes the packed copy, and a null `scratch` on
- * these paths is CVAE_EINVAL.  Every other layer of these handles, and every layer of precision 0
- * and 1, runs the fp32 kernels.
+ * these paths is CVAE_EINVAL.  Every other layer of these handles, and every layer of precision 0,
+ * runs the fp32 kernels.
+ * On a bf16 handle (precision 1) the conv ops run what the step runs there, on tensors in the
+ * handle's storage type: activations and activation gradients (in, out, dout, din, mask_src, o3,
+ * d_o3) are bf16 behind the float pointers; weights, biases, their gradients, recon and d_recon
+ * are fp32.  cvae_op_conv_fwd / cvae_op_conv_dgrad of layers 1..4 pack the layer's weights into
+ * `scratch` and take conv_route's kernel family at that batch (D0: split-K + finish at 64 x 64);
+ * layers 5..7 collapse and pack them and run the bf16 up-conv kernels (mask_src in bf16); layer 8
+ * and cvae_op_d4_bwd run D4's bf16 forms (the Tanh backward is applied inside: `dout` is not
+ * written and may be null); cvae_op_conv_wgrad of layers 1..7 runs the bf16 weight-gradient
+ * kernels.  Layer 0's weight gradient stays the fp32 kernel on fp32 tensors: its bf16 form exists
+ * only fused with block 0's BatchNorm backward.  A null `scratch` on these paths is CVAE_EINVAL.
  * ---------------------------------------------------------------------------------------- */
 int64_t cvae_op_scratch_floats(cvae_handle h, int32_t batch);
 int64_t cvae_op_bn_partial_floats(cvae_handle h, int32_t layer, int32_t batch);
@@ -687,6 +697,20 @@ int cvae_op_d4_bwd(cvae_handle h, int32_t batch, const float* o3, const float* d
 int cvae_op_bn_pool_act_fwd(cvae_handle h, int32_t layer, int32_t batch, const float* y,
                             const float* bn_partials, const float* gamma, const float* beta,
                             float* run_mean, float* run_var, float* coef, float* a, void* scratch,
+                            int32_t train, void* stream);
+/* How many 128-pixel tiles one BatchNorm partial row written by cvae_op_conv_fwd(layer 0..3) covers on this
+ * handle at this batch (conv_route: 4 or 8 for the big-tile bf16 kernels, 1 otherwise).  cvae_op_bn_pool_act_fwd
+ * expects one tile per row; rows of more tiles go through cvae_op_bn_fwd_finalize. */
+int32_t cvae_op_conv_tiles_per_partial(cvae_handle h, int32_t layer, int32_t batch);
+/* Host logic only (layers 5..7 ask the device's compute-unit count): out[0..2] = (tiles, splits, tiles per split) of the kernel that
+ * cvae_op_conv_wgrad(layer 1..7) launches on a bf16 handle at this batch, from the launchers' own split arithmetic.
+ * CVAE_EUNSUPPORTED on other handles and layers. */
+int cvae_op_conv_wgrad_plan(cvae_handle h, int32_t layer, int32_t batch, int32_t* out);
+/* The statistics half of cvae_op_bn_pool_act_fwd on partial rows of `tiles_per_partial` (1, 2, 4, 8) tiles each:
+ * coef (scale, shift, mean, invstd per channel) and, in train mode, the running statistics.  `scratch` as above. */
+int cvae_op_bn_fwd_finalize(cvae_handle h, int32_t layer, int32_t batch, const float* bn_partials,
+                            int32_t tiles_per_partial, const float* gamma, const float* beta,
+                            float* run_mean, float* run_var, float* coef, void* scratch,
                             int32_t train, void* stream);
 int cvae_op_bn_pool_act_bwd(cvae_handle h, int32_t layer, int32_t batch, const float* y,
                             const float* a, const float* da, const float* coef, const float* gamma,

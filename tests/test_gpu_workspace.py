@@ -257,27 +257,46 @@ def _empty(n, dtype=torch.float32):
 def test_conv_ops_do_not_depend_on_scratch_partials_or_outputs(W, B):
     """op_conv_fwd (all nine layers, with the BatchNorm partials of the encoder layers), op_conv_dgrad (1..7), op_conv_wgrad (0..7) and
     op_d4_bwd with the scratch, the partials and every output under the three fills.  At B = 3 also layers 1..4 on handles of the two
-    fp32-emulation modes, whose ops run the step's split-operand kernels: the packed weights and D0's split-K slabs sit in the scratch."""
+    fp32-emulation modes, whose ops run the step's split-operand kernels: the packed weights and D0's split-K slabs sit in the scratch;
+    and layers 1..8 and op_d4_bwd on a bf16 handle, whose ops run the step's bf16 kernels on bf16 activations."""
     _conv_ops_under_fills(handle(W, B), W, B, range(9))
     if B == 3:
         for mode in ("bf16x9", "bf16x6"):
             _conv_ops_under_fills(cvlib.Handle(W, B, precision=mode), W, B, range(1, 5))
+        # a bf16 handle: layers 1..8 on the step's bf16 kernels, activations and their gradients as bf16 (layer 0's weight gradient is the
+        # fp32 kernel there too and is covered above); the packed and collapsed weights, D0's slabs and the weight-gradient slabs sit in the scratch
+        Hb = cvlib.Handle(W, B, precision="bf16")
+        _conv_ops_under_fills(Hb, W, B, range(1, 9), bf16=True)
+        _d4_bwd_under_fills(Hb, W, B, bf16=True)
     _d4_bwd_under_fills(handle(W, B), W, B)
 
 
-def _conv_ops_under_fills(H, W, B, layers):
+def _as_bf16(t):
+    """A device fp32 tensor -> its bf16 rounding, as the fp32 tensor that holds it (two elements per float)."""
+    return t.to(torch.bfloat16).reshape(-1).view(torch.float32)
+
+
+def _conv_ops_under_fills(H, W, B, layers, bf16=False):
     for layer in layers:
         cin, cout, h, up, hs = geom(layer, W)
         x, w, b = rnd(f"x{layer}", (B, cin, hs, hs)), rnd(f"w{layer}", (cout, cin, 5, 5), -0.1, 0.1), rnd(f"b{layer}", (cout,))
         dout = rnd(f"do{layer}", (B, cout, h, h))
         xin, wn, bd, dn = (dev(x) if layer == 0 else nhwc(x)), wnat(w), dev(b), (dev(dout) if layer == 8 else nhwc(dout))
-        bufs = {"out": _empty(B * h * h * cout), "scratch": _empty(H.op_scratch_floats(B))}
+        mask = torch.relu(xin) if up else None
+        per = 1           # elements per float of the activation tensors
+        if bf16:          # activations and activation gradients (the ReLU mask source among them) in bf16 storage; recon and d_recon stay fp32
+            per = 2
+            xin, dn, mask = _as_bf16(xin), (dn if layer == 8 else _as_bf16(dn)), (_as_bf16(mask) if up else None)
+        bufs = {"out": _empty(B * h * h * cout // (1 if layer == 8 else per)), "scratch": _empty(H.op_scratch_floats(B))}
+        part = None
         if layer < 4:
             bufs["partials"] = _empty(H.op_bn_partial_floats(layer, B))
-        _under_fills(lambda: H.op_conv_fwd(layer, B, xin, wn, bd, bufs["out"], bufs.get("partials"), bufs["scratch"]), bufs)
+            # a partial row of the big-tile bf16 kernels covers several tiles: [S | M2] of ceil(tiles / that) rows at the front of the buffer
+            tiles, tpp = bufs["partials"].numel() // (2 * cout), H.op_conv_tiles_per_partial(layer, B)
+            part = {"partials": slice(0, 2 * -(-tiles // tpp) * cout)}
+        _under_fills(lambda: H.op_conv_fwd(layer, B, xin, wn, bd, bufs["out"], bufs.get("partials"), bufs["scratch"]), bufs, part)
         if 1 <= layer <= 7:
-            mask = torch.relu(xin) if up else None
-            bufs = {"din": _empty(B * hs * hs * cin), "scratch": _empty(H.op_scratch_floats(B))}
+            bufs = {"din": _empty(B * hs * hs * cin // per), "scratch": _empty(H.op_scratch_floats(B))}
             _under_fills(lambda: H.op_conv_dgrad(layer, B, dn, wn, mask, bufs["din"], bufs["scratch"]), bufs)
         if layer <= 7:
             bufs = {"dw": _empty(25 * cin * cout), "scratch": _empty(H.op_scratch_floats(B))}
@@ -286,12 +305,15 @@ def _conv_ops_under_fills(H, W, B, layers):
             _under_fills(lambda: H.op_conv_wgrad(layer, B, xin, dn, bufs["dw"], bufs.get("dbias"), bufs["scratch"]), bufs)
 
 
-def _d4_bwd_under_fills(H, W, B):
+def _d4_bwd_under_fills(H, W, B, bf16=False):
     o3 = torch.relu(nhwc(rnd("pre8", (B, 32, W // 2, W // 2))))
     d_recon, recon, w8 = dev(rnd("dr8", (B, 3, W, W))), dev(rnd("rc8", (B, 3, W, W), -0.9, 0.9)), wnat(rnd("w8", (3, 32, 5, 5), -0.1, 0.1))
-    bufs = {"dout": _empty(B * 3 * W * W), "d_o3": _empty(B * 32 * (W // 2) ** 2), "dw": _empty(2400), "db": _empty(3),
+    bufs = {"dout": _empty(B * 3 * W * W), "d_o3": _empty(B * 32 * (W // 2) ** 2 // (2 if bf16 else 1)), "dw": _empty(2400), "db": _empty(3),
             "scratch": _empty(H.op_scratch_floats(B))}
-    _under_fills(lambda: H.op_d4_bwd(B, o3, d_recon, recon, w8, bufs["dout"], bufs["d_o3"], bufs["dw"], bufs["db"], bufs["scratch"]), bufs)
+    if bf16:        # o3 / d_o3 in bf16; the Tanh backward runs inside the kernel and no dOut tensor is written
+        o3 = _as_bf16(o3)
+        del bufs["dout"]
+    _under_fills(lambda: H.op_d4_bwd(B, o3, d_recon, recon, w8, bufs.get("dout"), bufs["d_o3"], bufs["dw"], bufs["db"], bufs["scratch"]), bufs)
 
 
 @op_shapes
