@@ -96,16 +96,20 @@ class CriticTrainer(DeviceTrainer):
     load_state_dict is fine: it copies in place) would cut the critic off from the trainer; step() checks the address and
     raises instead of training a block nobody reads.  dropout: the p of the three Dropout layers (the reference class's default is
     0.5; its shipped checkpoint does not say what it was trained with).  loss: "bce" (torch's binary_cross_entropy on the
-    sigmoid output) or "mse".  skip_nonfinite / max_grad_norm: the guarded step of FusedTrainer (train.py)."""
+    sigmoid output) or "mse".  skip_nonfinite / max_grad_norm: the guarded step of FusedTrainer (train.py).  augment: an
+    augment.Augment or None — fit_device then builds every batch with cvae_preprocess_u8_gather_aug under
+    augment.at(step_count) (still one launch per batch); the TARGET of a frame stays the stored one.  evaluate() and step()
+    never augment; the augmentation is saved and restored with the trainer."""
 
     def __init__(self, critic, lr=1e-4, betas=P.adam_betas, eps=P.adam_eps, dropout=0.3, loss="bce", skip_nonfinite=False,
-                 max_grad_norm=None):
+                 max_grad_norm=None, augment=None):
         if loss not in CRITIC_LOSS:
             raise ValueError(f"loss {loss!r}: one of {sorted(CRITIC_LOSS)}")
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout {dropout!r} outside [0, 1)")
         self._init_shared(skip_nonfinite, max_grad_norm)      # guard fields, step_count, val_history / best_val / val_stale
         self.critic, self.h = critic, critic.handle
+        self._init_augment(augment, 64)
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
         self.dropout, self.loss = float(dropout), loss
         dev = critic.flat.device
@@ -193,7 +197,8 @@ class CriticTrainer(DeviceTrainer):
         """The loop of FusedTrainer.fit_device over a DeviceDataset whose `preds` slot holds the targets
         (episodes.critic_dataset): per epoch np.random.shuffle of the host indices, slices of batch_size with the ragged last
         batch kept, one cvae_preprocess_u8_gather launch per batch (x = frames[idx] / 255, target = preds[idx]), keep masks from
-        `generator`.  Returns the loss scalars of every step taken, (steps, 4), on the device.
+        `generator`.  With an augmentation (the constructor's `augment`) that launch is cvae_preprocess_u8_gather_aug.
+        Returns the loss scalars of every step taken, (steps, 4), on the device.
         val, val_every, on_val: held-out validation as in FusedTrainer.fit_device (the shared loop, fit.py), with this
         trainer's evaluate(val, batch_size); a fit that on_val ended returns the rows of the steps it took."""
         dev, B = self._check_dataset(dataset, batch_size, min(self.h.max_batch, MAX_BATCH))

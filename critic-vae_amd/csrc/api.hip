@@ -948,6 +948,37 @@ int cvae_gather_f32(cvae_handle h, int32_t batch, int32_t width, const float* fr
     return launch_gather_f32(width, batch, frames, preds, n_frames, idx, x, pred, (hipStream_t)stream);
 }
 
+// the augmented gathers: the plain gathers' checks, then the ranges of cvae_augment (fp32: no gain), all on the host
+static bool augment_ok(const cvae_augment* aug, int32_t width, bool allow_gain, const char* who) {
+    if (!aug) { cvae_set_error("%s: null aug", who); return false; }
+    if (aug->flip_below > (1u << 24)) { cvae_set_error("%s: flip_below %u above 2^24", who, aug->flip_below); return false; }
+    if (aug->max_shift < 0 || aug->max_shift > width / 4) {
+        cvae_set_error("%s: max_shift %d outside [0, %d] (width / 4)", who, aug->max_shift, width / 4); return false;
+    }
+    if (aug->gain_q16 < 0 || aug->gain_q16 > 65535) { cvae_set_error("%s: gain_q16 %d outside [0, 65535]", who, aug->gain_q16); return false; }
+    if (!allow_gain && aug->gain_q16 != 0) {
+        cvae_set_error("%s: gain_q16 %d: fp32 entries are Tanh outputs, a brightness gain clamped at 1 has no meaning for them", who, aug->gain_q16);
+        return false;
+    }
+    if (aug->reserved != 0) { cvae_set_error("%s: reserved must be 0", who); return false; }
+    return true;
+}
+
+int cvae_preprocess_u8_gather_aug(cvae_handle h, int32_t batch, int32_t width, const uint8_t* frames_hwc, const float* preds,
+                                  int64_t n_frames, const int64_t* idx, const cvae_augment* aug, float* x, float* pred,
+                                  int32_t* applied, void* stream) {
+    const char* who = "cvae_preprocess_u8_gather_aug";
+    if (!batch_gather_ok(h, batch, width, frames_hwc, preds, n_frames, idx, x, pred, who) || !augment_ok(aug, width, true, who)) return CVAE_EINVAL;
+    return launch_preprocess_u8_gather_aug(width, batch, frames_hwc, preds, n_frames, idx, *aug, x, pred, applied, (hipStream_t)stream);
+}
+
+int cvae_gather_f32_aug(cvae_handle h, int32_t batch, int32_t width, const float* frames, const float* preds, int64_t n_frames,
+                        const int64_t* idx, const cvae_augment* aug, float* x, float* pred, int32_t* applied, void* stream) {
+    const char* who = "cvae_gather_f32_aug";
+    if (!batch_gather_ok(h, batch, width, frames, preds, n_frames, idx, x, pred, who) || !augment_ok(aug, width, false, who)) return CVAE_EINVAL;
+    return launch_gather_f32_aug(width, batch, frames, preds, n_frames, idx, *aug, x, pred, applied, (hipStream_t)stream);
+}
+
 // |recon_zero - recon_one| -> greyscale difference mask (get_diff_image, vae_utility.py:256-277), batched
 int cvae_diff_grey(cvae_handle h, int32_t B, const float* recon_one, const float* recon_zero, float* diff, void* stream) {
     if (!h || B < 1) { cvae_set_error("cvae_diff_grey: bad handle/batch"); return CVAE_EINVAL; }

@@ -408,6 +408,10 @@ int launch_recon_zcat(int n_entries, const int64_t* ent_sel, const int32_t* ent_
 int launch_inject_zcat(int n_images, int n_rewards, const float* mu, const float* rewards, float* zcat, hipStream_t st);
 int launch_gather_f32(int width, int B, const float* frames, const float* preds, int64_t n, const int64_t* idx, float* x,
                       float* pred, hipStream_t st);
+int launch_preprocess_u8_gather_aug(int width, int B, const uint8_t* frames, const float* preds, int64_t n, const int64_t* idx,
+                                    const struct cvae_augment& aug, float* x, float* pred, int32_t* applied, hipStream_t st);
+int launch_gather_f32_aug(int width, int B, const float* frames, const float* preds, int64_t n, const int64_t* idx,
+                          const struct cvae_augment& aug, float* x, float* pred, int32_t* applied, hipStream_t st);
 int launch_diff_grey(int width, int B, const float* a, const float* b, float* diff, hipStream_t st);
 // segment.hip
 int64_t crf_scratch_bytes(int width, int B);

@@ -19,6 +19,11 @@
 //   gather_f32            x[b] = frames[idx[b]] (fp32 CHW, bit copy) and pred[b] = preds[idx[b]]: one training batch.
 //   inject_zcat           zcat rows (mu of image b, reward r) of the batched -inject: one decoder call for all of them.
 //
+// and the augmented forms of the two batch gathers (cvae_augment, include/cvae.h: per sample a hashed flip, a shift with edge
+// replication and, for uint8 frames, a brightness gain — inside the same single launch):
+//
+//   preprocess_u8_gather_aug, gather_f32_aug   source rows staged in LDS between replicated edge pads, one window per thread.
+//
 // Integer math only, no atomics: every result is deterministic.  Frame offsets are 64-bit (a 64x64 dataset passes
 // 2^31 bytes at 174 763 frames).
 #include "common.h"
@@ -318,6 +323,212 @@ __global__ __launch_bounds__(TPB) void gather_f32_kernel(const uint4* __restrict
     if (piece == 0 && threadIdx.x == 0) pred[b] = ok ? preds[s] : __builtin_nanf("");
 }
 
+// ---- the augmented gathers (include/cvae.h: cvae_augment) ----
+// What the hash draws for dataset index s.  Every input is uniform over the workgroup (s comes from idx[blockIdx]), so the
+// two mix64 run once per wave on the scalar unit, not per pixel.
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+struct AugDraw { int flip, dx, dy, dnum; };                     // dnum = num - 2^31 = gain_q16 * k
+
+__device__ __forceinline__ AugDraw aug_draw(const cvae_augment& a, int64_t s) {
+    const uint64_t r = mix64(a.key ^ mix64((uint64_t)s));
+    const uint32_t span = 2u * (uint32_t)a.max_shift + 1u;
+    AugDraw d;
+    d.flip = (uint32_t)(r >> 40) < a.flip_below;
+    d.dnum = a.gain_q16 * ((int)((r >> 24) & 0xFFFFu) - 32768);  // |.| <= 65535 * 32768 < 2^31
+    d.dx = (int)((uint32_t)((r >> 12) & 0xFFFu) % span) - a.max_shift;
+    d.dy = (int)((uint32_t)(r & 0xFFFu) % span) - a.max_shift;
+    return d;
+}
+
+__device__ __forceinline__ void aug_record(int32_t* __restrict__ applied, int64_t b, int f, int dx, int dy, int dnum) {
+    if (!applied) return;
+    applied[b * 4] = f; applied[b * 4 + 1] = dx; applied[b * 4 + 2] = dy; applied[b * 4 + 3] = dnum;
+}
+
+// Both kernels keep the plain kernels' grid and stores and stage the source rows of their 4096 output pixels in LDS, each
+// row between two pads of W/4 (>= max_shift) copies of its edge pixel:
+//   LDS row l = source row clamp(r0 + l - dy) — the vertical shift is done by WHICH row is fetched (16-byte global loads,
+//   rows are whole 16-byte units), the pads by the thread that fetched the row's first / last unit — so that the horizontal
+//   shift and the flip are one unclamped window per thread: output pixels j0 .. j0+15 (j0 % 16 == 0) are the 16 consecutive
+//   padded pixels from vmin + P, vmin = flip ? W-16-j0-dx : j0-dx, in reverse order if flipped.  The window starts at an
+//   arbitrary byte (uint8) or float (fp32), so the thread reads the aligned dwords (13) or 16-byte units (2) that cover it
+//   and shifts in registers — no byte-wide LDS reads.
+// One barrier; an out-of-range index leaves the workgroup before it (the test is uniform).
+template <int W> struct AugU8 {
+    static constexpr int P = W / 4;                      // pad pixels per side
+    static constexpr int ROWB = (W + 2 * P) * 3;         // 288 / 576 bytes: whole 16-byte units
+    static constexpr int R = 4096 / W;                   // rows per workgroup: 64 / 32
+    static constexpr int UPR = W * 3 / 16;               // 16-byte units per source row: 12 / 24
+    static constexpr int PADU = P * 3 / 16;              // ... per pad: 3 / 6
+    static constexpr int BPF = W * W / 4096;             // workgroups per frame
+    static constexpr int LDSB = R * ROWB + 64;           // the last row's window may read one unit past it (never used)
+};
+
+template <int W>
+__global__ __launch_bounds__(TPB) void preprocess_u8_gather_aug_kernel(const uint8_t* __restrict__ frames, const float* __restrict__ preds,
+                                                                       int64_t n, const int64_t* __restrict__ idx, cvae_augment aug,
+                                                                       float* __restrict__ x, float* __restrict__ pred,
+                                                                       int32_t* __restrict__ applied) {
+    using K = AugU8<W>;
+    __shared__ uint4 lds[K::LDSB / 16];
+    constexpr int hw = W * W;
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x / K::BPF;
+    const int piece = (int)(blockIdx.x % K::BPF);
+    const int64_t s = idx[b];
+    float* d = x + b * 3 * (int64_t)hw + (int64_t)piece * 4096 + tid * 16;
+    if (!(s >= 0 && s < n)) {
+        const float4 q = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
+        for (int c = 0; c < 3; ++c)
+            for (int j = 0; j < 4; ++j) reinterpret_cast<float4*>(d + (int64_t)c * hw)[j] = q;
+        if (piece == 0 && tid == 0) { pred[b] = __builtin_nanf(""); aug_record(applied, b, 0, 0, 0, 0); }
+        return;
+    }
+    const AugDraw a = aug_draw(aug, s);
+    const float g = (float)((uint32_t)a.dnum + 0x80000000u) * 0x1p-31f;
+    if (piece == 0 && tid == 0) { pred[b] = preds[s]; aug_record(applied, b, a.flip, a.dx, a.dy, a.dnum); }
+
+    // stage: 768 units of 16 bytes, three per thread, all loaded before the first LDS store
+    const uint4* src = reinterpret_cast<const uint4*>(frames + s * 3 * (int64_t)hw);
+    const int r0 = piece * K::R;
+    uint4 v[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int lu = j * TPB + tid, l = lu / K::UPR, wi = lu % K::UPR;
+        int si = r0 + l - a.dy;
+        si = si < 0 ? 0 : (si > W - 1 ? W - 1 : si);
+        v[j] = src[si * K::UPR + wi];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int lu = j * TPB + tid, l = lu / K::UPR, wi = lu % K::UPR;
+        uint4* row = lds + l * (K::ROWB / 16);
+        row[K::PADU + wi] = v[j];
+        if (wi == 0 || wi == K::UPR - 1) {                      // the row's first pixel (bytes 0..2) or last (bytes 13..15)
+            const uint32_t p = wi == 0 ? (v[j].x & 0xffffffu) : (v[j].w >> 8);
+            const uint32_t d0 = p | (p << 24), d1 = (p >> 8) | (p << 16), d2 = (p >> 16) | (p << 8);      // 12-byte period
+            uint4* pad = row + (wi == 0 ? 0 : K::PADU + K::UPR);
+#pragma unroll
+            for (int u = 0; u < K::PADU; u += 3) {
+                pad[u] = make_uint4(d0, d1, d2, d0); pad[u + 1] = make_uint4(d1, d2, d0, d1); pad[u + 2] = make_uint4(d2, d0, d1, d2);
+            }
+        }
+    }
+    __syncthreads();
+
+    // assemble: 48 bytes from byte `start` of the padded row
+    const int l = tid / (W / 16), j0 = (tid % (W / 16)) * 16;
+    const int vmin = a.flip ? W - 16 - j0 - a.dx : j0 - a.dx;
+    const int start = (vmin + K::P) * 3, sh = (start & 3) * 8;
+    const uint32_t* win = reinterpret_cast<const uint32_t*>(lds) + l * (K::ROWB / 4) + (start >> 2);
+    uint32_t e[13];                                             // the 13 aligned dwords that cover the window
+#pragma unroll
+    for (int m = 0; m < 13; ++m) e[m] = win[m];
+    uint32_t wd[12];
+#pragma unroll
+    for (int m = 0; m < 12; ++m) wd[m] = (uint32_t)((((uint64_t)e[m + 1] << 32) | e[m]) >> sh);
+    float o[3][16];
+#pragma unroll
+    for (int t = 0; t < 48; ++t) {
+        const float val = (float)((wd[t >> 2] >> ((t & 3) * 8)) & 0xffu) / 255.0f;      // the plain gather's value ...
+        o[t % 3][t / 3] = fminf(val * g, 1.0f);                                        // ... times the gain, clamped
+    }
+    if (a.flip) {                                               // uniform: the window holds the pixels in reverse order
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                reinterpret_cast<float4*>(d + (int64_t)c * hw)[j] = make_float4(o[c][15 - 4 * j], o[c][14 - 4 * j], o[c][13 - 4 * j], o[c][12 - 4 * j]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                reinterpret_cast<float4*>(d + (int64_t)c * hw)[j] = make_float4(o[c][4 * j], o[c][4 * j + 1], o[c][4 * j + 2], o[c][4 * j + 3]);
+    }
+}
+
+// fp32 entries: the same staging per channel plane (a workgroup's 1024 units are R whole rows of one plane), bit copies.
+template <int W> struct AugF32 {
+    static constexpr int P = W / 4;                      // pad floats per side
+    static constexpr int ROWU = (W + 2 * P) / 4;         // 16-byte units per padded row: 24 / 48
+    static constexpr int R = 4096 / W;                   // rows per workgroup
+    static constexpr int UPR = W / 4, PADU = P / 4;
+    static constexpr int BPF = 3 * W * W / 4096;         // workgroups per entry: 3 / 12
+    static constexpr int LDSU = R * ROWU + 2;
+};
+
+template <int W>
+__global__ __launch_bounds__(TPB) void gather_f32_aug_kernel(const uint4* __restrict__ frames, const float* __restrict__ preds, int64_t n,
+                                                             const int64_t* __restrict__ idx, cvae_augment aug, uint4* __restrict__ x,
+                                                             float* __restrict__ pred, int32_t* __restrict__ applied) {
+    using K = AugF32<W>;
+    __shared__ uint4 lds[K::LDSU];
+    constexpr int units = 3 * W * W / 4;
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x / K::BPF;
+    const int piece = (int)(blockIdx.x % K::BPF);
+    const int64_t s = idx[b];
+    uint4* d = x + b * units + piece * (TPB * GF32_PER) + tid;
+    if (!(s >= 0 && s < n)) {
+        const uint32_t q = 0x7fc00000u;
+#pragma unroll
+        for (int j = 0; j < GF32_PER; ++j) d[j * TPB] = make_uint4(q, q, q, q);
+        if (piece == 0 && tid == 0) { pred[b] = __builtin_nanf(""); aug_record(applied, b, 0, 0, 0, 0); }
+        return;
+    }
+    const AugDraw a = aug_draw(aug, s);
+    if (piece == 0 && tid == 0) { pred[b] = preds[s]; aug_record(applied, b, a.flip, a.dx, a.dy, a.dnum); }
+
+    const int c = piece * K::R / W, r0 = piece * K::R % W;       // the plane and the first row of this workgroup
+    const uint4* src = frames + s * units + c * (W * K::UPR);
+    uint4 v[GF32_PER];
+#pragma unroll
+    for (int j = 0; j < GF32_PER; ++j) {
+        const int lu = j * TPB + tid, l = lu / K::UPR, wi = lu % K::UPR;
+        int si = r0 + l - a.dy;
+        si = si < 0 ? 0 : (si > W - 1 ? W - 1 : si);
+        v[j] = src[si * K::UPR + wi];
+    }
+#pragma unroll
+    for (int j = 0; j < GF32_PER; ++j) {
+        const int lu = j * TPB + tid, l = lu / K::UPR, wi = lu % K::UPR;
+        uint4* row = lds + l * K::ROWU;
+        row[K::PADU + wi] = v[j];
+        if (wi == 0 || wi == K::UPR - 1) {
+            const uint32_t p = wi == 0 ? v[j].x : v[j].w;
+            uint4* pad = row + (wi == 0 ? 0 : K::PADU + K::UPR);
+#pragma unroll
+            for (int u = 0; u < K::PADU; ++u) pad[u] = make_uint4(p, p, p, p);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < GF32_PER; ++j) {
+        const int lu = j * TPB + tid, l = lu / K::UPR, j0 = (lu % K::UPR) * 4;
+        const int vmin = a.flip ? W - 4 - j0 - a.dx : j0 - a.dx;
+        const int start = vmin + K::P, q = start & 3;
+        const uint4* win = lds + l * K::ROWU + (start >> 2);
+        const uint4 w0 = win[0], w1 = win[1];
+        uint32_t e[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+        if (q & 1) {
+#pragma unroll
+            for (int m = 0; m < 7; ++m) e[m] = e[m + 1];
+        }
+        if (q & 2) {
+#pragma unroll
+            for (int m = 0; m < 6; ++m) e[m] = e[m + 2];
+        }
+        d[j * TPB] = a.flip ? make_uint4(e[3], e[2], e[1], e[0]) : make_uint4(e[0], e[1], e[2], e[3]);
+    }
+}
+
 // the three launches of one chunk's selection; the recon-only outputs are null at MIDW = 1
 template <int MIDW>
 int launch_curate(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect, int64_t total_images,
@@ -376,6 +587,32 @@ int launch_gather_f32(int width, int B, const float* frames, const float* preds,
     const int units = width * width * 3 / 4, bpf = units / (TPB * GF32_PER);
     hipLaunchKernelGGL(gather_f32_kernel, dim3((unsigned)((int64_t)B * bpf)), dim3(TPB), 0, st, (const uint4*)frames, preds, n, idx,
                        (uint4*)x, pred, units, bpf);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_preprocess_u8_gather_aug(int width, int B, const uint8_t* frames, const float* preds, int64_t n, const int64_t* idx,
+                                    const cvae_augment& aug, float* x, float* pred, int32_t* applied, hipStream_t st) {
+    if (width == 64)
+        hipLaunchKernelGGL(preprocess_u8_gather_aug_kernel<64>, dim3((unsigned)((int64_t)B * AugU8<64>::BPF)), dim3(TPB), 0, st, frames,
+                           preds, n, idx, aug, x, pred, applied);
+    else if (width == 128)
+        hipLaunchKernelGGL(preprocess_u8_gather_aug_kernel<128>, dim3((unsigned)((int64_t)B * AugU8<128>::BPF)), dim3(TPB), 0, st, frames,
+                           preds, n, idx, aug, x, pred, applied);
+    else { cvae_set_error("preprocess_u8_gather_aug: width %d unsupported", width); return -2; }
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_gather_f32_aug(int width, int B, const float* frames, const float* preds, int64_t n, const int64_t* idx,
+                          const cvae_augment& aug, float* x, float* pred, int32_t* applied, hipStream_t st) {
+    if (width == 64)
+        hipLaunchKernelGGL(gather_f32_aug_kernel<64>, dim3((unsigned)((int64_t)B * AugF32<64>::BPF)), dim3(TPB), 0, st,
+                           (const uint4*)frames, preds, n, idx, aug, (uint4*)x, pred, applied);
+    else if (width == 128)
+        hipLaunchKernelGGL(gather_f32_aug_kernel<128>, dim3((unsigned)((int64_t)B * AugF32<128>::BPF)), dim3(TPB), 0, st,
+                           (const uint4*)frames, preds, n, idx, aug, (uint4*)x, pred, applied);
+    else { cvae_set_error("gather_f32_aug: width %d unsupported", width); return -2; }
     CVAE_CHECK_LAUNCH();
     return 0;
 }

@@ -156,9 +156,16 @@ class DeviceDataset(_CuratedDataset):
     def width(self):
         return self.frames.shape[1]
 
-    def gather(self, handle, nb, idx, x, pred):
-        """One training batch: x = frames[idx] / 255 as CHW fp32, pred = preds[idx] (cvae_preprocess_u8_gather)."""
-        handle.preprocess_u8_gather(nb, self.frames, self.preds, idx, x, pred)
+    def gather(self, handle, nb, idx, x, pred, aug=None, applied=None):
+        """One training batch: x = frames[idx] / 255 as CHW fp32, pred = preds[idx] (cvae_preprocess_u8_gather).  aug: the
+        values of augment.Augment.at(draw) — the batch then comes from cvae_preprocess_u8_gather_aug (still one launch), and
+        applied (nb, 4) int32 receives what was drawn per row."""
+        if aug is None:
+            if applied is not None:
+                raise ValueError("applied needs aug: the plain gather draws nothing")
+            handle.preprocess_u8_gather(nb, self.frames, self.preds, idx, x, pred)
+        else:
+            handle.preprocess_u8_gather_aug(nb, self.frames, self.preds, idx, aug, x, pred, applied)
 
     @classmethod
     def from_host(cls, frames_u8, critic=None, device="cuda:0"):
@@ -418,9 +425,15 @@ class ReconDataset(_CuratedDataset):
     def width(self):
         return self.frames.shape[2]
 
-    def gather(self, handle, nb, idx, x, pred):
-        """One training batch: x = frames[idx] (a bit copy), pred = preds[idx] (cvae_gather_f32)."""
-        handle.gather_f32(nb, self.frames, self.preds, idx, x, pred)
+    def gather(self, handle, nb, idx, x, pred, aug=None, applied=None):
+        """One training batch: x = frames[idx] (a bit copy), pred = preds[idx] (cvae_gather_f32).  aug / applied as
+        DeviceDataset.gather, through cvae_gather_f32_aug: flip and shift only (a brightness gain is refused)."""
+        if aug is None:
+            if applied is not None:
+                raise ValueError("applied needs aug: the plain gather draws nothing")
+            handle.gather_f32(nb, self.frames, self.preds, idx, x, pred)
+        else:
+            handle.gather_f32_aug(nb, self.frames, self.preds, idx, aug, x, pred, applied)
 
     def save(self, path):
         """Plain arrays (numpy .npz, uncompressed): frames, preds, source, names, sizes, counts."""

@@ -7,6 +7,8 @@ Everything here is a plain attribute of the trainer, so a test can build one wit
 import numpy as np
 import torch
 
+from .augment import Augment
+
 
 class DeviceTrainer:
     def _init_shared(self, skip_nonfinite, max_grad_norm):
@@ -21,6 +23,22 @@ class DeviceTrainer:
         self.val_history = []             # (step_count, result of evaluate()) per evaluation that fit_device(val=...) ran
         self.best_val = None              # the lowest finite validation loss seen (the CLI's --keep-best / --patience)
         self.val_stale = 0                # evaluations in a row since it last improved
+        self.augment = None               # an augment.Augment: fit_device gathers through the augmented kernels (_init_augment)
+
+    def _init_augment(self, augment, width):
+        """The constructor's `augment` argument: None, or an Augment whose shift fits frames of `width`."""
+        if augment is not None:
+            if not isinstance(augment, Augment):
+                raise ValueError(f"augment {augment!r}: an augment.Augment or None")
+            augment.check_width(width)
+        self.augment = augment
+
+    def _check_augment(self, dataset):
+        """Before the first launch of a fit_device: fp32 entries (ReconDataset) take no brightness gain."""
+        augment = getattr(self, "augment", None)
+        if augment is not None and augment.gain_q16 != 0 and dataset.frames.dtype != torch.uint8:
+            raise ValueError(f"{augment!r} on a dataset of fp32 entries: they are Tanh outputs in (-1, 1), a brightness gain "
+                             "clamped at 1 has no meaning for them; use brightness=0")
 
     # ---- the optimizer launches ----
     def _update(self, theta, grad_scale):
@@ -68,12 +86,17 @@ class DeviceTrainer:
         applied, skipped = self._guard_read() if self.guarded else (self.step_count, 0)
         history = [(int(t), {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in r.items() if k not in ("per_image", "per_frame")})
                    for t, r in self.val_history]
-        return {"step_count": int(self.step_count), "applied": applied, "skipped": skipped, "val_history": history,
-                "best_val": self.best_val, "val_stale": int(self.val_stale)}
+        state = {"step_count": int(self.step_count), "applied": applied, "skipped": skipped, "val_history": history,
+                 "best_val": self.best_val, "val_stale": int(self.val_stale)}
+        if getattr(self, "augment", None) is not None:      # absent without one; draw = step_count: a resumed run continues exactly
+            state["augment"] = self.augment.state_dict()
+        return state
 
     def _load_shared_state(self, state):
         """The counterpart; raises before it changes anything."""
         applied, skipped, steps = int(state["applied"]), int(state["skipped"]), int(state["step_count"])
+        saved = state.get("augment")
+        restored = None if saved is None else Augment.from_state_dict(saved).check_width(self.h.width)
         if not self.guarded and applied != steps:
             raise ValueError(f"the state skipped {skipped} of {steps} steps: an unguarded trainer corrects Adam's bias by step_count "
                              "and cannot continue it; construct the trainer with skip_nonfinite=True")
@@ -81,6 +104,8 @@ class DeviceTrainer:
         self.val_history = [(int(t), dict(r)) for t, r in state.get("val_history", [])]      # absent in states written before validation existed
         self.best_val = state.get("best_val")
         self.val_stale = int(state.get("val_stale", 0))
+        if restored is not None:           # a state without one keeps what the trainer was built with
+            self.augment = restored
         if self.guarded:
             self._guard_write(applied, skipped)
 
@@ -95,7 +120,11 @@ class DeviceTrainer:
         """Per epoch np.random.shuffle of the host indices (one draw; uploaded once), slices of B with the ragged last one kept;
         per slice one dataset.gather launch into x / pred and batch(x[:nb], pred[:nb]), which takes the step.  val is evaluated
         (at val_batch) after every val_every steps, or at the end of every epoch; a true return value of on_val ends the fit.
-        Returns what the last batch() returned, None if none ran."""
+        With self.augment the gather is the augmented one under augment.at(step_count) (the step the batch is for); without,
+        gather is called with the five positional arguments it always had.  Returns what the last batch() returned, None if
+        none ran."""
+        self._check_augment(dataset)
+        augment = getattr(self, "augment", None)           # a trainer assembled by hand (tests) may not carry the field
         if val is not None:
             if val_every is not None and int(val_every) < 1:
                 raise ValueError(f"val_every {val_every!r}: a positive number of optimizer steps, or None for once per epoch")
@@ -109,7 +138,10 @@ class DeviceTrainer:
             d_idx = torch.from_numpy(idx).to(dev)          # indices of arange(n): in [0, n) by construction
             for b in range(0, n, B):
                 nb = min(B, n - b)
-                dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], pred[:nb])
+                if augment is None:
+                    dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], pred[:nb])
+                else:
+                    dataset.gather(self.h, nb, d_idx[b:b + nb], x[:nb], pred[:nb], aug=augment.at(self.step_count))
                 last = batch(x[:nb], pred[:nb])
                 if val is not None and val_every is not None and self.step_count % int(val_every) == 0 \
                         and self._validate(val, val_batch, on_val):

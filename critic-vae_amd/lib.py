@@ -50,6 +50,12 @@ class Objective(C.Structure):
 MSGRAD_REFERENCE, MSGRAD_USED = 0, 1
 
 
+class AugmentParams(C.Structure):
+    """cvae_augment (include/cvae.h): the key and ranges of one augmented batch gather."""
+    _fields_ = [("key", C.c_uint64), ("flip_below", C.c_uint32), ("max_shift", C.c_int32), ("gain_q16", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class Panel(C.Structure):
     """cvae_panel (include/cvae.h): one w x w panel of cvae_compose_frames."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("data", C.c_void_p), ("batch_stride", C.c_int64)]
@@ -131,6 +137,8 @@ _SIGS = {
     "cvae_curate_select_recon": (C.c_int, [_p, _i32, _p, _i64, _p, _i32, _i64] + [_p] * 10),
     "cvae_recon_zcat": (C.c_int, [_p, _i32, _p, _p, _p, _p, _i64, _p, _p]),
     "cvae_gather_f32": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p]),
+    "cvae_preprocess_u8_gather_aug": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, C.POINTER(AugmentParams), _p, _p, _p, _p]),
+    "cvae_gather_f32_aug": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, C.POINTER(AugmentParams), _p, _p, _p, _p]),
     "cvae_diff_normalize": (C.c_int, [_p, _i32, _p, C.c_double, C.c_double, _i32] + [_p] * 6),
     "cvae_mask_counts": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_crf_scratch_bytes": (_i64, [_p, _i32]),
@@ -555,6 +563,35 @@ class Handle:
         assert idx.numel() >= B and preds.numel() >= frames.shape[0] and x.numel() >= B * 3 * w * w and pred.numel() >= B
         self._check(self.lib.cvae_gather_f32(self.h, B, int(w), _ptr(frames), _ptr(preds), frames.shape[0],
                                              self._i64(idx, "idx"), _ptr(x), _ptr(pred), _stream()))
+
+    # ---- the augmented batch gathers (augment.py) ----
+    @staticmethod
+    def _aug(aug):
+        """An AugmentParams structure, a (key, flip_below, max_shift, gain_q16) tuple as augment.Augment.at() returns it, or
+        None (a null pointer: CVAE_EINVAL) -> the ctypes argument."""
+        if aug is not None and not isinstance(aug, AugmentParams):
+            aug = AugmentParams(*aug)
+        return None if aug is None else C.byref(aug)
+
+    def preprocess_u8_gather_aug(self, B, frames_u8, preds, idx, aug, x, pred, applied=None):
+        """preprocess_u8_gather with the flip / shift / gain `aug` draws per sample; applied: (>= B, 4) int32 device rows
+        [flip, dx, dy, num - 2^31] or None."""
+        w = frames_u8.shape[1]
+        assert idx.numel() >= B and preds.numel() >= frames_u8.shape[0] and x.numel() >= B * 3 * w * w and pred.numel() >= B
+        assert applied is None or isinstance(applied, int) or applied.numel() >= 4 * B
+        self._check(self.lib.cvae_preprocess_u8_gather_aug(self.h, B, int(w), self._u8(frames_u8, "frames"), _ptr(preds),
+                                                           frames_u8.shape[0], self._i64(idx, "idx"), self._aug(aug), _ptr(x),
+                                                           _ptr(pred), self._i32(applied, "applied"), _stream()))
+
+    def gather_f32_aug(self, B, frames, preds, idx, aug, x, pred, applied=None):
+        """gather_f32 with the flip / shift `aug` draws per sample (bit copies; a gain is CVAE_EINVAL); applied as above."""
+        w = frames.shape[2]
+        assert frames.dim() == 4 and frames.shape[1] == 3 and frames.shape[3] == w
+        assert idx.numel() >= B and preds.numel() >= frames.shape[0] and x.numel() >= B * 3 * w * w and pred.numel() >= B
+        assert applied is None or isinstance(applied, int) or applied.numel() >= 4 * B
+        self._check(self.lib.cvae_gather_f32_aug(self.h, B, int(w), _ptr(frames), _ptr(preds), frames.shape[0],
+                                                 self._i64(idx, "idx"), self._aug(aug), _ptr(x), _ptr(pred),
+                                                 self._i32(applied, "applied"), _stream()))
 
     # ---- segmentation evaluation (eval_textured_frames, vae_utility.py:162-212) ----
     def diff_normalize(self, B, diff, mean_max, diff_factor, thr, gt, diff_u8, mask=None, counts=None, hist=None):

@@ -33,6 +33,7 @@ from . import synth
 from .fit import DeviceTrainer
 from .lib import N_SCALARS, SCORE_COLS, SYNC_DOUBLES, SYNC_POINTS
 from .nets import VariationalAutoencoder
+from .augment import Augment
 from .objective import Objective, compose
 
 
@@ -88,7 +89,7 @@ class FusedTrainer(DeviceTrainer):
 
     def __init__(self, vae, lr=P.lr, betas=P.adam_betas, eps=P.adam_eps, process_group=None, world_size=1,
                  overlap=None, reduce_dtype=None, sync=True, global_stats=None, skip_nonfinite=False, max_grad_norm=None,
-                 objective=None):
+                 objective=None, augment=None):
         """Construction with world_size > 1 is a COLLECTIVE (sync_replicas: five broadcasts from rank 0) unless
         sync=False.
         overlap: all-reduce the gradient in three buckets while backward still runs (default for
@@ -113,7 +114,15 @@ class FusedTrainer(DeviceTrainer):
         and bits the step always had.  Otherwise the step calls cvae_loss_obj with objective.at(step_count): the four values
         travel by value in the launch, a schedule costs no copy and no synchronisation.  The objective is saved and restored
         with the trainer, so a run resumed in the middle of a warm-up continues exactly.  Not with global_stats: the fp64
-        record of the staged step has no slot for the squared-error sum, and its finish step carries the reference weights."""
+        record of the staged step has no slot for the squared-error sum, and its finish step carries the reference weights.
+        augment: an augment.Augment, or None = the plain batch gathers with the launches and bits fit_device always had.
+        Otherwise fit_device (only) builds every batch with cvae_preprocess_u8_gather_aug / cvae_gather_f32_aug under
+        augment.at(step_count): flip, shift and brightness happen inside the one gather launch, the key travels by value.
+        The critic value of a sample stays the stored one.  evaluate() never augments, step() takes the batch it is given,
+        fit_u8 (the host feeder) refuses.  A shift above width / 4 raises here; a ReconDataset with brightness > 0 raises in
+        fit_device before the first launch.  Saved and restored with the trainer: the draw is step_count, so a resumed run
+        applies exactly the transforms of the uninterrupted one.  With world_size > 1 every rank uses the same key on its
+        own dataset indices; no collective is added."""
         self.vae = vae
         self.h = vae.handle
         if overlap is None:
@@ -137,6 +146,7 @@ class FusedTrainer(DeviceTrainer):
         self.buckets = [self.h.grad_bucket(ph) for ph in range(3)]
         self.lr, self.betas, self.eps = lr, betas, eps
         self._init_shared(skip_nonfinite, max_grad_norm)      # guard fields, step_count, val_history / best_val / val_stale
+        self._init_augment(augment, vae.width)
         self.world_size, self.pg = world_size, process_group
         dev = vae.theta.device
         n = vae.theta.numel()
@@ -283,7 +293,8 @@ class FusedTrainer(DeviceTrainer):
         """What a restart needs beside the two network files: the Adam moments (CPU copies), step_count, the applied / skipped
         counters (an unguarded trainer applied every step) and the VAE's num_batches_tracked.  With the networks restored by
         load_networks, a resumed run is exact at the step() level — the caller supplies eps; the generators that fit_* draw
-        shuffles and eps from are not saved.  "objective": the objective's state_dict (absent with objective=None)."""
+        shuffles and eps from are not saved.  "objective": the objective's state_dict (absent with objective=None);
+        "augment": the augmentation's (absent with augment=None)."""
         state = {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(),
                  "num_batches_tracked": int(self.vae.num_batches_tracked), **self._shared_state()}
         if self.objective is not None:
@@ -309,6 +320,9 @@ class FusedTrainer(DeviceTrainer):
         batch i+1 is gathered, copied (pinned, side stream) while step i computes; uint8 -> fp32 CHW/255 and the
         critic run on the GPU.  eps ~ N(0,1) from `generator` (device).  Returns the loss scalars of the last step."""
         from .feeder import FrameFeeder
+        if self.augment is not None:
+            raise ValueError("fit_u8 with an augmentation: the transforms live in the device gathers (fit_device); the host "
+                             "feeder path has none")
         dev = self.vae.theta.device
         feeder = FrameFeeder(frames_u8, batch_size, dev, self.h, critic=critic)
         n, scal = frames_u8.shape[0], None
@@ -558,7 +572,22 @@ def build_parser():
     ap.add_argument("--kld-warmup", type=int, default=None, metavar="N", help="fused trainer: KLD weight * min(1, (step + 1) / N)")
     ap.add_argument("--msssim-from", type=int, default=None, metavar="N", help="fused trainer: no MS-SSIM term (and no pyramid) before "
                     "optimizer step N; needs --mse-weight > 0")
+    ap.add_argument("--augment-flip", type=float, default=None, metavar="P", help="-train --episodes, -second, -critic: flip a "
+                    "gathered frame horizontally with probability P.  Any of these four flags moves the batch gather to its "
+                    "augmented kernel (augment.py); critic values / targets stay the stored ones; validation never augments")
+    ap.add_argument("--augment-shift", type=int, default=None, metavar="S", help="shift by dx, dy in [-S, S] whole pixels, edges "
+                    "replicated; S <= width / 4")
+    ap.add_argument("--augment-brightness", type=float, default=None, metavar="B", help="gain within 1 +- B on uint8 frames, "
+                    "clamped at 1 (not -second: its entries are Tanh outputs)")
+    ap.add_argument("--augment-seed", type=int, default=None, metavar="N", help="seed of the per-sample hash (default 0)")
     return ap
+
+
+def augment_from_args(args):
+    """The Augment the four --augment-* flags describe, or None when none of them is given.  Raises ValueError as Augment does."""
+    given = {"flip": args.augment_flip, "shift": args.augment_shift, "brightness": args.augment_brightness, "seed": args.augment_seed}
+    given = {k: v for k, v in given.items() if v is not None}
+    return Augment(**given) if given else None
 
 
 def objective_from_args(args):
@@ -582,6 +611,19 @@ def main(argv=None):
     if args.objective is not None and args.train and args.episodes is None and (args.objective.kld_warmup or args.objective.msssim_from):
         ap.error("--kld-warmup and --msssim-from belong to the fused trainer (-train --episodes, -second): the synthetic -train "
                  "loop is the reference's own and follows no schedule")
+    try:
+        args.augment = augment_from_args(args)
+        if args.augment is not None:
+            args.augment.check_width(P.w)
+    except ValueError as e:
+        ap.error(str(e))
+    if args.augment is not None:
+        if not ((args.train and args.episodes is not None) or args.second or (args.critic_mode and not args.eval_only)):
+            ap.error("--augment-flip, --augment-shift, --augment-brightness and --augment-seed belong to the runs that gather their "
+                     "batches on the device: -train --episodes, -second and -critic")
+        if args.second and args.augment.gain_q16 != 0:
+            ap.error("-second takes no --augment-brightness: its entries are Tanh outputs in (-1, 1), a gain clamped at 1 has no "
+                     "meaning for them")
     if args.max_grad_norm is not None and not args.max_grad_norm > 0:
         ap.error("--max-grad-norm needs a positive number")
     if args.val_fraction is None:
@@ -672,15 +714,18 @@ def _fit_and_save(args, vae, ds, second):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     trainer = FusedTrainer(vae, skip_nonfinite=args.skip_nonfinite, max_grad_norm=args.max_grad_norm,
-                           objective=getattr(args, "objective", None))
+                           objective=getattr(args, "objective", None), augment=getattr(args, "augment", None))
     if args.resume:
-        given = trainer.objective
+        given, given_aug = trainer.objective, trainer.augment
         load_networks(vae, args.resume, second=second)
         load_trainer(trainer, os.path.join(args.resume, TRAINER_FILE))
         print(f"resumed from {args.resume} at step {trainer.step_count}")
         _check_resumed_objective(given, trainer, args.resume)
+        _check_resumed_augment(given_aug, trainer, args.resume)
     if trainer.objective is not None:
         print(trainer.objective.describe())
+    if trainer.augment is not None:
+        print(trainer.augment.describe())
     gen = torch.Generator(device=vae.theta.device)
     gen.manual_seed(args.seed)
     ds, val_kw = _hold_out(args, ds, _ValidationLog(args, second, by_objective=trainer.objective is not None), "entries", curated=True)
@@ -713,6 +758,21 @@ def _check_resumed_objective(given, trainer, directory):
         was = "none (the reference loss through cvae_loss, validation judged by total_loss)" if saved is None else repr(saved)
         raise SystemExit(f"--resume {directory}: the checkpoint's objective is {was}, the flags give {given!r}.  A resumed run keeps "
                          "its objective (schedules, best_val and --patience refer to it): drop the objective flags, or repeat the run's own")
+
+
+def _check_resumed_augment(given, trainer, directory):
+    """--resume with --augment-* flags, by the rule of the objective: the transforms of step s are a function of (seed, s), so
+    a resumed run continues the augmentation it was started with.  Without flags the saved one (or none) continues; flags that
+    describe another one are refused with both named."""
+    saved = trainer.augment if trainer.augment is not given else None       # load_trainer replaced it only if the state carried one
+    if given is None:
+        if trainer.augment is not None:
+            print(f"continuing with the augmentation saved in {directory}")
+        return
+    if saved is None or saved != given:
+        was = "none (the plain batch gathers)" if saved is None else repr(saved)
+        raise SystemExit(f"--resume {directory}: the checkpoint's augmentation is {was}, the flags give {given!r}.  A resumed run "
+                         "keeps its augmentation: drop the --augment-* flags, or repeat the run's own")
 
 
 BEST_DIR = "best"
@@ -859,7 +919,9 @@ def _train_critic(args):
     from .critic_train import CriticTrainer
     critic, ds, device = _critic_and_dataset(args, args.datasize)
     trainer = CriticTrainer(critic, lr=args.lr, dropout=args.dropout, loss=args.loss, skip_nonfinite=args.skip_nonfinite,
-                            max_grad_norm=args.max_grad_norm)
+                            max_grad_norm=args.max_grad_norm, augment=getattr(args, "augment", None))
+    if trainer.augment is not None:
+        print(trainer.augment.describe())
     gen = torch.Generator(device=device)
     gen.manual_seed(args.seed)
     ds, val_kw = _hold_out(args, ds, _CriticValidationLog(args), "frames", curated=False)

@@ -524,6 +524,49 @@ int cvae_recon_zcat(cvae_handle h, int32_t n_entries, const int64_t* ent_sel, co
 int cvae_gather_f32(cvae_handle h, int32_t batch, int32_t width, const float* frames, const float* preds,
                     int64_t n_frames, const int64_t* idx, float* x, float* pred, void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Augmentation in the batch gather (no reference counterpart: vae.py trains on the frames as stored): horizontal flip,
+ * shift by whole pixels with edge replication, and a brightness gain, applied inside the one launch that builds a batch.
+ *
+ * Per gathered sample four integers come from a counter-based hash, mix64(z) = the project's mixer (z += 0x9E3779B97F4A7C15;
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31; all mod 2^64):
+ *   r    = mix64(key ^ mix64((uint64) s)), s = the sample's dataset index idx[b]
+ *   flip = (r >> 40) < flip_below                                 (24 bits against flip_below in [0, 2^24])
+ *   k    = ((r >> 24) & 0xFFFF) - 32768, num = 2^31 + gain_q16 * k (fits 32 unsigned bits), gain g = (float) num * 2^-31
+ *          (round-to-nearest conversion, exact scaling): g = 1 + (gain_q16 / 65536) * (k / 32768), within 1 +- brightness
+ *   dx   = ((r >> 12) & 0xFFF) % (2 S + 1) - S,  dy = (r & 0xFFF) % (2 S + 1) - S,  S = max_shift
+ * Output pixel (i, j) of every channel is source pixel (clamp(i - dy, 0, W-1), clamp(jj - dx, 0, W-1)), jj = flip ? W-1-j : j:
+ * edge replication, no black border.  uint8 sources: the value is fminf(v * g, 1.0f), v = (float) u8 / 255.0f as the plain
+ * gather writes it (one multiply, no add beside it: nothing contracts).  fp32 sources: a bit copy, and gain_q16 must be 0
+ * (the entries are Tanh outputs in (-1, 1); a clamp at 1 means nothing there).  pred[b] = preds[s], the STORED value: the
+ * transforms are taken to preserve it, the critic is not run again on the augmented frame.
+ * {key, 0, 0, 0, 0} gives g = 1 exactly and writes the bits of the plain gather.
+ *
+ * aug is HOST memory, read during the call and passed to the kernel by value (as cvae_objective is): a new key per step
+ * costs no copy and no synchronisation.  The caller derives key from its seed and step; the library only hashes.
+ * applied_or_null: (batch, 4) int32 device rows [flip, dx, dy, num - 2^31] = what the kernel drew for row b (one thread per
+ * sample writes it).  An index outside [0, n_frames) gives a NaN image, a NaN pred and an applied row of zeros, and is never
+ * read.  Otherwise the contract of cvae_preprocess_u8_gather / cvae_gather_f32: same shapes, alignment, 64-bit frame offsets,
+ * float4 stores per channel plane; nothing allocates or synchronises.
+ * CVAE_EINVAL, before any device access: null aug, flip_below > 2^24, max_shift outside [0, width / 4], gain_q16 outside
+ * [0, 65535], gain_q16 != 0 in the fp32 variant, reserved != 0, and whatever the plain gathers refuse.
+ * Out of scope: re-evaluating the critic on augmented frames, the host feeder path, rotation / scaling / colour transforms
+ * beyond a gain.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct cvae_augment {
+    uint64_t key;            /* mixed (seed, draw): chosen by the caller per step */
+    uint32_t flip_below;     /* round(p_flip * 2^24), 0 = never, 2^24 = always */
+    int32_t  max_shift;      /* S: dx, dy in [-S, S]; 0 <= S <= width / 4 */
+    int32_t  gain_q16;       /* round(brightness * 65536), 0 = gain 1 */
+    int32_t  reserved;       /* 0 */
+} cvae_augment;
+int cvae_preprocess_u8_gather_aug(cvae_handle h, int32_t batch, int32_t width, const uint8_t* frames_hwc,
+                                  const float* preds, int64_t n_frames, const int64_t* idx, const cvae_augment* aug,
+                                  float* x, float* pred, int32_t* applied_or_null, void* stream);
+int cvae_gather_f32_aug(cvae_handle h, int32_t batch, int32_t width, const float* frames, const float* preds,
+                        int64_t n_frames, const int64_t* idx, const cvae_augment* aug, float* x, float* pred,
+                        int32_t* applied_or_null, void* stream);
+
 /* Difference mask of the inference path (get_diff_image, vae_utility.py:256-277), batched:
  * diff (B,W,W) = 0.2989|dR| + 0.5870|dG| + 0.1140|dB| of recon_zero - recon_one (both (B,3,W,W)). */
 int cvae_diff_grey(cvae_handle h, int32_t batch, const float* recon_one, const float* recon_zero,
