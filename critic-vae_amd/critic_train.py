@@ -25,6 +25,7 @@ import torch
 from . import params as P
 from . import synth
 from .fit import DeviceTrainer
+from .optim import critic_layout, decay_ranges
 from .lib import CRITIC_DECISIONS, CRITIC_KEEP, CRITIC_LOSS, CRITIC_SCORE_COLS, CRITIC_SCORE_STATE_DOUBLES, CRITIC_TRAIN_FLOATS
 
 MAX_BATCH = 65536            # cvae_critic_grad's and cvae_critic_score's own cap (include/cvae.h)
@@ -99,18 +100,24 @@ class CriticTrainer(DeviceTrainer):
     sigmoid output) or "mse".  skip_nonfinite / max_grad_norm: the guarded step of FusedTrainer (train.py).  augment: an
     augment.Augment or None — fit_device then builds every batch with cvae_preprocess_u8_gather_aug under
     augment.at(step_count) (still one launch per batch); the TARGET of a frame stays the stored one.  evaluate() and step()
-    never augment; the augmentation is saved and restored with the trainer."""
+    never augment; the augmentation is saved and restored with the trainer.  optim: an optim.Optim or None — as for
+    FusedTrainer: LR schedule with `lr` as the peak, decoupled weight decay on the seven *.weight tensors (their boundaries fall
+    anywhere in the flat block: the kernel's ranges are in elements), an EMA of the block in `ema` (no auxiliary buffer: the
+    critic has no BatchNorm), all inside the one Adam launch; evaluate(..., ema=True) scores the averaged block."""
 
     def __init__(self, critic, lr=1e-4, betas=P.adam_betas, eps=P.adam_eps, dropout=0.3, loss="bce", skip_nonfinite=False,
-                 max_grad_norm=None, augment=None):
+                 max_grad_norm=None, augment=None, optim=None):
         if loss not in CRITIC_LOSS:
             raise ValueError(f"loss {loss!r}: one of {sorted(CRITIC_LOSS)}")
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout {dropout!r} outside [0, 1)")
-        self._init_shared(skip_nonfinite, max_grad_norm)      # guard fields, step_count, val_history / best_val / val_stale
+        self._init_shared(skip_nonfinite, max_grad_norm, optim)      # guard fields, step_count, val_history / best_val / val_stale, optim
+        self.decay_ranges = decay_ranges(critic_layout())     # the seven *.weight tensors, at their element offsets
         self.critic, self.h = critic, critic.handle
         self._init_augment(augment, 64)
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
+        if self.optim is not None:
+            self.optim.check_lr(self.lr)
         self.dropout, self.loss = float(dropout), loss
         dev = critic.flat.device
         if dev.type != "cuda":
@@ -169,14 +176,19 @@ class CriticTrainer(DeviceTrainer):
             raise ValueError(f"the dataset is on {dataset.frames.device}, the critic on {dev}")
         return dev, int(batch_size)
 
-    def evaluate(self, dataset, batch_size, per_frame=False):
+    def evaluate(self, dataset, batch_size, per_frame=False, ema=False):
         """The critic on a held-out DeviceDataset whose `preds` slot holds the targets (episodes.critic_dataset,
         split_by_trajectory): the dataset in order, one cvae_critic_score launch per batch — uint8 frame, EVAL-mode forward
         (Dropout = identity), row, pooling — into ONE fp64 device record that the host reads once, at the end.  Returns
         summarize_record's dict (loss = this trainer's chosen loss), plus per_frame = the (N, 8) device rows when asked for.
         batch_size: 1..65 536, whatever the handle's max_batch.  Draws nothing from any random generator and leaves the
-        parameters, the Adam state, the step count and the guard record untouched."""
+        parameters, the Adam state, the step count and the guard record untouched.  ema=True: the averaged block instead of theta."""
         dev, B = self._check_dataset(dataset, batch_size, MAX_BATCH)
+        theta = self.theta
+        if ema:
+            if not self.has_ema():
+                raise ValueError("evaluate(ema=True): this trainer keeps no averaged weights (optim=Optim(ema=...))")
+            theta = self._ema_view(self.theta)[0]
         h, n = self.h, len(dataset)
         if n < 1:
             raise ValueError("evaluate(): the dataset is empty")
@@ -186,7 +198,7 @@ class CriticTrainer(DeviceTrainer):
         targets = dataset.preds.view(-1)
         for b in range(0, n, B):
             nb = min(B, n - b)
-            h.critic_score(nb, dataset.frames[b:b + nb], targets[b:b + nb], self.theta, state=state, scratch=scratch,
+            h.critic_score(nb, dataset.frames[b:b + nb], targets[b:b + nb], theta, state=state, scratch=scratch,
                            per_frame=None if rows is None else rows[b:b + nb])
         out = summarize_record(state[:RECORD_DOUBLES].cpu().numpy(), self.loss)        # the one host read
         if per_frame:

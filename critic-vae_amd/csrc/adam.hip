@@ -6,16 +6,78 @@
 #include "../../include/cvae.h"
 #include <math.h>
 
-// one grid-stride pass of the update, shared by the plain and the guarded kernel: the same expressions, the same bits
+// The options of cvae_adam_step_opt / cvae_adam_step_guarded_opt as the kernels take them: by value in the launch, as PadGaps is.
+struct OptRanges {
+    int32_t n;
+    int64_t begin[CVAE_OPT_MAX_RANGES], end[CVAE_OPT_MAX_RANGES];
+};
+struct OptArgs {
+    float decay_mul, ema_omd;
+    float* ema;                 // n floats, or nullptr
+    const float* aux;           // n_aux floats, read only
+    float* aux_ema;
+    int32_t n_aux;
+    OptRanges r;
+};
+
+// one grid-stride pass of the update, shared by the plain and the guarded kernel and by their _opt forms: the same expressions,
+// the same bits.  OPT: decoupled weight decay on the elements of o.r first (one fp32 product, rounded on its own: __fmul_rn keeps
+// it out of the fused multiply-add of the update); EMA: o.ema follows the p just written.
+template <bool OPT, bool EMA>
 __device__ __forceinline__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, int64_t n4, float omb1, float b2, float omb2, float step_size,
-                                            float sqrt_bc2, float eps, float gscale) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        float4 pv = reinterpret_cast<float4*>(p)[i];
-        const float4 gv = reinterpret_cast<const float4*>(g)[i];
-        float4 mv = reinterpret_cast<float4*>(m)[i];
-        float4 vv = reinterpret_cast<float4*>(v)[i];
+                                            float sqrt_bc2, float eps, float gscale, const OptArgs* o) {
+    // OPT: lane l keeps range l % 16 of the table (an unused slot is the empty [0, 0)), so one trip tests the wave's 256-element
+    // span [e0, e0 + 256) against all 16 ranges with four vector compares and two ballots.  Wholly inside one range, or outside
+    // all of them: done.  Where a boundary crosses the span, the ranges that touch it (one or two) are broadcast out of their
+    // lanes and every lane tests its four elements against them.  No memory access and no scalar loop per trip: the first form
+    // of this lookup walked the table with scalar loads per element in the boundary waves, and those 22 waves alone
+    // outlasted the rest of the pass (LABNOTES).  Every lane of a wave that still has a float4 takes the trip, so the ballots see all 16
+    // slots in a ragged last wave too.
+    const int64_t lane = threadIdx.x & 63;
+    int64_t rb = 0, re = 0;
+    bool ranged = false;
+    if constexpr (OPT) {
+        ranged = o->r.n > 0;
+        const int k = threadIdx.x & (CVAE_OPT_MAX_RANGES - 1);
+        if (k < o->r.n) { rb = o->r.begin[k]; re = o->r.end[k]; }
+    }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; (OPT ? i - lane : i) < n4; i += (int64_t)gridDim.x * 256) {
+        // the four loads go out first: the table's own loads (first trip) then return under them, not in front of them
+        const bool live = !OPT || i < n4;
+        float4 pv = make_float4(0.f, 0.f, 0.f, 0.f), gv = pv, mv = pv, vv = pv;
+        if (live) {
+            pv = reinterpret_cast<float4*>(p)[i];
+            gv = reinterpret_cast<const float4*>(g)[i];
+            mv = reinterpret_cast<float4*>(m)[i];
+            vv = reinterpret_cast<float4*>(v)[i];
+        }
+        unsigned decay = 0u;                // bit e: element 4 i + e lies in a decayed range
+        if constexpr (OPT) {
+            if (ranged) {
+                const int64_t e0 = 4 * (i - lane);
+                const bool full = rb <= e0 && re >= e0 + 256, touched = rb < e0 + 256 && re > e0;
+                if (__any((int)full)) {
+                    decay = 0xfu;
+                } else {
+                    uint64_t tm = __ballot((int)touched) & 0xffffull;          // the table's slots, once each
+                    while (tm) {
+                        const int k = __builtin_ctzll(tm);
+                        tm &= tm - 1;
+                        const int64_t b = ((int64_t)__builtin_amdgcn_readlane((int)(rb >> 32), k) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)rb, k);
+                        const int64_t e = ((int64_t)__builtin_amdgcn_readlane((int)(re >> 32), k) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)re, k);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) decay |= (4 * i + q >= b && 4 * i + q < e) ? 1u << q : 0u;
+                    }
+                }
+            }
+            if (!live) continue;
+        }
         float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+        if constexpr (OPT) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pp[e] = (decay >> e & 1u) ? __fmul_rn(pp[e], o->decay_mul) : pp[e];
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float gr = gp[e] * gscale;
@@ -27,6 +89,20 @@ __device__ __forceinline__ void adam_update(float* __restrict__ p, const float* 
         reinterpret_cast<float4*>(p)[i] = pv;
         reinterpret_cast<float4*>(m)[i] = mv;
         reinterpret_cast<float4*>(v)[i] = vv;
+        if constexpr (EMA) {
+            float4 ev = reinterpret_cast<float4*>(o->ema)[i];
+            float* ep = &ev.x;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ep[e] = ep[e] + (pp[e] - ep[e]) * o->ema_omd;
+            reinterpret_cast<float4*>(o->ema)[i] = ev;
+        }
+    }
+    if constexpr (EMA) {                                            // the small second buffer: the last workgroup, element by element
+        if (blockIdx.x == gridDim.x - 1)
+            for (int j = threadIdx.x; j < o->n_aux; j += 256) {
+                const float a = o->aux[j], e = o->aux_ema[j];
+                o->aux_ema[j] = e + (a - e) * o->ema_omd;
+            }
     }
 }
 
@@ -34,7 +110,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n4,
                                                    float omb1, float b2, float omb2, float step_size,
                                                    float sqrt_bc2, float eps, float gscale) {
-    adam_update(p, g, m, v, n4, omb1, b2, omb2, step_size, sqrt_bc2, eps, gscale);
+    adam_update<false, false>(p, g, m, v, n4, omb1, b2, omb2, step_size, sqrt_bc2, eps, gscale, nullptr);
 }
 
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2,
@@ -159,7 +235,7 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p
                                                            const cvae_guard_record* __restrict__ r) {
     if (r->apply == 0) return;
     const float b1 = r->beta1, b2 = r->beta2;
-    adam_update(p, g, m, v, n4, 1.0f - b1, b2, 1.0f - b2, r->step_size, r->sqrt_bc2, eps, r->gscale);
+    adam_update<false, false>(p, g, m, v, n4, 1.0f - b1, b2, 1.0f - b2, r->step_size, r->sqrt_bc2, eps, r->gscale, nullptr);
 }
 int launch_adam_guarded(float* p, const float* g, float* m, float* v, int64_t n, float eps, const void* state, hipStream_t st) {
     if (n % 4 != 0) { cvae_set_error("guarded adam: n=%lld must be a multiple of 4", (long long)n); return -1; }
@@ -169,6 +245,67 @@ int launch_adam_guarded(float* p, const float* g, float* m, float* v, int64_t n,
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n4, eps,
                        &reinterpret_cast<const GuardState*>(state)->rec);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the optimizer options (include/cvae.h): decoupled weight decay on element ranges, an EMA of the parameters and of one
+// small auxiliary buffer, inside the same single pass.  The plain and the guarded kernel above stay as they are. ----
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_opt_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, int64_t n4, float omb1, float b2, float omb2,
+                                                       float step_size, float sqrt_bc2, float eps, float gscale, OptArgs o) {
+    adam_update<true, EMA>(p, g, m, v, n4, omb1, b2, omb2, step_size, sqrt_bc2, eps, gscale, &o);
+}
+// apply == 0: no store at all, the EMA buffers included
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_guarded_opt_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, int64_t n4, float eps,
+                                                               const cvae_guard_record* __restrict__ r, OptArgs o) {
+    if (r->apply == 0) return;
+    const float b1 = r->beta1, b2 = r->beta2;
+    adam_update<true, EMA>(p, g, m, v, n4, 1.0f - b1, b2, 1.0f - b2, r->step_size, r->sqrt_bc2, eps, r->gscale, &o);
+}
+
+// The checked cvae_opt_args -> the kernels' OptArgs.  ema_omd == 0 moves no average: such a launch is the one without an EMA.
+static OptArgs opt_pack(const cvae_opt_args* opt, float* ema, const float* aux, float* aux_ema, int32_t n_aux) {
+    OptArgs o{};
+    o.decay_mul = opt->decay_mul;
+    o.r.n = opt->n_ranges;
+    for (int k = 0; k < opt->n_ranges; ++k) { o.r.begin[k] = opt->begin[k]; o.r.end[k] = opt->end[k]; }
+    if (ema && opt->ema_omd != 0.f) {
+        o.ema = ema; o.ema_omd = opt->ema_omd;
+        if (n_aux > 0) { o.aux = aux; o.aux_ema = aux_ema; o.n_aux = n_aux; }
+    }
+    return o;
+}
+static unsigned opt_blocks(int64_t n4) {
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    return (unsigned)(blocks < 1 ? 1 : blocks);              // n == 0 with an auxiliary buffer: one workgroup for it
+}
+int launch_adam_opt(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps,
+                    float gscale, const cvae_opt_args* opt, float* ema, const float* aux, float* aux_ema, int32_t n_aux, hipStream_t st) {
+    const OptArgs o = opt_pack(opt, ema, aux, aux_ema, n_aux);
+    if (n == 0 && o.n_aux == 0) return 0;
+    const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
+    const int64_t n4 = n / 4;
+    const float step_size = (float)((double)lr / bc1), sqrt_bc2 = (float)sqrt(bc2);
+    if (o.ema) hipLaunchKernelGGL(adam_opt_kernel<true>, dim3(opt_blocks(n4)), dim3(256), 0, st, p, g, m, v, n4, 1.0f - b1, b2, 1.0f - b2,
+                                  step_size, sqrt_bc2, eps, gscale, o);
+    else hipLaunchKernelGGL(adam_opt_kernel<false>, dim3(opt_blocks(n4)), dim3(256), 0, st, p, g, m, v, n4, 1.0f - b1, b2, 1.0f - b2,
+                            step_size, sqrt_bc2, eps, gscale, o);
+    CVAE_CHECK_LAUNCH();
+    return 0;
+}
+int launch_adam_guarded_opt(float* p, const float* g, float* m, float* v, int64_t n, float eps, const void* state,
+                            const cvae_opt_args* opt, float* ema, const float* aux, float* aux_ema, int32_t n_aux, hipStream_t st) {
+    const OptArgs o = opt_pack(opt, ema, aux, aux_ema, n_aux);
+    if (n == 0 && o.n_aux == 0) return 0;
+    const int64_t n4 = n / 4;
+    const cvae_guard_record* rec = &reinterpret_cast<const GuardState*>(state)->rec;
+    if (o.ema) hipLaunchKernelGGL(adam_guarded_opt_kernel<true>, dim3(opt_blocks(n4)), dim3(256), 0, st, p, g, m, v, n4, eps, rec, o);
+    else hipLaunchKernelGGL(adam_guarded_opt_kernel<false>, dim3(opt_blocks(n4)), dim3(256), 0, st, p, g, m, v, n4, eps, rec, o);
     CVAE_CHECK_LAUNCH();
     return 0;
 }

@@ -753,6 +753,47 @@ int cvae_adam_step_guarded(cvae_handle h, float* params, const float* grads, flo
     return launch_adam_guarded(params, grads, exp_avg, exp_avg_sq, n, eps, state, (hipStream_t)stream);
 }
 
+// the checks the two _opt entries share (include/cvae.h); `who` names the entry in the message.  Host values only.
+static int opt_check(const char* who, int64_t n, const cvae_opt_args* opt, const float* ema, const float* aux, const float* aux_ema,
+                     int32_t n_aux) {
+    if (!opt) { cvae_set_error("%s: opt is null", who); return CVAE_EINVAL; }
+    if (n < 0 || n % 4 != 0) { cvae_set_error("%s: n = %lld must be a non-negative multiple of 4", who, (long long)n); return CVAE_EINVAL; }
+    if (opt->n_ranges < 0 || opt->n_ranges > CVAE_OPT_MAX_RANGES) {
+        cvae_set_error("%s: n_ranges = %d outside 0..%d", who, (int)opt->n_ranges, CVAE_OPT_MAX_RANGES); return CVAE_EINVAL;
+    }
+    int64_t prev = 0;
+    for (int k = 0; k < opt->n_ranges; ++k) {
+        const int64_t b = opt->begin[k], e = opt->end[k];
+        if (b >= e || b < prev || e > n) {
+            cvae_set_error("%s: range %d = [%lld, %lld): ranges must be non-empty, ascending, disjoint and within [0, n = %lld)", who, k,
+                           (long long)b, (long long)e, (long long)n);
+            return CVAE_EINVAL;
+        }
+        prev = e;
+    }
+    if (!(opt->decay_mul > 0.f && opt->decay_mul <= 1.f)) { cvae_set_error("%s: decay_mul = %g outside (0, 1]", who, (double)opt->decay_mul); return CVAE_EINVAL; }
+    if (ema && !(opt->ema_omd >= 0.f && opt->ema_omd <= 1.f)) { cvae_set_error("%s: ema_omd = %g outside [0, 1]", who, (double)opt->ema_omd); return CVAE_EINVAL; }
+    if (n_aux < 0 || n_aux > 4096) { cvae_set_error("%s: n_aux = %d outside 0..4096", who, (int)n_aux); return CVAE_EINVAL; }
+    if (n_aux > 0 && (!aux || !aux_ema)) { cvae_set_error("%s: n_aux = %d with a null aux or aux_ema", who, (int)n_aux); return CVAE_EINVAL; }
+    if ((n_aux > 0 || aux_ema) && !ema) { cvae_set_error("%s: aux_ema without ema", who); return CVAE_EINVAL; }
+    return CVAE_OK;
+}
+int cvae_adam_step_opt(cvae_handle h, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                       int32_t step, float lr, float beta1, float beta2, float eps, float grad_scale, const cvae_opt_args* opt,
+                       float* ema, float* aux, float* aux_ema, int32_t n_aux, void* stream) {
+    if (!h || !params || !grads || !exp_avg || !exp_avg_sq || step < 1) { cvae_set_error("cvae_adam_step_opt: bad handle, null pointer or step < 1"); return CVAE_EINVAL; }
+    RC(opt_check("cvae_adam_step_opt", n, opt, ema, aux, aux_ema, n_aux));
+    return launch_adam_opt(params, grads, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, grad_scale, opt, ema, aux, aux_ema, n_aux,
+                           (hipStream_t)stream);
+}
+int cvae_adam_step_guarded_opt(cvae_handle h, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                               float eps, const void* state, const cvae_opt_args* opt, float* ema, float* aux, float* aux_ema,
+                               int32_t n_aux, void* stream) {
+    if (!h || !params || !grads || !exp_avg || !exp_avg_sq || !state) { cvae_set_error("cvae_adam_step_guarded_opt: bad handle or null pointer"); return CVAE_EINVAL; }
+    RC(opt_check("cvae_adam_step_guarded_opt", n, opt, ema, aux, aux_ema, n_aux));
+    return launch_adam_guarded_opt(params, grads, exp_avg, exp_avg_sq, n, eps, state, opt, ema, aux, aux_ema, n_aux, (hipStream_t)stream);
+}
+
 int cvae_grads_to_bf16(cvae_handle h, const float* grads, void* out_bf16, int64_t n, void* stream) {
     if (h && n == 0) return 0;                       // empty range (its pointers may be null): nothing to do
     if (!h || !grads || !out_bf16 || n < 0) { cvae_set_error("cvae_grads_to_bf16: bad argument"); return CVAE_EINVAL; }

@@ -434,6 +434,12 @@ int launch_guard_init(void* state, int64_t applied, int64_t skipped, hipStream_t
 int launch_grad_stats(const float* g, int64_t n, float gscale, float max_norm, int skip_nonfinite, float lr, float b1, float b2,
                       void* state, hipStream_t st);
 int launch_adam_guarded(float* p, const float* g, float* m, float* v, int64_t n, float eps, const void* state, hipStream_t st);
+// the optimizer options (cvae_opt_args, include/cvae.h): arguments already checked by the caller
+struct cvae_opt_args;
+int launch_adam_opt(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps,
+                    float gscale, const cvae_opt_args* opt, float* ema, const float* aux, float* aux_ema, int32_t n_aux, hipStream_t st);
+int launch_adam_guarded_opt(float* p, const float* g, float* m, float* v, int64_t n, float eps, const void* state,
+                            const cvae_opt_args* opt, float* ema, const float* aux, float* aux_ema, int32_t n_aux, hipStream_t st);
 int launch_zero(float* p, int64_t n, hipStream_t st);
 struct PadGaps { int64_t off[32]; int len[32]; int n; };
 int launch_zero_gaps(float* grads, const PadGaps& gaps, hipStream_t st);

@@ -8,10 +8,13 @@ import numpy as np
 import torch
 
 from .augment import Augment
+from .optim import Optim
 
 
 class DeviceTrainer:
-    def _init_shared(self, skip_nonfinite, max_grad_norm):
+    def _init_shared(self, skip_nonfinite, max_grad_norm, optim=None):
+        if optim is not None and not isinstance(optim, Optim):
+            raise ValueError(f"optim {optim!r}: an optim.Optim or None")
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError(f"max_grad_norm {max_grad_norm!r}: a positive number (inf = no clipping) or None")
         self.skip_nonfinite = bool(skip_nonfinite)
@@ -24,6 +27,10 @@ class DeviceTrainer:
         self.best_val = None              # the lowest finite validation loss seen (the CLI's --keep-best / --patience)
         self.val_stale = 0                # evaluations in a row since it last improved
         self.augment = None               # an augment.Augment: fit_device gathers through the augmented kernels (_init_augment)
+        self.optim = optim                # an optim.Optim: _update launches the _opt kernels under optim.args_at(step)
+        self.decay_ranges = []            # the element ranges weight decay touches (optim.decay_ranges of the subclass's layout)
+        self.ema = None                   # the averaged parameters and the averaged auxiliary buffer (the VAE's bn_state) of an
+        self.aux_ema = None               # Optim with an EMA: created by the first such _update, or by load_state_dict
 
     def _init_augment(self, augment, width):
         """The constructor's `augment` argument: None, or an Augment whose shift fits frames of `width`."""
@@ -41,10 +48,74 @@ class DeviceTrainer:
                              "clamped at 1 has no meaning for them; use brightness=0")
 
     # ---- the optimizer launches ----
+    def _opt_aux(self):
+        """The small buffer whose EMA rides in the Adam launch (FusedTrainer: the BatchNorm running statistics); None: none."""
+        return None
+
+    def has_ema(self):
+        optim = getattr(self, "optim", None)
+        return optim is not None and optim.ema is not None
+
+    def _ema_buffers(self, theta):
+        """(ema, aux_ema) of a trainer whose Optim has an EMA, created on first use as copies of `theta` and of the auxiliary
+        buffer as they stand — unless load_state_dict / sync_replicas supplied them.  So a load_networks after construction is
+        safe: nothing was copied at construction."""
+        if self.ema is None:
+            self.ema = theta.detach().clone()
+        aux = self._opt_aux()
+        if aux is not None and self.aux_ema is None:
+            self.aux_ema = aux.detach().clone()
+        return self.ema, self.aux_ema
+
+    def _ema_view(self, theta):
+        """(ema, aux_ema) for a READER (evaluate(ema=True), the save paths): the trainer's own buffers where they exist,
+        else temporaries — copies of `theta` / the auxiliary buffer that are NOT kept, so that only the first update (or a loaded
+        state) ever creates the averages and a load_networks after an early evaluation cannot leave them stale."""
+        aux = self._opt_aux()
+        ema = self.ema if self.ema is not None else theta.detach().clone()
+        aux_ema = self.aux_ema if (self.aux_ema is not None or aux is None) else aux.detach().clone()
+        return ema, aux_ema
+
+    def _sync_ema(self, theta, src):
+        """sync_replicas with an EMA: rank `src`'s averages reach every rank — or, where it has none yet, every rank drops
+        its own, so that all of them start theirs from the (already broadcast) parameters at the next step.  Two or three
+        collectives more, only for a trainer whose Optim has an EMA."""
+        dist = torch.distributed
+        flag = torch.tensor([0 if self.ema is None else 1], dtype=torch.int64, device=self.m.device)
+        dist.broadcast(flag, src=src, group=self.pg)
+        if int(flag.item()) == 0:
+            self.ema, self.aux_ema = None, None
+            return
+        for t in self._ema_buffers(theta):
+            if t is not None:
+                dist.broadcast(t, src=src, group=self.pg)
+
+    def _update_opt(self, theta, grad_scale):
+        """_update under an Optim: the same launch count, the _opt kernels in place of the plain ones.  The schedule and the EMA
+        warm-up count calls of step() (step_count is already this step's 1-based number); the guarded bias correction stays the
+        device's count of applied steps."""
+        h, optim = self.h, self.optim
+        a = optim.args_at(self.step_count - 1, self.lr, self.decay_ranges)
+        ema, aux, aux_ema = None, None, None
+        if optim.ema is not None:
+            ema, aux_ema = self._ema_buffers(theta)
+            aux = self._opt_aux()
+        if not self.guarded:
+            h.adam_step_opt(theta, self.grads, self.m, self.v, self.step_count, a["lr"], self.betas[0], self.betas[1], self.eps,
+                            grad_scale=grad_scale, opt=a, ema=ema, aux=aux, aux_ema=aux_ema)
+            return
+        if self.guard is None:
+            self.guard = h.guard_state(self.m.device, *self._guard_counts)
+        h.grad_stats(self.grads, self.guard, grad_scale, float("inf") if self.max_grad_norm is None else self.max_grad_norm,
+                     self.skip_nonfinite, a["lr"], self.betas[0], self.betas[1])
+        h.adam_step_guarded_opt(theta, self.grads, self.m, self.v, self.guard, self.eps, opt=a, ema=ema, aux=aux, aux_ema=aux_ema)
+
     def _update(self, theta, grad_scale):
         """cvae_adam_step, or the guarded pair: statistics of the reduced gradient -> decision record -> the Adam launch that
-        obeys it; nothing comes back to the host."""
+        obeys it; nothing comes back to the host.  With an Optim: _update_opt."""
         h = self.h
+        if getattr(self, "optim", None) is not None:
+            return self._update_opt(theta, grad_scale)
         if not self.guarded:
             h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
                         grad_scale=grad_scale)
@@ -90,6 +161,11 @@ class DeviceTrainer:
                  "best_val": self.best_val, "val_stale": int(self.val_stale)}
         if getattr(self, "augment", None) is not None:      # absent without one; draw = step_count: a resumed run continues exactly
             state["augment"] = self.augment.state_dict()
+        if getattr(self, "optim", None) is not None:        # absent without one; the EMA tensors once they exist
+            state["optim"] = self.optim.state_dict()
+            for key in ("ema", "aux_ema"):
+                if getattr(self, key) is not None:
+                    state[key] = getattr(self, key).detach().cpu().clone()
         return state
 
     def _load_shared_state(self, state):
@@ -97,6 +173,15 @@ class DeviceTrainer:
         applied, skipped, steps = int(state["applied"]), int(state["skipped"]), int(state["step_count"])
         saved = state.get("augment")
         restored = None if saved is None else Augment.from_state_dict(saved).check_width(self.h.width)
+        saved_optim = state.get("optim")
+        optim = None if saved_optim is None else Optim.from_state_dict(saved_optim)
+        ema, aux_ema = (state.get("ema"), state.get("aux_ema")) if optim is not None else (None, None)
+        if ema is not None and ema.numel() != self.m.numel():
+            raise ValueError(f"the state's averaged weights hold {ema.numel()} floats, this trainer has {self.m.numel()}")
+        aux = self._opt_aux()
+        if aux_ema is not None and (aux is None or aux_ema.numel() != aux.numel()):
+            raise ValueError(f"the state's averaged auxiliary buffer holds {aux_ema.numel()} floats, this trainer's "
+                             f"{0 if aux is None else aux.numel()}")
         if not self.guarded and applied != steps:
             raise ValueError(f"the state skipped {skipped} of {steps} steps: an unguarded trainer corrects Adam's bias by step_count "
                              "and cannot continue it; construct the trainer with skip_nonfinite=True")
@@ -106,13 +191,24 @@ class DeviceTrainer:
         self.val_stale = int(state.get("val_stale", 0))
         if restored is not None:           # a state without one keeps what the trainer was built with
             self.augment = restored
+        if optim is not None:              # likewise; averaged tensors the state does not carry are created by the next _update
+            self.optim = optim
+            self.ema = None if ema is None else ema.to(device=self.m.device, dtype=torch.float32).clone()
+            self.aux_ema = None if aux_ema is None else aux_ema.to(device=self.m.device, dtype=torch.float32).clone()
         if self.guarded:
             self._guard_write(applied, skipped)
 
     # ---- the loop of fit_device ----
     def _validate(self, val, batch_size, on_val):
-        """One evaluation inside fit_device: history entry, callback; True = the callback asked to stop."""
-        result = self.evaluate(val, batch_size)
+        """One evaluation inside fit_device: history entry, callback; True = the callback asked to stop.  A trainer with an
+        Optim evaluates its averaged weights when it keeps an EMA, and its result says which weights were judged: "weights":
+        "ema" or "live".  A trainer WITHOUT an Optim gets the call and the result dict it always got — no "weights" key — so
+        that results and saved histories of runs without the option stay what they were."""
+        if getattr(self, "optim", None) is None:
+            result = self.evaluate(val, batch_size)
+        else:                              # the averaged weights are what gets shipped: they are the ones judged
+            result = self.evaluate(val, batch_size, ema=True) if self.has_ema() else self.evaluate(val, batch_size)
+            result["weights"] = "ema" if self.has_ema() else "live"
         self.val_history.append((int(self.step_count), result))
         return bool(on_val(self, result)) if on_val is not None else False
 

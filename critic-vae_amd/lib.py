@@ -48,6 +48,26 @@ class Objective(C.Structure):
 
 
 MSGRAD_REFERENCE, MSGRAD_USED = 0, 1
+OPT_MAX_RANGES = 16       # CVAE_OPT_MAX_RANGES
+OPT_MAX_AUX = 4096
+
+
+class OptArgs(C.Structure):
+    """cvae_opt_args (include/cvae.h): weight-decay factor, EMA rate and the decayed element ranges of one optimizer step."""
+    _fields_ = [("decay_mul", C.c_float), ("ema_omd", C.c_float), ("n_ranges", C.c_int32), ("reserved", C.c_int32),
+                ("begin", C.c_int64 * OPT_MAX_RANGES), ("end", C.c_int64 * OPT_MAX_RANGES)]
+
+
+def opt_args(decay_mul=1.0, ema_omd=0.0, ranges=()):
+    """An OptArgs from host values; more than OPT_MAX_RANGES ranges raise here (the table has no room for them), every other
+    check is the library's."""
+    ranges = list(ranges)
+    if len(ranges) > OPT_MAX_RANGES:
+        raise ValueError(f"{len(ranges)} decayed ranges: at most {OPT_MAX_RANGES}")
+    a = OptArgs(float(decay_mul), float(ema_omd), len(ranges), 0)
+    for k, (b, e) in enumerate(ranges):
+        a.begin[k], a.end[k] = int(b), int(e)
+    return a
 
 
 class AugmentParams(C.Structure):
@@ -118,6 +138,8 @@ _SIGS = {
     "cvae_guard_init": (C.c_int, [_p, _p, _i64, _i64, _p]),
     "cvae_grad_stats": (C.c_int, [_p, _p, _i64, _f, _f, _i32, _f, _f, _f, _p, _p]),
     "cvae_adam_step_guarded": (C.c_int, [_p, _p, _p, _p, _p, _i64, _f, _p, _p]),
+    "cvae_adam_step_opt": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _f, _f, _f, _f, _f, C.POINTER(OptArgs), _p, _p, _p, _i32, _p]),
+    "cvae_adam_step_guarded_opt": (C.c_int, [_p, _p, _p, _p, _p, _i64, _f, _p, C.POINTER(OptArgs), _p, _p, _p, _i32, _p]),
     "cvae_grads_to_bf16": (C.c_int, [_p, _p, _p, _i64, _p]),
     "cvae_grads_from_bf16": (C.c_int, [_p, _p, _p, _i64, _p]),
     "cvae_critic_param_count": (_i32, []),
@@ -432,6 +454,34 @@ class Handle:
     def adam_step_guarded(self, params, grads, m, v, state, eps=1e-8, n=None):
         self._check(self.lib.cvae_adam_step_guarded(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v),
                                                     params.numel() if n is None else n, eps, self._guard_ptr(state), _stream()))
+
+    # ---- the optimizer options (include/cvae.h): weight decay on element ranges and the EMA buffers, in the Adam launch ----
+    @staticmethod
+    def _opt(opt):
+        """An OptArgs, a dict(decay_mul, ema_omd, ranges) as optim.Optim.args_at returns it, or None (a null pointer)."""
+        if opt is None or isinstance(opt, OptArgs):
+            return opt
+        return opt_args(opt.get("decay_mul", 1.0), opt.get("ema_omd", 0.0), opt.get("ranges", ()))
+
+    def adam_step_opt(self, params, grads, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0, opt=None, ema=None,
+                      aux=None, aux_ema=None, n_aux=None, n=None):
+        """cvae_adam_step with the options `opt`; ema / aux / aux_ema: fp32 device tensors or None."""
+        opt = self._opt(opt)
+        n_aux = (0 if aux is None else aux.numel()) if n_aux is None else n_aux
+        self._check(self.lib.cvae_adam_step_opt(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v),
+                                                params.numel() if n is None else n, step, lr, b1, b2, eps, grad_scale,
+                                                None if opt is None else C.byref(opt), _ptr(ema), _ptr(aux), _ptr(aux_ema),
+                                                n_aux, _stream()))
+
+    def adam_step_guarded_opt(self, params, grads, m, v, state, eps=1e-8, opt=None, ema=None, aux=None, aux_ema=None,
+                              n_aux=None, n=None):
+        """cvae_adam_step_guarded with the options `opt`; the record of `state` decides, as there."""
+        opt = self._opt(opt)
+        n_aux = (0 if aux is None else aux.numel()) if n_aux is None else n_aux
+        self._check(self.lib.cvae_adam_step_guarded_opt(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v),
+                                                        params.numel() if n is None else n, eps, self._guard_ptr(state),
+                                                        None if opt is None else C.byref(opt), _ptr(ema), _ptr(aux),
+                                                        _ptr(aux_ema), n_aux, _stream()))
 
     @staticmethod
     def guard_record(state):

@@ -35,6 +35,7 @@ from .lib import N_SCALARS, SCORE_COLS, SYNC_DOUBLES, SYNC_POINTS
 from .nets import VariationalAutoencoder
 from .augment import Augment
 from .objective import Objective, compose
+from .optim import Optim, decay_ranges
 
 
 def _reference_batches(dset, epoch_indices, starts, batch_size, device, critic_fn):
@@ -89,7 +90,7 @@ class FusedTrainer(DeviceTrainer):
 
     def __init__(self, vae, lr=P.lr, betas=P.adam_betas, eps=P.adam_eps, process_group=None, world_size=1,
                  overlap=None, reduce_dtype=None, sync=True, global_stats=None, skip_nonfinite=False, max_grad_norm=None,
-                 objective=None, augment=None):
+                 objective=None, augment=None, optim=None):
         """Construction with world_size > 1 is a COLLECTIVE (sync_replicas: five broadcasts from rank 0) unless
         sync=False.
         overlap: all-reduce the gradient in three buckets while backward still runs (default for
@@ -122,7 +123,16 @@ class FusedTrainer(DeviceTrainer):
         fit_u8 (the host feeder) refuses.  A shift above width / 4 raises here; a ReconDataset with brightness > 0 raises in
         fit_device before the first launch.  Saved and restored with the trainer: the draw is step_count, so a resumed run
         applies exactly the transforms of the uninterrupted one.  With world_size > 1 every rank uses the same key on its
-        own dataset indices; no collective is added."""
+        own dataset indices; no collective is added.
+        optim: an optim.Optim, or None = cvae_adam_step (or the guarded pair) at the constant `lr`, with the launches and bits the
+        step always had.  Otherwise the step ends in cvae_adam_step_opt (cvae_grad_stats + cvae_adam_step_guarded_opt when
+        guarded) — still one Adam launch — under optim.args_at(step): `lr` becomes the schedule's peak, weight decay (AdamW's
+        decoupled form) touches the eleven weight tensors (optim.decay_ranges: no bias, no BatchNorm gamma / beta), and with
+        optim.ema the launch also maintains `ema` (the averaged theta) and `aux_ema` (the averaged bn_state, which forward of
+        the same step has already written).  Both are created by the first such step as copies of theta / bn_state, so
+        load_networks after construction is safe.  evaluate(..., ema=True) runs on them, fit_device(val=...) judges them, and
+        state_dict carries them with the Optim: a run resumed in the middle of a schedule continues exactly.  Works with
+        global_stats and reduce_dtype="bf16" (the update is downstream of both); sync_replicas also broadcasts the averages."""
         self.vae = vae
         self.h = vae.handle
         if overlap is None:
@@ -145,8 +155,11 @@ class FusedTrainer(DeviceTrainer):
         self.objective = objective
         self.buckets = [self.h.grad_bucket(ph) for ph in range(3)]
         self.lr, self.betas, self.eps = lr, betas, eps
-        self._init_shared(skip_nonfinite, max_grad_norm)      # guard fields, step_count, val_history / best_val / val_stale
+        self._init_shared(skip_nonfinite, max_grad_norm, optim)      # guard fields, step_count, val_history / best_val / val_stale, optim
         self._init_augment(augment, vae.width)
+        if self.optim is not None:
+            self.optim.check_lr(self.lr)      # an lr_min above the peak raises here, not after the warm-up
+        self.decay_ranges = decay_ranges(self.h.layout)
         self.world_size, self.pg = world_size, process_group
         dev = vae.theta.device
         n = vae.theta.numel()
@@ -191,6 +204,11 @@ class FusedTrainer(DeviceTrainer):
         self.step_count, self.vae.num_batches_tracked = meta[0], meta[1]
         if self.guarded:
             self._guard_write(meta[2], meta[3])
+        if self.has_ema():
+            self._sync_ema(self.vae.theta.data, src)
+
+    def _opt_aux(self):
+        return self.vae.bn_state
 
     def step(self, x, pred, eps):
         """x (B,3,w,w), pred (B,1), eps (B,32): contiguous fp32 device tensors."""
@@ -345,7 +363,7 @@ class FusedTrainer(DeviceTrainer):
             raise ValueError(f"the dataset is on {dataset.frames.device}, the VAE on {dev}")
         return dev, int(batch_size)
 
-    def evaluate(self, dataset, batch_size, per_image=False):
+    def evaluate(self, dataset, batch_size, per_image=False, ema=False):
         """The model on a held-out DeviceDataset / ReconDataset: per batch one gather launch, the EVAL-mode forward (BatchNorm
         on its running statistics, z = mu, i.e. eps = 0, the entries' own critic values) and cvae_score into ONE pooled device
         record; the host reads once, at the end.  Returns a dict of host values:
@@ -365,7 +383,9 @@ class FusedTrainer(DeviceTrainer):
         Draws nothing from any random generator and leaves parameters, Adam state, bn_state, num_batches_tracked, step_count
         and the guard record untouched; it overwrites the workspace and the trainer's mu / logvar / recon buffers, which a
         step() rewrites before reading.  With world_size > 1 every rank evaluates the dataset IT is given and no collective
-        runs: give every rank the same set (identical results on identical replicas) or reduce the per-rank results yourself."""
+        runs: give every rank the same set (identical results on identical replicas) or reduce the per-rank results yourself.
+        ema=True (a trainer whose Optim has an EMA): the same loop on the averaged weights and the averaged BatchNorm statistics
+        (`ema`, `aux_ema`; before the first step temporaries, copies of theta and bn_state that are not kept).  Only the two pointers differ."""
         dev, B = self._check_dataset(dataset, batch_size)
         v, h, n = self.vae, self.h, len(dataset)
         if n < 1:
@@ -376,12 +396,16 @@ class FusedTrainer(DeviceTrainer):
         rows = torch.empty(n, SCORE_COLS, device=dev) if per_image else None
         state = h.score_state(dev)
         d_idx = torch.arange(n, dtype=torch.int64, device=dev)
-        theta = v.theta.data
+        theta, bn_state = v.theta.data, v.bn_state
+        if ema:
+            if not self.has_ema():
+                raise ValueError("evaluate(ema=True): this trainer keeps no averaged weights (optim=Optim(ema=...))")
+            theta, bn_state = self._ema_view(theta)
         v._stamp_workspace()
         for b in range(0, n, B):
             nb = min(B, n - b)
             dataset.gather(h, nb, d_idx[b:b + nb], x[:nb], pred[:nb])
-            h.forward(nb, x[:nb], pred[:nb], zero[:nb], theta, v.bn_state, self.mu, self.logvar, self.recon, self.ws, train=False)
+            h.forward(nb, x[:nb], pred[:nb], zero[:nb], theta, bn_state, self.mu, self.logvar, self.recon, self.ws, train=False)
             h.score(nb, x[:nb], self.mu, self.logvar, self.recon, self.ws, None if rows is None else rows[b:b + nb], state)
         scal = torch.empty(N_SCALARS, device=dev)
         h.score_finish(state, scal)
@@ -484,6 +508,23 @@ def load_networks(vae, directory, device=None, second=False):
     return vae
 
 
+def save_ema_networks(trainer, directory, second=False):
+    """The network files of a FusedTrainer's AVERAGED weights and BatchNorm statistics (the CLI's DIR/ema/), in save_networks'
+    format: load_networks / --networks DIR/ema of every mode loads them.  The live parameters are swapped out for the time of
+    the save and put back; nothing of the trainer changes."""
+    vae = trainer.vae
+    ema, aux_ema = trainer._ema_view(vae.theta.data)
+    live_theta, live_bn = vae.theta.data.clone(), vae.bn_state.clone()
+    try:
+        vae.theta.data.copy_(ema)
+        vae.bn_state.copy_(aux_ema)
+        save_networks(vae, directory, second=second)
+    finally:
+        vae.theta.data.copy_(live_theta)
+        vae.bn_state.copy_(live_bn)
+    return directory
+
+
 TRAINER_FILE = "trainer.pt"
 
 
@@ -580,7 +621,72 @@ def build_parser():
     ap.add_argument("--augment-brightness", type=float, default=None, metavar="B", help="gain within 1 +- B on uint8 frames, "
                     "clamped at 1 (not -second: its entries are Tanh outputs)")
     ap.add_argument("--augment-seed", type=int, default=None, metavar="N", help="seed of the per-sample hash (default 0)")
+    ap.add_argument("--lr-schedule", choices=("constant", "linear", "cosine"), default=None, help="-train --episodes, -second, "
+                    "-critic: the learning rate after the warm-up, with the run's lr as the peak.  Any of these seven flags moves the "
+                    "Adam launch to its _opt kernel (optim.py): schedule, weight decay and EMA ride in that one launch")
+    ap.add_argument("--lr-warmup", type=int, default=None, metavar="N", help="lr * (step + 1) / N over the first N optimizer steps")
+    ap.add_argument("--lr-min", type=float, default=None, metavar="F", help="where the linear / cosine schedule ends (default 0)")
+    ap.add_argument("--lr-total", type=int, default=None, metavar="N", help="the step at which it gets there (default: epochs * "
+                    "ceil(training entries / batch), the whole run)")
+    ap.add_argument("--weight-decay", type=float, default=None, metavar="W", help="decoupled weight decay (torch.optim.AdamW) on the "
+                    "weight tensors; biases and BatchNorm gamma / beta are left alone")
+    ap.add_argument("--ema", type=float, default=None, metavar="D", help="keep an exponential moving average of the weights (and of "
+                    "the BatchNorm statistics) with decay D; validation judges it, --save DIR also writes DIR/ema/")
+    ap.add_argument("--ema-warmup", action="store_true", help="with --ema: decay min(D, (1 + step) / (10 + step))")
     return ap
+
+
+OPTIM_FLAGS = "--lr-schedule, --lr-warmup, --lr-min, --lr-total, --weight-decay, --ema and --ema-warmup"
+EMA_DIR = "ema"
+
+
+def optim_kwargs_from_args(args):
+    """The Optim arguments the seven optimizer flags give, or None when none of them is given (the plain Adam launch).  `total`
+    may be missing: optim_from_kwargs fills in the length of the run once the training set is known."""
+    given = {"schedule": args.lr_schedule, "warmup": args.lr_warmup, "lr_min": args.lr_min, "total": args.lr_total,
+             "weight_decay": args.weight_decay, "ema": args.ema, "ema_warmup": True if args.ema_warmup else None}
+    given = {k: v for k, v in given.items() if v is not None}
+    return given or None
+
+
+def optim_from_kwargs(kw, default_total):
+    """Optim(**kw) with --lr-total's default for a decaying schedule; None stays None.  Raises ValueError as Optim does."""
+    if kw is None:
+        return None
+    if "total" not in kw and kw.get("schedule", "constant") != "constant":
+        kw = dict(kw, total=int(default_total))
+    return Optim(**kw)
+
+
+def _run_steps(args, n_entries):
+    return args.epochs * ((n_entries + args.batch - 1) // args.batch)
+
+
+def _settle_optim(args, trainer, provisional, n_entries, directory):
+    """After the training set is known: the Optim of the flags with its final `total`, installed in a fresh run; in a resumed
+    one the checkpoint's Optim continues, and flags that describe another one are refused (the rule of the objective)."""
+    try:
+        given = optim_from_kwargs(getattr(args, "optim_kw", None), _run_steps(args, n_entries))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    saved = trainer.optim if (directory and trainer.optim is not provisional) else None
+    try:                                   # an lr_min above the run's lr: an argument error now, not a ValueError after the warm-up
+        for o in (given, saved):
+            if o is not None:
+                o.check_lr(trainer.lr)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if not directory:
+        trainer.optim = given
+    elif given is None:
+        if saved is not None:
+            print(f"continuing with the optimizer options saved in {directory}")
+    elif saved is None or saved != given:
+        was = "none (the plain Adam launch at a constant lr)" if saved is None else repr(saved)
+        raise SystemExit(f"--resume {directory}: the checkpoint's optimizer options are {was}, the flags give {given!r}.  A resumed "
+                         "run keeps its schedule, weight decay and EMA: drop the optimizer flags, or repeat the run's own")
+    if trainer.optim is not None:
+        print(trainer.optim.describe())
 
 
 def augment_from_args(args):
@@ -626,6 +732,14 @@ def main(argv=None):
                      "meaning for them")
     if args.max_grad_norm is not None and not args.max_grad_norm > 0:
         ap.error("--max-grad-norm needs a positive number")
+    args.optim_kw = optim_kwargs_from_args(args)
+    if args.optim_kw is not None:
+        if not ((args.train and args.episodes is not None) or args.second or (args.critic_mode and not args.eval_only)):
+            ap.error(f"{OPTIM_FLAGS} belong to the fused trainers: -train --episodes, -second and -critic")
+        try:
+            optim_from_kwargs(args.optim_kw, args.optim_kw.get("warmup", 0) + 1)
+        except ValueError as e:
+            ap.error(str(e))
     if args.val_fraction is None:
         if args.val_every is not None or args.keep_best or args.patience is not None:
             ap.error("--val-every, --keep-best and --patience need --val-fraction")
@@ -713,8 +827,10 @@ def _fit_and_save(args, vae, ds, second):
     line, save_networks.  Nothing before it draws from the global generators (the networks are built from args.seed)."""
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
+    kw = getattr(args, "optim_kw", None)
+    provisional = optim_from_kwargs(kw, (kw or {}).get("warmup", 0) + 1)      # --lr-total's default needs the training set: _settle_optim
     trainer = FusedTrainer(vae, skip_nonfinite=args.skip_nonfinite, max_grad_norm=args.max_grad_norm,
-                           objective=getattr(args, "objective", None), augment=getattr(args, "augment", None))
+                           objective=getattr(args, "objective", None), augment=getattr(args, "augment", None), optim=provisional)
     if args.resume:
         given, given_aug = trainer.objective, trainer.augment
         load_networks(vae, args.resume, second=second)
@@ -729,6 +845,7 @@ def _fit_and_save(args, vae, ds, second):
     gen = torch.Generator(device=vae.theta.device)
     gen.manual_seed(args.seed)
     ds, val_kw = _hold_out(args, ds, _ValidationLog(args, second, by_objective=trainer.objective is not None), "entries", curated=True)
+    _settle_optim(args, trainer, provisional, len(ds), args.resume)
     t0 = time.time()
     scal = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen, **val_kw)
     torch.cuda.synchronize()
@@ -740,6 +857,8 @@ def _fit_and_save(args, vae, ds, second):
         enc, dec = save_networks(vae, args.save, second=second)
         print(f"saved {enc} and {dec}")
         print(f"saved {save_trainer(trainer, os.path.join(args.save, TRAINER_FILE))}")
+        if trainer.has_ema():
+            print(f"saved the averaged weights under {save_ema_networks(trainer, os.path.join(args.save, EMA_DIR), second=second)}")
     _print_guard(trainer)
     return ds
 
@@ -776,6 +895,12 @@ def _check_resumed_augment(given, trainer, directory):
 
 
 BEST_DIR = "best"
+
+
+def _has_ema(trainer):
+    """Whether --keep-best saves averaged weights; a stand-in trainer without the method has none."""
+    has = getattr(trainer, "has_ema", None)
+    return bool(has()) if callable(has) else False
 
 
 def _hold_out(args, ds, on_val, noun, curated):
@@ -837,8 +962,11 @@ class _ValidationLog(_KeepBestLog):
                 f"{r['images'] - r['finite_images']} non-finite; per image: mean {r['mean_total']:.6f} worst {r['worst']:.6f} "
                 f"psnr {r['psnr']:.2f} dB")
 
-    def save(self, trainer, directory):
-        save_networks(trainer.vae, directory, second=self.second)
+    def save(self, trainer, directory):                  # the weights that were judged: the averaged ones of a trainer with an EMA
+        if _has_ema(trainer):
+            save_ema_networks(trainer, directory, second=self.second)
+        else:
+            save_networks(trainer.vae, directory, second=self.second)
 
 
 def _load_critic(spec, handle, seed, device):
@@ -878,15 +1006,22 @@ class _CriticValidationLog(_KeepBestLog):
                 f"pearson {r['pearson']:.4f} bin agreement {r['bin_agreement']:.4f} worst {r['worst']:.4f} over {r['frames']} frames, "
                 f"{r['frames'] - r['finite_frames']} non-finite")
 
-    def save(self, trainer, directory):
-        print(f"saved {_save_critic(trainer.critic, directory)}")
+    def save(self, trainer, directory):                  # likewise
+        print(f"saved {_save_critic(trainer.critic, directory, ema=trainer if _has_ema(trainer) else None)}")
 
 
-def _save_critic(critic, directory):
-    """DIR/critic.pt in the reference's checkpoint format (what --critic of every mode loads)."""
+def _save_critic(critic, directory, ema=None):
+    """DIR/critic.pt in the reference's checkpoint format (what --critic of every mode loads).  ema: a CriticTrainer with
+    averaged weights — the file then holds those, cut up by the keys and shapes of the critic's own state_dict."""
     os.makedirs(directory, exist_ok=True)
     path = os.path.join(directory, CRITIC_FILE)
-    torch.save({k: v.detach().cpu() for k, v in critic.state_dict().items()}, path)
+    sd = critic.state_dict()
+    if ema is not None:
+        flat, off = ema._ema_view(ema.theta)[0], 0
+        for k, v in sd.items():
+            sd[k] = flat[off:off + v.numel()].reshape(v.shape).clone()
+            off += v.numel()
+    torch.save({k: v.detach().cpu() for k, v in sd.items()}, path)
     return path
 
 
@@ -925,6 +1060,7 @@ def _train_critic(args):
     gen = torch.Generator(device=device)
     gen.manual_seed(args.seed)
     ds, val_kw = _hold_out(args, ds, _CriticValidationLog(args), "frames", curated=False)
+    _settle_optim(args, trainer, None, len(ds), None)
     t0 = time.time()
     log = trainer.fit_device(ds, args.batch, epochs=args.epochs, generator=gen, **val_kw)
     torch.cuda.synchronize()
@@ -937,6 +1073,8 @@ def _train_critic(args):
     print(f"{images / dt:.1f} images/s over {span} of {len(ds)} frames; {args.loss} loss "
           f"{s[:per_epoch, 0].mean():.6f} (first epoch) -> {s[-per_epoch:, 0].mean():.6f} (last)")
     print(f"saved {_save_critic(critic, args.save)}")
+    if trainer.has_ema():
+        print(f"saved {_save_critic(critic, os.path.join(args.save, EMA_DIR), ema=trainer)}")
     _print_guard(trainer)
     return critic
 

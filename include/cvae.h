@@ -335,6 +335,49 @@ int cvae_adam_step_guarded(cvae_handle h, float* params, const float* grads, flo
                            float eps, const void* state, void* stream);
 
 /*
+ * Optimizer options (opt-in): decoupled weight decay (torch.optim.AdamW), an exponential moving average of the parameters and
+ * of one small auxiliary buffer, all inside the ONE launch of the Adam pass.  cvae_adam_step_opt is cvae_adam_step with them,
+ * cvae_adam_step_guarded_opt is cvae_adam_step_guarded with them; the two plain entries keep their kernels and bits.  A learning-rate
+ * schedule needs no entry of its own: lr (cvae_adam_step_opt, cvae_grad_stats) is an argument of every step.
+ *
+ * Weight decay: for every element inside one of the decayed ranges, p = p * decay_mul comes first — ONE fp32 product, rounded
+ * on its own as torch's param.mul_(1 - lr * weight_decay) is, never contracted into the update — and cvae_adam_step's arithmetic
+ * then runs on that p.  Elements outside every range skip the product.  Ranges are in ELEMENTS [begin, end), ascending and
+ * disjoint; they need not respect the float4s the kernel moves (the critic's block of cvae_critic_grad has its tensor boundaries
+ * anywhere).  The table travels by value in the launch; lane l of a wave holds slot l % 16, so a wave tests its 256-element
+ * span against all slots with four vector compares and two ballots, and broadcasts the one or two ranges that touch the span out
+ * of their lanes to test single elements only where a boundary crosses it.
+ * EMA (ema != NULL): e = e + (p_new - e) * ema_omd on the p just written, in the same trip.  params, exp_avg and exp_avg_sq get
+ * the same bits whether or not ema is given.  ema_omd == 0 writes nothing to ema / aux_ema.
+ * aux / aux_ema (n_aux floats each, no alignment asked, aux is only read): the same EMA for a second small buffer, done by one
+ * workgroup of the same launch — for the VAE the BatchNorm running statistics (cvae_bn_state_floats() floats, which cvae_forward
+ * of this step has already written), so that the averaged weights are evaluated with averaged statistics.
+ * decay_mul == 1, n_ranges == 0, ema == NULL: exactly cvae_adam_step's (cvae_adam_step_guarded's) bits.
+ * Guarded form: step_size, sqrt_bc2, gscale and the betas come from the record; decay_mul and ema_omd come from the host, which
+ * knows lr of this step (the lr it also gave cvae_grad_stats).  apply == 0: nothing is written at all — params, both moments,
+ * ema and aux_ema keep their bits.  cvae_guard_record and cvae_grad_stats are unchanged.
+ * CVAE_EINVAL, cvae_last_error() set and nothing launched, checked before any device access: a null handle, opt, params, grads
+ * or moment (or guard state); n < 0 or n % 4 != 0; step < 1; n_ranges outside 0..CVAE_OPT_MAX_RANGES; a range with begin >= end,
+ * before its predecessor's end, or past n; decay_mul outside (0, 1]; ema given and ema_omd outside [0, 1]; n_aux outside 0..4096;
+ * n_aux > 0 with a null aux or aux_ema; aux_ema without ema.
+ */
+#define CVAE_OPT_MAX_RANGES 16
+typedef struct cvae_opt_args {
+    float   decay_mul;                  /* (float)(1.0 - (double)lr * (double)weight_decay); 1.0f = no decay                 */
+    float   ema_omd;                    /* (float)(1.0 - ema_decay of this step); read only when ema != NULL                 */
+    int32_t n_ranges;                   /* decayed element ranges [begin, end), ascending, disjoint, within [0, n)           */
+    int32_t reserved;                   /* 0                                                                                 */
+    int64_t begin[CVAE_OPT_MAX_RANGES], end[CVAE_OPT_MAX_RANGES];
+} cvae_opt_args;
+int cvae_adam_step_opt(cvae_handle h, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                       int32_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
+                       const cvae_opt_args* opt /* host memory, copied into the launch */, float* ema /* n floats or NULL */,
+                       float* aux, float* aux_ema, int32_t n_aux /* 0..4096; both NULL when 0 */, void* stream);
+int cvae_adam_step_guarded_opt(cvae_handle h, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                               float eps, const void* state, const cvae_opt_args* opt, float* ema, float* aux, float* aux_ema,
+                               int32_t n_aux, void* stream);
+
+/*
  * Critic.evaluate (critic_net.py:66-69; eval mode) on frames x (B,3,64,64) in [0,1] -> pred (B,1),
  * the `preds` of vae.py:50.  critic_params: cvae_critic_param_count() (= 11 873) floats in the
  * reference's own state_dict order and layouts (features.{0,3,6,10,14}.{weight,bias},
