@@ -103,15 +103,16 @@ class CriticTrainer(DeviceTrainer):
     never augment; the augmentation is saved and restored with the trainer.  optim: an optim.Optim or None — as for
     FusedTrainer: LR schedule with `lr` as the peak, decoupled weight decay on the seven *.weight tensors (their boundaries fall
     anywhere in the flat block: the kernel's ranges are in elements), an EMA of the block in `ema` (no auxiliary buffer: the
-    critic has no BatchNorm), all inside the one Adam launch; evaluate(..., ema=True) scores the averaged block."""
+    critic has no BatchNorm), all inside the one Adam launch; evaluate(..., ema=True) scores the averaged block.  trace: a
+    trace.Trace or None — as for FusedTrainer, with the critic's 4 loss scalars and its 14 tensors."""
 
     def __init__(self, critic, lr=1e-4, betas=P.adam_betas, eps=P.adam_eps, dropout=0.3, loss="bce", skip_nonfinite=False,
-                 max_grad_norm=None, augment=None, optim=None):
+                 max_grad_norm=None, augment=None, optim=None, trace=None):
         if loss not in CRITIC_LOSS:
             raise ValueError(f"loss {loss!r}: one of {sorted(CRITIC_LOSS)}")
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout {dropout!r} outside [0, 1)")
-        self._init_shared(skip_nonfinite, max_grad_norm, optim)      # guard fields, step_count, val_history / best_val / val_stale, optim
+        self._init_shared(skip_nonfinite, max_grad_norm, optim, trace)      # guard fields, step_count, val_history / best_val / val_stale, optim, trace
         self.decay_ranges = decay_ranges(critic_layout())     # the seven *.weight tensors, at their element offsets
         self.critic, self.h = critic, critic.handle
         self._init_augment(augment, 64)
@@ -140,6 +141,9 @@ class CriticTrainer(DeviceTrainer):
         if self._pred is None or self._pred.numel() < B:
             self._pred = torch.empty(B, 1, device=self.theta.device)
         return self._scratch, self._pred[:B]
+
+    def _trace_layout(self):
+        return critic_layout()
 
     def draw_keep(self, B, generator=None):
         """(B, 800) uint8 keep mask on the device: torch.rand >= dropout."""

@@ -794,6 +794,32 @@ int cvae_adam_step_guarded_opt(cvae_handle h, float* params, const float* grads,
     return launch_adam_guarded_opt(params, grads, exp_avg, exp_avg_sq, n, eps, state, opt, ema, aux, aux_ema, n_aux, (hipStream_t)stream);
 }
 
+// ---- the training trace (include/cvae.h; trace.hip): every check on host values, before any device access ----
+int cvae_trace_push(cvae_handle h, void* ring, int64_t capacity, int64_t step, float lr, const float* loss_scalars, int32_t n_scalars,
+                    const void* guard_state_or_null, void* stream) {
+    if (!h || !ring || !loss_scalars) { cvae_set_error("cvae_trace_push: bad handle or null pointer"); return CVAE_EINVAL; }
+    if (capacity < 1 || step < 1) { cvae_set_error("cvae_trace_push: capacity = %lld and step = %lld must be at least 1", (long long)capacity, (long long)step); return CVAE_EINVAL; }
+    if (n_scalars < 0 || n_scalars > CVAE_TRACE_MAX_SCALARS) { cvae_set_error("cvae_trace_push: n_scalars = %d outside 0..%d", (int)n_scalars, CVAE_TRACE_MAX_SCALARS); return CVAE_EINVAL; }
+    return launch_trace_push(ring, capacity, step, lr, loss_scalars, n_scalars, guard_state_or_null, (hipStream_t)stream);
+}
+int cvae_tensor_stats(cvae_handle h, const float* params, const float* grads, const float* exp_avg, const float* exp_avg_sq, int64_t n,
+                      int32_t n_tensors, const int64_t* begin, const int64_t* end, int64_t step, float lr, float beta1, float beta2,
+                      float eps, float grad_scale, const void* guard_state_or_null, cvae_tensor_stat* out, void* scratch, void* stream) {
+    if (!h || !params || !grads || !exp_avg || !exp_avg_sq || !begin || !end || !out || !scratch) {
+        cvae_set_error("cvae_tensor_stats: bad handle or null pointer"); return CVAE_EINVAL;
+    }
+    if (n < 0 || step < 1) { cvae_set_error("cvae_tensor_stats: n = %lld must not be negative and step = %lld at least 1", (long long)n, (long long)step); return CVAE_EINVAL; }
+    return launch_tensor_stats(params, grads, exp_avg, exp_avg_sq, n, n_tensors, begin, end, step, lr, beta1, beta2, eps, grad_scale,
+                               guard_state_or_null, out, scratch, (hipStream_t)stream);
+}
+int64_t cvae_tensor_stats_scratch_bytes(int32_t n_tensors, const int64_t* begin, const int64_t* end) {
+    return tensor_stats_scratch_bytes(n_tensors, begin, end);
+}
+int cvae_tensor_stats_plan(int32_t n_tensors, const int64_t* begin, const int64_t* end, int32_t* chunk, int32_t* items, int32_t* grid) {
+    if (!chunk || !items || !grid) { cvae_set_error("cvae_tensor_stats_plan: null output"); return CVAE_EINVAL; }
+    return tensor_stats_plan(n_tensors, begin, end, chunk, items, grid);
+}
+
 int cvae_grads_to_bf16(cvae_handle h, const float* grads, void* out_bf16, int64_t n, void* stream) {
     if (h && n == 0) return 0;                       // empty range (its pointers may be null): nothing to do
     if (!h || !grads || !out_bf16 || n < 0) { cvae_set_error("cvae_grads_to_bf16: bad argument"); return CVAE_EINVAL; }

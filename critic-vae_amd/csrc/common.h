@@ -440,6 +440,16 @@ int launch_adam_opt(float* p, const float* g, float* m, float* v, int64_t n, int
                     float gscale, const cvae_opt_args* opt, float* ema, const float* aux, float* aux_ema, int32_t n_aux, hipStream_t st);
 int launch_adam_guarded_opt(float* p, const float* g, float* m, float* v, int64_t n, float eps, const void* state,
                             const cvae_opt_args* opt, float* ema, const float* aux, float* aux_ema, int32_t n_aux, hipStream_t st);
+// the training trace (trace.hip): arguments already checked by the caller, but for the range table (checked by the launcher,
+// which returns CVAE_EINVAL = -1 with the error set)
+struct cvae_tensor_stat;
+int launch_trace_push(void* ring, int64_t capacity, int64_t step, float lr, const float* scalars, int n_scalars,
+                      const void* guard_state, hipStream_t st);
+int launch_tensor_stats(const float* p, const float* g, const float* m, const float* v, int64_t n, int32_t n_tensors,
+                        const int64_t* begin, const int64_t* end, int64_t step, float lr, float b1, float b2, float eps, float gscale,
+                        const void* guard_state, cvae_tensor_stat* out, void* scratch, hipStream_t st);
+int64_t tensor_stats_scratch_bytes(int32_t n_tensors, const int64_t* begin, const int64_t* end);
+int tensor_stats_plan(int32_t n_tensors, const int64_t* begin, const int64_t* end, int32_t* chunk, int32_t* items, int32_t* grid);
 int launch_zero(float* p, int64_t n, hipStream_t st);
 struct PadGaps { int64_t off[32]; int len[32]; int n; };
 int launch_zero_gaps(float* grads, const PadGaps& gaps, hipStream_t st);

@@ -9,12 +9,15 @@ import torch
 
 from .augment import Augment
 from .optim import Optim
+from .trace import Trace
 
 
 class DeviceTrainer:
-    def _init_shared(self, skip_nonfinite, max_grad_norm, optim=None):
+    def _init_shared(self, skip_nonfinite, max_grad_norm, optim=None, trace=None):
         if optim is not None and not isinstance(optim, Optim):
             raise ValueError(f"optim {optim!r}: an optim.Optim or None")
+        if trace is not None and not isinstance(trace, Trace):
+            raise ValueError(f"trace {trace!r}: a trace.Trace or None")
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError(f"max_grad_norm {max_grad_norm!r}: a positive number (inf = no clipping) or None")
         self.skip_nonfinite = bool(skip_nonfinite)
@@ -31,6 +34,7 @@ class DeviceTrainer:
         self.decay_ranges = []            # the element ranges weight decay touches (optim.decay_ranges of the subclass's layout)
         self.ema = None                   # the averaged parameters and the averaged auxiliary buffer (the VAE's bn_state) of an
         self.aux_ema = None               # Optim with an EMA: created by the first such _update, or by load_state_dict
+        self.trace = trace                # a trace.Trace: every step ends in its _after_update (one or two more launches, no host read)
 
     def _init_augment(self, augment, width):
         """The constructor's `augment` argument: None, or an Augment whose shift fits frames of `width`."""
@@ -103,28 +107,43 @@ class DeviceTrainer:
         if not self.guarded:
             h.adam_step_opt(theta, self.grads, self.m, self.v, self.step_count, a["lr"], self.betas[0], self.betas[1], self.eps,
                             grad_scale=grad_scale, opt=a, ema=ema, aux=aux, aux_ema=aux_ema)
-            return
+            return a["lr"]
         if self.guard is None:
             self.guard = h.guard_state(self.m.device, *self._guard_counts)
         h.grad_stats(self.grads, self.guard, grad_scale, float("inf") if self.max_grad_norm is None else self.max_grad_norm,
                      self.skip_nonfinite, a["lr"], self.betas[0], self.betas[1])
         h.adam_step_guarded_opt(theta, self.grads, self.m, self.v, self.guard, self.eps, opt=a, ema=ema, aux=aux, aux_ema=aux_ema)
+        return a["lr"]
 
     def _update(self, theta, grad_scale):
+        """The optimizer launches of one step (_apply_update), then the trace's hook where the trainer has a trace: the one
+        place both trainers and every update path (plain, guarded, _opt; per-rank or global statistics) pass through."""
+        lr = self._apply_update(theta, grad_scale)
+        trace = getattr(self, "trace", None)               # a trainer assembled by hand (tests) may not carry the field
+        if trace is not None:
+            trace._after_update(self, theta, grad_scale, lr)
+
+    def _apply_update(self, theta, grad_scale):
         """cvae_adam_step, or the guarded pair: statistics of the reduced gradient -> decision record -> the Adam launch that
-        obeys it; nothing comes back to the host.  With an Optim: _update_opt."""
+        obeys it; nothing comes back to the host.  With an Optim: _update_opt.  Returns the lr the step was given."""
         h = self.h
         if getattr(self, "optim", None) is not None:
             return self._update_opt(theta, grad_scale)
         if not self.guarded:
             h.adam_step(theta, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
                         grad_scale=grad_scale)
-            return
+            return self.lr
         if self.guard is None:
             self.guard = h.guard_state(self.m.device, *self._guard_counts)
         h.grad_stats(self.grads, self.guard, grad_scale, float("inf") if self.max_grad_norm is None else self.max_grad_norm,
                      self.skip_nonfinite, self.lr, self.betas[0], self.betas[1])
         h.adam_step_guarded(theta, self.grads, self.m, self.v, self.guard, self.eps)
+        return self.lr
+
+    def _trace_layout(self):
+        """{name: (offset, numel)} of the flat buffers, for the trace's tensor table: the handle's (the VAE); CriticTrainer
+        has its own."""
+        return self.h.layout
 
     # ---- the guard's counters ----
     def _guard_read(self):

@@ -70,6 +70,50 @@ def opt_args(decay_mul=1.0, ema_omd=0.0, ranges=()):
     return a
 
 
+TRACE_MAX_SCALARS = 16   # CVAE_TRACE_MAX_SCALARS
+TRACE_MAX_TENSORS = 32   # CVAE_TRACE_MAX_TENSORS
+
+
+class TraceRow(C.Structure):
+    """cvae_trace_row (include/cvae.h): one step row of the trace ring, 128 bytes."""
+    _fields_ = [("step", C.c_int64), ("lr", C.c_float), ("applied", C.c_int32), ("nonfinite", C.c_uint32),
+                ("grad_norm", C.c_float), ("coef", C.c_float), ("n_scalars", C.c_int32), ("reserved", C.c_uint8 * 32),
+                ("scalars", C.c_float * TRACE_MAX_SCALARS)]
+
+
+class TensorStat(C.Structure):
+    """cvae_tensor_stat (include/cvae.h): the statistics of one tensor, 48 bytes."""
+    _fields_ = [("g2", C.c_double), ("p2", C.c_double), ("u2", C.c_double), ("gmax", C.c_float), ("pmax", C.c_float),
+                ("g_nonfinite", C.c_uint32), ("p_nonfinite", C.c_uint32), ("step", C.c_int64)]
+
+
+def _range_arrays(ranges):
+    """(n, begin, end) as ctypes int64 arrays from [(begin, end), ...]; the library checks the table."""
+    ranges = [(int(b), int(e)) for b, e in ranges]
+    n = len(ranges)
+    return n, (C.c_int64 * max(n, 1))(*[b for b, _ in ranges]), (C.c_int64 * max(n, 1))(*[e for _, e in ranges])
+
+
+def tensor_stats_plan(ranges):
+    """cvae_tensor_stats_plan (host logic only): dict(chunk, items, grid) of cvae_tensor_stats on the ranges."""
+    lib = load()
+    n, b, e = _range_arrays(ranges)
+    chunk, items, grid = C.c_int32(), C.c_int32(), C.c_int32()
+    if lib.cvae_tensor_stats_plan(n, b, e, C.byref(chunk), C.byref(items), C.byref(grid)) != 0:
+        raise CvaeError(f"cvae_tensor_stats_plan: {lib.cvae_last_error().decode()}")
+    return {"chunk": chunk.value, "items": items.value, "grid": grid.value}
+
+
+def tensor_stats_scratch_bytes(ranges):
+    """cvae_tensor_stats_scratch_bytes (host logic only)."""
+    lib = load()
+    n, b, e = _range_arrays(ranges)
+    size = lib.cvae_tensor_stats_scratch_bytes(n, b, e)
+    if size < 0:
+        raise CvaeError(f"cvae_tensor_stats_scratch_bytes: {lib.cvae_last_error().decode()}")
+    return size
+
+
 class AugmentParams(C.Structure):
     """cvae_augment (include/cvae.h): the key and ranges of one augmented batch gather."""
     _fields_ = [("key", C.c_uint64), ("flip_below", C.c_uint32), ("max_shift", C.c_int32), ("gain_q16", C.c_int32),
@@ -140,6 +184,11 @@ _SIGS = {
     "cvae_adam_step_guarded": (C.c_int, [_p, _p, _p, _p, _p, _i64, _f, _p, _p]),
     "cvae_adam_step_opt": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _f, _f, _f, _f, _f, C.POINTER(OptArgs), _p, _p, _p, _i32, _p]),
     "cvae_adam_step_guarded_opt": (C.c_int, [_p, _p, _p, _p, _p, _i64, _f, _p, C.POINTER(OptArgs), _p, _p, _p, _i32, _p]),
+    "cvae_trace_push": (C.c_int, [_p, _p, _i64, _i64, _f, _p, _i32, _p, _p]),
+    "cvae_tensor_stats": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i64, _f, _f, _f, _f, _f,
+                                    _p, _p, _p, _p]),
+    "cvae_tensor_stats_scratch_bytes": (_i64, [_i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "cvae_tensor_stats_plan": (C.c_int, [_i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 3),
     "cvae_grads_to_bf16": (C.c_int, [_p, _p, _p, _i64, _p]),
     "cvae_grads_from_bf16": (C.c_int, [_p, _p, _p, _i64, _p]),
     "cvae_critic_param_count": (_i32, []),
@@ -482,6 +531,35 @@ class Handle:
                                                         params.numel() if n is None else n, eps, self._guard_ptr(state),
                                                         None if opt is None else C.byref(opt), _ptr(ema), _ptr(aux),
                                                         _ptr(aux_ema), n_aux, _stream()))
+
+    # ---- the training trace (include/cvae.h; trace.py): ring and records are caller-owned device tensors of any dtype ----
+    @staticmethod
+    def _raw(t, nbytes, what):
+        """The address of a contiguous device tensor of at least `nbytes` bytes; None stays None, an int is an address."""
+        if t is None or isinstance(t, int):
+            return t
+        assert t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= nbytes, f"{what}: need {nbytes} contiguous device bytes"
+        return t.data_ptr()
+
+    def trace_push(self, ring, capacity, step, lr, loss_scalars, n_scalars=None, guard=None):
+        """cvae_trace_push: row (step - 1) % capacity of `ring` (capacity rows of 128 bytes); guard: a guard state or None."""
+        n_scalars = loss_scalars.numel() if n_scalars is None else n_scalars
+        self._check(self.lib.cvae_trace_push(self.h, self._raw(ring, 128 * max(int(capacity), 0), "trace ring"), int(capacity), int(step),
+                                             float(lr), _ptr(loss_scalars), int(n_scalars),
+                                             None if guard is None else self._guard_ptr(guard), _stream()))
+
+    def tensor_stats(self, params, grads, m, v, ranges, step, out, scratch, lr=0.0, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0,
+                     guard=None, n=None):
+        """cvae_tensor_stats on the element ranges [(begin, end), ...]: len(ranges) records of 48 bytes into `out`."""
+        nt, b, e = _range_arrays(ranges)
+        need = self.lib.cvae_tensor_stats_scratch_bytes(nt, b, e)            # negative: a table the entry itself refuses below
+        assert need < 0 or isinstance(scratch, int) or scratch is None or scratch.numel() * scratch.element_size() >= need, \
+            f"tensor scratch: need {need} bytes"
+        self._check(self.lib.cvae_tensor_stats(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel() if n is None else n,
+                                               nt, b, e, int(step), float(lr), b1, b2, eps, grad_scale,
+                                               None if guard is None else self._guard_ptr(guard),
+                                               self._raw(out, 48 * nt, "tensor records"), self._raw(scratch, 16, "tensor scratch"),
+                                               _stream()))
 
     @staticmethod
     def guard_record(state):

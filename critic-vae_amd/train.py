@@ -36,6 +36,7 @@ from .nets import VariationalAutoencoder
 from .augment import Augment
 from .objective import Objective, compose
 from .optim import Optim, decay_ranges
+from .trace import Trace, nonfinite_tensors
 
 
 def _reference_batches(dset, epoch_indices, starts, batch_size, device, critic_fn):
@@ -90,7 +91,7 @@ class FusedTrainer(DeviceTrainer):
 
     def __init__(self, vae, lr=P.lr, betas=P.adam_betas, eps=P.adam_eps, process_group=None, world_size=1,
                  overlap=None, reduce_dtype=None, sync=True, global_stats=None, skip_nonfinite=False, max_grad_norm=None,
-                 objective=None, augment=None, optim=None):
+                 objective=None, augment=None, optim=None, trace=None):
         """Construction with world_size > 1 is a COLLECTIVE (sync_replicas: five broadcasts from rank 0) unless
         sync=False.
         overlap: all-reduce the gradient in three buckets while backward still runs (default for
@@ -132,7 +133,12 @@ class FusedTrainer(DeviceTrainer):
         the same step has already written).  Both are created by the first such step as copies of theta / bn_state, so
         load_networks after construction is safe.  evaluate(..., ema=True) runs on them, fit_device(val=...) judges them, and
         state_dict carries them with the Optim: a run resumed in the middle of a schedule continues exactly.  Works with
-        global_stats and reduce_dtype="bf16" (the update is downstream of both); sync_replicas also broadcasts the averages."""
+        global_stats and reduce_dtype="bf16" (the update is downstream of both); sync_replicas also broadcasts the averages.
+        trace: a trace.Trace, or None = the step launches exactly what it always did.  Otherwise every step ends with
+        cvae_trace_push (its 16 loss scalars, lr and the guard's decision into a device ring) and, every tensors_every steps,
+        cvae_tensor_stats (per-tensor gradient / weight / update norms of the REDUCED gradient and the buffers Adam left); nothing
+        is read on the host before trace.read().  Each rank traces its own loss scalars; no collective is added.  The trace is
+        not part of state_dict()."""
         self.vae = vae
         self.h = vae.handle
         if overlap is None:
@@ -155,7 +161,7 @@ class FusedTrainer(DeviceTrainer):
         self.objective = objective
         self.buckets = [self.h.grad_bucket(ph) for ph in range(3)]
         self.lr, self.betas, self.eps = lr, betas, eps
-        self._init_shared(skip_nonfinite, max_grad_norm, optim)      # guard fields, step_count, val_history / best_val / val_stale, optim
+        self._init_shared(skip_nonfinite, max_grad_norm, optim, trace)      # guard fields, step_count, val_history / best_val / val_stale, optim, trace
         self._init_augment(augment, vae.width)
         if self.optim is not None:
             self.optim.check_lr(self.lr)      # an lr_min above the peak raises here, not after the warm-up
@@ -633,6 +639,15 @@ def build_parser():
     ap.add_argument("--ema", type=float, default=None, metavar="D", help="keep an exponential moving average of the weights (and of "
                     "the BatchNorm statistics) with decay D; validation judges it, --save DIR also writes DIR/ema/")
     ap.add_argument("--ema-warmup", action="store_true", help="with --ema: decay min(D, (1 + step) / (10 + step))")
+    ap.add_argument("--trace-out", metavar="FILE.npz", default=None, help="-train --episodes, -second, -critic: keep a training trace on "
+                    "the device (trace.py) and write it wherever the run saves; an existing file of the same run is continued "
+                    "(--resume).  python -m critic_vae_amd.trace FILE.npz prints it")
+    ap.add_argument("--trace-every", type=int, default=None, metavar="N", help="with --trace-out: a step row (loss scalars, lr, the "
+                    "guard's decision) every N optimizer steps (default 1; 0: none)")
+    ap.add_argument("--trace-tensors-every", type=int, default=None, metavar="M", help="with --trace-out: per-tensor gradient / weight / "
+                    "update norms every M optimizer steps (default 0: none)")
+    ap.add_argument("--trace-capacity", type=int, default=None, metavar="C", help="with --trace-out: rows of the step ring (default 4096; "
+                    "older rows are overwritten)")
     return ap
 
 
@@ -689,6 +704,25 @@ def _settle_optim(args, trainer, provisional, n_entries, directory):
         print(trainer.optim.describe())
 
 
+def trace_from_args(args):
+    """The Trace the four --trace-* flags describe, or None when none of them is given.  Raises ValueError as Trace does, and
+    for flags without --trace-out."""
+    given = {"every": args.trace_every, "tensors_every": args.trace_tensors_every, "capacity": args.trace_capacity}
+    given = {k: v for k, v in given.items() if v is not None}
+    if args.trace_out is None:
+        if given:
+            raise ValueError("--trace-every, --trace-tensors-every and --trace-capacity need --trace-out FILE.npz")
+        return None
+    return Trace(**given)
+
+
+def _save_trace(args, trainer):
+    """--trace-out: the trainer's trace -> the file (one device -> host copy of each ring); called wherever the run saves."""
+    trace, path = getattr(trainer, "trace", None), getattr(args, "trace_out", None)
+    if trace is not None and path:
+        print(f"saved {trace.save(path)}")
+
+
 def augment_from_args(args):
     """The Augment the four --augment-* flags describe, or None when none of them is given.  Raises ValueError as Augment does."""
     given = {"flip": args.augment_flip, "shift": args.augment_shift, "brightness": args.augment_brightness, "seed": args.augment_seed}
@@ -732,6 +766,13 @@ def main(argv=None):
                      "meaning for them")
     if args.max_grad_norm is not None and not args.max_grad_norm > 0:
         ap.error("--max-grad-norm needs a positive number")
+    try:
+        args.trace = trace_from_args(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if args.trace is not None and not ((args.train and args.episodes is not None) or args.second or (args.critic_mode and not args.eval_only)):
+        ap.error("--trace-out, --trace-every, --trace-tensors-every and --trace-capacity belong to the fused trainers: "
+                 "-train --episodes, -second and -critic")
     args.optim_kw = optim_kwargs_from_args(args)
     if args.optim_kw is not None:
         if not ((args.train and args.episodes is not None) or args.second or (args.critic_mode and not args.eval_only)):
@@ -830,7 +871,8 @@ def _fit_and_save(args, vae, ds, second):
     kw = getattr(args, "optim_kw", None)
     provisional = optim_from_kwargs(kw, (kw or {}).get("warmup", 0) + 1)      # --lr-total's default needs the training set: _settle_optim
     trainer = FusedTrainer(vae, skip_nonfinite=args.skip_nonfinite, max_grad_norm=args.max_grad_norm,
-                           objective=getattr(args, "objective", None), augment=getattr(args, "augment", None), optim=provisional)
+                           objective=getattr(args, "objective", None), augment=getattr(args, "augment", None), optim=provisional,
+                           trace=getattr(args, "trace", None))
     if args.resume:
         given, given_aug = trainer.objective, trainer.augment
         load_networks(vae, args.resume, second=second)
@@ -859,6 +901,7 @@ def _fit_and_save(args, vae, ds, second):
         print(f"saved {save_trainer(trainer, os.path.join(args.save, TRAINER_FILE))}")
         if trainer.has_ema():
             print(f"saved the averaged weights under {save_ema_networks(trainer, os.path.join(args.save, EMA_DIR), second=second)}")
+    _save_trace(args, trainer)
     _print_guard(trainer)
     return ds
 
@@ -920,6 +963,11 @@ def _print_guard(trainer):
     if trainer.guarded:
         st = trainer.guard_stats()
         print(f"guard: {st['applied']} steps applied, {st['skipped']} skipped")
+        trace = getattr(trainer, "trace", None)
+        if st["skipped"] > 0 and trace is not None and trace.tensors_every:
+            found = nonfinite_tensors(trace.read())
+            if found is not None:
+                print(f"guard: the skipped step {found[0]} had non-finite gradients in {', '.join(found[1]) or 'no traced tensor'}")
 
 
 class _KeepBestLog:
@@ -938,6 +986,7 @@ class _KeepBestLog:
             trainer.best_val, trainer.val_stale = float(loss), 0
             if self.args.keep_best:
                 self.save(trainer, os.path.join(self.args.save, BEST_DIR))
+                _save_trace(self.args, trainer)
         else:
             trainer.val_stale += 1
         if self.args.patience is not None and trainer.val_stale >= self.args.patience:
@@ -1054,7 +1103,7 @@ def _train_critic(args):
     from .critic_train import CriticTrainer
     critic, ds, device = _critic_and_dataset(args, args.datasize)
     trainer = CriticTrainer(critic, lr=args.lr, dropout=args.dropout, loss=args.loss, skip_nonfinite=args.skip_nonfinite,
-                            max_grad_norm=args.max_grad_norm, augment=getattr(args, "augment", None))
+                            max_grad_norm=args.max_grad_norm, augment=getattr(args, "augment", None), trace=getattr(args, "trace", None))
     if trainer.augment is not None:
         print(trainer.augment.describe())
     gen = torch.Generator(device=device)
@@ -1075,6 +1124,7 @@ def _train_critic(args):
     print(f"saved {_save_critic(critic, args.save)}")
     if trainer.has_ema():
         print(f"saved {_save_critic(critic, os.path.join(args.save, EMA_DIR), ema=trainer)}")
+    _save_trace(args, trainer)
     _print_guard(trainer)
     return critic
 

@@ -378,6 +378,73 @@ int cvae_adam_step_guarded_opt(cvae_handle h, float* params, const float* grads,
                                int32_t n_aux, void* stream);
 
 /*
+ * Training trace on the device (opt-in): a ring of step rows and per-tensor statistics of the flat buffers, written by launches
+ * on the caller's stream — no host read, no allocation, no synchronisation.  A trainer without a trace launches neither.
+ *
+ * cvae_trace_push: ONE small launch that writes row (step - 1) % capacity of `ring` (capacity rows of 128 bytes, 8-byte aligned,
+ * caller-owned device memory).  Every byte of the row is written, so a ring may hold anything on entry; no other row is touched.
+ * loss_scalars: n_scalars device floats, copied bit for bit (the VAE's 16, the critic's 4).  guard_state: the state cvae_grad_stats
+ * of this step has written (so the push runs after it), or NULL; it is only read.
+ * CVAE_EINVAL, cvae_last_error() set and nothing launched: a null handle, ring or loss_scalars; capacity < 1; step < 1; n_scalars
+ * outside 0..16.
+ */
+#define CVAE_TRACE_MAX_SCALARS 16
+typedef struct cvae_trace_row {          /* 128 bytes                                                                       */
+    int64_t  step;                       /*   0: 1-based optimizer step (the trainer's step_count after the step)            */
+    float    lr;                         /*   8: the lr this step was given                                                  */
+    int32_t  applied;                    /*  12: guard record's apply; 1 without a guard                                     */
+    uint32_t nonfinite;                  /*  16: guard record's; 0 without a guard                                           */
+    float    grad_norm, coef;            /*  20, 24: guard record's norm and coef; NaN and 1 without a guard                 */
+    int32_t  n_scalars;                  /*  28: 0..16                                                                       */
+    uint8_t  reserved[32];               /*  32: 0                                                                           */
+    float    scalars[16];                /*  64: the step's loss scalars, bit for bit; unused slots 0                        */
+} cvae_trace_row;
+int cvae_trace_push(cvae_handle h, void* ring, int64_t capacity, int64_t step, float lr,
+                    const float* loss_scalars, int32_t n_scalars, const void* guard_state_or_null, void* stream);
+
+/*
+ * cvae_tensor_stats: per-tensor statistics of the flat buffers AS THE OPTIMIZER LEFT THEM — it runs after the Adam launch of the
+ * step, reads params (already updated), grads and both moments (already updated) and writes n_tensors records to `out`.
+ * The tensors are element ranges [begin, end) of the flat buffers, ascending and disjoint; they may begin and end anywhere (no
+ * multiple of 4 is asked), and elements between ranges (alignment padding) are never read.
+ *     g   = grads[i] * gscale, one fp32 product: the gradient as Adam consumed it.  gscale is the record's (grad_scale * coef)
+ *           when a guard state is given, grad_scale otherwise.                      g2 = sum (double)g * (double)g
+ *     u   = step_size * (m / (sqrtf(v) / sqrt_bc2 + eps)), cvae_adam_step's fp32 expressions on the moments it left: the Adam
+ *           displacement of the step just taken.  step_size and sqrt_bc2 come from the record when one is given (apply == 0:
+ *           every u2 is exactly 0), otherwise from cvae_adam_step's host arithmetic on `step`, lr and the betas.
+ *           The displacement of decoupled weight decay (cvae_adam_step_opt's p * decay_mul) is NOT part of u.
+ *     p   = params[i] after the update.
+ * g_nonfinite / p_nonfinite count the elements of grads / params whose exponent bits are all set (Inf or NaN), taken from the
+ * stored bits as cvae_grad_stats takes them; a NaN never enters gmax / pmax (an Inf does).
+ * Work: every tensor is cut into chunks of `chunk` elements (a constant of the library); an item is one (tensor, chunk) pair;
+ * min(items, compute units, 256) persistent workgroups stride over the items and each item leaves one fp64 partial in `scratch`.
+ * The last workgroup to arrive merges the partials tensor by tensor: lane l of one wave sums chunks l, l + 64, ... in ascending
+ * order, then the wave's fixed xor tree.  Every addition has a fixed place and there are no floating-point atomics: the same
+ * buffers give the same bits.  16-byte loads wherever the four buffers are 16-byte aligned (scalar for the up to three elements
+ * in front of the first and behind the last aligned float4 of a chunk); element by element otherwise.
+ * scratch: cvae_tensor_stats_scratch_bytes() bytes, 16-byte aligned; it may hold anything on entry (the arrival counter in its
+ * first 16 bytes is zeroed on the stream in front of the launch).  out: n_tensors records, 8-byte aligned.
+ * cvae_tensor_stats_plan / cvae_tensor_stats_scratch_bytes are host logic only (no device access; without a device the grid
+ * assumes 256 compute units): chunk, item count and grid as the launcher computes them.
+ * CVAE_EINVAL (the size query: a negative value), cvae_last_error() set, before any device access: a null pointer; n_tensors
+ * outside 1..CVAE_TRACE_MAX_TENSORS; a range that is empty, before its predecessor's end or past n; step < 1.
+ */
+#define CVAE_TRACE_MAX_TENSORS 32
+typedef struct cvae_tensor_stat {        /* 48 bytes, one per tensor, device memory                                          */
+    double   g2, p2, u2;                 /*  0, 8, 16: sums of squares, fp64                                                 */
+    float    gmax, pmax;                 /* 24, 28: max |g * gscale|, max |p|; NaN elements do not enter the maxima          */
+    uint32_t g_nonfinite, p_nonfinite;   /* 32, 36: elements whose exponent bits are all set                                 */
+    int64_t  step;                       /* 40: as given                                                                     */
+} cvae_tensor_stat;
+int cvae_tensor_stats(cvae_handle h, const float* params, const float* grads, const float* exp_avg, const float* exp_avg_sq,
+                      int64_t n, int32_t n_tensors, const int64_t* begin, const int64_t* end /* host; copied into the launch */,
+                      int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
+                      const void* guard_state_or_null, cvae_tensor_stat* out, void* scratch, void* stream);
+int64_t cvae_tensor_stats_scratch_bytes(int32_t n_tensors, const int64_t* begin, const int64_t* end);   /* host only */
+int cvae_tensor_stats_plan(int32_t n_tensors, const int64_t* begin, const int64_t* end,
+                           int32_t* chunk, int32_t* items, int32_t* grid);                              /* host only; from the launcher */
+
+/*
  * Critic.evaluate (critic_net.py:66-69; eval mode) on frames x (B,3,64,64) in [0,1] -> pred (B,1),
  * the `preds` of vae.py:50.  critic_params: cvae_critic_param_count() (= 11 873) floats in the
  * reference's own state_dict order and layouts (features.{0,3,6,10,14}.{weight,bias},
