@@ -1,7 +1,9 @@
 """cvae_critic_grad and CriticTrainer on the device (csrc/critic_train.hip, critic_train.py) against the torch-CPU
 restatement tests/critic_train_ref.py, which tests/golden/make_critic_train_golden.py pins to the reference's own Critic
 class.  Smallest shapes at which the kernel can go wrong: B = 1, 5 and 37 (ragged against any power-of-two blocking, more
-than one workgroup, and — under CVAE_PERSIST_MAXWG — several images per workgroup)."""
+than one workgroup, and — under CVAE_PERSIST_MAXWG — several images per workgroup), and B = 256, 257 and 300 around the
+grid clamp at 256 workgroups: from 257 on some workgroups walk two images, the scratch holds 256 partials and not B, and the
+finalize takes a second trip over the loss terms."""
 import os
 import subprocess
 import sys
@@ -39,6 +41,15 @@ def noise():
                 target=rng.random(37, dtype=np.float32), keep=(rng.random((37, cvlib.CRITIC_KEEP)) >= 0.3).astype(np.uint8))
 
 
+@pytest.fixture(scope="module")
+def noise300():
+    """300 noise images for the batches past the grid clamp (MAX_GRID = 256 workgroups, critic_train.hip)."""
+    rng = np.random.default_rng(300)
+    w = synth.make_critic_params(0)
+    return dict(w=w, flat=ref.flatten(w).astype(np.float32), x=rng.random((300, 3, 64, 64), dtype=np.float32),
+                target=rng.random(300, dtype=np.float32), keep=(rng.random((300, cvlib.CRITIC_KEEP)) >= 0.3).astype(np.uint8))
+
+
 def _inputs(fx, noise, source):
     if source == "real":
         return fx["w"], fx["flat"], fx["x"], fx["z"]["target"], fx["z"]["keep"]
@@ -61,6 +72,31 @@ def test_parity_with_imposed_decisions(fx, noise, handle, B, source, loss, mode)
     k = keep[:B] if given else None
     res = T.run_kernel(handle, flat, x[:B], target[:B], k, p, loss)
     T.imposed_parity(res, w, x[:B], target[:B], k, p, loss, f"B={B} {source} {loss} {mode}")
+
+
+@pytest.mark.parametrize("loss", ["bce", "mse"])
+@pytest.mark.parametrize("B", [256, 257, 300])
+def test_parity_past_the_grid(noise300, handle, B, loss):
+    """The method and bounds of test_parity_with_imposed_decisions at the grid clamp: 256 images in 256 workgroups, 257 and
+    300 in 256 workgroups of which the first B - 256 walk two images (the scratch then holds 256 partials, the loss terms
+    start after them, and the finalize sums the terms in two trips).  Measured on the MI355X, worst of the six
+    cases: |d pred| 5.3e-08, |d loss| 3.7e-08, gradient gap 1.1e-06 of a tensor's max, no decision flips; the fp32 CPU
+    restatement's own gap to the fp64 one at B = 300 is 4.7e-08 / 2.3e-08 / 7.6e-06, so PRED_TOL and GRAD_TOL stay."""
+    n = noise300
+    res = T.run_kernel(handle, n["flat"], n["x"][:B], n["target"][:B], n["keep"][:B], 0.3, loss)
+    if "CVAE_PERSIST_MAXWG" not in os.environ:
+        assert res["partials_written"] == min(B, 256)
+    if B > 256:
+        assert res["partials_written"] < B
+    T.imposed_parity(res, n["w"], n["x"][:B], n["target"][:B], n["keep"][:B], 0.3, loss, f"B={B} noise {loss} p0.3-keep")
+
+
+@pytest.mark.parametrize("B", [1, 255, 256, 257, 300])
+def test_scratch_bytes_follow_the_grid_clamp(handle, B):
+    """min(B, 256) partials of 11 876 floats, then the (2, B) loss terms, rounded up to 256 bytes (host only)."""
+    assert cvlib.CRITIC_TRAIN_FLOATS == 11876
+    want = -(-((min(B, 256) * 11876 + 2 * B) * 4) // 256) * 256
+    assert handle.critic_grad_scratch_bytes(B) == want
 
 
 @pytest.mark.parametrize("loss", ["bce", "mse"])
@@ -109,15 +145,22 @@ def test_saturated_sigmoid(fx, handle, B):
     assert (r["flat_grads"] == 0).all() and abs(r["bce"] - float(res["scalars"][1])) <= 1e-5
 
 
-def test_determinism_and_hygiene(fx, handle):
+@pytest.mark.parametrize("B", [37, 257])
+def test_determinism_and_hygiene(fx, noise300, handle, B):
     """Same bits twice; NaN bytes in scratch, grads and decisions before the call change nothing; padding zero; 64 KB guard
-    bands after grads, pred, decisions and scratch untouched."""
-    z, B, G = fx["z"], 37, 65536
+    bands after grads, pred, decisions and scratch untouched.  B = 257 (noise images): the scratch is clamped to 256 partials,
+    so the band starts right after the loss terms that follow them, and the terms region is NaN before the third call."""
+    z, G = fx["z"], 65536
     sizes = dict(grads=cvlib.CRITIC_TRAIN_FLOATS * 4, pred=B * 4, dec=B * cvlib.CRITIC_DECISIONS,
                  scratch=handle.critic_grad_scratch_bytes(B))
     buf = {k: torch.empty(n + G, dtype=torch.uint8, device=DEV) for k, n in sizes.items()}
-    x, target = torch.from_numpy(fx["x"]).to(DEV), torch.from_numpy(z["target"]).to(DEV)
-    keep, flat = torch.from_numpy(z["keep"]).to(DEV), torch.from_numpy(fx["flat"]).to(DEV)
+    if B == 37:
+        src = dict(x=fx["x"], target=z["target"], keep=z["keep"], flat=fx["flat"])
+    else:
+        src = {k: noise300[k][:B] if k != "flat" else noise300[k] for k in ("x", "target", "keep", "flat")}
+    x, target = torch.from_numpy(src["x"]).to(DEV), torch.from_numpy(src["target"]).to(DEV)
+    keep, flat = torch.from_numpy(src["keep"]).to(DEV), torch.from_numpy(src["flat"]).to(DEV)
+    assert x.shape[0] == target.shape[0] == keep.shape[0] == B
     scal = torch.empty(4, device=DEV)
 
     def call(fill):

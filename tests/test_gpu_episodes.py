@@ -14,6 +14,7 @@ from critic_vae_amd.critic import Critic
 from critic_vae_amd.lib import Handle
 from critic_vae_amd.nets import VariationalAutoencoder
 from critic_vae_amd.train import FusedTrainer
+from dataset_ops_tools import device_select as _device_select
 from recon_tools import first_vae_params
 
 pytestmark = pytest.mark.gpu
@@ -65,33 +66,6 @@ def _adversarial_trajectories():
             a = rng.choice(vals, size=n)
         trajs.append(a.astype(np.float32))
     return trajs
-
-
-def _device_select(h, trajs, collect, total_images, n_chunks):
-    """The walk in n_chunks calls of cvae_curate_select, the running count carried on the device; returns the
-    selected (t, i), first and counts of every trajectory."""
-    bounds = np.linspace(0, len(trajs), n_chunks + 1).round().astype(int)
-    running = torch.zeros(1, dtype=torch.int64, device=DEV)
-    span = torch.zeros(2, dtype=torch.int64, device=DEV)
-    selected, first, counts = [], [], []
-    for c in range(n_chunks):
-        ts = list(range(bounds[c], bounds[c + 1]))
-        lens = [len(trajs[t]) for t in ts]
-        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        preds = torch.from_numpy(np.concatenate([trajs[t] for t in ts]) if ts else np.zeros(0, np.float32)).to(DEV)
-        n = preds.numel()
-        sel = torch.full((max(n, 1),), -7, dtype=torch.int64, device=DEV)
-        d_counts = torch.full((len(ts), 3), -7, dtype=torch.int64, device=DEV)
-        d_first = torch.full((len(ts),), -7, dtype=torch.int64, device=DEV)
-        h.curate_select(torch.from_numpy(offs).to(DEV), preds, collect, total_images, running, d_counts, d_first, span, sel)
-        sp = span.cpu().numpy()
-        picked = sel[:int(sp[1])].cpu().numpy()
-        tr = np.searchsorted(offs, picked, side="right") - 1
-        selected += [(ts[a], int(p - offs[a])) for a, p in zip(tr, picked)]
-        first += d_first.cpu().tolist()
-        counts += d_counts.cpu().tolist()
-        assert sp[0] + sp[1] == int(running.item())
-    return selected, first, np.array(counts, np.int64).reshape(-1, 3), int(running.item())
 
 
 def test_curate_select_matches_restatement():

@@ -17,6 +17,7 @@ from critic_vae_amd.critic import Critic
 from critic_vae_amd.lib import Handle
 from critic_vae_amd.nets import VariationalAutoencoder
 from critic_vae_amd.train import FusedTrainer
+from dataset_ops_tools import device_select_recon as _device_select_recon
 from oracle import cvae_oracle as orc
 from recon_tools import SAMPLE_STRIDE, first_vae_params, sample_of
 
@@ -108,39 +109,6 @@ def _adversarial_trajectories():
             a = rng.choice(vals, size=n)
         trajs.append(a.astype(np.float32))
     return trajs
-
-
-def _device_select_recon(h, trajs, collect, total_images, n_chunks):
-    bounds = np.linspace(0, len(trajs), n_chunks + 1).round().astype(int)
-    running = torch.zeros(1, dtype=torch.int64, device=DEV)
-    span = torch.zeros(3, dtype=torch.int64, device=DEV)
-    entries, first, counts = [], [], []
-    for c in range(n_chunks):
-        ts = list(range(bounds[c], bounds[c + 1]))
-        lens = [len(trajs[t]) for t in ts]
-        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        preds = torch.from_numpy(np.concatenate([trajs[t] for t in ts]) if ts else np.zeros(0, np.float32)).to(DEV)
-        n = preds.numel()
-        full = lambda m, dt=torch.int64: torch.full((max(m, 1),), -7, dtype=dt, device=DEV)          # noqa: E731
-        sel, ent_frame, ent_sel, ent_kind = full(n), full(2 * n), full(2 * n), full(2 * n, torch.int32)
-        d_counts = torch.full((len(ts), 3), -7, dtype=torch.int64, device=DEV)
-        d_first, d_sfirst = full(len(ts))[:len(ts)], full(len(ts))[:len(ts)]
-        h.curate_select_recon(torch.from_numpy(offs).to(DEV), preds, collect, total_images, running, d_counts, d_first,
-                              d_sfirst, span, ent_frame, ent_kind, ent_sel, sel)
-        e0, ne, ns = span.cpu().tolist()
-        ef, ek, es = ent_frame[:ne].cpu().numpy(), ent_kind[:ne].cpu().numpy(), ent_sel[:ne].cpu().numpy()
-        fs = sel[:ns].cpu().numpy()
-        tr = np.searchsorted(offs, ef, side="right") - 1
-        entries += [(ts[a], int(p - offs[a]), int(k)) for a, p, k in zip(tr, ef, ek)]
-        # the per-selected-frame index: frames in walk order, each once, and every entry points at its own frame
-        assert np.all(np.diff(fs) > 0) and np.array_equal(fs[es], ef) and len(set(ef.tolist())) == ns
-        sf, cn = d_sfirst.cpu().numpy(), d_counts.cpu().numpy()
-        want_sf = np.where(d_first.cpu().numpy() >= 0, np.concatenate([[0], np.cumsum(cn.sum(1))[:-1]]) if len(ts) else [], -1)
-        assert np.array_equal(sf, want_sf)
-        first += d_first.cpu().tolist()
-        counts += cn.tolist()
-        assert e0 + ne == int(running.item())
-    return entries, first, np.array(counts, np.int64).reshape(-1, 3), int(running.item())
 
 
 def test_curate_select_recon_matches_restatement(fx, ep):
