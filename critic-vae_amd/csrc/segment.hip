@@ -171,9 +171,14 @@ int run_crf(int B, const uint8_t* frames, const float* prob1, const cvae_crf_par
             void* scratch, hipStream_t st) {
     const int64_t npix = (int64_t)B * W * W;
     const CrfScratch s = carve_crf(scratch, npix);
-    const float sa = sqrtf(LOG2E / (2.0f * p.alpha * p.alpha));      // exp(-x^2 / (2 s^2)) = exp2(-(x * sqrt(log2 e / (2 s^2)))^2)
-    const float sb = sqrtf(LOG2E / (2.0f * p.beta * p.beta));
-    const float cg = LOG2E / (2.0f * p.gamma * p.gamma);
+    // exp(-x^2 / (2 s^2)) = exp2(-(x * sqrt(log2 e / (2 s^2)))^2).  A tiny alpha, beta or gamma sends its scale to +inf, and
+    // 0 * inf (pixel 0, colour 0, tap 0) is NaN; a large finite sa is no better, since (qy - y * sa) contracts to an fma that
+    // returns the rounding error of qy, whose square then zeroes a pixel's own tap.  The scales stop where exp2 of the
+    // smallest nonzero distance is already 0 (2^-256) and that of distance 0 is 1: the identity filter, as in exact
+    // arithmetic.  Powers of two, so that coordinate * scale is exact.
+    const float sa = fminf(sqrtf(LOG2E / (2.0f * p.alpha * p.alpha)), 16.0f);
+    const float sb = fminf(sqrtf(LOG2E / (2.0f * p.beta * p.beta)), 16.0f);
+    const float cg = fminf(LOG2E / (2.0f * p.gamma * p.gamma), 256.0f);
     const unsigned pix_blocks = (unsigned)((npix + TPB - 1) / TPB);
     const unsigned crf_blocks = (unsigned)(npix / QBLK);
     hipLaunchKernelGGL(crf_init_kernel, dim3(pix_blocks), dim3(TPB), 0, st, frames, prob1, s, W, npix, sb, cg, p.p_floor);

@@ -715,6 +715,8 @@ int cvae_mask_counts(cvae_handle h, int32_t batch, const uint8_t* mask, const ui
  * tie); q1_or_null (B,W,W) fp32 = Q(1).  frames_hwc (B,W,W,3) uint8, prob1 (B,W,W) fp32.  Deterministic: a
  * frame's result is bitwise independent of the batch it is in and its position there.
  * Ranges: w1, w2 >= 0; alpha, beta, gamma > 0; 0 < p_floor <= 1; 0 <= iterations <= 10000; all finite.
+ * A width below about 0.05 reaches no neighbour in fp32 (the nearest tap is under 2^-256): that kernel is then the
+ * identity filter, for any width > 0 however small.
  * `scratch`: cvae_crf_scratch_bytes(h, batch) bytes of device memory, 256-byte aligned (host-only query; -1 for
  * a bad handle or batch). */
 typedef struct cvae_crf_params {

@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from crf_ref import crf_ref  # noqa: E402
+from segment_tools import _structured_frames  # noqa: E402
 
 from critic_vae_amd import segment as seg  # noqa: E402
 from critic_vae_amd.critic import Critic  # noqa: E402
@@ -19,29 +20,6 @@ from critic_vae_amd.nets import VariationalAutoencoder  # noqa: E402
 from critic_vae_amd import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _structured_frames(n, w, seed):
-    """Blocky colour regions with noise and their masks (a disk, stripes, speckle, a soft probability)."""
-    rng = np.random.default_rng(seed)
-    frames = np.empty((n, w, w, 3), np.uint8)
-    masks = np.empty((n, w, w), np.float32)
-    yy, xx = np.mgrid[0:w, 0:w]
-    for i in range(n):
-        cells = rng.integers(0, 256, size=(4, 4, 3))
-        base = np.repeat(np.repeat(cells, w // 4, 0), w // 4, 1).astype(np.int32)
-        frames[i] = np.clip(base + rng.integers(-6, 7, size=(w, w, 3)), 0, 255).astype(np.uint8)
-        cx, cy, r = rng.integers(w // 4, 3 * w // 4, size=2).tolist() + [rng.integers(w // 8, w // 3)]
-        m = ((xx - cx) ** 2 + (yy - cy) ** 2 < r * r).astype(np.float32)
-        kind = i % 4
-        if kind == 1:
-            m = ((xx // 5 + i) % 3 == 0).astype(np.float32)
-        elif kind == 2:
-            m = np.where(rng.random((w, w)) < 0.1, 1 - m, m)
-        elif kind == 3:
-            m = np.clip(0.5 + 0.4 * np.sin(xx / 7.0 + i) * np.cos(yy / 5.0), 0, 1).astype(np.float32)
-        masks[i] = m
-    return frames, masks
 
 
 def _real_frames(golden_dir, n):
