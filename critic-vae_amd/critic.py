@@ -4,7 +4,7 @@ buffer in the reference's state_dict order (what cvae_critic_forward reads)."""
 import torch
 from torch import nn
 
-from .lib import Handle
+from .lib import CRITIC_DECISIONS, CRITIC_EMBED_SHAPES, Handle
 
 # reference state_dict keys, in order, with shapes (critic_net.py:15-41, default arguments)
 CRITIC_KEYS = (("features.0.weight", (8, 3, 3, 3)), ("features.0.bias", (8,)),
@@ -51,9 +51,49 @@ class Critic(nn.Module):
         return out
 
     def forward(self, X, collect=False):
-        if collect:
-            raise NotImplementedError("collect=True (embeddings) is not on the training path")
-        return self.evaluate(X)
+        """critic_net.py:44-59 in eval mode: pred (B,1), or with collect (pred, [e1..e5]): the four pooled feature maps and
+        the bottleneck (features.14 after its ReLU), as the reference's list."""
+        if not collect:
+            return self.evaluate(X)
+        with torch.no_grad():
+            X = X.to(torch.float32).contiguous()
+            B = X.shape[0]
+            pred = torch.empty(B, 1, device=X.device)
+            embeds = [torch.empty(B, *s, device=X.device) for s in CRITIC_EMBED_SHAPES]
+            self.handle.critic_collect(B, X, self.flat, pred, embeds)
+        return pred, embeds
+
+    def saliency(self, X, steps=1, return_grad=False, return_decisions=False):
+        """The gradient of the critic's logit with respect to the pixels of X (B,3,64,64) in [0,1]: steps == 1 at X itself,
+        steps 2..256 integrated gradients from the black frame (include/cvae.h, cvae_critic_saliency).
+        -> dict(pred (B,1), map (B,64,64) grey |gradient|, max_values (B) [, grad (B,3,64,64)] [, decisions (B,11072) uint8])."""
+        with torch.no_grad():
+            X = X.to(torch.float32).contiguous()
+            B, dev = X.shape[0], X.device
+            out = {"pred": torch.empty(B, 1, device=dev), "map": torch.empty(B, 64, 64, device=dev), "max_values": torch.empty(B, device=dev)}
+            if return_grad:
+                out["grad"] = torch.empty(B, 3, 64, 64, device=dev)
+            if return_decisions:
+                out["decisions"] = torch.empty(B, CRITIC_DECISIONS, dtype=torch.uint8, device=dev)
+            self.handle.critic_saliency(B, X, self.flat, steps, out["pred"], out["map"], out["max_values"], grad=out.get("grad"),
+                                        decisions=out.get("decisions"))
+        return out
+
+    def occlusion(self, X, patch=8, fill=None):
+        """Occlusion sensitivity (cvae_critic_occlusion): every non-overlapping patch x patch window (4, 8 or 16) of X is covered
+        with the colour `fill` (three floats; None: the mean colour of X) and the critic runs again.
+        -> dict(pred (B,1), drop (B,64/patch,64/patch) = pred - occluded pred, map (B,64,64) = max(drop, 0) over its patch,
+        max_values (B), fill)."""
+        with torch.no_grad():
+            X = X.to(torch.float32).contiguous()
+            B, dev, g = X.shape[0], X.device, 64 // int(patch)
+            if fill is None:
+                fill = X.mean(dim=(0, 2, 3)).tolist()
+            fill = tuple(float(v) for v in fill)
+            out = {"pred": torch.empty(B, 1, device=dev), "drop": torch.empty(B, g, g, device=dev), "map": torch.empty(B, 64, 64, device=dev),
+                   "max_values": torch.empty(B, device=dev), "fill": fill}
+            self.handle.critic_occlusion(B, X, self.flat, patch, fill, out["pred"], out["drop"], out["map"], out["max_values"])
+        return out
 
     def evaluate(self, X):
         """critic_net.py:66-69: no_grad forward, returns (B,1) in (0,1)."""

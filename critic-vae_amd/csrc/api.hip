@@ -875,6 +875,62 @@ int cvae_critic_grad(cvae_handle h, int32_t B, const float* x, const float* targ
                               decisions_or_null, scratch, (hipStream_t)stream);
 }
 
+// ---- critic-side masks: embeddings, the logit's input gradient, occlusion (critic_saliency.hip) ----
+// what the three entries share: handle, width, batch, the frames and the parameters; 0 or the error code
+static int critic_mask_args(const char* fn, cvae_handle h, int32_t B, const float* x, const float* critic_params) {
+    if (!h) { cvae_set_error("%s: null handle", fn); return CVAE_EINVAL; }
+    if (h->cfg.width != 64) { cvae_set_error("%s: width %d unsupported (the reference critic is 64x64 only)", fn, h->cfg.width); return CVAE_EUNSUPPORTED; }
+    if (B < 1 || B > kCriticGradMaxBatch) { cvae_set_error("%s: batch %d outside [1, %d]", fn, B, kCriticGradMaxBatch); return CVAE_EINVAL; }
+    if (!x) { cvae_set_error("%s: x is null", fn); return CVAE_EINVAL; }
+    if ((uintptr_t)x & 15) { cvae_set_error("%s: x must be 16-byte aligned", fn); return CVAE_EINVAL; }
+    if (!critic_params || ((uintptr_t)critic_params & 3)) { cvae_set_error("%s: critic_params is null or not 4-byte aligned", fn); return CVAE_EINVAL; }
+    return 0;
+}
+
+// a required (or, with optional, nullable) fp32 output: non-null and 4-byte aligned
+static int critic_mask_out(const char* fn, const char* name, const void* p, bool optional) {
+    if (!p && !optional) { cvae_set_error("%s: %s is null", fn, name); return CVAE_EINVAL; }
+    if ((uintptr_t)p & 3) { cvae_set_error("%s: %s must be 4-byte aligned", fn, name); return CVAE_EINVAL; }
+    return 0;
+}
+
+int cvae_critic_collect(cvae_handle h, int32_t B, const float* x, const float* critic_params, float* pred, float* e1_or_null,
+                        float* e2_or_null, float* e3_or_null, float* e4_or_null, float* e5_or_null, void* stream) {
+    const char* fn = "cvae_critic_collect";
+    if (int rc = critic_mask_args(fn, h, B, x, critic_params)) return rc;
+    if (int rc = critic_mask_out(fn, "pred", pred, false)) return rc;
+    float* const e[5] = {e1_or_null, e2_or_null, e3_or_null, e4_or_null, e5_or_null};
+    const char* names[5] = {"e1", "e2", "e3", "e4", "e5"};
+    for (int i = 0; i < 5; ++i)
+        if (int rc = critic_mask_out(fn, names[i], e[i], true)) return rc;
+    return launch_critic_collect(B, x, critic_params, pred, e, (hipStream_t)stream);
+}
+
+int cvae_critic_saliency(cvae_handle h, int32_t B, const float* x, const float* critic_params, int32_t steps, float* pred,
+                         float* grad_or_null, float* map, float* max_values, uint8_t* decisions_or_null, void* stream) {
+    const char* fn = "cvae_critic_saliency";
+    if (int rc = critic_mask_args(fn, h, B, x, critic_params)) return rc;
+    if (steps < 1 || steps > CVAE_CRITIC_IG_MAX_STEPS) { cvae_set_error("%s: steps %d outside [1, %d]", fn, steps, CVAE_CRITIC_IG_MAX_STEPS); return CVAE_EINVAL; }
+    if (int rc = critic_mask_out(fn, "pred", pred, false)) return rc;
+    if (int rc = critic_mask_out(fn, "grad", grad_or_null, true)) return rc;
+    if (int rc = critic_mask_out(fn, "map", map, false)) return rc;
+    if (int rc = critic_mask_out(fn, "max_values", max_values, false)) return rc;
+    if (int rc = critic_mask_out(fn, "decisions", decisions_or_null, true)) return rc;
+    return launch_critic_saliency(B, x, critic_params, steps, pred, grad_or_null, map, max_values, decisions_or_null, (hipStream_t)stream);
+}
+
+int cvae_critic_occlusion(cvae_handle h, int32_t B, const float* x, const float* critic_params, int32_t patch, float fill_r,
+                          float fill_g, float fill_b, float* pred, float* drop, float* map, float* max_values, void* stream) {
+    const char* fn = "cvae_critic_occlusion";
+    if (int rc = critic_mask_args(fn, h, B, x, critic_params)) return rc;
+    if (patch != 4 && patch != 8 && patch != 16) { cvae_set_error("%s: patch %d (4, 8 or 16)", fn, patch); return CVAE_EINVAL; }
+    if (int rc = critic_mask_out(fn, "pred", pred, false)) return rc;
+    if (int rc = critic_mask_out(fn, "drop", drop, false)) return rc;
+    if (int rc = critic_mask_out(fn, "map", map, false)) return rc;
+    if (int rc = critic_mask_out(fn, "max_values", max_values, false)) return rc;
+    return launch_critic_occlusion(B, x, critic_params, patch, fill_r, fill_g, fill_b, pred, drop, map, max_values, (hipStream_t)stream);
+}
+
 // ---- per-frame scores of the critic against its targets and the pooled record (critic_score.hip) ----
 int64_t cvae_critic_score_state_bytes(void) { return critic_score_state_bytes(); }
 

@@ -390,6 +390,12 @@ int64_t critic_score_scratch_bytes(int B);
 int launch_critic_score_init(void* state, hipStream_t st);
 int launch_critic_score(int B, const uint8_t* frames, const float* targets, int64_t n, const int64_t* idx, const float* critic_params,
                         float* rows, void* state, hipStream_t st);
+// critic_saliency.hip: embeddings, the logit's input gradient (plain / integrated) and occlusion drops (include/cvae.h)
+int launch_critic_collect(int B, const float* x, const float* critic_params, float* pred, float* const e[5], hipStream_t st);
+int launch_critic_saliency(int B, const float* x, const float* critic_params, int steps, float* pred, float* grad, float* map,
+                           float* max_values, uint8_t* decisions, hipStream_t st);
+int launch_critic_occlusion(int B, const float* x, const float* critic_params, int patch, float fill_r, float fill_g, float fill_b,
+                            float* pred, float* drop, float* map, float* max_values, hipStream_t st);
 // dataset.hip
 int launch_curate_select(int n_traj, const int64_t* off, int64_t n_frames, const float* preds, int collect,
                          int64_t total_images, int64_t* running, int64_t* counts, int64_t* first, int64_t* span,

@@ -130,6 +130,9 @@ MAX_PANELS = 8
 COMPOSE_CLAMP = 1
 CRITIC_KEEP, CRITIC_DECISIONS, CRITIC_TRAIN_FLOATS = 800, 11072, 11876      # include/cvae.h: cvae_critic_grad
 CRITIC_LOSS = {"bce": 0, "mse": 1}
+CRITIC_EMBED_SHAPES = ((8, 32, 32), (8, 16, 16), (8, 8, 8), (16, 4, 4), (32, 1, 1))     # cvae_critic_collect: e1..e5
+CRITIC_IG_MAX_STEPS = 256         # CVAE_CRITIC_IG_MAX_STEPS
+CRITIC_OCCLUSION_PATCHES = (4, 8, 16)
 CRITIC_SCORE_COLS = 8             # CVAE_CRITIC_SCORE_COLS: floats per frame row of cvae_critic_score
 CRITIC_SCORE_STATE_DOUBLES = 40   # CVAE_CRITIC_SCORE_STATE_DOUBLES: the pooled fp64 record of cvae_critic_score
 
@@ -196,6 +199,9 @@ _SIGS = {
     "cvae_critic_train_floats": (_i64, []),
     "cvae_critic_grad_scratch_bytes": (_i64, [_p, _i32]),
     "cvae_critic_grad": (C.c_int, [_p, _i32, _p, _p, _p, _f, _i32] + [_p] * 7),
+    "cvae_critic_collect": (C.c_int, [_p, _i32] + [_p] * 9),
+    "cvae_critic_saliency": (C.c_int, [_p, _i32, _p, _p, _i32] + [_p] * 6),
+    "cvae_critic_occlusion": (C.c_int, [_p, _i32, _p, _p, _i32, _f, _f, _f] + [_p] * 5),
     "cvae_critic_score_state_bytes": (_i64, []),
     "cvae_critic_score_scratch_bytes": (_i64, [_p, _i32]),
     "cvae_critic_score_init": (C.c_int, [_p, _p, _p]),
@@ -587,6 +593,33 @@ class Handle:
         self._check(self.lib.cvae_critic_grad(self.h, B, _ptr(x), _ptr(target), self._u8(keep, "keep"), float(dropout_p), int(loss_kind),
                                               _ptr(critic_params), _ptr(grads), _ptr(pred), _ptr(loss_scalars),
                                               self._u8(decisions, "decisions"), scratch.data_ptr(), _stream()))
+
+    # ---- critic-side masks: embeddings, the logit's input gradient, occlusion (include/cvae.h) ----
+    def critic_collect(self, B, x, critic_params, pred, embeds=(None,) * 5):
+        """Eval-mode forward + the five tensors of Critic.forward(X, collect=True); any of `embeds` (e1..e5) may be None."""
+        assert len(embeds) == 5 and pred.numel() >= B and x.numel() >= B * 3 * 64 * 64
+        for e, shape in zip(embeds, CRITIC_EMBED_SHAPES):
+            assert e is None or e.numel() >= B * shape[0] * shape[1] * shape[2]
+        self._check(self.lib.cvae_critic_collect(self.h, B, _ptr(x), _ptr(critic_params), _ptr(pred), *[_ptr(e) for e in embeds], _stream()))
+
+    def critic_saliency(self, B, x, critic_params, steps, pred, map_, max_values, grad=None, decisions=None):
+        """d logit / d x (steps == 1) or integrated gradients from black (steps 2..256): pred (B), map_ (B,64,64), max_values (B),
+        grad (B,3,64,64) or None, decisions (B, 11072) uint8 or None."""
+        assert x.numel() >= B * 3 * 64 * 64 and pred.numel() >= B and map_.numel() >= B * 64 * 64 and max_values.numel() >= B
+        assert grad is None or grad.numel() >= B * 3 * 64 * 64
+        assert decisions is None or decisions.numel() >= B * CRITIC_DECISIONS
+        self._check(self.lib.cvae_critic_saliency(self.h, B, _ptr(x), _ptr(critic_params), int(steps), _ptr(pred), _ptr(grad), _ptr(map_),
+                                                  _ptr(max_values), self._u8(decisions, "decisions"), _stream()))
+
+    def critic_occlusion(self, B, x, critic_params, patch, fill_rgb, pred, drop, map_, max_values):
+        """Occlusion sensitivity with non-overlapping patch x patch windows (4, 8 or 16) filled with fill_rgb (three floats):
+        pred (B), drop (B, 64/patch, 64/patch), map_ (B,64,64), max_values (B)."""
+        g = 64 // int(patch) if int(patch) in CRITIC_OCCLUSION_PATCHES else 0
+        assert x.numel() >= B * 3 * 64 * 64 and pred.numel() >= B and map_.numel() >= B * 64 * 64 and max_values.numel() >= B
+        assert drop.numel() >= B * g * g
+        r, gr, b = (float(v) for v in fill_rgb)
+        self._check(self.lib.cvae_critic_occlusion(self.h, B, _ptr(x), _ptr(critic_params), int(patch), r, gr, b, _ptr(pred), _ptr(drop),
+                                                   _ptr(map_), _ptr(max_values), _stream()))
 
     # ---- per-frame critic scores and the pooled record of a held-out set (include/cvae.h) ----
     def critic_score_state(self, device):

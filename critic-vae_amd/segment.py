@@ -14,6 +14,10 @@ unary_from_softmax helper); whether SimpleCRF clamps a 0/1 mask the same way has
 
     python -m critic_vae_amd.segment -video [-thresh] --frames X.npy --gt Y.npy --networks DIR [--critic CKPT]
                                      [--out DIR [--gif] [--no-text]]
+
+`--mask-source critic-grad | critic-ig | critic-occlusion` builds the masks from the critic alone (critic_maps: the
+gradient of its logit with respect to the pixels, integrated gradients, occlusion sensitivity) and sends them through the
+same tail (eval_maps / sweep_maps): the baselines that show what the VAE adds.  No pictures for these sources.
 """
 import argparse
 import os
@@ -229,17 +233,51 @@ def _crf_counts(frames, thr_mask, gt, crf_params_, p_floor):
     return crf, iou_from_counts(*c)
 
 
-def eval_frames(frames_u8, vae, gt, critic=None, preds=None, t=THRESHOLD, crf_params=CRF_REF, chunk=None,
-                p_floor=P_FLOOR, keep_device=False):
-    """eval_textured_frames (vae_utility.py:162-212) without the PIL frames.  frames_u8 (B,W,W,3) uint8, gt (B,W,W)
-    bool; either a critic (64x64 only, as the reference's) or explicit preds (B,).  The VAE runs in eval mode in
-    chunks of at most vae.max_batch; normalisation, threshold, CRF and IoU run over the whole set at once.
-    Returns a dict: preds, diff (fp32), max_values, diff_u8, thr_masks, crf_masks (host arrays), thr_iou, crf_iou,
-    bins, mean_max, hist (the (2,256) histograms of diff_u8).  keep_device=True adds "device": what render.video_frames
-    composes the pictures from, left on the device (frames, gt, preds, recon_one, recon_zero, diff_u8, thr_masks, crf_masks;
-    the masks as uint8 0/1)."""
-    p, diff, maxv, *recons = _infer(frames_u8, vae, critic, preds, chunk, keep_recons=keep_device)
+MASK_SOURCES = {"vae": None, "critic-grad": "grad", "critic-ig": "ig", "critic-occlusion": "occlusion"}      # --mask-source
+IG_STEPS, OCCLUSION_PATCH = 32, 8
+
+
+def critic_maps(frames_u8, critic, source="grad", steps=IG_STEPS, patch=OCCLUSION_PATCH, fill=None, chunk=256):
+    """Masks from the critic alone, to set beside the VAE's difference masks: (preds (B,) fp32, maps (B,64,64) fp32 >= 0,
+    per-frame maxima (B,) fp32), on the device.  source "grad": the grey |d logit / d x|; "ig": the same of integrated
+    gradients over `steps` passes from the black frame; "occlusion": the drop of the critic's value under a `patch` x `patch`
+    cover of colour `fill` (None: the mean colour of the whole set).  Frames go through preprocess_u8 in chunks, as _infer's."""
+    if source not in ("grad", "ig", "occlusion"):
+        raise ValueError(f"source {source!r}: one of 'grad', 'ig', 'occlusion'")
     frames = _cuda(frames_u8, torch.uint8)
+    B, W = frames.shape[0], frames.shape[1]
+    if W != 64:
+        raise ValueError(f"frames are {W}x{W}, the critic is 64x64 only")
+    chunk = min(max(1, int(chunk or 256)), critic.handle.max_batch)       # preprocess_u8 takes at most the handle's max_batch
+    if source == "occlusion" and fill is None:
+        fill = (frames.sum(dim=(0, 1, 2), dtype=torch.float64) / (B * W * W * 255.0)).tolist()
+    out_p = torch.empty(B, device=frames.device)
+    maps = torch.empty(B, W, W, device=frames.device)
+    maxv = torch.empty(B, device=frames.device)
+    x = torch.empty(chunk, 3, W, W, device=frames.device)
+    for s in range(0, B, chunk):
+        e = min(B, s + chunk)
+        xs = x[:e - s]
+        critic.handle.preprocess_u8(e - s, frames[s:e], xs)
+        if source == "occlusion":
+            r = critic.occlusion(xs, patch=patch, fill=fill)
+        else:
+            r = critic.saliency(xs, steps=1 if source == "grad" else steps)
+        out_p[s:e] = r["pred"].reshape(-1)
+        maps[s:e] = r["map"]
+        maxv[s:e] = r["max_values"]
+    return out_p, maps, maxv
+
+
+def eval_maps(frames_u8, maps, max_values, preds, gt, t=THRESHOLD, crf_params=CRF_REF, p_floor=P_FLOOR):
+    """The tail of eval_frames for any non-negative per-pixel map (B,W,W) with its per-frame maxima: normalisation by the
+    set-wide mean of the maxima, threshold, histograms, thr_iou, CRF, crf_iou, bins.  Returns eval_frames' dict (its "diff"
+    is `maps`), and under "device" the tensors left on the device (frames, gt, preds, diff_u8, thr_masks, crf_masks; the
+    masks as uint8 0/1)."""
+    frames = _cuda(frames_u8, torch.uint8)
+    diff = _cuda(maps, torch.float32)
+    maxv = _cuda(max_values, torch.float32).reshape(-1)
+    p = _cuda(preds, torch.float32).reshape(-1)
     gt_d = _cuda(_np(gt).astype(np.uint8), torch.uint8)
     hist = torch.zeros(2, 256, dtype=torch.int64, device=frames.device)
     u8, m, c, mean_max = _normalize(diff, maxv.cpu(), t, gt=gt_d, mask=True, counts=True, hist=hist)
@@ -247,23 +285,19 @@ def eval_frames(frames_u8, vae, gt, critic=None, preds=None, t=THRESHOLD, crf_pa
     crf, crf_iou = _crf_counts(frames, m, gt_d, crf_params, p_floor)
     thr_np = _np(m).astype(bool)
     preds_np = _np(p)
-    r = {"preds": preds_np, "diff": _np(diff), "max_values": _np(maxv), "diff_u8": _np(u8), "thr_masks": thr_np, "crf_masks": _np(crf), "thr_iou": thr_iou,
-         "crf_iou": crf_iou, "bins": bin_info(preds_np, gt, thr_np), "mean_max": mean_max, "hist": _np(hist)}
-    if keep_device:
-        r["device"] = {"frames": frames, "gt": gt_d, "preds": p, "recon_one": recons[0], "recon_zero": recons[1], "diff_u8": u8,
-                       "thr_masks": m, "crf_masks": crf.to(torch.uint8)}
-    return r
+    return {"preds": preds_np, "diff": _np(diff), "max_values": _np(maxv), "diff_u8": _np(u8), "thr_masks": thr_np, "crf_masks": _np(crf),
+            "thr_iou": thr_iou, "crf_iou": crf_iou, "bins": bin_info(preds_np, gt, thr_np), "mean_max": mean_max, "hist": _np(hist),
+            "device": {"frames": frames, "gt": gt_d, "preds": p, "diff_u8": u8, "thr_masks": m, "crf_masks": crf.to(torch.uint8)}}
 
 
-def threshold_sweep(frames_u8, vae, gt, critic=None, preds=None, thresholds=SWEEP, crf_params=CRF_REF, chunk=None,
-                    p_floor=P_FLOOR):
-    """The -thresh loop (vae.py:119-124): the VAE and critic run once, the masks are normalised once (thr_iou at every
-    threshold from its histograms), the CRF once per threshold.  Returns [(t, thr_iou, crf_iou), ...]."""
-    p, diff, maxv = _infer(frames_u8, vae, critic, preds, chunk)
+def sweep_maps(frames_u8, maps, max_values, gt, thresholds=SWEEP, crf_params=CRF_REF, p_floor=P_FLOOR):
+    """The tail of threshold_sweep for any non-negative map: normalised once (thr_iou at every threshold from its
+    histograms), the CRF once per threshold.  Returns [(t, thr_iou, crf_iou), ...]."""
     frames = _cuda(frames_u8, torch.uint8)
+    diff = _cuda(maps, torch.float32)
     gt_d = _cuda(_np(gt).astype(np.uint8), torch.uint8)
     hist = torch.zeros(2, 256, dtype=torch.int64, device=frames.device)
-    maxv = maxv.cpu()
+    maxv = _cuda(max_values, torch.float32).reshape(-1).cpu()
     _normalize(diff, maxv, 0, gt=gt_d, hist=hist)
     hist = _np(hist)
     out = []
@@ -272,6 +306,31 @@ def threshold_sweep(frames_u8, vae, gt, critic=None, preds=None, thresholds=SWEE
         _, crf_iou = _crf_counts(frames, m, gt_d, crf_params, p_floor)
         out.append((t, iou_from_hist(hist, t), crf_iou))
     return out
+
+
+def eval_frames(frames_u8, vae, gt, critic=None, preds=None, t=THRESHOLD, crf_params=CRF_REF, chunk=None,
+                p_floor=P_FLOOR, keep_device=False):
+    """eval_textured_frames (vae_utility.py:162-212) without the PIL frames.  frames_u8 (B,W,W,3) uint8, gt (B,W,W)
+    bool; either a critic (64x64 only, as the reference's) or explicit preds (B,).  The VAE runs in eval mode in
+    chunks of at most vae.max_batch; normalisation, threshold, CRF and IoU run over the whole set at once (eval_maps).
+    Returns a dict: preds, diff (fp32), max_values, diff_u8, thr_masks, crf_masks (host arrays), thr_iou, crf_iou,
+    bins, mean_max, hist (the (2,256) histograms of diff_u8).  keep_device=True adds "device": what render.video_frames
+    composes the pictures from, left on the device (frames, gt, preds, recon_one, recon_zero, diff_u8, thr_masks, crf_masks;
+    the masks as uint8 0/1)."""
+    p, diff, maxv, *recons = _infer(frames_u8, vae, critic, preds, chunk, keep_recons=keep_device)
+    r = eval_maps(frames_u8, diff, maxv, p, gt, t, crf_params, p_floor)
+    dev = r.pop("device")
+    if keep_device:
+        r["device"] = dict(dev, recon_one=recons[0], recon_zero=recons[1])
+    return r
+
+
+def threshold_sweep(frames_u8, vae, gt, critic=None, preds=None, thresholds=SWEEP, crf_params=CRF_REF, chunk=None,
+                    p_floor=P_FLOOR):
+    """The -thresh loop (vae.py:119-124): the VAE and critic run once, the masks are normalised once (thr_iou at every
+    threshold from its histograms), the CRF once per threshold (sweep_maps).  Returns [(t, thr_iou, crf_iou), ...]."""
+    p, diff, maxv = _infer(frames_u8, vae, critic, preds, chunk)
+    return sweep_maps(frames_u8, diff, maxv, gt, thresholds, crf_params, p_floor)
 
 
 def load_episode(x_npy, y_npy):
@@ -301,6 +360,12 @@ def parse_args(argv=None):
                     "frames.npy without PIL)")
     ap.add_argument("--gif", action="store_true", help=f"with --out: also DIR/video-threshold={THRESHOLD}.gif (needs PIL)")
     ap.add_argument("--no-text", dest="text", action="store_false", help="with --out: bare panels, no titles, IoUs or critic value")
+    ap.add_argument("--mask-source", choices=tuple(MASK_SOURCES), default="vae", help="where the masks come from: the VAE's "
+                    "difference masks (default), or the critic alone: the gradient of its logit with respect to the pixels, "
+                    "integrated gradients from the black frame, or occlusion sensitivity.  A critic source needs no --networks")
+    ap.add_argument("--ig-steps", type=int, default=IG_STEPS, help="critic-ig: passes from the black frame to the frame (2..256)")
+    ap.add_argument("--occlusion-patch", type=int, default=OCCLUSION_PATCH, choices=(4, 8, 16),
+                    help="critic-occlusion: side of the non-overlapping cover, filled with the episode's mean colour")
     args = ap.parse_args(argv)
     if not args.video:
         ap.error("-video is required (-dataset and -second are modes of critic_vae_amd.train; -inject and the folder "
@@ -311,6 +376,12 @@ def parse_args(argv=None):
         ap.error("--out writes the pictures of one evaluation: not with -thresh")
     if args.chunk < 1:
         ap.error("--chunk must be >= 1")
+    if args.mask_source != "vae" and args.out is not None:
+        ap.error("--out composes the 7-panel pictures, which have reconstruction panels: not with a critic --mask-source")
+    if args.mask_source != "vae" and args.second:
+        ap.error("--second selects a VAE: not with a critic --mask-source")
+    if not 2 <= args.ig_steps <= 256:
+        ap.error("--ig-steps must be in 2..256")
     if args.critic is None:
         args.critic = os.path.join(args.networks, CRITIC_FILE)
     return args
@@ -319,13 +390,25 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     from .critic import Critic
-    from .nets import VariationalAutoencoder
     frames, gt = load_episode(args.frames, args.gt)
-    vae = VariationalAutoencoder(max_batch=args.chunk).to("cuda")
-    from .train import load_networks
-    load_networks(vae, args.networks, second=args.second)
     critic = Critic(64, handle=Handle(64, args.chunk)).to("cuda")
     critic.load_state_dict(torch.load(args.critic, map_location="cpu"))
+    if args.mask_source != "vae":
+        preds, maps, maxv = critic_maps(frames, critic, MASK_SOURCES[args.mask_source], steps=args.ig_steps, patch=args.occlusion_patch,
+                                        chunk=args.chunk)
+        if args.thresh:
+            print("testing thresholds (thr):")
+            for t, thr_iou, crf_iou in sweep_maps(frames, maps, maxv, gt):
+                print(f"thr={t}, thr_iou={thr_iou}, crf_iou={crf_iou}")
+        else:
+            r = eval_maps(frames, maps, maxv, preds, gt)
+            print(f"thr_iou={r['thr_iou']}")
+            print(f"crf_iou={r['crf_iou']}")
+        return 0
+    from .nets import VariationalAutoencoder
+    from .train import load_networks
+    vae = VariationalAutoencoder(max_batch=args.chunk).to("cuda")
+    load_networks(vae, args.networks, second=args.second)
     if args.thresh:
         print("testing thresholds (thr):")
         for t, thr_iou, crf_iou in threshold_sweep(frames, vae, gt, critic=critic, chunk=args.chunk):

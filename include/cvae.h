@@ -540,6 +540,51 @@ int cvae_critic_score(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, c
                       const int64_t* idx_or_null, const float* critic_params, float* per_frame_or_null,
                       void* state_or_null, void* scratch, void* stream);
 
+/*
+ * Critic-side masks: what the critic alone says about a frame, to set beside the VAE's difference mask.  Three entries,
+ * each ONE launch of a persistent grid (at most one workgroup of 256 threads per compute unit, CVAE_PERSIST_MAXWG caps it),
+ * one workgroup per image at a time, every activation in on-chip memory.  They share these rules: x (B,3,64,64) fp32 in
+ * [0,1], 16-byte aligned; critic_params the 11 873 floats cvae_critic_forward reads; 1 <= batch <= 65 536, independent of
+ * the handle's max_batch; a handle of another width than 64: CVAE_EUNSUPPORTED; caller's buffers and stream, no allocation,
+ * no synchronisation, no floating-point atomics (a frame's results depend on that frame alone: the same inputs give the
+ * same bits whatever the grid); every argument is checked before any device access; every output given is fully written.
+ *
+ * cvae_critic_collect: Critic.forward(X, collect=True) (critic_net.py:44-59) in eval mode.  pred (B) is bit-equal to
+ * cvae_critic_forward's (the same device code).  The embeddings are the reference's list, NCHW fp32: e1 (B,8,32,32),
+ * e2 (B,8,16,16), e3 (B,8,8,8), e4 (B,16,4,4) behind the four max-pools, e5 (B,32,1,1) = features.14 after its ReLU.
+ * Any of e1..e5 may be null: nothing is written for it.
+ *
+ * cvae_critic_saliency: the gradient of z, the pre-sigmoid output of crit.4, with respect to the pixels (the logit, not p:
+ * a saturated sigmoid would scale the gradient of a confident frame to nothing before the set-wide normalisation of the
+ * masks).  The forward and the backward are cvae_critic_grad's device code with every element kept and unscaled (pred and
+ * decisions are bit-equal to cvae_critic_grad(keep = NULL, dropout_p = 0) on the same frames), plus the input gradient of
+ * features.0; no weight gradient is taken.
+ *   steps == 1: grad (B,3,64,64) = d z / d x at x.
+ *   steps == N, 2 <= N <= CVAE_CRITIC_IG_MAX_STEPS: integrated gradients from the black frame.  For k = 1 .. N in that
+ *     order the pass runs on x * ((float)k / (float)N) (one fp32 product per pixel) and its gradient is added to an fp32
+ *     accumulator per element; then grad = (sum * x) * (1.0f / N).  pred and decisions are those of the pass k = N, x itself.
+ *   map (B,64,64) = |grad_r| * 0.2989f + |grad_g| * 0.5870f + |grad_b| * 0.1140f (cvae_diff_grey's weights and order),
+ *   max_values (B) = the maximum of the frame's map: what cvae_diff_normalize takes.  grad and decisions
+ *   ((B, CVAE_CRITIC_DECISIONS) uint8, 4-byte aligned, the layout of cvae_critic_grad) may be null.
+ *
+ * cvae_critic_occlusion: occlusion sensitivity with non-overlapping patch x patch windows, patch 4, 8 or 16.  The frame is
+ * staged once; pred (B) is its value (cvae_critic_forward's bits).  Then for every patch in row-major order the patch is
+ * set aside, filled with (fill_r, fill_g, fill_b), the eval-mode forward runs again and the patch is put back:
+ * drop (B, 64/patch, 64/patch) = pred - (value of the occluded frame), one fp32 subtraction, where the occluded value is
+ * bit-equal to cvae_critic_forward on the frame with that patch filled by the host.  map (B,64,64) = max(drop, 0)
+ * replicated over its patch, max_values (B) = the maximum of the frame's map.  (64 / patch)^2 + 1 forwards per frame.
+ */
+#define CVAE_CRITIC_IG_MAX_STEPS 256
+int cvae_critic_collect(cvae_handle h, int32_t batch, const float* x, const float* critic_params, float* pred,
+                        float* e1_or_null, float* e2_or_null, float* e3_or_null, float* e4_or_null, float* e5_or_null,
+                        void* stream);
+int cvae_critic_saliency(cvae_handle h, int32_t batch, const float* x, const float* critic_params, int32_t steps,
+                         float* pred, float* grad_or_null, float* map, float* max_values, uint8_t* decisions_or_null,
+                         void* stream);
+int cvae_critic_occlusion(cvae_handle h, int32_t batch, const float* x, const float* critic_params, int32_t patch,
+                          float fill_r, float fill_g, float fill_b, float* pred, float* drop, float* map,
+                          float* max_values, void* stream);
+
 /* adjust_values + HWC->CHW of preprocess_observation (vae_utility.py:324-343): uint8 frames
  * (B,W,W,3) -> float (B,3,W,W) / 255, so that only 1 byte per value crosses PCIe. */
 int cvae_preprocess_u8(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, float* x, void* stream);
