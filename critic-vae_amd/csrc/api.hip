@@ -1138,6 +1138,49 @@ int cvae_dense_crf(cvae_handle h, int32_t B, const uint8_t* frames_hwc, const fl
     return launch_dense_crf(h->cfg.width, B, frames_hwc, prob1, *p, labels, q1, scratch, (hipStream_t)stream);
 }
 
+// ---- the CRF for a grid of variants (kernels in crf_grid.hip) ----
+int32_t cvae_crf_grid_group(cvae_handle h) {
+    if (!h) { cvae_set_error("cvae_crf_grid_group: null handle"); return CVAE_EINVAL; }
+    return crf_grid_group();
+}
+
+int64_t cvae_crf_grid_scratch_bytes(cvae_handle h, int32_t B, int32_t n_variants) {
+    if (!seg_batch_ok(h, B, "cvae_crf_grid_scratch_bytes")) return CVAE_EINVAL;
+    if (n_variants < 1 || n_variants > CVAE_CRF_GRID_MAX_VARIANTS) {
+        cvae_set_error("cvae_crf_grid_scratch_bytes: n_variants %d outside [1, %d]", n_variants, CVAE_CRF_GRID_MAX_VARIANTS); return CVAE_EINVAL;
+    }
+    return crf_grid_scratch_bytes(h->cfg.width, B, n_variants);
+}
+
+int cvae_crf_grid(cvae_handle h, int32_t B, const uint8_t* frames_hwc, const float* prob1, const uint8_t* diff_u8, const uint8_t* gt,
+                  float alpha, float beta, float gamma, const cvae_crf_variant* variants, int32_t n_variants, const int32_t* snaps,
+                  int32_t n_snaps, int64_t* counts, uint8_t* labels, float* q1, void* scratch, void* stream) {
+    const char* who = "cvae_crf_grid";
+    if (!seg_batch_ok(h, B, who)) return CVAE_EINVAL;
+    if (!frames_hwc || !variants || !snaps || !scratch) { cvae_set_error("%s: null frames, variants, snaps or scratch", who); return CVAE_EINVAL; }
+    if (n_variants < 1 || n_variants > CVAE_CRF_GRID_MAX_VARIANTS) { cvae_set_error("%s: n_variants %d outside [1, %d]", who, n_variants, CVAE_CRF_GRID_MAX_VARIANTS); return CVAE_EINVAL; }
+    if (n_snaps < 1 || n_snaps > CVAE_CRF_GRID_MAX_SNAPS) { cvae_set_error("%s: n_snaps %d outside [1, %d]", who, n_snaps, CVAE_CRF_GRID_MAX_SNAPS); return CVAE_EINVAL; }
+    if (!counts && !labels && !q1) { cvae_set_error("%s: no output requested (counts, labels and q1 are all null)", who); return CVAE_EINVAL; }
+    if (counts && !gt) { cvae_set_error("%s: counts need the ground truth", who); return CVAE_EINVAL; }
+    if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(gamma)) { cvae_set_error("%s: non-finite parameter", who); return CVAE_EINVAL; }
+    if (!(alpha > 0.f && beta > 0.f && gamma > 0.f)) { cvae_set_error("%s: alpha %g, beta %g, gamma %g must be > 0", who, alpha, beta, gamma); return CVAE_EINVAL; }
+    for (int k = 0; k < n_variants; ++k) {
+        const cvae_crf_variant& v = variants[k];
+        if (v.thr < -1 || v.thr > 255) { cvae_set_error("%s: variant %d: thr %d outside [-1, 255]", who, k, v.thr); return CVAE_EINVAL; }
+        if (v.thr < 0 ? !prob1 : !diff_u8) { cvae_set_error("%s: variant %d (thr %d) needs the %s plane, which is null", who, k, v.thr, v.thr < 0 ? "prob1" : "diff_u8"); return CVAE_EINVAL; }
+        if (!std::isfinite(v.p_floor) || !std::isfinite(v.w1) || !std::isfinite(v.w2)) { cvae_set_error("%s: variant %d: non-finite parameter", who, k); return CVAE_EINVAL; }
+        if (v.w1 < 0.f || v.w2 < 0.f) { cvae_set_error("%s: variant %d: weights w1 %g, w2 %g must be >= 0", who, k, v.w1, v.w2); return CVAE_EINVAL; }
+        if (!(v.p_floor > 0.f && v.p_floor <= 1.f)) { cvae_set_error("%s: variant %d: p_floor %g outside (0, 1]", who, k, v.p_floor); return CVAE_EINVAL; }
+    }
+    for (int s = 0; s < n_snaps; ++s) {
+        if (snaps[s] < 0 || snaps[s] > 10000) { cvae_set_error("%s: snapshot %d outside [0, 10000]", who, snaps[s]); return CVAE_EINVAL; }
+        if (s > 0 && snaps[s] <= snaps[s - 1]) { cvae_set_error("%s: snapshots must ascend strictly (%d after %d)", who, snaps[s], snaps[s - 1]); return CVAE_EINVAL; }
+    }
+    if (((uintptr_t)scratch & 255) != 0) { cvae_set_error("%s: scratch not 256-byte aligned", who); return CVAE_EINVAL; }
+    return launch_crf_grid(h->cfg.width, B, frames_hwc, prob1, diff_u8, gt, alpha, beta, gamma, variants, n_variants, snaps, n_snaps,
+                           counts, labels, q1, scratch, (hipStream_t)stream);
+}
+
 int cvae_diff_normalize(cvae_handle h, int32_t B, const float* diff, double mean_max, double diff_factor, int32_t thr,
                         const uint8_t* gt, uint8_t* diff_u8, uint8_t* mask, int64_t* counts, int64_t* hist, void* stream) {
     if (!seg_batch_ok(h, B, "cvae_diff_normalize")) return CVAE_EINVAL;

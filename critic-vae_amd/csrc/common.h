@@ -426,6 +426,12 @@ int launch_dense_crf(int width, int B, const uint8_t* frames, const float* prob1
 int launch_diff_normalize(int width, int B, const float* diff, double mean_max, double factor, int thr, const uint8_t* gt,
                           uint8_t* u8, uint8_t* mask, int64_t* counts, int64_t* hist, hipStream_t st);
 int launch_mask_counts(int width, int B, const uint8_t* mask, const uint8_t* gt, int64_t* counts, hipStream_t st);
+// crf_grid.hip
+int crf_grid_group();
+int64_t crf_grid_scratch_bytes(int width, int B, int K);
+int launch_crf_grid(int width, int B, const uint8_t* frames, const float* prob1, const uint8_t* u8, const uint8_t* gt, float alpha,
+                    float beta, float gamma, const struct cvae_crf_variant* var, int K, const int32_t* snaps, int n_snaps,
+                    int64_t* counts, uint8_t* labels, float* q1, void* scratch, hipStream_t st);
 // render.hip
 int launch_compose_frames(int width, int B, int n_panels, const struct cvae_panel* panels, int ih, int clamp, const uint8_t* overlay,
                           const uint8_t* atlas, int n_labels, int lh, int lw, const int32_t* label_idx, int lx, int ly,

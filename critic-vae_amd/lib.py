@@ -33,6 +33,14 @@ class CrfParams(C.Structure):
                 ("gamma", C.c_float), ("p_floor", C.c_float), ("iterations", C.c_int32)]
 
 
+class CrfVariant(C.Structure):
+    """cvae_crf_variant (include/cvae.h): one variant of cvae_crf_grid: thr -1 = the prob1 plane, 0..255 = diff_u8 > thr."""
+    _fields_ = [("thr", C.c_int32), ("p_floor", C.c_float), ("w1", C.c_float), ("w2", C.c_float)]
+
+
+CRF_GRID_MAX_VARIANTS, CRF_GRID_MAX_SNAPS = 64, 8       # CVAE_CRF_GRID_MAX_VARIANTS, CVAE_CRF_GRID_MAX_SNAPS
+
+
 class GuardRecord(C.Structure):
     """cvae_guard_record (include/cvae.h): the decision record at offset 0 of a guard state."""
     _fields_ = [("apply", C.c_int32), ("nonfinite", C.c_uint32), ("coef", C.c_float), ("norm", C.c_float),
@@ -220,6 +228,10 @@ _SIGS = {
     "cvae_mask_counts": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
     "cvae_crf_scratch_bytes": (_i64, [_p, _i32]),
     "cvae_dense_crf": (C.c_int, [_p, _i32, _p, _p, C.POINTER(CrfParams), _p, _p, _p, _p]),
+    "cvae_crf_grid_group": (_i32, [_p]),
+    "cvae_crf_grid_scratch_bytes": (_i64, [_p, _i32, _i32]),
+    "cvae_crf_grid": (C.c_int, [_p, _i32, _p, _p, _p, _p, C.c_float, C.c_float, C.c_float, C.POINTER(CrfVariant), _i32,
+                                C.POINTER(C.c_int32), _i32, _p, _p, _p, _p, _p]),
     "cvae_compose_frames": (C.c_int, [_p, _i32, _i32, C.POINTER(Panel), _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _p, _p]),
     "cvae_inject_zcat": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p]),
     "cvae_probe_config": (C.c_int, [_p, C.c_uint32]),
@@ -776,6 +788,32 @@ class Handle:
         assert scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= self.crf_scratch_bytes(B)
         self._check(self.lib.cvae_dense_crf(self.h, B, self._u8(frames_u8, "frames"), _ptr(prob1), C.byref(params),
                                             self._u8(labels, "labels"), _ptr(q1), scratch.data_ptr(), _stream()))
+
+    def crf_grid_group(self):
+        """variants per pair pass of cvae_crf_grid"""
+        return self.lib.cvae_crf_grid_group(self.h)
+
+    def crf_grid_scratch_bytes(self, B, n_variants):
+        n = self.lib.cvae_crf_grid_scratch_bytes(self.h, B, n_variants)
+        if n < 0:
+            raise CvaeError(f"cvae_crf_grid_scratch_bytes: {self.lib.cvae_last_error().decode()}")
+        return n
+
+    def crf_grid(self, B, frames_u8, prob1, diff_u8, gt, kernel, variants, snaps, counts, labels, q1, scratch):
+        """kernel (alpha, beta, gamma); variants [(thr, p_floor, w1, w2), ...]; snaps ascending iteration counts (host
+        values, read before the call returns); counts (len(snaps), K, B, 3) int64, labels (K,B,W,W) uint8, q1 (K,B,W,W)
+        fp32 or None; scratch: a device tensor of at least crf_grid_scratch_bytes(B, K) bytes.  Every check is the library's."""
+        variants, snaps = list(variants), list(snaps)
+        if 1 <= len(variants) <= CRF_GRID_MAX_VARIANTS:
+            assert scratch.is_cuda and scratch.is_contiguous() and \
+                scratch.numel() * scratch.element_size() >= self.crf_grid_scratch_bytes(B, len(variants))
+        va = (CrfVariant * max(1, len(variants)))(*[CrfVariant(int(t), float(pf), float(w1), float(w2)) for t, pf, w1, w2 in variants])
+        sa = (C.c_int32 * max(1, len(snaps)))(*[int(s) for s in snaps])
+        alpha, beta, gamma = (float(x) for x in kernel)
+        self._check(self.lib.cvae_crf_grid(self.h, B, self._u8(frames_u8, "frames"), _ptr(prob1), self._u8(diff_u8, "diff_u8"),
+                                           self._u8(gt, "gt"), alpha, beta, gamma, va, len(variants), sa, len(snaps),
+                                           self._i64(counts, "counts"), self._u8(labels, "labels"), _ptr(q1),
+                                           scratch.data_ptr(), _stream()))
 
     # ---- the reference's pictures (get_final_frame / get_injected_img, vae_utility.py:240-322; render.py) ----
     def compose_frames(self, B, panels, row_offset, out, overlay=None, atlas=None, label_idx=None, label_xy=(0, 0), clamp=False):

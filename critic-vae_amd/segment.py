@@ -13,7 +13,11 @@ permutohedral lattice.  Its unary clamps probabilities at `p_floor` (default 1e-
 unary_from_softmax helper); whether SimpleCRF clamps a 0/1 mask the same way has not been checked against SimpleCRF.
 
     python -m critic_vae_amd.segment -video [-thresh] --frames X.npy --gt Y.npy --networks DIR [--critic CKPT]
-                                     [--out DIR [--gif] [--no-text]]
+                                     [--out DIR [--gif] [--no-text]] [--thr T] [--crf W1,ALPHA,BETA,W2,GAMMA,IT] [--p-floor F]
+    python -m critic_vae_amd.segment -video -search [--grid-thr 0,10,...] [--grid-w1 ...] ... [--skip N] [--top N]
+
+`-search` is the grid search the reference's crf() is written as (lists for every parameter, the IoU per tuple): every
+threshold and every (w1, w2, p_floor) of one (alpha, beta, gamma) ride on one pairwise pass (crf_search / cvae_crf_grid).
 
 `--mask-source critic-grad | critic-ig | critic-occlusion` builds the masks from the critic alone (critic_maps: the
 gradient of its logit with respect to the pixels, integrated gradients, occlusion sensitivity) and sends them through the
@@ -141,6 +145,124 @@ def mask_counts(mask, gt):
     c = torch.empty(mask.shape[0], 3, dtype=torch.int64, device=mask.device)
     _handle(mask.shape[-1]).mask_counts(mask.shape[0], mask, gt, c)
     return c
+
+
+# ---- the grid search of crf() (vae_utility.py:22-54: lists for every parameter, the IoU per tuple, a `skip`) ----
+GRID_SCRATCH_LIMIT = 4 << 30            # crf_search's default frame chunk keeps a call's scratch under this many bytes
+PROB1 = -1                              # a variant's thr that selects the prob1 plane instead of a threshold of diff_u8
+
+
+def crf_grid(frames_u8, gt, kernel, variants, its=(CRF_REF[5],), prob1=None, diff_u8=None, labels=False, q1=False):
+    """cvae_crf_grid: the dense CRF for every variant (thr, p_floor, w1, w2) of one frame set under one kernel
+    (alpha, beta, gamma); thr = -1 takes `prob1` (B,W,W) fp32, thr in 0..255 the mask `diff_u8` > thr.  `its`: ascending
+    iteration counts; with gt, counts (len(its), K, B, 3) int64 hold the per-frame (tp, fn, fp) after each.  Returns the counts
+    (None without gt) on the device; with labels and / or q1 a tuple (counts, labels (K,B,W,W) bool, Q(1) (K,B,W,W) fp32) of
+    what was asked for, both at the last of `its`."""
+    frames = _cuda(frames_u8, torch.uint8)
+    B, W = frames.shape[0], frames.shape[1]
+    assert frames.shape == (B, W, W, 3), tuple(frames.shape)
+    dev = frames.device
+    gt_d = None if gt is None else _cuda(gt if torch.is_tensor(gt) else _np(gt).astype(np.uint8), torch.uint8)
+    p1 = None if prob1 is None else _cuda(prob1, torch.float32)
+    u8 = None if diff_u8 is None else _cuda(diff_u8, torch.uint8)
+    for t in (gt_d, p1, u8):
+        assert t is None or t.shape == (B, W, W), tuple(t.shape)
+    variants, its = [tuple(v) for v in variants], [int(i) for i in its]
+    K = len(variants)
+    h = _handle(W)
+    counts = torch.empty(len(its), K, B, 3, dtype=torch.int64, device=dev) if gt_d is not None else None
+    lab = torch.empty(K, B, W, W, dtype=torch.uint8, device=dev) if labels else None
+    q = torch.empty(K, B, W, W, device=dev) if q1 else None
+    scratch = torch.empty(h.crf_grid_scratch_bytes(B, K), dtype=torch.uint8, device=dev)
+    h.crf_grid(B, frames, p1, u8, gt_d, kernel, variants, its, counts, lab, q, scratch)
+    if not labels and not q1:
+        return counts
+    return (counts,) + ((lab.bool(),) if labels else ()) + ((q,) if q1 else ())
+
+
+def grid_plan(thresholds=SWEEP, w1=(CRF_REF[0],), alpha=(CRF_REF[1],), beta=(CRF_REF[2],), w2=(CRF_REF[3],),
+              gamma=(CRF_REF[4],), it=(CRF_REF[5],), p_floor=(P_FLOOR,)):
+    """The grid as calls of crf_grid (host only).  Returns (rows, calls): rows, in grid order (thr, p_floor, then the
+    reference's nesting w1, alpha, beta, w2, gamma, it), are (thr, (w1, alpha, beta, w2, gamma, it), p_floor, call, variant,
+    snapshot); calls, in order of first use, are ((alpha, beta, gamma), [(thr, p_floor, w1, w2), ...], sorted its): one per
+    kernel, every thresholds x p_floor x w1 x w2 a variant, every `it` a snapshot."""
+    its = sorted(set(int(i) for i in it))
+    calls, call_of, var_of, rows = [], {}, [], []
+    for t in thresholds:
+        for pf in p_floor:
+            for a in w1:
+                for b in alpha:
+                    for c in beta:
+                        for d in w2:
+                            for e in gamma:
+                                kern = (float(b), float(c), float(e))
+                                if kern not in call_of:
+                                    call_of[kern] = len(calls)
+                                    calls.append((kern, [], its))
+                                    var_of.append({})
+                                ci = call_of[kern]
+                                var = (int(t), float(pf), float(a), float(d))
+                                if var not in var_of[ci]:
+                                    var_of[ci][var] = len(calls[ci][1])
+                                    calls[ci][1].append(var)
+                                for i in it:
+                                    rows.append((t, (a, b, c, d, e, i), pf, ci, var_of[ci][var], its.index(int(i))))
+    return rows, calls
+
+
+def rank_rows(rows):
+    """Best crf_iou first; ties of the 3-place value go to the larger unrounded tp / (tp + fn + fp) (1 for an empty union),
+    then to grid order (the sort is stable).  The reference sorts ascending and discards the result."""
+    def ratio(r):
+        tp, fn, fp = r["counts"]
+        return tp / (tp + fn + fp) if tp + fn + fp else 1.0
+    return sorted(rows, key=lambda r: (-r["crf_iou"], -ratio(r)))
+
+
+def _grid_chunk(h, B, K, limit=GRID_SCRATCH_LIMIT):
+    per_frame = h.crf_grid_scratch_bytes(1, K)
+    return max(1, min(B, (limit - 4096) // per_frame))
+
+
+def crf_search(frames_u8, maps, max_values, gt, thresholds=SWEEP, w1=(CRF_REF[0],), alpha=(CRF_REF[1],), beta=(CRF_REF[2],),
+               w2=(CRF_REF[3],), gamma=(CRF_REF[4],), it=(CRF_REF[5],), p_floor=(P_FLOOR,), skip=1, chunk=None):
+    """The grid search of the reference's crf() over thresholds and CRF parameters, for any non-negative map (B,W,W) with its
+    per-frame maxima (as sweep_maps takes them).  `skip` evaluates frames [::skip], as crf() does.  The masks are normalised
+    once (thr_iou from the histograms); per (alpha, beta, gamma) and per chunk of `chunk` frames (default: as many as keep the
+    scratch under 4 GiB) ONE crf_grid call serves every thresholds x p_floor x w1 x w2 as a variant and every `it` as a
+    snapshot.  Counts are summed over the frames on the device and read once.  Returns a list of dicts {"thr", "params":
+    (w1, alpha, beta, w2, gamma, it), "p_floor", "thr_iou", "crf_iou", "counts": (tp, fn, fp)}, best crf_iou first (rank_rows)."""
+    skip = int(skip)
+    if skip < 1:
+        raise ValueError(f"skip {skip} must be >= 1")
+    frames = _cuda(frames_u8, torch.uint8)[::skip].contiguous()
+    diff = _cuda(maps, torch.float32)[::skip].contiguous()
+    gt_d = _cuda(_np(gt).astype(np.uint8), torch.uint8)[::skip].contiguous()
+    maxv = _cuda(max_values, torch.float32).reshape(-1)[::skip].cpu()
+    B, W = frames.shape[0], frames.shape[1]
+    rows, calls = grid_plan(thresholds, w1, alpha, beta, w2, gamma, it, p_floor)
+    hist = torch.zeros(2, 256, dtype=torch.int64, device=frames.device)
+    u8, _, _, _ = _normalize(diff, maxv, 0, gt=gt_d, hist=hist)
+    h = _handle(W)
+    sums = []
+    for kern, variants, its in calls:
+        total = torch.zeros(len(its), len(variants), 3, dtype=torch.int64, device=frames.device)
+        for v0 in range(0, len(variants), 64):                            # CVAE_CRF_GRID_MAX_VARIANTS per call
+            vs = variants[v0:v0 + 64]
+            step = int(chunk) if chunk else _grid_chunk(h, B, len(vs))
+            for s in range(0, B, step):
+                e = min(B, s + step)
+                total[:, v0:v0 + len(vs)] += crf_grid(frames[s:e], gt_d[s:e], kern, vs, its, diff_u8=u8[s:e]).sum(2)
+        sums.append(total)
+    host = torch.cat([t.reshape(-1) for t in sums] + [hist.reshape(-1)]).cpu().numpy()          # the one read
+    sums = [a.reshape(t.shape) for a, t in zip(np.split(host[:-512], np.cumsum([t.numel() for t in sums])[:-1]), sums)]
+    hist = host[-512:].reshape(2, 256)
+    out = []
+    for t, params, pf, ci, vi, si in rows:
+        c = tuple(int(x) for x in sums[ci][si, vi])
+        out.append({"thr": t, "params": params, "p_floor": pf, "thr_iou": iou_from_hist(hist, t), "crf_iou": iou_from_counts(*c),
+                    "counts": c})
+    return rank_rows(out)
 
 
 # ---- per-critic-value bins (save_bin_info / save_bin_info_file, vae_utility.py:112-146) ----
@@ -366,7 +488,47 @@ def parse_args(argv=None):
     ap.add_argument("--ig-steps", type=int, default=IG_STEPS, help="critic-ig: passes from the black frame to the frame (2..256)")
     ap.add_argument("--occlusion-patch", type=int, default=OCCLUSION_PATCH, choices=(4, 8, 16),
                     help="critic-occlusion: side of the non-overlapping cover, filled with the episode's mean colour")
+    ap.add_argument("--thr", type=int, default=THRESHOLD, help="threshold of the single evaluation (0..255)")
+    ap.add_argument("--crf", default=None, metavar="W1,ALPHA,BETA,W2,GAMMA,IT", help="CRF parameters of the single evaluation "
+                    "and of -thresh (default: the reference's " + ",".join(str(v) for v in CRF_REF) + ")")
+    ap.add_argument("--p-floor", type=float, default=P_FLOOR, help="unary floor of the single evaluation and of -thresh")
+    ap.add_argument("-search", action="store_true", help="grid search over thresholds and CRF parameters (the --grid-* lists), "
+                    "best crf_iou first")
+    ap.add_argument("--top", type=int, default=10, help="-search: rows to print")
+    ap.add_argument("--skip", type=int, default=1, help="-search: evaluate frames [::N], as the reference's crf(skip=N)")
+    ap.add_argument("--grid-thr", default=",".join(str(t) for t in SWEEP), help="-search: thresholds, a comma list")
+    for name, ref in zip(("w1", "alpha", "beta", "w2", "gamma", "it"), CRF_REF):
+        ap.add_argument(f"--grid-{name}", default=str(ref), help=f"-search: {name} values, a comma list")
+    ap.add_argument("--grid-p-floor", default=str(P_FLOOR), help="-search: unary floors, a comma list")
     args = ap.parse_args(argv)
+
+    def numbers(text, kind, flag):
+        try:
+            vals = tuple(kind(v) for v in text.split(","))
+        except ValueError:
+            ap.error(f"{flag}: {text!r} is not a comma list of {kind.__name__} values")
+        return vals
+    if args.crf is None:
+        args.crf = CRF_REF
+    else:
+        v = numbers(args.crf, float, "--crf")
+        if len(v) != 6 or v[5] != int(v[5]):
+            ap.error("--crf takes W1,ALPHA,BETA,W2,GAMMA,IT with an integer IT")
+        args.crf = v[:5] + (int(v[5]),)
+    if not 0 <= args.thr <= 255:
+        ap.error("--thr must be in 0..255")
+    args.grid = {"thresholds": numbers(args.grid_thr, int, "--grid-thr"), "it": numbers(args.grid_it, int, "--grid-it"),
+                 "p_floor": numbers(args.grid_p_floor, float, "--grid-p-floor")}
+    for name in ("w1", "alpha", "beta", "w2", "gamma"):
+        args.grid[name] = numbers(getattr(args, f"grid_{name}"), float, f"--grid-{name}")
+    if args.search and (args.out is not None or args.thresh):
+        ap.error("-search prints the table of a grid: not with --out or -thresh")
+    if args.search and (args.thr != THRESHOLD or args.crf != CRF_REF or args.p_floor != P_FLOOR):
+        ap.error("-search takes its values from the --grid-* lists: not with --thr, --crf or --p-floor")
+    if args.thresh and args.thr != THRESHOLD:
+        ap.error("-thresh sweeps the thresholds: not with --thr")
+    if args.skip < 1 or args.top < 1:
+        ap.error("--skip and --top must be >= 1")
     if not args.video:
         ap.error("-video is required (-dataset and -second are modes of critic_vae_amd.train; -inject and the folder "
                  "evaluation of -evalsecond are python -m critic_vae_amd.render)")
@@ -387,6 +549,15 @@ def parse_args(argv=None):
     return args
 
 
+def print_search(rows, top):
+    """The table of -search: the best `top` rows of crf_search."""
+    print(f"grid search: {len(rows)} candidates, best crf_iou first")
+    for r in rows[:top]:
+        w1, alpha, beta, w2, gamma, it = r["params"]
+        print(f"thr={r['thr']}, w1={w1:g}, alpha={alpha:g}, beta={beta:g}, w2={w2:g}, gamma={gamma:g}, it={it}, "
+              f"p_floor={r['p_floor']:g}, thr_iou={r['thr_iou']}, crf_iou={r['crf_iou']}")
+
+
 def main(argv=None):
     args = parse_args(argv)
     from .critic import Critic
@@ -396,12 +567,14 @@ def main(argv=None):
     if args.mask_source != "vae":
         preds, maps, maxv = critic_maps(frames, critic, MASK_SOURCES[args.mask_source], steps=args.ig_steps, patch=args.occlusion_patch,
                                         chunk=args.chunk)
-        if args.thresh:
+        if args.search:
+            print_search(crf_search(frames, maps, maxv, gt, skip=args.skip, **args.grid), args.top)
+        elif args.thresh:
             print("testing thresholds (thr):")
-            for t, thr_iou, crf_iou in sweep_maps(frames, maps, maxv, gt):
+            for t, thr_iou, crf_iou in sweep_maps(frames, maps, maxv, gt, crf_params=args.crf, p_floor=args.p_floor):
                 print(f"thr={t}, thr_iou={thr_iou}, crf_iou={crf_iou}")
         else:
-            r = eval_maps(frames, maps, maxv, preds, gt)
+            r = eval_maps(frames, maps, maxv, preds, gt, args.thr, args.crf, args.p_floor)
             print(f"thr_iou={r['thr_iou']}")
             print(f"crf_iou={r['crf_iou']}")
         return 0
@@ -409,20 +582,25 @@ def main(argv=None):
     from .train import load_networks
     vae = VariationalAutoencoder(max_batch=args.chunk).to("cuda")
     load_networks(vae, args.networks, second=args.second)
-    if args.thresh:
+    if args.search:
+        _, diff, maxv = _infer(frames, vae, critic, None, args.chunk)
+        print_search(crf_search(frames, diff, maxv, gt, skip=args.skip, **args.grid), args.top)
+    elif args.thresh:
         print("testing thresholds (thr):")
-        for t, thr_iou, crf_iou in threshold_sweep(frames, vae, gt, critic=critic, chunk=args.chunk):
+        for t, thr_iou, crf_iou in threshold_sweep(frames, vae, gt, critic=critic, crf_params=args.crf, chunk=args.chunk,
+                                                   p_floor=args.p_floor):
             print(f"thr={t}, thr_iou={thr_iou}, crf_iou={crf_iou}")
     else:
-        r = eval_frames(frames, vae, gt, critic=critic, chunk=args.chunk, keep_device=args.out is not None)
+        r = eval_frames(frames, vae, gt, critic=critic, t=args.thr, crf_params=args.crf, chunk=args.chunk, p_floor=args.p_floor,
+                        keep_device=args.out is not None)
         print(f"thr_iou={r['thr_iou']}")
         print(f"crf_iou={r['crf_iou']}")
         if args.out is not None:
             from . import render
-            pictures = render.video_frames(r, text=args.text).cpu().numpy()
+            pictures = render.video_frames(r, text=args.text, threshold=args.thr).cpu().numpy()
             render.save_pngs(args.out, pictures)
             if args.gif:
-                render.save_gif(os.path.join(args.out, f"video-threshold={THRESHOLD}.gif"), pictures)
+                render.save_gif(os.path.join(args.out, f"video-threshold={args.thr}.gif"), pictures)
     return 0
 
 

@@ -773,6 +773,41 @@ int cvae_dense_crf(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, cons
                    const cvae_crf_params* params, uint8_t* labels, float* q1_or_null, void* scratch,
                    void* stream);
 
+/* The grid search crf() is written as (vae_utility.py:22-54: lists for every parameter, the IoU per tuple): the dense
+ * CRF above for n_variants VARIANTS of one frame set in one call.  All variants share (alpha, beta, gamma), hence the
+ * kernels and both normalisers, which are computed once; the bilateral kernel value of a pixel pair is computed once per
+ * pass and applied to every variant of a group of cvae_crf_grid_group(h) variants (more run as consecutive groups over
+ * the same scratch).  A variant is its unary and its weights: thr == -1 takes prob1 (B,W,W) fp32 as cvae_dense_crf
+ * does, thr in 0..255 takes the mask diff_u8 > thr of diff_u8 (B,W,W) uint8 as prob1 = 1.0 / 0.0; p_floor, w1, w2 as in
+ * cvae_crf_params.  The equations, and per variant the summation order of the bilateral sum, are cvae_dense_crf's; the
+ * results agree with it to rounding, not bitwise (this entry fixes its fused operations).
+ * `snaps`: n_snaps (1..8) strictly ascending iteration counts, each in [0, 10000]; the last is the number of updates
+ * run, 0 stands for the labels of softmax(-u).  After each listed iteration counts_or_null (n_snaps, n_variants, B, 3)
+ * int64 receives per (snapshot, variant, frame) the (tp, fn, fp) of get_iou(gt, label) with label = Q(1) > Q(0) (the buffer
+ * is cleared by the call; integer atomics, order-free; gt (B,W,W) uint8, nonzero = set).  At the LAST snapshot only:
+ * labels_or_null (n_variants, B, W, W) uint8 and q1_or_null (n_variants, B, W, W) fp32; with both null no mask is ever
+ * written (the search needs the counts alone).
+ * Deterministic: the bits of one (frame, variant) result depend on that frame and that variant alone, not on the batch,
+ * the frame's position, the number of variants, the variant's slot in its group or the group.
+ * `variants` and `snaps` are HOST arrays, read before the call returns.  Ranges as for cvae_dense_crf, all finite.
+ * CVAE_EINVAL before any device access, every output untouched: a variant whose plane (prob1 / diff_u8) is null; thr
+ * outside -1..255; counts without gt; no output at all; snapshots unsorted, repeated or out of range; n_variants outside
+ * 1..64; n_snaps outside 1..8; a non-finite value; scratch null or not 256-byte aligned.
+ * `scratch`: cvae_crf_grid_scratch_bytes(h, batch, n_variants) bytes of device memory (host-only query; -1 for a bad
+ * handle, batch or n_variants).  cvae_crf_grid_group is host-only too (-1 for a null handle). */
+typedef struct cvae_crf_variant {
+    int32_t thr;             /* -1: prob1; 0..255: diff_u8 > thr */
+    float p_floor, w1, w2;
+} cvae_crf_variant;
+#define CVAE_CRF_GRID_MAX_VARIANTS 64
+#define CVAE_CRF_GRID_MAX_SNAPS 8
+int32_t cvae_crf_grid_group(cvae_handle h);
+int64_t cvae_crf_grid_scratch_bytes(cvae_handle h, int32_t batch, int32_t n_variants);
+int cvae_crf_grid(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, const float* prob1_or_null,
+                  const uint8_t* diff_u8_or_null, const uint8_t* gt_or_null, float alpha, float beta, float gamma,
+                  const cvae_crf_variant* variants, int32_t n_variants, const int32_t* snaps, int32_t n_snaps,
+                  int64_t* counts_or_null, uint8_t* labels_or_null, float* q1_or_null, void* scratch, void* stream);
+
 /* ---------------------------------------------------------------------------------------- *
  * The reference's pictures: the PNG strips of image_evaluate (vae.py:68-108) and get_injected_img
  * (vae_utility.py:240-254) and the 7-panel video frames of get_final_frame (vae_utility.py:286-322).
