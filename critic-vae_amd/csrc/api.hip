@@ -1382,6 +1382,21 @@ int cvae_op_conv_wgrad_plan(cvae_handle h, int32_t layer, int32_t B, int32_t* ou
     return CVAE_OK;
 }
 
+// include/cvae.h: the same of the fp32 kernels, from the launchers' own split functions (host logic only, no handle, no device access)
+int32_t cvae_op_conv_wgrad_plan_f32(int32_t width, int32_t layer, int32_t B, int32_t num_cus, int32_t* out) {
+    if ((width != 64 && width != 128) || layer < 0 || layer > 8 || B < 1 || num_cus < 1 || !out) {
+        cvae_set_error("cvae_op_conv_wgrad_plan_f32: width %d not 64 / 128, layer %d outside [0, 8], batch %d or compute units %d below 1, or null pointer",
+                       width, layer, B, num_cus);
+        return CVAE_EINVAL;
+    }
+    int plan[3] = {0, 0, 0};
+    RC(layer == 0 || layer == 8 ? thin_wgrad_plan_f32(layer, width, B, plan)
+       : layer >= 5             ? conv_up_wgrad_plan_f32(layer, width, B, num_cus, plan)
+                                : conv_wgrad_plan_f32(layer, width, B, plan));
+    for (int i = 0; i < 3; ++i) out[i] = plan[i];
+    return CVAE_OK;
+}
+
 // the statistics half of cvae_op_bn_pool_act_fwd, on partial rows of `tiles_per_partial` tiles each
 int cvae_op_bn_fwd_finalize(cvae_handle h, int32_t layer, int32_t B, const float* bn_partials, int32_t tiles_per_partial,
                             const float* gamma, const float* beta, float* run_mean, float* run_var, float* coef,

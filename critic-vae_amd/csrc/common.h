@@ -299,6 +299,10 @@ int launch_up_wgrad_bf16_main(int layer, int width, int B, const float* in, cons
 // (tiles, splits, tiles per split) of the bf16 weight-gradient kernels at a batch, from the launchers' own arithmetic (no launch; layers 5..7 ask the device's CU count)
 int conv_wgrad_bf16_plan(int layer, int width, int B, int plan[3]);       // layers 1..4
 int conv_up_wgrad_bf16_plan(int layer, int width, int B, int plan[3]);    // layers 5..7
+// the same of the fp32 kernels: layers 1..4 (conv_wgrad.hip), 5..7 on a device of `cus` compute units (conv_up.hip), 0 and 8 (conv_thin.hip).  No device access.
+int conv_wgrad_plan_f32(int layer, int width, int B, int plan[3]);
+int conv_up_wgrad_plan_f32(int layer, int width, int B, int cus, int plan[3]);
+int thin_wgrad_plan_f32(int layer, int width, int B, int plan[3]);
 // bn.hip
 int bn_num_tiles(int layer, int width, int B);
 int launch_bn_fwd_finalize(int layer, int width, int B, const float* bnpart, const float* gamma,

@@ -817,11 +817,24 @@ int launch_e1_fwd(int width, int B, const float* x, const float* w, const float*
     return 0;
 }
 
+static int d4_splits(int width, int B, int* tps, bool bf16io);
+static int e1_splits(int width, int B, int* tps, bool bf16 = false) {
+    return thin_splits(B * (width / 4) * (width / 32), tps, bf16 ? E1W_OCC * cvae_num_cus() : 512);
+}
+// (tiles, splits, tiles per split) of the fp32 E1 weight-gradient launch (layer 0) and of the fp32 D4 backward launch (layer 8) at a
+// batch, from the launchers' own split functions: host arithmetic only (the fp32 forms do not ask the device)
+int thin_wgrad_plan_f32(int layer, int width, int B, int plan[3]) {
+    if ((width != 64 && width != 128) || (layer != 0 && layer != 8)) { cvae_set_error("thin_wgrad_plan_f32: unsupported layer %d at width %d", layer, width); return -2; }
+    plan[0] = layer == 0 ? B * (width / 4) * (width / 32) : B * (width / 16) * (width / 32);
+    plan[1] = layer == 0 ? e1_splits(width, B, &plan[2]) : d4_splits(width, B, &plan[2], false);
+    return 0;
+}
+
 int launch_e1_wgrad(int width, int B, const float* x, const float* dy, float* dw, float* dbias, float* ws, hipStream_t st, bool bf16,
                     const float* const* fuse, const float* xp) {
     if (width != 64 && width != 128) { cvae_set_error("e1_wgrad: width %d unsupported", width); return -2; }
     int tps; const int tiles = B * (width / 4) * (width / 32);
-    const int S = thin_splits(tiles, &tps, bf16 ? E1W_OCC * cvae_num_cus() : 512);
+    const int S = e1_splits(width, B, &tps, bf16);
     ThinWgradArgs a{x, nullptr, dy, nullptr, nullptr, ws, B, tiles, tps, xp};
     // fuse = {y0, a0, d_a0, coef0, bcoef0, w1, b1}: block 0's BatchNorm/pool/ReLU backward is applied while staging (no dy
     // tensor); the bf16 kernel recomputes y0 from x, w1, b1 and never reads fuse[0]
@@ -1440,7 +1453,7 @@ static_assert(D4_BWD_BF16_SMEM >= (20 * D4P_IW * 4 + 128 * 32) * 2, "staging buf
 
 static constexpr int D4_BWD_SMEM = (3 * 720 + 128 * 32 + 128 * 77 + 32 + 76 * 32) * 4;
 
-static int d4_splits(int width, int B, int* tps, bool bf16io = false) {
+static int d4_splits(int width, int B, int* tps, bool bf16io) {
     return thin_splits(B * (width / 16) * (width / 32), tps, bf16io ? D4B_OCC * cvae_num_cus() : 512);
 }
 // ws of launch_d4_bwd = [S*3072 split-K slab | B*3 plane sums of dOut]
@@ -1454,8 +1467,8 @@ int64_t d4_bwd_ws_floats(int width, int B) {
 int launch_d4_fwd(int width, int B, const float* in, const float* w, const float* bias, float* recon, hipStream_t st, bool bf16io) {
     // persistent: 16 x 32-output tiles; bf16 mode 4 workgroups per CU (18 KB of LDS), fp32 2 (their prologue builds the 72 collapsed
     // weight values of every lane: fewer, longer-lived workgroups); each loops over its share
-    const int want = (bf16io ? 4 : 2) * cvae_num_cus();
-    const int tiles = B * (width / 16) * (width / 32), grid = tiles < want ? tiles : want;
+    // (persistent_grid: CVAE_PERSIST_MAXWG caps this grid too, so that a test batch walks several tiles per workgroup)
+    const int tiles = B * (width / 16) * (width / 32), grid = persistent_grid(bf16io ? 4 : 2, tiles);
     cvae_probe_begin(st);
     if (width == 64 && bf16io) hipLaunchKernelGGL(d4_fwd_bf16_kernel<64>, dim3(grid), dim3(256), 0, st, in, w, bias, recon, B);
     else if (width == 128 && bf16io) hipLaunchKernelGGL(d4_fwd_bf16_kernel<128>, dim3(grid), dim3(256), 0, st, in, w, bias, recon, B);

@@ -580,21 +580,30 @@ int launch_conv_up_dgrad(int layer, int width, int B, const float* dout, const f
     return -2;
 }
 
+// Split arithmetic of run_up_wgrad on a device of `cus` compute units: a whole number of workgroups per CU (one for the fp32 kernel,
+// two for the bf16 one, whose cap Scap also sizes the slabs) with equal tile counts -- 1.5 per CU leaves a third of the CUs with
+// twice the work of the rest.  The launcher passes cvae_num_cus(); conv_up_wgrad_plan_f32 reports it for any count.
+struct UpWgradSplits { int numTiles, Scap, S, tps; };
+template <int HS>
+static UpWgradSplits up_wgrad_splits(int B, int bps, int cus) {
+    using T = UpTile64<HS>;
+    UpWgradSplits p;
+    p.numTiles = cdiv(B, T::IMGS) * T::TILES_PER_IMG;
+    p.Scap = cdiv(2 * cus, bps);
+    if (p.Scap > p.numTiles) p.Scap = p.numTiles;
+    p.S = cdiv(cus, bps);
+    if (p.S > p.numTiles) p.S = p.numTiles;
+    p.tps = cdiv(p.numTiles, p.S);
+    p.S = cdiv(p.numTiles, p.tps);
+    return p;
+}
+
 template <int CIN, int COUT, int HS>
 static int run_up_wgrad(int B, const float* in, const float* dout, float* dw, float* dbias, float* ws, hipStream_t st,
                         int64_t* need, int bf16_layer = 0, int bf16_width = 64, int* plan = nullptr) {
-    using T = UpTile64<HS>;
-    const int numTiles = cdiv(B, T::IMGS) * T::TILES_PER_IMG;
-    const int bps = (CIN / 32) * (COUT / 32);
-    // splits: a whole number of workgroups per CU (one for the fp32 kernel, two for the bf16 one) with equal tile
-    // counts -- 1.5 per CU leaves a third of the CUs with twice the work of the rest
-    const int cus = cvae_num_cus();
-    int Scap = cdiv(2 * cus, bps);
-    if (Scap > numTiles) Scap = numTiles;
-    int S = cdiv(cus, bps);
-    if (S > numTiles) S = numTiles;
-    const int tps = cdiv(numTiles, S);
-    S = cdiv(numTiles, tps);
+    const UpWgradSplits sp = up_wgrad_splits<HS>(B, (CIN / 32) * (COUT / 32), cvae_num_cus());
+    const int numTiles = sp.numTiles, Scap = sp.Scap, tps = sp.tps;
+    int S = sp.S;
     const int64_t nc = (int64_t)36 * CIN * COUT, row = nc + COUT;
     // plan (bf16 mode, no launch): the (tiles, splits, tiles per split) the bf16 main kernel would run with under this cap; tests/bf16_ops_tools.py
     // mirrors this arithmetic (wgrad_geometry) and test_gpu_bf16_ops.py holds the mirror to it
@@ -648,6 +657,20 @@ int64_t conv_up_wgrad_ws_floats(int layer, int width, int B) {
 }
 int conv_up_wgrad_bf16_plan(int layer, int width, int B, int plan[3]) {
     return dispatch_up_wgrad(layer, width, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, plan);
+}
+// (tiles, splits, tiles per split) of the fp32 kernel on a device of `cus` compute units: host arithmetic only, no device access
+int conv_up_wgrad_plan_f32(int layer, int width, int B, int cus, int plan[3]) {
+    if ((width != 64 && width != 128) || layer < 5 || layer > 7) { cvae_set_error("conv_up_wgrad_plan_f32: unsupported layer %d at width %d", layer, width); return -2; }
+    const int bps = (kLayers[layer].cin / 32) * (kLayers[layer].cout / 32);
+    UpWgradSplits p;
+    switch ((4 << (layer - 5)) * (width / 64)) {          // HS of run_up_wgrad's instantiations
+        case 4: p = up_wgrad_splits<4>(B, bps, cus); break;
+        case 8: p = up_wgrad_splits<8>(B, bps, cus); break;
+        case 16: p = up_wgrad_splits<16>(B, bps, cus); break;
+        default: p = up_wgrad_splits<32>(B, bps, cus); break;
+    }
+    plan[0] = p.numTiles; plan[1] = p.S; plan[2] = p.tps;
+    return 0;
 }
 int launch_conv_up_wgrad(int layer, int width, int B, const float* in, const float* dout, float* dw, float* dbias,
                          float* ws, hipStream_t st, bool bf16) {

@@ -318,13 +318,14 @@ static int wgrad_splits(int B, int blocksPerSplit, int* tilesPerSplit) {
 
 template <int CIN, int COUT, int H, bool UP>
 static int run_wgrad(int B, const float* in, const float* dout, float* dw, float* dbias, float* ws, hipStream_t st,
-                     int64_t* ws_need) {
+                     int64_t* ws_need, int* plan) {
     using T = Tile<H>;
     int tps;
     const int bps = (CIN / 32) * (COUT / 32);
     const int S = wgrad_splits<H>(B, bps, &tps);
     const int64_t n = (int64_t)25 * CIN * COUT, row = n + COUT;
     if (ws_need) { *ws_need = (int64_t)(S + 16) * row; return 0; }
+    if (plan) { plan[0] = cdiv(B, T::IMGS) * T::TILES_PER_IMG; plan[1] = S; plan[2] = tps; return 0; }      // no launch: conv_wgrad_plan_f32
     WgradArgs a{in, dout, ws, B, cdiv(B, T::IMGS) * T::TILES_PER_IMG, tps};
     constexpr int SMEM = (T::HP * 32 + 128 * 32) * 4;
     auto kern = conv5x5_wgrad_kernel<CIN, COUT, H, UP>;
@@ -343,21 +344,21 @@ static int run_wgrad(int B, const float* in, const float* dout, float* dw, float
 }
 
 static int dispatch_wgrad(int layer, int width, int B, const float* in, const float* dout, float* dw, float* dbias,
-                          float* ws, hipStream_t st, int64_t* need) {
+                          float* ws, hipStream_t st, int64_t* need, int* plan = nullptr) {
     if (width == 64) {
         switch (layer) {
-            case 1: return run_wgrad<32, 64, 32, false>(B, in, dout, dw, dbias, ws, st, need);
-            case 2: return run_wgrad<64, 128, 16, false>(B, in, dout, dw, dbias, ws, st, need);
-            case 3: return run_wgrad<128, 256, 8, false>(B, in, dout, dw, dbias, ws, st, need);
-            case 4: return run_wgrad<256, 128, 4, false>(B, in, dout, dw, dbias, ws, st, need);
+            case 1: return run_wgrad<32, 64, 32, false>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 2: return run_wgrad<64, 128, 16, false>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 3: return run_wgrad<128, 256, 8, false>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 4: return run_wgrad<256, 128, 4, false>(B, in, dout, dw, dbias, ws, st, need, plan);
         }
     }
     if (width == 128) {
         switch (layer) {
-            case 1: return run_wgrad<32, 64, 64, false>(B, in, dout, dw, dbias, ws, st, need);
-            case 2: return run_wgrad<64, 128, 32, false>(B, in, dout, dw, dbias, ws, st, need);
-            case 3: return run_wgrad<128, 256, 16, false>(B, in, dout, dw, dbias, ws, st, need);
-            case 4: return run_wgrad<256, 128, 8, false>(B, in, dout, dw, dbias, ws, st, need);
+            case 1: return run_wgrad<32, 64, 64, false>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 2: return run_wgrad<64, 128, 32, false>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 3: return run_wgrad<128, 256, 16, false>(B, in, dout, dw, dbias, ws, st, need, plan);
+            case 4: return run_wgrad<256, 128, 8, false>(B, in, dout, dw, dbias, ws, st, need, plan);
         }
     }
     cvae_set_error("conv_wgrad: unsupported layer %d at width %d", layer, width);
@@ -368,6 +369,11 @@ int64_t wgrad_ws_floats(int layer, int width, int B) {
     int64_t need = 0;
     if (dispatch_wgrad(layer, width, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need) != 0) return 0;
     return need;
+}
+
+// (tiles, splits, tiles per split) of run_wgrad's launch at a batch, answered by run_wgrad itself: host arithmetic only, no launch
+int conv_wgrad_plan_f32(int layer, int width, int B, int plan[3]) {
+    return dispatch_wgrad(layer, width, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, plan);
 }
 
 int launch_conv_wgrad(int layer, int width, int B, const float* in, const float* dout, float* dw, float* dbias,

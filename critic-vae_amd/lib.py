@@ -247,6 +247,7 @@ _SIGS = {
     "cvae_op_bn_pool_act_bwd": (C.c_int, [_p, _i32, _i32] + [_p] * 11),
     "cvae_op_conv_tiles_per_partial": (_i32, [_p, _i32, _i32]),
     "cvae_op_conv_wgrad_plan": (C.c_int, [_p, _i32, _i32, C.POINTER(C.c_int32)]),
+    "cvae_op_conv_wgrad_plan_f32": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int32)]),
     "cvae_op_bn_fwd_finalize": (C.c_int, [_p, _i32, _i32, _p, _i32] + [_p] * 6 + [_i32, _p]),
     "cvae_op_msssim": (C.c_int, [_p, _i32] + [_p] * 6),
     "cvae_op_latent_scratch_floats": (_i64, [_p, _i32]),
@@ -321,6 +322,16 @@ def latent_plan(width, B, num_cus):
             "decin_bwd": {"jobs": {"bgemm": (v[3], v[4]), "gemm": (v[5], v[6])}, "grid": v[6]},
             "fc_bwd": {"imgs": v[7], "jobs": {"bgemm": (v[8], v[9]), "dflat": (v[10], v[11]), "colsum": (v[12], v[13])},
                        "grid": v[13], "split": bool(v[14])}}
+
+
+def conv_wgrad_plan_f32(width, layer, B, num_cus):
+    """cvae_op_conv_wgrad_plan_f32 (host logic only): (tiles, splits, tiles per split) of the fp32 weight-gradient kernel of conv
+    layer 0..8 (8: the fused D4 backward) at batch B on a device of num_cus compute units."""
+    lib = load()
+    out = (C.c_int32 * 3)()
+    if lib.cvae_op_conv_wgrad_plan_f32(width, layer, B, num_cus, out) != 0:
+        raise CvaeError(f"cvae_op_conv_wgrad_plan_f32: {lib.cvae_last_error().decode()}")
+    return tuple(out)
 
 
 def _stream():

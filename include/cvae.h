@@ -941,6 +941,13 @@ int32_t cvae_op_conv_tiles_per_partial(cvae_handle h, int32_t layer, int32_t bat
  * cvae_op_conv_wgrad(layer 1..7) launches on a bf16 handle at this batch, from the launchers' own split arithmetic.
  * CVAE_EUNSUPPORTED on other handles and layers. */
 int cvae_op_conv_wgrad_plan(cvae_handle h, int32_t layer, int32_t batch, int32_t* out);
+/* Host logic only (no handle, no device access): out[0..2] = (tiles, splits, tiles per split) of the fp32 kernel that
+ * cvae_op_conv_wgrad(layer 0..7) and cvae_op_d4_bwd (layer 8) launch on a precision 0 handle of this width at this batch, on a
+ * device of `num_cus` compute units (only layers 5..7 depend on it; the launchers pass the current device's count), from the
+ * launchers' own split functions.  Tiles are 128 pixels for layers 1..4, 64 low-resolution pixels for layers 5..7, and
+ * batch * (width / 4) * (width / 32) / batch * (width / 16) * (width / 32) strips for layers 0 / 8.
+ * Width other than 64 / 128, layer outside 0..8, batch or num_cus below 1, or a null pointer: CVAE_EINVAL. */
+int32_t cvae_op_conv_wgrad_plan_f32(int32_t width, int32_t layer, int32_t batch, int32_t num_cus, int32_t* out);
 /* The statistics half of cvae_op_bn_pool_act_fwd on partial rows of `tiles_per_partial` (1, 2, 4, 8) tiles each:
  * coef (scale, shift, mean, invstd per channel) and, in train mode, the running statistics.  `scratch` as above. */
 int cvae_op_bn_fwd_finalize(cvae_handle h, int32_t layer, int32_t batch, const float* bn_partials,
