@@ -126,6 +126,7 @@ static int ensure_streams(cvae_handle_s* h) {
 }
 
 static int layer_h(const cvae_handle_s* h, int layer) { return kLayers[layer].h * (h->cfg.width / 64); }
+static int64_t pack_floats(const cvae_handle_s* h);      // with the conv table below
 
 static WsLayout carve(const cvae_handle_s* h, int B) {
     WsLayout w{};
@@ -158,13 +159,13 @@ static WsLayout carve(const cvae_handle_s* h, int B) {
     w.dout4 = take(b16 ? 0 : (int64_t)B * 3 * W * W);          // bf16 mode applies the Tanh backward inside d4_bwd: no dOut tensor
     for (int i = 0; i < 3; ++i) w.wc[i] = take(conv_up_wc_floats(5 + i));
     w.xp = take(b16 ? (int64_t)B * W * W * 2 : 0);
-    w.wpack = take(h->cfg.precision != 0 ? conv_bf16_pack_floats(h->cfg.precision >= 2 ? 3 : 1) : 0);
+    w.wpack = take(pack_floats(h));
     w.ms = take(msssim_ws_floats(W, B));
     int64_t sc = 0, scw = 0;
     auto mx = [&](int64_t v) { if (v > sc) sc = v; };
     for (int l = 1; l <= 4; ++l) { if (wgrad_ws_floats(l, W, B) > scw) scw = wgrad_ws_floats(l, W, B);
-        if (h->cfg.precision == 1 && conv_bf16_supported(l, W) && wgrad_bf16_ws_floats(l, W, B) > scw) scw = wgrad_bf16_ws_floats(l, W, B);
-        if (h->cfg.precision >= 2 && conv_bf16_supported(l, W) && wgrad_split_ws_floats(l, W, B) > scw) scw = wgrad_split_ws_floats(l, W, B);
+        if (h->cfg.precision == 1 && wgrad_bf16_ws_floats(l, W, B) > scw) scw = wgrad_bf16_ws_floats(l, W, B);
+        if (h->cfg.precision >= 2 && wgrad_split_ws_floats(l, W, B) > scw) scw = wgrad_split_ws_floats(l, W, B);
         mx(conv_fwd_ws_floats(l, W, B)); mx(conv_dgrad_ws_floats(l, W, B)); }
     for (int l = 5; l <= 7; ++l) { if (conv_up_wgrad_ws_floats(l, W, B) > scw) scw = conv_up_wgrad_ws_floats(l, W, B); mx(conv_up_ws_floats(l, W, B)); }
     if (e1_wgrad_ws_floats(W, B) > scw) scw = e1_wgrad_ws_floats(W, B);
@@ -275,34 +276,94 @@ int cvae_backward_phases(cvae_handle h, int32_t B, const float* x, const float* 
 #define G_(idx) (grads + h->params[(idx)].offset)
 #define RC(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
-// cvae_config.precision: 1 = bf16-MFMA kernels for every pass of E2..E4 / D0..D3 (conv_bf16.hip); 2 / 3 = E2..E4 / D0 on the same
-// forward / input-gradient kernels with 3-way split operands (exact fp32 products, 9 / the 6 leading MFMAs each) and their weight
-// gradients on the split-operand bf16-MFMA kernel (conv_wgrad_split.hip)
-static bool use_bf16(cvae_handle h, int layer) {
-    if (h->cfg.precision >= 2 && layer > 4) return false;     // D1..D3: the fp32 phase-collapsed kernels beat nine bf16 MFMAs per block
-    return h->cfg.precision != 0 && conv_bf16_supported(layer, h->cfg.width);
+// ---- the one place a conv family is chosen: layers 1..7 (E2..E4, D0, D1..D3), by cvae_config.precision ----
+// The step (FwdCtx, cvae_decode, BwdCtx, hence the staged entry points) and the per-op entry points cvae_op_conv_* reach the launchers
+// of these layers only through conv_fwd / conv_dgrad / conv_wgrad and prepare_conv_weights, which read this table.  Precision 2 / 3:
+// 3-way split operands on the bf16 MFMA (exact fp32 products, 9 / the 6 leading MFMAs each) for E2..E4 / D0; D1..D3 stay on the fp32
+// phase-collapsed kernels, which beat nine bf16 MFMAs per block.  Layers 0 and 8 (E1, D4) are outside on purpose: the step runs their
+// fused forms (two-pass E1, packed frame, E1Fuse, fused D4 backward), the per-op entry points the plain ones.
+enum ConvFamilyFD { FD_F32, FD_BF16, FD_UP, FD_UP_BF16 };      // forward / input gradient: launch_conv_*, _bf16, _up_*, _up_*_bf16
+enum ConvFamilyWG { WG_F32, WG_BF16, WG_SPLIT, WG_UP };        // weight gradient: launch_conv_wgrad, _bf16, _split, launch_conv_up_wgrad
+enum WeightForm { W_RAW, W_COLLAPSED, W_PACKED };              // fp32 [25][Cin][Cout]; D1..D3 phase-collapsed; packed bf16 (D1..D3: of the collapsed)
+enum FdScratch { SCRATCH_D0_AT_64, SCRATCH_ALWAYS };           // split-K slabs of D0 at 64 x 64 only; every layer
+struct ConvRow {
+    int precision, first, last;      // key: layers first..last of a handle of this precision
+    ConvFamilyFD fd; int mode;       // forward / input gradient; bf16 families: launcher mode 1 = bf16, 3 = x9, 6 = x6
+    WeightForm wform;                // the weights that family reads (a weight gradient reads none)
+    FdScratch scratch;               // where that family writes scratch (slabs; a per-op call also prepares its weights there)
+    ConvFamilyWG wg; int wgArg;      // weight gradient, always with split-K slabs in scratch; WG_SPLIT: 9 / 6 products, WG_UP: the bf16 flag
+    int splits() const { return mode == 1 ? 1 : 3; }      // copies of a packed weight
+};
+static constexpr ConvRow kConvTable[] = {
+    {0, 1, 4, FD_F32,     0, W_RAW,       SCRATCH_D0_AT_64, WG_F32,   0},
+    {0, 5, 7, FD_UP,      0, W_COLLAPSED, SCRATCH_ALWAYS,   WG_UP,    0},
+    {1, 1, 4, FD_BF16,    1, W_PACKED,    SCRATCH_ALWAYS,   WG_BF16,  0},
+    {1, 5, 7, FD_UP_BF16, 1, W_PACKED,    SCRATCH_ALWAYS,   WG_UP,    1},
+    {2, 1, 4, FD_BF16,    3, W_PACKED,    SCRATCH_ALWAYS,   WG_SPLIT, 9},
+    {2, 5, 7, FD_UP,      0, W_COLLAPSED, SCRATCH_ALWAYS,   WG_UP,    0},
+    {3, 1, 4, FD_BF16,    6, W_PACKED,    SCRATCH_ALWAYS,   WG_SPLIT, 6},
+    {3, 5, 7, FD_UP,      0, W_COLLAPSED, SCRATCH_ALWAYS,   WG_UP,    0},
+};
+static const ConvRow& conv_row(const cvae_handle_s* h, int layer) {      // layer 1..7: the step's constants, the range cvae_op_conv_* check
+    for (const ConvRow& r : kConvTable)
+        if (r.precision == h->cfg.precision && layer >= r.first && layer <= r.last) return r;
+    abort();
+}
+static bool fd_uses_scratch(const ConvRow& r, int layer, int width) { return r.scratch == SCRATCH_ALWAYS || (layer == 4 && width == 64); }
+static int64_t pack_floats(const cvae_handle_s* h) {      // the packed-weight block: workspace slot wpack, the head of a per-op scratch
+    return conv_row(h, 1).wform == W_PACKED ? conv_bf16_pack_floats(conv_row(h, 1).splits()) : 0;
 }
 // precision 1: activations and activation gradients are bf16 IN HBM (every kernel that touches them is told so)
 static bool io_bf16(cvae_handle h) { return h->cfg.precision == 1; }
-static bool use_bf16_wgrad(cvae_handle h, int layer) { return h->cfg.precision == 1 && conv_bf16_supported(layer, h->cfg.width); }
-// fp32-emulation modes: weight gradients of E2..E4 / D0 on the bf16 MFMA with exact 3-way operand splits (conv_wgrad_split.hip)
-static bool use_split_wgrad(cvae_handle h, int layer) {
-    if (h->cfg.precision < 2 || layer < 1 || layer > 4 || !conv_bf16_supported(layer, h->cfg.width)) return false;
-    return conv_wgrad_split_supported(h->cfg.precision == 3 ? 6 : 9);
+// raw[l - 1] = the fp32 weights of layer l (null: not given); collapsed[l - 5] and packed (the whole pack block) = where their other forms go
+struct ConvWeights { const float* raw[7]; float* collapsed[3]; float* packed; };
+static int conv_fwd(cvae_handle h, int layer, int B, const float* in, const ConvWeights& wt, const float* bias, float* out, float* bnpart, float* scratch, hipStream_t st, int* tilesPerPartial) {
+    const ConvRow& r = conv_row(h, layer);
+    switch (r.fd) {
+        case FD_F32: return launch_conv_fwd(layer, h->cfg.width, B, in, wt.raw[layer - 1], bias, out, bnpart, scratch, st);
+        case FD_BF16: return launch_conv_fwd_bf16(layer, h->cfg.width, r.mode, B, in, wt.packed, bias, out, bnpart, scratch, st, tilesPerPartial);
+        case FD_UP: return launch_conv_up_fwd(layer, h->cfg.width, B, in, wt.collapsed[layer - 5], bias, out, scratch, st);
+        case FD_UP_BF16: return launch_conv_up_fwd_bf16(layer, h->cfg.width, r.mode, B, in, wt.packed, bias, out, st);
+    }
+    return CVAE_EINVAL;
 }
-static int bf16_splits(cvae_handle h) { return h->cfg.precision >= 2 ? 3 : 1; }          // packed weight copies
-static int bf16_mode(cvae_handle h) { return h->cfg.precision == 2 ? 3 : (h->cfg.precision == 3 ? 6 : 1); }   // launcher code: 1 bf16, 3 x9, 6 x6
-// weight gradient of conv layer 1..4 (E2..E4, D0): bf16 MFMA, exact 3-way operand splits (fp32-emulation modes) or fp32 MFMA
-static int conv_wgrad(cvae_handle h, int layer, int B, const float* in, const float* dout, float* dw, float* dbias, float* ws, hipStream_t st) {
-    const int W = h->cfg.width;
-    if (use_bf16_wgrad(h, layer)) return launch_conv_wgrad_bf16(layer, W, B, in, dout, dw, dbias, ws, st);
-    if (use_split_wgrad(h, layer)) return launch_conv_wgrad_split(layer, W, bf16_mode(h) == 6 ? 6 : 9, B, in, dout, dw, dbias, ws, st);
-    return launch_conv_wgrad(layer, W, B, in, dout, dw, dbias, ws, st);
+static int conv_dgrad(cvae_handle h, int layer, int B, const float* dout, const ConvWeights& wt, const float* mask_src, float* din, float* scratch, hipStream_t st) {
+    const ConvRow& r = conv_row(h, layer);
+    switch (r.fd) {
+        case FD_F32: return launch_conv_dgrad(layer, h->cfg.width, B, dout, wt.raw[layer - 1], mask_src, din, scratch, st);
+        case FD_BF16: return launch_conv_dgrad_bf16(layer, h->cfg.width, r.mode, B, dout, wt.packed, din, scratch, st);
+        case FD_UP: return launch_conv_up_dgrad(layer, h->cfg.width, B, dout, wt.collapsed[layer - 5], mask_src, din, scratch, st);
+        case FD_UP_BF16: return launch_conv_up_dgrad_bf16(layer, h->cfg.width, r.mode, B, dout, wt.packed, mask_src, din, st);
+    }
+    return CVAE_EINVAL;
 }
-static int pack_bf16_weights(cvae_handle h, const float* params, float* ws, const WsLayout& w, hipStream_t st) {
-    if (!use_bf16(h, 1)) return 0;
-    const float* wl[4] = {P_(h->enc_w[1]), P_(h->enc_w[2]), P_(h->enc_w[3]), P_(h->dec_w[0])};
-    return launch_pack_w_bf16(wl, ws + w.wpack, bf16_splits(h), st);
+static int conv_wgrad(cvae_handle h, int layer, int B, const float* in, const float* dout, float* dw, float* dbias, float* scratch, hipStream_t st) {
+    const ConvRow& r = conv_row(h, layer);
+    switch (r.wg) {
+        case WG_F32: return launch_conv_wgrad(layer, h->cfg.width, B, in, dout, dw, dbias, scratch, st);
+        case WG_BF16: return launch_conv_wgrad_bf16(layer, h->cfg.width, B, in, dout, dw, dbias, scratch, st);
+        case WG_SPLIT: return launch_conv_wgrad_split(layer, h->cfg.width, r.wgArg, B, in, dout, dw, dbias, scratch, st);
+        case WG_UP: return launch_conv_up_wgrad(layer, h->cfg.width, B, in, dout, dw, dbias, scratch, st, r.wgArg != 0);
+    }
+    return CVAE_EINVAL;
+}
+// The forms the table asks for, of the layers given: 1..4 packed (one launch); 5..7 collapsed (one launch for all three, else one each), then packed (one launch)
+static int prepare_conv_weights(cvae_handle h, const ConvWeights& f, hipStream_t st) {
+    const ConvRow &enc = conv_row(h, 1), &up_row = conv_row(h, 5);
+    if (enc.wform == W_PACKED && (f.raw[0] || f.raw[1] || f.raw[2] || f.raw[3])) RC(launch_pack_w_bf16(f.raw, f.packed, enc.splits(), st));
+    const float* const* up = f.raw + 4;
+    const int n_up = (up[0] != nullptr) + (up[1] != nullptr) + (up[2] != nullptr);
+    if (n_up == 3) RC(launch_collapse_w3(up, f.collapsed, st));
+    else for (int i = 0; i < 3; ++i) if (up[i]) RC(launch_collapse_w(5 + i, up[i], f.collapsed[i], st));
+    if (n_up == 0 || up_row.wform != W_PACKED) return 0;
+    const float* wcs[3] = {up[0] ? f.collapsed[0] : nullptr, up[1] ? f.collapsed[1] : nullptr, up[2] ? f.collapsed[2] : nullptr};      // the packer skips a null layer
+    return launch_pack_up_bf16(wcs, f.packed, up_row.splits(), st);
+}
+// the step's: layers first..last of the parameters, the workspace slots wc[] and wpack (rebuilt every forward)
+static ConvWeights step_weights(cvae_handle h, const float* params, float* ws, const WsLayout& w, int first = 1, int last = 7) {
+    ConvWeights f{{}, {ws + w.wc[0], ws + w.wc[1], ws + w.wc[2]}, ws + w.wpack};
+    for (int l = first; l <= last; ++l) f.raw[l - 1] = l < 4 ? P_(h->enc_w[l]) : P_(h->dec_w[l - 4]);
+    return f;
 }
 
 static int check(cvae_handle h, int32_t batch, const void* ws) {
@@ -332,8 +393,7 @@ struct FwdCtx {
             return 0;
         }
         if (l == 0) { ProbeArm pa(h, 0, 0); RC(launch_e1_fwd(W, B, x, P_(h->enc_w[0]), P_(h->enc_b[0]), ws + w.y[0], ws + w.bnpart[0], st)); }
-        else if (use_bf16(h, l)) { ProbeArm pa(h, 0, l); RC(launch_conv_fwd_bf16(l, W, bf16_mode(h), B, ws + w.a[l - 1], ws + w.wpack, P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st, &tpp)); }
-        else { ProbeArm pa(h, 0, l); RC(launch_conv_fwd(l, W, B, ws + w.a[l - 1], P_(h->enc_w[l]), P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st)); }
+        else { ProbeArm pa(h, 0, l); RC(conv_fwd(h, l, B, ws + w.a[l - 1], step_weights(h, params, ws, w), P_(h->enc_b[l]), ws + w.y[l], ws + w.bnpart[l], ws + w.scratch, st, &tpp)); }
         return 0;
     }
     int stats(int l, double* sync) {
@@ -363,7 +423,7 @@ int cvae_forward(cvae_handle h, int32_t B, const float* x, const float* pred, co
     float* ws = (float*)wsv;
     const WsLayout w = carve(h, B);
     const int W = h->cfg.width;
-    RC(pack_bf16_weights(h, params, ws, w, st));
+    RC(prepare_conv_weights(h, step_weights(h, params, ws, w, 1, 4), st));
     FwdCtx f{h, B, W, train, x, params, bn_state, ws, wsv, w, st};
     for (int l = 0; l < 4; ++l) {
         RC(f.conv(l));
@@ -386,29 +446,15 @@ int cvae_decode(cvae_handle h, int32_t B, const float* zcat, const float* params
     if (zcat) {
         hipError_t e = hipMemcpyAsync(ws + w.zcat, zcat, (size_t)B * 33 * sizeof(float), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) { cvae_set_error("cvae_decode: copy failed: %s", hipGetErrorString(e)); return (int)e; }
-        RC(pack_bf16_weights(h, params, ws, w, st));          // stand-alone decode: cvae_forward did not run
     }
     RC(launch_decin_fwd(W, B, ws + w.zcat, P_(h->di_w), P_(h->di_b), ws + w.h, st, io_bf16(h)));
-    // Upsample -> Conv of D1..D3 runs at the low resolution with phase-collapsed weights (conv_up.hip)
-    {
-        const float* wsrc[3] = {P_(h->dec_w[1]), P_(h->dec_w[2]), P_(h->dec_w[3])};
-        float* wdst[3] = {ws + w.wc[0], ws + w.wc[1], ws + w.wc[2]};
-        RC(launch_collapse_w3(wsrc, wdst, st));
-    }
-    if (use_bf16(h, 5)) {
-        const float* wcs[3] = {ws + w.wc[0], ws + w.wc[1], ws + w.wc[2]};
-        RC(launch_pack_up_bf16(wcs, ws + w.wpack, bf16_splits(h), st));
-    }
+    // Upsample -> Conv of D1..D3 runs at the low resolution with phase-collapsed weights (conv_up.hip); a stand-alone decode
+    // (cvae_forward did not run) prepares layers 1..4 as well
+    RC(prepare_conv_weights(h, step_weights(h, params, ws, w, zcat ? 1 : 5, 7), st));
     for (int i = 0; i < 4; ++i) {
         ProbeArm pa(h, 0, 4 + i);
-        if (i == 0) {
-            if (use_bf16(h, 4)) RC(launch_conv_fwd_bf16(4, W, bf16_mode(h), B, ws + w.h, ws + w.wpack, P_(h->dec_b[0]), ws + w.o[0], nullptr, ws + w.scratch, st));
-            else RC(launch_conv_fwd(4, W, B, ws + w.h, P_(h->dec_w[0]), P_(h->dec_b[0]), ws + w.o[0], nullptr, ws + w.scratch, st));
-        } else if (use_bf16(h, 4 + i)) {
-            RC(launch_conv_up_fwd_bf16(4 + i, W, bf16_mode(h), B, ws + w.o[i - 1], ws + w.wpack, P_(h->dec_b[i]), ws + w.o[i], st));
-        } else {
-            RC(launch_conv_up_fwd(4 + i, W, B, ws + w.o[i - 1], ws + w.wc[i - 1], P_(h->dec_b[i]), ws + w.o[i], ws + w.scratch, st));
-        }
+        RC(conv_fwd(h, 4 + i, B, i == 0 ? ws + w.h : ws + w.o[i - 1], step_weights(h, params, ws, w), P_(h->dec_b[i]), ws + w.o[i], nullptr,
+                    ws + w.scratch, st, nullptr));
     }
     { ProbeArm pa(h, 0, 8); RC(launch_d4_fwd(W, B, ws + w.o[3], P_(h->dec_w[4]), P_(h->dec_b[4]), recon, st, io_bf16(h))); }
     return 0;
@@ -543,18 +589,9 @@ struct BwdCtx {
             const int l = 4 + i;
             const float* in = i == 0 ? ws + w.h : ws + w.o[i - 1];
             RC(fork(3 - i));
-            if (i == 0) {
-                { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, 4, B, in, ws + w.d_o[0], G_(h->dec_w[0]), G_(h->dec_b[0]), scw, sd)); }
-                { ProbeArm pa(h, 1, l);
-                  if (use_bf16(h, 4)) RC(launch_conv_dgrad_bf16(4, W, bf16_mode(h), B, ws + w.d_o[0], ws + w.wpack, ws + w.d_h, ws + w.scratch, st));
-                  else RC(launch_conv_dgrad(l, W, B, ws + w.d_o[0], P_(h->dec_w[0]), nullptr, ws + w.d_h, ws + w.scratch, st)); }
-            } else {
-                { ProbeArm pa(h, 2, l);
-                  RC(launch_conv_up_wgrad(l, W, B, in, ws + w.d_o[i], G_(h->dec_w[i]), G_(h->dec_b[i]), scw, sd, use_bf16_wgrad(h, l))); }
-                { ProbeArm pa(h, 1, l);
-                  if (use_bf16(h, l)) RC(launch_conv_up_dgrad_bf16(l, W, bf16_mode(h), B, ws + w.d_o[i], ws + w.wpack, ws + w.o[i - 1], ws + w.d_o[i - 1], st));
-                  else RC(launch_conv_up_dgrad(l, W, B, ws + w.d_o[i], ws + w.wc[i - 1], ws + w.o[i - 1], ws + w.d_o[i - 1], sc, st)); }
-            }
+            { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, l, B, in, ws + w.d_o[i], G_(h->dec_w[i]), G_(h->dec_b[i]), scw, sd)); }
+            { ProbeArm pa(h, 1, l);      // D1..D3 mask with the ReLU of their input o[i - 1]
+              RC(conv_dgrad(h, l, B, ws + w.d_o[i], step_weights(h, params, ws, w), i == 0 ? nullptr : in, i == 0 ? ws + w.d_h : ws + w.d_o[i - 1], sc, st)); }
         }
         RC(launch_decin_bwd(W, B, ws + w.zcat, ws + w.d_h, P_(h->di_w), G_(h->di_w), G_(h->di_b), ws + w.d_zcat, sc, st, io_bf16(h)));
         return join();
@@ -584,8 +621,7 @@ struct BwdCtx {
         }
         { ProbeArm pa(h, 2, l); RC(conv_wgrad(h, l, B, ws + w.a[l - 1], ws + w.d_y[l], G_(h->enc_w[l]), G_(h->enc_b[l]), scw, sd)); }
         ProbeArm pa(h, 1, l);
-        if (use_bf16(h, l)) return launch_conv_dgrad_bf16(l, W, bf16_mode(h), B, ws + w.d_y[l], ws + w.wpack, ws + w.d_a[l - 1], ws + w.scratch, st);
-        return launch_conv_dgrad(l, W, B, ws + w.d_y[l], P_(h->enc_w[l]), nullptr, ws + w.d_a[l - 1], nullptr, st);
+        return conv_dgrad(h, l, B, ws + w.d_y[l], step_weights(h, params, ws, w), nullptr, ws + w.d_a[l - 1], sc, st);
     }
 };
 
@@ -661,7 +697,7 @@ static int forward_stage(cvae_handle h, int32_t B, const float* x, const float* 
     const WsLayout w = carve(h, B);
     const int W = h->cfg.width;
     FwdCtx f{h, B, W, 1, x, params, bn_state, ws, wsv, w, st};
-    if (k == 0) RC(pack_bf16_weights(h, params, ws, w, st));
+    if (k == 0) RC(prepare_conv_weights(h, step_weights(h, params, ws, w, 1, 4), st));
     if (k > 0) {                                        // block k-1 from the summed record
         RC(f.finish(k - 1, sync));
         RC(f.apply(k - 1));
@@ -1267,96 +1303,60 @@ int cvae_probe_read(cvae_handle h, int32_t id, float* ms_host, int32_t cap) {
 }
 
 // ------------------------------ per-op entry points ------------------------------
-// Layers 1..4 follow the handle's precision in the fp32-emulation modes (2, 3): the kernels the step runs there, on fp32 tensors.
-// Their scratch is [packed 3-split weights (the step's wpack block, only the layer's own slots written) | everything else].
-// bf16 mode (1): layers 1..8 run what the step runs, on tensors in the handle's storage type (bf16 activations and activation
-// gradients; fp32 weights, biases, their gradients and recon / d_recon).  Scratch = [packed bf16 weights (the step's wpack block,
-// only the layer's own slots written) | collapsed weights of D1..D3 | everything else].
-static bool op_emulated(cvae_handle h, int layer) { return h->cfg.precision >= 2 && layer >= 1 && layer <= 4 && use_bf16(h, layer); }
-static bool op_bf16(cvae_handle h, int layer) { return h->cfg.precision == 1 && layer >= 1 && layer <= 7 && use_bf16(h, layer); }
-static int64_t op_pack_floats(cvae_handle h) { return h->cfg.precision != 0 ? align_up(conv_bf16_pack_floats(bf16_splits(h)), 64) : 0; }
-static int op_pack_layer(cvae_handle h, int layer, const float* wt, void* scratch, hipStream_t st) {
-    if (!scratch) { cvae_set_error("per-op conv, layer %d: the bf16 and fp32-emulation modes pack the weights into scratch (null)", layer); return CVAE_EINVAL; }
-    const float* wl[4] = {nullptr, nullptr, nullptr, nullptr};          // the packer skips the layers it is not given
-    wl[layer - 1] = wt;
-    return launch_pack_w_bf16(wl, (float*)scratch, bf16_splits(h), st);
+// Conv layers 1..7 go through the conv table: the kernels the step runs on this handle, on tensors in the handle's storage type
+// (precision 1: bf16 activations and activation gradients; fp32 weights, biases, their gradients and recon / d_recon); layers 0 and 8
+// run the plain forms of E1 / D4.  Host-only checks of a conv entry, before any device access: lo..hi = the layers it documents; a null
+// scratch is refused on every weight gradient and on the forward / input-gradient passes whose table row writes scratch.
+static int op_conv_check(const char* who, cvae_handle h, int layer, int lo, int hi, int B, bool wgrad, const void* scratch) {
+    if (!h) { cvae_set_error("%s: null handle", who); return CVAE_EINVAL; }
+    if (layer < lo || layer > hi) { cvae_set_error("%s: layer %d outside [%d, %d]", who, layer, lo, hi); return CVAE_EINVAL; }
+    if (B < 1 || B > h->cfg.max_batch) { cvae_set_error("%s: batch %d outside [1, %d]", who, B, h->cfg.max_batch); return CVAE_EINVAL; }
+    if (scratch || !(wgrad || (layer >= 1 && layer <= 7 && fd_uses_scratch(conv_row(h, layer), layer, h->cfg.width)))) return 0;
+    cvae_set_error("%s: null scratch (layer %d on this handle prepares its weights or reduces split-K slabs there)", who, layer);
+    return CVAE_EINVAL;
 }
-// bf16 mode, D1..D3: collapse the layer's 5x5 weights into the scratch behind the pack block, then pack them (both orientations)
-static int op_pack_up_layer(cvae_handle h, int layer, const float* wt, void* scratch, hipStream_t st) {
-    if (!scratch) { cvae_set_error("per-op conv, layer %d: bf16 mode collapses and packs the weights into scratch (null)", layer); return CVAE_EINVAL; }
-    float* wc = (float*)scratch + op_pack_floats(h);
-    RC(launch_collapse_w(layer, wt, wc, st));
-    const float* wcs[3] = {nullptr, nullptr, nullptr};
-    wcs[layer - 5] = wc;
-    return launch_pack_up_bf16(wcs, (float*)scratch, bf16_splits(h), st);
+// The weight forms of a forward / input-gradient call, prepared in its scratch: [pack block (the step's wpack, only the layer's own
+// slots written) | the layer's collapsed weights | *rest: everything else], each part only where the table row reads it
+static int op_weights(cvae_handle h, int layer, const float* wt, float* scratch, hipStream_t st, ConvWeights* f, float** rest) {
+    *f = ConvWeights{};
+    f->raw[layer - 1] = wt;
+    if (conv_row(h, layer).wform == W_PACKED) { f->packed = scratch; scratch += align_up(pack_floats(h), 64); }
+    if (layer >= 5) { f->collapsed[layer - 5] = scratch; scratch += conv_up_wc_floats(layer); }
+    *rest = scratch;
+    return prepare_conv_weights(h, *f, st);
 }
 
 int cvae_op_conv_fwd(cvae_handle h, int32_t layer, int32_t B, const float* in, const float* wt, const float* bias,
                      float* out, float* bn_partials, void* scratch, void* stream) {
-    const int W = h->cfg.width;
+    RC(op_conv_check("cvae_op_conv_fwd", h, layer, 0, 8, B, false, scratch));
     hipStream_t st = (hipStream_t)stream;
-    if (layer == 0) return launch_e1_fwd(W, B, in, wt, bias, out, bn_partials, st, io_bf16(h));   // y in the handle's storage type
-    if (layer == 8) return launch_d4_fwd(W, B, in, wt, bias, out, st, io_bf16(h));                // o3 in the handle's storage type
-    if (op_bf16(h, layer)) {
-        if (layer >= 5) {
-            RC(op_pack_up_layer(h, layer, wt, scratch, st));
-            return launch_conv_up_fwd_bf16(layer, W, 1, B, in, (float*)scratch, bias, out, st);
-        }
-        RC(op_pack_layer(h, layer, wt, scratch, st));          // fails on a null scratch, before any pointer is formed from it
-        return launch_conv_fwd_bf16(layer, W, 1, B, in, (float*)scratch, bias, out, bn_partials, (float*)scratch + op_pack_floats(h), st, nullptr);
-    }
-    if (layer >= 5) {
-        float* wc = (float*)scratch;
-        RC(launch_collapse_w(layer, wt, wc, st));
-        return launch_conv_up_fwd(layer, W, B, in, wc, bias, out, wc + conv_up_wc_floats(layer), st);
-    }
-    if (op_emulated(h, layer)) {
-        RC(op_pack_layer(h, layer, wt, scratch, st));
-        return launch_conv_fwd_bf16(layer, W, bf16_mode(h), B, in, (float*)scratch, bias, out, bn_partials, (float*)scratch + op_pack_floats(h), st, nullptr);
-    }
-    return launch_conv_fwd(layer, W, B, in, wt, bias, out, bn_partials, (float*)scratch, st);
+    if (layer == 0) return launch_e1_fwd(h->cfg.width, B, in, wt, bias, out, bn_partials, st, io_bf16(h));   // y in the handle's storage type
+    if (layer == 8) return launch_d4_fwd(h->cfg.width, B, in, wt, bias, out, st, io_bf16(h));                // o3 in the handle's storage type
+    ConvWeights forms; float* rest;
+    RC(op_weights(h, layer, wt, (float*)scratch, st, &forms, &rest));
+    return conv_fwd(h, layer, B, in, forms, bias, out, bn_partials, rest, st, nullptr);
 }
 
 int cvae_op_conv_dgrad(cvae_handle h, int32_t layer, int32_t B, const float* dout, const float* wt,
                        const float* mask_src, float* din, void* scratch, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (op_bf16(h, layer)) {
-        if (layer >= 5) {
-            RC(op_pack_up_layer(h, layer, wt, scratch, st));
-            return launch_conv_up_dgrad_bf16(layer, h->cfg.width, 1, B, dout, (float*)scratch, mask_src, din, st);
-        }
-        RC(op_pack_layer(h, layer, wt, scratch, st));
-        return launch_conv_dgrad_bf16(layer, h->cfg.width, 1, B, dout, (float*)scratch, din, (float*)scratch + op_pack_floats(h), st);
-    }
-    if (layer >= 5) {
-        float* wc = (float*)scratch;
-        RC(launch_collapse_w(layer, wt, wc, st));
-        return launch_conv_up_dgrad(layer, h->cfg.width, B, dout, wc, mask_src, din, wc + conv_up_wc_floats(layer), st);
-    }
-    if (op_emulated(h, layer)) {
-        RC(op_pack_layer(h, layer, wt, scratch, st));
-        return launch_conv_dgrad_bf16(layer, h->cfg.width, bf16_mode(h), B, dout, (float*)scratch, din, (float*)scratch + op_pack_floats(h), st);
-    }
-    return launch_conv_dgrad(layer, h->cfg.width, B, dout, wt, mask_src, din, (float*)scratch, st);
+    RC(op_conv_check("cvae_op_conv_dgrad", h, layer, 1, 7, B, false, scratch));
+    ConvWeights forms; float* rest;
+    RC(op_weights(h, layer, wt, (float*)scratch, (hipStream_t)stream, &forms, &rest));
+    return conv_dgrad(h, layer, B, dout, forms, mask_src, din, rest, (hipStream_t)stream);
 }
 
 // [pack block | the step's scratch, which starts with room for one layer's collapsed weights and covers the split-K and weight-gradient
 // slabs of every precision's launchers and d4_bwd's workspace (carve)]
 int64_t cvae_op_scratch_floats(cvae_handle h, int32_t B) {
     const WsLayout w = carve(h, B);
-    return w.total - w.scratch + op_pack_floats(h);
+    return w.total - w.scratch + align_up(pack_floats(h), 64);
 }
 
 int cvae_op_conv_wgrad(cvae_handle h, int32_t layer, int32_t B, const float* in, const float* dout, float* dw,
                        float* dbias, void* scratch, void* stream) {
-    const int W = h->cfg.width;
-    hipStream_t st = (hipStream_t)stream;
-    float* sc = (float*)scratch;
-    if (layer == 0) return launch_e1_wgrad(W, B, in, dout, dw, dbias, sc, st);
-    if ((op_emulated(h, layer) || op_bf16(h, layer)) && !sc) { cvae_set_error("per-op conv_wgrad, layer %d: null scratch", layer); return CVAE_EINVAL; }
-    if (layer >= 5) return launch_conv_up_wgrad(layer, W, B, in, dout, dw, dbias, sc, st, use_bf16_wgrad(h, layer));      // bf16 mode: the step's bf16 kernel
-    if (op_emulated(h, layer) || op_bf16(h, layer)) return conv_wgrad(h, layer, B, in, dout, dw, dbias, sc, st);
-    return launch_conv_wgrad(layer, W, B, in, dout, dw, dbias, sc, st);
+    RC(op_conv_check("cvae_op_conv_wgrad", h, layer, 0, 7, B, true, scratch));
+    if (layer == 0) return launch_e1_wgrad(h->cfg.width, B, in, dout, dw, dbias, (float*)scratch, (hipStream_t)stream);
+    return conv_wgrad(h, layer, B, in, dout, dw, dbias, (float*)scratch, (hipStream_t)stream);
 }
 
 // bf16 mode: o3 / d_o3 in bf16, the Tanh backward applied while the kernel stages (`dout` is not written and may be null)
@@ -1368,14 +1368,13 @@ int cvae_op_d4_bwd(cvae_handle h, int32_t B, const float* o3, const float* d_rec
 // 128-pixel tiles behind one BatchNorm partial row of cvae_op_conv_fwd (the route table's; 1 for the per-tile kernels and layer 0)
 int32_t cvae_op_conv_tiles_per_partial(cvae_handle h, int32_t layer, int32_t B) {
     if (!h || layer < 0 || layer > 3 || B < 1) { cvae_set_error("cvae_op_conv_tiles_per_partial: null handle, layer %d outside [0, 3] or batch %d below 1", layer, B); return CVAE_EINVAL; }
-    if (layer == 0 || !use_bf16(h, layer)) return 1;
     return conv_route(h->cfg.precision, layer, h->cfg.width, false, B).tilesPerPartial;
 }
 
 // (tiles, splits, tiles per split) of cvae_op_conv_wgrad's kernel on a bf16 handle, from the launchers' own split arithmetic (no launch)
 int cvae_op_conv_wgrad_plan(cvae_handle h, int32_t layer, int32_t B, int32_t* out) {
     if (!h || !out || B < 1) { cvae_set_error("cvae_op_conv_wgrad_plan: null handle or output, or batch %d below 1", B); return CVAE_EINVAL; }
-    if (!op_bf16(h, layer)) { cvae_set_error("cvae_op_conv_wgrad_plan: layer %d on this handle does not run a bf16 weight-gradient kernel (bf16 handles, layers 1..7)", layer); return CVAE_EUNSUPPORTED; }
+    if (h->cfg.precision != 1 || layer < 1 || layer > 7) { cvae_set_error("cvae_op_conv_wgrad_plan: layer %d on this handle does not run a bf16 weight-gradient kernel (bf16 handles, layers 1..7)", layer); return CVAE_EUNSUPPORTED; }
     int plan[3] = {0, 0, 0};
     RC(layer >= 5 ? conv_up_wgrad_bf16_plan(layer, h->cfg.width, B, plan) : conv_wgrad_bf16_plan(layer, h->cfg.width, B, plan));
     for (int i = 0; i < 3; ++i) out[i] = plan[i];

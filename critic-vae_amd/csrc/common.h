@@ -212,10 +212,9 @@ int launch_conv_fwd(int layer, int width, int B, const float* in, const float* w
                     float* out, float* bnpart, float* ws, hipStream_t st);
 int64_t conv_fwd_ws_floats(int layer, int width, int B);
 int launch_conv_dgrad(int layer, int width, int B, const float* dout, const float* w,
-                      const float* mask_src, float* din, float* ws, hipStream_t st);   // ws may be null (no split-K)
+                      const float* mask_src, float* din, float* ws, hipStream_t st);   // ws: D0's split-K slabs at 64 x 64 (conv_dgrad_ws_floats)
 int64_t conv_dgrad_ws_floats(int layer, int width, int B);
 // conv_bf16.hip — precision mode 1: bf16-MFMA forward / dgrad / wgrad of layers 1..7
-bool conv_bf16_supported(int layer, int width);
 int64_t conv_bf16_pack_floats(int ns);
 int launch_pack_w_bf16(const float* const w[4], float* packed, int ns, hipStream_t st);     // ns = 1 (bf16) or 3 (fp32 emulation)
 int launch_conv_fwd_bf16(int layer, int width, int ns, int B, const float* in, const float* packed, const float* bias, float* out,
@@ -226,7 +225,6 @@ int launch_conv_up_fwd_bf16(int layer, int width, int ns, int B, const float* in
 int launch_conv_up_dgrad_bf16(int layer, int width, int ns, int B, const float* dout, const float* packed, const float* aux, float* din, hipStream_t st);
 int64_t wgrad_bf16_ws_floats(int layer, int width, int B);
 int launch_conv_wgrad_bf16(int layer, int width, int B, const float* in, const float* dout, float* dw, float* dbias, float* ws, hipStream_t st);
-bool conv_wgrad_split_supported(int products);
 int64_t wgrad_split_ws_floats(int layer, int width, int B);        // fp32-emulation modes: exact 3-way operand splits on the bf16 MFMA
 int launch_conv_wgrad_split(int layer, int width, int products, int B, const float* in, const float* dout, float* dw, float* dbias,
                             float* ws, hipStream_t st);

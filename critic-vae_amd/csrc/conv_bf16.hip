@@ -722,8 +722,6 @@ static int run4x4_bf16(const ConvBf16Args& a, hipStream_t st) {
     return 0;
 }
 
-bool conv_bf16_supported(int layer, int width) { return (width == 64 || width == 128) && layer >= 1 && layer <= 7; }
-
 // launcher code ns (1 bf16, 3 / 6 the fp32-emulation modes with nine / six partial products) -> cvae_config precision
 static int ns_precision(int ns) { return ns == 1 ? 1 : (ns == 3 ? 2 : 3); }
 

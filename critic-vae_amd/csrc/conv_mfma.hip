@@ -488,8 +488,7 @@ int launch_conv_fwd(int layer, int width, int B, const float* in, const float* w
     return -2;
 }
 
-// D0 dgrad at 4x4 images is 256 workgroups only: split-K over the co chunks when the caller
-// provides scratch (the training step and the single-op entry point do)
+// D0 dgrad at 4x4 images is 256 workgroups only: split-K over the co chunks, slabs in the caller's scratch
 static constexpr int D0_DGRAD_KSPLIT = 4;
 int64_t conv_dgrad_ws_floats(int layer, int width, int B) {
     if (layer != 4 || width != 64) return 0;
@@ -501,7 +500,7 @@ int launch_conv_dgrad(int layer, int width, int B, const float* dout, const floa
     // KCH = layer Cout (channels of dout), NCH = layer Cin (channels of din)
     if (!mask_src && conv_route(0, layer, width, true, B).family == CONV_PS) return launch_conv_mfma_ps(layer, width, true, B, dout, w, nullptr, din, nullptr, st);
     ConvArgs a{dout, w, nullptr, mask_src, din, nullptr, B, 0};
-    if (width == 64 && layer == 4 && ws != nullptr) {
+    if (width == 64 && layer == 4) {
         const int64_t slice = (int64_t)B * 16 * 256;
         a.out = ws; a.sliceFloats = slice;
         int rc = run4x4<128, 256, true, 64, D0_DGRAD_KSPLIT>(a, st);
@@ -513,7 +512,6 @@ int launch_conv_dgrad(int layer, int width, int B, const float* dout, const floa
             case 1: return run<64, 32, 32, true, 32, EPI_PLAIN>(a, st);
             case 2: return run<128, 64, 16, true, 64, EPI_PLAIN>(a, st);
             case 3: return run<256, 128, 8, true, 32, EPI_PLAIN>(a, st);
-            case 4: return run<128, 256, 4, true, 32, EPI_PLAIN>(a, st);
         }
     }
     if (width == 128) {

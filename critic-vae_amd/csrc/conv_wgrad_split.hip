@@ -238,7 +238,6 @@ static int dispatch_wgrad_split(int layer, int width, int products, int B, const
     cvae_set_error("conv_wgrad_split: unsupported layer %d at width %d", layer, width);
     return -2;
 }
-bool conv_wgrad_split_supported(int products) { return products == 6 || products == 9; }
 int64_t wgrad_split_ws_floats(int layer, int width, int B) {
     int64_t need = 0;
     if (dispatch_wgrad_split(layer, width, 6, B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need) != 0) return 0;

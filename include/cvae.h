@@ -892,22 +892,35 @@ int cvae_probe_read(cvae_handle h, int32_t id, float* ms_host, int32_t cap);
  * encoder conv blocks E1..E4 (vae_nets.py:69,74,79,84), 4..8 = decoder convs D0..D4
  * (vae_nets.py:117,121,125,129,133).  Activations are NHWC except x/recon (NCHW); decoder
  * layers 5..8 read the stored (pre-Upsample) tensor.  `scratch` needs cvae_op_scratch_floats().
- * On a handle of the fp32-emulation modes (precision 2, 3) the conv ops of layers 1..4 run the kernels
- * the step runs there: forward and input gradient on the bf16 MFMA with 3-way split operands (the
- * fp32 weight is packed into `scratch` first), weight gradient on the split-operand kernel.  All
- * tensors stay fp32; cvae_op_scratch_floats() includes the packed copy, and a null `scratch` on
- * these paths is CVAE_EINVAL.  Every other layer of these handles, and every layer of precision 0,
- * runs the fp32 kernels.
- * On a bf16 handle (precision 1) the conv ops run what the step runs there, on tensors in the
- * handle's storage type: activations and activation gradients (in, out, dout, din, mask_src, o3,
- * d_o3) are bf16 behind the float pointers; weights, biases, their gradients, recon and d_recon
- * are fp32.  cvae_op_conv_fwd / cvae_op_conv_dgrad of layers 1..4 pack the layer's weights into
- * `scratch` and take conv_route's kernel family at that batch (D0: split-K + finish at 64 x 64);
- * layers 5..7 collapse and pack them and run the bf16 up-conv kernels (mask_src in bf16); layer 8
- * and cvae_op_d4_bwd run D4's bf16 forms (the Tanh backward is applied inside: `dout` is not
- * written and may be null); cvae_op_conv_wgrad of layers 1..7 runs the bf16 weight-gradient
- * kernels.  Layer 0's weight gradient stays the fp32 kernel on fp32 tensors: its bf16 form exists
- * only fused with block 0's BatchNorm backward.  A null `scratch` on these paths is CVAE_EINVAL.
+ * The conv ops of layers 1..7 run the kernels the step runs there: the step and these entry points
+ * choose their launcher in the same three functions over one table of (precision, layers) rows
+ * (api.hip, kConvTable), and a call on the operands the step stored stores the words the step
+ * stored.  Layers 0 and 8 (E1, D4) are not in the table: the step runs their fused forms, these
+ * entry points the plain ones.
+ * On a handle of the fp32-emulation modes (precision 2, 3) that is, for layers 1..4: forward and
+ * input gradient on the bf16 MFMA with 3-way split operands (the fp32 weight is packed into
+ * `scratch` first), weight gradient on the split-operand kernel.  All tensors stay fp32;
+ * cvae_op_scratch_floats() includes the packed copy.  Every other layer of these handles, and every
+ * layer of precision 0, runs the fp32 kernels (layers 5..7: the weight is collapsed into `scratch`).
+ * On a bf16 handle (precision 1) the tensors are in the handle's storage type: activations and
+ * activation gradients (in, out, dout, din, mask_src, o3, d_o3) are bf16 behind the float pointers;
+ * weights, biases, their gradients, recon and d_recon are fp32.  cvae_op_conv_fwd /
+ * cvae_op_conv_dgrad of layers 1..4 pack the layer's weights into `scratch` and take conv_route's
+ * kernel family at that batch (D0: split-K + finish at 64 x 64); layers 5..7 collapse and pack them
+ * and run the bf16 up-conv kernels (mask_src in bf16); layer 8 and cvae_op_d4_bwd run D4's bf16
+ * forms (the Tanh backward is applied inside: `dout` is not written and may be null);
+ * cvae_op_conv_wgrad of layers 1..7 runs the bf16 weight-gradient kernels.  Layer 0's weight
+ * gradient stays the fp32 kernel on fp32 tensors: its bf16 form exists only fused with block 0's
+ * BatchNorm backward.
+ * The three cvae_op_conv_* entry points check their arguments before any device access and return
+ * CVAE_EINVAL, with cvae_last_error() naming the argument, for a null handle, a layer outside the
+ * entry's range (forward 0..8, input gradient 1..7, weight gradient 0..7), a batch outside
+ * [1, max_batch], and a null `scratch` on a pass that uses it.  On every precision alike that is:
+ * every weight gradient; forward and input gradient of every layer whose weights are prepared in
+ * `scratch` (packed: layers 1..7 of precision 1, 1..4 of precision 2 and 3; collapsed: layers
+ * 5..7 of every precision) and of D0 (layer 4) at 64 x 64, whose split-K slabs live there.  A null
+ * `scratch` is valid everywhere else: layers 0 and 8, layers 1..3 of precision 0, D0 of
+ * precision 0 at 128 x 128.
  * ---------------------------------------------------------------------------------------- */
 int64_t cvae_op_scratch_floats(cvae_handle h, int32_t batch);
 int64_t cvae_op_bn_partial_floats(cvae_handle h, int32_t layer, int32_t batch);

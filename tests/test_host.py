@@ -155,6 +155,37 @@ def test_latent_ops_refuse_bad_batches_and_null_scratch():
         assert h.op_latent_scratch_floats(B) >= max(32 * B * 64, 34 * 4096) + B * 64
 
 
+@pytest.mark.parametrize("W", [64, 128])
+@pytest.mark.parametrize("precision", ["f32", "bf16", "bf16x9", "bf16x6"])
+def test_conv_ops_refuse_bad_handles_layers_batches_and_null_scratch(precision, W):
+    """cvae_op_conv_fwd / dgrad / wgrad: a null handle, a layer outside the entry's range, batch < 1, batch > max_batch, or a null
+    scratch on a pass whose row of the conv table uses scratch is CVAE_EINVAL before anything is launched, and the error string names
+    the cause (the pointers here are not device memory; no call below is one that is accepted)."""
+    h = cvlib.Handle(W, 8, precision=precision)
+    lib, p = h.lib, 0x1000
+    entries = [("cvae_op_conv_fwd", lib.cvae_op_conv_fwd, 5, range(0, 9)), ("cvae_op_conv_dgrad", lib.cvae_op_conv_dgrad, 4, range(1, 8)),
+               ("cvae_op_conv_wgrad", lib.cvae_op_conv_wgrad, 4, range(0, 8))]
+
+    def refused(name, fn, n_ptr, handle, layer, B, scratch, cause):
+        assert fn(handle, layer, B, *[p] * n_ptr, scratch, None) == -1, (name, layer, B, scratch)
+        err = lib.cvae_last_error().decode()
+        assert name in err and cause in err, (name, layer, B, scratch, err)
+
+    for name, fn, n_ptr, layers in entries:
+        refused(name, fn, n_ptr, None, layers[0], 8, p, "null handle")
+        for layer in layers:
+            for B in (0, -1, 9):
+                refused(name, fn, n_ptr, h.h, layer, B, p, f"batch {B} outside [1, 8]")
+        for layer in (layers[0] - 1, layers[-1] + 1, 100):
+            refused(name, fn, n_ptr, h.h, layer, 8, p, f"layer {layer} outside [{layers[0]}, {layers[-1]}]")
+    # a null scratch: every weight gradient; forward and input gradient of every bf16 or emulated pass (layers 1..7 of a bf16 handle, 1..4
+    # of the emulation modes), of every up-conv pass (layers 5..7) and of D0 at 64 x 64 in fp32
+    fd_layers = {"f32": [5, 6, 7] + ([4] if W == 64 else []), "bf16": list(range(1, 8))}.get(precision, list(range(1, 8)))
+    for name, fn, n_ptr, layers in entries:
+        for layer in (layers if name == "cvae_op_conv_wgrad" else fd_layers):
+            refused(name, fn, n_ptr, h.h, layer, 8, None, "null scratch")
+
+
 def test_two_handles_do_not_share_state():
     """include/cvae.h: one handle per device / configuration, no global state."""
     a, b = cvlib.Handle(64, 4), cvlib.Handle(128, 2, precision="bf16")
