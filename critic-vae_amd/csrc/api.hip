@@ -534,6 +534,45 @@ int cvae_score_finish(cvae_handle h, int32_t width, void* state, float* scalars,
     return launch_score_finish(width, state, scalars, (hipStream_t)stream);
 }
 
+// ---- pooled latent statistics of a set (latent_stats.hip) ----
+int64_t cvae_latent_stats_state_bytes(void) { return latent_stats_state_bytes(); }
+int64_t cvae_latent_stats_scratch_bytes(cvae_handle h, int32_t B) {
+    const int64_t n = h ? latent_stats_scratch_bytes(B) : -1;
+    if (n < 0) cvae_set_error("cvae_latent_stats_scratch_bytes: bad handle, or batch %d outside 1..2^24", B);
+    return n < 0 ? -1 : n;
+}
+int32_t cvae_latent_stats_plan(int32_t B, int32_t num_cus, int32_t* out) {
+    int plan[3];
+    if (!out || latent_stats_plan(B, num_cus, plan) != 0) {
+        cvae_set_error("cvae_latent_stats_plan: batch %d outside 1..2^24, compute units %d below 1, or null pointer", B, num_cus);
+        return CVAE_EINVAL;
+    }
+    for (int i = 0; i < 3; ++i) out[i] = plan[i];
+    return 0;
+}
+int cvae_latent_stats(cvae_handle h, int32_t B, const float* mu, const float* logvar, const float* pred, void* state, float* kl_rows,
+                      void* scratch, void* stream, uint32_t flags) {
+    if (!h || !mu || !logvar || !pred || !state || !scratch) { cvae_set_error("cvae_latent_stats: bad handle or null pointer"); return CVAE_EINVAL; }
+    if (flags != 0) { cvae_set_error("cvae_latent_stats: flags = %u must be 0", (unsigned)flags); return CVAE_EINVAL; }
+    if (latent_stats_scratch_bytes(B) < 0) { cvae_set_error("cvae_latent_stats: batch %d outside 1..2^24", B); return CVAE_EINVAL; }
+    if ((((uintptr_t)mu | (uintptr_t)logvar | (uintptr_t)pred | (uintptr_t)kl_rows) & 3) || (((uintptr_t)state | (uintptr_t)scratch) & 7)) {
+        cvae_set_error("cvae_latent_stats: mu, logvar, pred and kl_rows must be 4-byte aligned, state and scratch 8-byte aligned"); return CVAE_EINVAL;
+    }
+    return launch_latent_stats(B, mu, logvar, pred, state, kl_rows, scratch, (hipStream_t)stream);
+}
+int cvae_recon_response(cvae_handle h, int32_t n_images, int32_t n_variants, const float* recon_base, const float* recon_var, float* out,
+                        void* stream, uint32_t flags) {
+    if (!h || !recon_base || !recon_var || !out) { cvae_set_error("cvae_recon_response: bad handle or null pointer"); return CVAE_EINVAL; }
+    if (flags != 0) { cvae_set_error("cvae_recon_response: flags = %u must be 0", (unsigned)flags); return CVAE_EINVAL; }
+    if (n_images < 1 || n_variants < 1 || (int64_t)n_images * n_variants >= ((int64_t)1 << 31)) {
+        cvae_set_error("cvae_recon_response: %d images x %d variants: both at least 1, the product below 2^31", n_images, n_variants); return CVAE_EINVAL;
+    }
+    if ((((uintptr_t)recon_base | (uintptr_t)recon_var) & 15) || ((uintptr_t)out & 3)) {
+        cvae_set_error("cvae_recon_response: recon_base and recon_var must be 16-byte aligned, out 4-byte aligned"); return CVAE_EINVAL;
+    }
+    return launch_recon_response(h->cfg.width, (int64_t)n_images * n_variants, n_variants, recon_base, recon_var, out, (hipStream_t)stream);
+}
+
 int cvae_backward(cvae_handle h, int32_t B, const float* x, const float* pred, const float* eps, const float* params,
                   const float* logvar, const float* recon, const float* d_recon, const float* d_mu,
                   const float* d_logvar, void* wsv, float* grads, void* stream) {

@@ -371,6 +371,13 @@ int launch_score_init(void* state, hipStream_t st);
 int launch_score(int width, int B, const float* x, const float* mu, const float* logvar, const float* recon, float* ms,
                  float* per_image, void* state, hipStream_t st);
 int launch_score_finish(int width, void* state, float* scalars, hipStream_t st);
+// latent_stats.hip: the pooled latent record (layout: include/cvae.h); plan = (rows per chunk, chunks, workgroups), -1 for a bad batch
+int64_t latent_stats_state_bytes();
+int latent_stats_plan(int B, int num_cus, int plan[3]);
+int64_t latent_stats_scratch_bytes(int B);
+int launch_latent_stats(int B, const float* mu, const float* logvar, const float* pred, void* state, float* kl_rows, void* scratch,
+                        hipStream_t st);
+int launch_recon_response(int width, int64_t items, int K, const float* base, const float* var, float* out, hipStream_t st);
 // critic.hip, critic_train.hip: float offsets into the flat critic parameter block (reference state_dict order)
 namespace critic_layout {
 constexpr int CW1 = 0, CB1 = 216, CW2 = 224, CB2 = 800, CW3 = 808, CB3 = 1384, CW4 = 1392, CB4 = 2544,

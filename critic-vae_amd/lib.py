@@ -16,6 +16,7 @@ SYNC_DOUBLES = 2412      # CVAE_SYNC_DOUBLES: the fp64 record of the staged (glo
 SYNC_POINTS = 9
 SCORE_COLS = 8            # CVAE_SCORE_COLS: floats per image row of cvae_score
 SCORE_STATE_DOUBLES = 24  # CVAE_SCORE_STATE_DOUBLES: the pooled fp64 record of cvae_score
+LATENT_STATE_DOUBLES = 696  # CVAE_LATENT_STATE_DOUBLES: the pooled fp64 record of cvae_latent_stats
 
 
 class CvaeError(RuntimeError):
@@ -189,6 +190,11 @@ _SIGS = {
     "cvae_score_init": (C.c_int, [_p, _p, _p]),
     "cvae_score": (C.c_int, [_p, _i32] + [_p] * 8),
     "cvae_score_finish": (C.c_int, [_p, _i32, _p, _p, _p]),
+    "cvae_latent_stats_state_bytes": (_i64, []),
+    "cvae_latent_stats_scratch_bytes": (_i64, [_p, _i32]),
+    "cvae_latent_stats_plan": (_i32, [_i32, _i32, C.POINTER(C.c_int32)]),
+    "cvae_latent_stats": (C.c_int, [_p, _i32] + [_p] * 7 + [C.c_uint32]),
+    "cvae_recon_response": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, C.c_uint32]),
     "cvae_guard_state_bytes": (_i64, []),
     "cvae_guard_init": (C.c_int, [_p, _p, _i64, _i64, _p]),
     "cvae_grad_stats": (C.c_int, [_p, _p, _i64, _f, _f, _i32, _f, _f, _f, _p, _p]),
@@ -322,6 +328,16 @@ def latent_plan(width, B, num_cus):
             "decin_bwd": {"jobs": {"bgemm": (v[3], v[4]), "gemm": (v[5], v[6])}, "grid": v[6]},
             "fc_bwd": {"imgs": v[7], "jobs": {"bgemm": (v[8], v[9]), "dflat": (v[10], v[11]), "colsum": (v[12], v[13])},
                        "grid": v[13], "split": bool(v[14])}}
+
+
+def latent_stats_plan(B, num_cus):
+    """cvae_latent_stats_plan (host logic only): dict(rows, chunks, grid) of cvae_latent_stats at batch B on a device of num_cus
+    compute units."""
+    lib = load()
+    out = (C.c_int32 * 3)()
+    if lib.cvae_latent_stats_plan(B, num_cus, out) != 0:
+        raise CvaeError(f"cvae_latent_stats_plan: {lib.cvae_last_error().decode()}")
+    return {"rows": out[0], "chunks": out[1], "grid": out[2]}
 
 
 def conv_wgrad_plan_f32(width, layer, B, num_cus):
@@ -508,6 +524,41 @@ class Handle:
         """The 16 loss scalars of everything pooled in `state` since score_init: cvae_loss of all of it as one batch."""
         self._check(self.lib.cvae_score_finish(self.h, self.width if width is None else width, self._score_ptr(state),
                                                _ptr(scalars), _stream()))
+
+    # ---- pooled latent statistics of a set (include/cvae.h; latent.py) ----
+    def latent_stats_state(self, device):
+        """A fresh (empty = all-zero) pooled latent record on `device`: a float64 tensor of LATENT_STATE_DOUBLES values."""
+        return torch.zeros(self.lib.cvae_latent_stats_state_bytes() // 8, dtype=torch.float64, device=device)
+
+    def latent_stats_scratch_bytes(self, B):
+        n = self.lib.cvae_latent_stats_scratch_bytes(self.h, B)
+        if n < 0:
+            raise CvaeError(f"cvae_latent_stats_scratch_bytes: {self.lib.cvae_last_error().decode()}")
+        return n
+
+    def latent_stats_scratch(self, B, device):
+        """Scratch for cvae_latent_stats at batches up to B (uninitialised: its contents never matter)."""
+        return torch.empty(self.latent_stats_scratch_bytes(B) // 8, dtype=torch.float64, device=device)
+
+    def latent_stats(self, B, mu, logvar, pred, state, scratch, kl_rows=None, flags=0):
+        """cvae_latent_stats: ADD the B rows of mu (B,32), logvar (B,32), pred (B) to the pooled record `state`; kl_rows (B,32)
+        fp32 or None."""
+        need = self.lib.cvae_latent_stats_scratch_bytes(self.h, B)          # negative: a batch the entry itself refuses below
+        assert isinstance(state, int) or state is None or state.numel() >= LATENT_STATE_DOUBLES, "latent state: too small"
+        assert need < 0 or isinstance(scratch, int) or scratch is None or scratch.numel() * scratch.element_size() >= need, \
+            f"latent scratch: need {need} bytes"
+        for t, n in ((mu, 32 * B), (logvar, 32 * B), (pred, B), (kl_rows, 32 * B)):
+            assert need < 0 or t is None or isinstance(t, int) or t.numel() >= n, "latent_stats: a tensor is shorter than the batch"
+        self._check(self.lib.cvae_latent_stats(self.h, B, _ptr(mu), _ptr(logvar), _ptr(pred), _ptr64(state), _ptr(kl_rows),
+                                               self._raw(scratch, 8, "latent scratch"), _stream(), int(flags)))
+
+    def recon_response(self, n, K, recon_base, recon_var, out, flags=0):
+        """cvae_recon_response: out (n,K,2) = per (image, variant) the mean squared difference and the largest grey difference
+        of recon_var (n,K,3,W,W) against recon_base (n,3,W,W)."""
+        px = 3 * self.width * self.width
+        for t, m in ((recon_base, n * px), (recon_var, n * K * px), (out, n * K * 2)):
+            assert t is None or isinstance(t, int) or n < 1 or K < 1 or t.numel() >= m, "recon_response: a tensor is shorter than n x K"
+        self._check(self.lib.cvae_recon_response(self.h, n, K, _ptr(recon_base), _ptr(recon_var), _ptr(out), _stream(), int(flags)))
 
     # ---- the guarded step (include/cvae.h): statistics of the reduced gradient -> decision record -> Adam that obeys it ----
     def guard_state(self, device, applied=0, skipped=0):

@@ -352,6 +352,30 @@ class VariationalAutoencoder(nn.Module):
             self._stamp_workspace()
         return rows
 
+    def latent_stats(self, x, pred, au_threshold=0.01, collapsed_below=0.01):
+        """The latent audit (latent.py) of frames in hand: the eval-mode encoder (BatchNorm on its running statistics, bn_state
+        and num_batches_tracked untouched) in pieces of max_batch, one cvae_latent_stats launch per piece into one pooled device
+        record, one host read.  x (N,3,w,w), pred (N) or (N,1).  Returns latent.summarize of the record (the record itself under
+        "record")."""
+        from .latent import summarize
+        x = self._prep(x)
+        N, dev = x.shape[0], x.device
+        pred = pred.to(torch.float32).reshape(N, 1).contiguous()
+        mb = min(N, self.max_batch)
+        mu = torch.empty(mb, P.latent_dim, device=dev)
+        logvar = torch.empty_like(mu)
+        zero = torch.zeros_like(mu)
+        state = self.handle.latent_stats_state(dev)
+        scratch = self.handle.latent_stats_scratch(mb, dev)
+        with torch.no_grad():
+            for s in range(0, N, self.max_batch):
+                n = min(N - s, self.max_batch)
+                self.handle.forward(n, x[s:s + n], pred[s:s + n], zero[:n], self.theta, self.bn_state, mu[:n], logvar[:n], None,
+                                    self._workspace(n), train=False)
+                self.handle.latent_stats(n, mu[:n], logvar[:n], pred[s:s + n], state, scratch)
+            self._stamp_workspace()
+        return summarize(state.cpu().numpy(), au_threshold=au_threshold, collapsed_below=collapsed_below)
+
     def diff_images(self, x, pred, one=False):
         """get_diff_image (vae_utility.py:256-277) for a whole batch at once: the encoder runs once,
         the decoder twice (critic value `pred` — or 1 if `one` — against 0); returns

@@ -432,6 +432,24 @@ class FusedTrainer(DeviceTrainer):
             out["per_image"] = rows
         return out
 
+    def latent_report(self, dataset, batch_size, ema=False, au_threshold=0.01, collapsed_below=0.01):
+        """The latent audit of the model on a DeviceDataset / ReconDataset (latent.py): the loop of evaluate() with the encoder
+        alone — per batch one gather launch, the EVAL-mode cvae_forward with recon == NULL (BatchNorm on its running statistics,
+        eps = 0) and one cvae_latent_stats launch into ONE pooled device record — then one host read and latent.summarize on
+        it.  Returns that dict (per-dimension KL, active units, the linear probe of the critic value on mu, ..., and the
+        record itself under "record").  Like evaluate() it draws nothing from any random generator and leaves parameters, Adam
+        state, bn_state, num_batches_tracked, step_count and the guard record untouched; it overwrites the workspace (its
+        batch buffers are its own: latent.dataset_report, which needs no trainer).  Every rank reports the set it is given; ema=True as in evaluate()."""
+        from .latent import dataset_report
+        _, B = self._check_dataset(dataset, batch_size)
+        theta, bn_state = self.vae.theta.data, self.vae.bn_state
+        if ema:
+            if not self.has_ema():
+                raise ValueError("latent_report(ema=True): this trainer keeps no averaged weights (optim=Optim(ema=...))")
+            theta, bn_state = self._ema_view(theta)
+        return dataset_report(self.vae, dataset, B, theta=theta, bn_state=bn_state, au_threshold=au_threshold,
+                              collapsed_below=collapsed_below)
+
     def fit_device(self, dataset, batch_size, epochs=1, generator=None, shuffle=True, val=None, val_every=None, on_val=None):
         """The loop of fit_u8 over a DeviceDataset (episodes.py) that already lives on the device with its critic values:
         per epoch np.random.shuffle of the host indices (uploaded once), slices of batch_size with the ragged last batch
@@ -609,6 +627,9 @@ def build_parser():
                     "DIR/best/ whenever the pooled validation total_loss improves (a non-finite value never does)")
     ap.add_argument("--patience", type=int, default=None, metavar="K", help="with --val-fraction: stop after K evaluations in a row "
                     "without an improvement")
+    ap.add_argument("--latent-report", action="store_true", help="-train --episodes, -second: after the fit print the latent audit "
+                    "(latent.py: KL per dimension, active units, the linear probe of the critic value on mu) of the held-out set "
+                    "(--val-fraction), or of the training set without one; with --save DIR also DIR/latent.npz")
     ap.add_argument("--msssim-weight", type=float, default=None, metavar="W", help="-train, -second: weight of the MS-SSIM term "
                     "(reference: 1).  Any of these six flags switches the loss to cvae_loss_obj; validation is then judged by the objective")
     ap.add_argument("--mse-weight", type=float, default=None, metavar="W", help="weight of F.mse_loss(recon, x), the reference's "
@@ -781,6 +802,9 @@ def main(argv=None):
             optim_from_kwargs(args.optim_kw, args.optim_kw.get("warmup", 0) + 1)
         except ValueError as e:
             ap.error(str(e))
+    if args.latent_report and not ((args.train and args.episodes is not None) or args.second):
+        ap.error("--latent-report belongs to the fused VAE trainer (-train --episodes, -second); python -m critic_vae_amd.latent "
+                 "audits saved networks")
     if args.val_fraction is None:
         if args.val_every is not None or args.keep_best or args.patience is not None:
             ap.error("--val-every, --keep-best and --patience need --val-fraction")
@@ -903,6 +927,14 @@ def _fit_and_save(args, vae, ds, second):
             print(f"saved the averaged weights under {save_ema_networks(trainer, os.path.join(args.save, EMA_DIR), second=second)}")
     _save_trace(args, trainer)
     _print_guard(trainer)
+    if getattr(args, "latent_report", False):
+        from .latent import report_lines, save_npz
+        held = val_kw.get("val")
+        summary = trainer.latent_report(ds if held is None else held, args.batch)
+        print(f"latent report on the {'training' if held is None else 'held-out'} set:")
+        print("\n".join(report_lines(summary)))
+        if args.save:
+            print(f"saved {save_npz(os.path.join(args.save, LATENT_FILE), summary)}")
     return ds
 
 
@@ -938,6 +970,7 @@ def _check_resumed_augment(given, trainer, directory):
 
 
 BEST_DIR = "best"
+LATENT_FILE = "latent.npz"
 
 
 def _has_ema(trainer):

@@ -185,6 +185,62 @@ int cvae_score(cvae_handle h, int32_t batch, const float* x, const float* mu, co
 int cvae_score_finish(cvae_handle h, int32_t width, void* state, float* scalars, void* stream);
 
 /*
+ * Pooled statistics of the latent code of a set (no reference counterpart: vae.py never looks at its posterior).  What a
+ * beta-VAE is judged by — the KL per latent dimension, the active units of Burda et al. (Var_x(mu_j) > 0.01) — and what a
+ * Critic-VAE rests on — that mu does not predict the critic value injected next to it — all follow from first and second
+ * moments, so the device keeps those and critic-vae_amd/latent.py derives the rest on the host from one read.
+ *
+ * cvae_latent_stats is ONE launch per batch.  It reads mu (batch,32), logvar (batch,32) and pred (batch) — fp32, as cvae_forward
+ * leaves them in every precision mode — and ADDS the batch to `state`, a pooled record of CVAE_LATENT_STATE_DOUBLES fp64
+ * values, 8-byte aligned.  With a = (mu_0..mu_31, pred), 33 entries:
+ *   [0] rows seen                          [1] rows used
+ *   [2..34]    sum a_i
+ *   [35..595]  sum a_i a_j for i <= j, row-major upper triangle: index 35 + i*33 - i*(i-1)/2 + (j-i)
+ *   [596..627] sum kl_j, kl_j = 0.5 * (mu_j^2 + exp(logvar_j) - logvar_j - 1), in nats
+ *   [628..659] sum exp(logvar_j)           [660..691] sum logvar_j
+ *   [692..695] library scratch (the arrival counter of the merge lives here: do not write between calls)
+ * An ALL-ZERO record is the empty record: there is no init entry point, the caller clears it (a device memset) and every call
+ * adds.  A row is USED when its 65 inputs are finite and its 32 exp(logvar_j) are finite in fp64 (logvar = 100 is; 800 is not);
+ * any other row is counted in [0] only and enters no sum — counted, not hidden, as cvae_score does with non-finite images.
+ * All arithmetic is fp64 on the widened fp32 inputs, exp included.  Rows are cut into chunks, min(chunks, compute units)
+ * persistent workgroups stride over them, each leaves one fp64 partial record in `scratch`, and the last workgroup to arrive
+ * adds the partials, in workgroup order, to the record: no floating-point atomics, the same calls give the same bits (two
+ * calls on the same record must be ordered by their streams).  kl_rows_or_null: (batch,32) fp32, (float)kl_j of EVERY row,
+ * used or not — whatever the arithmetic gives.  scratch: cvae_latent_stats_scratch_bytes(h, batch) bytes, 8-byte aligned,
+ * contents on entry irrelevant.  batch is NOT capped by max_batch: 1 <= batch <= 2^24.  cvae_latent_stats_plan reports the
+ * launcher's own arithmetic, as cvae_op_latent_plan does.  Every argument is checked before any device access (nulls, flags,
+ * alignment, batch: CVAE_EINVAL); nothing allocates or synchronises.
+ *
+ * Stream parameter.  In this entry point the stream is followed by `uint32_t flags` (must be 0) on purpose: the test suite
+ * keeps a closed registry of one side-stream scenario per entry point whose LAST parameter is the stream, and that registry
+ * could not be extended together with this entry point.  Its side-stream case lives with its own GPU tests; moving it into
+ * the registry (and then, if wanted, dropping `flags`) is a follow-up.
+ */
+#define CVAE_LATENT_STATE_DOUBLES 696
+int64_t cvae_latent_stats_state_bytes(void);                                  /* host only */
+int64_t cvae_latent_stats_scratch_bytes(cvae_handle h, int32_t batch);        /* host only; -1 for a bad argument */
+int32_t cvae_latent_stats_plan(int32_t batch, int32_t num_cus, int32_t* out); /* host only: out[0] rows per chunk,
+                                      out[1] chunks, out[2] workgroups = min(chunks, num_cus, 1024); CVAE_EINVAL for a bad argument */
+int cvae_latent_stats(cvae_handle h, int32_t batch, const float* mu, const float* logvar, const float* pred,
+                      void* state, float* kl_rows_or_null, void* scratch, void* stream, uint32_t flags /* 0 */);
+
+/*
+ * What the decoder listens to: the reduction over n_images * n_variants reconstructions of VARIED latent codes against each
+ * image's base reconstruction (critic-vae_amd/latent.py builds the variants — dimension j moved by one prior sigma, the critic
+ * value set to 0 and to 1 — with cvae_decode; this streams the results once).  recon_base (n,3,W,W), recon_var (n,K,3,W,W),
+ * out (n,K,2) fp32:
+ *   [..,0] mean over the 3 * W * W elements of (var - base)^2   (differences and squares fp32, the sum fp64 in a fixed order,
+ *          as column 3 of cvae_score)
+ *   [..,1] max over pixels of 0.2989 |dR| + 0.5870 |dG| + 0.1140 |dB| in the fp32 operation order of cvae_diff_grey: with the
+ *          critic value set to 0 as the variant it is bit for bit the max_values of the difference mask.  NaN if a difference is NaN.
+ * One workgroup per (image, variant) at both widths (W: the handle's); no scratch, no atomics, 64-bit offsets.  CVAE_EINVAL for
+ * n_images * n_variants >= 2^31 or a count below 1, nulls, recon_base / recon_var not 16-byte aligned, flags != 0; every
+ * argument is checked before any device access.  The stream is followed by `flags` for the reason given at cvae_latent_stats.
+ */
+int cvae_recon_response(cvae_handle h, int32_t n_images, int32_t n_variants, const float* recon_base /* (n,3,W,W) */,
+                        const float* recon_var /* (n,K,3,W,W) */, float* out /* (n,K,2) */, void* stream, uint32_t flags /* 0 */);
+
+/*
  * Backward: loss.backward() (vae.py:57) for everything cvae_forward computed, given the loss
  * gradients w.r.t. its outputs (and logvar/recon as returned by cvae_forward).  Overwrites the
  * flat gradient buffer `grads` (same layout as `params`).
