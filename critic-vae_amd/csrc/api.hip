@@ -1384,11 +1384,18 @@ int cvae_op_conv_dgrad(cvae_handle h, int32_t layer, int32_t B, const float* dou
     return conv_dgrad(h, layer, B, dout, forms, mask_src, din, rest, (hipStream_t)stream);
 }
 
+// cvae_op_e1_wgrad_fused with flag bit 0: [E1's weight-gradient workspace | packed bf16 frame | partials of the statistics pass]
+static int64_t e1_fused_xp_floats(const cvae_handle_s* h, int B) {
+    const int64_t W = h->cfg.width;
+    return align_up(e1_wgrad_ws_floats((int)W, B), 64) + align_up((int64_t)B * W * W * 2, 64) + (int64_t)2 * bn_num_tiles(0, (int)W, B) * 32;
+}
 // [pack block | the step's scratch, which starts with room for one layer's collapsed weights and covers the split-K and weight-gradient
-// slabs of every precision's launchers and d4_bwd's workspace (carve)]
+// slabs of every precision's launchers and d4_bwd's workspace (carve)]; on a bf16 handle at least what
+// cvae_op_e1_wgrad_fused lays out with flag bit 0
 int64_t cvae_op_scratch_floats(cvae_handle h, int32_t B) {
     const WsLayout w = carve(h, B);
-    return w.total - w.scratch + align_up(pack_floats(h), 64);
+    const int64_t n = w.total - w.scratch + align_up(pack_floats(h), 64);
+    return h->cfg.precision == 1 && e1_fused_xp_floats(h, B) > n ? e1_fused_xp_floats(h, B) : n;
 }
 
 int cvae_op_conv_wgrad(cvae_handle h, int32_t layer, int32_t B, const float* in, const float* dout, float* dw,
@@ -1396,6 +1403,39 @@ int cvae_op_conv_wgrad(cvae_handle h, int32_t layer, int32_t B, const float* in,
     RC(op_conv_check("cvae_op_conv_wgrad", h, layer, 0, 7, B, true, scratch));
     if (layer == 0) return launch_e1_wgrad(h->cfg.width, B, in, dout, dw, dbias, (float*)scratch, (hipStream_t)stream);
     return conv_wgrad(h, layer, B, in, dout, dw, dbias, (float*)scratch, (hipStream_t)stream);
+}
+
+// E1's weight gradient as the step runs it (block_grads(0)): block 0's BatchNorm / pool / ReLU backward applied while the kernel stages
+// its tiles.  Host-only checks first, as in op_conv_check.  flags bit 0 (bf16 handles): the statistics pass of the forward writes the
+// packed bf16 frame into `scratch` and the kernel stages its strips from it, as after a train-mode forward.
+int cvae_op_e1_wgrad_fused(cvae_handle h, int32_t B, const float* x, const float* y0, const float* a0, const float* d_a0,
+                           const float* coef0, const float* bcoef0, const float* w1, const float* b1, float* dw, float* dbias,
+                           void* scratch, int32_t flags, void* stream) {
+    const char* who = "cvae_op_e1_wgrad_fused";
+    if (!h) { cvae_set_error("%s: null handle", who); return CVAE_EINVAL; }
+    if (B < 1 || B > h->cfg.max_batch) { cvae_set_error("%s: batch %d outside [1, %d]", who, B, h->cfg.max_batch); return CVAE_EINVAL; }
+    const bool bf16 = io_bf16(h);
+    const struct { const void* p; const char* name; bool needed; } args[] = {
+        {x, "x", true}, {y0, "y0", !bf16}, {a0, "a0", true}, {d_a0, "d_a0", true}, {coef0, "coef0", true}, {bcoef0, "bcoef0", true},
+        {w1, "w1", bf16}, {b1, "b1", bf16}, {dw, "dw", true}, {scratch, "scratch", true}};
+    for (const auto& a : args)
+        if (a.needed && !a.p) { cvae_set_error("%s: null %s (y0 may be null on bf16 handles only, w1 and b1 on the others)", who, a.name); return CVAE_EINVAL; }
+    if (flags & ~1) { cvae_set_error("%s: unknown flag bits in flags = %d (bit 0: stage the packed bf16 frame)", who, flags); return CVAE_EINVAL; }
+    const int W = h->cfg.width;
+    if ((flags & 1) && !bf16) { cvae_set_error("%s: flags bit 0 (packed bf16 frame) on a handle that is not bf16", who); return CVAE_EINVAL; }
+    if ((flags & 1) && conv_route(1, 0, W, false, B).family != E1_PACKED_FRAME) {
+        cvae_set_error("%s: flags bit 0 at batch %d, where the step stages the fp32 frame (cvae_conv_route)", who, B); return CVAE_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* sc = (float*)scratch;
+    const float* xp = nullptr;
+    if (flags & 1) {
+        float* xpf = sc + align_up(e1_wgrad_ws_floats(W, B), 64);
+        RC(launch_e1_fwd(W, B, x, w1, b1, nullptr, xpf + align_up((int64_t)B * W * W * 2, 64), st, true, 1, nullptr, nullptr, xpf));
+        xp = xpf;
+    }
+    const float* fu[7] = {y0, a0, d_a0, coef0, bcoef0, w1, b1};
+    return launch_e1_wgrad(W, B, x, nullptr, dw, dbias, sc, st, bf16, fu, xp);
 }
 
 // bf16 mode: o3 / d_o3 in bf16, the Tanh backward applied while the kernel stages (`dout` is not written and may be null)
@@ -1410,12 +1450,14 @@ int32_t cvae_op_conv_tiles_per_partial(cvae_handle h, int32_t layer, int32_t B) 
     return conv_route(h->cfg.precision, layer, h->cfg.width, false, B).tilesPerPartial;
 }
 
-// (tiles, splits, tiles per split) of cvae_op_conv_wgrad's kernel on a bf16 handle, from the launchers' own split arithmetic (no launch)
+// (tiles, splits, tiles per split) of cvae_op_conv_wgrad's kernel on a bf16 handle (layer 0: cvae_op_e1_wgrad_fused's), from the launchers'
+// own split arithmetic (no launch)
 int cvae_op_conv_wgrad_plan(cvae_handle h, int32_t layer, int32_t B, int32_t* out) {
     if (!h || !out || B < 1) { cvae_set_error("cvae_op_conv_wgrad_plan: null handle or output, or batch %d below 1", B); return CVAE_EINVAL; }
-    if (h->cfg.precision != 1 || layer < 1 || layer > 7) { cvae_set_error("cvae_op_conv_wgrad_plan: layer %d on this handle does not run a bf16 weight-gradient kernel (bf16 handles, layers 1..7)", layer); return CVAE_EUNSUPPORTED; }
+    if (h->cfg.precision != 1 || layer < 0 || layer > 7) { cvae_set_error("cvae_op_conv_wgrad_plan: layer %d on this handle does not run a bf16 weight-gradient kernel (bf16 handles, layers 0..7)", layer); return CVAE_EUNSUPPORTED; }
     int plan[3] = {0, 0, 0};
-    RC(layer >= 5 ? conv_up_wgrad_bf16_plan(layer, h->cfg.width, B, plan) : conv_wgrad_bf16_plan(layer, h->cfg.width, B, plan));
+    RC(layer == 0  ? e1_wgrad_plan_bf16(h->cfg.width, B, plan)
+       : layer >= 5 ? conv_up_wgrad_bf16_plan(layer, h->cfg.width, B, plan) : conv_wgrad_bf16_plan(layer, h->cfg.width, B, plan));
     for (int i = 0; i < 3; ++i) out[i] = plan[i];
     return CVAE_OK;
 }

@@ -301,6 +301,7 @@ int conv_up_wgrad_bf16_plan(int layer, int width, int B, int plan[3]);    // lay
 int conv_wgrad_plan_f32(int layer, int width, int B, int plan[3]);
 int conv_up_wgrad_plan_f32(int layer, int width, int B, int cus, int plan[3]);
 int thin_wgrad_plan_f32(int layer, int width, int B, int plan[3]);
+int e1_wgrad_plan_bf16(int width, int B, int plan[3]);                                        // E1's bf16 weight-gradient launch (asks the device's compute-unit count)
 // bn.hip
 int bn_num_tiles(int layer, int width, int B);
 int launch_bn_fwd_finalize(int layer, int width, int B, const float* bnpart, const float* gamma,

@@ -830,6 +830,14 @@ int thin_wgrad_plan_f32(int layer, int width, int B, int plan[3]) {
     return 0;
 }
 
+// the same of the bf16 E1 weight-gradient launch (E1W_OCC splits per compute unit of the current device)
+int e1_wgrad_plan_bf16(int width, int B, int plan[3]) {
+    if (width != 64 && width != 128) { cvae_set_error("e1_wgrad_plan_bf16: width %d unsupported", width); return -2; }
+    plan[0] = B * (width / 4) * (width / 32);
+    plan[1] = e1_splits(width, B, &plan[2], true);
+    return 0;
+}
+
 int launch_e1_wgrad(int width, int B, const float* x, const float* dy, float* dw, float* dbias, float* ws, hipStream_t st, bool bf16,
                     const float* const* fuse, const float* xp) {
     if (width != 64 && width != 128) { cvae_set_error("e1_wgrad: width %d unsupported", width); return -2; }

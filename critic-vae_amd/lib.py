@@ -249,6 +249,7 @@ _SIGS = {
     "cvae_op_conv_dgrad": (C.c_int, [_p, _i32, _i32] + [_p] * 6),
     "cvae_op_conv_wgrad": (C.c_int, [_p, _i32, _i32] + [_p] * 6),
     "cvae_op_d4_bwd": (C.c_int, [_p, _i32] + [_p] * 10),
+    "cvae_op_e1_wgrad_fused": (C.c_int, [_p, _i32] + [_p] * 11 + [_i32, _p]),
     "cvae_op_bn_pool_act_fwd": (C.c_int, [_p, _i32, _i32] + [_p] * 9 + [_i32, _p]),
     "cvae_op_bn_pool_act_bwd": (C.c_int, [_p, _i32, _i32] + [_p] * 11),
     "cvae_op_conv_tiles_per_partial": (_i32, [_p, _i32, _i32]),
@@ -947,6 +948,12 @@ class Handle:
         self._check(self.lib.cvae_op_conv_wgrad(self.h, layer, B, _ptr(inp), _ptr(dout), _ptr(dw), _ptr(dbias),
                                                 _ptr(scratch), _stream()))
 
+    def op_e1_wgrad_fused(self, B, x, y0, a0, d_a0, coef0, bcoef0, w1, b1, dw, dbias, scratch, flags=0):
+        """E1's weight gradient as the step runs it (block 0's BatchNorm / pool / ReLU backward applied while staging); flags bit 0
+        (bf16 handles): stage the packed bf16 frame, which the entry writes into scratch first."""
+        self._check(self.lib.cvae_op_e1_wgrad_fused(self.h, B, _ptr(x), _ptr(y0), _ptr(a0), _ptr(d_a0), _ptr(coef0), _ptr(bcoef0),
+                                                    _ptr(w1), _ptr(b1), _ptr(dw), _ptr(dbias), _ptr(scratch), int(flags), _stream()))
+
     def op_d4_bwd(self, B, o3, d_recon, recon, w, dout, d_o3, dw, db, scratch):
         self._check(self.lib.cvae_op_d4_bwd(self.h, B, _ptr(o3), _ptr(d_recon), _ptr(recon), _ptr(w), _ptr(dout),
                                             _ptr(d_o3), _ptr(dw), _ptr(db), _ptr(scratch), _stream()))
@@ -968,7 +975,8 @@ class Handle:
         return n
 
     def op_conv_wgrad_plan(self, layer, B):
-        """(tiles, splits, tiles per split) of op_conv_wgrad's kernel on a bf16 handle, from the launchers (no launch)."""
+        """(tiles, splits, tiles per split) of op_conv_wgrad's kernel (layer 0: op_e1_wgrad_fused's) on a bf16 handle, from the launchers
+        (no launch)."""
         out = (C.c_int32 * 3)()
         self._check(self.lib.cvae_op_conv_wgrad_plan(self.h, layer, B, out))
         return tuple(out)

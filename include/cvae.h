@@ -967,7 +967,7 @@ int cvae_probe_read(cvae_handle h, int32_t id, float* ms_host, int32_t cap);
  * forms (the Tanh backward is applied inside: `dout` is not written and may be null);
  * cvae_op_conv_wgrad of layers 1..7 runs the bf16 weight-gradient kernels.  Layer 0's weight
  * gradient stays the fp32 kernel on fp32 tensors: its bf16 form exists only fused with block 0's
- * BatchNorm backward.
+ * BatchNorm backward (cvae_op_e1_wgrad_fused, which runs the step's fused form on every handle).
  * The three cvae_op_conv_* entry points check their arguments before any device access and return
  * CVAE_EINVAL, with cvae_last_error() naming the argument, for a null handle, a layer outside the
  * entry's range (forward 0..8, input gradient 1..7, weight gradient 0..7), a batch outside
@@ -997,6 +997,22 @@ int cvae_op_conv_wgrad(cvae_handle h, int32_t layer, int32_t batch, const float*
 int cvae_op_d4_bwd(cvae_handle h, int32_t batch, const float* o3, const float* d_recon,
                    const float* recon, const float* w, float* dout, float* d_o3, float* dw,
                    float* db, void* scratch, void* stream);
+/* E1's weight (+ optional bias) gradient in the form the training step runs: the kernel applies block 0's BatchNorm / MaxPool / ReLU
+ * backward while it stages a tile, dy[p] = scale * ((p == argmax ? g : 0) - k1 - xhat[p] * k2) with g = d_a0 * [a0 > 0] and the argmax
+ * the first maximum of fma(y, scale, shift) in scan order (0,0) (0,1) (1,0) (1,1), and no dy tensor exists.  The same launcher call as
+ * the step's: precision 0, 2 and 3 run the fp32 kernel, precision 1 the bf16 kernel, which also recomputes y from x, w1 and b1.
+ * x: the fp32 NCHW frame; y0, a0, d_a0: NHWC in the handle's storage type; coef0: 128 floats, (scale, shift, mean, invstd) per channel;
+ * bcoef0: 64 floats, (k1, k2) per channel; w1 [75][32] and b1: E1's parameters.  On a bf16 handle y0 is never read and may be null;
+ * on the other handles w1 and b1 are never read and may be null.  dbias may be null; dbias == dw + 2432 (the flat gradient buffer's
+ * layout) takes the step's single column reduction, which leaves the 32 floats between the two alone.
+ * flags: bit 0, bf16 handles only: the kernel stages its strips from the packed bf16 frame, as after a train-mode forward; the entry
+ * first runs the forward's statistics pass, which writes that frame, into `scratch`.  CVAE_EINVAL at a batch where
+ * cvae_conv_route(1, width, 0, 0, batch) is not 1.  `scratch`: cvae_op_scratch_floats().
+ * Checked before any launch, CVAE_EINVAL with cvae_last_error() naming the argument: a null handle, a batch outside [1, max_batch], a
+ * null required pointer, unknown flag bits, flag bit 0 on a handle that is not bf16. */
+int cvae_op_e1_wgrad_fused(cvae_handle h, int32_t batch, const float* x, const float* y0, const float* a0, const float* d_a0,
+                           const float* coef0, const float* bcoef0, const float* w1, const float* b1,
+                           float* dw, float* dbias, void* scratch, int32_t flags, void* stream);
 /* BatchNorm2d(train) -> MaxPool2d(2) -> ReLU/Tanh of encoder block `layer` (0..3) */
 int cvae_op_bn_pool_act_fwd(cvae_handle h, int32_t layer, int32_t batch, const float* y,
                             const float* bn_partials, const float* gamma, const float* beta,
@@ -1006,9 +1022,9 @@ int cvae_op_bn_pool_act_fwd(cvae_handle h, int32_t layer, int32_t batch, const f
  * handle at this batch (conv_route: 4 or 8 for the big-tile bf16 kernels, 1 otherwise).  cvae_op_bn_pool_act_fwd
  * expects one tile per row; rows of more tiles go through cvae_op_bn_fwd_finalize. */
 int32_t cvae_op_conv_tiles_per_partial(cvae_handle h, int32_t layer, int32_t batch);
-/* Host logic only (layers 5..7 ask the device's compute-unit count): out[0..2] = (tiles, splits, tiles per split) of the kernel that
- * cvae_op_conv_wgrad(layer 1..7) launches on a bf16 handle at this batch, from the launchers' own split arithmetic.
- * CVAE_EUNSUPPORTED on other handles and layers. */
+/* Host logic only (layers 0 and 5..7 ask the device's compute-unit count): out[0..2] = (tiles, splits, tiles per split) of the kernel
+ * that cvae_op_conv_wgrad(layer 1..7) or cvae_op_e1_wgrad_fused (layer 0: strips of 4 x 32 pixels) launches on a bf16 handle at this
+ * batch, from the launchers' own split arithmetic.  CVAE_EUNSUPPORTED on other handles and layers. */
 int cvae_op_conv_wgrad_plan(cvae_handle h, int32_t layer, int32_t batch, int32_t* out);
 /* Host logic only (no handle, no device access): out[0..2] = (tiles, splits, tiles per split) of the fp32 kernel that
  * cvae_op_conv_wgrad(layer 0..7) and cvae_op_d4_bwd (layer 8) launch on a precision 0 handle of this width at this batch, on a

@@ -955,6 +955,34 @@ def _op_d4(H):
     return Built(lambda: h.op_d4_bwd(B, o3, d_recon, recon, w, o["dout"], o["d_o3"], o["dw"], o["db"], scratch), _named(**o), [scratch])
 
 
+@scenario("op-e1-wgrad-fused", "ops", ("cvae_op_e1_wgrad_fused",))
+def _op_e1_fused(H):
+    """The step's fused E1 weight gradient on the operands a step left: the fp32 kernel (its y0 from the workspace), the bf16 kernel
+    (no y0) from the fp32 frame and, with flag bit 0, from the packed frame that the entry's statistics pass writes into scratch."""
+    jobs, outs, scr = [], [], []
+    for p in ("f32", "bf16"):
+        r = _stepped_rig(H, p)
+        h, B, W = r.h, r.B, r.W
+        per = 2 if p == "bf16" else 1
+        n_pool = B * (W // 2) ** 2 * 32 // per
+        y0 = h.ws_view(r.ws, B, "y0", B * W * W * 32).clone() if p == "f32" else None
+        a0, d_a0 = h.ws_view(r.ws, B, "a0", n_pool).clone(), h.ws_view(r.ws, B, "d_a0", n_pool).clone()
+        coef0, bcoef0 = h.ws_view(r.ws, B, "coef0", 128).clone(), _randn(930, 64, scale=0.01)
+        (ow, nw), (ob, nb) = h.layout["enc0.w"], h.layout["enc0.b"]
+        w1, b1 = r.theta[ow:ow + nw].clone(), r.theta[ob:ob + nb].clone()
+        scratch = _empty(h.op_scratch_floats(B))
+        scr.append(scratch)
+        for flags in ((0,) if p == "f32" else (0, 1)):
+            o = dict(dw=_empty(nw), db=_empty(nb))
+            jobs.append((h, B, r.x.clone(), y0, a0, d_a0, coef0, bcoef0, w1, b1, o, scratch, flags))
+            outs += [(f"{p}.f{flags}.{k}", t) for k, t in o.items()]
+
+    def fn():
+        for h, B, x, y0, a0, d_a0, coef0, bcoef0, w1, b1, o, scratch, flags in jobs:
+            h.op_e1_wgrad_fused(B, x, y0, a0, d_a0, coef0, bcoef0, w1, b1, o["dw"], o["db"], scratch, flags)
+    return Built(fn, outs, scr)
+
+
 @scenario("op-bn", "ops", ("cvae_op_bn_pool_act_fwd", "cvae_op_bn_fwd_finalize", "cvae_op_bn_pool_act_bwd"))
 def _op_bn(H):
     import torch

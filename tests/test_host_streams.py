@@ -10,7 +10,7 @@ def test_header_parse_finds_the_stream_entries():
     names = ST.header_stream_entries()
     with open(ST.HEADER) as f:
         text = f.read()
-    assert len(names) == len(re.findall(r"void\*\s*stream\)", text)) == 58
+    assert len(names) == len(re.findall(r"void\*\s*stream\)", text)) == 59
     for known in ("cvae_forward", "cvae_decode", "cvae_crf_grid", "cvae_tensor_stats", "cvae_op_msssim", "cvae_op_fc_bwd", "cvae_guard_init"):
         assert known in names
     for host_only in ("cvae_create", "cvae_ws_offset", "cvae_probe_config", "cvae_op_latent_plan", "cvae_grad_bucket", "cvae_sync_slot"):
