@@ -1274,6 +1274,40 @@ int cvae_mask_counts(cvae_handle h, int32_t B, const uint8_t* mask, const uint8_
     return launch_mask_counts(h->cfg.width, B, mask, gt, counts, (hipStream_t)stream);
 }
 
+// ---- objects from masks (components.hip) ----
+int cvae_mask_objects(cvae_handle h, int32_t B, const uint8_t* mask, const uint8_t* values, const cvae_object_params* p,
+                      uint8_t* mask_out, uint16_t* labels, int32_t* info, int32_t* table, void* stream, uint32_t flags) {
+    const char* who = "cvae_mask_objects";
+    if (!seg_batch_ok(h, B, who)) return CVAE_EINVAL;
+    if (!mask || !p || !info) { cvae_set_error("%s: null mask, params or info", who); return CVAE_EINVAL; }
+    if (flags != 0) { cvae_set_error("%s: flags = %u must be 0", who, (unsigned)flags); return CVAE_EINVAL; }
+    if (p->connectivity != 4 && p->connectivity != 8) { cvae_set_error("%s: connectivity %d must be 4 or 8", who, p->connectivity); return CVAE_EINVAL; }
+    if (p->fill_holes != 0 && p->fill_holes != 1) { cvae_set_error("%s: fill_holes %d must be 0 or 1", who, p->fill_holes); return CVAE_EINVAL; }
+    if (p->min_area < 1) { cvae_set_error("%s: min_area %d must be >= 1", who, p->min_area); return CVAE_EINVAL; }
+    if (p->keep_largest < 0) { cvae_set_error("%s: keep_largest %d must be >= 0", who, p->keep_largest); return CVAE_EINVAL; }
+    if (p->max_objects < 1 || p->max_objects > CVAE_OBJECTS_MAX) {
+        cvae_set_error("%s: max_objects %d outside [1, %d]", who, p->max_objects, CVAE_OBJECTS_MAX); return CVAE_EINVAL;
+    }
+    if (((uintptr_t)mask | (uintptr_t)values | (uintptr_t)mask_out | (uintptr_t)labels) & 15) {
+        cvae_set_error("%s: mask, values, mask_out and labels must be 16-byte aligned", who); return CVAE_EINVAL;
+    }
+    if (((uintptr_t)info | (uintptr_t)table) & 3) { cvae_set_error("%s: info and table must be 4-byte aligned", who); return CVAE_EINVAL; }
+    return launch_mask_objects(h->cfg.width, B, mask, values, p->connectivity == 8, p->fill_holes, p->min_area, p->keep_largest,
+                               p->max_objects, mask_out, labels, info, table, (hipStream_t)stream);
+}
+
+int cvae_object_overlap(cvae_handle h, int32_t B, const uint16_t* labels_a, const uint16_t* labels_b, int32_t M, int32_t* inter,
+                        void* stream, uint32_t flags) {
+    const char* who = "cvae_object_overlap";
+    if (!seg_batch_ok(h, B, who)) return CVAE_EINVAL;
+    if (!labels_a || !labels_b || !inter) { cvae_set_error("%s: null labels_a, labels_b or inter", who); return CVAE_EINVAL; }
+    if (flags != 0) { cvae_set_error("%s: flags = %u must be 0", who, (unsigned)flags); return CVAE_EINVAL; }
+    if (M < 1 || M > CVAE_OBJECTS_MAX) { cvae_set_error("%s: max_objects %d outside [1, %d]", who, M, CVAE_OBJECTS_MAX); return CVAE_EINVAL; }
+    if (((uintptr_t)labels_a | (uintptr_t)labels_b) & 15) { cvae_set_error("%s: labels_a and labels_b must be 16-byte aligned", who); return CVAE_EINVAL; }
+    if ((uintptr_t)inter & 3) { cvae_set_error("%s: inter must be 4-byte aligned", who); return CVAE_EINVAL; }
+    return launch_object_overlap(h->cfg.width, B, labels_a, labels_b, M, inter, (hipStream_t)stream);
+}
+
 // ---- the reference's pictures (get_final_frame / get_injected_img, vae_utility.py:240-322; kernel in render.hip) ----
 int cvae_compose_frames(cvae_handle h, int32_t B, int32_t n_panels, const cvae_panel* panels, int32_t row_offset, int32_t flags,
                         const uint8_t* overlay, const uint8_t* atlas, int32_t n_labels, int32_t label_h, int32_t label_w,

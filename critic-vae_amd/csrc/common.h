@@ -436,6 +436,10 @@ int launch_dense_crf(int width, int B, const uint8_t* frames, const float* prob1
 int launch_diff_normalize(int width, int B, const float* diff, double mean_max, double factor, int thr, const uint8_t* gt,
                           uint8_t* u8, uint8_t* mask, int64_t* counts, int64_t* hist, hipStream_t st);
 int launch_mask_counts(int width, int B, const uint8_t* mask, const uint8_t* gt, int64_t* counts, hipStream_t st);
+// components.hip: objects from masks; arguments already checked by the caller
+int launch_mask_objects(int width, int B, const uint8_t* mask, const uint8_t* values, int conn8, int fill, int min_area, int keep, int M,
+                        uint8_t* mask_out, uint16_t* labels, int32_t* info, int32_t* table, hipStream_t st);
+int launch_object_overlap(int width, int B, const uint16_t* la, const uint16_t* lb, int M, int32_t* inter, hipStream_t st);
 // crf_grid.hip
 int crf_grid_group();
 int64_t crf_grid_scratch_bytes(int width, int B, int K);

@@ -39,7 +39,14 @@ class CrfVariant(C.Structure):
     _fields_ = [("thr", C.c_int32), ("p_floor", C.c_float), ("w1", C.c_float), ("w2", C.c_float)]
 
 
-CRF_GRID_MAX_VARIANTS, CRF_GRID_MAX_SNAPS = 64, 8       # CVAE_CRF_GRID_MAX_VARIANTS, CVAE_CRF_GRID_MAX_SNAPS
+class ObjectParams(C.Structure):
+    """cvae_object_params (include/cvae.h): connectivity, hole fill, area filter, keep-largest and table rows of cvae_mask_objects."""
+    _fields_ = [("connectivity", C.c_int32), ("fill_holes", C.c_int32), ("min_area", C.c_int32), ("keep_largest", C.c_int32),
+                ("max_objects", C.c_int32)]
+
+
+OBJECTS_MAX = 64          # CVAE_OBJECTS_MAX
+CRF_GRID_MAX_VARIANTS, CRF_GRID_MAX_SNAPS = 64, 8      # CVAE_CRF_GRID_MAX_VARIANTS, CVAE_CRF_GRID_MAX_SNAPS
 
 
 class GuardRecord(C.Structure):
@@ -232,6 +239,8 @@ _SIGS = {
     "cvae_gather_f32_aug": (C.c_int, [_p, _i32, _i32, _p, _p, _i64, _p, C.POINTER(AugmentParams), _p, _p, _p, _p]),
     "cvae_diff_normalize": (C.c_int, [_p, _i32, _p, C.c_double, C.c_double, _i32] + [_p] * 6),
     "cvae_mask_counts": (C.c_int, [_p, _i32, _p, _p, _p, _p]),
+    "cvae_mask_objects": (C.c_int, [_p, _i32, _p, _p, C.POINTER(ObjectParams), _p, _p, _p, _p, _p, C.c_uint32]),
+    "cvae_object_overlap": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _p, C.c_uint32]),
     "cvae_crf_scratch_bytes": (_i64, [_p, _i32]),
     "cvae_dense_crf": (C.c_int, [_p, _i32, _p, _p, C.POINTER(CrfParams), _p, _p, _p, _p]),
     "cvae_crf_grid_group": (_i32, [_p]),
@@ -283,7 +292,8 @@ def load():
     return lib
 
 
-_DTYPE_NAMES = {torch.float32: "fp32", torch.float64: "fp64", torch.uint8: "uint8", torch.int64: "int64", torch.int32: "int32"}
+_DTYPE_NAMES = {torch.float32: "fp32", torch.float64: "fp64", torch.uint8: "uint8", torch.int64: "int64", torch.int32: "int32",
+                torch.uint16: "uint16"}
 
 
 def _dev_ptr(t, dtype, what):
@@ -839,6 +849,22 @@ class Handle:
     def mask_counts(self, B, mask, gt, counts):
         self._check(self.lib.cvae_mask_counts(self.h, B, self._u8(mask, "mask"), self._u8(gt, "gt"),
                                               self._i64(counts, "counts"), _stream()))
+
+    # ---- objects from masks (include/cvae.h; objects.py) ----
+    _u16 = staticmethod(lambda t, what: _dev_ptr(t, torch.uint16, what))
+
+    def mask_objects(self, B, mask, params, info, values=None, mask_out=None, labels=None, table=None, flags=0):
+        """cvae_mask_objects: params an ObjectParams or None (a null pointer); info (B,4) int32; mask_out (B,W,W) uint8, labels
+        (B,W,W) uint16 and table (B,M,8) int32 or None."""
+        self._check(self.lib.cvae_mask_objects(self.h, B, self._u8(mask, "mask"), self._u8(values, "values"),
+                                               None if params is None else C.byref(params), self._u8(mask_out, "mask_out"),
+                                               self._u16(labels, "labels"), self._i32(info, "info"), self._i32(table, "table"),
+                                               _stream(), int(flags)))
+
+    def object_overlap(self, B, labels_a, labels_b, M, inter, flags=0):
+        """cvae_object_overlap: inter (B,M,M) int32 = pixels with labels_a == i + 1 and labels_b == j + 1."""
+        self._check(self.lib.cvae_object_overlap(self.h, B, self._u16(labels_a, "labels_a"), self._u16(labels_b, "labels_b"), int(M),
+                                                 self._i32(inter, "inter"), _stream(), int(flags)))
 
     def crf_scratch_bytes(self, B):
         n = self.lib.cvae_crf_scratch_bytes(self.h, B)

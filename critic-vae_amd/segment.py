@@ -14,6 +14,8 @@ unary_from_softmax helper); whether SimpleCRF clamps a 0/1 mask the same way has
 
     python -m critic_vae_amd.segment -video [-thresh] --frames X.npy --gt Y.npy --networks DIR [--critic CKPT]
                                      [--out DIR [--gif] [--no-text]] [--thr T] [--crf W1,ALPHA,BETA,W2,GAMMA,IT] [--p-floor F]
+                                     [--objects [--connectivity 4|8] [--fill-holes] [--min-area A] [--keep-largest K]
+                                      [--max-objects M] [--objects-out FILE.npz]]
     python -m critic_vae_amd.segment -video -search [--grid-thr 0,10,...] [--grid-w1 ...] ... [--skip N] [--top N]
 
 `-search` is the grid search the reference's crf() is written as (lists for every parameter, the IoU per tuple): every
@@ -22,6 +24,10 @@ threshold and every (w1, w2, p_floor) of one (alpha, beta, gamma) ride on one pa
 `--mask-source critic-grad | critic-ig | critic-occlusion` builds the masks from the critic alone (critic_maps: the
 gradient of its logit with respect to the pixels, integrated gradients, occlusion sensitivity) and sends them through the
 same tail (eval_maps / sweep_maps): the baselines that show what the VAE adds.  No pictures for these sources.
+
+`--objects` reports the thresholded and the CRF mask as objects as well (critic_vae_amd.objects: connected components after an
+optional hole fill and area filter, matched with the ground truth's components at IoU > 0.5): precision, recall and panoptic
+quality per mask kind, for every mask source.
 """
 import argparse
 import os
@@ -391,11 +397,39 @@ def critic_maps(frames_u8, critic, source="grad", steps=IG_STEPS, patch=OCCLUSIO
     return out_p, maps, maxv
 
 
-def eval_maps(frames_u8, maps, max_values, preds, gt, t=THRESHOLD, crf_params=CRF_REF, p_floor=P_FLOOR):
+def object_eval(mask, gt, filt, values=None, gt_objects=None):
+    """One mask kind as objects (objects.py): `mask` (B,W,W) through cvae_mask_objects under the ObjectFilter `filt` (sum_value
+    over `values`), the ground truth labelled with the same connectivity and no filter (or `gt_objects`, that result, to share
+    it), the overlap matrix, the matches at IoU > 0.5.  Returns {"iou": the filtered mask's pixel IoU (mask_counts), "pq", "sq",
+    "rq", "precision", "recall", "tp", "fp", "fn", "truncated_frames", and on the device "mask", "labels", "info", "table",
+    "gt_info", "gt_table"}."""
+    from . import objects as ob
+    gt_d = _cuda(gt, torch.uint8)
+    if gt_objects is None:
+        gt_objects = ob.mask_objects(gt_d, ob.ObjectFilter(connectivity=filt.connectivity, max_objects=filt.max_objects), labels=True)
+    o = ob.mask_objects(mask, filt, values=values, labels=True)
+    inter = ob.object_overlap(o["labels"], gt_objects["labels"], filt.max_objects)
+    c = mask_counts(o["mask"], gt_d).sum(0)
+    ta, ia, tb, ib, it, c = ob._host(o["table"], o["info"], gt_objects["table"], gt_objects["info"], inter, c)     # the one read
+    r = ob.panoptic(ob.match(ta, ia[:, ob.INFO_KEPT], tb, ib[:, ob.INFO_KEPT], it))
+    r["iou"] = iou_from_counts(*c.tolist())
+    r.update(mask=o["mask"], labels=o["labels"], info=o["info"], table=o["table"], gt_info=gt_objects["info"],
+             gt_table=gt_objects["table"])
+    return r
+
+
+def _objects_entry(thr, crf, gt_d, u8, filt):
+    from . import objects as ob
+    gto = ob.mask_objects(gt_d, ob.ObjectFilter(connectivity=filt.connectivity, max_objects=filt.max_objects), labels=True)
+    return {"thr": object_eval(thr, gt_d, filt, u8, gto), "crf": object_eval(crf, gt_d, filt, u8, gto)}
+
+
+def eval_maps(frames_u8, maps, max_values, preds, gt, t=THRESHOLD, crf_params=CRF_REF, p_floor=P_FLOOR, objects=None):
     """The tail of eval_frames for any non-negative per-pixel map (B,W,W) with its per-frame maxima: normalisation by the
     set-wide mean of the maxima, threshold, histograms, thr_iou, CRF, crf_iou, bins.  Returns eval_frames' dict (its "diff"
     is `maps`), and under "device" the tensors left on the device (frames, gt, preds, diff_u8, thr_masks, crf_masks; the
-    masks as uint8 0/1)."""
+    masks as uint8 0/1).  objects: an objects.ObjectFilter adds one key, "objects": {"thr", "crf"}, each object_eval's dict of
+    the thresholded and of the CRF mask (sum_value over diff_u8); None returns and launches exactly what it did without."""
     frames = _cuda(frames_u8, torch.uint8)
     diff = _cuda(maps, torch.float32)
     maxv = _cuda(max_values, torch.float32).reshape(-1)
@@ -407,9 +441,12 @@ def eval_maps(frames_u8, maps, max_values, preds, gt, t=THRESHOLD, crf_params=CR
     crf, crf_iou = _crf_counts(frames, m, gt_d, crf_params, p_floor)
     thr_np = _np(m).astype(bool)
     preds_np = _np(p)
-    return {"preds": preds_np, "diff": _np(diff), "max_values": _np(maxv), "diff_u8": _np(u8), "thr_masks": thr_np, "crf_masks": _np(crf),
-            "thr_iou": thr_iou, "crf_iou": crf_iou, "bins": bin_info(preds_np, gt, thr_np), "mean_max": mean_max, "hist": _np(hist),
-            "device": {"frames": frames, "gt": gt_d, "preds": p, "diff_u8": u8, "thr_masks": m, "crf_masks": crf.to(torch.uint8)}}
+    r = {"preds": preds_np, "diff": _np(diff), "max_values": _np(maxv), "diff_u8": _np(u8), "thr_masks": thr_np, "crf_masks": _np(crf),
+         "thr_iou": thr_iou, "crf_iou": crf_iou, "bins": bin_info(preds_np, gt, thr_np), "mean_max": mean_max, "hist": _np(hist),
+         "device": {"frames": frames, "gt": gt_d, "preds": p, "diff_u8": u8, "thr_masks": m, "crf_masks": crf.to(torch.uint8)}}
+    if objects is not None:
+        r["objects"] = _objects_entry(m, r["device"]["crf_masks"], gt_d, u8, objects)
+    return r
 
 
 def sweep_maps(frames_u8, maps, max_values, gt, thresholds=SWEEP, crf_params=CRF_REF, p_floor=P_FLOOR):
@@ -431,16 +468,16 @@ def sweep_maps(frames_u8, maps, max_values, gt, thresholds=SWEEP, crf_params=CRF
 
 
 def eval_frames(frames_u8, vae, gt, critic=None, preds=None, t=THRESHOLD, crf_params=CRF_REF, chunk=None,
-                p_floor=P_FLOOR, keep_device=False):
+                p_floor=P_FLOOR, keep_device=False, objects=None):
     """eval_textured_frames (vae_utility.py:162-212) without the PIL frames.  frames_u8 (B,W,W,3) uint8, gt (B,W,W)
     bool; either a critic (64x64 only, as the reference's) or explicit preds (B,).  The VAE runs in eval mode in
     chunks of at most vae.max_batch; normalisation, threshold, CRF and IoU run over the whole set at once (eval_maps).
     Returns a dict: preds, diff (fp32), max_values, diff_u8, thr_masks, crf_masks (host arrays), thr_iou, crf_iou,
     bins, mean_max, hist (the (2,256) histograms of diff_u8).  keep_device=True adds "device": what render.video_frames
     composes the pictures from, left on the device (frames, gt, preds, recon_one, recon_zero, diff_u8, thr_masks, crf_masks;
-    the masks as uint8 0/1)."""
+    the masks as uint8 0/1).  objects: an objects.ObjectFilter adds the key "objects", as eval_maps does."""
     p, diff, maxv, *recons = _infer(frames_u8, vae, critic, preds, chunk, keep_recons=keep_device)
-    r = eval_maps(frames_u8, diff, maxv, p, gt, t, crf_params, p_floor)
+    r = eval_maps(frames_u8, diff, maxv, p, gt, t, crf_params, p_floor, objects=objects)
     dev = r.pop("device")
     if keep_device:
         r["device"] = dict(dev, recon_one=recons[0], recon_zero=recons[1])
@@ -500,6 +537,15 @@ def parse_args(argv=None):
     for name, ref in zip(("w1", "alpha", "beta", "w2", "gamma", "it"), CRF_REF):
         ap.add_argument(f"--grid-{name}", default=str(ref), help=f"-search: {name} values, a comma list")
     ap.add_argument("--grid-p-floor", default=str(P_FLOOR), help="-search: unary floors, a comma list")
+    ap.add_argument("--objects", action="store_true", help="also report both masks as objects: connected components after an "
+                    "optional hole fill and area filter, matched with the ground truth's at IoU > 0.5 (precision, recall, PQ = SQ * RQ)")
+    ap.add_argument("--connectivity", type=int, default=8, choices=(4, 8), help="--objects: connectivity of the set pixels")
+    ap.add_argument("--fill-holes", action="store_true", help="--objects: set every clear region that does not reach the frame border")
+    ap.add_argument("--min-area", type=int, default=1, help="--objects: drop components of fewer pixels")
+    ap.add_argument("--keep-largest", type=int, default=0, help="--objects: keep the K largest components per frame (0: all)")
+    ap.add_argument("--max-objects", type=int, default=32, help="--objects: table rows per frame (1..64)")
+    ap.add_argument("--objects-out", default=None, metavar="FILE.npz", help="--objects: write info, tables and centroids of both "
+                    "masks and of the ground truth")
     args = ap.parse_args(argv)
 
     def numbers(text, kind, flag):
@@ -546,7 +592,48 @@ def parse_args(argv=None):
         ap.error("--ig-steps must be in 2..256")
     if args.critic is None:
         args.critic = os.path.join(args.networks, CRITIC_FILE)
+    args.object_filter = None
+    if args.objects:
+        if args.search or args.thresh:
+            ap.error("--objects reports the single evaluation: not with -search or -thresh")
+        from .objects import ObjectFilter
+        try:
+            args.object_filter = ObjectFilter(args.connectivity, args.fill_holes, args.min_area, args.keep_largest, args.max_objects)
+        except ValueError as e:
+            ap.error(f"--objects: {e}")
+    elif (args.objects_out is not None or args.fill_holes or args.connectivity != 8 or args.min_area != 1 or args.keep_largest != 0
+          or args.max_objects != 32):
+        ap.error("--connectivity, --fill-holes, --min-area, --keep-largest, --max-objects and --objects-out need --objects")
     return args
+
+
+def print_objects(entry):
+    """One line per mask kind of an "objects" entry."""
+    for kind in ("thr", "crf"):
+        o = entry[kind]
+        print(f"objects {kind}: iou={o['iou']}, pq={o['pq']:.3f}, sq={o['sq']:.3f}, rq={o['rq']:.3f}, precision={o['precision']:.3f}, "
+              f"recall={o['recall']:.3f}, tp={o['tp']}, fp={o['fp']}, fn={o['fn']}, truncated_frames={o['truncated_frames']}")
+
+
+def save_objects(path, entry):
+    """FILE.npz of --objects-out: per mask kind (thr, crf) and for the ground truth (gt) the info, the table and the centroids."""
+    from .objects import centroids
+    out = {}
+    for kind in ("thr", "crf"):
+        o = entry[kind]
+        out[f"{kind}_info"], out[f"{kind}_table"] = _np(o["info"]), _np(o["table"])
+        out[f"{kind}_centroids"] = centroids(out[f"{kind}_table"])
+    out["gt_info"], out["gt_table"] = _np(entry["thr"]["gt_info"]), _np(entry["thr"]["gt_table"])
+    out["gt_centroids"] = centroids(out["gt_table"])
+    with open(path, "wb") as f:
+        np.savez(f, **out)
+
+
+def _report_objects(args, r):
+    if args.object_filter is not None:
+        print_objects(r["objects"])
+        if args.objects_out is not None:
+            save_objects(args.objects_out, r["objects"])
 
 
 def print_search(rows, top):
@@ -574,9 +661,10 @@ def main(argv=None):
             for t, thr_iou, crf_iou in sweep_maps(frames, maps, maxv, gt, crf_params=args.crf, p_floor=args.p_floor):
                 print(f"thr={t}, thr_iou={thr_iou}, crf_iou={crf_iou}")
         else:
-            r = eval_maps(frames, maps, maxv, preds, gt, args.thr, args.crf, args.p_floor)
+            r = eval_maps(frames, maps, maxv, preds, gt, args.thr, args.crf, args.p_floor, objects=args.object_filter)
             print(f"thr_iou={r['thr_iou']}")
             print(f"crf_iou={r['crf_iou']}")
+            _report_objects(args, r)
         return 0
     from .nets import VariationalAutoencoder
     from .train import load_networks
@@ -592,9 +680,10 @@ def main(argv=None):
             print(f"thr={t}, thr_iou={thr_iou}, crf_iou={crf_iou}")
     else:
         r = eval_frames(frames, vae, gt, critic=critic, t=args.thr, crf_params=args.crf, chunk=args.chunk, p_floor=args.p_floor,
-                        keep_device=args.out is not None)
+                        keep_device=args.out is not None, objects=args.object_filter)
         print(f"thr_iou={r['thr_iou']}")
         print(f"crf_iou={r['crf_iou']}")
+        _report_objects(args, r)
         if args.out is not None:
             from . import render
             pictures = render.video_frames(r, text=args.text, threshold=args.thr).cpu().numpy()

@@ -864,6 +864,52 @@ int cvae_crf_grid(cvae_handle h, int32_t batch, const uint8_t* frames_hwc, const
                   const cvae_crf_variant* variants, int32_t n_variants, const int32_t* snaps, int32_t n_snaps,
                   int64_t* counts_or_null, uint8_t* labels_or_null, float* q1_or_null, void* scratch, void* stream);
 
+/* Objects from masks (no reference counterpart: vae_utility.py scores pixels only).  cvae_mask_objects is ONE launch for any
+ * batch, one workgroup per frame at both widths; the frame's mask (B,W,W) uint8, nonzero = set, is read once and everything up
+ * to the output writes stays in LDS.  Per frame, in this order:
+ *   1. fill_holes: every clear region not connected to the frame border becomes set.  Clear pixels connect under the
+ *      COMPLEMENTARY connectivity: 4 when the set pixels use 8, 8 when they use 4 (scipy.ndimage.binary_fill_holes with that
+ *      structure).
+ *   2. the set pixels are labelled under `connectivity` (4 or 8).
+ *   3. components of fewer than min_area pixels are cleared.
+ *   4. keep_largest = k >= 1 keeps the k largest of the rest, ties on area to the component whose first pixel comes earlier in
+ *      raster order; 0 keeps all.
+ *   5. the survivors are labelled 1..kept in raster order of each component's first pixel (scipy.ndimage.label's order).
+ * Outputs, every element written:
+ *   mask_out_or_null (B,W,W) uint8  0 / 1
+ *   labels_or_null   (B,W,W) uint16 0 = background; every kept object is labelled, those past max_objects included
+ *   info             (B,4) int32    [0] components after step 1, [1] components kept, [2] pixels set by the hole fill,
+ *                                   [3] labelling passes used (a diagnostic: 1 .. W*W + 1, not part of the result)
+ *   table_or_null    (B,M,8) int32  M = max_objects; row i is label i + 1: area, x0, y0, x1, y1 (inclusive box), sum x, sum y,
+ *                                   sum value over values_u8_or_null (B,W,W) uint8 (0 without that plane).  Rows at or past
+ *                                   `kept` are zero; kept > M means the table is truncated while labels and counts stay complete.
+ * Labelling is label equivalence on 16-bit labels in LDS: a pass writes the smallest neighbouring label to the label's root
+ * with an atomic minimum and then flattens every chain.  Labels only decrease, a pass that changes nothing ends the loop, and
+ * W*W + 1 passes end it whatever the input.  The final label of a component is a function of the component alone (its minimum
+ * linear index, ranked in raster order among the survivors), and all accumulations are integer atomics: a frame's result is
+ * bitwise independent of the batch and of its slot in it.
+ * CVAE_EINVAL before any device access: null handle, mask, params or info; flags != 0; connectivity not 4 or 8; fill_holes not
+ * 0 or 1; min_area < 1; keep_largest < 0; max_objects outside 1..CVAE_OBJECTS_MAX; batch < 1 or batch * W * W >= 2^31 (batch
+ * is NOT capped by max_batch); mask, values, mask_out or labels not 16-byte aligned.  Nothing allocates or synchronises.
+ * The stream is followed by `flags` for the reason given at cvae_latent_stats.
+ *
+ * cvae_object_overlap: inter (B,M,M) int32 = the number of pixels with labels_a == i + 1 and labels_b == j + 1 (both (B,W,W)
+ * uint16, 16-byte aligned; labels above M are ignored).  One workgroup per frame, the matrix in LDS, integer atomics, one write.
+ * Same argument checks. */
+#define CVAE_OBJECTS_MAX 64
+typedef struct cvae_object_params {
+    int32_t connectivity;    /* 4 or 8: of the set pixels */
+    int32_t fill_holes;      /* 0 or 1 */
+    int32_t min_area;        /* >= 1 */
+    int32_t keep_largest;    /* 0: all; k >= 1: the k largest */
+    int32_t max_objects;     /* M: table rows, 1..CVAE_OBJECTS_MAX */
+} cvae_object_params;
+int cvae_mask_objects(cvae_handle h, int32_t batch, const uint8_t* mask, const uint8_t* values_u8_or_null,
+                      const cvae_object_params* params, uint8_t* mask_out_or_null, uint16_t* labels_or_null, int32_t* info,
+                      int32_t* table_or_null, void* stream, uint32_t flags /* 0 */);
+int cvae_object_overlap(cvae_handle h, int32_t batch, const uint16_t* labels_a, const uint16_t* labels_b, int32_t max_objects,
+                        int32_t* inter, void* stream, uint32_t flags /* 0 */);
+
 /* ---------------------------------------------------------------------------------------- *
  * The reference's pictures: the PNG strips of image_evaluate (vae.py:68-108) and get_injected_img
  * (vae_utility.py:240-254) and the 7-panel video frames of get_final_frame (vae_utility.py:286-322).
